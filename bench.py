@@ -18,7 +18,16 @@ before anything in the parent touches a GPU.
 
 A step = one pass of the path over the rank's cells: raw climatology (ring kernel) + Feb-29 /
 smoothing (finish kernel).  Timing: barrier + device sync, K steps, device sync + barrier, MAX over
-ranks.  One JSON line on rank 0's stdout (see the driver contract):
+ranks.  One JSON line on rank 0's stdout (see the driver contract).
+
+A plain run sets up, warms up, times the K steps and prints the line: metric, value, ms_per_step,
+the roofline of the ring kernel from the HIP events of the timed steps.  `--dump-outputs DIR` then
+also writes what the last timed step computed, as the caller of the path receives it: DIR/thresh.npy
+and DIR/seas.npy, float64 (D, n), for a fixed seeded sample of n cells in ascending cell order (all
+cells when the grid is small; at most 64 MB in all).  The inputs are generated on the device from
+fixed seeds, so two runs with the same arguments see the same series.  Everything else below --
+the live counters, the CPU baseline, the parity checks, the other configurations, the N > 1
+single-rank comparison -- runs only with `--full`:
   roofline      ring kernel: algorithmic bytes (T*4 + 2*D*8 per cell) / average launch time from HIP
                 events recorded on the kernels' stream; `traffic` = HBM bytes per launch measured
                 LIVE: before this process touches the GPU it runs itself three times under
@@ -50,6 +59,9 @@ for _p in (ROOT, os.path.join(ROOT, "oracle")):
 
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 HBM_COPY_GBS = 6290.0   # same table: what a float4 streaming copy measures (79 % of the spec); SURVEY 8(d) asks for both
+DUMP_BYTES = 64_000_000    # --dump-outputs: at most this many bytes of arrays in all
+DUMP_CELLS = 8192          # --dump-outputs: at most this many cells
+DUMP_SEED = 20260101       # --dump-outputs: the seed of the sample of cells
 
 PRESETS = {
     "0.25deg": dict(cells=1440 * 720, years=(1982, 2021), nan=0.0, tstep=False, skipna=False, index=2,
@@ -103,6 +115,11 @@ def parse_args(argv=None):
     ap.add_argument("--ring2", type=int, default=None, help="ring2 variant override (-2 auto, -1 round-1 kernel, 0..11)")
     ap.add_argument("--chunks", type=int, default=0)
     ap.add_argument("--dtype", default="f32", choices=["f32", "f64"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure: live counters, cpu_baseline, parity, other_configs, "
+                         "the N > 1 single-rank comparison (the --no-* options below leave out single legs of it)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write thresh / seas of the last timed step (a fixed seeded sample of cells) as DIR/<name>.npy")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 traffic measurement")
     ap.add_argument("--force-dist", action="store_true", help="build the RCCL communicator and gather even with one rank")
@@ -397,11 +414,11 @@ def run(args):
 
     # ---- everything that forks / spawns happens BEFORE this process touches the GPU -------------
     pool = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         import parallel as opar
         pool = opar.OraclePool(doy, w)
     traffic, traffic_src, sq = None, None, None
-    if rank == 0 and world == 1 and not args.no_pmc and not args.pmc_child:
+    if rank == 0 and world == 1 and args.full and not args.no_pmc and not args.pmc_child:
         child_argv = ["--gpus", "1", "--config", cfg, "--dtype", args.dtype, "--kernel", args.kernel,
                       "--chunks", str(args.chunks), "--cells", str(args.cells)]
         if args.ring2 is not None:
@@ -531,6 +548,59 @@ def run(args):
     ms_per_step = 1e3 * dt / args.steps
     cells_per_step = C_total if (strong or world == 1) else world * C_total
     value = cells_per_step * args.steps / dt
+
+    def gather_cols(buf, itemsize, rows, ld, idx, dtype, base=0):
+        d_idx = DeviceBuffer.from_array(idx.astype(np.int64))
+        d_out = DeviceBuffer(itemsize * rows * idx.size)
+        try:
+            h.gather_cells(buf.ptr + base, itemsize, rows, ld, d_idx.ptr, idx.size, d_out.ptr, idx.size)
+            h.stream_sync(0)
+            return d_out.to_array((rows, idx.size), dtype)
+        finally:
+            d_idx.free()
+            d_out.free()
+
+    def rank0_columns(idx):
+        """columns idx (indices into rank 0's block) of the step's output: (thresh, seas)"""
+        th = np.empty((D, idx.size))
+        se = np.empty((D, idx.size))
+        for i, (a, b) in enumerate(slabs):
+            sel = np.nonzero((idx >= a) & (idx < b))[0]
+            if sel.size:
+                both = gather_cols(out[i], 8, 2 * D, b - a, idx[sel] - a, np.float64)
+                th[:, sel], se[:, sel] = both[:D], both[D:]
+        return th, se
+
+    def gathered_columns(idx):
+        """columns idx (cell indices of the whole step, rank by rank) of what rank 0 received in the step's gathers:
+        (thresh, seas).  recv[i] holds slab i of every rank, rank after rank, each a dense (2D, width) block."""
+        th = np.empty((D, idx.size))
+        se = np.empty((D, idx.size))
+        bounds = slab_bounds(C_total, world) if strong else [(r * C_total, (r + 1) * C_total) for r in range(world)]
+        for r, (a, _) in enumerate(bounds):
+            start = a
+            for i in range(len(slabs)):
+                cr = cols_of_rank[i]
+                width = int(cr[r])
+                sel = np.nonzero((idx >= start) & (idx < start + width))[0]
+                if sel.size:
+                    both = gather_cols(recv[i], 8, 2 * D, width, idx[sel] - start, np.float64, base=2 * D * int(cr[:r].sum()) * 8)
+                    th[:, sel], se[:, sel] = both[:D], both[D:]
+                start += width
+        return th, se
+
+    # ---- what the last timed step computed (rank 0): thresh and seas of a fixed seeded sample of cells ----
+    if rank == 0 and args.dump_outputs:
+        n_dump = min(cells_per_step, DUMP_CELLS, DUMP_BYTES // (2 * D * 8))
+        if n_dump == cells_per_step:
+            d_idx = np.arange(cells_per_step, dtype=np.int64)
+        else:
+            d_idx = np.sort(np.random.default_rng(DUMP_SEED).choice(cells_per_step, n_dump, replace=False)).astype(np.int64)
+        d_th, d_se = gathered_columns(d_idx) if use_dist else rank0_columns(d_idx)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "thresh.npy"), d_th)
+        np.save(os.path.join(args.dump_outputs, "seas.npy"), d_se)
+
     # ---- roofline of the dominant kernel (ring): algorithmic bytes / launch time ----------------
     bytes_per_cell = T * isz + 2 * D * 8
     cells_per_launch = float(np.mean([b - a for a, b in slabs]))
@@ -613,7 +683,7 @@ def run(args):
 
     # ---- N > 1: the SAME workload on rank 0 alone (the N = 1 default line measures configs[2], a clean grid;
     # the sharded run measures configs[3]: a speed-up must divide like by like) --------------------------------
-    if rank == 0 and world > 1 and strong and not args.pmc_child:
+    if rank == 0 and world > 1 and strong and args.full and not args.pmc_child:
         try:
             f_ts = DeviceBuffer(isz * T * C_total)
             h.synth_sst(f_ts.ptr, isz, T, C_total, C_total, 0, seed, ps["nan"], 0)
@@ -641,29 +711,7 @@ def run(args):
             result["multi_gpu"]["single_rank_error"] = f"{type(e).__name__}: {e}"
 
     # ---- parity (rank 0) ----------------------------------------------------------------------
-    def gather_cols(buf, itemsize, rows, ld, idx, dtype, base=0):
-        d_idx = DeviceBuffer.from_array(idx.astype(np.int64))
-        d_out = DeviceBuffer(itemsize * rows * idx.size)
-        try:
-            h.gather_cells(buf.ptr + base, itemsize, rows, ld, d_idx.ptr, idx.size, d_out.ptr, idx.size)
-            h.stream_sync(0)
-            return d_out.to_array((rows, idx.size), dtype)
-        finally:
-            d_idx.free()
-            d_out.free()
-
-    def rank0_columns(idx):
-        """columns idx (indices into rank 0's block) of the step's output: (thresh, seas)"""
-        th = np.empty((D, idx.size))
-        se = np.empty((D, idx.size))
-        for i, (a, b) in enumerate(slabs):
-            sel = np.nonzero((idx >= a) & (idx < b))[0]
-            if sel.size:
-                both = gather_cols(out[i], 8, 2 * D, b - a, idx[sel] - a, np.float64)
-                th[:, sel], se[:, sel] = both[:D], both[D:]
-        return th, se
-
-    if rank == 0 and args.parity_cells > 0:
+    if rank == 0 and args.full and args.parity_cells > 0:
         import oracle_fast as fast
         idx = np.unique(np.linspace(0, C - 1, min(args.parity_cells, C)).astype(np.int64))
         sample = gather_cols(ts, isz, T, C, idx, np.float32 if isz == 4 else np.float64)
@@ -674,7 +722,7 @@ def run(args):
         err_se = float(np.nanmax(np.abs(got_se - se0) / np.abs(se0)))
         result["parity"] = {"cells": int(idx.size), "max_rel_err_thresh": err_th, "max_rel_err_seas": err_se,
                             "tolerance": 1e-6, "ok": bool(err_th < 1e-6 and err_se < 1e-6)}
-    if rank == 0 and use_dist and args.parity_cells > 0:
+    if rank == 0 and use_dist and args.full and args.parity_cells > 0:
         # N-rank == 1-rank: for EVERY rank two probes of k columns each -- the first columns of its first slab and
         # the last columns of its last slab, i.e. always inside one slab -- recomputed on rank 0 alone (the
         # synthetic input is a function of the global cell index) and compared bit for bit with what arrived in
@@ -739,7 +787,7 @@ def run(args):
         }
         pool.close()
     # ---- the other BASELINE configs and float64 (N = 1): 3 steps each, same contract, a small parity sample ---
-    if rank == 0 and world == 1 and not args.no_other and not args.pmc_child and not args.force_dist:
+    if rank == 0 and world == 1 and args.full and not args.no_other and not args.pmc_child and not args.force_dist:
         for b_ in [ts] + raw_th + raw_se + out:
             b_.free()
         release_device_cache()

@@ -9,7 +9,7 @@ cp xmhw_amd/libxmhw_amd.so /tmp/lib_keep.so
 for round in $(seq 1 $REPS); do
   for f in ab/*.so; do
     cp "$f" xmhw_amd/libxmhw_amd.so
-    python bench.py --no-pmc --no-cpu --no-other > /tmp/ab.json 2> /tmp/ab.err || { echo "$f failed"; tail -3 /tmp/ab.err; continue; }
+    python bench.py --full --no-pmc --no-cpu --no-other > /tmp/ab.json 2> /tmp/ab.err || { echo "$f failed"; tail -3 /tmp/ab.err; continue; }
     python -c "
 import json; d=json.load(open('/tmp/ab.json')); print('$f', round(d['ms_per_step'],2), round(d['roofline']['avg_launch_ms'],2), d['parity']['ok'])"
     for sh in $SHAPES; do

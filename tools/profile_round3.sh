@@ -9,7 +9,7 @@
 # Every step runs under its own timeout.
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_r3; mkdir -p $O
-timeout 900 python3 $R/bench.py > $O/r3_bench.json 2> $O/bench.err
+timeout 900 python3 $R/bench.py --full > $O/r3_bench.json 2> $O/bench.err
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --steps 5 --warmup 1 --no-cpu --no-pmc --no-other > $O/trace.log 2>&1
 cp $(ls $O/trace/*/*kernel_stats.csv | head -1) $O/r3_kernel_stats.csv
 timeout 600 bash $R/tools/pmc_ring2.sh r3v21 21 > /dev/null 2>&1

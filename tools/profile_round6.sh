@@ -12,7 +12,7 @@
 # Every step runs under its own timeout; the program sits directly after `--`.
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_r6; mkdir -p $O
-timeout 900 python3 $R/bench.py > $O/r6_bench.json 2> $O/bench.err
+timeout 900 python3 $R/bench.py --full > $O/r6_bench.json 2> $O/bench.err
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --steps 5 --warmup 1 --no-cpu --no-pmc --no-other --parity-cells 0 > $O/trace.log 2>&1
 cp $(ls $O/trace/*/*kernel_stats.csv | head -1) $O/r6_kernel_stats.csv
 timeout 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY --output-format csv -d $O/sq -- python3 $R/bench.py --steps 1 --warmup 0 --no-pmc --no-cpu --no-other --parity-cells 0 > $O/sq.log 2>&1
