@@ -106,3 +106,23 @@ def threshold_cells_fast(ts, doy, pctile=90, windowHalfWidth=5, smoothPercentile
         th[:, c] = finish_cell(doys, th[:, c], tstep, smoothPercentile, smoothPercentileWidth)
         se[:, c] = finish_cell(doys, se[:, c], tstep, smoothPercentile, smoothPercentileWidth)
     return doys, th, se
+
+
+def packed_mean_f64(codes, doy, w, scale, offset, fill=None, negate=False):
+    """The pooled mean xmhw_clim_raw_i16 documents for int16 codes with float64 packing attributes
+    (xmhw_amd/csrc/packed_src.h): the exact integer sum S of a pool's valid codes, divided once by their
+    count n, decoded in float64 with two roundings -- ``(S / n) * scale + offset``, negated for cold spells;
+    NaN where a pool has no valid code.  ``fill``: the fill code (None: every code is a value)."""
+    codes = np.asarray(codes)
+    valid = np.ones(codes.shape, dtype=bool) if fill is None else codes != fill
+    c = np.where(valid, codes.astype(np.int64), 0)
+    doys, pools = pool_index(doy, w)
+    out = np.full((doys.shape[0], codes.shape[1]), np.nan)
+    for i, idx in enumerate(pools):
+        S = c[idx].sum(axis=0)                      # int64: exact
+        n = valid[idx].sum(axis=0)
+        m = S.astype(np.float64) / np.where(n > 0, n, 1)
+        y = m * scale
+        y = y + offset
+        out[i] = np.where(n > 0, -y if negate else y, np.nan)
+    return out

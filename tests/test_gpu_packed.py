@@ -6,6 +6,14 @@ float32 decode (float32 attributes, the packing of tests/golden/hdf5/packed_earl
 orders): bit-identical, thresh AND seas, to xmhw_decode + the float32 path.  float64 decode (float64 attributes): the
 kernel selects on the codes and decodes the two selected codes in float64 -- thresh bit-identical to the float64 path on
 the decoded series and to the oracle on numpy's decode; seas = decode(exact mean of the codes), within rounding.
+
+What this module pins to the GENERIC kernel (or to xmhw_decode + the float32 path) on the decoded series: the float32
+decode with both byte orders, the float64 decode at q = 0.9, the recomputation of overflowing lists, partial years with
+ties, a handful of record lengths.  It also pins what threshold() does with a packed netCDF file (float32 / float64
+attributes, _FillValue or missing_value alone; pctile 90 and 10 in place, 50 decoded first) to threshold() on the
+host-decoded array.  The oracle is the referee of tests/test_gpu_packed_oracle.py: every recipe and sign, mirrored
+quantiles, every i16 instantiation, other fill codes, pitched buffers -- thresh bit for bit, seas bit for bit in modes 2
+and 3 (the float64 restatement oracle_fast.packed_mean_f64 / the oracle itself).
 """
 import numpy as np
 import numpy.testing as npt
@@ -181,12 +189,16 @@ def test_plans_the_sorted_kernel_does_not_serve_are_refused(dev):
         _packed(dev, codes, doy, 0.9, False, 0.0, 10.0, FILL, "float64")             # scale_factor 0
 
 
-@pytest.mark.parametrize("kind", ["i16_f32attrs", "i16_f64attrs"])
+@pytest.mark.parametrize("kind,pctile", [pytest.param(k, p, id=k if p == 90 else f"{k}-p{p}")
+                                         for p in (90, 10, 50)
+                                         for k in ("i16_f32attrs", "i16_f64attrs", "i16_fill_only", "i16_missing_only")])
 @pytest.mark.parametrize("cold", [False, True])
-def test_threshold_from_a_packed_file_reads_the_codes_in_place(tmp_path, dev, monkeypatch, kind, cold):
+def test_threshold_from_a_packed_file_reads_the_codes_in_place(tmp_path, dev, monkeypatch, kind, cold, pctile):
     """threshold() on the mapped netCDF file of a 12-year packed archive: the codes are what is uploaded, masked (land =
     every code the fill code), compacted and read by the kernels; the result equals threshold() on the host-decoded
-    array (float32 attributes: bit for bit; float64 attributes: thresh bit for bit, seas within rounding)"""
+    array (float32 attributes, _FillValue or missing_value alone: bit for bit; float64 attributes: thresh bit for bit,
+    seas within rounding).  pctile 10 runs mirrored on the same in-place path; pctile 50 is not the sorted kernel's:
+    the codes are decoded first, with the same result"""
     import xmhw_amd
     import xmhw_amd.device as device
     from xmhw_amd import GridSeries, ingest, netcdf3
@@ -202,9 +214,12 @@ def test_threshold_from_a_packed_file_reads_the_codes_in_place(tmp_path, dev, mo
     if kind == "i16_f32attrs":
         at = {"scale_factor": np.float32(0.01), "add_offset": np.float32(10.0), "_FillValue": np.int16(-32768)}
         packed = np.where(np.isnan(sst), -32768, np.round((sst - 10.0) / 0.01)).astype(np.int16)
-    else:
+    elif kind == "i16_f64attrs":
         at = {"scale_factor": 0.005, "add_offset": 10.0, "_FillValue": np.int16(-32768)}
         packed = np.where(np.isnan(sst), -32768, np.round((sst - 10.0) / 0.005)).astype(np.int16)
+    else:                                                # no packing attributes: the codes are the values
+        at = {"_FillValue" if kind == "i16_fill_only" else "missing_value": np.int16(-32768)}
+        packed = np.where(np.isnan(sst), -32768, np.round((sst - 10.0) / 0.01)).astype(np.int16)
     p = tmp_path / "packed.nc"
     days = (time - np.datetime64("2001-01-01")).astype(np.float64)
     netcdf3.write_classic(str(p), {"time": T, "lat": ny, "lon": nx},
@@ -213,14 +228,18 @@ def test_threshold_from_a_packed_file_reads_the_codes_in_place(tmp_path, dev, mo
                            "sst": (("time", "lat", "lon"), packed, at)}, record_dim="time")
     temp = ingest.open_series(str(p), "sst")
     host = decode_packed(temp.values)
-    ref = xmhw_amd.threshold(GridSeries(host, temp.dims, temp.coords, time_encoding=temp.time_encoding), coldSpells=cold)
+    ref = xmhw_amd.threshold(GridSeries(host, temp.dims, temp.coords, time_encoding=temp.time_encoding), coldSpells=cold,
+                             pctile=pctile)
     calls = []
     real = device.clim_raw_packed
     monkeypatch.setattr(device, "clim_raw_packed", lambda *a, **k: (calls.append(k.get("decoded")), real(*a, **k))[1])
-    got = xmhw_amd.threshold(temp, coldSpells=cold)
-    assert calls == ["float32" if kind == "i16_f32attrs" else "float64"], "the packed file did not take the in-place path"
+    got = xmhw_amd.threshold(temp, coldSpells=cold, pctile=pctile)
+    if pctile == 50:
+        assert calls == [], "a median is not the sorted kernel's: the codes must be decoded first"
+    else:
+        assert calls == ["float64" if kind == "i16_f64attrs" else "float32"], "the packed file did not take the in-place path"
     npt.assert_array_equal(got["thresh"], ref["thresh"])
-    if kind == "i16_f32attrs":
+    if kind != "i16_f64attrs" or pctile == 50:
         npt.assert_array_equal(got["seas"], ref["seas"])
     else:
         npt.assert_allclose(got["seas"], ref["seas"], rtol=1e-12, atol=1e-12)
@@ -228,7 +247,7 @@ def test_threshold_from_a_packed_file_reads_the_codes_in_place(tmp_path, dev, mo
     # ... and with the in-place path switched off the decoded path gives the same
     monkeypatch.setenv("XMHW_PACKED_DIRECT", "0")
     calls.clear()
-    off = xmhw_amd.threshold(temp, coldSpells=cold)
+    off = xmhw_amd.threshold(temp, coldSpells=cold, pctile=pctile)
     assert calls == []
     npt.assert_array_equal(off["thresh"], ref["thresh"])
     npt.assert_array_equal(off["seas"], ref["seas"])

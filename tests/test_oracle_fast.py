@@ -71,3 +71,30 @@ def test_percell_baseline_matches_dumb():
         npt.assert_array_equal(d0, d1)
         npt.assert_array_equal(t1, t0)
         npt.assert_array_equal(s1, s0)
+
+
+@pytest.mark.parametrize("negate", [False, True])
+@pytest.mark.parametrize("scale,offset,fill", [(0.01, 1.5, -32768), (-0.0021973, 0.3, 0), (0.5, -7.25, None)])
+def test_packed_mean_f64_is_the_mean_of_the_decoded_series(negate, scale, offset, fill):
+    """oracle_fast.packed_mean_f64 (the restatement of the int16 kernels' float64 mean: exact sum of codes, one
+    division, decode) against raw_clim's mean of numpy's float64 decode, within rounding; NaN where raw_clim has NaN"""
+    rng = np.random.default_rng(17)
+    time = np.arange("2001-01-01", "2013-01-01", dtype="datetime64[D]")
+    doy = ora.add_doy(time)
+    T, C = time.shape[0], 9
+    codes = rng.integers(-32768, 32768, size=(T, C)).astype(np.int16)
+    codes[:, 2] = rng.integers(-300, 300, size=T)            # values near 0: the atol
+    if fill is not None:
+        codes[rng.random((T, C)) < 0.05] = fill
+        codes[:, 4] = fill
+        codes[(doy >= 100) & (doy <= 120), 5] = fill
+    x = codes.astype(np.float64) * scale + offset
+    if fill is not None:
+        x[codes == fill] = np.nan
+    _, _, se = fast.raw_clim(-x if negate else x, doy, 0.9, 5)
+    got = fast.packed_mean_f64(codes, doy, 5, scale, offset, fill=fill, negate=negate)
+    npt.assert_array_equal(np.isnan(got), np.isnan(se))
+    amax = np.nanmax(np.abs(x))
+    npt.assert_allclose(got, se, rtol=1e-12, atol=1e-13 * amax)
+    if fill is not None:
+        assert np.isnan(got[:, 4]).all() and np.isnan(got[105 - 1, 5])

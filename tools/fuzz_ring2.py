@@ -164,31 +164,60 @@ def check_f64_case(dev, x, doy, pct, tstep, cold, nchunks, msg="", kernel="auto"
             npt.assert_allclose(s1, s0, rtol=1e-12, atol=1e-12, equal_nan=True, err_msg=f"{msg} narrowing={narrowing}")
 
 
-def check_packed_case(dev, x, doy, pct, cold, rng, msg=""):
-    """int16 codes read in place (xmhw_clim_raw_i16) against the generic kernel on the series xmhw_decode() makes of the
-    same codes: thresh bit for bit, seas within rounding; float32 and float64 decode, either byte order, a random recipe"""
-    h = dev.hip()
-    T, C = x.shape
+def random_packed_recipe(rng):
+    """a random CF recipe for int16 codes: packing attributes (float32 or float64 decode: xmhw_clim_raw_i16's modes 1 and 2,
+    either sign of scale_factor), a _FillValue alone or nothing at all (mode 3: the codes stand for themselves); a fill
+    code at either end of the range or inside it; either byte order.  ``scale`` also sets the code step of encode_packed()"""
+    kind = str(rng.choice(["attrs", "attrs", "fill_only", "none"]))
     scale = float(rng.choice([0.01, 0.5, 0.001, -0.01, 0.0021973]))
     offset = float(rng.choice([0.0, 10.0, 273.15]))
-    fill = int(rng.choice([-32768, -999, 32767]))
+    fill = int(rng.choice([-32768, -999, 0, 32767]))
     decoded = str(rng.choice(["float32", "float64"]))
     big = bool(rng.integers(0, 2))
+    if kind == "attrs" and decoded == "float32":
+        scale, offset = float(np.float32(scale)), float(np.float32(offset))
+    return dict(kind=kind, scale=scale, offset=offset, fill=None if kind == "none" else fill, decoded=decoded, big_endian=big)
+
+
+def encode_packed(x, r):
+    """x -> int16 codes round((x - offset) / scale), clipped; NaN -> the fill code (no fill: -32768, then an ordinary
+    value); a code that equals the fill code by chance is moved one step"""
     finite = np.isfinite(x)
     with np.errstate(invalid="ignore", over="ignore"):
-        c = np.rint((np.where(finite, x, 0.0).astype(np.float64) - offset) / scale)
+        c = np.rint((np.where(finite, x, 0.0).astype(np.float64) - r["offset"]) / r["scale"])
     codes = np.clip(c, -32767, 32766).astype(np.int16)
-    codes[codes == fill] += 1 if fill < 32766 else -1
-    codes[~finite] = fill
-    if decoded == "float32":
-        scale, offset = float(np.float32(scale)), float(np.float32(offset))
+    if r["fill"] is not None:
+        codes[codes == r["fill"]] += 1 if r["fill"] < 32766 else -1
+    codes[~finite] = -32768 if r["fill"] is None else r["fill"]
+    return codes
+
+
+def packed_call_args(r):
+    """clim_raw_packed()'s recipe keywords for a random_packed_recipe()"""
+    attrs = r["kind"] == "attrs"
+    return dict(scale_factor=r["scale"] if attrs else None, add_offset=r["offset"] if attrs else None, fill=r["fill"],
+                decoded=r["decoded"], big_endian=r["big_endian"])
+
+
+def check_packed_case(dev, x, doy, pct, cold, rng, msg=""):
+    """int16 codes read in place (xmhw_clim_raw_i16) against the generic kernel on the series xmhw_decode() makes of the
+    same codes: thresh bit for bit, seas within rounding; a random_packed_recipe()"""
+    h = dev.hip()
+    T, C = x.shape
+    r = random_packed_recipe(rng)
+    codes = encode_packed(x, r)
+    kw = packed_call_args(r)
+    big, decoded = r["big_endian"], r["decoded"]
+    has_scale = kw["scale_factor"] is not None
+    scale, offset = (r["scale"], r["offset"]) if has_scale else (1.0, 0.0)
     isz = 4 if decoded == "float32" else 8
     stored = np.ascontiguousarray(codes.astype(">i2") if big else codes).view(np.int16)
     d_codes = dev.DeviceBuffer.from_array(stored)
     d_dec = dev.DeviceBuffer(isz * T * C)
     bufs = [d_codes, d_dec]
     try:
-        h.decode(d_codes.ptr, 2, int(big), T, C, C, d_dec.ptr, isz, C, True, scale, offset, True, float(fill), 0)
+        h.decode(d_codes.ptr, 2, int(big), T, C, C, d_dec.ptr, isz, C, has_scale, scale, offset, r["fill"] is not None,
+                 0.0 if r["fill"] is None else float(r["fill"]), 0)
         h.stream_sync(0)
         out = {}
         for which in ("packed", "generic"):
@@ -196,15 +225,14 @@ def check_packed_case(dev, x, doy, pct, cold, rng, msg=""):
             th, se = dev.DeviceBuffer(8 * plan.D * C), dev.DeviceBuffer(8 * plan.D * C)
             try:
                 if which == "packed":
-                    dev.clim_raw_packed(plan, d_codes, C, pct / 100.0, cold, th, se, scale_factor=scale, add_offset=offset,
-                                        fill=fill, decoded=decoded, big_endian=big)
+                    dev.clim_raw_packed(plan, d_codes, C, pct / 100.0, cold, th, se, **kw)
                 else:
                     dev.clim_raw(plan, d_dec, isz, C, pct / 100.0, cold, th, se)
                 h.stream_sync(0)
                 out[which] = (th.to_array((plan.D, C), np.float64), se.to_array((plan.D, C), np.float64))
             finally:
                 th.free(); se.free(); plan.destroy()
-        m = f"{msg} scale={scale} offset={offset} fill={fill} decoded={decoded} big_endian={big}"
+        m = f"{msg} recipe={r['kind']} scale={kw['scale_factor']} offset={kw['add_offset']} fill={r['fill']} decoded={decoded} big_endian={big}"
         with np.errstate(invalid="ignore"):
             npt.assert_array_equal(out["packed"][0], out["generic"][0], err_msg=m)
             amax = float(np.abs(codes.astype(np.float64) * scale + offset).max())
@@ -246,7 +274,7 @@ def main():
                 refused += 1
                 continue
             done += 1
-        print(f"{args.cases} random int16-packed cases (codes read in place; float32 / float64 decode, either byte order): 0 mismatches "
+        print(f"{args.cases} random int16-packed cases (codes read in place; float32 / float64 decode, fill only, no attributes, either byte order): 0 mismatches "
               f"against the generic kernel on the decoded series; {refused} draws refused as plans of another kernel ({time.perf_counter() - t0:.0f} s)")
         return
     if args.dtype == "f64":
