@@ -134,6 +134,13 @@ template hipError_t launch_generic<double>(const double*, int64_t, int64_t, int6
 // column with NaN rows (empty pools) the neighbours are the next present rows
 // (positional rolling); a column without NaN takes the direct path.
 // blockIdx.y selects the array (0 thresh, 1 seas); thread = cell.
+// Both paths slide the window sum (+ lead - trail) and replace it every `width`
+// rows by `fresh`, the sum of the rows that entered since, oldest first -- the
+// window summed directly -- so the sliding error spans `width` rows, not the
+// column.  The replacement rows (every width-th row, counted from row 0 on the
+// direct path and from the first present row on the positional one) depend on
+// the column alone; for width 31 the direct path re-sums at the rows
+// clim_finish_stream does, in the same order: bit-identical to it.
 // ---------------------------------------------------------------------------
 struct FinishCol {
     const double* in;
@@ -188,18 +195,26 @@ __global__ __launch_bounds__(256) void clim_finish(const double* __restrict__ th
         // every group present: window of row d is rows (d-h .. d+h) mod D
         int32_t trail = ((-h) % D + D) % D;
         int32_t lead = trail;
-        double s = 0.0;
+        double s = -0.0;
         for (int32_t i = 0; i < width; ++i) {
             s += col.val(lead);
             if (i + 1 < width) lead = (lead + 1 == D) ? 0 : lead + 1;
         }
+        double fresh = -0.0;    // (-0.0: x + -0.0 == x for every x, so the first add is exact)
+        int32_t nfresh = 0;
         for (int32_t d = 0; d < D; ++d) {
             out[static_cast<int64_t>(d) * ld] = s / inv;
             s -= col.val(trail);
             trail = (trail + 1 == D) ? 0 : trail + 1;
             lead = (lead + 1 == D) ? 0 : lead + 1;
-            s += col.val(lead);
-            if (!(fabs(s) <= 1.7976931348623157e308)) {
+            const double v = col.val(lead);
+            s += v;
+            fresh += v;
+            if (++nfresh == width) {          // the window of row d + 1 is the last `width` rows that entered
+                s = fresh;
+                fresh = -0.0;
+                nfresh = 0;
+            } else if (!(fabs(s) <= 1.7976931348623157e308)) {
                 // an infinite value went through the sliding sum (inf - inf = NaN): sum the window
                 // directly, which gives what numpy's mean gives (+-inf while it is inside, NaN for both signs)
                 s = 0.0;
@@ -227,11 +242,13 @@ __global__ __launch_bounds__(256) void clim_finish(const double* __restrict__ th
     int32_t trail = first;
     for (int32_t i = 0; i < h; ++i) trail = prev_present(trail);
     int32_t lead = trail;
-    double s = 0.0;
+    double s = -0.0;
     for (int32_t i = 0; i < width; ++i) {
         s += col.val(lead);
         if (i + 1 < width) lead = next_present(lead);
     }
+    double fresh = -0.0;
+    int32_t nfresh = 0;
     int32_t cur = first;
     for (int32_t d = 0; d < first; ++d) out[static_cast<int64_t>(d) * ld] = make_nan();
     for (int32_t j = 0; j < np; ++j) {
@@ -239,8 +256,14 @@ __global__ __launch_bounds__(256) void clim_finish(const double* __restrict__ th
         s -= col.val(trail);
         trail = next_present(trail);
         lead = next_present(lead);
-        s += col.val(lead);
-        if (!(fabs(s) <= 1.7976931348623157e308)) {
+        const double v = col.val(lead);
+        s += v;
+        fresh += v;
+        if (++nfresh == width) {
+            s = fresh;
+            fresh = -0.0;
+            nfresh = 0;
+        } else if (!(fabs(s) <= 1.7976931348623157e308)) {
             s = 0.0;
             for (int32_t i = 0, k = trail; i < width; ++i, k = next_present(k)) s += col.val(k);
         }
@@ -258,10 +281,13 @@ __global__ __launch_bounds__(256) void clim_finish(const double* __restrict__ th
 // (D x CT cells) tile of one array in LDS (row-major, CT*8-byte rows, loaded with
 // CT*8 contiguous bytes per row); CT cells x PARTS threads then produce the
 // outputs, thread (cell, part) owning a contiguous slice of the doy range:
-// Feb-29 value from LDS, window sum initialised per slice (the running sum never
-// drifts over more than D/PARTS steps), sliding updates from LDS, stores
-// coalesced over the tile's cells.  Columns with absent groups (NaN rows) are rare
-// and are rolled over their present rows by the part-0 thread alone.
+// Feb-29 value from LDS, window sum initialised per slice, sliding updates from
+// LDS, stores coalesced over the tile's cells.  Columns with absent groups (NaN
+// rows) are rare and are rolled over their present rows by the part-0 thread
+// alone.  Both paths replace the sliding sum every `width` rows by the direct sum
+// of the rows that entered since (see clim_finish): on the direct path every
+// width-th row of a slice (slices depend on D only), on the positional path every
+// width-th present row from the first.
 // ---------------------------------------------------------------------------
 template <int CT>
 __global__ __launch_bounds__(256) void clim_finish_tiled(const double* __restrict__ th_in,
@@ -325,18 +351,26 @@ __global__ __launch_bounds__(256) void clim_finish_tiled(const double* __restric
         }
         int32_t trail = ((d0 - h) % D + D) % D;
         int32_t lead = trail;
-        double s = 0.0;
+        double s = -0.0;
         for (int32_t i = 0; i < width; ++i) {
             s += val(lead);
             if (i + 1 < width) lead = (lead + 1 == D) ? 0 : lead + 1;
         }
+        double fresh = -0.0;
+        int32_t nfresh = 0;
         for (int32_t d = d0; d < d1; ++d) {
             out[static_cast<int64_t>(d) * ld + c] = s / wd;
             s -= val(trail);
             trail = (trail + 1 == D) ? 0 : trail + 1;
             lead = (lead + 1 == D) ? 0 : lead + 1;
-            s += val(lead);
-            if (!(fabs(s) <= 1.7976931348623157e308)) {   // infinite value in the window: direct sum (see clim_finish)
+            const double v = val(lead);
+            s += v;
+            fresh += v;
+            if (++nfresh == width) {                       // re-sum (see clim_finish)
+                s = fresh;
+                fresh = -0.0;
+                nfresh = 0;
+            } else if (!(fabs(s) <= 1.7976931348623157e308)) {   // infinite value in the window: direct sum (see clim_finish)
                 s = 0.0;
                 for (int32_t i = 0, k = trail; i < width; ++i, k = (k + 1 == D) ? 0 : k + 1) s += val(k);
             }
@@ -363,11 +397,13 @@ __global__ __launch_bounds__(256) void clim_finish_tiled(const double* __restric
     int32_t trail = first;
     for (int32_t i = 0; i < h; ++i) trail = prev_present(trail);
     int32_t lead = trail;
-    double s = 0.0;
+    double s = -0.0;
     for (int32_t i = 0; i < width; ++i) {
         s += val(lead);
         if (i + 1 < width) lead = next_present(lead);
     }
+    double fresh = -0.0;
+    int32_t nfresh = 0;
     int32_t cur = first;
     for (int32_t d = 0; d < first; ++d) out[static_cast<int64_t>(d) * ld + c] = make_nan();
     for (int32_t j = 0; j < np; ++j) {
@@ -375,8 +411,14 @@ __global__ __launch_bounds__(256) void clim_finish_tiled(const double* __restric
         s -= val(trail);
         trail = next_present(trail);
         lead = next_present(lead);
-        s += val(lead);
-        if (!(fabs(s) <= 1.7976931348623157e308)) {
+        const double v = val(lead);
+        s += v;
+        fresh += v;
+        if (++nfresh == width) {
+            s = fresh;
+            fresh = -0.0;
+            nfresh = 0;
+        } else if (!(fabs(s) <= 1.7976931348623157e308)) {
             s = 0.0;
             for (int32_t i = 0, k = trail; i < width; ++i, k = next_present(k)) s += val(k);
         }
