@@ -485,6 +485,22 @@ int xmhw_block_time_f64(const double *ts_dev, int64_t T, int64_t C, int64_t ld, 
                         int64_t ldcat, const int32_t *bin_of_t_dev, int32_t nbins, double *out_dev,
                         int64_t ldo, void *stream);
 
+/* ---- mhw_rank() (xmhw/stats.py:446-510) ------------------------------------------------------ *
+ * Per-cell ranks and return periods of event properties, on the compact event table of detect()
+ * (table_dev row-major with leading dimension ld_table; the events of cell c are rows
+ * offsets_dev[c]..offsets_dev[c+1]).  For column k of the list (columns[k] < ld_table, host array,
+ * 1 <= ncols <= 31) and event i of a cell, over the values v of that column in that cell:
+ *     rank_i = 1 + #{j : v_j > v_i} + #{j > i : v_j == v_i}
+ * i.e. the largest value has rank 1 and of equal values the later event ranks first
+ * (= N - argsort(argsort(v, kind="stable")) over the N non-NaN values); values compare as float64,
+ * so -0.0 == 0.0.  A NaN value gets a NaN rank and does not count for the other events.
+ * Return period rp_i = (n_years + 1) / rank_i (one float64 division; NaN where the rank is NaN),
+ * n_years finite and > 0.  Results go to rank_dev / rp_dev [row][ld_out] at column k (ld_out >= ncols);
+ * no other element is written.  Asynchronous on `stream`; nothing is launched for C == 0.        */
+int xmhw_event_rank(const double *table_dev, int64_t ld_table, const int64_t *offsets_dev, int64_t C,
+                    const int32_t *columns, int32_t ncols, double n_years, double *rank_dev, double *rp_dev,
+                    int64_t ld_out, void *stream);
+
 /* ---- the sharded path: cells split across the GPUs of a node, ONE gather at the end ------- *
  * Replaces the reference's collect, dask.compute(climls) + xr.concat(dim='cell')
  * (xmhw/xmhw.py:197, :210-211).  Cells are independent (xmhw/xmhw.py:184-196), so rank r runs the

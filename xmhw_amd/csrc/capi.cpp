@@ -5,6 +5,7 @@
 #include <unistd.h>
 
 #include <cerrno>
+#include <cmath>
 
 #include <algorithm>
 #include <cstdio>
@@ -1679,6 +1680,52 @@ int xmhw_block_time_f32(const float* ts, int64_t T, int64_t C, int64_t ld, const
 int xmhw_block_time_f64(const double* ts, int64_t T, int64_t C, int64_t ld, const double* cats, int64_t ldcat,
                         const int32_t* bin_of_t, int32_t nbins, double* out, int64_t ldo, void* stream) {
     return block_time<double>(ts, T, C, ld, cats, ldcat, bin_of_t, nbins, out, ldo, stream);
+}
+
+int xmhw_event_rank(const double* table, int64_t ld_table, const int64_t* offsets, int64_t C, const int32_t* columns,
+                    int32_t ncols, double n_years, double* rank, double* rp, int64_t ld_out, void* stream) {
+    if (C < 0 || ld_table < 1) return fail(XMHW_ERR_INVALID, "bad C/ld_table");
+    if (ncols < 1 || ncols > xmhw::kEventColumns) return fail(XMHW_ERR_INVALID, "ncols must be in 1..31");
+    if (!columns) return fail(XMHW_ERR_INVALID, "NULL column list");
+    for (int32_t k = 0; k < ncols; ++k)
+        if (columns[k] < 0 || columns[k] >= ld_table) return fail(XMHW_ERR_INVALID, "column outside the table row (ld_table)");
+    if (ld_out < ncols) return fail(XMHW_ERR_INVALID, "ld_out must be >= ncols");
+    if (!(n_years > 0.0) || !std::isfinite(n_years)) return fail(XMHW_ERR_INVALID, "n_years must be finite and > 0");
+    if (C == 0) return XMHW_OK;
+    if (!table || !offsets || !rank || !rp) return fail(XMHW_ERR_INVALID, "NULL buffer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // scratch: item counts (int32, C), item offsets (int64, C + 1), the scan's block sums, the item counter
+    const size_t n_counts = static_cast<size_t>(C + 1) & ~size_t{1};
+    const size_t n_sums = static_cast<size_t>((C + 1023) / 1024 + 1);
+    void* sp = nullptr;
+    ScratchRef scratch_keep;
+    hipError_t e = scratch_get(st, sizeof(int32_t) * n_counts + sizeof(int64_t) * (static_cast<size_t>(C) + 2 + n_sums), &sp,
+                               &scratch_keep);
+    if (e != hipSuccess) return hip_fail(e, "scratch allocation");
+    int32_t* counts = static_cast<int32_t*>(sp);
+    int64_t* item_off = reinterpret_cast<int64_t*>(counts + n_counts);
+    int64_t* sums = item_off + C + 1;
+    unsigned long long* next_item = reinterpret_cast<unsigned long long*>(sums + n_sums);
+    // one launch per window of at most kRankWindow table columns (the ranked columns of detect(): two)
+    std::vector<std::pair<int32_t, int32_t>> cols;             // (table column, output column)
+    for (int32_t k = 0; k < ncols; ++k) cols.push_back({columns[k], k});
+    std::sort(cols.begin(), cols.end());
+    for (size_t a = 0; a < cols.size();) {
+        xmhw::RankColumns rc{};
+        rc.cmin = cols[a].first;
+        size_t b = a;
+        while (b < cols.size() && b - a < xmhw::kRankWindow && cols[b].first - rc.cmin < xmhw::kRankWindow) {
+            rc.col[b - a] = cols[b].first;
+            rc.out[b - a] = cols[b].second;
+            ++b;
+        }
+        rc.ncols = static_cast<int32_t>(b - a);
+        rc.span = cols[b - 1].first - rc.cmin + 1;
+        e = xmhw::launch_event_rank(table, ld_table, offsets, C, rc, n_years, rank, rp, ld_out, counts, item_off, sums, next_item, st);
+        if (e != hipSuccess) return hip_fail(e, "event_rank launch");
+        a = b;
+    }
+    return XMHW_OK;
 }
 
 int xmhw_synth_sst_f32(float* ts, int64_t T, int64_t C, int64_t ld, int64_t cell0, uint64_t seed,

@@ -208,6 +208,22 @@ template <typename T>
 hipError_t launch_block_time(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* cats, int64_t ldcat,
                              const int32_t* bin_of_t, int32_t nbins, double* out, int64_t ldo, hipStream_t stream);
 
+// mhw_rank() (kernels_rank.hip): per-cell ranks (largest = 1, ties: the later event first, NaN -> NaN) and
+// return periods (n_years + 1) / rank of the table columns col[0..ncols), written to column out[k] of the
+// rows of rank / rp (leading dimension ld_out).  One launch covers a window of table columns
+// [cmin, cmin + span), span <= kRankWindow, ncols <= kRankWindow.  Scratch: item_counts[C] int32,
+// item_off[C + 1] int64, scan_scratch (C + 1023) / 1024 + 1 int64, next_item one uint64.
+constexpr int kRankWindow = 16;
+struct RankColumns {
+    int32_t col[kRankWindow];
+    int32_t out[kRankWindow];
+    int32_t ncols, cmin, span;
+};
+hipError_t launch_event_rank(const double* table, int64_t ld_table, const int64_t* offsets, int64_t C,
+                             const RankColumns& rc, double n_years, double* rank, double* rp, int64_t ld_out,
+                             int32_t* item_counts, int64_t* item_off, int64_t* scan_scratch,
+                             unsigned long long* next_item, hipStream_t stream);
+
 // file bytes -> samples (kernels_ingest.hip): raw_type = item size of the stored type (2 int16, 4 float32,
 // 8 float64), swap = the file is big-endian, optional scale/offset (CF packing) and fill value -> NaN
 hipError_t launch_encode_i16(const float* in, int64_t rows, int64_t cols, int64_t ld_in, int16_t* out, int64_t ld_out,

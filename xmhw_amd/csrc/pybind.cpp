@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "../../include/xmhw_amd.h"
 
@@ -517,6 +518,15 @@ PYBIND11_MODULE(_xmhw_hip, m) {
                                 ldo, vp(stream)));
     }, py::arg("table"), py::arg("offsets"), py::arg("C"), py::arg("bin_of_t"), py::arg("T"), py::arg("nbins"),
        py::arg("mtime_col"), py::arg("out"), py::arg("ldo"), py::arg("stream") = 0);
+    m.def("event_rank", [](uintptr_t table, int64_t ld_table, uintptr_t offsets, int64_t C, py::sequence cols,
+                           double n_years, uintptr_t rank, uintptr_t rp, int64_t ld_out, uintptr_t stream) {
+        std::vector<int32_t> columns;
+        for (auto c : cols) columns.push_back(c.cast<int32_t>());
+        check(xmhw_event_rank(static_cast<const double*>(vp(table)), ld_table, static_cast<const int64_t*>(vp(offsets)), C,
+                              columns.data(), static_cast<int32_t>(columns.size()), n_years, static_cast<double*>(vp(rank)),
+                              static_cast<double*>(vp(rp)), ld_out, vp(stream)));
+    }, py::arg("table"), py::arg("ld_table"), py::arg("offsets"), py::arg("C"), py::arg("columns"), py::arg("n_years"),
+       py::arg("rank"), py::arg("rp"), py::arg("ld_out"), py::arg("stream") = 0);
     m.def("block_time", [](uintptr_t ts, int itemsize, int64_t T, int64_t C, int64_t ld, uintptr_t cats, int64_t ldcat,
                            uintptr_t bin_of_t, int nbins, uintptr_t out, int64_t ldo, uintptr_t stream) {
         if (itemsize == 4)
