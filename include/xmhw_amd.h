@@ -501,6 +501,34 @@ int xmhw_event_rank(const double *table_dev, int64_t ld_table, const int64_t *of
                     const int32_t *columns, int32_t ncols, double n_years, double *rank_dev, double *rp_dev,
                     int64_t ld_out, void *stream);
 
+/* ---- mean_trend() (Oliver's marineHeatWaves.meanTrend(); not in xmhw) -------------------------- *
+ * Per (cell, statistic) trends of the planes of block_average(): y_dev[stat][block][ld] float64, cells
+ * contiguous (ld >= C), nstat x nb x C items' worth.  x_dev[nb]: the abscissa, years centred on the
+ * whole period, STRICTLY INCREASING (not checked: it lives on the device).  A NaN block is left out of
+ * its series (m = the valid blocks of an item); an item with a valid +-Inf, or with m == 0, is NaN in
+ * every output.  Outputs are planes out_dev[what][stat][ldo] (ldo >= C); elements at columns >= C are
+ * not written.  Asynchronous on `stream`; nothing is launched for nstat == 0 or C == 0; nb == 0 gives
+ * NaN everywhere.  No FMA contraction, sums in block order: results are the same from run to run.
+ *
+ * xmhw_block_trend_ols: what = 0 mean, 1 trend, 2 dtrend.  Least squares of y on [1, x] over the valid
+ * blocks: xb = sum(x)/m, yb = sum(y)/m, Sxx = sum((x-xb)^2), Sxy = sum((x-xb)(y-yb)), trend = Sxy/Sxx,
+ * mean = yb - trend*xb (the fit at x = 0), r = y - (mean + trend*x), s = sqrt(sum(r^2)/(m-2)),
+ * dtrend = tcrit[m-2]*s/sqrt(Sxx).  tcrit_dev[k], k = 1..nb-2: the two-sided Student-t critical value
+ * for k degrees of freedom (nb - 1 entries, entry 0 unused; may be NULL for nb < 3).  m == 1: mean = y,
+ * trend and dtrend NaN; m == 2: dtrend NaN.
+ *
+ * xmhw_block_trend_theil_sen: what = 0 trend, 1 mean, 2 mk_s, 3 mk_var.  Over the pairs i < j of valid
+ * blocks, N = m(m-1)/2: trend = the median (s[(N-1)/2] + s[N/2])/2 of the slopes (y_j-y_i)/(x_j-x_i)
+ * sorted in IEEE total order; mean = median(y) - trend*median(x) over the valid blocks; mk_s =
+ * sum sign(y_j - y_i) (Mann-Kendall S); mk_var = (m(m-1)(2m+5) - sum_b (c_b-1)(2c_b+5))/18 with
+ * c_b = #{j: y_j == y_b}, the tie-corrected variance (integer numerator, one division).  m < 2: trend
+ * NaN (mean = y for m == 1); m < 3: mk_s and mk_var NaN.  nb above 128 blocks: XMHW_ERR_UNSUPPORTED.  */
+int xmhw_block_trend_ols(const double *y_dev, int32_t nstat, int32_t nb, int64_t C, int64_t ld,
+                         const double *x_dev, const double *tcrit_dev, double *out_dev, int64_t ldo,
+                         void *stream);
+int xmhw_block_trend_theil_sen(const double *y_dev, int32_t nstat, int32_t nb, int64_t C, int64_t ld,
+                               const double *x_dev, double *out_dev, int64_t ldo, void *stream);
+
 /* ---- the sharded path: cells split across the GPUs of a node, ONE gather at the end ------- *
  * Replaces the reference's collect, dask.compute(climls) + xr.concat(dim='cell')
  * (xmhw/xmhw.py:197, :210-211).  Cells are independent (xmhw/xmhw.py:184-196), so rank r runs the

@@ -1728,6 +1728,40 @@ int xmhw_event_rank(const double* table, int64_t ld_table, const int64_t* offset
     return XMHW_OK;
 }
 
+static int trend_args(const double* y, int32_t nstat, int32_t nb, int64_t C, int64_t ld, const double* x, const double* out,
+               int64_t ldo) {
+    if (nstat < 0 || nb < 0 || C < 0) return fail(XMHW_ERR_INVALID, "bad nstat/nb/C");
+    if (ld < C) return fail(XMHW_ERR_INVALID, "ld must be >= C");
+    if (ldo < C) return fail(XMHW_ERR_INVALID, "ldo must be >= C");
+    if (nstat == 0 || C == 0) return XMHW_OK;
+    if (!out) return fail(XMHW_ERR_INVALID, "NULL output buffer");
+    if (nb > 0 && (!y || !x)) return fail(XMHW_ERR_INVALID, "NULL buffer");
+    return XMHW_OK;
+}
+
+int xmhw_block_trend_ols(const double* y, int32_t nstat, int32_t nb, int64_t C, int64_t ld, const double* x,
+                         const double* tcrit, double* out, int64_t ldo, void* stream) {
+    if (int rc = trend_args(y, nstat, nb, C, ld, x, out, ldo)) return rc;
+    if (nstat == 0 || C == 0) return XMHW_OK;
+    if (nb >= 3 && !tcrit) return fail(XMHW_ERR_INVALID, "NULL tcrit table");
+    if (static_cast<int64_t>(nstat) * ((C + 63) / 64) > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "nstat * C too large for one launch");
+    hipError_t e = xmhw::launch_trend_ols(y, nstat, nb, C, ld, x, tcrit, out, ldo, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "trend_ols launch");
+    return XMHW_OK;
+}
+
+int xmhw_block_trend_theil_sen(const double* y, int32_t nstat, int32_t nb, int64_t C, int64_t ld, const double* x,
+                               double* out, int64_t ldo, void* stream) {
+    if (int rc = trend_args(y, nstat, nb, C, ld, x, out, ldo)) return rc;
+    if (nb > xmhw::kTrendMaxBlocks)
+        return fail(XMHW_ERR_UNSUPPORTED, "Theil-Sen trend: nb above the cap of " + std::to_string(xmhw::kTrendMaxBlocks) + " blocks");
+    if (nstat == 0 || C == 0) return XMHW_OK;
+    if (static_cast<int64_t>(nstat) * ((C + 15) / 16) > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "nstat * C too large for one launch");
+    hipError_t e = xmhw::launch_trend_theil_sen(y, nstat, nb, C, ld, x, out, ldo, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "trend_theil_sen launch");
+    return XMHW_OK;
+}
+
 int xmhw_synth_sst_f32(float* ts, int64_t T, int64_t C, int64_t ld, int64_t cell0, uint64_t seed,
                        double nan_frac, void* stream) {
     if (C < 0 || ld < C || T <= 0) return fail(XMHW_ERR_INVALID, "bad T/C/ld");

@@ -224,6 +224,16 @@ hipError_t launch_event_rank(const double* table, int64_t ld_table, const int64_
                              int32_t* item_counts, int64_t* item_off, int64_t* scan_scratch,
                              unsigned long long* next_item, hipStream_t stream);
 
+// mean_trend() (kernels_trend.hip): per (cell, statistic) trends of the block_average() planes y[stat][nb][ld]
+// along the abscissa x[nb] (device, strictly increasing), NaN blocks left out.  OLS writes out[what][stat][ldo] with
+// what = mean, trend, dtrend (tcrit[dof], device, nb - 1 entries, entry 0 unused); Theil-Sen writes what = trend,
+// mean, mk_s, mk_var and takes at most kTrendMaxBlocks blocks (its slopes live in LDS).
+constexpr int kTrendMaxBlocks = 128;
+hipError_t launch_trend_ols(const double* y, int32_t nstat, int32_t nb, int64_t C, int64_t ld, const double* x,
+                            const double* tcrit, double* out, int64_t ldo, hipStream_t stream);
+hipError_t launch_trend_theil_sen(const double* y, int32_t nstat, int32_t nb, int64_t C, int64_t ld, const double* x,
+                                  double* out, int64_t ldo, hipStream_t stream);
+
 // file bytes -> samples (kernels_ingest.hip): raw_type = item size of the stored type (2 int16, 4 float32,
 // 8 float64), swap = the file is big-endian, optional scale/offset (CF packing) and fill value -> NaN
 hipError_t launch_encode_i16(const float* in, int64_t rows, int64_t cols, int64_t ld_in, int16_t* out, int64_t ld_out,

@@ -527,6 +527,18 @@ PYBIND11_MODULE(_xmhw_hip, m) {
                               static_cast<double*>(vp(rp)), ld_out, vp(stream)));
     }, py::arg("table"), py::arg("ld_table"), py::arg("offsets"), py::arg("C"), py::arg("columns"), py::arg("n_years"),
        py::arg("rank"), py::arg("rp"), py::arg("ld_out"), py::arg("stream") = 0);
+    m.def("block_trend_ols", [](uintptr_t y, int32_t nstat, int32_t nb, int64_t C, int64_t ld, uintptr_t x, uintptr_t tcrit,
+                                uintptr_t out, int64_t ldo, uintptr_t stream) {
+        check(xmhw_block_trend_ols(static_cast<const double*>(vp(y)), nstat, nb, C, ld, static_cast<const double*>(vp(x)),
+                                   static_cast<const double*>(vp(tcrit)), static_cast<double*>(vp(out)), ldo, vp(stream)));
+    }, py::arg("y"), py::arg("nstat"), py::arg("nb"), py::arg("C"), py::arg("ld"), py::arg("x"), py::arg("tcrit"),
+       py::arg("out"), py::arg("ldo"), py::arg("stream") = 0);
+    m.def("block_trend_theil_sen", [](uintptr_t y, int32_t nstat, int32_t nb, int64_t C, int64_t ld, uintptr_t x,
+                                      uintptr_t out, int64_t ldo, uintptr_t stream) {
+        check(xmhw_block_trend_theil_sen(static_cast<const double*>(vp(y)), nstat, nb, C, ld,
+                                         static_cast<const double*>(vp(x)), static_cast<double*>(vp(out)), ldo, vp(stream)));
+    }, py::arg("y"), py::arg("nstat"), py::arg("nb"), py::arg("C"), py::arg("ld"), py::arg("x"), py::arg("out"),
+       py::arg("ldo"), py::arg("stream") = 0);
     m.def("block_time", [](uintptr_t ts, int itemsize, int64_t T, int64_t C, int64_t ld, uintptr_t cats, int64_t ldcat,
                            uintptr_t bin_of_t, int nbins, uintptr_t out, int64_t ldo, uintptr_t stream) {
         if (itemsize == 4)
