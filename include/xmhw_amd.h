@@ -529,6 +529,39 @@ int xmhw_block_trend_ols(const double *y_dev, int32_t nstat, int32_t nb, int64_t
 int xmhw_block_trend_theil_sen(const double *y_dev, int32_t nstat, int32_t nb, int64_t C, int64_t ld,
                                const double *x_dev, double *out_dev, int64_t ldo, void *stream);
 
+/* ---- mhw_coverage(): daily area in each MHW category, by region (Hobday et al. 2018, fig. 3) ------ *
+ * The one reduction ACROSS cells.  For every step t of the dense series ts_dev (T, C) and every region
+ * r < R, ADDS to cells_dev[t][r][k] the number of cells c with region_dev[c] == r that are in state k on
+ * step t, and to area_q_dev[t][r][k] the sum of their weights wq_dev[c]; both [T][R][5] int64, contiguous,
+ * zeroed by the caller before the first slab of cells: calls for consecutive slabs accumulate, on the same
+ * stream, without a read-back in between.  States k: 0 moderate, 1 strong, 2 severe, 3 extreme, 4 event.
+ * A step is "in an event" iff detect() labels it: mhw_filter() + join_gaps() (xmhw/identify.py:415-479,
+ * 273-325) on bits_dev, the exceedance words written by xmhw_exceed_bits_* for the same slab (ldb >= C);
+ * the walk is the one of xmhw_events_from_bits.  Its category is the per-step one of mhw_df()
+ * (xmhw/features.py:52-66): cats = floor(1 + (ts - thresh)/(thresh - seas)) in float64 with seas / thresh
+ * re-expanded by row_of_t_host; k = 0..3 for cats == 1, == 2, == 3, >= 4.  A step inside a joined gap
+ * (below the threshold, or NaN) is in an event and in none of the four, so column 4 >= the sum of 0..3.
+ * negate != 0: the series is negated first (cold spells).
+ * region_dev[C] int32 in [-1, R): -1 = the cell counts nowhere.  wq_dev[C] int64, 0 <= wq <= 2^31 (not
+ * checked: it lives on the device): with C < 2^32 no sum can overflow.  All sums are integer sums: the
+ * result is exact and does not depend on the order of the adds, the slabs or the launch geometry.
+ * R >= 1; R above XMHW_COVERAGE_MAX_REGIONS: XMHW_ERR_UNSUPPORTED.  Asynchronous on `stream`; nothing is
+ * launched for C == 0.  Scratch: one in-event bit per sample, in the stream's scratch buffer.           */
+#define XMHW_COVERAGE_MAX_REGIONS 1024
+#define XMHW_COVERAGE_STATES 5
+int xmhw_coverage_accumulate_f32(const float *ts_dev, int64_t T, int64_t C, int64_t ld,
+                                 const double *seas_dev, const double *thresh_dev, int64_t ldc,
+                                 const int32_t *row_of_t_host, int32_t negate, const uint64_t *bits_dev,
+                                 int64_t ldb, int32_t min_duration, int32_t join_gaps, int32_t max_gap,
+                                 const int64_t *wq_dev, const int32_t *region_dev, int32_t R,
+                                 int64_t *cells_dev, int64_t *area_q_dev, void *stream);
+int xmhw_coverage_accumulate_f64(const double *ts_dev, int64_t T, int64_t C, int64_t ld,
+                                 const double *seas_dev, const double *thresh_dev, int64_t ldc,
+                                 const int32_t *row_of_t_host, int32_t negate, const uint64_t *bits_dev,
+                                 int64_t ldb, int32_t min_duration, int32_t join_gaps, int32_t max_gap,
+                                 const int64_t *wq_dev, const int32_t *region_dev, int32_t R,
+                                 int64_t *cells_dev, int64_t *area_q_dev, void *stream);
+
 /* ---- the sharded path: cells split across the GPUs of a node, ONE gather at the end ------- *
  * Replaces the reference's collect, dask.compute(climls) + xr.concat(dim='cell')
  * (xmhw/xmhw.py:197, :210-211).  Cells are independent (xmhw/xmhw.py:184-196), so rank r runs the

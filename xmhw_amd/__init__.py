@@ -15,10 +15,12 @@ from .device import release_device_cache
 from .stats import block_average, BlockDataset
 from .rank import mhw_rank
 from .trend import mean_trend, TrendDataset
+from .coverage import mhw_coverage, CoverageDataset
 from .ingest import open_series, threshold_file
 
 __all__ = ["threshold", "threshold_array", "GridSeries", "ClimDataset", "XmhwException",
            "add_doy", "get_calendar", "land_check", "detect", "threshold_detect", "EventDataset", "InterDataset",
-           "climatology_series", "release_device_cache", "block_average", "BlockDataset", "mhw_rank", "mean_trend", "TrendDataset", "open_series",
+           "climatology_series", "release_device_cache", "block_average", "BlockDataset", "mhw_rank", "mean_trend", "TrendDataset", "mhw_coverage",
+           "CoverageDataset", "open_series",
            "threshold_file"]
 __version__ = "0.1.0"

@@ -878,6 +878,39 @@ int exceed_bits(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* th
 }
 
 template <typename T>
+int coverage_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* seas, const double* thresh,
+                        int64_t ldc, const int32_t* row_of_t, int32_t negate, const uint64_t* bits, int64_t ldb,
+                        int32_t min_duration, int32_t join_gaps, int32_t max_gap, const int64_t* wq,
+                        const int32_t* region, int32_t R, int64_t* cells, int64_t* area_q, void* stream) {
+    if (Tn <= 0 || C < 0 || ld < C || ldc < C || ldb < C) return fail(XMHW_ERR_INVALID, "bad T/C/ld/ldc/ldb");
+    if (Tn >= (int64_t{1} << 31)) return fail(XMHW_ERR_INVALID, "T too large");
+    if (min_duration < 1 || max_gap < 0) return fail(XMHW_ERR_INVALID, "bad minDuration/maxGap");
+    if (R < 1) return fail(XMHW_ERR_INVALID, "R must be >= 1");
+    if (R > xmhw::kCoverageMaxRegions)
+        return fail(XMHW_ERR_UNSUPPORTED, "coverage: R above the cap of " + std::to_string(xmhw::kCoverageMaxRegions) + " regions");
+    if (C == 0) return XMHW_OK;
+    if (!ts || !seas || !thresh || !row_of_t || !bits || !wq || !region || !cells || !area_q)
+        return fail(XMHW_ERR_INVALID, "NULL buffer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipError_t e = hipSuccess;
+    const RowsRef rows = cached_rows(row_of_t, Tn, &e);
+    if (!rows) return hip_fail(e, "row table upload");
+    // the per-day in-event bitmap lives in this stream's scratch buffer: (T + 63) / 64 words per cell
+    const int64_t W = (Tn + 63) / 64;
+    void* sp = nullptr;
+    ScratchRef scratch_keep;
+    e = scratch_get(st, sizeof(uint64_t) * static_cast<size_t>(W) * static_cast<size_t>(C), &sp, &scratch_keep);
+    if (e != hipSuccess) return hip_fail(e, "scratch allocation");
+    uint64_t* inev = static_cast<uint64_t*>(sp);
+    e = xmhw::launch_event_day_bits(bits, Tn, C, ldb, min_duration, join_gaps, max_gap, inev, C, st);
+    if (e != hipSuccess) return hip_fail(e, "event_day_bits launch");
+    e = xmhw::launch_coverage_accumulate<T>(ts, Tn, C, ld, seas, thresh, ldc, rows->d_rows, negate, inev, C, wq, region, R,
+                                     cells, area_q, st);
+    if (e != hipSuccess) return hip_fail(e, "coverage_accumulate launch");
+    return XMHW_OK;
+}
+
+template <typename T>
 int event_stats_sparse(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* seas, const double* thresh,
                        int64_t ldc, const int32_t* row_of_t, int32_t negate, int64_t n_events, double* table,
                        void* stream) {
@@ -1760,6 +1793,23 @@ int xmhw_block_trend_theil_sen(const double* y, int32_t nstat, int32_t nb, int64
     hipError_t e = xmhw::launch_trend_theil_sen(y, nstat, nb, C, ld, x, out, ldo, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hip_fail(e, "trend_theil_sen launch");
     return XMHW_OK;
+}
+
+int xmhw_coverage_accumulate_f32(const float* ts, int64_t T, int64_t C, int64_t ld, const double* seas,
+                                 const double* thresh, int64_t ldc, const int32_t* row_of_t, int32_t negate,
+                                 const uint64_t* bits, int64_t ldb, int32_t min_duration, int32_t join_gaps,
+                                 int32_t max_gap, const int64_t* wq, const int32_t* region, int32_t R, int64_t* cells,
+                                 int64_t* area_q, void* stream) {
+    return coverage_accumulate<float>(ts, T, C, ld, seas, thresh, ldc, row_of_t, negate, bits, ldb, min_duration,
+                                      join_gaps, max_gap, wq, region, R, cells, area_q, stream);
+}
+int xmhw_coverage_accumulate_f64(const double* ts, int64_t T, int64_t C, int64_t ld, const double* seas,
+                                 const double* thresh, int64_t ldc, const int32_t* row_of_t, int32_t negate,
+                                 const uint64_t* bits, int64_t ldb, int32_t min_duration, int32_t join_gaps,
+                                 int32_t max_gap, const int64_t* wq, const int32_t* region, int32_t R, int64_t* cells,
+                                 int64_t* area_q, void* stream) {
+    return coverage_accumulate<double>(ts, T, C, ld, seas, thresh, ldc, row_of_t, negate, bits, ldb, min_duration,
+                                       join_gaps, max_gap, wq, region, R, cells, area_q, stream);
 }
 
 int xmhw_synth_sst_f32(float* ts, int64_t T, int64_t C, int64_t ld, int64_t cell0, uint64_t seed,

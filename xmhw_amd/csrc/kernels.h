@@ -234,6 +234,20 @@ hipError_t launch_trend_ols(const double* y, int32_t nstat, int32_t nb, int64_t 
 hipError_t launch_trend_theil_sen(const double* y, int32_t nstat, int32_t nb, int64_t C, int64_t ld, const double* x,
                                   double* out, int64_t ldo, hipStream_t stream);
 
+// mhw_coverage() (kernels_coverage.hip): event_day_bits turns the exceedance words of exceed_bits into the per-day
+// in-event bitmap inev[w][ldi] (steps first..last of every filtered, gap-joined event; zeroed here first);
+// coverage_accumulate ADDS, for every step t and region r < R, the number of in-event cells per state (moderate, strong,
+// severe, extreme, event) to cells[t][r][5] and the sum of their weights wq[c] to area_q[t][r][5].  region[c] in
+// [-1, R), -1 = the cell counts nowhere; R <= kCoverageMaxRegions.  row_of_t is a DEVICE array here.
+constexpr int kCoverageMaxRegions = 1024;
+hipError_t launch_event_day_bits(const uint64_t* bits, int64_t Tn, int64_t C, int64_t ldb, int32_t min_duration,
+                                 int32_t join_gaps, int32_t max_gap, uint64_t* inev, int64_t ldi, hipStream_t stream);
+template <typename T>
+hipError_t launch_coverage_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* seas,
+                                      const double* thresh, int64_t ldc, const int32_t* row_of_t, int32_t negate,
+                                      const uint64_t* inev, int64_t ldi, const int64_t* wq, const int32_t* region,
+                                      int32_t R, int64_t* cells, int64_t* area_q, hipStream_t stream);
+
 // file bytes -> samples (kernels_ingest.hip): raw_type = item size of the stored type (2 int16, 4 float32,
 // 8 float64), swap = the file is big-endian, optional scale/offset (CF packing) and fill value -> NaN
 hipError_t launch_encode_i16(const float* in, int64_t rows, int64_t cols, int64_t ld_in, int16_t* out, int64_t ld_out,

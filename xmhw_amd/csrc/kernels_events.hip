@@ -17,6 +17,7 @@
 //                      neighbours are read.
 #include "device_common.h"
 #include "event_acc.h"
+#include "event_walk.h"
 #include "kernels.h"
 
 namespace xmhw {
@@ -159,46 +160,21 @@ template hipError_t launch_exceed_bits_tiled<double, double, 32>(const double*, 
                                                                  int32_t, uint64_t*, int64_t, hipStream_t);
 
 // ---------------------------------------------------------------------------
-// State of mhw_filter() + join_gaps() while walking the runs of one cell.
-// A qualified run [s, e] (length test of identify.py:445-449 with the fillna(0) quirk: a run that
-// begins at step 0 has p = 0, label 1, and loses its first step) either extends the pending
-// event (gap to the previous qualified run <= maxGap) or closes it and opens a new one.
+// events_from_bits: the walk itself is event_walk.h (shared with the coverage kernels); here a finished
+// event goes to its row of the table (fill mode) or is only counted.
 // ---------------------------------------------------------------------------
-struct EventWalk {
-    int64_t count = 0;
-    bool have = false;            // a pending (not yet emitted) event
-    int64_t first = 0, last = 0;  // its label (= first labelled step) and end step
+struct TableSink {
     double* rows = nullptr;       // fill mode: the cell's slice of the table
     int64_t nmax = 0;
     int64_t cell = 0;
-
-    __device__ __forceinline__ void emit() {
-        if (rows && count < nmax) {
-            double* r = rows + count * kEventColumns;
+    __device__ __forceinline__ void operator()(int64_t index, int64_t first, int64_t last) const {
+        if (rows && index < nmax) {
+            double* r = rows + index * kEventColumns;
             r[0] = static_cast<double>(first);
             r[1] = static_cast<double>(cell);
             r[3] = static_cast<double>(first);
             r[4] = static_cast<double>(last);
         }
-        ++count;
-    }
-    __device__ __forceinline__ void run(int64_t s, int64_t e, int32_t min_duration, int32_t join_gaps,
-                                        int32_t max_gap) {
-        const int64_t p = s > 0 ? s - 1 : 0;
-        if (e - p < min_duration) return;
-        const int64_t S = p + 1;
-        if (have && join_gaps && S - last <= max_gap + 1) {
-            last = e;
-            return;
-        }
-        if (have) emit();
-        have = true;
-        first = S;
-        last = e;
-    }
-    __device__ __forceinline__ void finish() {
-        if (have) emit();
-        have = false;
     }
 };
 
@@ -208,61 +184,13 @@ __global__ __launch_bounds__(256) void events_from_bits(const uint64_t* __restri
                                                         int32_t* __restrict__ nevents, double* __restrict__ table) {
     const int64_t c = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    const int64_t W = (Tn + 63) / 64;
-    EventWalk ew;
-    ew.cell = c;
+    EventWalk<TableSink> ew;
+    ew.sink.cell = c;
     if (offsets) {
-        ew.rows = table + offsets[c] * kEventColumns;
-        ew.nmax = offsets[c + 1] - offsets[c];
+        ew.sink.rows = table + offsets[c] * kEventColumns;
+        ew.sink.nmax = offsets[c + 1] - offsets[c];
     }
-    bool in_run = false;
-    int64_t s = 0;
-    // Morphological opening by min_duration before the walk: runs shorter than min_duration can
-    // never qualify (identify.py:445-449), and white-noise exceedances are mostly such runs.
-    // eroded[t] = AND_{j<m} x[t+j] (needs the next word), opened[t] = OR_{j<m} eroded[t-j] (needs the
-    // previous eroded word): every run of >= m ones survives unchanged, every shorter run vanishes.
-    const int m = min_duration <= 64 ? min_duration : 1;
-    constexpr int U = 4;
-    uint64_t cur = bits[c];
-    uint64_t er_prev = 0;
-    for (int64_t w0 = 0; w0 < W; w0 += U) {
-        uint64_t ws[U + 1];
-        ws[0] = cur;
-#pragma unroll
-        for (int u = 1; u <= U; ++u) ws[u] = w0 + u < W ? bits[(w0 + u) * ldb + c] : 0;
-        cur = ws[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (w0 + u >= W) break;
-            const int64_t base = (w0 + u) * 64;
-            uint64_t er = ws[u];
-            for (int j = 1; j < m; ++j) er &= (ws[u] >> j) | (ws[u + 1] << (64 - j));
-            uint64_t x = er;
-            for (int j = 1; j < m; ++j) x |= (er << j) | (er_prev >> (64 - j));
-            er_prev = er;
-            int pos = 0;
-            while (pos < 64) {
-                const uint64_t rest = x >> pos;
-                if (in_run) {
-                    const uint64_t z = ~rest;                       // zeros of the remaining bits
-                    if (z == 0) break;                              // pos == 0, all ones: continues
-                    const int k = __builtin_ctzll(z);               // ones from pos on
-                    if (pos + k >= 64) break;                       // the run continues into the next word
-                    ew.run(s, base + pos + k - 1, min_duration, join_gaps, max_gap);
-                    in_run = false;
-                    pos += k;
-                } else {
-                    if (rest == 0) break;
-                    const int k = __builtin_ctzll(rest);
-                    s = base + pos + k;
-                    in_run = true;
-                    pos += k;
-                }
-            }
-        }
-    }
-    if (in_run) ew.run(s, Tn - 1, min_duration, join_gaps, max_gap);   // bits beyond T-1 are zero
-    ew.finish();
+    walk_exceed_bits(bits, c, Tn, ldb, min_duration, join_gaps, max_gap, ew);
     if (nevents) nevents[c] = static_cast<int32_t>(ew.count);
 }
 

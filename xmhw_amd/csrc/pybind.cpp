@@ -527,6 +527,33 @@ PYBIND11_MODULE(_xmhw_hip, m) {
                               static_cast<double*>(vp(rp)), ld_out, vp(stream)));
     }, py::arg("table"), py::arg("ld_table"), py::arg("offsets"), py::arg("C"), py::arg("columns"), py::arg("n_years"),
        py::arg("rank"), py::arg("rp"), py::arg("ld_out"), py::arg("stream") = 0);
+    m.attr("COVERAGE_MAX_REGIONS") = XMHW_COVERAGE_MAX_REGIONS;
+    m.attr("COVERAGE_STATES") = XMHW_COVERAGE_STATES;
+    m.def("coverage_accumulate", [](uintptr_t ts, int itemsize, int64_t T, int64_t C, int64_t ld, uintptr_t seas,
+                                    uintptr_t thresh, int64_t ldc, i32arr row_of_t, int negate, uintptr_t bits, int64_t ldb,
+                                    int min_duration, int join_gaps, int max_gap, uintptr_t wq, uintptr_t region, int32_t R,
+                                    uintptr_t cells, uintptr_t area_q, uintptr_t stream) {
+        if (row_of_t.size() != T) throw InvalidError("row_of_t length must equal T");
+        py::gil_scoped_release r;
+        int rc = -1;
+        if (itemsize == 4)
+            rc = xmhw_coverage_accumulate_f32(static_cast<const float*>(vp(ts)), T, C, ld, static_cast<const double*>(vp(seas)),
+                                              static_cast<const double*>(vp(thresh)), ldc, row_of_t.data(), negate,
+                                              static_cast<const uint64_t*>(vp(bits)), ldb, min_duration, join_gaps, max_gap,
+                                              static_cast<const int64_t*>(vp(wq)), static_cast<const int32_t*>(vp(region)), R,
+                                              static_cast<int64_t*>(vp(cells)), static_cast<int64_t*>(vp(area_q)), vp(stream));
+        else if (itemsize == 8)
+            rc = xmhw_coverage_accumulate_f64(static_cast<const double*>(vp(ts)), T, C, ld, static_cast<const double*>(vp(seas)),
+                                              static_cast<const double*>(vp(thresh)), ldc, row_of_t.data(), negate,
+                                              static_cast<const uint64_t*>(vp(bits)), ldb, min_duration, join_gaps, max_gap,
+                                              static_cast<const int64_t*>(vp(wq)), static_cast<const int32_t*>(vp(region)), R,
+                                              static_cast<int64_t*>(vp(cells)), static_cast<int64_t*>(vp(area_q)), vp(stream));
+        if (rc == -1) throw InvalidError("itemsize must be 4 or 8");
+        check(rc);
+    }, py::arg("ts"), py::arg("itemsize"), py::arg("T"), py::arg("C"), py::arg("ld"), py::arg("seas"), py::arg("thresh"),
+       py::arg("ldc"), py::arg("row_of_t"), py::arg("negate"), py::arg("bits"), py::arg("ldb"), py::arg("min_duration"),
+       py::arg("join_gaps"), py::arg("max_gap"), py::arg("wq"), py::arg("region"), py::arg("R"), py::arg("cells"),
+       py::arg("area_q"), py::arg("stream") = 0);
     m.def("block_trend_ols", [](uintptr_t y, int32_t nstat, int32_t nb, int64_t C, int64_t ld, uintptr_t x, uintptr_t tcrit,
                                 uintptr_t out, int64_t ldo, uintptr_t stream) {
         check(xmhw_block_trend_ols(static_cast<const double*>(vp(y)), nstat, nb, C, ld, static_cast<const double*>(vp(x)),

@@ -239,6 +239,17 @@ def detect_cells(ts, seas, thresh, doy, doys, minDuration=5, joinGaps=True, maxG
     return dict(table=table, offsets=offsets, inter=inter)
 
 
+def _rows_as_they_are(a):
+    # threshold() hands its climatologies over as row-pitched views when an all-land band was cut
+    # from the grid (landmask.compress_axis): the pitched upload takes them as they are; only other
+    # layouts / dtypes are copied (2 x 2.5 GB on the host for a global grid otherwise)
+    a = np.asarray(a)
+    if a.ndim == 2 and a.dtype == np.float64 and a.dtype.isnative and (a.shape[1] <= 1 or a.strides[1] == 8) \
+            and a.strides[0] >= 8 * a.shape[1]:
+        return a
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
 def detect_grid(stacked, anynans, seas, thresh, doy, doys, minDuration=5, joinGaps=True, maxGap=2, coldSpells=False,
                 intermediate=False, max_batch_bytes=None, clim_stacked=False, columns=None, exchange=None,
                 resident=None, pad=None):
@@ -316,18 +327,8 @@ def detect_grid(stacked, anynans, seas, thresh, doy, doys, minDuration=5, joinGa
             return path(host_compact(np.asarray(seas, dtype=np.float64))[0],
                         host_compact(np.asarray(thresh, dtype=np.float64))[0])
         return path(np.asarray(seas, dtype=np.float64), np.asarray(thresh, dtype=np.float64))
-    def rows_as_they_are(a):
-        # threshold() hands its climatologies over as row-pitched views when an all-land band was cut
-        # from the grid (landmask.compress_axis): the pitched upload takes them as they are; only other
-        # layouts / dtypes are copied (2 x 2.5 GB on the host for a global grid otherwise)
-        a = np.asarray(a)
-        if a.ndim == 2 and a.dtype == np.float64 and a.dtype.isnative and (a.shape[1] <= 1 or a.strides[1] == 8) \
-                and a.strides[0] >= 8 * a.shape[1]:
-            return a
-        return np.ascontiguousarray(a, dtype=np.float64)
-
-    seas = rows_as_they_are(seas)
-    thresh = rows_as_they_are(thresh)
+    seas = _rows_as_they_are(seas)
+    thresh = _rows_as_they_are(thresh)
     if seas.ndim != 2 or thresh.ndim != 2 or seas.shape[0] != thresh.shape[0]:
         raise XmhwException("seas and thresh must be (D, cells) arrays")
     D = thresh.shape[0]
