@@ -562,6 +562,37 @@ int xmhw_coverage_accumulate_f64(const double *ts_dev, int64_t T, int64_t C, int
                                  const int64_t *wq_dev, const int32_t *region_dev, int32_t R,
                                  int64_t *cells_dev, int64_t *area_q_dev, void *stream);
 
+/* ---- mhw_objects(): the events of detect() grouped into objects connected in space and time -------- *
+ * A table row r is a run of days start_dev[r]..end_dev[r] (inclusive positions along the time axis, int32)
+ * in one ocean cell; the rows of cell c are offsets_dev[c]..offsets_dev[c+1] (offsets_dev[C] == n), in time
+ * order and at least one day apart (not checked: they live on the device).  nbr_dev[C][K] int32 lists the
+ * spatial neighbours of every cell as cell numbers, -1 = none (land, outside the grid); the relation must be
+ * symmetric and a cell is not its own neighbour.  Rows a, b of DIFFERENT cells are linked iff one cell is a
+ * neighbour of the other and start_a <= end_b + gap and start_b <= end_a + gap (gap 0: the runs share a day,
+ * 6-connectivity of the voxels; gap 1: they may also be a day apart, 26-connectivity with K = 8).
+ *
+ * xmhw_event_objects writes cell_of_row_dev[n] (the cell of every row) and root_dev[n]: the SMALLEST row of
+ * the row's connected component, whatever the schedule (a lock-free union-find; no wave waits for another).
+ * n or C of 2^31 and more: XMHW_ERR_UNSUPPORTED.  Nothing is launched for n == 0.
+ *
+ * xmhw_object_reduce reduces the rows into per-object slots: slot_dev[r] in [0, n_slots) is equal for the rows
+ * of one object (root_dev with n_slots = n serves; a row whose slot is outside the range is left out).  It
+ * initialises and fills, for every slot: n_events (rows), n_cells (distinct cells), time_start = min start,
+ * time_end = max end, cell_days = sum (end - start + 1), area_days_q = sum wq_dev[cell] * (end - start + 1)
+ * (wq_dev[C] int64 >= 0; the caller sizes it so that no sum passes 2^63), intensity_max = the largest
+ * imax_dev[r] compared as float64 with -0.0 counted as 0.0, NaN rows ignored (NaN if there is none), and
+ * peak_row = the smallest row that attains it (-1 if none).  A slot without rows keeps 0, 0, 2^31-1, -1, 0,
+ * 0, NaN, -1.  Only integer sums, minima and maxima: the result is exact and the same from run to run.
+ * Both are asynchronous on `stream`.                                                                        */
+int xmhw_event_objects(const int32_t *start_dev, const int32_t *end_dev, int64_t n, const int64_t *offsets_dev,
+                       int64_t C, const int32_t *nbr_dev, int32_t K, int32_t gap, int32_t *cell_of_row_dev,
+                       int32_t *root_dev, void *stream);
+int xmhw_object_reduce(const int32_t *start_dev, const int32_t *end_dev, const double *imax_dev, int64_t n,
+                       const int32_t *cell_of_row_dev, const int64_t *offsets_dev, const int64_t *wq_dev,
+                       const int32_t *slot_dev, int64_t n_slots, int32_t *n_events_dev, int32_t *n_cells_dev,
+                       int32_t *time_start_dev, int32_t *time_end_dev, int64_t *cell_days_dev,
+                       int64_t *area_days_q_dev, double *intensity_max_dev, int32_t *peak_row_dev, void *stream);
+
 /* ---- the sharded path: cells split across the GPUs of a node, ONE gather at the end ------- *
  * Replaces the reference's collect, dask.compute(climls) + xr.concat(dim='cell')
  * (xmhw/xmhw.py:197, :210-211).  Cells are independent (xmhw/xmhw.py:184-196), so rank r runs the

@@ -16,11 +16,12 @@ from .stats import block_average, BlockDataset
 from .rank import mhw_rank
 from .trend import mean_trend, TrendDataset
 from .coverage import mhw_coverage, CoverageDataset
+from .objects import mhw_objects, ObjectDataset
 from .ingest import open_series, threshold_file
 
 __all__ = ["threshold", "threshold_array", "GridSeries", "ClimDataset", "XmhwException",
            "add_doy", "get_calendar", "land_check", "detect", "threshold_detect", "EventDataset", "InterDataset",
            "climatology_series", "release_device_cache", "block_average", "BlockDataset", "mhw_rank", "mean_trend", "TrendDataset", "mhw_coverage",
-           "CoverageDataset", "open_series",
+           "CoverageDataset", "mhw_objects", "ObjectDataset", "open_series",
            "threshold_file"]
 __version__ = "0.1.0"

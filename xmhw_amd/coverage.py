@@ -37,8 +37,8 @@ WEIGHT_ONE = 1 << 31            # the quantised value of the largest weight
 MAX_REGIONS = 1024              # XMHW_COVERAGE_MAX_REGIONS (include/xmhw_amd.h)
 
 
-def quantise_weights(w):
-    """(wq int64, weight_unit): wq = rint(w / w.max() * 2**31); w finite, >= 0, not all zero."""
+def quantise_weights(w, bits=31):
+    """(wq int64, weight_unit): wq = rint(w / w.max() * 2**bits); w finite, >= 0, not all zero."""
     w = np.asarray(w, dtype=np.float64)
     if w.size == 0 or not np.isfinite(w).all():
         raise XmhwException("weights should be finite numbers")
@@ -47,7 +47,8 @@ def quantise_weights(w):
     wmax = float(w.max())
     if not wmax > 0:
         raise XmhwException("weights are all zero")
-    return np.rint(w / wmax * WEIGHT_ONE).astype(np.int64), wmax / WEIGHT_ONE
+    one = 1 << int(bits)
+    return np.rint(w / wmax * one).astype(np.int64), wmax / one
 
 
 def _check_cells(C, wq, region, R):

@@ -1812,6 +1812,37 @@ int xmhw_coverage_accumulate_f64(const double* ts, int64_t T, int64_t C, int64_t
                                        join_gaps, max_gap, wq, region, R, cells, area_q, stream);
 }
 
+int xmhw_event_objects(const int32_t* start, const int32_t* end, int64_t n, const int64_t* offsets, int64_t C,
+                       const int32_t* nbr, int32_t K, int32_t gap, int32_t* cell_of_row, int32_t* root, void* stream) {
+    if (n < 0 || C < 0) return fail(XMHW_ERR_INVALID, "bad n/C");
+    if (K < 1 || gap < 0) return fail(XMHW_ERR_INVALID, "K must be >= 1 and gap >= 0");
+    if (n > 0x7FFFFFFFll || C > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "event_objects: 2^31 rows or cells and more");
+    if (n == 0) return XMHW_OK;
+    if (C == 0) return fail(XMHW_ERR_INVALID, "rows without cells");
+    if (!start || !end || !offsets || !nbr || !cell_of_row || !root) return fail(XMHW_ERR_INVALID, "NULL buffer");
+    hipError_t e = xmhw::launch_event_objects(start, end, n, offsets, C, nbr, K, gap, cell_of_row, root,
+                                              static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "event_objects launch");
+    return XMHW_OK;
+}
+
+int xmhw_object_reduce(const int32_t* start, const int32_t* end, const double* imax, int64_t n, const int32_t* cell_of_row,
+                       const int64_t* offsets, const int64_t* wq, const int32_t* slot, int64_t n_slots, int32_t* n_events,
+                       int32_t* n_cells, int32_t* time_start, int32_t* time_end, int64_t* cell_days, int64_t* area_days_q,
+                       double* intensity_max, int32_t* peak_row, void* stream) {
+    if (n < 0 || n_slots < 0) return fail(XMHW_ERR_INVALID, "bad n/n_slots");
+    if (n > 0x7FFFFFFFll || n_slots > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "object_reduce: 2^31 rows or slots and more");
+    if (n_slots == 0) return XMHW_OK;
+    if (!n_events || !n_cells || !time_start || !time_end || !cell_days || !area_days_q || !intensity_max || !peak_row)
+        return fail(XMHW_ERR_INVALID, "NULL output buffer");
+    if (n > 0 && (!start || !end || !imax || !cell_of_row || !offsets || !wq || !slot)) return fail(XMHW_ERR_INVALID, "NULL buffer");
+    hipError_t e = xmhw::launch_object_reduce(start, end, imax, n, cell_of_row, offsets, wq, slot, n_slots, n_events, n_cells,
+                                              time_start, time_end, cell_days, area_days_q, intensity_max, peak_row,
+                                              static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "object_reduce launch");
+    return XMHW_OK;
+}
+
 int xmhw_synth_sst_f32(float* ts, int64_t T, int64_t C, int64_t ld, int64_t cell0, uint64_t seed,
                        double nan_frac, void* stream) {
     if (C < 0 || ld < C || T <= 0) return fail(XMHW_ERR_INVALID, "bad T/C/ld");

@@ -248,6 +248,21 @@ hipError_t launch_coverage_accumulate(const T* ts, int64_t Tn, int64_t C, int64_
                                       const uint64_t* inev, int64_t ldi, const int64_t* wq, const int32_t* region,
                                       int32_t R, int64_t* cells, int64_t* area_q, hipStream_t stream);
 
+// mhw_objects() (kernels_objects.hip): launch_event_objects groups the table rows (runs of days start..end in one cell,
+// rows of cell c = offsets[c]..offsets[c + 1], in time order) into connected components: rows of DIFFERENT cells are
+// linked iff one cell is among the other's K neighbours nbr[c][K] (-1: none) and start_a <= end_b + gap and start_b <=
+// end_a + gap.  Writes cell_of_row[n] and root[n] = the smallest row of the row's component.  launch_object_reduce
+// reduces the rows into the per-object slots slot[r] in [0, n_slots) (root itself is a valid slot array); it initialises
+// its outputs.  intensity_max doubles as the 64-bit key accumulator until the last kernel.
+hipError_t launch_event_objects(const int32_t* start, const int32_t* end, int64_t n, const int64_t* offsets, int64_t C,
+                                const int32_t* nbr, int32_t K, int32_t gap, int32_t* cell_of_row, int32_t* root,
+                                hipStream_t stream);
+hipError_t launch_object_reduce(const int32_t* start, const int32_t* end, const double* imax, int64_t n,
+                                const int32_t* cell_of_row, const int64_t* offsets, const int64_t* wq,
+                                const int32_t* slot, int64_t n_slots, int32_t* n_events, int32_t* n_cells,
+                                int32_t* time_start, int32_t* time_end, int64_t* cell_days, int64_t* area_days_q,
+                                double* intensity_max, int32_t* peak_row, hipStream_t stream);
+
 // file bytes -> samples (kernels_ingest.hip): raw_type = item size of the stored type (2 int16, 4 float32,
 // 8 float64), swap = the file is big-endian, optional scale/offset (CF packing) and fill value -> NaN
 hipError_t launch_encode_i16(const float* in, int64_t rows, int64_t cols, int64_t ld_in, int16_t* out, int64_t ld_out,

@@ -554,6 +554,29 @@ PYBIND11_MODULE(_xmhw_hip, m) {
        py::arg("ldc"), py::arg("row_of_t"), py::arg("negate"), py::arg("bits"), py::arg("ldb"), py::arg("min_duration"),
        py::arg("join_gaps"), py::arg("max_gap"), py::arg("wq"), py::arg("region"), py::arg("R"), py::arg("cells"),
        py::arg("area_q"), py::arg("stream") = 0);
+    m.def("event_objects", [](uintptr_t start, uintptr_t end, int64_t n, uintptr_t offsets, int64_t C, uintptr_t nbr, int32_t K,
+                              int32_t gap, uintptr_t cell_of_row, uintptr_t root, uintptr_t stream) {
+        check(xmhw_event_objects(static_cast<const int32_t*>(vp(start)), static_cast<const int32_t*>(vp(end)), n,
+                                 static_cast<const int64_t*>(vp(offsets)), C, static_cast<const int32_t*>(vp(nbr)), K, gap,
+                                 static_cast<int32_t*>(vp(cell_of_row)), static_cast<int32_t*>(vp(root)), vp(stream)));
+    }, py::arg("start"), py::arg("end"), py::arg("n"), py::arg("offsets"), py::arg("C"), py::arg("nbr"), py::arg("K"),
+       py::arg("gap"), py::arg("cell_of_row"), py::arg("root"), py::arg("stream") = 0);
+    m.def("object_reduce", [](uintptr_t start, uintptr_t end, uintptr_t imax, int64_t n, uintptr_t cell_of_row,
+                              uintptr_t offsets, uintptr_t wq, uintptr_t slot, int64_t n_slots, uintptr_t n_events,
+                              uintptr_t n_cells, uintptr_t time_start, uintptr_t time_end, uintptr_t cell_days,
+                              uintptr_t area_days_q, uintptr_t intensity_max, uintptr_t peak_row, uintptr_t stream) {
+        check(xmhw_object_reduce(static_cast<const int32_t*>(vp(start)), static_cast<const int32_t*>(vp(end)),
+                                 static_cast<const double*>(vp(imax)), n, static_cast<const int32_t*>(vp(cell_of_row)),
+                                 static_cast<const int64_t*>(vp(offsets)), static_cast<const int64_t*>(vp(wq)),
+                                 static_cast<const int32_t*>(vp(slot)), n_slots, static_cast<int32_t*>(vp(n_events)),
+                                 static_cast<int32_t*>(vp(n_cells)), static_cast<int32_t*>(vp(time_start)),
+                                 static_cast<int32_t*>(vp(time_end)), static_cast<int64_t*>(vp(cell_days)),
+                                 static_cast<int64_t*>(vp(area_days_q)), static_cast<double*>(vp(intensity_max)),
+                                 static_cast<int32_t*>(vp(peak_row)), vp(stream)));
+    }, py::arg("start"), py::arg("end"), py::arg("imax"), py::arg("n"), py::arg("cell_of_row"), py::arg("offsets"),
+       py::arg("wq"), py::arg("slot"), py::arg("n_slots"), py::arg("n_events"), py::arg("n_cells"), py::arg("time_start"),
+       py::arg("time_end"), py::arg("cell_days"), py::arg("area_days_q"), py::arg("intensity_max"), py::arg("peak_row"),
+       py::arg("stream") = 0);
     m.def("block_trend_ols", [](uintptr_t y, int32_t nstat, int32_t nb, int64_t C, int64_t ld, uintptr_t x, uintptr_t tcrit,
                                 uintptr_t out, int64_t ldo, uintptr_t stream) {
         check(xmhw_block_trend_ols(static_cast<const double*>(vp(y)), nstat, nb, C, ld, static_cast<const double*>(vp(x)),
