@@ -529,6 +529,43 @@ int xmhw_block_trend_ols(const double *y_dev, int32_t nstat, int32_t nb, int64_t
 int xmhw_block_trend_theil_sen(const double *y_dev, int32_t nstat, int32_t nb, int64_t C, int64_t ld,
                                const double *x_dev, double *out_dev, int64_t ldo, void *stream);
 
+/* ---- detrend(): per-cell trend fit and removal on the resident series (not in xmhw / marineHeatWaves) -- *
+ * ts_dev (T, C) float32 / float64, time-major, cells contiguous (ld >= C).  basis_dev[T][P] float64: the
+ * design matrix, one row per step, shared by all cells (xmhw_amd/detrend.py builds it: powers of the time
+ * in decades since a reference, the constant, annual harmonics).  weight_dev[T] uint8 in {0, 1}: the steps
+ * of the fit period (NULL: all of them).  A sample CONTRIBUTES when its step has weight 1 and it is not NaN.
+ *
+ * xmhw_series_fit_*: coef_dev[k][ldc] (ldc >= C), k < P: the least-squares solution over the contributing
+ * samples of every cell -- normal equations G = sum b b', r = sum b y accumulated in float64 in time order
+ * (r in batches of eight steps that join the running sum by a compensated add, the shared Gram matrix by a
+ * compensated sum), Cholesky with the columns in the order of the basis, two triangular solves; no FMA.  (The
+ * Gram matrix of the steps with weight 1 is summed once per call; a cell takes it less the outer products of
+ * its own missing steps, or -- when more of its samples are missing than contribute -- sums its own.)  A cell
+ * FAILS, and all its coefficients are NaN, when it has fewer than max(min_valid, P) contributing samples,
+ * when a contributing sample is +-Inf, or when a pivot d_j = G_jj - sum_k L_jk^2 is not > 1e-6 * G_jj (NaN
+ * and negative pivots included).  nvalid_dev[C] (may be NULL): the contributing samples of every cell.
+ * A cell's result depends on its own samples only -- not on C, ld or the launch -- and is the same from run
+ * to run.  1 <= P <= XMHW_FIT_MAX_TERMS, above: XMHW_ERR_UNSUPPORTED and nothing is written.
+ *
+ * xmhw_series_remove_*: in place, for every step, y' = y - sum_{k<R} coef[k] basis[t][k]: the sum in float64
+ * in column order, one subtraction in float64, one rounding to the sample type.  1 <= R <= P: the leading
+ * columns are removed, the others were fitted and stay.  NaN stays NaN; a failed cell becomes NaN everywhere.
+ *
+ * Both are asynchronous on `stream`; nothing is launched for C == 0 or T == 0; elements at columns >= C of
+ * ts_dev, coef_dev and nvalid_dev are never touched.  Scratch: 512 + C bytes of the stream's scratch buffer.
+ * xmhw_series_remove_* takes at most 65535 * 64 steps (above: XMHW_ERR_UNSUPPORTED).                          */
+#define XMHW_FIT_MAX_TERMS 10
+int xmhw_series_fit_f32(const float *ts_dev, int64_t T, int64_t C, int64_t ld, const double *basis_dev,
+                        int32_t P, const uint8_t *weight_dev, int32_t min_valid, double *coef_dev,
+                        int64_t ldc, int32_t *nvalid_dev, void *stream);
+int xmhw_series_fit_f64(const double *ts_dev, int64_t T, int64_t C, int64_t ld, const double *basis_dev,
+                        int32_t P, const uint8_t *weight_dev, int32_t min_valid, double *coef_dev,
+                        int64_t ldc, int32_t *nvalid_dev, void *stream);
+int xmhw_series_remove_f32(float *ts_dev, int64_t T, int64_t C, int64_t ld, const double *basis_dev,
+                           int32_t P, int32_t R, const double *coef_dev, int64_t ldc, void *stream);
+int xmhw_series_remove_f64(double *ts_dev, int64_t T, int64_t C, int64_t ld, const double *basis_dev,
+                           int32_t P, int32_t R, const double *coef_dev, int64_t ldc, void *stream);
+
 /* ---- mhw_coverage(): daily area in each MHW category, by region (Hobday et al. 2018, fig. 3) ------ *
  * The one reduction ACROSS cells.  For every step t of the dense series ts_dev (T, C) and every region
  * r < R, ADDS to cells_dev[t][r][k] the number of cells c with region_dev[c] == r that are in state k on

@@ -135,7 +135,7 @@ def threshold(
 
 def _threshold(temp, compute, tdim="time", climatologyPeriod=[None, None], pctile=90,
                windowHalfWidth=5, smoothPercentile=True, smoothPercentileWidth=31, maxPadLength=None,
-               coldSpells=False, tstep=False, anynans=False, skipna=False, grid_compute=None):
+               coldSpells=False, tstep=False, anynans=False, skipna=False, grid_compute=None, detrend=None):
     """Host side of threshold() around a device stage ``compute`` with the signature of
     ``device.calc_clim_device``.  The public threshold() passes the HIP path; the CPU tests of
     the host logic and of the multi-rank sharding pass a stand-in here.  ``grid_compute``
@@ -189,6 +189,9 @@ def _threshold(temp, compute, tdim="time", climatologyPeriod=[None, None], pctil
     # ts.interpolate_na(dim=tdim, max_gap=maxPadLength) after land_check (xmhw.py:157-160): on the device
     # copy of the compacted series, handed to the device stage as a recipe (None: no interpolation)
     pad = make_pad(maxPadLength, time)
+    if detrend is not None:               # threshold_detect(detrend=...): a detrend.DetrendSpec, applied after the padding
+        from .detrend import SeriesRecipe
+        pad = SeriesRecipe(pad, detrend)
     extra = {} if pad is None else {"pad": pad}
     try:
         if on_device:
@@ -214,6 +217,8 @@ def _threshold(temp, compute, tdim="time", climatologyPeriod=[None, None], pctil
         "xmhw_parameters": _params_text(pctile, (int(yrs[0]), int(yrs[-1])), windowHalfWidth, skipna,
                                         smoothPercentile, smoothPercentileWidth, anynans),
     }
+    if detrend is not None:
+        out_attrs["xmhw_detrend"] = detrend.describe()
     var_attrs = {"thresh": {"units": "degree_C"}, "seas": {"units": "degree_C"}}   # quirk Q9
     doy_attrs = {"units": "1", "long_name": "Day of the year"}
     if point:

@@ -990,6 +990,49 @@ static int block_time(const T* ts, int64_t Tn, int64_t C, int64_t ld, const doub
     return XMHW_OK;
 }
 
+static int fit_args(const void* ts, int64_t Tn, int64_t C, int64_t ld, const double* basis, int32_t P, const double* coef,
+                    int64_t ldc) {
+    if (Tn < 0 || C < 0) return fail(XMHW_ERR_INVALID, "bad T/C");
+    if (P < 1) return fail(XMHW_ERR_INVALID, "P must be >= 1");
+    if (P > XMHW_FIT_MAX_TERMS)
+        return fail(XMHW_ERR_UNSUPPORTED, "series fit: more than " + std::to_string(XMHW_FIT_MAX_TERMS) + " terms");
+    if (ld < C) return fail(XMHW_ERR_INVALID, "ld must be >= C");
+    if (ldc < C) return fail(XMHW_ERR_INVALID, "ldc must be >= C");
+    if (C == 0 || Tn == 0) return XMHW_OK;
+    if (!ts || !basis || !coef) return fail(XMHW_ERR_INVALID, "NULL buffer");
+    if ((C + 63) / 64 > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "C too large for one launch");
+    return XMHW_OK;
+}
+
+template <typename T>
+static int series_fit(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* basis, int32_t P, const uint8_t* weight,
+                      int32_t min_valid, double* coef, int64_t ldc, int32_t* nvalid, void* stream) {
+    if (int rc = fit_args(ts, Tn, C, ld, basis, P, coef, ldc)) return rc;
+    if (C == 0 || Tn == 0) return XMHW_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    void* sp = nullptr;
+    ScratchRef scratch_keep;
+    const size_t gram_bytes = sizeof(double) * xmhw::kFitGramWords;      // then one flag byte per cell
+    hipError_t e = scratch_get(st, gram_bytes + static_cast<size_t>(C), &sp, &scratch_keep);
+    if (e != hipSuccess) return hip_fail(e, "scratch allocation");
+    e = xmhw::launch_series_fit<T>(ts, Tn, C, ld, basis, P, weight, min_valid > P ? min_valid : P, static_cast<double*>(sp),
+                                   static_cast<uint8_t*>(sp) + gram_bytes, coef, ldc, nvalid, st);
+    if (e != hipSuccess) return hip_fail(e, "series_fit launch");
+    return XMHW_OK;
+}
+
+template <typename T>
+static int series_remove(T* ts, int64_t Tn, int64_t C, int64_t ld, const double* basis, int32_t P, int32_t R,
+                         const double* coef, int64_t ldc, void* stream) {
+    if (int rc = fit_args(ts, Tn, C, ld, basis, P, coef, ldc)) return rc;
+    if (R < 1 || R > P) return fail(XMHW_ERR_INVALID, "R must be in [1, P]");
+    if (C == 0 || Tn == 0) return XMHW_OK;
+    if ((Tn + 63) / 64 > 65535) return fail(XMHW_ERR_UNSUPPORTED, "T too large for one launch");
+    hipError_t e = xmhw::launch_series_remove<T>(ts, Tn, C, ld, basis, P, R, coef, ldc, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "series_remove launch");
+    return XMHW_OK;
+}
+
 extern "C" {
 
 int xmhw_version(void) { return 1000 * 0 + 1; }
@@ -1793,6 +1836,23 @@ int xmhw_block_trend_theil_sen(const double* y, int32_t nstat, int32_t nb, int64
     hipError_t e = xmhw::launch_trend_theil_sen(y, nstat, nb, C, ld, x, out, ldo, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hip_fail(e, "trend_theil_sen launch");
     return XMHW_OK;
+}
+
+int xmhw_series_fit_f32(const float* ts, int64_t T, int64_t C, int64_t ld, const double* basis, int32_t P,
+                        const uint8_t* weight, int32_t min_valid, double* coef, int64_t ldc, int32_t* nvalid, void* stream) {
+    return series_fit<float>(ts, T, C, ld, basis, P, weight, min_valid, coef, ldc, nvalid, stream);
+}
+int xmhw_series_fit_f64(const double* ts, int64_t T, int64_t C, int64_t ld, const double* basis, int32_t P,
+                        const uint8_t* weight, int32_t min_valid, double* coef, int64_t ldc, int32_t* nvalid, void* stream) {
+    return series_fit<double>(ts, T, C, ld, basis, P, weight, min_valid, coef, ldc, nvalid, stream);
+}
+int xmhw_series_remove_f32(float* ts, int64_t T, int64_t C, int64_t ld, const double* basis, int32_t P, int32_t R,
+                           const double* coef, int64_t ldc, void* stream) {
+    return series_remove<float>(ts, T, C, ld, basis, P, R, coef, ldc, stream);
+}
+int xmhw_series_remove_f64(double* ts, int64_t T, int64_t C, int64_t ld, const double* basis, int32_t P, int32_t R,
+                           const double* coef, int64_t ldc, void* stream) {
+    return series_remove<double>(ts, T, C, ld, basis, P, R, coef, ldc, stream);
 }
 
 int xmhw_coverage_accumulate_f32(const float* ts, int64_t T, int64_t C, int64_t ld, const double* seas,

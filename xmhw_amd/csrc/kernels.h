@@ -234,6 +234,22 @@ hipError_t launch_trend_ols(const double* y, int32_t nstat, int32_t nb, int64_t 
 hipError_t launch_trend_theil_sen(const double* y, int32_t nstat, int32_t nb, int64_t C, int64_t ld, const double* x,
                                   double* out, int64_t ldo, hipStream_t stream);
 
+// detrend() (kernels_fit.hip): launch_series_fit solves, per cell of the series ts[T][ld], the least squares of its
+// samples on the design matrix basis[T][P] (device, float64, shared by all cells) over the steps with weight[t] != 0
+// (device, NULL: all) and a non-NaN sample, and writes coef[P][ldc] (NaN for a failed cell: fewer than `need`
+// contributing samples, a contributing +-Inf, a Cholesky pivot not above 1e-6 of its diagonal entry) and nvalid[C]
+// (may be NULL).  gram: kFitGramWords doubles, flags: C bytes of device workspace, written by the call.  launch_series_remove
+// subtracts sum_{k<R} coef[k] basis[t][k] from every sample in place.  P <= kFitMaxTerms.
+constexpr int kFitMaxTerms = 10;
+constexpr int kFitGramWords = 64;
+template <typename T>
+hipError_t launch_series_fit(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* basis, int32_t P,
+                             const uint8_t* weight, int32_t need, double* gram, uint8_t* flags, double* coef, int64_t ldc,
+                             int32_t* nvalid, hipStream_t stream);
+template <typename T>
+hipError_t launch_series_remove(T* ts, int64_t Tn, int64_t C, int64_t ld, const double* basis, int32_t P, int32_t R,
+                                const double* coef, int64_t ldc, hipStream_t stream);
+
 // mhw_coverage() (kernels_coverage.hip): event_day_bits turns the exceedance words of exceed_bits into the per-day
 // in-event bitmap inev[w][ldi] (steps first..last of every filtered, gap-joined event; zeroed here first);
 // coverage_accumulate ADDS, for every step t and region r < R, the number of in-event cells per state (moderate, strong,

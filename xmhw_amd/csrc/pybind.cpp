@@ -589,6 +589,31 @@ PYBIND11_MODULE(_xmhw_hip, m) {
                                          static_cast<const double*>(vp(x)), static_cast<double*>(vp(out)), ldo, vp(stream)));
     }, py::arg("y"), py::arg("nstat"), py::arg("nb"), py::arg("C"), py::arg("ld"), py::arg("x"), py::arg("out"),
        py::arg("ldo"), py::arg("stream") = 0);
+    m.attr("FIT_MAX_TERMS") = XMHW_FIT_MAX_TERMS;
+    m.def("series_fit", [](uintptr_t ts, int itemsize, int64_t T, int64_t C, int64_t ld, uintptr_t basis, int32_t P,
+                           uintptr_t weight, int32_t min_valid, uintptr_t coef, int64_t ldc, uintptr_t nvalid, uintptr_t stream) {
+        if (itemsize == 4)
+            check(xmhw_series_fit_f32(static_cast<const float*>(vp(ts)), T, C, ld, static_cast<const double*>(vp(basis)), P,
+                                      static_cast<const uint8_t*>(vp(weight)), min_valid, static_cast<double*>(vp(coef)), ldc,
+                                      static_cast<int32_t*>(vp(nvalid)), vp(stream)));
+        else if (itemsize == 8)
+            check(xmhw_series_fit_f64(static_cast<const double*>(vp(ts)), T, C, ld, static_cast<const double*>(vp(basis)), P,
+                                      static_cast<const uint8_t*>(vp(weight)), min_valid, static_cast<double*>(vp(coef)), ldc,
+                                      static_cast<int32_t*>(vp(nvalid)), vp(stream)));
+        else throw InvalidError("itemsize must be 4 or 8");
+    }, py::arg("ts"), py::arg("itemsize"), py::arg("T"), py::arg("C"), py::arg("ld"), py::arg("basis"), py::arg("P"),
+       py::arg("weight"), py::arg("min_valid"), py::arg("coef"), py::arg("ldc"), py::arg("nvalid") = 0, py::arg("stream") = 0);
+    m.def("series_remove", [](uintptr_t ts, int itemsize, int64_t T, int64_t C, int64_t ld, uintptr_t basis, int32_t P,
+                              int32_t R, uintptr_t coef, int64_t ldc, uintptr_t stream) {
+        if (itemsize == 4)
+            check(xmhw_series_remove_f32(static_cast<float*>(vp(ts)), T, C, ld, static_cast<const double*>(vp(basis)), P, R,
+                                         static_cast<const double*>(vp(coef)), ldc, vp(stream)));
+        else if (itemsize == 8)
+            check(xmhw_series_remove_f64(static_cast<double*>(vp(ts)), T, C, ld, static_cast<const double*>(vp(basis)), P, R,
+                                         static_cast<const double*>(vp(coef)), ldc, vp(stream)));
+        else throw InvalidError("itemsize must be 4 or 8");
+    }, py::arg("ts"), py::arg("itemsize"), py::arg("T"), py::arg("C"), py::arg("ld"), py::arg("basis"), py::arg("P"),
+       py::arg("R"), py::arg("coef"), py::arg("ldc"), py::arg("stream") = 0);
     m.def("block_time", [](uintptr_t ts, int itemsize, int64_t T, int64_t C, int64_t ld, uintptr_t cats, int64_t ldcat,
                            uintptr_t bin_of_t, int nbins, uintptr_t out, int64_t ldo, uintptr_t stream) {
         if (itemsize == 4)

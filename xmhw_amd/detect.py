@@ -264,6 +264,7 @@ def threshold_detect(
     joinGaps=True,
     maxGap=2,
     intermediate=False,
+    detrend=None,
 ):
     """``clim = threshold(temp, ...)`` followed by ``detect(temp, clim['thresh'], clim['seas'], ...)``
     (the reference's usual pair, docs/gettingstarted.rst:37-45) with the series uploaded ONCE: the
@@ -273,12 +274,37 @@ def threshold_detect(
     the two separate calls with the same arguments.  When the climatology period selects a part of
     the time axis, or the series does not leave room in HBM, or ``intermediate`` is asked for (the
     per-step columns take the host-compacted path), detect() uploads the series again as the separate
-    call would."""
+    call would.
+
+    ``detrend`` (not in the reference): None changes nothing.  True, or a dict of detrend()'s keyword arguments
+    (order, harmonics, fitPeriod, reference, min_valid), removes every cell's long-term trend from the device copy of
+    the series right after the maxPadLength interpolation and before the climatology (xmhw_amd/detrend.py); the
+    retained slabs are the detrended ones and detect() consumes them, and where detect() uploads the series itself
+    it applies the same recipe: every value equals ``detrend(temp)`` followed by ``threshold_detect()`` on its
+    output.  The parameters are recorded in ``clim.attrs["xmhw_detrend"]``; the coefficients come from detrend().
+    Not together with a ``climatologyPeriod`` that cuts the time axis (the cut and the full series would need two
+    fits): call detrend(temp, fitPeriod=[a, b]) first, then threshold_detect(climatologyPeriod=[a, b])."""
     from .api import _threshold
     from .device import ResidentSeries, calc_clim_device, calc_clim_grid_device
     if maxGap >= minDuration:                                  # detect()'s check, before any work is done
         raise XmhwException("Maximum gap between mhw events should"
                             + " be smaller than event minimum duration")
+    spec = None
+    if detrend is not None and detrend is not False:
+        from .detrend import make_spec
+        if tdim not in list(temp.dims):
+            raise XmhwException(f"{tdim} dimension not present, default"
+                                + "is 'time' or pass as tdim='time_dimension_name'")
+        full_time = np.asarray(temp[tdim].values if _is_xarray(temp) else temp.coords[tdim])
+        if all(climatologyPeriod):
+            yrs = cal.years_of(full_time)
+            if not ((yrs >= int(climatologyPeriod[0])) & (yrs <= int(climatologyPeriod[1]))).all():
+                raise XmhwException(
+                    f"threshold_detect(detrend=...) with climatologyPeriod={list(climatologyPeriod)} cutting the time "
+                    "axis is not supported (the cut series and the full series would need two fits): call "
+                    f"detrend(temp, fitPeriod={list(climatologyPeriod)}) first, then "
+                    f"threshold_detect(climatologyPeriod={list(climatologyPeriod)}) on its output")
+        spec = make_spec(detrend, full_time)
     store = ResidentSeries()
 
     def clim_grid(*a, **k):
@@ -290,21 +316,23 @@ def threshold_detect(
     try:
         clim = _threshold(temp, calc_clim_device, tdim, climatologyPeriod, pctile, windowHalfWidth,
                           smoothPercentile, smoothPercentileWidth, maxPadLength, coldSpells, tstep,
-                          anynans, skipna, grid_compute=clim_grid)
+                          anynans, skipna, grid_compute=clim_grid, detrend=spec)
         if _is_xarray(clim):
             th, se = clim["thresh"], clim["seas"]
         else:
             th, se = climatology_series(clim, "thresh"), climatology_series(clim, "seas")
         out = _detect(temp, th, se, detect_cells, tdim, minDuration, joinGaps, maxGap,
-                      maxPadLength, coldSpells, intermediate, anynans, tstep, grid_compute=events_grid)
+                      maxPadLength, coldSpells, intermediate, anynans, tstep, grid_compute=events_grid, detrend=spec)
     finally:
         store.free()
+        if spec is not None:
+            spec.free()
     if intermediate:
         return (clim,) + tuple(out)
     return clim, out
 
 def _detect(temp, th, se, compute, tdim="time", minDuration=5, joinGaps=True, maxGap=2, maxPadLength=None,
-            coldSpells=False, intermediate=False, anynans=False, tstep=False, grid_compute=None):
+            coldSpells=False, intermediate=False, anynans=False, tstep=False, grid_compute=None, detrend=None):
     """Host side of detect() around a device stage ``compute`` with the signature of
     ``detect_front.detect_cells``.  The public detect() passes the HIP path; the CPU tests of the
     host logic pass an oracle-based stand-in.  ``grid_compute`` (signature of
@@ -360,6 +388,9 @@ def _detect(temp, th, se, compute, tdim="time", minDuration=5, joinGaps=True, ma
     from .device import _trace
     _t0 = _time.perf_counter()
     pad = make_pad(maxPadLength, time)                         # xmhw.py:407-410, after land_check
+    if detrend is not None:               # threshold_detect(detrend=...): the recipe threshold() applied, applied again
+        from .detrend import SeriesRecipe
+        pad = SeriesRecipe(pad, detrend)
     extra = {} if pad is None else {"pad": pad}
     try:
         if on_device:

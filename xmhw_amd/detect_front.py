@@ -11,7 +11,7 @@ reference-shaped entry point on top of detect_cells().
 import numpy as np
 
 from ._lib import hip
-from .device import DeviceBuffer, native_float
+from .device import DeviceBuffer, apply_recipe_in_place, native_float
 from .exception import XmhwException
 
 
@@ -130,7 +130,7 @@ def _table_only_batch(h, ts, seas, thresh, rows, T, n, isz, neg, minDuration, jo
     try:
         d_ts = DeviceBuffer.from_array(ts); bufs.append(d_ts)
         if pad is not None:
-            pad.apply(d_ts.ptr, isz, T, n)
+            apply_recipe_in_place(pad, d_ts.ptr, isz, T, n)
         d_se = DeviceBuffer.from_array(seas); bufs.append(d_se)
         d_th = DeviceBuffer.from_array(thresh); bufs.append(d_th)
         return _table_only_device(h, d_ts, isz, d_se.ptr, d_th.ptr, n, thresh.shape[0], rows, T, n, neg, minDuration,
@@ -188,7 +188,7 @@ def detect_cells(ts, seas, thresh, doy, doys, minDuration=5, joinGaps=True, maxG
         try:
             d_ts = DeviceBuffer.from_array(np.ascontiguousarray(ts[:, c0:c1])); bufs.append(d_ts)
             if pad is not None:
-                pad.apply(d_ts.ptr, isz, T, n)
+                apply_recipe_in_place(pad, d_ts.ptr, isz, T, n)
                 if intermediate:
                     filled = d_ts.to_array((T, n), ts.dtype)
                     inter["ts"][:, c0:c1] = -filled if coldSpells else filled
@@ -250,6 +250,28 @@ def _rows_as_they_are(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def _recipe_through_device(ts, recipe, max_batch_bytes):
+    """a slab recipe (detrend.SeriesRecipe) applied to a dense host (T, C) series through the device, in batches:
+    (the transformed series, the mask of the cells it failed)"""
+    T, C = ts.shape
+    isz = ts.dtype.itemsize
+    out = np.empty_like(ts)
+    failed = np.zeros(C, dtype=bool)
+    cb = int(max(1, min(C, max_batch_bytes // max(1, 2 * T * isz))))
+    for lo in range(0, C, cb):
+        n = min(cb, C - lo)
+        d_ts = DeviceBuffer.from_array(np.ascontiguousarray(ts[:, lo:lo + n]))
+        try:
+            f = recipe.apply(d_ts.ptr, isz, T, n)
+            if f is not None:
+                failed[lo:lo + n] = f
+            hip().stream_sync(0)
+            out[:, lo:lo + n] = d_ts.to_array((T, n), ts.dtype)
+        finally:
+            d_ts.free()
+    return out, failed
+
+
 def detect_grid(stacked, anynans, seas, thresh, doy, doys, minDuration=5, joinGaps=True, maxGap=2, coldSpells=False,
                 intermediate=False, max_batch_bytes=None, clim_stacked=False, columns=None, exchange=None,
                 resident=None, pad=None):
@@ -266,7 +288,7 @@ def detect_grid(stacked, anynans, seas, thresh, doy, doys, minDuration=5, joinGa
     all-land block).  ``resident`` (device.ResidentSeries filled by calc_clim_grid_device for the same host
     array and mask rule): its compacted device slabs are used instead of a second upload."""
     import time as _time
-    from .device import ResidentSeries, _grid_batch, _trace, compact_columns, decode_through_device, device_itemsize, is_packed
+    from .device import ResidentSeries, _grid_batch, _trace, apply_recipe, compact_columns, decode_through_device, device_itemsize, is_packed
     _t_all = _time.perf_counter()
     rkey = ResidentSeries.key_of(stacked, anynans) if resident is not None else None
     T, N = stacked.shape
@@ -292,11 +314,22 @@ def detect_grid(stacked, anynans, seas, thresh, doy, doys, minDuration=5, joinGa
     def host_path(seas_c, thresh_c):
         # positional pairing needs the global compact order: compact the series on the host
         ts_c, keep = host_compact(stacked)
+        recipe = pad
+        if recipe is not None and hasattr(recipe, "spec"):
+            # a detrending recipe may fail cells, and they drop out like land BEFORE the cells pair up: it runs here,
+            # batch by batch on the device (a cell's result does not depend on its batch), not inside detect_cells
+            ts_c, failed = _recipe_through_device(ts_c, recipe, max_batch_bytes if max_batch_bytes is not None else 64 << 30)
+            if failed.any():
+                keep[np.nonzero(keep)[0][failed]] = False
+                ts_c = np.ascontiguousarray(ts_c[:, ~failed])
+                if ts_c.shape[1] == 0:
+                    raise XmhwException("All points of grid are either land or NaN")
+            recipe = None
         if ts_c.shape[1] != thresh_c.shape[1] or seas_c.shape[1] != thresh_c.shape[1]:
             raise XmhwException(f"temp, th and se do not have the same ocean cells: {ts_c.shape[1]}, "
                                 f"{thresh_c.shape[1]}, {seas_c.shape[1]}")
         r = detect_cells(ts_c, seas_c, thresh_c, doy, doys, minDuration, joinGaps, maxGap, coldSpells, intermediate,
-                         max_batch_bytes if max_batch_bytes is not None else 64 << 30, pad=pad)
+                         max_batch_bytes if max_batch_bytes is not None else 64 << 30, pad=recipe)
         r["keep"] = keep
         return r
 
@@ -382,13 +415,13 @@ def detect_grid(stacked, anynans, seas, thresh, doy, doys, minDuration=5, joinGa
                     _tl = _time.perf_counter()
                     d_ts, keep = compact_columns(stacked, lo, hi, anynans)
                     _trace(f"detect: upload + mask + compact [{lo},{hi})", _tl)
+                if pad is not None and not reuse and d_ts is not None:
+                    d_ts, keep = apply_recipe(pad, d_ts, isz, T, keep)      # (a retained slab already went through it)
                 keeps.append(keep)
                 n = int(keep.sum())
                 if d_ts is None:
                     continue
                 try:
-                    if pad is not None:
-                        pad.apply(d_ts.ptr, isz, T, n)      # (a retained slab is already interpolated: a no-op then)
                     if k0 + n > C:
                         raise XmhwException(f"temp has more ocean cells than th and se ({C})")
                     _tl = _time.perf_counter()

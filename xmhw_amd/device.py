@@ -320,7 +320,7 @@ def calc_clim_device(ts, doy, pctile, windowHalfWidth, smoothPercentile, smoothP
             slab = np.ascontiguousarray(ts[:, lo:lo + n])
             h.memcpy_h2d(d_ts.ptr, slab)
             if pad is not None:
-                pad.apply(d_ts.ptr, isz, T, n)
+                apply_recipe_in_place(pad, d_ts.ptr, isz, T, n)
             clim_raw(plan, d_ts, isz, n, pctile / 100.0, coldSpells, raw_th, raw_se)
             if finish:
                 clim_finish(plan, raw_th, raw_se, n, feb29_fix, smoothPercentile, smoothPercentileWidth,
@@ -508,6 +508,44 @@ def mask_compact(d_raw, isz, T, n, anynans):
         return out, keep
     finally:
         for b in (d_raw, d_mask, d_idx, d_out):
+            if b is not None:
+                b.free()
+
+
+def apply_recipe_in_place(pad, d_ts_ptr, isz, T, n):
+    """Apply a slab recipe where the stage cannot drop cells afterwards (a single point, a dense host batch, a
+    sharded block): a recipe that fails cells (detrending) is an error there, never a silently NaN cell."""
+    failed = pad.apply(d_ts_ptr, isz, T, n)
+    if failed is not None and failed.any():
+        raise XmhwException(f"detrend: the fit failed for {int(failed.sum())} of {n} cell(s) (too few contributing samples, "
+                            "an infinite sample or an ill-posed fit) on a path that cannot drop them: detrend() first")
+
+
+def apply_recipe(pad, d_ts, isz, T, keep):
+    """Apply a slab recipe (padding.PadSpec, or detrend.SeriesRecipe) in place to the compacted device slab d_ts
+    whose cells are keep's survivors.  A recipe may fail cells (a detrending fit without enough samples: the cell is
+    NaN everywhere then): they are dropped like land -- the slab is compacted again and keep updated.  Consumes d_ts
+    when it re-compacts.  Returns (DeviceBuffer or None, keep)."""
+    n = int(keep.sum())
+    failed = pad.apply(d_ts.ptr, isz, T, n)
+    if failed is None or not failed.any():
+        return d_ts, keep
+    keep = keep.copy()
+    keep[np.nonzero(keep)[0][failed]] = False
+    ok = np.nonzero(~failed)[0].astype(np.int64)
+    d_idx = d_out = None
+    try:
+        if ok.size == 0:
+            return None, keep
+        h = hip()
+        d_idx = DeviceBuffer.from_array(ok)
+        d_out = DeviceBuffer(isz * T * ok.size)
+        h.gather_cells(d_ts.ptr, isz, T, n, d_idx.ptr, ok.size, d_out.ptr, ok.size)
+        h.stream_sync(0)
+        out, d_out = d_out, None
+        return out, keep
+    finally:
+        for b in (d_ts, d_idx, d_out):
             if b is not None:
                 b.free()
 
@@ -724,7 +762,7 @@ def _grid_block_on_device(plan, stacked, c0, c1, anynans, pctile, coldSpells, fe
             return keep, plan.doys.copy(), block, None
         bufs.append(d_ts)
         if pad is not None:
-            pad.apply(d_ts.ptr, isz, stacked.shape[0], n)
+            apply_recipe_in_place(pad, d_ts.ptr, isz, stacked.shape[0], n)
         raw_th, raw_se = DeviceBuffer(8 * D * n), DeviceBuffer(8 * D * n)
         bufs += [raw_th, raw_se]
         clim_raw(plan, d_ts, isz, n, pctile / 100.0, coldSpells, raw_th, raw_se)
@@ -774,7 +812,8 @@ def calc_clim_grid_device(stacked, doy, anynans, pctile, windowHalfWidth, smooth
     ``resident`` (a ResidentSeries) keeps every slab's compacted device copy for a later consumer of the
     same host array instead of freeing it.  ``pad`` (padding.PadSpec): maxPadLength's interpolate_na, applied
     to every compacted slab AFTER the mask (the reference interpolates after land_check, xmhw.py:137-160);
-    a retained slab is the interpolated one."""
+    a retained slab is the interpolated one.  A detrend.SeriesRecipe in its place also detrends the slab
+    (threshold_detect(detrend=...)); cells whose fit fails are dropped like land."""
     rkey = ResidentSeries.key_of(stacked, anynans) if resident is not None else None
     if is_packed(stacked):
         if stacked.ndim != 2 or stacked.strides[1] != stacked.dtype.itemsize:
@@ -833,6 +872,8 @@ def calc_clim_grid_device(stacked, doy, anynans, pctile, windowHalfWidth, smooth
                 d_ts, keep = mask_compact(d_up, up_isz, T, hi - lo, anynans)
             _trace("mask + compact", _tl)
             _tl = _time.perf_counter()
+            if pad is not None and d_ts is not None:
+                d_ts, keep = apply_recipe(pad, d_ts, isz, T, keep)       # (may drop cells: before anything is recorded)
             keeps.append(keep)
             w = hi - lo
             if retain:
@@ -848,8 +889,6 @@ def calc_clim_grid_device(stacked, doy, anynans, pctile, windowHalfWidth, smooth
             n = int(keep.sum())
             bufs = [] if retain else [d_ts]
             try:
-                if pad is not None:
-                    pad.apply(d_ts.ptr, isz, T, n)
                 raw_th, raw_se = DeviceBuffer(8 * D * n), DeviceBuffer(8 * D * n)
                 bufs += [raw_th, raw_se]
                 if direct:
