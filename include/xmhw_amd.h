@@ -630,6 +630,32 @@ int xmhw_object_reduce(const int32_t *start_dev, const int32_t *end_dev, const d
                        int32_t *time_start_dev, int32_t *time_end_dev, int64_t *cell_days_dev,
                        int64_t *area_days_q_dev, double *intensity_max_dev, int32_t *peak_row_dev, void *stream);
 
+/* ---- mhw_tracks(): the daily series of the objects (cells, area, first moments), ragged ------------- *
+ * The rows are those of xmhw_object_reduce (start_dev, end_dev, cell_of_row_dev as xmhw_event_objects wrote it).
+ * slot_dev[r] is the position of row r's object in the caller's SELECTION, in [0, n_slots); a row with any other
+ * slot does nothing.  Selected object i lives from time_start_dev[i] to its last day and owns the entries
+ * offsets_dev[i] .. offsets_dev[i + 1] - 1 of every series, one per day (offsets_dev[n_slots + 1] int64,
+ * offsets_dev[0] == 0, offsets_dev[n_slots] == L = the sum of the durations).  vec_dev[4][ldv] int64 holds four
+ * addends per cell (ldv >= C): mhw_tracks() passes the area weight wq and the moment terms wm*ux, wm*uy, wm*uz.
+ *
+ * Initialises and fills n_cells_dev[L + 1] int32 and sums_dev[4][ld] int64 (ld >= L + 1): entry
+ * offsets[i] + (t - time_start[i]) of n_cells is the number of rows of object i that cover day t (one per cell:
+ * the rows of a cell are disjoint), and of sums[k] the sum of vec[k][cell] over them.  Entry L of all five is a
+ * sentinel that ends as 0.  Method: every row adds its vector at its first day and subtracts it behind its last
+ * (integer atomics; a row that ends on its object's last day puts the negative term on the next object's first
+ * entry, or on the sentinel), then ONE inclusive scan of the whole array, in place, as reduce-then-scan over tiles
+ * of XMHW_TRACKS_TILE entries in separate launches.  No kernel waits for another workgroup; sums wrap modulo 2^64
+ * on the way and are exact whenever the true values fit int64 (int32 for n_cells).  The result is the same from
+ * run to run.  *n_bad_dev (one int32) counts the rows left out because their days fall outside their object's
+ * entries or their cell outside [0, C): 0 for consistent inputs; nothing outside entries 0..L is written.
+ * n, n_slots or L + 1 of 2^31 and more: XMHW_ERR_UNSUPPORTED (select fewer objects).  Scratch for the tile sums
+ * comes from the stream's scratch buffer.  Asynchronous on `stream`.                                         */
+#define XMHW_TRACKS_TILE 1024
+int xmhw_object_tracks(const int32_t *start_dev, const int32_t *end_dev, int64_t n, const int32_t *slot_dev,
+                       const int32_t *cell_of_row_dev, int64_t C, const int64_t *vec_dev, int64_t ldv,
+                       const int32_t *time_start_dev, const int64_t *offsets_dev, int64_t n_slots, int64_t L,
+                       int32_t *n_cells_dev, int64_t *sums_dev, int64_t ld, int32_t *n_bad_dev, void *stream);
+
 /* ---- the sharded path: cells split across the GPUs of a node, ONE gather at the end ------- *
  * Replaces the reference's collect, dask.compute(climls) + xr.concat(dim='cell')
  * (xmhw/xmhw.py:197, :210-211).  Cells are independent (xmhw/xmhw.py:184-196), so rank r runs the

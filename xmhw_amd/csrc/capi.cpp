@@ -1903,6 +1903,27 @@ int xmhw_object_reduce(const int32_t* start, const int32_t* end, const double* i
     return XMHW_OK;
 }
 
+int xmhw_object_tracks(const int32_t* start, const int32_t* end, int64_t n, const int32_t* slot, const int32_t* cell_of_row,
+                       int64_t C, const int64_t* vec, int64_t ldv, const int32_t* time_start, const int64_t* offsets,
+                       int64_t n_slots, int64_t L, int32_t* n_cells, int64_t* sums, int64_t ld, int32_t* n_bad, void* stream) {
+    if (n < 0 || C < 0 || n_slots < 0 || L < 0) return fail(XMHW_ERR_INVALID, "bad n/C/n_slots/L");
+    if (n > 0x7FFFFFFFll || n_slots > 0x7FFFFFFFll || L >= 0x7FFFFFFFll)
+        return fail(XMHW_ERR_UNSUPPORTED, "object_tracks: 2^31 rows, slots or series entries (L + 1) and more");
+    if (ld < L + 1 || ldv < C) return fail(XMHW_ERR_INVALID, "ld must be >= L + 1 and ldv >= C");
+    if (!n_cells || !sums || !n_bad) return fail(XMHW_ERR_INVALID, "NULL output buffer");
+    if (n > 0 && n_slots > 0 && L > 0 && (!start || !end || !slot || !cell_of_row || !vec || !time_start || !offsets))
+        return fail(XMHW_ERR_INVALID, "NULL buffer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    void* sp = nullptr;                              // the levels of tile sums live in this stream's scratch buffer
+    ScratchRef scratch_keep;
+    hipError_t e = scratch_get(st, xmhw::object_tracks_scratch_bytes(L + 1), &sp, &scratch_keep);
+    if (e != hipSuccess) return hip_fail(e, "scratch allocation");
+    e = xmhw::launch_object_tracks(start, end, n, slot, cell_of_row, C, vec, ldv, time_start, offsets, n_slots, L, n_cells, sums,
+                                   ld, n_bad, static_cast<int64_t*>(sp), st);
+    if (e != hipSuccess) return hip_fail(e, "object_tracks launch");
+    return XMHW_OK;
+}
+
 int xmhw_synth_sst_f32(float* ts, int64_t T, int64_t C, int64_t ld, int64_t cell0, uint64_t seed,
                        double nan_frac, void* stream) {
     if (C < 0 || ld < C || T <= 0) return fail(XMHW_ERR_INVALID, "bad T/C/ld");

@@ -279,6 +279,22 @@ hipError_t launch_object_reduce(const int32_t* start, const int32_t* end, const 
                                 int32_t* time_start, int32_t* time_end, int64_t* cell_days, int64_t* area_days_q,
                                 double* intensity_max, int32_t* peak_row, hipStream_t stream);
 
+// mhw_tracks() (kernels_tracks.hip): the daily series of the selected objects as one ragged array of L entries plus a
+// sentinel.  slot[r] in [0, n_slots) is the position of row r's object in the selection (anything else: the row does
+// nothing); object i owns the entries offsets[i]..offsets[i + 1] - 1, one per day from time_start[i]; offsets[n_slots]
+// == L.  vec[4][ldv] holds the four per-cell addends (area weight and three moment terms).  Initialises and fills
+// n_cells[L + 1] and sums[4][ld] (ld >= L + 1): a scatter into difference arrays, then an inclusive scan in place by
+// reduce-then-scan over tiles of kTracksTile entries (scratch: object_tracks_scratch_bytes(L + 1)).  Entry L of every
+// channel ends as 0.  *n_bad counts the rows left out because their days or cell do not fit (0 for consistent inputs).
+constexpr int kTracksTile = 1024;
+constexpr int kTracksChannels = 5;
+size_t object_tracks_scratch_bytes(int64_t L1);
+hipError_t launch_object_tracks(const int32_t* start, const int32_t* end, int64_t n, const int32_t* slot,
+                                const int32_t* cell_of_row, int64_t C, const int64_t* vec, int64_t ldv,
+                                const int32_t* time_start, const int64_t* offsets, int64_t n_slots, int64_t L,
+                                int32_t* n_cells, int64_t* sums, int64_t ld, int32_t* n_bad, int64_t* scratch,
+                                hipStream_t stream);
+
 // file bytes -> samples (kernels_ingest.hip): raw_type = item size of the stored type (2 int16, 4 float32,
 // 8 float64), swap = the file is big-endian, optional scale/offset (CF packing) and fill value -> NaN
 hipError_t launch_encode_i16(const float* in, int64_t rows, int64_t cols, int64_t ld_in, int16_t* out, int64_t ld_out,

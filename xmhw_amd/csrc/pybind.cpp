@@ -577,6 +577,18 @@ PYBIND11_MODULE(_xmhw_hip, m) {
        py::arg("wq"), py::arg("slot"), py::arg("n_slots"), py::arg("n_events"), py::arg("n_cells"), py::arg("time_start"),
        py::arg("time_end"), py::arg("cell_days"), py::arg("area_days_q"), py::arg("intensity_max"), py::arg("peak_row"),
        py::arg("stream") = 0);
+    m.def("object_tracks", [](uintptr_t start, uintptr_t end, int64_t n, uintptr_t slot, uintptr_t cell_of_row, int64_t C,
+                              uintptr_t vec, int64_t ldv, uintptr_t time_start, uintptr_t offsets, int64_t n_slots, int64_t L,
+                              uintptr_t n_cells, uintptr_t sums, int64_t ld, uintptr_t n_bad, uintptr_t stream) {
+        check(xmhw_object_tracks(static_cast<const int32_t*>(vp(start)), static_cast<const int32_t*>(vp(end)), n,
+                                 static_cast<const int32_t*>(vp(slot)), static_cast<const int32_t*>(vp(cell_of_row)), C,
+                                 static_cast<const int64_t*>(vp(vec)), ldv, static_cast<const int32_t*>(vp(time_start)),
+                                 static_cast<const int64_t*>(vp(offsets)), n_slots, L, static_cast<int32_t*>(vp(n_cells)),
+                                 static_cast<int64_t*>(vp(sums)), ld, static_cast<int32_t*>(vp(n_bad)), vp(stream)));
+    }, py::arg("start"), py::arg("end"), py::arg("n"), py::arg("slot"), py::arg("cell_of_row"), py::arg("C"), py::arg("vec"),
+       py::arg("ldv"), py::arg("time_start"), py::arg("offsets"), py::arg("n_slots"), py::arg("L"), py::arg("n_cells"),
+       py::arg("sums"), py::arg("ld"), py::arg("n_bad"), py::arg("stream") = 0);
+    m.attr("TRACKS_TILE") = XMHW_TRACKS_TILE;
     m.def("block_trend_ols", [](uintptr_t y, int32_t nstat, int32_t nb, int64_t C, int64_t ld, uintptr_t x, uintptr_t tcrit,
                                 uintptr_t out, int64_t ldo, uintptr_t stream) {
         check(xmhw_block_trend_ols(static_cast<const double*>(vp(y)), nstat, nb, C, ld, static_cast<const double*>(vp(x)),
