@@ -101,6 +101,11 @@ def test_region_cap(dev):
     # the C ABI itself: XMHW_ERR_UNSUPPORTED (code 3) above the cap, before anything is touched
     with pytest.raises(h.HipError, match=r"code 3"):
         h.coverage_accumulate(8, 4, 130, C, C, 8, 8, C, np.zeros(130, np.int32), 0, 8, C, 5, 1, 2, 8, 8, MAX_REGIONS + 1, 8, 8)
+    # ... raised as its own type, which is a HipError still
+    with pytest.raises(h.HipError) as raised:
+        h.coverage_accumulate(8, 4, 130, C, C, 8, 8, C, np.zeros(130, np.int32), 0, 8, C, 5, 1, 2, 8, 8, MAX_REGIONS + 1, 8, 8)
+    assert isinstance(raised.value, h.Unsupported) and isinstance(raised.value, h.HipError)
+    assert issubclass(h.Unsupported, h.HipError) and h.Unsupported is not h.HipError
 
 
 def test_weights_zero_and_one(dev):

@@ -183,6 +183,13 @@ def test_exceptions():
     touching = grid(1, 2, {(0, 0): [(0, 4), (5, 9)]})
     with pytest.raises(XmhwException, match="one step apart"):
         run(touching)
+    # offsets that do not cover the table; the weights are looked at first
+    broken = EventDataset(ds.table, ds.offsets[:-1], ds.time, ds.cell_index, ds.keep, ds.sdims, ds.sshape, ds.coords, {}, {}, {},
+                          False)
+    with pytest.raises(XmhwException, match="offsets and cell_index do not describe the table"):
+        run(broken)
+    with pytest.raises(XmhwException, match="weights should be None, 'coslat' or an array, got 'area'"):
+        run(broken, weights="area")
 
     class Huge(EventDataset):
         n_events = 1 << 31

@@ -113,6 +113,15 @@ def test_refusals():
             tracks(ds, obj, ids=bad)
     with pytest.raises(XmhwException, match="weights"):
         tracks(ds, obj, weights="area")
+    with pytest.raises(XmhwException, match="weights should be None, 'coslat' or an array, got 'area'"):
+        tracks(ds, obj, weights="area")
+    # offsets that do not cover the table; the weights are looked at first
+    broken = EventDataset(ds.table, ds.offsets[:-1], ds.time, ds.cell_index, ds.keep, ds.sdims, ds.sshape, ds.coords, {}, {}, {},
+                          False)
+    with pytest.raises(XmhwException, match="offsets and cell_index do not describe the table"):
+        tracks(broken, obj)
+    with pytest.raises(XmhwException, match="weights should be None, 'coslat' or an array, got 'area'"):
+        tracks(broken, obj, weights="area")
     with pytest.raises(XmhwException, match="shape"):
         tracks(ds, obj, weights=np.ones((2, 2, 2)))
     with pytest.raises(XmhwException, match="wrap"):                # index mode on a wrapping grid

@@ -27,28 +27,16 @@ Host side here (validation, weights, region labels, slabs); device side in csrc/
 """
 import numpy as np
 
+from . import gridweights
 from ._lib import hip
 from .api import GridSeries, _from_xarray, _is_xarray
-from .device import DeviceBuffer
+from .device import DeviceScope, as_xmhw_errors
 from .exception import XmhwException
+from .gridweights import quantise_weights, resolve_weights, weights_label     # (quantise_weights: imported from here too)
 
 CATEGORIES = ("moderate", "strong", "severe", "extreme", "event")
 WEIGHT_ONE = 1 << 31            # the quantised value of the largest weight
 MAX_REGIONS = 1024              # XMHW_COVERAGE_MAX_REGIONS (include/xmhw_amd.h)
-
-
-def quantise_weights(w, bits=31):
-    """(wq int64, weight_unit): wq = rint(w / w.max() * 2**bits); w finite, >= 0, not all zero."""
-    w = np.asarray(w, dtype=np.float64)
-    if w.size == 0 or not np.isfinite(w).all():
-        raise XmhwException("weights should be finite numbers")
-    if (w < 0).any():
-        raise XmhwException("weights should be >= 0")
-    wmax = float(w.max())
-    if not wmax > 0:
-        raise XmhwException("weights are all zero")
-    one = 1 << int(bits)
-    return np.rint(w / wmax * one).astype(np.int64), wmax / one
 
 
 def _check_cells(C, wq, region, R):
@@ -74,21 +62,13 @@ def _accumulate_device(h, d_ts, isz, se_ptr, th_ptr, ldc, D, rows, T, n, neg, mi
     column offset, leading dimension ldc): exceedance bits, then the reduction ADDS into d_cells / d_area."""
     ld = n if ld is None else ld
     W = (T + 63) // 64
-    d_bits = DeviceBuffer(8 * W * n)
-    try:
-        try:
+    with DeviceScope() as s:
+        d_bits = s.alloc(8 * W * n)
+        with as_xmhw_errors(also="Unsupported"):
             h.exceed_bits(d_ts.ptr, isz, T, n, ld, th_ptr, ldc, D, rows, neg, d_bits.ptr, n)
             h.coverage_accumulate(d_ts.ptr, isz, T, n, ld, se_ptr, th_ptr, ldc, rows, neg, d_bits.ptr, n, int(minDuration),
                                   int(bool(joinGaps)), int(maxGap), d_wq.ptr, d_reg.ptr, R, d_cells.ptr, d_area.ptr)
-        except h.InvalidArgument as e:
-            raise XmhwException(str(e)) from e
-        except h.HipError as e:
-            if "(code 3)" in str(e):                    # XMHW_ERR_UNSUPPORTED
-                raise XmhwException(str(e)) from e
-            raise
-        h.stream_sync(0)                                # d_bits is freed below
-    finally:
-        d_bits.free()
+        h.stream_sync(0)                                # d_bits is freed on the way out
 
 
 class _Accumulators:
@@ -97,7 +77,8 @@ class _Accumulators:
     def __init__(self, h, T, R):
         self.h, self.shape = h, (T, R, len(CATEGORIES))
         nbytes = 8 * T * R * len(CATEGORIES)
-        self.cells, self.area = DeviceBuffer(nbytes), DeviceBuffer(nbytes)
+        self._scope = DeviceScope()
+        self.cells, self.area = self._scope.alloc(nbytes), self._scope.alloc(nbytes)
         h.memset(self.cells.ptr, 0, nbytes)
         h.memset(self.area.ptr, 0, nbytes)
 
@@ -106,8 +87,7 @@ class _Accumulators:
         return self.cells.to_array(self.shape, np.int64), self.area.to_array(self.shape, np.int64)
 
     def free(self):
-        self.cells.free()
-        self.area.free()
+        self._scope.free()
 
 
 def coverage_cells(ts, seas, thresh, doy, doys, wq, region, R, minDuration=5, joinGaps=True, maxGap=2, coldSpells=False,
@@ -131,20 +111,15 @@ def coverage_cells(ts, seas, thresh, doy, doys, wq, region, R, minDuration=5, jo
         for c0 in range(0, C, batch):
             c1 = min(C, c0 + batch)
             n = c1 - c0
-            bufs = []
-            try:
-                d_ts = DeviceBuffer.from_array(np.ascontiguousarray(ts[:, c0:c1])); bufs.append(d_ts)
+            with DeviceScope() as s:
+                d_ts = s.upload(np.ascontiguousarray(ts[:, c0:c1]))
                 if pad is not None:
                     pad.apply(d_ts.ptr, isz, T, n)
-                d_se = DeviceBuffer.from_array(np.ascontiguousarray(seas[:, c0:c1])); bufs.append(d_se)
-                d_th = DeviceBuffer.from_array(np.ascontiguousarray(thresh[:, c0:c1])); bufs.append(d_th)
-                d_wq = DeviceBuffer.from_array(wq[c0:c1]); bufs.append(d_wq)
-                d_reg = DeviceBuffer.from_array(region[c0:c1]); bufs.append(d_reg)
+                d_se = s.upload(np.ascontiguousarray(seas[:, c0:c1]))
+                d_th = s.upload(np.ascontiguousarray(thresh[:, c0:c1]))
+                d_wq, d_reg = s.upload(wq[c0:c1]), s.upload(region[c0:c1])
                 _accumulate_device(h, d_ts, isz, d_se.ptr, d_th.ptr, n, D, rows, T, n, neg, minDuration, joinGaps, maxGap,
                                    d_wq, d_reg, R, acc.cells, acc.area)
-            finally:
-                for b in bufs:
-                    b.free()
         return acc.result()
     finally:
         acc.free()
@@ -171,21 +146,21 @@ def coverage_grid(stacked, anynans, seas, thresh, doy, doys, wq, region, R, minD
     h = hip()
     isz = device_itemsize(stacked)
     neg = int(bool(coldSpells))
-    clim_bufs, keeps = [], []
+    keeps = []
     acc = _Accumulators(h, T, R)
+    clim = DeviceScope()
     k0 = 0
     try:
         if clim_stacked:
             d_th, keep_th = compact_columns(thresh, 0, thresh.shape[1], anynans)
-            clim_bufs += [d_th] if d_th is not None else []
+            clim.adopt(d_th)
             d_se, keep_se = compact_columns(seas, 0, seas.shape[1], anynans)
-            clim_bufs += [d_se] if d_se is not None else []
+            clim.adopt(d_se)
             C, Cse = int(keep_th.sum()), int(keep_se.sum())
             if C == 0 or Cse == 0:
                 raise XmhwException("All points of grid are either land or NaN")
         else:
-            d_th = DeviceBuffer.from_array(thresh); clim_bufs.append(d_th)
-            d_se = DeviceBuffer.from_array(seas); clim_bufs.append(d_se)
+            d_th, d_se = clim.upload(thresh), clim.upload(seas)
             C, Cse = thresh.shape[1], seas.shape[1]
         if C != Cse:
             raise XmhwException(f"th and se do not have the same ocean cells: {C}, {Cse}")
@@ -197,19 +172,15 @@ def coverage_grid(stacked, anynans, seas, thresh, doy, doys, wq, region, R, minD
             n = int(keep.sum())
             if d_ts is None:
                 continue
-            bufs = [d_ts]
-            try:
+            with DeviceScope() as s:
+                s.adopt(d_ts)
                 if pad is not None:
                     pad.apply(d_ts.ptr, isz, T, n)
                 if k0 + n > C:
                     raise XmhwException(f"temp has more ocean cells than th and se ({C})")
-                d_wq = DeviceBuffer.from_array(wq[lo:hi][keep]); bufs.append(d_wq)
-                d_reg = DeviceBuffer.from_array(region[lo:hi][keep]); bufs.append(d_reg)
+                d_wq, d_reg = s.upload(wq[lo:hi][keep]), s.upload(region[lo:hi][keep])
                 _accumulate_device(h, d_ts, isz, d_se.ptr + 8 * k0, d_th.ptr + 8 * k0, C, D, rows, T, n, neg, minDuration,
                                    joinGaps, maxGap, d_wq, d_reg, R, acc.cells, acc.area)
-            finally:
-                for b in bufs:
-                    b.free()
             k0 += n
         keep = np.concatenate(keeps) if keeps else np.zeros(0, dtype=bool)
         if not keep.any():
@@ -220,8 +191,7 @@ def coverage_grid(stacked, anynans, seas, thresh, doy, doys, wq, region, R, minD
         return cells, area, keep
     finally:
         acc.free()
-        for b in clim_bufs:
-            b.free()
+        clim.free()
 
 
 class CoverageDataset:
@@ -258,27 +228,6 @@ class CoverageDataset:
             attrs=dict(self.attrs, weight_unit=self.weight_unit))
 
 
-def _on_grid(a, what, dims, tdim, sdims, sshape):
-    """An array given on the spatial grid (the non-time dims in the order of `temp`) -> (N,) in stacked order."""
-    a = np.asarray(a)
-    rest = [d for d in dims if d != tdim]
-    shape = tuple(sshape[sdims.index(d)] for d in rest)
-    if a.shape != shape:
-        raise XmhwException(f"{what} should have the shape of the spatial grid {dict(zip(rest, shape))}, got {a.shape}")
-    return np.transpose(a, [rest.index(d) for d in sdims]).reshape(-1)
-
-
-def _coslat(coords, sdims, sshape):
-    name = next((d for d in sdims if d.lower() in ("lat", "latitude", "y", "yt_ocean", "nav_lat")), None)
-    if name is None:
-        raise XmhwException(f"weights='coslat' needs a latitude dimension (lat / latitude), got {sdims}")
-    w = np.cos(np.deg2rad(np.asarray(coords[name], dtype=np.float64)))
-    w = np.where(np.abs(w) < 1e-15, 0.0, w)                     # cos(90 degrees) is 6e-17 in float64
-    shape = [1] * len(sdims)
-    shape[sdims.index(name)] = -1
-    return np.broadcast_to(w.reshape(shape), sshape).reshape(-1)
-
-
 def mhw_coverage(temp, th, se, weights=None, regions=None, tdim="time", minDuration=5, joinGaps=True, maxGap=2,
                  maxPadLength=None, coldSpells=False, tstep=False, anynans=False, _compute=None, max_batch_bytes=None):
     """Daily count and weighted area of the cells in each MHW category, by region.
@@ -311,18 +260,7 @@ def mhw_coverage(temp, th, se, weights=None, regions=None, tdim="time", minDurat
     sshape = tuple(shape[dims.index(d)] for d in sdims)
     N = int(np.prod(sshape, dtype=np.int64)) if not point else 1
     # weights and region labels on the whole grid, in stacked order
-    if weights is None:
-        w = np.ones(N)
-    elif isinstance(weights, str):
-        if weights != "coslat":
-            raise XmhwException(f"weights should be None, 'coslat' or an array, got {weights!r}")
-        w = np.ones(1) if point else _coslat(coords, sdims, sshape)
-    else:
-        w = np.asarray(weights, dtype=np.float64).reshape(-1) if point else \
-            _on_grid(np.asarray(weights, dtype=np.float64), "weights", dims, tdim, sdims, sshape)
-        if w.shape != (N,):
-            raise XmhwException("weights should have one entry per cell")
-    wq, unit = quantise_weights(w)
+    wq, unit = quantise_weights(resolve_weights(weights, coords, dims, tdim, sdims, sshape, point))
     if regions is None:
         labels = np.zeros(N, dtype=np.int64)
     else:
@@ -330,7 +268,7 @@ def mhw_coverage(temp, th, se, weights=None, regions=None, tdim="time", minDurat
         if regions.dtype.kind not in "iu":
             raise XmhwException(f"regions should be an integer array, got {regions.dtype}")
         labels = regions.astype(np.int64).reshape(-1) if point else \
-            _on_grid(regions, "regions", dims, tdim, sdims, sshape).astype(np.int64)
+            gridweights.on_grid(regions, "regions", dims, tdim, sdims, sshape).astype(np.int64)
         if labels.shape != (N,):
             raise XmhwException("regions should have one entry per cell")
     found = np.unique(labels[labels >= 0])                     # candidates: the labels on the whole grid
@@ -382,7 +320,6 @@ def mhw_coverage(temp, th, se, weights=None, regions=None, tdim="time", minDurat
         cells, area, ncells, total_q, region = cells[:, sel], area[:, sel], ncells[sel], total_q[sel], found[sel]
     else:
         region = np.zeros(1, dtype=np.int64)                    # every cell excluded: one empty region
-    attrs = {"weights": "coslat" if isinstance(weights, str) else ("uniform" if weights is None else "array"),
-             "xmhw_parameters": mhw.attrs["xmhw_parameters"]}
+    attrs = {"weights": weights_label(weights), "xmhw_parameters": mhw.attrs["xmhw_parameters"]}
     return CoverageDataset(np.asarray(coords[tdim]), region, np.ascontiguousarray(cells), np.ascontiguousarray(area),
                            total_q, ncells, unit, tdim=tdim, attrs=attrs)

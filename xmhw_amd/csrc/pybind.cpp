@@ -16,6 +16,7 @@ namespace py = pybind11;
 namespace {
 
 struct HipError : std::runtime_error { using std::runtime_error::runtime_error; };
+struct Unsupported : HipError { using HipError::HipError; };       // XMHW_ERR_UNSUPPORTED
 struct InvalidError : std::runtime_error { using std::runtime_error::runtime_error; };
 struct CommError : std::runtime_error { using std::runtime_error::runtime_error; };
 
@@ -25,7 +26,9 @@ void check(int rc) {
     if (rc == XMHW_ERR_INVALID) throw InvalidError(msg);
     if (rc == XMHW_ERR_NOMEM) throw std::bad_alloc();
     if (rc == XMHW_ERR_COMM) throw CommError(msg);
-    throw HipError(msg + " (code " + std::to_string(rc) + ")");
+    msg += " (code " + std::to_string(rc) + ")";
+    if (rc == XMHW_ERR_UNSUPPORTED) throw Unsupported(msg);
+    throw HipError(msg);
 }
 
 inline void* vp(uintptr_t p) { return reinterpret_cast<void*>(p); }
@@ -37,7 +40,8 @@ using i32arr = py::array_t<int32_t, py::array::c_style | py::array::forcecast>;
 
 PYBIND11_MODULE(_xmhw_hip, m) {
     m.doc() = "C-ABI bindings of the gfx950 xmhw threshold() path";
-    py::register_exception<HipError>(m, "HipError");
+    auto& hip_error = py::register_exception<HipError>(m, "HipError");
+    py::register_exception<Unsupported>(m, "Unsupported", hip_error.ptr());
     py::register_exception<InvalidError>(m, "InvalidArgument");
     py::register_exception<CommError>(m, "CommError");
 

@@ -104,6 +104,13 @@ def _compress_grid(a, alive, first_axis):
     return a
 
 
+def _positions(col, what):
+    col = np.asarray(col, dtype=np.float64)
+    if col.size and not (np.isfinite(col).all() and col.min() >= 0 and col.max() < (1 << 31) - 2):
+        raise XmhwException(f"{what} should hold time positions in [0, 2**31 - 2)")
+    return col.astype(np.int32)
+
+
 class EventDataset:
     """What detect() returns for GridSeries input: the content of the reference's `mhw` Dataset.
 
@@ -155,6 +162,23 @@ class EventDataset:
             out = np.full(pos.shape, None, dtype=object)
         out[ok] = t[pos[ok].astype(np.int64)]
         return out
+
+    def compact_view(self):
+        """The table as the stages that walk it row by row (mhw_objects(), mhw_tracks()) take it, validated: a dict
+        of n, C, offsets (C+1,) int64, cell_index (C,) int64, cell_of_row (n,) int64 -- the ocean cell of every row --
+        and start / end (n,) int32, the index_start / index_end positions."""
+        n = self.n_events
+        offsets = np.ascontiguousarray(self.offsets, dtype=np.int64)
+        cell_index = np.asarray(self.cell_index, dtype=np.int64)
+        C = offsets.shape[0] - 1
+        if cell_index.shape != (C,) or offsets[0] != 0 or offsets[-1] != n or (np.diff(offsets) < 0).any():
+            raise XmhwException("offsets and cell_index do not describe the table")
+        start = _positions(self.table[:, self.columns.index("index_start")], "index_start")
+        end = _positions(self.table[:, self.columns.index("index_end")], "index_end")
+        if (end < start).any():
+            raise XmhwException("index_end before index_start")
+        return dict(n=n, C=C, offsets=offsets, cell_index=cell_index, start=start, end=end,
+                    cell_of_row=np.repeat(np.arange(C, dtype=np.int64), np.diff(offsets)))
 
     def to_dense(self, variables=None):
         """The reference's layout: (dims, coords, {name: array}) with dims ("events", *sdims); NaN / NaT

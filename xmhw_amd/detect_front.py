@@ -11,7 +11,7 @@ reference-shaped entry point on top of detect_cells().
 import numpy as np
 
 from ._lib import hip
-from .device import DeviceBuffer, apply_recipe_in_place, native_float
+from .device import DeviceScope, apply_recipe_in_place, as_xmhw_errors, native_float
 from .exception import XmhwException
 
 
@@ -34,26 +34,18 @@ def mhw_filter_cells(ts, thresh, doy, doys, minDuration=5, joinGaps=True, maxGap
     ts, _, thresh, rows = _check_inputs(ts, thresh, thresh, doy, doys)
     T, C = ts.shape
     h = hip()
-    bufs = []
-    try:
-        d_ts = DeviceBuffer.from_array(ts); bufs.append(d_ts)
-        d_th = DeviceBuffer.from_array(thresh); bufs.append(d_th)
-        d_ev, d_st, d_en = (DeviceBuffer(4 * T * C) for _ in range(3))
-        d_b = DeviceBuffer(T * C)
-        bufs += [d_ev, d_st, d_en, d_b]
-        try:
+    with DeviceScope() as s:
+        d_ts, d_th = s.upload(ts), s.upload(thresh)
+        d_ev, d_st, d_en = s.alloc(4 * T * C), s.alloc(4 * T * C), s.alloc(4 * T * C)
+        d_b = s.alloc(T * C)
+        with as_xmhw_errors():
             h.detect_events(d_ts.ptr, ts.dtype.itemsize, T, C, C, d_th.ptr, C, rows,
                             int(minDuration), int(bool(joinGaps)), int(maxGap), int(bool(coldSpells)),
                             d_ev.ptr, d_st.ptr, d_en.ptr, d_b.ptr, C)
-        except h.InvalidArgument as e:
-            raise XmhwException(str(e)) from e
         ev = d_ev.to_array((T, C), np.int32)
         st = d_st.to_array((T, C), np.int32)
         en = d_en.to_array((T, C), np.int32)
         b = d_b.to_array((T, C), np.uint8).astype(bool)
-    finally:
-        for x in bufs:
-            x.free()
     return dict(bthresh=b, start=_nan_where_negative(st), end=_nan_where_negative(en),
                 events=_nan_where_negative(ev))
 
@@ -95,19 +87,16 @@ def _table_only_device(h, d_ts, isz, se_ptr, th_ptr, ldc, D, rows, T, n, neg, mi
     first of the n columns, leading dimension ldc) are already on the device, without per-step
     outputs: exceedance bits -> run walk (count, device prefix sum, fill) -> one thread per event
     (csrc/kernels_events.hip)."""
-    bufs = []
-    try:
+    with DeviceScope() as s:
         W = (T + 63) // 64
-        d_bits = DeviceBuffer(8 * W * n); bufs.append(d_bits)
-        d_n = DeviceBuffer(4 * n); bufs.append(d_n)
-        try:
+        d_bits = s.alloc(8 * W * n)
+        d_n = s.alloc(4 * n)
+        with as_xmhw_errors():
             h.exceed_bits(d_ts.ptr, isz, T, n, n, th_ptr, ldc, D, rows, neg, d_bits.ptr, n)
             h.events_from_bits(d_bits.ptr, T, n, n, int(minDuration), int(bool(joinGaps)), int(maxGap), 0, d_n.ptr, 0)
-        except h.InvalidArgument as e:
-            raise XmhwException(str(e)) from e
         # table offsets = exclusive prefix sum of the counts, on the device; the host only learns the
         # total (8 bytes) to size the table, and takes the counts along for its own bookkeeping
-        d_off = DeviceBuffer(8 * (n + 1)); bufs.append(d_off)
+        d_off = s.alloc(8 * (n + 1))
         h.offsets_from_counts(d_n.ptr, n, d_off.ptr)
         total = np.empty(1, dtype=np.int64)
         h.memcpy_d2h(total, d_off.ptr + 8 * n)          # synchronises the stream
@@ -115,29 +104,21 @@ def _table_only_device(h, d_ts, isz, se_ptr, th_ptr, ldc, D, rows, T, n, neg, mi
         counts = d_n.to_array((n,), np.int32)
         if ntot == 0:
             return np.zeros((0, h.EVENT_COLUMNS)), counts
-        d_tab = DeviceBuffer(8 * ntot * h.EVENT_COLUMNS); bufs.append(d_tab)
+        d_tab = s.alloc(8 * ntot * h.EVENT_COLUMNS)
         h.events_from_bits(d_bits.ptr, T, n, n, int(minDuration), int(bool(joinGaps)), int(maxGap), d_off.ptr, 0,
                            d_tab.ptr)
         h.event_stats_sparse(d_ts.ptr, isz, T, n, n, se_ptr, th_ptr, ldc, rows, neg, ntot, d_tab.ptr)
         return d_tab.to_array((ntot, h.EVENT_COLUMNS), np.float64), counts
-    finally:
-        for b in bufs:
-            b.free()
 
 
 def _table_only_batch(h, ts, seas, thresh, rows, T, n, isz, neg, minDuration, joinGaps, maxGap, pad=None):
-    bufs = []
-    try:
-        d_ts = DeviceBuffer.from_array(ts); bufs.append(d_ts)
+    with DeviceScope() as s:
+        d_ts = s.upload(ts)
         if pad is not None:
             apply_recipe_in_place(pad, d_ts.ptr, isz, T, n)
-        d_se = DeviceBuffer.from_array(seas); bufs.append(d_se)
-        d_th = DeviceBuffer.from_array(thresh); bufs.append(d_th)
+        d_se, d_th = s.upload(seas), s.upload(thresh)
         return _table_only_device(h, d_ts, isz, d_se.ptr, d_th.ptr, n, thresh.shape[0], rows, T, n, neg, minDuration,
                                   joinGaps, maxGap)
-    finally:
-        for b in bufs:
-            b.free()
 
 
 def detect_cells(ts, seas, thresh, doy, doys, minDuration=5, joinGaps=True, maxGap=2, coldSpells=False,
@@ -184,41 +165,35 @@ def detect_cells(ts, seas, thresh, doy, doys, minDuration=5, joinGaps=True, maxG
             tables.append(tab)
             counts_all.append(counts)
             continue
-        bufs = []
-        try:
-            d_ts = DeviceBuffer.from_array(np.ascontiguousarray(ts[:, c0:c1])); bufs.append(d_ts)
+        with DeviceScope() as s:
+            d_ts = s.upload(np.ascontiguousarray(ts[:, c0:c1]))
             if pad is not None:
                 apply_recipe_in_place(pad, d_ts.ptr, isz, T, n)
                 if intermediate:
                     filled = d_ts.to_array((T, n), ts.dtype)
                     inter["ts"][:, c0:c1] = -filled if coldSpells else filled
-            d_th = DeviceBuffer.from_array(np.ascontiguousarray(thresh[:, c0:c1])); bufs.append(d_th)
-            d_se = DeviceBuffer.from_array(np.ascontiguousarray(seas[:, c0:c1])); bufs.append(d_se)
-            d_ev, d_st, d_en = (DeviceBuffer(4 * T * n) for _ in range(3))
-            d_n = DeviceBuffer(4 * n)
-            bufs += [d_ev, d_st, d_en, d_n]
-            d_b = None
-            if intermediate:
-                d_b = DeviceBuffer(T * n); bufs.append(d_b)
-            try:
+            d_th = s.upload(np.ascontiguousarray(thresh[:, c0:c1]))
+            d_se = s.upload(np.ascontiguousarray(seas[:, c0:c1]))
+            d_ev, d_st, d_en = s.alloc(4 * T * n), s.alloc(4 * T * n), s.alloc(4 * T * n)
+            d_n = s.alloc(4 * n)
+            d_b = s.alloc(T * n) if intermediate else None
+            with as_xmhw_errors():
                 h.detect_events(d_ts.ptr, isz, T, n, n, d_th.ptr, n, rows, int(minDuration), int(bool(joinGaps)),
                                 int(maxGap), neg, d_ev.ptr, d_st.ptr, d_en.ptr, d_b.ptr if d_b else 0, n, d_n.ptr)
-            except h.InvalidArgument as e:
-                raise XmhwException(str(e)) from e
             h.stream_sync(0)
             counts = d_n.to_array((n,), np.int32)
             offs = np.zeros(n + 1, dtype=np.int64)
             np.cumsum(counts, out=offs[1:])
             ntot = int(offs[-1])
-            d_off = DeviceBuffer.from_array(offs); bufs.append(d_off)
-            d_tab = DeviceBuffer(8 * max(ntot, 1) * h.EVENT_COLUMNS); bufs.append(d_tab)
+            d_off = s.upload(offs)
+            d_tab = s.alloc(8 * max(ntot, 1) * h.EVENT_COLUMNS)
             h.event_stats(d_ts.ptr, isz, T, n, n, d_se.ptr, d_th.ptr, n, rows, neg, d_ev.ptr, n, d_off.ptr, d_tab.ptr)
             tables.append(d_tab.to_array((ntot, h.EVENT_COLUMNS), np.float64) if ntot
                           else np.zeros((0, h.EVENT_COLUMNS)))
             counts_all.append(counts)
             if intermediate:
-                d_out = DeviceBuffer(8 * len(INTERMEDIATE_F64) * T * n); bufs.append(d_out)
-                d_dur = DeviceBuffer(len(INTERMEDIATE_U8) * T * n); bufs.append(d_dur)
+                d_out = s.alloc(8 * len(INTERMEDIATE_F64) * T * n)
+                d_dur = s.alloc(len(INTERMEDIATE_U8) * T * n)
                 h.event_intermediate(d_ts.ptr, isz, T, n, n, d_se.ptr, d_th.ptr, n, rows, neg, d_ev.ptr, n,
                                      d_out.ptr, n, d_dur.ptr)
                 out = d_out.to_array((len(INTERMEDIATE_F64), T, n), np.float64)
@@ -229,9 +204,6 @@ def detect_cells(ts, seas, thresh, doy, doys, minDuration=5, joinGaps=True, maxG
                     inter[name][:, c0:c1] = dur[k] != 0
                 inter["events"][:, c0:c1] = _nan_where_negative(d_ev.to_array((T, n), np.int32))
                 inter["bthresh"][:, c0:c1] = d_b.to_array((T, n), np.uint8) != 0
-        finally:
-            for b in bufs:
-                b.free()
     counts = np.concatenate(counts_all) if counts_all else np.zeros(0, np.int32)
     offsets = np.zeros(C + 1, dtype=np.int64)
     np.cumsum(counts, out=offsets[1:])
@@ -260,15 +232,13 @@ def _recipe_through_device(ts, recipe, max_batch_bytes):
     cb = int(max(1, min(C, max_batch_bytes // max(1, 2 * T * isz))))
     for lo in range(0, C, cb):
         n = min(cb, C - lo)
-        d_ts = DeviceBuffer.from_array(np.ascontiguousarray(ts[:, lo:lo + n]))
-        try:
+        with DeviceScope() as s:
+            d_ts = s.upload(np.ascontiguousarray(ts[:, lo:lo + n]))
             f = recipe.apply(d_ts.ptr, isz, T, n)
             if f is not None:
                 failed[lo:lo + n] = f
             hip().stream_sync(0)
             out[:, lo:lo + n] = d_ts.to_array((T, n), ts.dtype)
-        finally:
-            d_ts.free()
     return out, failed
 
 
@@ -370,22 +340,20 @@ def detect_grid(stacked, anynans, seas, thresh, doy, doys, minDuration=5, joinGa
     h = hip()
     isz = device_itemsize(stacked)
     neg = int(bool(coldSpells))
-    clim_bufs = []
     keeps, tables, counts_all = [], [], []
     k0 = 0
-    try:
+    with DeviceScope() as clim, DeviceScope() as waiting:
         # the climatologies are small next to the series: whole on the device, compacted there if needed
         if clim_stacked:
             d_th, keep_th = compact_columns(thresh, 0, thresh.shape[1], anynans)
-            clim_bufs += [d_th] if d_th is not None else []
+            clim.adopt(d_th)
             d_se, keep_se = compact_columns(seas, 0, seas.shape[1], anynans)
-            clim_bufs += [d_se] if d_se is not None else []
+            clim.adopt(d_se)
             C, Cse = int(keep_th.sum()), int(keep_se.sum())
             if C == 0 or Cse == 0:
                 raise XmhwException("All points of grid are either land or NaN")
         else:
-            d_th = DeviceBuffer.from_array(thresh); clim_bufs.append(d_th)
-            d_se = DeviceBuffer.from_array(seas); clim_bufs.append(d_se)
+            d_th, d_se = clim.upload(thresh), clim.upload(seas)
             C, Cse = thresh.shape[1], seas.shape[1]
         if C != Cse:
             raise XmhwException(f"th and se do not have the same ocean cells: {C}, {Cse}")
@@ -395,52 +363,43 @@ def detect_grid(stacked, anynans, seas, thresh, doy, doys, minDuration=5, joinGa
         reuse = resident is not None and columns is None and resident.matches(rkey, c0, c1)
         if reuse:
             slabs = [b for b, _, _, _ in resident.slabs]
-        held = []                                   # sharded: compacted slabs wait for the offset exchange
-        try:
+        held = []                                   # sharded: compacted slabs wait (in `waiting`) for the offset exchange
+        if columns is not None:
+            for lo, hi in slabs:
+                d_ts, keep = compact_columns(stacked, lo, hi, anynans)
+                held.append((waiting.adopt(d_ts), keep))
+            k0, total = exchange(int(sum(int(k.sum()) for _, k in held)))
+            if total != C:
+                raise XmhwException(f"temp has {total} ocean cells, th and se have {C}")
+        first = k0
+        for i, (lo, hi) in enumerate(slabs):
             if columns is not None:
-                for lo, hi in slabs:
-                    d_ts, keep = compact_columns(stacked, lo, hi, anynans)
-                    held.append((d_ts, keep))
-                k0, total = exchange(int(sum(int(k.sum()) for _, k in held)))
-                if total != C:
-                    raise XmhwException(f"temp has {total} ocean cells, th and se have {C}")
-            first = k0
-            for i, (lo, hi) in enumerate(slabs):
-                if columns is not None:
-                    d_ts, keep = held[i]
-                    held[i] = (None, keep)
-                elif reuse:
-                    _, d_ts, keep, _ = resident.slabs[i]
-                else:
-                    _tl = _time.perf_counter()
-                    d_ts, keep = compact_columns(stacked, lo, hi, anynans)
-                    _trace(f"detect: upload + mask + compact [{lo},{hi})", _tl)
-                if pad is not None and not reuse and d_ts is not None:
-                    d_ts, keep = apply_recipe(pad, d_ts, isz, T, keep)      # (a retained slab already went through it)
-                keeps.append(keep)
-                n = int(keep.sum())
-                if d_ts is None:
-                    continue
-                try:
-                    if k0 + n > C:
-                        raise XmhwException(f"temp has more ocean cells than th and se ({C})")
-                    _tl = _time.perf_counter()
-                    tab, counts = _table_only_device(h, d_ts, isz, d_se.ptr + 8 * k0, d_th.ptr + 8 * k0, C, D, rows, T,
-                                                     n, neg, minDuration, joinGaps, maxGap)
-                    _trace(f"detect: bits + runs + event table ({tab.shape[0]} events)", _tl)
-                finally:
-                    if not reuse:
-                        d_ts.free()
-                tables.append(tab)
-                counts_all.append(counts)
-                k0 += n
-        finally:
-            for d_ts, _ in held:
-                if d_ts is not None:
-                    d_ts.free()
-    finally:
-        for b in clim_bufs:
-            b.free()
+                d_ts, keep = held[i]
+                waiting.release(d_ts)
+            elif reuse:
+                _, d_ts, keep, _ = resident.slabs[i]
+            else:
+                _tl = _time.perf_counter()
+                d_ts, keep = compact_columns(stacked, lo, hi, anynans)
+                _trace(f"detect: upload + mask + compact [{lo},{hi})", _tl)
+            if pad is not None and not reuse and d_ts is not None:
+                d_ts, keep = apply_recipe(pad, d_ts, isz, T, keep)      # (a retained slab already went through it)
+            keeps.append(keep)
+            n = int(keep.sum())
+            if d_ts is None:
+                continue
+            with DeviceScope() as s:
+                if not reuse:                       # (a retained slab stays the store's)
+                    s.adopt(d_ts)
+                if k0 + n > C:
+                    raise XmhwException(f"temp has more ocean cells than th and se ({C})")
+                _tl = _time.perf_counter()
+                tab, counts = _table_only_device(h, d_ts, isz, d_se.ptr + 8 * k0, d_th.ptr + 8 * k0, C, D, rows, T,
+                                                 n, neg, minDuration, joinGaps, maxGap)
+                _trace(f"detect: bits + runs + event table ({tab.shape[0]} events)", _tl)
+            tables.append(tab)
+            counts_all.append(counts)
+            k0 += n
     _trace("detect_grid: all slabs", _t_all)
     keep = np.concatenate(keeps) if keeps else np.zeros(0, dtype=bool)
     if columns is None:

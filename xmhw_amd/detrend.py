@@ -141,19 +141,16 @@ class DetrendSpec:
         (or DeviceBuffers) that receive coef[P][C] float64 and nvalid[C] int32; without ``coef_out`` the
         coefficients live in a buffer of this call.  Returns the mask of the cells that FAILED (bool, C)."""
         from ._lib import hip
-        from .device import DeviceBuffer
+        from .device import DeviceScope, _ptr as ptr
         if T != self.T:
             raise ValueError("series and time axis differ in length")
         if C == 0 or T == 0:
             return np.zeros(C, dtype=bool)
         h = hip()
         d_basis, d_w = self._upload()
-        ptr = lambda b: b.ptr if hasattr(b, "ptr") else int(b)
-        own = None
-        try:
+        with DeviceScope() as s:
             if coef_out is None:
-                own = DeviceBuffer(8 * self.P * C)
-                coef_out = own
+                coef_out = s.alloc(8 * self.P * C)
             ld = int(C if ld is None else ld)
             h.series_fit(int(d_ts_ptr), int(itemsize), int(T), int(C), ld, d_basis.ptr, self.P,
                          d_w.ptr if d_w is not None else 0, self.min_valid, ptr(coef_out), int(C),
@@ -163,9 +160,6 @@ class DetrendSpec:
             first = np.empty(C, dtype=np.float64)
             h.memcpy_d2h(first, ptr(coef_out), stream)          # the first coefficient row: NaN = failed (synchronises)
             return np.isnan(first)
-        finally:
-            if own is not None:
-                own.free()
 
     def free(self):
         if self._dev is not None:
@@ -212,7 +206,7 @@ def make_spec(detrend, time):
 def detrend_cells_device(ts, spec, max_batch_bytes=32 << 30):
     """Device stage on a dense host (T, C) series: (detrended (T, C) of ts' dtype, coef (P, C), n_valid (C,))."""
     from ._lib import hip
-    from .device import DeviceBuffer, native_float
+    from .device import DeviceScope, native_float
     ts = np.ascontiguousarray(native_float(ts))
     T, C = ts.shape
     isz = ts.dtype.itemsize
@@ -223,19 +217,14 @@ def detrend_cells_device(ts, spec, max_batch_bytes=32 << 30):
     h = hip()
     for lo in range(0, C, cb):
         n = min(cb, C - lo)
-        bufs = []
-        try:
-            d_ts = DeviceBuffer.from_array(np.ascontiguousarray(ts[:, lo:lo + n])); bufs.append(d_ts)
-            d_coef = DeviceBuffer(8 * spec.P * n); bufs.append(d_coef)
-            d_nv = DeviceBuffer(4 * n); bufs.append(d_nv)
+        with DeviceScope() as s:
+            d_ts = s.upload(np.ascontiguousarray(ts[:, lo:lo + n]))
+            d_coef, d_nv = s.alloc(8 * spec.P * n), s.alloc(4 * n)
             spec.apply(d_ts.ptr, isz, T, n, coef_out=d_coef, nvalid_out=d_nv)
             h.stream_sync(0)
             out[:, lo:lo + n] = d_ts.to_array((T, n), ts.dtype)
             coef[:, lo:lo + n] = d_coef.to_array((spec.P, n), np.float64)
             nvalid[lo:lo + n] = d_nv.to_array((n,), np.int32)
-        finally:
-            for b in bufs:
-                b.free()
     return out, coef, nvalid
 
 
@@ -244,7 +233,7 @@ def detrend_grid_device(stacked, spec, anynans, max_batch_bytes=None):
     budget: mask and compaction on the device as in threshold().  Returns (keep[N], detrended (T, N) with NaN at
     the dropped cells, coef (P, N) NaN there, n_valid (N,) 0 there)."""
     from ._lib import hip
-    from .device import (DeviceBuffer, SlabPrefetcher, _grid_batch, device_itemsize, is_packed, mask_compact,
+    from .device import (DeviceScope, SlabPrefetcher, _grid_batch, device_itemsize, is_packed, mask_compact,
                          native_float)
     if is_packed(stacked):
         if stacked.ndim != 2 or stacked.strides[1] != stacked.dtype.itemsize:
@@ -270,10 +259,9 @@ def detrend_grid_device(stacked, spec, anynans, max_batch_bytes=None):
             if d_ts is None:
                 continue
             n = int(keep.sum())
-            bufs = [d_ts]
-            try:
-                d_coef = DeviceBuffer(8 * spec.P * n); bufs.append(d_coef)
-                d_nv = DeviceBuffer(4 * n); bufs.append(d_nv)
+            with DeviceScope() as s:
+                s.adopt(d_ts)
+                d_coef, d_nv = s.alloc(8 * spec.P * n), s.alloc(4 * n)
                 spec.apply(d_ts.ptr, isz, T, n, coef_out=d_coef, nvalid_out=d_nv)
                 h.stream_sync(0)
                 cols = lo + np.nonzero(keep)[0]
@@ -283,9 +271,6 @@ def detrend_grid_device(stacked, spec, anynans, max_batch_bytes=None):
                     out[:, cols] = d_ts.to_array((T, n), dt)
                 coef[:, cols] = d_coef.to_array((spec.P, n), np.float64)
                 nvalid[cols] = d_nv.to_array((n,), np.int32)
-            finally:
-                for b in bufs:
-                    b.free()
     finally:
         pre.close()
     keep = np.concatenate(keeps) if keeps else np.zeros(0, dtype=bool)

@@ -1,5 +1,12 @@
 """Thin object layer over the C ABI: device buffers, plans, and the two
 device-side stages of calc_clim() (xmhw/xmhw.py:250-307)."""
+import os as _os
+import sys
+import threading as _threading
+import time as _time
+from concurrent.futures import ThreadPoolExecutor
+from contextlib import contextmanager
+
 import numpy as np
 
 from ._lib import hip
@@ -66,16 +73,17 @@ def native_float(a):
 # total are held (XMHW_AMD_POOL_GB overrides the total; 0 disables the cache); entries carry the
 # device they were ALLOCATED on.  release_device_cache() frees them; every entry point of the C ABI
 # that runs out of device memory calls it and retries once (xmhw_amd._lib).
-import os as _os
-
-import threading as _threading
-
 _POOL = []
 _POOL_LOCK = _threading.Lock()      # the upload thread of the slab pipeline allocates while the main thread frees
 _POOL_SLOTS = 4
 _POOL_MIN = 1 << 30
 _POOL_MAX_BYTES = int(float(_os.environ.get("XMHW_AMD_POOL_GB", "96")) * (1 << 30))
 _TRACE = _os.environ.get("XMHW_AMD_TRACE", "0") != "0"
+
+
+def _trace(label, t0):
+    if _TRACE:
+        print(f"[xmhw_amd] {label}: {_time.perf_counter() - t0:.3f} s", file=sys.stderr, flush=True)
 
 
 def release_device_cache():
@@ -121,13 +129,10 @@ class DeviceBuffer:
                         self.capacity, self.ptr = cap, ptr
                         return
                     _POOL.append((cap, ptr, dev))
-        if _TRACE and self.nbytes >= _POOL_MIN:
-            import time as _time
-            _t0 = _time.perf_counter()
-            self.ptr = self._h.malloc(self.nbytes)
-            _trace(f"hipMalloc {self.nbytes / 1e9:.2f} GB (pool: {[round(c / 1e9, 2) for c, _, _ in _POOL]})", _t0)
-            return
+        _t0 = _time.perf_counter()
         self.ptr = self._h.malloc(self.nbytes)   # out of memory: the pool is drained and the call retried (_lib)
+        if self.nbytes >= _POOL_MIN:
+            _trace(f"hipMalloc {self.nbytes / 1e9:.2f} GB (pool: {[round(c / 1e9, 2) for c, _, _ in _POOL]})", _t0)
 
     @classmethod
     def from_array(cls, a):
@@ -154,15 +159,11 @@ class DeviceBuffer:
                             and sum(c for c, _, _ in _POOL) + self.capacity <= _POOL_MAX_BYTES):
                         _POOL.append((self.capacity, self.ptr, self.device))
                         kept = True
-            if kept:
-                pass
-            elif _TRACE and self.capacity >= _POOL_MIN:
-                import time as _time
+            if not kept:
                 _t0 = _time.perf_counter()
                 self._h.free(self.ptr)
-                _trace(f"hipFree {self.capacity / 1e9:.2f} GB (pool: {[round(c / 1e9, 2) for c, _, _ in _POOL]})", _t0)
-            else:
-                self._h.free(self.ptr)
+                if self.capacity >= _POOL_MIN:
+                    _trace(f"hipFree {self.capacity / 1e9:.2f} GB (pool: {[round(c / 1e9, 2) for c, _, _ in _POOL]})", _t0)
             self.ptr = 0
 
     def __del__(self):
@@ -170,6 +171,60 @@ class DeviceBuffer:
             self.free()
         except Exception:
             pass
+
+
+class DeviceScope:
+    """The device buffers of one call: ``with DeviceScope() as s`` frees, on the way out and in every case, what the
+    scope still owns, in the order it came to own it.  Buffers only: exceptions pass through untouched."""
+
+    def __init__(self):
+        self._owned = []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+        return False
+
+    def alloc(self, nbytes):
+        return self.adopt(DeviceBuffer(nbytes))
+
+    def upload(self, array):
+        return self.adopt(DeviceBuffer.from_array(array))
+
+    def adopt(self, buf):
+        """own a buffer made elsewhere (a slab of compact_columns, of the prefetcher); None passes through"""
+        if buf is not None:
+            self._owned.append(buf)
+        return buf
+
+    def release(self, buf):
+        """hand a buffer back to the caller: the scope no longer frees it"""
+        self._owned = [b for b in self._owned if b is not buf]
+        return buf
+
+    def free(self):
+        owned, self._owned = self._owned, []
+        for b in owned:
+            b.free()
+
+
+@contextmanager
+def as_xmhw_errors(also=None, hint=None):
+    """The bindings' InvalidArgument raised inside becomes an XmhwException with the same text; ``also`` names one
+    more exception of the bindings to treat alike ("Unsupported", or "HipError" for all of them).  ``hint`` is
+    appended to an Unsupported (XMHW_ERR_UNSUPPORTED).  Everything else passes through."""
+    h = hip()
+    kinds = (h.InvalidArgument, getattr(h, also)) if also else h.InvalidArgument
+    try:
+        yield
+    except kinds as e:
+        raise XmhwException(f"{e}: {hint}" if hint and isinstance(e, h.Unsupported) else str(e)) from e
+
+
+def _ptr(b):
+    return b.ptr if hasattr(b, "ptr") else int(b)
 
 
 # include/xmhw_amd.h: XMHW_LAYOUT_*
@@ -183,10 +238,8 @@ class Plan:
     def __init__(self, doy, window_half_width, kernel="auto", nchunks=0, narrowing=True, ring2=None, layout=None):
         self._h = hip()
         doy = np.ascontiguousarray(doy, dtype=np.int32)
-        try:
+        with as_xmhw_errors():
             self.handle = self._h.plan_create(doy, int(window_half_width))
-        except self._h.InvalidArgument as e:
-            raise XmhwException(str(e)) from e
         self._h.plan_set_kernel(self.handle, KERNELS[kernel])
         self._h.plan_set_chunks(self.handle, int(nchunks))
         self._h.plan_set_narrowing(self.handle, int(bool(narrowing)))
@@ -239,15 +292,9 @@ class Plan:
 
 
 def clim_raw(plan, ts_dev, itemsize, C, q, negate, thresh_dev, seas_dev, ld=None, ldo=None, stream=0):
-    h = hip()
-    try:
-        h.clim_raw(plan.handle, ts_dev.ptr if hasattr(ts_dev, "ptr") else int(ts_dev), itemsize, C,
-                   C if ld is None else ld, float(q), int(bool(negate)),
-                   thresh_dev.ptr if hasattr(thresh_dev, "ptr") else int(thresh_dev),
-                   seas_dev.ptr if hasattr(seas_dev, "ptr") else int(seas_dev),
-                   C if ldo is None else ldo, stream)
-    except h.InvalidArgument as e:
-        raise XmhwException(str(e)) from e
+    with as_xmhw_errors():
+        hip().clim_raw(plan.handle, _ptr(ts_dev), itemsize, C, C if ld is None else ld, float(q), int(bool(negate)),
+                       _ptr(thresh_dev), _ptr(seas_dev), C if ldo is None else ldo, stream)
 
 
 def clim_raw_packed(plan, codes_dev, C, q, negate, thresh_dev, seas_dev, scale_factor=None, add_offset=None, fill=None,
@@ -255,26 +302,36 @@ def clim_raw_packed(plan, codes_dev, C, q, negate, thresh_dev, seas_dev, scale_f
     """xmhw_clim_raw_i16: the raw climatology of an int16-packed series read in place (CF packing attributes as xarray
     would apply them before threshold() sees the data; `decoded` = the dtype it would decode to).  Raises XmhwException
     where the sorted-list kernel does not serve the plan or the quantile: decode first (hip().decode) and use clim_raw."""
-    h = hip()
-    p = lambda b: b.ptr if hasattr(b, "ptr") else int(b)
     has_scale = scale_factor is not None or add_offset is not None
-    try:
-        h.clim_raw_i16(plan.handle, p(codes_dev), C, C if ld is None else ld, int(bool(big_endian)), int(has_scale),
-                       1.0 if scale_factor is None else float(scale_factor), 0.0 if add_offset is None else float(add_offset),
-                       int(fill is not None), 0 if fill is None else int(fill), 8 if str(decoded) in ("float64", "f64", "8") else 4,
-                       float(q), int(bool(negate)), p(thresh_dev), p(seas_dev), C if ldo is None else ldo, stream)
-    except (h.InvalidArgument, h.HipError) as e:       # (HipError: XMHW_ERR_UNSUPPORTED -- the plan is not the sorted kernel's)
-        raise XmhwException(str(e)) from e
+    with as_xmhw_errors(also="HipError"):       # (HipError: XMHW_ERR_UNSUPPORTED -- the plan is not the sorted kernel's)
+        hip().clim_raw_i16(plan.handle, _ptr(codes_dev), C, C if ld is None else ld, int(bool(big_endian)), int(has_scale),
+                           1.0 if scale_factor is None else float(scale_factor), 0.0 if add_offset is None else float(add_offset),
+                           int(fill is not None), 0 if fill is None else int(fill), 8 if str(decoded) in ("float64", "f64", "8") else 4,
+                           float(q), int(bool(negate)), _ptr(thresh_dev), _ptr(seas_dev), C if ldo is None else ldo, stream)
 
 
 def clim_finish(plan, th_in, se_in, C, feb29_fix, smooth, width, th_out, se_out, ldo=None, stream=0):
-    h = hip()
-    p = lambda b: b.ptr if hasattr(b, "ptr") else int(b)
-    try:
-        h.clim_finish(plan.handle, p(th_in), p(se_in), C, C if ldo is None else ldo, int(bool(feb29_fix)),
-                      int(bool(smooth)), int(width), p(th_out), p(se_out), stream)
-    except h.InvalidArgument as e:
-        raise XmhwException(str(e)) from e
+    with as_xmhw_errors():
+        hip().clim_finish(plan.handle, _ptr(th_in), _ptr(se_in), C, C if ldo is None else ldo, int(bool(feb29_fix)),
+                          int(bool(smooth)), int(width), _ptr(th_out), _ptr(se_out), stream)
+
+
+def _clim_on_device(scope, plan, d_ts, isz, n, q, negate, finish, raw=None, out=None, recipe=None):
+    """The climatology of n cells whose dense series is on the device: the raw kernel (on int16 codes read in place
+    where ``recipe`` = their packed_recipe()), then, for ``finish`` = (feb29_fix, smooth, width) instead of None, the
+    finish kernels.  ``raw`` / ``out``: the (thresh, seas) pair of buffers or device pointers each stage writes;
+    a missing pair is allocated in ``scope`` when its stage runs.  Returns the pair that holds the result."""
+    raw_th, raw_se = raw or (scope.alloc(8 * plan.D * n), scope.alloc(8 * plan.D * n))
+    if recipe is not None:
+        clim_raw_packed(plan, d_ts, n, q, negate, raw_th, raw_se, scale_factor=recipe["scale"], add_offset=recipe["offset"],
+                        fill=recipe["fill"], decoded=recipe["decoded"], big_endian=recipe["big_endian"])
+    else:
+        clim_raw(plan, d_ts, isz, n, q, negate, raw_th, raw_se)
+    if finish is None:
+        return raw_th, raw_se
+    out_th, out_se = out or (scope.alloc(8 * plan.D * n), scope.alloc(8 * plan.D * n))
+    clim_finish(plan, raw_th, raw_se, n, *finish, out_th, out_se)
+    return out_th, out_se
 
 
 def calc_clim_device(ts, doy, pctile, windowHalfWidth, smoothPercentile, smoothPercentileWidth,
@@ -296,46 +353,37 @@ def calc_clim_device(ts, doy, pctile, windowHalfWidth, smoothPercentile, smoothP
     T, C = ts.shape
     h = hip()
     plan = Plan(doy, windowHalfWidth, kernel=kernel, nchunks=nchunks, narrowing=narrowing)
-    bufs = []
     try:
-        D = plan.D
-        th = np.empty((D, C), dtype=np.float64)
-        se = np.empty((D, C), dtype=np.float64)
-        if C == 0:
+        with DeviceScope() as s:
+            D = plan.D
+            th = np.empty((D, C), dtype=np.float64)
+            se = np.empty((D, C), dtype=np.float64)
+            if C == 0:
+                return plan.doys.copy(), th, se
+            isz = ts.dtype.itemsize
+            cb = int(max(1, min(C, max_batch_bytes // max(1, T * isz))))
+            feb29_fix = tstep is False
+            finish = (feb29_fix, smoothPercentile, smoothPercentileWidth) if feb29_fix or smoothPercentile else None
+            # one set of buffers, sized for a full batch, serves every batch
+            d_ts = s.alloc(isz * T * cb)
+            raw = s.alloc(8 * D * cb), s.alloc(8 * D * cb)
+            out = (s.alloc(8 * D * cb), s.alloc(8 * D * cb)) if finish else None
+            for lo in range(0, C, cb):
+                n = min(cb, C - lo)
+                slab = np.ascontiguousarray(ts[:, lo:lo + n])
+                h.memcpy_h2d(d_ts.ptr, slab)
+                if pad is not None:
+                    apply_recipe_in_place(pad, d_ts.ptr, isz, T, n)
+                out_th, out_se = _clim_on_device(s, plan, d_ts, isz, n, pctile / 100.0, coldSpells, finish, raw=raw, out=out)
+                h.stream_sync(0)
+                bt = np.empty((D, n), dtype=np.float64)
+                bs = np.empty((D, n), dtype=np.float64)
+                h.memcpy_d2h(bt, out_th.ptr)
+                h.memcpy_d2h(bs, out_se.ptr)
+                th[:, lo:lo + n] = bt
+                se[:, lo:lo + n] = bs
             return plan.doys.copy(), th, se
-        isz = ts.dtype.itemsize
-        cb = int(max(1, min(C, max_batch_bytes // max(1, T * isz))))
-        feb29_fix = tstep is False
-        finish = feb29_fix or smoothPercentile
-        d_ts = DeviceBuffer(isz * T * cb)
-        raw_th, raw_se = DeviceBuffer(8 * D * cb), DeviceBuffer(8 * D * cb)
-        bufs += [d_ts, raw_th, raw_se]
-        if finish:
-            out_th, out_se = DeviceBuffer(8 * D * cb), DeviceBuffer(8 * D * cb)
-            bufs += [out_th, out_se]
-        else:
-            out_th, out_se = raw_th, raw_se
-        for lo in range(0, C, cb):
-            n = min(cb, C - lo)
-            slab = np.ascontiguousarray(ts[:, lo:lo + n])
-            h.memcpy_h2d(d_ts.ptr, slab)
-            if pad is not None:
-                apply_recipe_in_place(pad, d_ts.ptr, isz, T, n)
-            clim_raw(plan, d_ts, isz, n, pctile / 100.0, coldSpells, raw_th, raw_se)
-            if finish:
-                clim_finish(plan, raw_th, raw_se, n, feb29_fix, smoothPercentile, smoothPercentileWidth,
-                            out_th, out_se)
-            h.stream_sync(0)
-            bt = np.empty((D, n), dtype=np.float64)
-            bs = np.empty((D, n), dtype=np.float64)
-            h.memcpy_d2h(bt, out_th.ptr)
-            h.memcpy_d2h(bs, out_se.ptr)
-            th[:, lo:lo + n] = bt
-            se[:, lo:lo + n] = bs
-        return plan.doys.copy(), th, se
     finally:
-        for b in bufs:
-            b.free()
         plan.destroy()
 
 
@@ -350,13 +398,6 @@ _USE_STAGING = _os.environ.get("XMHW_AMD_STAGING", "1") != "0"
 _USE_PREAD = _os.environ.get("XMHW_AMD_PREAD", "1") != "0"
 _STAGE_BYTES = int(_os.environ.get("XMHW_AMD_STAGE_MB", "256")) << 20   # per buffer, two of them; 128-1024 MB measured alike, the small ones ramp up faster per slab
 _STAGE_THREADS = int(_os.environ.get("XMHW_AMD_STAGE_THREADS", "32"))
-
-
-def _trace(label, t0):
-    if _TRACE:
-        import sys
-        import time
-        print(f"[xmhw_amd] {label}: {time.perf_counter() - t0:.3f} s", file=sys.stderr, flush=True)
 _STAGE_MIN = 256 << 20
 
 
@@ -365,7 +406,6 @@ def _stage():
     dev = h.get_device()
     st = _STAGE.get(dev)
     if st is None:
-        from concurrent.futures import ThreadPoolExecutor
         ptrs = [h.host_alloc(_STAGE_BYTES) for _ in range(2)]
         st = dict(ptrs=ptrs, views=[h.host_view(p, _STAGE_BYTES) for p in ptrs],
                   events=[h.event_create(), h.event_create()], stream=h.stream_create(),
@@ -438,14 +478,13 @@ def upload_columns(stacked, lo, hi, raw=False):
     DECODED dtype: a pitched upload of the raw bytes, then -- for file views (PackedArray: big-endian
     and / or CF-packed samples) -- the decode kernel.  Returns (DeviceBuffer, itemsize).
     ``raw=True``: the stored bytes as they are (int16 codes for the kernels that read them in place)."""
-    import time as _time
     h = hip()
     T = stacked.shape[0]
     n = hi - lo
     raw_isz = stacked.dtype.itemsize
     _t0 = _time.perf_counter()
-    d_raw = DeviceBuffer(raw_isz * T * n)
-    try:
+    with DeviceScope() as s:
+        d_raw = s.alloc(raw_isz * T * n)
         if raw_isz * T * n >= _STAGE_MIN and _USE_STAGING:
             _staged_upload(d_raw.ptr, np.asarray(stacked)[:, lo:hi],
                            file=stacked.decode.get("file") if is_packed(stacked) else None)
@@ -455,8 +494,7 @@ def upload_columns(stacked, lo, hi, raw=False):
             h.memcpy2d_h2d(d_raw.ptr, np.asarray(stacked), lo, n)
         _trace(f"upload columns [{lo},{hi}) {raw_isz * T * n / 1e9:.2f} GB", _t0)
         if raw or not is_packed(stacked):
-            out, d_raw = d_raw, None
-            return out, raw_isz
+            return s.release(d_raw), raw_isz
         d = stacked.decode
         out_isz = np.dtype(d["out"]).itemsize
         big = stacked.dtype.byteorder == ">" or (stacked.dtype.byteorder == "=" and not np.little_endian)
@@ -465,51 +503,50 @@ def upload_columns(stacked, lo, hi, raw=False):
             raise XmhwException(f"stored type {stacked.dtype} is not supported by the device decoder")
         plain = (kind == "f" and not big and d.get("scale") is None and d.get("fill") is None and out_isz == raw_isz)
         if plain:
-            out, d_raw = d_raw, None
-            return out, raw_isz
-        d_out = DeviceBuffer(out_isz * T * n)
-        try:
-            h.decode(d_raw.ptr, raw_isz, int(big), T, n, n, d_out.ptr, out_isz, n, d.get("scale") is not None,
-                     float(d.get("scale") or 1.0), float(d.get("offset") or 0.0), d.get("fill") is not None,
-                     float(d.get("fill") or 0.0))
-            h.stream_sync(0)
-            out, d_out = d_out, None
-            return out, out_isz
-        finally:
-            if d_out is not None:
-                d_out.free()
-    finally:
-        if d_raw is not None:
-            d_raw.free()
-
-
-def mask_compact(d_raw, isz, T, n, anynans):
-    """land_check()'s dropna + compaction (xmhw/identify.py:520-525) of a dense device (T, n) array:
-    land_mask kernel, gather of the surviving columns.  Consumes d_raw.  Returns (DeviceBuffer holding
-    the dense (T, n_keep) array or None if n_keep == 0, keep mask)."""
-    h = hip()
-    d_mask = d_idx = d_out = None
-    try:
-        d_mask = DeviceBuffer(n)
-        h.land_mask(d_raw.ptr, isz, T, n, n, int(bool(anynans)), d_mask.ptr)
+            return s.release(d_raw), raw_isz
+        d_out = s.alloc(out_isz * T * n)
+        h.decode(d_raw.ptr, raw_isz, int(big), T, n, n, d_out.ptr, out_isz, n, d.get("scale") is not None,
+                 float(d.get("scale") or 1.0), float(d.get("offset") or 0.0), d.get("fill") is not None,
+                 float(d.get("fill") or 0.0))
         h.stream_sync(0)
+        return s.release(d_out), out_isz
+
+
+def _gather_columns(d_src, isz, T, n, idx):
+    """The columns idx (int64, ascending) of the dense device (T, n) array d_src as a dense (T, len(idx)) buffer of
+    the caller's."""
+    h = hip()
+    with DeviceScope() as s:
+        d_idx = s.upload(idx)
+        d_out = s.alloc(isz * T * idx.size)
+        h.gather_cells(d_src.ptr, isz, T, n, d_idx.ptr, idx.size, d_out.ptr, idx.size)
+        h.stream_sync(0)
+        return s.release(d_out)
+
+
+def _compact(d_raw, isz, T, n, launch_mask):
+    """Compaction of a dense device (T, n) array: ``launch_mask(d_mask)`` starts the kernel that writes the n keep
+    flags, the surviving columns are gathered.  Consumes d_raw.  Returns (DeviceBuffer holding the dense (T, n_keep)
+    array or None if n_keep == 0, keep mask)."""
+    with DeviceScope() as s:
+        s.adopt(d_raw)
+        d_mask = s.alloc(n)
+        launch_mask(d_mask)
+        hip().stream_sync(0)
         keep = d_mask.to_array((n,), np.uint8) != 0
         nk = int(keep.sum())
         if nk == n:
-            out, d_raw = d_raw, None
-            return out, keep
+            return s.release(d_raw), keep
         if nk == 0:
             return None, keep
-        d_idx = DeviceBuffer.from_array(np.nonzero(keep)[0].astype(np.int64))
-        d_out = DeviceBuffer(isz * T * nk)
-        h.gather_cells(d_raw.ptr, isz, T, n, d_idx.ptr, nk, d_out.ptr, nk)
-        h.stream_sync(0)
-        out, d_out = d_out, None
-        return out, keep
-    finally:
-        for b in (d_raw, d_mask, d_idx, d_out):
-            if b is not None:
-                b.free()
+        return _gather_columns(d_raw, isz, T, n, np.nonzero(keep)[0].astype(np.int64)), keep
+
+
+def mask_compact(d_raw, isz, T, n, anynans):
+    """land_check()'s dropna + compaction (xmhw/identify.py:520-525) of a dense device (T, n) array: land_mask
+    kernel, then _compact()."""
+    return _compact(d_raw, isz, T, n,
+                    lambda d_mask: hip().land_mask(d_raw.ptr, isz, T, n, n, int(bool(anynans)), d_mask.ptr))
 
 
 def apply_recipe_in_place(pad, d_ts_ptr, isz, T, n):
@@ -533,21 +570,11 @@ def apply_recipe(pad, d_ts, isz, T, keep):
     keep = keep.copy()
     keep[np.nonzero(keep)[0][failed]] = False
     ok = np.nonzero(~failed)[0].astype(np.int64)
-    d_idx = d_out = None
-    try:
+    with DeviceScope() as s:
+        s.adopt(d_ts)
         if ok.size == 0:
             return None, keep
-        h = hip()
-        d_idx = DeviceBuffer.from_array(ok)
-        d_out = DeviceBuffer(isz * T * ok.size)
-        h.gather_cells(d_ts.ptr, isz, T, n, d_idx.ptr, ok.size, d_out.ptr, ok.size)
-        h.stream_sync(0)
-        out, d_out = d_out, None
-        return out, keep
-    finally:
-        for b in (d_ts, d_idx, d_out):
-            if b is not None:
-                b.free()
+        return _gather_columns(d_ts, isz, T, n, ok), keep
 
 
 def packed_recipe(stacked):
@@ -564,30 +591,9 @@ def packed_recipe(stacked):
 
 def mask_compact_codes(d_raw, T, n, anynans, recipe):
     """mask_compact() on int16 codes: a sample is missing when its code is the fill code"""
-    h = hip()
-    d_mask = d_idx = d_out = None
-    try:
-        d_mask = DeviceBuffer(n)
-        h.land_mask_i16(d_raw.ptr, T, n, n, int(recipe["big_endian"]), int(recipe["fill"] is not None),
-                        0 if recipe["fill"] is None else recipe["fill"], int(bool(anynans)), d_mask.ptr)
-        h.stream_sync(0)
-        keep = d_mask.to_array((n,), np.uint8) != 0
-        nk = int(keep.sum())
-        if nk == n:
-            out, d_raw = d_raw, None
-            return out, keep
-        if nk == 0:
-            return None, keep
-        d_idx = DeviceBuffer.from_array(np.nonzero(keep)[0].astype(np.int64))
-        d_out = DeviceBuffer(2 * T * nk)
-        h.gather_cells(d_raw.ptr, 2, T, n, d_idx.ptr, nk, d_out.ptr, nk)
-        h.stream_sync(0)
-        out, d_out = d_out, None
-        return out, keep
-    finally:
-        for b in (d_raw, d_mask, d_idx, d_out):
-            if b is not None:
-                b.free()
+    return _compact(d_raw, 2, T, n, lambda d_mask: hip().land_mask_i16(
+        d_raw.ptr, T, n, n, int(recipe["big_endian"]), int(recipe["fill"] is not None),
+        0 if recipe["fill"] is None else recipe["fill"], int(bool(anynans)), d_mask.ptr))
 
 
 def compact_columns(stacked, lo, hi, anynans):
@@ -654,9 +660,7 @@ class SlabPrefetcher:
     thread, not a second stream; the bindings release the GIL during copies."""
 
     def __init__(self, stacked, slabs, raw=False):
-        import threading
         self._stacked, self._slabs, self._raw = stacked, list(slabs), bool(raw)
-        self._threading = threading
         self._next = None
         self._start(0)
 
@@ -674,7 +678,7 @@ class SlabPrefetcher:
             except BaseException as e:                     # noqa: BLE001 -- re-raised in the consumer
                 box["err"] = e
 
-        t = self._threading.Thread(target=work, daemon=True)
+        t = _threading.Thread(target=work, daemon=True)
         t.start()
         self._next = (i, t, box)
 
@@ -731,14 +735,12 @@ def _prefault(*arrays):
     page on its first write (6 GB for a global 0.25 degree grid, 0.23 s inside the first device-to-host
     copy otherwise), and that can happen while the first slab is still on its way to the device.
     The toucher writes zeros, so the caller JOINS the returned thread before the first result is stored."""
-    import threading
-
     def touch():
         for a in arrays:
             flat = a.reshape(-1)
             flat[::512] = 0.0            # one write per 4 KB (numpy releases the GIL for the strided fill)
 
-    t = threading.Thread(target=touch, daemon=True)
+    t = _threading.Thread(target=touch, daemon=True)
     t.start()
     return t
 
@@ -751,48 +753,29 @@ def _grid_block_on_device(plan, stacked, c0, c1, anynans, pctile, coldSpells, fe
     isz = device_itemsize(stacked)     # the DECODED item size (an int16 CF-packed archive arrives as float32)
     if w == 0:                         # more ranks than columns: a zero-byte block, nothing to send
         return np.zeros(0, dtype=bool), plan.doys.copy(), DeviceBuffer(0), None
-    block = DeviceBuffer(8 * 2 * D * w)
-    bufs = []
-    try:
+    with DeviceScope() as s:
+        block = s.alloc(8 * 2 * D * w)
         d_ts, keep = compact_columns(stacked, c0, c1, anynans)
         n = int(keep.sum())
         if d_ts is None:
             h.scatter_cells(0, 2 * D, 1, 0, 0, block.ptr, w)          # all land: a block of NaN
             h.stream_sync(0)
-            return keep, plan.doys.copy(), block, None
-        bufs.append(d_ts)
+            return keep, plan.doys.copy(), s.release(block), None
+        s.adopt(d_ts)
         if pad is not None:
             apply_recipe_in_place(pad, d_ts.ptr, isz, stacked.shape[0], n)
-        raw_th, raw_se = DeviceBuffer(8 * D * n), DeviceBuffer(8 * D * n)
-        bufs += [raw_th, raw_se]
-        clim_raw(plan, d_ts, isz, n, pctile / 100.0, coldSpells, raw_th, raw_se)
-        finish = feb29_fix or smooth
+        finish = (feb29_fix, smooth, width) if feb29_fix or smooth else None
         th_ptr, se_ptr = block.ptr, block.ptr + 8 * D * w
-        if n == w:
-            # no land in the block: the finish kernel (or a copy) writes the block directly
-            if finish:
-                clim_finish(plan, raw_th, raw_se, n, feb29_fix, smooth, width, th_ptr, se_ptr)
-            else:
-                idx = DeviceBuffer.from_array(np.arange(n, dtype=np.int64)); bufs.append(idx)
-                h.scatter_cells(raw_th.ptr, D, n, idx.ptr, n, th_ptr, w)
-                h.scatter_cells(raw_se.ptr, D, n, idx.ptr, n, se_ptr, w)
+        if n == w and finish:
+            # no land in the block: the finish kernel writes the block directly
+            _clim_on_device(s, plan, d_ts, isz, n, pctile / 100.0, coldSpells, finish, out=(th_ptr, se_ptr))
         else:
-            out_th, out_se = raw_th, raw_se
-            if finish:
-                out_th, out_se = DeviceBuffer(8 * D * n), DeviceBuffer(8 * D * n)
-                bufs += [out_th, out_se]
-                clim_finish(plan, raw_th, raw_se, n, feb29_fix, smooth, width, out_th, out_se)
-            idx = DeviceBuffer.from_array(np.nonzero(keep)[0].astype(np.int64)); bufs.append(idx)
+            out_th, out_se = _clim_on_device(s, plan, d_ts, isz, n, pctile / 100.0, coldSpells, finish)
+            idx = s.upload(np.nonzero(keep)[0].astype(np.int64))      # (every column where the block has no land)
             h.scatter_cells(out_th.ptr, D, n, idx.ptr, n, th_ptr, w)
             h.scatter_cells(out_se.ptr, D, n, idx.ptr, n, se_ptr, w)
         h.stream_sync(0)
-        out, block = block, None
-        return keep, plan.doys.copy(), out, None
-    finally:
-        for b in bufs:
-            b.free()
-        if block is not None:
-            block.free()
+        return keep, plan.doys.copy(), s.release(block), None
 
 
 def calc_clim_grid_device(stacked, doy, anynans, pctile, windowHalfWidth, smoothPercentile, smoothPercentileWidth,
@@ -827,7 +810,7 @@ def calc_clim_grid_device(stacked, doy, anynans, pctile, windowHalfWidth, smooth
     D = plan.D
     isz = device_itemsize(stacked)
     feb29_fix = tstep is False
-    finish = feb29_fix or smoothPercentile
+    finish = (feb29_fix, smoothPercentile, smoothPercentileWidth) if feb29_fix or smoothPercentile else None
     keeps, ths, ses = [], [], []
     pre = None
     touching = None
@@ -861,7 +844,6 @@ def calc_clim_grid_device(stacked, doy, anynans, pctile, windowHalfWidth, smooth
         recipe = packed_recipe(stacked) if direct else None
         # slab k+1 is uploaded (and decoded) by a second thread while slab k computes
         pre = SlabPrefetcher(stacked, slabs, raw=direct)
-        import time as _time
         _tl = _time.perf_counter()
         for (lo, hi), (d_up, up_isz) in pre:
             _trace(f"wait for slab [{lo},{hi})", _tl)
@@ -887,27 +869,14 @@ def calc_clim_grid_device(stacked, doy, anynans, pctile, windowHalfWidth, smooth
                     se[:, lo - c0:hi - c0] = np.nan
                 continue
             n = int(keep.sum())
-            bufs = [] if retain else [d_ts]
-            try:
-                raw_th, raw_se = DeviceBuffer(8 * D * n), DeviceBuffer(8 * D * n)
-                bufs += [raw_th, raw_se]
-                if direct:
-                    clim_raw_packed(plan, d_ts, n, pctile / 100.0, coldSpells, raw_th, raw_se, scale_factor=recipe["scale"],
-                                    add_offset=recipe["offset"], fill=recipe["fill"], decoded=recipe["decoded"],
-                                    big_endian=recipe["big_endian"])
-                else:
-                    clim_raw(plan, d_ts, isz, n, pctile / 100.0, coldSpells, raw_th, raw_se)
-                out_th, out_se = raw_th, raw_se
-                if finish:
-                    out_th, out_se = DeviceBuffer(8 * D * n), DeviceBuffer(8 * D * n)
-                    bufs += [out_th, out_se]
-                    clim_finish(plan, raw_th, raw_se, n, feb29_fix, smoothPercentile, smoothPercentileWidth,
-                                out_th, out_se)
+            with DeviceScope() as s:
+                if not retain:                     # (a retained slab is the store's, freed with it)
+                    s.adopt(d_ts)
+                out_th, out_se = _clim_on_device(s, plan, d_ts, isz, n, pctile / 100.0, coldSpells, finish, recipe=recipe)
                 h.stream_sync(0)
                 if scatter and n != w:
-                    d_idx = DeviceBuffer.from_array(np.nonzero(keep)[0].astype(np.int64)); bufs.append(d_idx)
-                    full_th, full_se = DeviceBuffer(8 * D * w), DeviceBuffer(8 * D * w)
-                    bufs += [full_th, full_se]
+                    d_idx = s.upload(np.nonzero(keep)[0].astype(np.int64))
+                    full_th, full_se = s.alloc(8 * D * w), s.alloc(8 * D * w)
                     h.scatter_cells(out_th.ptr, D, n, d_idx.ptr, n, full_th.ptr, w)
                     h.scatter_cells(out_se.ptr, D, n, d_idx.ptr, n, full_se.ptr, w)
                     h.stream_sync(0)
@@ -925,9 +894,6 @@ def calc_clim_grid_device(stacked, doy, anynans, pctile, windowHalfWidth, smooth
                 else:
                     ths.append(((lo, hi), out_th.to_array((D, n), np.float64)))
                     ses.append(((lo, hi), out_se.to_array((D, n), np.float64)))
-            finally:
-                for b in bufs:
-                    b.free()
         keep = np.concatenate(keeps) if keeps else np.zeros(0, dtype=bool)
         if not keep.any() and columns is None:
             raise XmhwException("All points of grid are either land or NaN")     # identify.py:527-528

@@ -23,10 +23,10 @@ csrc/kernels_objects.hip.
 import numpy as np
 
 from ._lib import hip
-from .coverage import _coslat, _on_grid, quantise_weights
 from .detect import EventDataset
-from .device import DeviceBuffer
+from .device import DeviceScope, as_xmhw_errors
 from .exception import XmhwException
+from .gridweights import quantise_weights, resolve_weights, weights_label
 
 PER_OBJECT = ("n_events", "n_cells", "time_start", "time_end", "cell_days", "area_days_q", "intensity_max", "peak_row")
 _DTYPES = dict(n_events=np.int32, n_cells=np.int32, time_start=np.int32, time_end=np.int32, cell_days=np.int64,
@@ -82,18 +82,10 @@ def objects_device(start, end, imax, offsets, nbr, gap, wq):
         raise XmhwException(f"mhw_objects handles fewer than 2**31 events, got {n}")
     if n == 0:
         return dict(root=np.zeros(0, dtype=np.int32), **{k: np.zeros(0, dtype=_DTYPES[k]) for k in PER_OBJECT})
-    bufs = []
-
-    def up(a):
-        b = DeviceBuffer.from_array(a)
-        bufs.append(b)
-        return b
-
-    try:
-        try:
-            d_start, d_end, d_off, d_nbr = up(start), up(end), up(offsets), up(nbr)
-            d_cell = DeviceBuffer(4 * n); bufs.append(d_cell)
-            d_root = DeviceBuffer(4 * n); bufs.append(d_root)
+    with DeviceScope() as s:
+        with as_xmhw_errors(also="Unsupported"):
+            d_start, d_end, d_off, d_nbr = s.upload(start), s.upload(end), s.upload(offsets), s.upload(nbr)
+            d_cell, d_root = s.alloc(4 * n), s.alloc(4 * n)
             h.event_objects(d_start.ptr, d_end.ptr, n, d_off.ptr, C, d_nbr.ptr, nbr.shape[1], int(gap), d_cell.ptr, d_root.ptr)
             h.stream_sync(0)
             root = d_root.to_array((n,), np.int32)
@@ -102,24 +94,13 @@ def objects_device(start, end, imax, offsets, nbr, gap, wq):
             m = roots.shape[0]
             slot_of_root = np.empty(n, dtype=np.int32)
             slot_of_root[roots] = np.arange(m, dtype=np.int32)
-            d_slot = up(slot_of_root[root])
-            d_imax, d_wq = up(imax), up(wq)
-            outs = {}
-            for k in PER_OBJECT:
-                outs[k] = DeviceBuffer(np.dtype(_DTYPES[k]).itemsize * m); bufs.append(outs[k])
+            d_slot = s.upload(slot_of_root[root])
+            d_imax, d_wq = s.upload(imax), s.upload(wq)
+            outs = {k: s.alloc(np.dtype(_DTYPES[k]).itemsize * m) for k in PER_OBJECT}
             h.object_reduce(d_start.ptr, d_end.ptr, d_imax.ptr, n, d_cell.ptr, d_off.ptr, d_wq.ptr, d_slot.ptr, m,
                             *[outs[k].ptr for k in PER_OBJECT])
             h.stream_sync(0)
-        except h.InvalidArgument as e:
-            raise XmhwException(str(e)) from e
-        except h.HipError as e:
-            if "(code 3)" in str(e):                    # XMHW_ERR_UNSUPPORTED
-                raise XmhwException(str(e)) from e
-            raise
         return dict(root=root, **{k: outs[k].to_array((m,), _DTYPES[k]) for k in PER_OBJECT})
-    finally:
-        for b in bufs:
-            b.free()
 
 
 class ObjectDataset:
@@ -173,13 +154,6 @@ class ObjectDataset:
                                      connectivity=self.connectivity, periodic=self.periodic or ""))
 
 
-def _positions(col, what):
-    col = np.asarray(col, dtype=np.float64)
-    if col.size and not (np.isfinite(col).all() and col.min() >= 0 and col.max() < (1 << 31) - 2):
-        raise XmhwException(f"{what} should hold time positions in [0, 2**31 - 2)")
-    return col.astype(np.int32)
-
-
 def mhw_objects(mhw, connectivity=6, periodic=None, weights=None, _compute=None):
     """Group the events of a gridded detect() into objects connected in space and time.
 
@@ -203,30 +177,14 @@ def mhw_objects(mhw, connectivity=6, periodic=None, weights=None, _compute=None)
     if periodic is not None and periodic not in mhw.sdims:
         raise XmhwException(f"periodic should be None or one of {mhw.sdims}, got {periodic!r}")
     sshape = tuple(int(v) for v in mhw.sshape)
-    N = int(np.prod(sshape, dtype=np.int64))
-    if weights is None:
-        w = np.ones(N)
-    elif isinstance(weights, str):
-        if weights != "coslat":
-            raise XmhwException(f"weights should be None, 'coslat' or an array, got {weights!r}")
-        w = _coslat(mhw.coords, list(mhw.sdims), sshape)
-    else:
-        w = _on_grid(np.asarray(weights, dtype=np.float64), "weights", list(mhw.sdims), None, list(mhw.sdims), sshape)
+    w = resolve_weights(weights, mhw.coords, list(mhw.sdims), None, list(mhw.sdims), sshape)
     n = mhw.n_events
     if n >= 1 << 31:
         raise XmhwException(f"mhw_objects handles fewer than 2**31 events, got {n}")
-    offsets = np.ascontiguousarray(mhw.offsets, dtype=np.int64)
-    cell_index = np.asarray(mhw.cell_index, dtype=np.int64)
-    C = offsets.shape[0] - 1
-    if cell_index.shape != (C,) or offsets[0] != 0 or offsets[-1] != n or (np.diff(offsets) < 0).any():
-        raise XmhwException("offsets and cell_index do not describe the table")
+    view = mhw.compact_view()
+    offsets, cell_index, cell_of_row, start, end = (view[k] for k in ("offsets", "cell_index", "cell_of_row", "start", "end"))
     cols = mhw.columns
-    start = _positions(mhw.table[:, cols.index("index_start")], "index_start")
-    end = _positions(mhw.table[:, cols.index("index_end")], "index_end")
     imax = np.ascontiguousarray(mhw.table[:, cols.index("intensity_max")], dtype=np.float64)
-    cell_of_row = np.repeat(np.arange(C, dtype=np.int64), np.diff(offsets))
-    if (end < start).any():
-        raise XmhwException("index_end before index_start")
     same = cell_of_row[1:] == cell_of_row[:-1]
     if (start[1:][same].astype(np.int64) <= end[:-1][same].astype(np.int64) + 1).any():
         raise XmhwException("events of one cell should be in time order and at least one step apart")
@@ -264,7 +222,7 @@ def mhw_objects(mhw, connectivity=6, periodic=None, weights=None, _compute=None)
     pc = np.full(m, -1, dtype=np.int64)
     pc[has] = cell_index[cell_of_row[pk[has]]]
     fields["time_peak"], fields["peak_cell"] = tp, pc
-    attrs = {"weights": "coslat" if isinstance(weights, str) else ("uniform" if weights is None else "array")}
+    attrs = {"weights": weights_label(weights)}
     if "xmhw_parameters" in mhw.attrs:
         attrs["xmhw_parameters"] = mhw.attrs["xmhw_parameters"]
     return ObjectDataset(fields, mhw.time, mhw.sdims, sshape, mhw.coords, start, end, cell_index[cell_of_row], bits, unit,

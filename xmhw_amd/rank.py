@@ -17,7 +17,7 @@ import numpy as np
 
 from . import calendar as cal
 from .detect import EventDataset
-from .device import DeviceBuffer
+from .device import DeviceScope
 from .exception import XmhwException
 from ._lib import hip
 
@@ -59,12 +59,9 @@ def rank_device(table, offsets, columns, n_years):
     rp = np.empty((n, 1 + ncol))
     if C == 0 or n == 0:
         return rank, rp
-    bufs = []
-    try:
-        d_tab = DeviceBuffer.from_array(table); bufs.append(d_tab)
-        d_off = DeviceBuffer.from_array(offsets); bufs.append(d_off)
-        d_rank = DeviceBuffer(8 * n * (1 + ncol)); bufs.append(d_rank)
-        d_rp = DeviceBuffer(8 * n * (1 + ncol)); bufs.append(d_rp)
+    with DeviceScope() as s:
+        d_tab, d_off = s.upload(table), s.upload(offsets)
+        d_rank, d_rp = s.alloc(8 * n * (1 + ncol)), s.alloc(8 * n * (1 + ncol))
         # the kernel writes columns 1.. of every row (ld_out = 1 + ncol), column 0 stays the caller's
         h.event_rank(d_tab.ptr, table.shape[1], d_off.ptr, C, [int(c) for c in columns], float(n_years),
                      d_rank.ptr + 8, d_rp.ptr + 8, 1 + ncol)
@@ -72,9 +69,6 @@ def rank_device(table, offsets, columns, n_years):
         rank = d_rank.to_array((n, 1 + ncol), np.float64)
         rp = d_rp.to_array((n, 1 + ncol), np.float64)
         return rank, rp
-    finally:
-        for b in bufs:
-            b.free()
 
 
 def _attrs(name, what):

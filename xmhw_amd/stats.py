@@ -16,7 +16,7 @@ import numpy as np
 
 from . import calendar as cal
 from .detect import EventDataset, InterDataset, _alive_axes, _compress_grid
-from .device import DeviceBuffer, native_float
+from .device import DeviceScope, native_float
 from .exception import XmhwException
 from ._lib import hip
 
@@ -70,12 +70,11 @@ def block_stats_device(table, offsets, years_of_t, edges, mtime="time_start", ts
     out = {}
     if C == 0 or nb <= 0:
         return {k: np.zeros((max(nb, 0), C)) for k in MHW_STATS}
-    bufs = []
-    try:
-        d_bin = DeviceBuffer.from_array(_bin_of_t(np.asarray(years_of_t, dtype=np.int64), edges)); bufs.append(d_bin)
-        d_tab = DeviceBuffer.from_array(table if table.size else np.zeros((1, len(EventDataset.columns)))); bufs.append(d_tab)
-        d_off = DeviceBuffer.from_array(offsets); bufs.append(d_off)
-        d_out = DeviceBuffer(8 * len(MHW_STATS) * nb * C); bufs.append(d_out)
+    with DeviceScope() as s:
+        d_bin = s.upload(_bin_of_t(np.asarray(years_of_t, dtype=np.int64), edges))
+        d_tab = s.upload(table if table.size else np.zeros((1, len(EventDataset.columns))))
+        d_off = s.upload(offsets)
+        d_out = s.alloc(8 * len(MHW_STATS) * nb * C)
         h.block_events(d_tab.ptr, d_off.ptr, C, d_bin.ptr, T, nb, col, d_out.ptr, C)
         h.stream_sync(0)
         ev = d_out.to_array((len(MHW_STATS), nb, C), np.float64)
@@ -83,11 +82,9 @@ def block_stats_device(table, offsets, years_of_t, edges, mtime="time_start", ts
         if ts is not None:
             ts = np.ascontiguousarray(native_float(ts))
             names = TS_STATS + (CAT_STATS if cats is not None else [])
-            d_ts = DeviceBuffer.from_array(ts); bufs.append(d_ts)
-            d_cat = None
-            if cats is not None:
-                d_cat = DeviceBuffer.from_array(np.ascontiguousarray(cats, dtype=np.float64)); bufs.append(d_cat)
-            d_o2 = DeviceBuffer(8 * len(names) * nb * C); bufs.append(d_o2)
+            d_ts = s.upload(ts)
+            d_cat = s.upload(np.ascontiguousarray(cats, dtype=np.float64)) if cats is not None else None
+            d_o2 = s.alloc(8 * len(names) * nb * C)
             h.block_time(d_ts.ptr, ts.dtype.itemsize, T, C, C, d_cat.ptr if d_cat else 0, C, d_bin.ptr, nb, d_o2.ptr, C)
             h.stream_sync(0)
             tt = d_o2.to_array((len(names), nb, C), np.float64)
@@ -95,9 +92,6 @@ def block_stats_device(table, offsets, years_of_t, edges, mtime="time_start", ts
             if cats is not None:
                 out["total_days"] = sum(out[k] for k in CAT_STATS)                # stats.py:306-312
         return out
-    finally:
-        for b in bufs:
-            b.free()
 
 
 def block_average(mhw, dstime=None, period=None, blockLength=1, mtime="time_start", removeMissing=False, split=False,

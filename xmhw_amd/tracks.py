@@ -34,16 +34,14 @@ integers); device side in csrc/kernels_tracks.hip behind tracks_device().
 import numpy as np
 
 from ._lib import hip
-from .coverage import _coslat, _on_grid, quantise_weights
 from .detect import EventDataset
-from .device import DeviceBuffer
+from .device import DeviceScope, as_xmhw_errors
 from .exception import XmhwException
-from .objects import ObjectDataset, _positions
+from .gridweights import LAT_NAMES, LON_NAMES, quantise_weights, resolve_weights, weights_label
+from .objects import ObjectDataset
 
 EARTH_RADIUS_KM = 6371.0088
 UNIT_BITS = 20
-_LAT = ("lat", "latitude", "y", "yt_ocean", "nav_lat")          # the names _coslat accepts
-_LON = ("lon", "longitude", "x", "xt_ocean", "nav_lon")
 _SQRT3 = 3.0 ** 0.5
 
 
@@ -67,35 +65,17 @@ def tracks_device(start, end, slot, cell, vec, time_start, offsets):
         raise XmhwException(f"mhw_tracks handles fewer than 2**31 rows, objects and series entries, got {n}, {m}, "
                             f"{L + 1}: select fewer objects with ids=")
     h = hip()
-    bufs = []
-
-    def up(a):
-        b = DeviceBuffer.from_array(a)
-        bufs.append(b)
-        return b
-
-    try:
-        try:
-            d_start, d_end, d_slot, d_cell, d_vec, d_ts, d_off = (up(a) for a in (start, end, slot, cell, vec, time_start,
-                                                                                  offsets))
-            d_cnt = DeviceBuffer(4 * (L + 1)); bufs.append(d_cnt)
-            d_sums = DeviceBuffer(8 * 4 * (L + 1)); bufs.append(d_sums)
-            d_bad = DeviceBuffer(4); bufs.append(d_bad)
+    with DeviceScope() as s:
+        with as_xmhw_errors(also="Unsupported", hint="select fewer objects with ids="):
+            d_start, d_end, d_slot, d_cell, d_vec, d_ts, d_off = (s.upload(a) for a in (start, end, slot, cell, vec,
+                                                                                        time_start, offsets))
+            d_cnt, d_sums, d_bad = s.alloc(4 * (L + 1)), s.alloc(8 * 4 * (L + 1)), s.alloc(4)
             h.object_tracks(d_start.ptr, d_end.ptr, n, d_slot.ptr, d_cell.ptr, C, d_vec.ptr, C, d_ts.ptr, d_off.ptr, m, L,
                             d_cnt.ptr, d_sums.ptr, L + 1, d_bad.ptr)
             h.stream_sync(0)
-        except h.InvalidArgument as e:
-            raise XmhwException(str(e)) from e
-        except h.HipError as e:
-            if "(code 3)" in str(e):                    # XMHW_ERR_UNSUPPORTED
-                raise XmhwException(f"{e}: select fewer objects with ids=") from e
-            raise
         cnt = d_cnt.to_array((L + 1,), np.int32)
         sums = d_sums.to_array((4, L + 1), np.int64)
         bad = int(d_bad.to_array((1,), np.int32)[0])
-    finally:
-        for b in bufs:
-            b.free()
     if bad:
         raise XmhwException(f"{bad} table rows do not lie within their object's days: obj does not belong to mhw")
     if cnt[L] != 0 or sums[:, L].any():
@@ -200,8 +180,8 @@ class TrackDataset:
 def _latlon(coords, sdims):
     """(name of the latitude dim, name of the longitude dim) when the two spatial dims are those and ``coords`` holds
     both, else None"""
-    lat = [d for d in sdims if d.lower() in _LAT]
-    lon = [d for d in sdims if d.lower() in _LON]
+    lat = [d for d in sdims if d.lower() in LAT_NAMES]
+    lon = [d for d in sdims if d.lower() in LON_NAMES]
     if len(lat) == 1 and len(lon) == 1 and lat[0] != lon[0] and lat[0] in coords and lon[0] in coords:
         return lat[0], lon[0]
     return None
@@ -273,24 +253,9 @@ def mhw_tracks(mhw, obj, ids=None, weights=None, _compute=None):
     m = ids.shape[0]
     N = int(np.prod(sshape, dtype=np.int64))
     sdims = list(mhw.sdims)
-    if weights is None:
-        w = np.ones(N)
-    elif isinstance(weights, str):
-        if weights != "coslat":
-            raise XmhwException(f"weights should be None, 'coslat' or an array, got {weights!r}")
-        w = _coslat(mhw.coords, sdims, sshape)
-    else:
-        w = _on_grid(np.asarray(weights, dtype=np.float64), "weights", sdims, None, sdims, sshape)
-    offsets_cells = np.ascontiguousarray(mhw.offsets, dtype=np.int64)
-    cell_index = np.asarray(mhw.cell_index, dtype=np.int64)
-    C = offsets_cells.shape[0] - 1
-    if cell_index.shape != (C,) or offsets_cells[0] != 0 or offsets_cells[-1] != n or (np.diff(offsets_cells) < 0).any():
-        raise XmhwException("offsets and cell_index do not describe the table")
-    cols = mhw.columns
-    start = _positions(mhw.table[:, cols.index("index_start")], "index_start")
-    end = _positions(mhw.table[:, cols.index("index_end")], "index_end")
-    if (end < start).any():
-        raise XmhwException("index_end before index_start")
+    w = resolve_weights(weights, mhw.coords, sdims, None, sdims, sshape)
+    view = mhw.compact_view()
+    C, cell_index, start, end = (view[k] for k in ("C", "cell_index", "start", "end"))
     names = _latlon(mhw.coords, sdims)
     mode = "sphere" if names else "index"
     if mode == "index" and obj.periodic is not None:
@@ -322,7 +287,7 @@ def mhw_tracks(mhw, obj, ids=None, weights=None, _compute=None):
     position = np.full(m_all, -1, dtype=np.int32)
     position[ids] = np.arange(m, dtype=np.int32)
     slot = position[object_of_row]
-    cell_of_row = np.repeat(np.arange(C, dtype=np.int32), np.diff(offsets_cells))
+    cell_of_row = view["cell_of_row"].astype(np.int32)
     sel = slot >= 0
     if sel.any() and ((start[sel] < t0[slot[sel]]).any() or (end[sel] > t1[slot[sel]]).any()):
         raise XmhwException("a table row lies outside the days of its object: obj does not belong to mhw")
@@ -366,7 +331,7 @@ def mhw_tracks(mhw, obj, ids=None, weights=None, _compute=None):
     else:
         f["area_max_q"], f["pos_area_max"] = np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int32)
     f["area_max"] = f["area_max_q"] * unit
-    attrs = {"weights": "coslat" if isinstance(weights, str) else ("uniform" if weights is None else "array")}
+    attrs = {"weights": weights_label(weights)}
     return TrackDataset(f, mhw.time, mhw.sdims, sshape, mode, bits, unit, mb, C, attrs)
 
 

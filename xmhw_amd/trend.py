@@ -42,7 +42,7 @@ import math
 
 import numpy as np
 
-from .device import DeviceBuffer
+from .device import DeviceScope
 from .exception import XmhwException
 from .stats import BlockDataset
 from ._lib import hip
@@ -159,21 +159,17 @@ def trend_device(planes, x, tcrit, method):
         return out
     if method == "theil_sen" and nb > MAX_BLOCKS:
         raise XmhwException(f"mean_trend(method='theil_sen') handles at most {MAX_BLOCKS} blocks, got {nb}")
-    bufs = []
-    try:
-        d_in = DeviceBuffer.from_array(planes); bufs.append(d_in)
-        d_x = DeviceBuffer.from_array(np.ascontiguousarray(x, dtype=np.float64)); bufs.append(d_x)
-        d_out = DeviceBuffer(8 * nwhat * nstat * C); bufs.append(d_out)
+    with DeviceScope() as s:
+        d_in = s.upload(planes)
+        d_x = s.upload(np.ascontiguousarray(x, dtype=np.float64))
+        d_out = s.alloc(8 * nwhat * nstat * C)
         if method == "ols":
-            d_t = DeviceBuffer.from_array(np.ascontiguousarray(tcrit, dtype=np.float64)); bufs.append(d_t)
+            d_t = s.upload(np.ascontiguousarray(tcrit, dtype=np.float64))
             h.block_trend_ols(d_in.ptr, nstat, nb, C, C, d_x.ptr, d_t.ptr, d_out.ptr, C)
         else:
             h.block_trend_theil_sen(d_in.ptr, nstat, nb, C, C, d_x.ptr, d_out.ptr, C)
         h.stream_sync(0)
         return d_out.to_array((nwhat, nstat, C), np.float64)
-    finally:
-        for b in bufs:
-            b.free()
 
 
 def mann_kendall_z(mk_s, mk_var):
