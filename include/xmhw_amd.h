@@ -656,6 +656,62 @@ int xmhw_object_tracks(const int32_t *start_dev, const int32_t *end_dev, int64_t
                        const int32_t *time_start_dev, const int64_t *offsets_dev, int64_t n_slots, int64_t L,
                        int32_t *n_cells_dev, int64_t *sums_dev, int64_t ld, int32_t *n_bad_dev, void *stream);
 
+/* ---- mhw_track_intensity(): the daily intensity and category series of the objects, ragged ----------- *
+ * The one object stage that visits voxels: it joins the series, the climatology and the object partition.  The
+ * ragged layout is that of xmhw_object_tracks: selected object i lives from time_start_dev[i] and owns the entries
+ * offsets_dev[i] .. offsets_dev[i + 1] - 1, one per day (offsets_dev[n_slots] == L).  A voxel is a step t of a cell c
+ * inside a table row (start..end inclusive) whose slot is in [0, n_slots); with x = the sample as float64 (negated
+ * when negate != 0) and seas / thresh re-expanded by row_of_t_host (values in [0, D)), its anomaly is a = x - seas,
+ * the expression of xmhw_event_stats_*, and it is VALID iff a is not NaN.  Entry offsets[slot] + (t - time_start[slot])
+ * receives, over the valid voxels: n_valid += 1, wsum_i += wi[c], isum_q += wi[c] * rint(a * 2^XMHW_TRACK_INTENSITY_BITS),
+ * intensity_max = max(a) (compared as float64 through the order-preserving 64-bit key and an integer atomic maximum,
+ * -0.0 counted as 0.0; NaN where there is none), and cat_cells[k][.] += 1 for the per-step category of mhw_df(),
+ * cats = floor(1 + (x - thresh)/(thresh - seas)): k = 0..3 for cats == 1, == 2, == 3, >= 4 (below the threshold or
+ * NaN: none).  A valid voxel with |a| >= 2^7, or infinite, is left out of everything and counted in *n_range_dev; the
+ * voxels of a row whose days do not lie within its object's entries are left out and counted in *n_bad_dev (both
+ * int64, 0 for consistent inputs): nothing outside entries 0..L-1 is ever written, and with wi <= 2^ib,
+ * ib <= 61 - 16 - 7 - bit_length(cells of the grid), |isum_q| stays below 2^61 whatever the data.
+ *
+ *  1. xmhw_track_intensity_init zeroes the accumulators (n_valid int32[L], wsum_i / isum_q int64[L], intensity_max
+ *     [L] used as the key array, cat_cells int32[4][ldcat], ldcat >= L) and both counters.
+ *  2. xmhw_track_intensity_accumulate_* handles one slab of n compacted cells: the series ts_dev (T, n) with leading
+ *     dimension ld, seas_dev / thresh_dev at the slab's column offset with leading dimension ldc, the slab's n_rows
+ *     table rows start_dev / end_dev / slot_dev (int32; the rows of cell c are row_offsets_dev[c] ..
+ *     row_offsets_dev[c + 1], relative to the slab's first row, in time order) and wi_dev[n] int64.  It ADDS into
+ *     the accumulators: calls for consecutive slabs follow each other on one stream without a read-back.  Lane = cell,
+ *     workgroup = 256 cells x XMHW_TRACK_INTENSITY_CHUNK steps; integer atomics without a return value, so the
+ *     result is exact and the same whatever the chunks, the slabs and the schedule.
+ *  3. xmhw_track_intensity_finish turns the keys into float64.
+ * All three are asynchronous on `stream`; nothing is launched for n == 0.  T, n, n_rows, n_slots or L of 2^31 and
+ * more: XMHW_ERR_UNSUPPORTED.  xmhw_set_track_intensity_combine (process-wide; tests and measurements): 1 = runs of
+ * equal target entries among the lanes of a wave are summed before the atomics (the default), 0 = one set of
+ * atomics per voxel.  Same results.                                                                        */
+#define XMHW_TRACK_INTENSITY_CHUNK 64
+#define XMHW_TRACK_INTENSITY_BITS 16
+int xmhw_set_track_intensity_combine(int32_t on);
+int xmhw_track_intensity_init(int64_t L, int32_t *n_valid_dev, int64_t *wsum_i_dev, int64_t *isum_q_dev,
+                              double *intensity_max_dev, int32_t *cat_cells_dev, int64_t ldcat,
+                              int64_t *n_range_dev, int64_t *n_bad_dev, void *stream);
+int xmhw_track_intensity_accumulate_f32(const float *ts_dev, int64_t T, int64_t n, int64_t ld,
+                                        const double *seas_dev, const double *thresh_dev, int64_t ldc, int64_t D,
+                                        const int32_t *row_of_t_host, int32_t negate, const int32_t *start_dev,
+                                        const int32_t *end_dev, const int32_t *slot_dev, int64_t n_rows,
+                                        const int64_t *row_offsets_dev, const int64_t *wi_dev,
+                                        const int32_t *time_start_dev, const int64_t *offsets_dev, int64_t n_slots,
+                                        int64_t L, int32_t *n_valid_dev, int64_t *wsum_i_dev, int64_t *isum_q_dev,
+                                        double *intensity_max_dev, int32_t *cat_cells_dev, int64_t ldcat,
+                                        int64_t *n_range_dev, int64_t *n_bad_dev, void *stream);
+int xmhw_track_intensity_accumulate_f64(const double *ts_dev, int64_t T, int64_t n, int64_t ld,
+                                        const double *seas_dev, const double *thresh_dev, int64_t ldc, int64_t D,
+                                        const int32_t *row_of_t_host, int32_t negate, const int32_t *start_dev,
+                                        const int32_t *end_dev, const int32_t *slot_dev, int64_t n_rows,
+                                        const int64_t *row_offsets_dev, const int64_t *wi_dev,
+                                        const int32_t *time_start_dev, const int64_t *offsets_dev, int64_t n_slots,
+                                        int64_t L, int32_t *n_valid_dev, int64_t *wsum_i_dev, int64_t *isum_q_dev,
+                                        double *intensity_max_dev, int32_t *cat_cells_dev, int64_t ldcat,
+                                        int64_t *n_range_dev, int64_t *n_bad_dev, void *stream);
+int xmhw_track_intensity_finish(int64_t L, double *intensity_max_dev, void *stream);
+
 /* ---- the sharded path: cells split across the GPUs of a node, ONE gather at the end ------- *
  * Replaces the reference's collect, dask.compute(climls) + xr.concat(dim='cell')
  * (xmhw/xmhw.py:197, :210-211).  Cells are independent (xmhw/xmhw.py:184-196), so rank r runs the

@@ -18,12 +18,14 @@ from .trend import mean_trend, TrendDataset
 from .coverage import mhw_coverage, CoverageDataset
 from .objects import mhw_objects, ObjectDataset
 from .tracks import mhw_tracks, TrackDataset
+from .track_intensity import mhw_track_intensity, TrackIntensityDataset
 from .ingest import open_series, threshold_file
 from .detrend import detrend, DetrendSpec, FitDataset
 
 __all__ = ["threshold", "threshold_array", "GridSeries", "ClimDataset", "XmhwException",
            "add_doy", "get_calendar", "land_check", "detect", "threshold_detect", "EventDataset", "InterDataset",
            "climatology_series", "release_device_cache", "block_average", "BlockDataset", "mhw_rank", "mean_trend", "TrendDataset", "mhw_coverage",
-           "CoverageDataset", "mhw_objects", "ObjectDataset", "mhw_tracks", "TrackDataset", "open_series",
+           "CoverageDataset", "mhw_objects", "ObjectDataset", "mhw_tracks", "TrackDataset", "mhw_track_intensity",
+           "TrackIntensityDataset", "open_series",
            "threshold_file", "detrend", "DetrendSpec", "FitDataset"]
 __version__ = "0.1.0"

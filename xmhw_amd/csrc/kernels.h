@@ -295,6 +295,30 @@ hipError_t launch_object_tracks(const int32_t* start, const int32_t* end, int64_
                                 int32_t* n_cells, int64_t* sums, int64_t ld, int32_t* n_bad, int64_t* scratch,
                                 hipStream_t stream);
 
+// mhw_track_intensity() (kernels_track_intensity.hip): the per-voxel pass over one slab of n compacted cells.  The slab's
+// table rows (start / end / slot, n_rows of them, the rows of cell c = row_offsets[c]..row_offsets[c + 1], in time
+// order) are walked together with the steps of a chunk of kTrackIntensityChunk steps; a voxel of a row whose slot is in
+// [0, n_slots) ADDS to entry offsets[slot] + (t - time_start[slot]) of n_valid / wsum_i / isum_q / cat_cells[4][ldcat]
+// and raises the 64-bit key kept in intensity_max (launch_track_intensity_init zeroes them; launch_track_intensity_finish
+// turns the keys into float64, NaN for none).  *n_range counts the voxels left out for |a| >= 2^7, *n_bad those of rows
+// that do not lie within their object's entries.  row_of_t is a DEVICE array here.  combine_runs: runs of equal target
+// entries among the lanes of a wave are summed by a segmented scan before the atomics.
+constexpr int kTrackIntensityChunk = 64;
+constexpr int kTrackIntensityBits = 16;
+hipError_t launch_track_intensity_init(int64_t L, int32_t* n_valid, int64_t* wsum_i, int64_t* isum_q, double* intensity_max,
+                                       int32_t* cat_cells, int64_t ldcat, int64_t* n_range, int64_t* n_bad,
+                                       hipStream_t stream);
+template <typename T>
+hipError_t launch_track_intensity_accumulate(const T* ts, int64_t Tn, int64_t n, int64_t ld, const double* seas,
+                                             const double* thresh, int64_t ldc, const int32_t* row_of_t, int32_t negate,
+                                             const int32_t* start, const int32_t* end, const int32_t* slot,
+                                             int64_t n_rows, const int64_t* row_offsets, const int64_t* wi,
+                                             const int32_t* time_start, const int64_t* offsets, int64_t n_slots, int64_t L,
+                                             int32_t* n_valid, int64_t* wsum_i, int64_t* isum_q, double* intensity_max,
+                                             int32_t* cat_cells, int64_t ldcat, int64_t* n_range, int64_t* n_bad,
+                                             int32_t combine_runs, hipStream_t stream);
+hipError_t launch_track_intensity_finish(int64_t L, double* intensity_max, hipStream_t stream);
+
 // file bytes -> samples (kernels_ingest.hip): raw_type = item size of the stored type (2 int16, 4 float32,
 // 8 float64), swap = the file is big-endian, optional scale/offset (CF packing) and fill value -> NaN
 hipError_t launch_encode_i16(const float* in, int64_t rows, int64_t cols, int64_t ld_in, int16_t* out, int64_t ld_out,

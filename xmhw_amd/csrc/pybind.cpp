@@ -593,6 +593,50 @@ PYBIND11_MODULE(_xmhw_hip, m) {
        py::arg("ldv"), py::arg("time_start"), py::arg("offsets"), py::arg("n_slots"), py::arg("L"), py::arg("n_cells"),
        py::arg("sums"), py::arg("ld"), py::arg("n_bad"), py::arg("stream") = 0);
     m.attr("TRACKS_TILE") = XMHW_TRACKS_TILE;
+    m.attr("TRACK_INTENSITY_CHUNK") = XMHW_TRACK_INTENSITY_CHUNK;
+    m.attr("TRACK_INTENSITY_BITS") = XMHW_TRACK_INTENSITY_BITS;
+    m.def("set_track_intensity_combine", [](int on) { check(xmhw_set_track_intensity_combine(on)); }, py::arg("on"));
+    m.def("track_intensity_init", [](int64_t L, uintptr_t n_valid, uintptr_t wsum_i, uintptr_t isum_q, uintptr_t intensity_max,
+                                     uintptr_t cat_cells, int64_t ldcat, uintptr_t n_range, uintptr_t n_bad, uintptr_t stream) {
+        check(xmhw_track_intensity_init(L, static_cast<int32_t*>(vp(n_valid)), static_cast<int64_t*>(vp(wsum_i)),
+                                        static_cast<int64_t*>(vp(isum_q)), static_cast<double*>(vp(intensity_max)),
+                                        static_cast<int32_t*>(vp(cat_cells)), ldcat, static_cast<int64_t*>(vp(n_range)),
+                                        static_cast<int64_t*>(vp(n_bad)), vp(stream)));
+    }, py::arg("L"), py::arg("n_valid"), py::arg("wsum_i"), py::arg("isum_q"), py::arg("intensity_max"), py::arg("cat_cells"),
+       py::arg("ldcat"), py::arg("n_range"), py::arg("n_bad"), py::arg("stream") = 0);
+    m.def("track_intensity_accumulate", [](uintptr_t ts, int itemsize, int64_t T, int64_t n, int64_t ld, uintptr_t seas,
+                                           uintptr_t thresh, int64_t ldc, int64_t D, i32arr row_of_t, int negate,
+                                           uintptr_t start, uintptr_t end, uintptr_t slot, int64_t n_rows,
+                                           uintptr_t row_offsets, uintptr_t wi, uintptr_t time_start, uintptr_t offsets,
+                                           int64_t n_slots, int64_t L, uintptr_t n_valid, uintptr_t wsum_i, uintptr_t isum_q,
+                                           uintptr_t intensity_max, uintptr_t cat_cells, int64_t ldcat, uintptr_t n_range,
+                                           uintptr_t n_bad, uintptr_t stream) {
+        if (row_of_t.size() != T) throw InvalidError("row_of_t length must equal T");
+        if (itemsize != 4 && itemsize != 8) throw InvalidError("itemsize must be 4 or 8");
+        py::gil_scoped_release r;
+        const auto i32 = [](uintptr_t p) { return static_cast<int32_t*>(vp(p)); };
+        const auto i64 = [](uintptr_t p) { return static_cast<int64_t*>(vp(p)); };
+        const auto f64 = [](uintptr_t p) { return static_cast<double*>(vp(p)); };
+        if (itemsize == 4)
+            check(xmhw_track_intensity_accumulate_f32(static_cast<const float*>(vp(ts)), T, n, ld, f64(seas), f64(thresh), ldc, D,
+                                                      row_of_t.data(), negate, i32(start), i32(end), i32(slot), n_rows,
+                                                      i64(row_offsets), i64(wi), i32(time_start), i64(offsets), n_slots, L,
+                                                      i32(n_valid), i64(wsum_i), i64(isum_q), f64(intensity_max),
+                                                      i32(cat_cells), ldcat, i64(n_range), i64(n_bad), vp(stream)));
+        else
+            check(xmhw_track_intensity_accumulate_f64(f64(ts), T, n, ld, f64(seas), f64(thresh), ldc, D, row_of_t.data(),
+                                                      negate, i32(start), i32(end), i32(slot), n_rows, i64(row_offsets),
+                                                      i64(wi), i32(time_start), i64(offsets), n_slots, L, i32(n_valid),
+                                                      i64(wsum_i), i64(isum_q), f64(intensity_max), i32(cat_cells), ldcat,
+                                                      i64(n_range), i64(n_bad), vp(stream)));
+    }, py::arg("ts"), py::arg("itemsize"), py::arg("T"), py::arg("n"), py::arg("ld"), py::arg("seas"), py::arg("thresh"),
+       py::arg("ldc"), py::arg("D"), py::arg("row_of_t"), py::arg("negate"), py::arg("start"), py::arg("end"), py::arg("slot"),
+       py::arg("n_rows"), py::arg("row_offsets"), py::arg("wi"), py::arg("time_start"), py::arg("offsets"), py::arg("n_slots"),
+       py::arg("L"), py::arg("n_valid"), py::arg("wsum_i"), py::arg("isum_q"), py::arg("intensity_max"), py::arg("cat_cells"),
+       py::arg("ldcat"), py::arg("n_range"), py::arg("n_bad"), py::arg("stream") = 0);
+    m.def("track_intensity_finish", [](int64_t L, uintptr_t intensity_max, uintptr_t stream) {
+        check(xmhw_track_intensity_finish(L, static_cast<double*>(vp(intensity_max)), vp(stream)));
+    }, py::arg("L"), py::arg("intensity_max"), py::arg("stream") = 0);
     m.def("block_trend_ols", [](uintptr_t y, int32_t nstat, int32_t nb, int64_t C, int64_t ld, uintptr_t x, uintptr_t tcrit,
                                 uintptr_t out, int64_t ldo, uintptr_t stream) {
         check(xmhw_block_trend_ols(static_cast<const double*>(vp(y)), nstat, nb, C, ld, static_cast<const double*>(vp(x)),

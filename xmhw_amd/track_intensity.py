@@ -1,0 +1,444 @@
+"""mhw_track_intensity(): how hot every object of mhw_objects() was on each of its days -- the daily mean and maximum
+anomaly over the object's footprint, its cumulative intensity, and how much of it was Moderate, Strong, Severe or
+Extreme -- aligned with the ragged (CSR) arrays of mhw_tracks(): entry tr.offsets[i] + (t - tr.time_start[i]) belongs
+to object tr.ids[i] on time position t.  The tracking tools of the field loop regionprops with an intensity image over
+a dense labelled volume.  Every earlier object stage could avoid visiting voxels, because its quantities are constant
+along a table row; this one cannot: it is the first reduction that joins the resident series, the climatology and the
+object partition, one streaming pass over the series (csrc/kernels_track_intensity.hip).
+
+The definition.  For a selected object o and a position t, take the voxels of o on t: the cells c that hold a row of o
+with index_start <= t <= index_end (gap days of joined events included).  With x = float64(ts[t, c]), negated under
+coldSpells, and the climatology rows of t:
+    a[t, c] = x - seas[row(t), c]
+the anomaly as the event statistics of detect() form it (xmhw_event_stats_*: the series is negated, the climatologies
+are those of the negated series; the sign is the device's, positive for a cold spell too, before detect() flips the
+table).  A voxel is *valid* iff a is not NaN.  Over the valid voxels:
+    n_valid (int32) = their number,                 wsum_i (int64) = sum wi[c],
+    isum_q (int64)  = sum wi[c] * aq[t, c],         aq = rint(a * 2**16)   (INTENSITY_BITS = 16),
+    intensity_max (float64) = the largest a (NaN where there is none; -0.0 counts as 0.0, as in mhw_objects()): an
+        integer maximum of the order-preserving 64-bit key, exact and independent of the schedule,
+    cat_cells (4, L) int32 = the voxels whose per-step category floor(1 + (x - thresh) / (thresh - seas)), in float64,
+        is 1, 2, 3 or >= 4: the semantics of mhw_coverage(); a voxel below the threshold or NaN is in none of the four.
+A valid voxel with |a| >= 2**7, or infinite, is left out of every sum and counted, and the call raises: no value
+outside the stated bound ever reaches a sum.
+
+The bit budget.  wi = rint(w / w.max() * 2**ib) with ib = min(obj.weight_bits, 61 - 16 - 7 - bit_length(C)), C = the
+ocean cells of the grid.  A day of an object holds at most C voxels, wi <= 2**ib and |aq| <= 2**23, so
+|isum_q| <= C * 2**(ib + 23) < 2**(bit_length(C) + ib + 23) <= 2**61, whatever the data.  ib < 1 is refused.
+
+Derived on the host, in float64: intensity_mean = isum_q / (wsum_i * 2**16) (NaN where wsum_i == 0); per object
+intensity_cumulative = the sum of its defined intensity_mean, intensity_peak = the largest intensity_max of its days
+and pos_peak, the first position that attains it (NaN and -1 for an object without a valid voxel).
+
+Host side here (validation, selection, weights, slabs); device side in csrc/kernels_track_intensity.hip behind
+track_intensity_cells() (a compact host series) and track_intensity_grid() (a stacked grid, masked and compacted on the
+device slab by slab, as coverage_grid()).
+"""
+import numpy as np
+
+from ._lib import hip
+from .api import GridSeries, _from_xarray, _is_xarray
+from .detect import EventDataset
+from .device import DeviceScope, as_xmhw_errors
+from .exception import XmhwException
+from .gridweights import quantise_weights, resolve_weights, weights_label
+from .objects import ObjectDataset
+from .tracks import TrackDataset
+
+INTENSITY_BITS = 16             # XMHW_TRACK_INTENSITY_BITS (include/xmhw_amd.h)
+RANGE_BITS = 7                  # |a| < 2**7
+CATEGORIES = ("moderate", "strong", "severe", "extreme")
+STAGE_FIELDS = ("n_valid", "wsum_i", "isum_q", "intensity_max", "cat_cells")
+_COLD_TEXT = "cold events were detected"
+
+
+def intensity_bits(weight_bits, n_ocean):
+    """ib of the module docstring"""
+    return int(min(int(weight_bits), 61 - INTENSITY_BITS - RANGE_BITS - int(n_ocean).bit_length()))
+
+
+class _Rows:
+    """The selection as the device stage takes it: the table rows (start, end, slot; int32) with the (C + 1,) int64
+    offsets of the cells' rows, and the ragged layout (time_start (m,) int32, offsets (m + 1,) int64)."""
+
+    def __init__(self, start, end, slot, row_offsets, time_start, offsets):
+        self.start = np.ascontiguousarray(start, dtype=np.int32)
+        self.end = np.ascontiguousarray(end, dtype=np.int32)
+        self.slot = np.ascontiguousarray(slot, dtype=np.int32)
+        self.row_offsets = np.ascontiguousarray(row_offsets, dtype=np.int64)
+        self.time_start = np.ascontiguousarray(time_start, dtype=np.int32)
+        self.offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        self.m, self.L = self.time_start.shape[0], int(self.offsets[-1])
+        if max(self.start.shape[0], self.m, self.L) >= 1 << 31:
+            raise XmhwException(f"mhw_track_intensity handles fewer than 2**31 rows, objects and series entries, got "
+                                f"{self.start.shape[0]}, {self.m}, {self.L}: select fewer objects with ids= in mhw_tracks()")
+
+
+def selection_rows(mhw, obj, tr):
+    """The _Rows of the selection of ``tr``: the rows of ``mhw`` with the position of their object in ``tr.ids`` (-1: not
+    selected) and the ragged layout of ``tr``, checked against ``obj``."""
+    # the selection and its layout: those of tr, checked against obj
+    n = mhw.n_events
+    object_of_row = np.asarray(obj.object, dtype=np.int64)
+    m_all = obj.n_objects
+    if object_of_row.shape != (n,) or (n and (object_of_row.min() < 0 or object_of_row.max() >= m_all)):
+        raise XmhwException("obj.object should hold one object id per table row: obj does not belong to mhw")
+    ids = np.asarray(tr.ids, dtype=np.int64)
+    m = ids.shape[0]
+    if m and (ids.min() < 0 or ids.max() >= m_all or np.unique(ids).shape[0] != m):
+        raise XmhwException("tr.ids should be distinct object ids of obj: tr does not belong to obj")
+    t0 = np.ascontiguousarray(tr.time_start, dtype=np.int32)
+    offsets = np.ascontiguousarray(tr.offsets, dtype=np.int64)
+    dur = np.asarray(obj.time_end, dtype=np.int64)[ids] - np.asarray(obj.time_start, dtype=np.int64)[ids] + 1
+    if (offsets.shape != (m + 1,) or not np.array_equal(t0, np.asarray(obj.time_start)[ids])
+            or not np.array_equal(np.diff(offsets), dur) or offsets[0] != 0):
+        raise XmhwException("tr.time_start and tr.offsets are not those of its objects in obj: tr does not belong to obj")
+    L = int(offsets[-1])
+    if L >= 1 << 31:
+        raise XmhwException(f"the series of the {m} selected objects hold {L} entries, 2**31 and more: select fewer "
+                            "objects with ids= in mhw_tracks()")
+    view = mhw.compact_view()
+    C = view["C"]
+    position = np.full(m_all, -1, dtype=np.int32)
+    position[ids] = np.arange(m, dtype=np.int32)
+    slot = position[object_of_row] if n else np.zeros(0, dtype=np.int32)
+    return _Rows(view["start"], view["end"], slot, view["offsets"], t0, offsets)
+
+
+class _Accumulators:
+    """The device accumulators of one call, initialised; they persist across the slabs and are read back once."""
+
+    def __init__(self, h, rows):
+        self.h, self.L, self.m = h, rows.L, rows.m
+        L = max(self.L, 1)
+        self._scope = s = DeviceScope()
+        try:
+            self.n_valid, self.wsum, self.isum, self.imax = s.alloc(4 * L), s.alloc(8 * L), s.alloc(8 * L), s.alloc(8 * L)
+            self.cat, self.count = s.alloc(4 * 4 * L), s.alloc(16)
+            self.time_start, self.offsets = s.upload(rows.time_start), s.upload(rows.offsets)
+            with as_xmhw_errors(also="Unsupported", hint="select fewer objects with ids= in mhw_tracks()"):
+                h.track_intensity_init(self.L, *self._out())
+        except BaseException:
+            s.free()
+            raise
+
+    def _out(self):
+        return (self.n_valid.ptr, self.wsum.ptr, self.isum.ptr, self.imax.ptr, self.cat.ptr, max(self.L, 1),
+                self.count.ptr, self.count.ptr + 8)
+
+    def add_slab(self, d_ts, isz, T, n, ld, se_ptr, th_ptr, ldc, D, row_of_t, neg, rows, k0, wi):
+        """the slab of compact cells k0..k0 + n - 1, its series already on the device: upload its rows, queue the pass"""
+        r0, r1 = int(rows.row_offsets[k0]), int(rows.row_offsets[k0 + n])
+        if r1 == r0 or self.L == 0 or self.m == 0:
+            return
+        with DeviceScope() as s:
+            d_start, d_end, d_slot = (s.upload(a[r0:r1]) for a in (rows.start, rows.end, rows.slot))
+            d_roff = s.upload(rows.row_offsets[k0:k0 + n + 1] - r0)
+            d_wi = s.upload(np.ascontiguousarray(wi[k0:k0 + n], dtype=np.int64))
+            with as_xmhw_errors(also="Unsupported", hint="select fewer objects with ids= in mhw_tracks()"):
+                self.h.track_intensity_accumulate(d_ts.ptr, isz, T, n, ld, se_ptr, th_ptr, ldc, D, row_of_t, neg, d_start.ptr,
+                                                  d_end.ptr, d_slot.ptr, r1 - r0, d_roff.ptr, d_wi.ptr, self.time_start.ptr,
+                                                  self.offsets.ptr, self.m, self.L, *self._out())
+            self.h.stream_sync(0)                       # the slab's rows are freed on the way out
+
+    def result(self):
+        h, L = self.h, self.L
+        with as_xmhw_errors(also="Unsupported"):
+            h.track_intensity_finish(L, self.imax.ptr)
+        h.stream_sync(0)
+        count = self.count.to_array((2,), np.int64)
+        return dict(n_valid=self.n_valid.to_array((L,), np.int32), wsum_i=self.wsum.to_array((L,), np.int64),
+                    isum_q=self.isum.to_array((L,), np.int64), intensity_max=self.imax.to_array((L,), np.float64),
+                    cat_cells=self.cat.to_array((4, max(L, 1)), np.int32)[:, :L].copy(), n_range=int(count[0]),
+                    n_bad=int(count[1]))
+
+    def free(self):
+        self._scope.free()
+
+
+def track_intensity_cells(ts, seas, thresh, doy, doys, rows, wi, coldSpells=False, max_batch_bytes=64 << 30, pad=None):
+    """The device stage for a dense (T, C) host series (arguments as coverage.coverage_cells): ``rows`` the _Rows of the
+    selection, ``wi`` (C,) int64 weights.  Returns a dict of STAGE_FIELDS plus the counters n_range and n_bad.  Cells go
+    through the device in batches below max_batch_bytes; the sums are integers, so the batch size does not change a bit."""
+    from .detect_front import _check_inputs
+    ts, seas, thresh, row_of_t = _check_inputs(ts, seas, thresh, doy, doys)
+    T, C = ts.shape
+    D = thresh.shape[0]
+    if rows.row_offsets.shape != (C + 1,) or np.shape(wi) != (C,):
+        raise XmhwException("the table does not have one block of rows per ocean cell of temp: mhw does not belong to temp")
+    h = hip()
+    isz = ts.dtype.itemsize
+    per_cell = T * isz + 2 * D * 8 + 64
+    batch = int(max(1, min(C, max_batch_bytes // max(per_cell, 1))))
+    acc = _Accumulators(h, rows)
+    try:
+        for c0 in range(0, C, batch):
+            n = min(C, c0 + batch) - c0
+            with DeviceScope() as s:
+                d_ts = s.upload(np.ascontiguousarray(ts[:, c0:c0 + n]))
+                if pad is not None:
+                    pad.apply(d_ts.ptr, isz, T, n)
+                d_se = s.upload(np.ascontiguousarray(seas[:, c0:c0 + n]))
+                d_th = s.upload(np.ascontiguousarray(thresh[:, c0:c0 + n]))
+                acc.add_slab(d_ts, isz, T, n, n, d_se.ptr, d_th.ptr, n, D, row_of_t, int(bool(coldSpells)), rows, c0, wi)
+        return acc.result()
+    finally:
+        acc.free()
+
+
+def track_intensity_grid(stacked, anynans, seas, thresh, doy, doys, rows, wi, keep_want, coldSpells=False,
+                         max_batch_bytes=None, clim_stacked=False, pad=None):
+    """track_intensity_cells() for an UNCOMPACTED stacked host series (T, N), as coverage.coverage_grid: the land mask and
+    the compaction run on the device slab by slab, the climatologies are compacted there as well and pair up with the
+    series' survivors by position.  ``keep_want`` (N,) bool: the land mask of the detection; a slab whose mask differs
+    is refused before it is used.  Returns (the stage dict, keep[N])."""
+    from .detect_front import _check_inputs, _rows_as_they_are
+    from .device import _grid_batch, compact_columns, device_itemsize, is_packed, native_float
+    T, N = stacked.shape
+    if not is_packed(stacked):
+        stacked = np.ascontiguousarray(native_float(stacked))
+    seas, thresh = _rows_as_they_are(seas), _rows_as_they_are(thresh)
+    if seas.ndim != 2 or thresh.ndim != 2 or seas.shape[0] != thresh.shape[0]:
+        raise XmhwException("seas and thresh must be (D, cells) arrays")
+    D = thresh.shape[0]
+    sample_dtype = stacked.decoded_dtype if is_packed(stacked) else stacked.dtype
+    _, _, _, row_of_t = _check_inputs(np.zeros((T, 1), dtype=sample_dtype), seas[:, :1], thresh[:, :1], doy, doys)
+    if keep_want.shape != (N,):
+        raise XmhwException(f"temp has {N} grid points, the detection {keep_want.shape[0]}: mhw does not belong to temp")
+    h = hip()
+    isz = device_itemsize(stacked)
+    keeps = []
+    acc = _Accumulators(h, rows)
+    clim = DeviceScope()
+    k0 = 0
+    try:
+        if clim_stacked:
+            d_th, keep_th = compact_columns(thresh, 0, thresh.shape[1], anynans)
+            clim.adopt(d_th)
+            d_se, keep_se = compact_columns(seas, 0, seas.shape[1], anynans)
+            clim.adopt(d_se)
+            C, Cse = int(keep_th.sum()), int(keep_se.sum())
+            if C == 0 or Cse == 0:
+                raise XmhwException("All points of grid are either land or NaN")
+        else:
+            d_th, d_se = clim.upload(thresh), clim.upload(seas)
+            C, Cse = thresh.shape[1], seas.shape[1]
+        if C != Cse:
+            raise XmhwException(f"th and se do not have the same ocean cells: {C}, {Cse}")
+        cb = _grid_batch(stacked, max_batch_bytes, per_cell_extra=6 * D * 8 + 64)
+        for lo in range(0, N, cb):
+            hi = min(N, lo + cb)
+            d_ts, keep = compact_columns(stacked, lo, hi, anynans)
+            keeps.append(keep)
+            n = int(keep.sum())
+            with DeviceScope() as s:
+                s.adopt(d_ts)
+                if not np.array_equal(keep, keep_want[lo:hi]):
+                    raise XmhwException("the land mask of temp differs from mhw.keep: mhw does not belong to temp")
+                if d_ts is None:
+                    continue
+                if pad is not None:
+                    pad.apply(d_ts.ptr, isz, T, n)
+                if k0 + n > C:
+                    raise XmhwException(f"temp has more ocean cells than th and se ({C})")
+                acc.add_slab(d_ts, isz, T, n, n, d_se.ptr + 8 * k0, d_th.ptr + 8 * k0, C, D, row_of_t, int(bool(coldSpells)),
+                             rows, k0, wi)
+            k0 += n
+        keep = np.concatenate(keeps) if keeps else np.zeros(0, dtype=bool)
+        if not keep.any():
+            raise XmhwException("All points of grid are either land or NaN")
+        if k0 != C:
+            raise XmhwException(f"temp has {k0} ocean cells, th and se have {C}")
+        return acc.result(), keep
+    finally:
+        acc.free()
+        clim.free()
+
+
+class TrackIntensityDataset:
+    """What mhw_track_intensity() returns, as plain arrays, aligned with the TrackDataset it was given: m objects, L =
+    offsets[-1] entries; entry offsets[i] + (t - time_start[i]) belongs to object ids[i] on time position t.
+
+    ids, offsets, time_start, time_end, duration, pos    those of the TrackDataset, unchanged;
+    n_valid (L,) int32              voxels of the object on that day with a defined anomaly;
+    wsum_i, isum_q (L,) int64       the sums of wi and of wi * rint(a * 2**16) over them (module docstring);
+    intensity_mean (L,) float64     isum_q / (wsum_i * 2**16): the weighted mean anomaly (NaN where wsum_i == 0);
+    intensity_max (L,) float64      the largest anomaly of the day (NaN where n_valid == 0);
+    cat_cells (4, L) int32          voxels in category moderate, strong, severe, extreme (CATEGORIES);
+    intensity_cumulative (m,)       the sum of the object's defined intensity_mean (0 where none is);
+    intensity_peak (m,), pos_peak (m,) int32    the largest intensity_max of the object's days and the first position
+                                    that attains it (NaN, -1 for an object without a valid voxel);
+    intensity_weight_bits (ib), n_ocean (C)."""
+
+    _SERIES = ("pos", "n_valid", "wsum_i", "isum_q", "intensity_mean", "intensity_max")
+    _PER_OBJECT = ("ids", "time_start", "time_end", "duration", "intensity_cumulative", "intensity_peak", "pos_peak")
+
+    def __init__(self, fields, time, sdims, sshape, intensity_weight_bits, n_ocean, attrs=None):
+        for k, v in fields.items():
+            setattr(self, k, v)
+        self.time, self.sdims, self.sshape = np.asarray(time), tuple(sdims), tuple(sshape)
+        self.intensity_weight_bits, self.n_ocean = int(intensity_weight_bits), int(n_ocean)
+        self.category = CATEGORIES
+        self.attrs = dict(attrs or {})
+
+    @property
+    def n_selected(self):
+        return int(self.ids.shape[0])
+
+    time_stamps = EventDataset.time_stamps
+
+    def series(self, i):
+        """The slices of the i-th selected object: a dict of its series (cat_cells as (4, days)) plus ``time``."""
+        i = int(i)
+        if not 0 <= i < self.n_selected:
+            raise XmhwException(f"series() takes a position in [0, {self.n_selected}), got {i}")
+        sl = slice(int(self.offsets[i]), int(self.offsets[i + 1]))
+        out = {k: getattr(self, k)[sl] for k in self._SERIES}
+        out["cat_cells"] = self.cat_cells[:, sl]
+        out["time"] = self.time_stamps(out["pos"])
+        return out
+
+    def quantisation_bound(self):
+        """(L,) float64: a bound on |intensity_mean - sum(w a) / sum(w)| over the valid voxels of every entry, for the
+        unquantised float64 weights w and anomalies a.  Derived from the two roundings, not fitted.
+
+        Write s = 2**ib / w.max().  The stored numbers are wi[c] = s w[c] + d[c], |d[c]| <= 1/2, and aq = 2**16 a + r,
+        |r| <= 1/2.  First rounding: sum(wi aq) / (2**16 sum wi) = sum(wi a) / sum(wi) + sum(wi r) / (2**16 sum wi), and
+        the second term is a weighted mean of r / 2**16: at most 2**-17.  Second rounding: with mu = sum(w a) / sum(w)
+        (sum w > 0 whenever sum wi > 0: a zero weight is quantised to 0),
+            sum(wi a) / sum(wi) - mu = sum(wi (a - mu)) / sum(wi) = sum(d (a - mu)) / sum(wi),
+        because sum(s w (a - mu)) = 0.  mu lies among the a, all within (-2**7, 2**7), so |a - mu| < 2**8 and the term is
+        below n_valid * 2**7 / wsum_i.  The float64 evaluation (two conversions and a division of a value below 2**7)
+        adds less than 2**-44.  NaN where wsum_i == 0."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            b = self.n_valid.astype(np.float64) * 2.0 ** RANGE_BITS / self.wsum_i.astype(np.float64)
+        return np.where(self.wsum_i > 0, b + 2.0 ** -(INTENSITY_BITS + 1) + 2.0 ** -44, np.nan)
+
+    def to_xarray(self):
+        import xarray as xr
+        data = {k: (("obs",), getattr(self, k)) for k in self._SERIES}
+        data["cat_cells"] = (("category", "obs"), self.cat_cells)
+        data["time"] = (("obs",), self.time_stamps(self.pos))
+        for k in self._PER_OBJECT:
+            data["object_id" if k == "ids" else k] = (("track",), getattr(self, k))
+        data["offsets"] = (("track_edge",), self.offsets)
+        return xr.Dataset(data, coords={"category": list(CATEGORIES)},
+                          attrs=dict(self.attrs, intensity_bits=INTENSITY_BITS, intensity_weight_bits=self.intensity_weight_bits))
+
+
+def mhw_track_intensity(temp, th, se, mhw, obj, tr, weights=None, tdim="time", maxPadLength=None, coldSpells=False,
+                        tstep=False, anynans=False, _compute=None, max_batch_bytes=None):
+    """The daily intensity and category series of the objects of mhw_tracks().
+
+    ``temp``, ``th``, ``se`` and the options shared with detect() mean and validate what they do in mhw_coverage() (same
+    exceptions, land masking, positional pairing of series and climatology cells, ``maxPadLength`` applied to the device
+    copy of the series); give what detect() was given.  ``mhw``, ``obj``, ``tr``: the EventDataset of that detect(), the
+    ObjectDataset of mhw_objects() and the TrackDataset of mhw_tracks() for it; the result uses ``tr.ids``,
+    ``tr.offsets``, ``tr.time_start`` and ``tr.pos`` unchanged.  ``weights``: as for mhw_tracks(), and the same ones
+    (they weight the mean).
+
+    Returns a TrackIntensityDataset (module docstring: the definition; class docstring: the fields).  Every integer is
+    a sum of integers and the maximum is an integer maximum: exact, and the same from run to run and for every
+    ``max_batch_bytes``.  ``_compute``: a stand-in for track_intensity_cells() (host tests)."""
+    from .detect import _detect
+    if not isinstance(mhw, EventDataset):
+        raise XmhwException("mhw_track_intensity expects the EventDataset returned by xmhw_amd.detect()")
+    if not isinstance(obj, ObjectDataset):
+        raise XmhwException("mhw_track_intensity expects the ObjectDataset returned by xmhw_amd.mhw_objects()")
+    if not isinstance(tr, TrackDataset):
+        raise XmhwException("mhw_track_intensity expects the TrackDataset returned by xmhw_amd.mhw_tracks()")
+    if mhw.point:
+        raise XmhwException("mhw_track_intensity needs a grid: a single-point series has no objects")
+    if weights_label(weights) != tr.attrs.get("weights"):
+        raise XmhwException(f"tr was made with weights {tr.attrs.get('weights')!r}, got {weights_label(weights)!r}: give "
+                            "mhw_track_intensity() the weights mhw_tracks() was given")
+    params = mhw.attrs.get("xmhw_parameters")
+    if params is not None and (_COLD_TEXT in params) != bool(coldSpells):
+        raise XmhwException(f"coldSpells={bool(coldSpells)} differs from the detection's recorded parameters")
+    if _is_xarray(temp):
+        coords, coord_attrs = _from_xarray(temp)
+        dims = list(temp.dims)
+    else:
+        coords, dims = dict(temp.coords), list(temp.dims)
+    if tdim not in dims:
+        raise XmhwException(f"{tdim} dimension not present, default"
+                            + "is 'time' or pass as tdim='time_dimension_name'")
+    if len(dims) == 1:
+        raise XmhwException("mhw_track_intensity needs a grid: a single-point series has no objects")
+    sdims = sorted(d for d in dims if d != tdim)
+    shape = tuple(temp.shape) if _is_xarray(temp) else tuple(np.shape(temp.values))
+    sshape = tuple(int(shape[dims.index(d)]) for d in sdims)
+    if tuple(mhw.sdims) != tuple(sdims) or tuple(int(v) for v in mhw.sshape) != sshape:
+        raise XmhwException(f"temp is on the grid {dict(zip(sdims, sshape))}, the detection on "
+                            f"{dict(zip(mhw.sdims, mhw.sshape))}: mhw does not belong to temp")
+    T = int(np.asarray(coords[tdim]).shape[0])
+    if np.asarray(mhw.time).shape[0] != T:
+        raise XmhwException(f"temp has {T} time steps, the detection {np.asarray(mhw.time).shape[0]}")
+    rows = selection_rows(mhw, obj, tr)
+    view = mhw.compact_view()
+    C, t0, offsets = view["C"], rows.time_start, rows.offsets
+    m, L = rows.m, rows.L
+    ib = intensity_bits(obj.weight_bits, C)
+    if ib < 1:
+        raise XmhwException(f"a grid of {sshape} with {C} ocean cells leaves no bits for the intensity weights")
+    w = resolve_weights(weights, mhw.coords, list(sdims), None, list(sdims), sshape)
+    wi = quantise_weights(w, ib)[0][view["cell_index"]]
+    keep_want = np.asarray(mhw.keep, dtype=bool).reshape(-1)
+    got = {}
+
+    def on_cells(ts, sec, thc, doy, doys, minDuration, joinGaps, maxGap, coldSpells, intermediate, pad=None):
+        # _detect() has masked and compacted on the host (a stand-in device stage)
+        from .landmask import keep_mask, stack_cells
+        keep = keep_mask(stack_cells(np.asarray(temp.values), dims, tdim)[0], anynans)
+        if not np.array_equal(keep, keep_want):
+            raise XmhwException("the land mask of temp differs from mhw.keep: mhw does not belong to temp")
+        extra = {} if pad is None else {"pad": pad}
+        if max_batch_bytes is not None and _compute is None:
+            extra["max_batch_bytes"] = max_batch_bytes
+        got["stage"] = (_compute or track_intensity_cells)(ts, sec, thc, doy, doys, rows, wi, coldSpells, **extra)
+        return dict(table=np.zeros((0, 31)), offsets=np.zeros(ts.shape[1] + 1, dtype=np.int64), inter=None)
+
+    def on_grid(stacked, anynans_, sec, thc, doy, doys, minDuration, joinGaps, maxGap, coldSpells, intermediate,
+                clim_stacked=False, pad=None):
+        got["stage"], keep = track_intensity_grid(stacked, anynans_, sec, thc, doy, doys, rows, wi, keep_want, coldSpells,
+                                                  max_batch_bytes=max_batch_bytes, clim_stacked=clim_stacked, pad=pad)
+        return dict(table=np.zeros((0, 31)), offsets=np.zeros(int(keep.sum()) + 1, dtype=np.int64), inter=None, keep=keep)
+
+    series = GridSeries(temp.values, dims, coords, coord_attrs=coord_attrs) if _is_xarray(temp) else temp
+    as_series = lambda a: GridSeries(a.values, a.dims, _from_xarray(a)[0]) if _is_xarray(a) else a   # noqa: E731
+    _detect(series, as_series(th), as_series(se), on_cells, tdim, 5, True, 2, maxPadLength, coldSpells, False, anynans, tstep,
+            grid_compute=None if _compute is not None else on_grid)
+    st = got["stage"]
+    if st.get("n_bad"):
+        raise XmhwException(f"{st['n_bad']} voxels of table rows do not lie within their object's days: obj or tr does "
+                            "not belong to mhw")
+    if st.get("n_range"):
+        raise XmhwException(f"{st['n_range']} voxels hold an anomaly of 2**{RANGE_BITS} and more in magnitude: are temp, th "
+                            "and se in the same units, and se the climatology of temp?")
+    f = dict(ids=tr.ids, offsets=tr.offsets, time_start=tr.time_start, time_end=tr.time_end, duration=tr.duration, pos=tr.pos)
+    f["n_valid"] = np.ascontiguousarray(st["n_valid"], dtype=np.int32)
+    f["wsum_i"], f["isum_q"] = (np.ascontiguousarray(st[k], dtype=np.int64) for k in ("wsum_i", "isum_q"))
+    f["intensity_max"] = np.ascontiguousarray(st["intensity_max"], dtype=np.float64)
+    f["cat_cells"] = np.ascontiguousarray(st["cat_cells"], dtype=np.int32)
+    if any(f[k].shape != (L,) for k in STAGE_FIELDS[:4]) or f["cat_cells"].shape != (4, L):
+        raise XmhwException(f"track intensity stage returned arrays that do not fit {L} entries")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = f["isum_q"].astype(np.float64) / (f["wsum_i"].astype(np.float64) * 2.0 ** INTENSITY_BITS)
+    f["intensity_mean"] = np.where(f["wsum_i"] > 0, mean, np.nan)
+    first = offsets[:-1]
+    if m:
+        durs = np.diff(offsets)
+        f["intensity_cumulative"] = np.add.reduceat(np.where(np.isnan(f["intensity_mean"]), 0.0, f["intensity_mean"]), first)
+        low = np.where(np.isnan(f["intensity_max"]), -np.inf, f["intensity_max"])
+        peak = np.maximum.reduceat(low, first)
+        at = np.where(low == np.repeat(peak, durs), np.arange(L, dtype=np.int64), L)
+        has = np.isfinite(peak)
+        f["intensity_peak"] = np.where(has, peak, np.nan)
+        f["pos_peak"] = np.where(has, np.minimum.reduceat(at, first) - first + t0, -1).astype(np.int32)
+    else:
+        f["intensity_cumulative"], f["intensity_peak"] = np.zeros(0), np.zeros(0)
+        f["pos_peak"] = np.zeros(0, dtype=np.int32)
+    attrs = {"weights": weights_label(weights)}
+    if params is not None:
+        attrs["xmhw_parameters"] = params
+    return TrackIntensityDataset(f, mhw.time, mhw.sdims, sshape, ib, C, attrs)
