@@ -656,6 +656,43 @@ int xmhw_object_tracks(const int32_t *start_dev, const int32_t *end_dev, int64_t
                        const int32_t *time_start_dev, const int64_t *offsets_dev, int64_t n_slots, int64_t L,
                        int32_t *n_cells_dev, int64_t *sums_dev, int64_t ld, int32_t *n_bad_dev, void *stream);
 
+/* ---- mhw_track_parts(): the connected parts of every object on each of its days, ragged -------------- *
+ * The rows and the ragged layout are those of xmhw_object_tracks: start_dev / end_dev / slot_dev / cell_of_row_dev
+ * [n] int32, slot in [0, n_slots) = the position of the row's object in the selection (any other slot: the row does
+ * nothing), selected object i owns the entries offsets_dev[i] .. offsets_dev[i + 1] - 1, one per day from
+ * time_start_dev[i]; offsets_dev[n_slots] == L.  The rows of cell c are row_offsets_dev[c] .. row_offsets_dev[c + 1]
+ * (int64[C + 1]), in time order, as for xmhw_event_objects; nbr_dev[C][K] int32 lists every cell's spatial neighbours
+ * (-1: none; symmetric, a cell is not its own neighbour; K = 4 or 8 in mhw_track_parts()).  wq_dev[C] int64 >= 0.
+ *
+ * The footprint of object i on day t is the set of cells holding a row of slot i with start <= t <= end; two
+ * footprint cells are adjacent iff one is among the other's neighbours; a part is a connected component.  Rows of
+ * different slots are never joined, whatever nbr says.  Entry offsets[i] + (t - time_start[i]) receives n_parts
+ * (int32, the number of parts), cells_largest (int32, the most cells in one part) and area_largest_q (int64, the
+ * largest sum of wq over one part).  The two maxima are independent: they may come from different parts.
+ *
+ * Voxels.  vox_off_dev[n + 1] int64 is the exclusive prefix sum of end - start + 1 over the rows with a slot in
+ * [0, n_slots), 0 for the others; V = vox_off_dev[n], given by the caller; day t of row r is voxel vox_off[r] + t -
+ * start[r].  SCRATCH: XMHW_PARTS_VOXEL_BYTES (16) per voxel -- parent int32, cells int32, area int64 -- taken from
+ * the stream's scratch buffer, as in xmhw_coverage_accumulate_*; the caller passes none.
+ *
+ * Method, five launches on `stream`: parent[v] = v and the outputs zeroed; lane = row: for every neighbour cell with a
+ * smaller number, the rows of that cell that overlap the lane's in time and have its slot are found by a binary search
+ * and a walk, and the two voxels of every common day are united by the lock-free union-find of xmhw_event_objects
+ * (the smaller root wins by compare-and-swap; no wave waits for another); the roots are flattened; every voxel adds 1
+ * and wq[cell] to its root (integer atomics); every root adds 1 to n_parts and raises the two maxima of its entry
+ * (integer atomic maxima, the area as unsigned 64-bit).  Exact, and the same from run to run.
+ * A selected row whose days leave its object's entries, whose cell is outside [0, C) or whose voxel numbers are not
+ * vox_off[r] .. vox_off[r + 1] - 1 within [0, V) is left out and counted in *n_bad_dev (int32; 0 for consistent
+ * inputs): nothing outside entries 0..L-1 and voxels 0..V-1 is ever written.  n, C, n_slots, L or V of 2^31 and more:
+ * XMHW_ERR_UNSUPPORTED (select fewer objects).  Asynchronous on `stream`.                                   */
+#define XMHW_PARTS_VOXEL_BYTES 16
+int xmhw_object_parts(const int32_t *start_dev, const int32_t *end_dev, const int32_t *slot_dev,
+                      const int32_t *cell_of_row_dev, int64_t n, const int64_t *row_offsets_dev, int64_t C,
+                      const int32_t *nbr_dev, int32_t K, const int64_t *wq_dev, const int64_t *vox_off_dev, int64_t V,
+                      const int32_t *time_start_dev, const int64_t *offsets_dev, int64_t n_slots, int64_t L,
+                      int32_t *n_parts_dev, int32_t *cells_largest_dev, int64_t *area_largest_q_dev,
+                      int32_t *n_bad_dev, void *stream);
+
 /* ---- mhw_track_intensity(): the daily intensity and category series of the objects, ragged ----------- *
  * The one object stage that visits voxels: it joins the series, the climatology and the object partition.  The
  * ragged layout is that of xmhw_object_tracks: selected object i lives from time_start_dev[i] and owns the entries

@@ -1956,6 +1956,30 @@ int xmhw_object_tracks(const int32_t* start, const int32_t* end, int64_t n, cons
     return XMHW_OK;
 }
 
+int xmhw_object_parts(const int32_t* start, const int32_t* end, const int32_t* slot, const int32_t* cell_of_row, int64_t n,
+                      const int64_t* row_offsets, int64_t C, const int32_t* nbr, int32_t K, const int64_t* wq,
+                      const int64_t* vox_off, int64_t V, const int32_t* time_start, const int64_t* offsets, int64_t n_slots,
+                      int64_t L, int32_t* n_parts, int32_t* cells_largest, int64_t* area_largest_q, int32_t* n_bad,
+                      void* stream) {
+    if (n < 0 || C < 0 || n_slots < 0 || L < 0 || V < 0) return fail(XMHW_ERR_INVALID, "bad n/C/n_slots/L/V");
+    if (K < 1) return fail(XMHW_ERR_INVALID, "K must be >= 1");
+    if (n > 0x7FFFFFFFll || C > 0x7FFFFFFFll || n_slots > 0x7FFFFFFFll || L > 0x7FFFFFFFll || V > 0x7FFFFFFFll)
+        return fail(XMHW_ERR_UNSUPPORTED, "object_parts: 2^31 rows, cells, slots, series entries or voxels and more");
+    if (!n_bad || (L > 0 && (!n_parts || !cells_largest || !area_largest_q))) return fail(XMHW_ERR_INVALID, "NULL output buffer");
+    if (n > 0 && n_slots > 0 && L > 0 &&
+        (!start || !end || !slot || !cell_of_row || !row_offsets || !nbr || !wq || !vox_off || !time_start || !offsets))
+        return fail(XMHW_ERR_INVALID, "NULL buffer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    void* sp = nullptr;                              // parent, cells and area of every voxel live in this stream's scratch buffer
+    ScratchRef scratch_keep;
+    hipError_t e = scratch_get(st, xmhw::object_parts_scratch_bytes(V), &sp, &scratch_keep);
+    if (e != hipSuccess) return hip_fail(e, "scratch allocation");
+    e = xmhw::launch_object_parts(start, end, slot, cell_of_row, n, row_offsets, C, nbr, K, wq, vox_off, V, time_start, offsets,
+                                  n_slots, L, n_parts, cells_largest, area_largest_q, n_bad, sp, st);
+    if (e != hipSuccess) return hip_fail(e, "object_parts launch");
+    return XMHW_OK;
+}
+
 int xmhw_set_track_intensity_combine(int32_t on) {
     if (on != 0 && on != 1) return fail(XMHW_ERR_INVALID, "on must be 0 or 1");
     g_track_intensity_combine = on;

@@ -295,6 +295,22 @@ hipError_t launch_object_tracks(const int32_t* start, const int32_t* end, int64_
                                 int32_t* n_cells, int64_t* sums, int64_t ld, int32_t* n_bad, int64_t* scratch,
                                 hipStream_t stream);
 
+// mhw_track_parts() (kernels_parts.hip): the connected parts of every selected object on each of its days, in the
+// ragged layout of launch_object_tracks (entry offsets[slot] + (t - time_start[slot])).  The rows of cell c are
+// row_offsets[c]..row_offsets[c + 1] in time order; nbr[C][K] lists the spatial neighbours (-1: none); only rows of
+// equal slot are united.  vox_off[n + 1] is the exclusive prefix sum of the durations of the selected rows (0 for the
+// others), V = vox_off[n] the number of voxels.  Initialises and fills n_parts[L], cells_largest[L] (int32) and
+// area_largest_q[L] (the largest sum of wq over one part; an independent maximum).  scratch: kPartsVoxelBytes per voxel
+// (area int64[V], parent int32[V], cells int32[V]), object_parts_scratch_bytes(V).  *n_bad counts the selected rows
+// left out because their days, cell or voxel numbers do not fit (0 for consistent inputs).
+constexpr int kPartsVoxelBytes = 16;
+size_t object_parts_scratch_bytes(int64_t V);
+hipError_t launch_object_parts(const int32_t* start, const int32_t* end, const int32_t* slot, const int32_t* cell_of_row,
+                               int64_t n, const int64_t* row_offsets, int64_t C, const int32_t* nbr, int32_t K,
+                               const int64_t* wq, const int64_t* vox_off, int64_t V, const int32_t* time_start,
+                               const int64_t* offsets, int64_t n_slots, int64_t L, int32_t* n_parts, int32_t* cells_largest,
+                               int64_t* area_largest_q, int32_t* n_bad, void* scratch, hipStream_t stream);
+
 // mhw_track_intensity() (kernels_track_intensity.hip): the per-voxel pass over one slab of n compacted cells.  The slab's
 // table rows (start / end / slot, n_rows of them, the rows of cell c = row_offsets[c]..row_offsets[c + 1], in time
 // order) are walked together with the steps of a chunk of kTrackIntensityChunk steps; a voxel of a row whose slot is in

@@ -8,7 +8,7 @@
 //   objects_link     lane = row.  Rows are numbered cell by cell, so every row of a neighbour cell nc < c is smaller
 //                    than the lane's own: only those neighbours are searched, which unites every pair exactly once.
 //                    Per neighbour: a binary search of its rows (in time order, ends increasing) for the first with
-//                    end >= start - gap, then a walk while start' <= end + gap.  unite() is a lock-free union-find:
+//                    end >= start - gap, then a walk while start' <= end + gap.  unite() (union_find.h) is a lock-free union-find:
 //                    the larger root goes under the smaller by a compare-and-swap that succeeds only while the target
 //                    is still its own parent; on failure both ends are found again.  parent[x] <= x always, so a
 //                    tree's root is its smallest row under any schedule.  find() reads with relaxed agent-scope atomic
@@ -26,6 +26,7 @@
 //   objects_finish   key -> float64 (NaN where no row had a value).
 #include "device_common.h"
 #include "kernels.h"
+#include "union_find.h"                             // parent_load, find_root, unite
 
 namespace xmhw {
 
@@ -33,34 +34,6 @@ namespace {
 
 constexpr int kObjThreads = 256;
 constexpr int kObjChunks = 8;                       // chunks of 64 rows per wave in objects_reduce
-
-__device__ __forceinline__ int32_t parent_load(const int32_t* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ int32_t find_root(int32_t* __restrict__ parent, int32_t x) {
-    int32_t p = parent_load(parent + x);
-    while (p != x) {                                 // parent[x] < x for every non-root: the walk ends
-        const int32_t gp = parent_load(parent + p);
-        if (gp != p) __hip_atomic_store(parent + x, gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        x = p;
-        p = gp;
-    }
-    return x;
-}
-
-__device__ __forceinline__ void unite(int32_t* __restrict__ parent, int32_t a, int32_t b) {
-    for (;;) {
-        a = find_root(parent, a);
-        b = find_root(parent, b);
-        if (a == b) return;
-        if (a < b) { const int32_t t = a; a = b; b = t; }
-        int32_t expected = a;                        // only a root may be linked: a stale root is found again
-        if (__hip_atomic_compare_exchange_strong(parent + a, &expected, b, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_AGENT))
-            return;
-    }
-}
 
 __global__ __launch_bounds__(kObjThreads) void objects_init(const int64_t* __restrict__ offsets, int64_t C, int64_t n,
                                                             int32_t* __restrict__ cell_of_row,

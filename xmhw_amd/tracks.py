@@ -211,24 +211,17 @@ def moment_bits(weight_bits, n_ocean, index_extent=None):
     return int(min(int(weight_bits), 61 - ubits - int(n_ocean).bit_length()))
 
 
-def mhw_tracks(mhw, obj, ids=None, weights=None, _compute=None):
-    """The daily series of the objects of mhw_objects(): cells, area and centre on every day of every object.
-
-    ``mhw``: the EventDataset of detect(); ``obj``: the ObjectDataset mhw_objects() returned for it.  ``ids``: None
-    for every object, or a 1-D integer array of distinct object ids; the result keeps their order.  ``weights``:
-    None, "coslat" or an array on the spatial grid, as for mhw_objects(); give the same ones and the area series of
-    an object sums to its ``area_days_q``.  They are quantised with ``obj.weight_bits``.
-
-    Returns a TrackDataset (module docstring: the definition; class docstring: the fields).  Every series is a sum
-    of integers: exact, and the same from run to run.  ``_compute``: a stand-in for tracks_device() (host tests)."""
+def checked_selection(mhw, obj, ids, who):
+    """The checks every stage of the object chain makes of ``mhw``, ``obj`` and ``ids`` (``who``: the function's name
+    in the messages).  Returns (sshape, the object of every table row as int64, ids as (m,) int32)."""
     if not isinstance(mhw, EventDataset):
-        raise XmhwException("mhw_tracks expects the EventDataset returned by xmhw_amd.detect()")
+        raise XmhwException(f"{who} expects the EventDataset returned by xmhw_amd.detect()")
     if not isinstance(obj, ObjectDataset):
-        raise XmhwException("mhw_tracks expects the ObjectDataset returned by xmhw_amd.mhw_objects()")
+        raise XmhwException(f"{who} expects the ObjectDataset returned by xmhw_amd.mhw_objects()")
     if mhw.point:
-        raise XmhwException("mhw_tracks needs a grid: a single-point series has no objects")
+        raise XmhwException(f"{who} needs a grid: a single-point series has no objects")
     if len(mhw.sdims) != 2:
-        raise XmhwException(f"mhw_tracks handles two spatial dims, got {mhw.sdims}")
+        raise XmhwException(f"{who} handles two spatial dims, got {mhw.sdims}")
     n = mhw.n_events
     sshape = tuple(int(v) for v in mhw.sshape)
     if np.asarray(obj.object).shape != (n,) or tuple(obj.sshape) != sshape:
@@ -250,6 +243,44 @@ def mhw_tracks(mhw, obj, ids=None, weights=None, _compute=None):
         if np.unique(ids).shape[0] != ids.shape[0]:
             raise XmhwException("ids should be distinct")
         ids = ids.astype(np.int32)
+    return sshape, object_of_row, ids
+
+
+def selection_layout(obj, ids, object_of_row, start, end):
+    """The ragged layout of the selection ``ids`` and the rows that fill it: (time_start (m,) int32, time_end (m,) int32,
+    duration (m,) int64, offsets (m + 1,) int64, slot (n,) int32 = the position of every row's object in ``ids`` or -1)."""
+    m, m_all = ids.shape[0], obj.n_objects
+    # the selection: where its objects start, how long they live, which rows are theirs
+    t0 = np.ascontiguousarray(np.asarray(obj.time_start, dtype=np.int32)[ids])
+    t1 = np.ascontiguousarray(np.asarray(obj.time_end, dtype=np.int32)[ids])
+    dur = t1.astype(np.int64) - t0 + 1
+    if m and dur.min() < 1:
+        raise XmhwException("obj holds an object that ends before it starts")
+    offsets = np.concatenate([[0], np.cumsum(dur)]).astype(np.int64)
+    L = int(offsets[-1])
+    if L + 1 >= 1 << 31:
+        raise XmhwException(f"the series of the {m} selected objects hold {L} entries, 2**31 - 1 and more: select fewer "
+                            "objects with ids=")
+    position = np.full(m_all, -1, dtype=np.int32)
+    position[ids] = np.arange(m, dtype=np.int32)
+    slot = position[object_of_row]
+    sel = slot >= 0
+    if sel.any() and ((start[sel] < t0[slot[sel]]).any() or (end[sel] > t1[slot[sel]]).any()):
+        raise XmhwException("a table row lies outside the days of its object: obj does not belong to mhw")
+    return t0, t1, dur, offsets, slot
+
+
+def mhw_tracks(mhw, obj, ids=None, weights=None, _compute=None):
+    """The daily series of the objects of mhw_objects(): cells, area and centre on every day of every object.
+
+    ``mhw``: the EventDataset of detect(); ``obj``: the ObjectDataset mhw_objects() returned for it.  ``ids``: None
+    for every object, or a 1-D integer array of distinct object ids; the result keeps their order.  ``weights``:
+    None, "coslat" or an array on the spatial grid, as for mhw_objects(); give the same ones and the area series of
+    an object sums to its ``area_days_q``.  They are quantised with ``obj.weight_bits``.
+
+    Returns a TrackDataset (module docstring: the definition; class docstring: the fields).  Every series is a sum
+    of integers: exact, and the same from run to run.  ``_compute``: a stand-in for tracks_device() (host tests)."""
+    sshape, object_of_row, ids = checked_selection(mhw, obj, ids, "mhw_tracks")
     m = ids.shape[0]
     N = int(np.prod(sshape, dtype=np.int64))
     sdims = list(mhw.sdims)
@@ -273,24 +304,9 @@ def mhw_tracks(mhw, obj, ids=None, weights=None, _compute=None):
     else:
         i, j = np.divmod(np.arange(N, dtype=np.int64), sshape[1])
         vec = np.stack([wq, wm * i, wm * j, wm])[:, cell_index]
-    # the selection: where its objects start, how long they live, which rows are theirs
-    t0 = np.ascontiguousarray(np.asarray(obj.time_start, dtype=np.int32)[ids])
-    t1 = np.ascontiguousarray(np.asarray(obj.time_end, dtype=np.int32)[ids])
-    dur = t1.astype(np.int64) - t0 + 1
-    if m and dur.min() < 1:
-        raise XmhwException("obj holds an object that ends before it starts")
-    offsets = np.concatenate([[0], np.cumsum(dur)]).astype(np.int64)
+    t0, t1, dur, offsets, slot = selection_layout(obj, ids, object_of_row, start, end)
     L = int(offsets[-1])
-    if L + 1 >= 1 << 31:
-        raise XmhwException(f"the series of the {m} selected objects hold {L} entries, 2**31 - 1 and more: select fewer "
-                            "objects with ids=")
-    position = np.full(m_all, -1, dtype=np.int32)
-    position[ids] = np.arange(m, dtype=np.int32)
-    slot = position[object_of_row]
     cell_of_row = view["cell_of_row"].astype(np.int32)
-    sel = slot >= 0
-    if sel.any() and ((start[sel] < t0[slot[sel]]).any() or (end[sel] > t1[slot[sel]]).any()):
-        raise XmhwException("a table row lies outside the days of its object: obj does not belong to mhw")
     if L == 0:
         got = dict(n_cells=np.zeros(0, dtype=np.int32), sums=np.zeros((4, 0), dtype=np.int64))
     else:
