@@ -37,7 +37,7 @@ def oracle_compute(table, offsets, years, edges, mtime, ts, cats):
     return out
 
 
-def _mhw(point=False):
+def _mhw(point=False, land_lines=False):
     g = np.load(os.path.join(GOLD, "mhw_features_cases.npz"))
     cases = [0, 3, 6, 9] if not point else [0]
     T = min(int(g["offsets"][c + 1] - g["offsets"][c]) for c in cases)
@@ -50,6 +50,10 @@ def _mhw(point=False):
     time = np.arange("2001-01-01", T, dtype="datetime64[D]") if False else np.datetime64("2001-01-01") + np.arange(T)
     if point:
         return EventDataset(table, offsets, time, np.array([0]), np.array([True]), (), (), {}, {}, {}, {}, True), T
+    if land_lines:                                                # 4 x 3 grid, lines 1 and 3 and column 1 all land
+        keep = np.array([True, False, True, False, False, False, True, False, True, False, False, False])
+        return EventDataset(table, offsets, time, np.nonzero(keep)[0], keep, ("lat", "lon"), (4, 3),
+                            {"lat": np.array([10.0, 20.0, 30.0, 40.0]), "lon": np.array([1.0, 2.0, 3.0])}, {}, {}, {}, False), T
     keep = np.array([True, False, True, True, True, False])       # 2 x 3 grid, two land cells, no all-land line
     return EventDataset(table, offsets, time, np.nonzero(keep)[0], keep, ("lat", "lon"), (2, 3),
                         {"lat": np.array([10.0, 20.0]), "lon": np.array([1.0, 2.0, 3.0])}, {}, {}, {}, False), T
@@ -96,3 +100,67 @@ def test_point_and_time_statistics():
     npt.assert_array_equal(blk2["total_days"], blk2["moderate_days"] + blk2["strong_days"] + blk2["severe_days"]
                            + blk2["extreme_days"])
     assert blk2["total_days"].sum() == np.isin(cats, [1, 2, 3, 4]).sum()
+
+
+def _grid_series(T, shape, seed=3):
+    """ts whose mean names its cell (100 * line + 10 * column, noise below 1) and cats, on (T, *shape)"""
+    rng = np.random.default_rng(seed)
+    i, j = np.meshgrid(np.arange(shape[0]), np.arange(shape[1]), indexing="ij")
+    ts = (100.0 * i + 10.0 * j + rng.uniform(-0.9, 0.9, size=(T,) + shape)).astype(np.float32)
+    return ts, np.floor(rng.uniform(-2, 5, size=(T,) + shape))
+
+
+def _same(a, b):
+    assert a.dims == b.dims and list(a.data_vars) == list(b.data_vars)
+    for k in a.data_vars:
+        npt.assert_array_equal(a[k], b[k], err_msg=k)
+    for k in a.coords:
+        npt.assert_array_equal(a.coords[k], b.coords[k])
+
+
+def test_series_without_the_all_land_lines_of_the_grid():
+    """a series (InterDataset) on the grid as detect() returns it -- all-land lines gone -- lands in the same cells
+    as the series on the full grid the events were detected on"""
+    from xmhw_amd.detect import InterDataset
+    mhw, T = _mhw(land_lines=True)
+    ts, cats = _grid_series(T, (4, 3))
+    full = block_average(mhw, dstime=InterDataset({"ts": ts, "cats": cats}, ("time", "lat", "lon"), {}),
+                         _compute=oracle_compute)
+    rows, cols = [0, 2], [0, 2]
+    sub = InterDataset({"ts": ts[:, rows][:, :, cols], "cats": cats[:, rows][:, :, cols]}, ("time", "lat", "lon"), {})
+    got = block_average(mhw, dstime=sub, _compute=oracle_compute)
+    _same(got, full)
+    assert got["ts_mean"].shape[1:] == (2, 2) and "total_days" in got.data_vars
+    npt.assert_array_equal(got.coords["lat"], [10.0, 30.0])
+    npt.assert_array_equal(got.coords["lon"], [1.0, 3.0])
+    for a, i in enumerate(rows):
+        for b, j in enumerate(cols):
+            npt.assert_array_equal(np.rint(got["ts_mean"][:, a, b]), 100 * i + 10 * j)       # every cell got ITS series
+            years = mhw.time.astype("datetime64[Y]").astype(int) + 1970
+            npt.assert_array_equal(got["strong_days"][:, a, b], [(cats[years == y, i, j] == 2).sum() for y in got.coords["years"]])
+
+
+@pytest.mark.parametrize("dims", [("lat", "time", "lon"), ("lon", "lat", "time"), ("lat", "lon", "time")])
+def test_series_whose_first_dimension_is_not_time(dims):
+    from xmhw_amd import GridSeries
+    mhw, T = _mhw()
+    ts, _ = _grid_series(T, (2, 3))
+    coords = {"time": mhw.time, "lat": mhw.coords["lat"], "lon": mhw.coords["lon"]}
+    want = block_average(mhw, dstime=GridSeries(ts, ("time", "lat", "lon"), coords), _compute=oracle_compute)
+    moved = np.transpose(ts, [("time", "lat", "lon").index(d) for d in dims])
+    got = block_average(mhw, dstime=GridSeries(moved, dims, coords), _compute=oracle_compute)
+    _same(got, want)
+    assert np.isnan(got["ts_mean"][:, 0, 1]).all()                                           # land
+    npt.assert_array_equal(np.rint(got["ts_mean"][:, 1, 1]), 110)
+
+
+def test_series_that_does_not_fit_the_events():
+    from xmhw_amd import GridSeries
+    mhw, T = _mhw()
+    coords = {"lat": mhw.coords["lat"], "lon": mhw.coords["lon"]}
+    short = GridSeries(np.zeros((T - 1, 2, 3), dtype=np.float32), ("time", "lat", "lon"), dict(coords, time=mhw.time[:-1]))
+    with pytest.raises(XmhwException, match="do not share the time axis"):
+        block_average(mhw, dstime=short, _compute=oracle_compute)
+    other = GridSeries(np.zeros((T, 3, 2), dtype=np.float32), ("time", "lat", "lon"), dict(coords, time=mhw.time))
+    with pytest.raises(XmhwException, match=r"dstime has grid \(3, 2\), the events were detected on \(2, 3\)"):
+        block_average(mhw, dstime=other, _compute=oracle_compute)

@@ -68,8 +68,11 @@ def block_stats_device(table, offsets, years_of_t, edges, mtime="time_start", ts
         raise XmhwException(f"mtime should be one of time_start, time_peak, time_end, got {mtime}")
     col = EventDataset.columns.index(mtime)
     out = {}
-    if C == 0 or nb <= 0:
-        return {k: np.zeros((max(nb, 0), C)) for k in MHW_STATS}
+    if C == 0 or nb <= 0:                 # nothing to launch: the keys of the call with cells, arrays without entries
+        names = MHW_STATS + (TS_STATS if ts is not None else [])
+        if ts is not None and cats is not None:
+            names = names + CAT_STATS + ["total_days"]
+        return {k: np.zeros((max(nb, 0), C)) for k in names}
     with DeviceScope() as s:
         d_bin = s.upload(_bin_of_t(np.asarray(years_of_t, dtype=np.int64), edges))
         d_tab = s.upload(table if table.size else np.zeros((1, len(EventDataset.columns))))
