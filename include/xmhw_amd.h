@@ -693,6 +693,52 @@ int xmhw_object_parts(const int32_t *start_dev, const int32_t *end_dev, const in
                       int32_t *n_parts_dev, int32_t *cells_largest_dev, int64_t *area_largest_q_dev,
                       int32_t *n_bad_dev, void *stream);
 
+/* ---- mhw_track_genealogy(): the links between the parts of consecutive days of every object ----------- *
+ * The rows, the ragged layout, the neighbour table, the voxels and the parts are those of xmhw_object_parts (no
+ * weights).  Part A of day t - 1 and part B of day t of one selected object are linked iff some cell lies in A on
+ * t - 1 and in B on t (overlap; a neighbouring cell does not link).  The distinct links are the edges of the
+ * genealogy; the in-degree of a part counts its links to the day before, its out-degree those to the day after.
+ * counts_dev[XMHW_GENEALOGY_FIELDS][L] int32, one array of L entries per field in the order of the XMHW_GENEALOGY_*
+ * indices: entry offsets[i] + (t - time_start[i]) receives, over the parts of object i on day t, their number, the sum
+ * of their in-degrees, the parts of in-degree 0, of in-degree >= 2, of out-degree 0 and of out-degree >= 2.
+ * edges_dev[edge_capacity] uint64 receives the *n_edges_dev (int64) edges as (root of A << 32) | root of B in ARBITRARY
+ * order; the root of a part is its smallest voxel number, a voxel of its smallest cell: the caller finds row, day and
+ * cell of a root by a search of vox_off.  edge_capacity must be at least the number of (row, day) pairs of the selected
+ * rows that have a next day in the same row, plus the pairs of consecutive rows of one cell and one slot with
+ * start == end + 1: then the hash set below is never more than half full.
+ *
+ * SCRATCH, from the stream's scratch buffer: XMHW_GENEALOGY_VOXEL_BYTES (12) per voxel -- parent, in-degree and
+ * out-degree, int32 -- plus XMHW_GENEALOGY_SLOT_BYTES (8) per slot of a hash set whose capacity is the smallest power
+ * of two >= 2 * max(edge_capacity, 1).
+ *
+ * Method, seven launches on `stream`: everything initialised (an empty slot is all ones; roots are below 2^31, so no
+ * key equals it); the link and flatten passes of xmhw_object_parts; lane = row: for every day of the row but its last
+ * the key (root today, root tomorrow), and the key across two touching rows of one cell and slot, inserted by linear
+ * probing from a mixed hash with one 64-bit compare-and-swap per probe -- an empty slot taken makes the lane the one
+ * winner of that distinct pair, which adds 1 to the two degrees; the same key found is a duplicate; another key sends
+ * the lane to the next slot; the loop ends after `capacity` probes at the latest and then sets *overflow_dev (int32;
+ * 0 whenever edge_capacity is as stated above); no lane waits for another; lane = slot: the slots in use are copied to
+ * edges_dev, a wave taking its places with one atomic, nothing at or beyond edge_capacity written; lane = row: every
+ * voxel that is its own root adds to the six counts of its entry (integer atomics).  Exact, and the same from run to
+ * run once the edges are sorted.  Rows that do not fit are left out and counted in *n_bad_dev as in
+ * xmhw_object_parts.  n, C, n_slots, L, V or edge_capacity of 2^31 and more: XMHW_ERR_UNSUPPORTED.  Asynchronous on
+ * `stream`.                                                                                                */
+#define XMHW_GENEALOGY_VOXEL_BYTES 12
+#define XMHW_GENEALOGY_SLOT_BYTES 8
+#define XMHW_GENEALOGY_FIELDS 6
+#define XMHW_GENEALOGY_PARTS 0
+#define XMHW_GENEALOGY_LINKS 1
+#define XMHW_GENEALOGY_BORN 2
+#define XMHW_GENEALOGY_MERGED 3
+#define XMHW_GENEALOGY_ENDED 4
+#define XMHW_GENEALOGY_SPLIT 5
+int xmhw_object_genealogy(const int32_t *start_dev, const int32_t *end_dev, const int32_t *slot_dev,
+                          const int32_t *cell_of_row_dev, int64_t n, const int64_t *row_offsets_dev, int64_t C,
+                          const int32_t *nbr_dev, int32_t K, const int64_t *vox_off_dev, int64_t V,
+                          const int32_t *time_start_dev, const int64_t *offsets_dev, int64_t n_slots, int64_t L,
+                          int32_t *counts_dev, uint64_t *edges_dev, int64_t edge_capacity, int64_t *n_edges_dev,
+                          int32_t *n_bad_dev, int32_t *overflow_dev, void *stream);
+
 /* ---- mhw_track_intensity(): the daily intensity and category series of the objects, ragged ----------- *
  * The one object stage that visits voxels: it joins the series, the climatology and the object partition.  The
  * ragged layout is that of xmhw_object_tracks: selected object i lives from time_start_dev[i] and owns the entries

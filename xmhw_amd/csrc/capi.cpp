@@ -1980,6 +1980,40 @@ int xmhw_object_parts(const int32_t* start, const int32_t* end, const int32_t* s
     return XMHW_OK;
 }
 
+static_assert(xmhw::kGenealogyVoxelBytes == XMHW_GENEALOGY_VOXEL_BYTES && xmhw::kGenealogySlotBytes == XMHW_GENEALOGY_SLOT_BYTES &&
+                  xmhw::kGenealogyFields == XMHW_GENEALOGY_FIELDS && xmhw::kGenealogyParts == XMHW_GENEALOGY_PARTS &&
+                  xmhw::kGenealogyLinks == XMHW_GENEALOGY_LINKS && xmhw::kGenealogyBorn == XMHW_GENEALOGY_BORN &&
+                  xmhw::kGenealogyMerged == XMHW_GENEALOGY_MERGED && xmhw::kGenealogyEnded == XMHW_GENEALOGY_ENDED &&
+                  xmhw::kGenealogySplit == XMHW_GENEALOGY_SPLIT,
+              "the genealogy constants of include/xmhw_amd.h and kernels.h differ");
+
+int xmhw_object_genealogy(const int32_t* start, const int32_t* end, const int32_t* slot, const int32_t* cell_of_row, int64_t n,
+                          const int64_t* row_offsets, int64_t C, const int32_t* nbr, int32_t K, const int64_t* vox_off,
+                          int64_t V, const int32_t* time_start, const int64_t* offsets, int64_t n_slots, int64_t L,
+                          int32_t* counts, uint64_t* edges, int64_t edge_capacity, int64_t* n_edges, int32_t* n_bad,
+                          int32_t* overflow, void* stream) {
+    if (n < 0 || C < 0 || n_slots < 0 || L < 0 || V < 0 || edge_capacity < 0)
+        return fail(XMHW_ERR_INVALID, "bad n/C/n_slots/L/V/edge_capacity");
+    if (K < 1) return fail(XMHW_ERR_INVALID, "K must be >= 1");
+    if (n > 0x7FFFFFFFll || C > 0x7FFFFFFFll || n_slots > 0x7FFFFFFFll || L > 0x7FFFFFFFll || V > 0x7FFFFFFFll ||
+        edge_capacity > 0x7FFFFFFFll)
+        return fail(XMHW_ERR_UNSUPPORTED, "object_genealogy: 2^31 rows, cells, slots, series entries, voxels or edges and more");
+    if (!n_bad || !overflow || !n_edges || (L > 0 && !counts) || (edge_capacity > 0 && !edges))
+        return fail(XMHW_ERR_INVALID, "NULL output buffer");
+    if (n > 0 && n_slots > 0 && L > 0 &&
+        (!start || !end || !slot || !cell_of_row || !row_offsets || !nbr || !vox_off || !time_start || !offsets))
+        return fail(XMHW_ERR_INVALID, "NULL buffer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    void* sp = nullptr;                              // the hash set and parent, indeg, outdeg of every voxel: this stream's scratch
+    ScratchRef scratch_keep;
+    hipError_t e = scratch_get(st, xmhw::object_genealogy_scratch_bytes(V, edge_capacity), &sp, &scratch_keep);
+    if (e != hipSuccess) return hip_fail(e, "scratch allocation");
+    e = xmhw::launch_object_genealogy(start, end, slot, cell_of_row, n, row_offsets, C, nbr, K, vox_off, V, time_start, offsets,
+                                      n_slots, L, counts, edges, edge_capacity, n_edges, n_bad, overflow, sp, st);
+    if (e != hipSuccess) return hip_fail(e, "object_genealogy launch");
+    return XMHW_OK;
+}
+
 int xmhw_set_track_intensity_combine(int32_t on) {
     if (on != 0 && on != 1) return fail(XMHW_ERR_INVALID, "on must be 0 or 1");
     g_track_intensity_combine = on;

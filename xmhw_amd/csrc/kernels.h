@@ -311,6 +311,29 @@ hipError_t launch_object_parts(const int32_t* start, const int32_t* end, const i
                                const int64_t* offsets, int64_t n_slots, int64_t L, int32_t* n_parts, int32_t* cells_largest,
                                int64_t* area_largest_q, int32_t* n_bad, void* scratch, hipStream_t stream);
 
+// mhw_track_genealogy() (kernels_genealogy.hip): the links between the parts of consecutive days of every selected
+// object, in the ragged layout and on the rows and voxels of launch_object_parts.  Initialises and fills counts[6][L]
+// (int32, one array of L per field, in the order of the kGenealogy* indices below), writes the *n_edges distinct
+// links as (root voxel of the earlier part << 32) | root voxel of the later part to edges[edge_capacity] in arbitrary
+// order (a root is the smallest voxel number of its part) and sets *n_bad (rows left out, as launch_object_parts) and
+// *overflow (nonzero: the hash set was full, edge_capacity did not bound the number of keys).  edge_capacity >= the
+// number of (row, day) pairs with a next day in the row plus the row pairs of one cell and slot that touch in time.
+// scratch: the hash set of object_genealogy_table_slots(edge_capacity) slots of kGenealogySlotBytes, then
+// kGenealogyVoxelBytes per voxel (parent, indeg, outdeg int32[V]); object_genealogy_scratch_bytes(V, edge_capacity).
+constexpr int kGenealogyVoxelBytes = 12;
+constexpr int kGenealogySlotBytes = 8;
+constexpr int kGenealogyFields = 6;
+constexpr int kGenealogyParts = 0, kGenealogyLinks = 1, kGenealogyBorn = 2, kGenealogyMerged = 3, kGenealogyEnded = 4,
+              kGenealogySplit = 5;
+int64_t object_genealogy_table_slots(int64_t edge_capacity);
+size_t object_genealogy_scratch_bytes(int64_t V, int64_t edge_capacity);
+hipError_t launch_object_genealogy(const int32_t* start, const int32_t* end, const int32_t* slot,
+                                   const int32_t* cell_of_row, int64_t n, const int64_t* row_offsets, int64_t C,
+                                   const int32_t* nbr, int32_t K, const int64_t* vox_off, int64_t V,
+                                   const int32_t* time_start, const int64_t* offsets, int64_t n_slots, int64_t L,
+                                   int32_t* counts, uint64_t* edges, int64_t edge_capacity, int64_t* n_edges,
+                                   int32_t* n_bad, int32_t* overflow, void* scratch, hipStream_t stream);
+
 // mhw_track_intensity() (kernels_track_intensity.hip): the per-voxel pass over one slab of n compacted cells.  The slab's
 // table rows (start / end / slot, n_rows of them, the rows of cell c = row_offsets[c]..row_offsets[c + 1], in time
 // order) are walked together with the steps of a chunk of kTrackIntensityChunk steps; a voxel of a row whose slot is in

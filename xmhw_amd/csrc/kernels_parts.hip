@@ -20,14 +20,15 @@
 //   parts_count    the same walk: a voxel that is its own root adds 1 to n_parts[e] and raises cells_largest[e] and
 //                  area_largest_q[e] (an unsigned 64-bit maximum: areas are >= 0) by atomic maxima.
 //
-// A row is *fit* iff its slot is in [0, n_slots), its cell in [0, C), start <= end, its days lie within its object's
+// PartRows, part_row() and the bodies of parts_link and parts_flatten live in parts_rows.h, shared with
+// kernels_genealogy.hip.  A row is *fit* iff its slot is in [0, n_slots), its cell in [0, C), start <= end, its days lie within its object's
 // entries (which lie within 0..L-1) and its voxel numbers vox_off[r] .. vox_off[r + 1] - 1 are exactly its days within
 // [0, V).  A selected row that is not fit is left out of every kernel and counted in *n_bad by parts_count; nothing
 // outside entries 0..L-1 and voxels 0..V-1 is ever written.  Everything is an integer sum or maximum: exact, and the
 // same under any schedule.
 #include "device_common.h"
 #include "kernels.h"
-#include "union_find.h"
+#include "parts_rows.h"
 
 namespace xmhw {
 
@@ -35,36 +36,6 @@ namespace {
 
 constexpr int kPartThreads = 256;
 using u64 = unsigned long long;
-
-struct PartRows {
-    const int32_t *start, *end, *slot, *cell;
-    const int64_t* vox_off;
-    const int32_t* time_start;
-    const int64_t* offsets;
-    int64_t n, C, n_slots, L, V;
-};
-
-struct PartRow {
-    int32_t s, e, sl, c;
-    int64_t vox;                                     // the voxel of day s
-    int64_t entry;                                   // the entry of day s
-};
-
-// 1: the row is fit and `row` describes it; 0: its slot is outside the selection; -1: selected but not fit
-__device__ __forceinline__ int part_row(const PartRows& a, int64_t r, PartRow& row) {
-    const int32_t sl = a.slot[r];
-    if (sl < 0 || sl >= a.n_slots) return 0;
-    const int32_t s = a.start[r], e = a.end[r], c = a.cell[r];
-    const int64_t v0 = a.vox_off[r], v1 = a.vox_off[r + 1];
-    const int64_t o0 = a.offsets[sl], o1 = a.offsets[sl + 1], t0 = a.time_start[sl];
-    const int64_t days = static_cast<int64_t>(e) - s + 1;
-    const int64_t p0 = o0 + (static_cast<int64_t>(s) - t0);
-    if (c < 0 || c >= a.C || days < 1 || v0 < 0 || v1 - v0 != days || v1 > a.V || o0 < 0 || o1 > a.L || p0 < o0 ||
-        p0 + days > o1)
-        return -1;
-    row = PartRow{s, e, sl, c, v0, p0};
-    return 1;
-}
 
 __global__ __launch_bounds__(kPartThreads) void parts_init(int64_t V, int32_t* __restrict__ parent,
                                                            int32_t* __restrict__ cells, int64_t* __restrict__ area,
@@ -89,36 +60,13 @@ __global__ __launch_bounds__(kPartThreads) void parts_link(PartRows a, const int
                                                            int32_t* __restrict__ parent) {
     const int64_t r = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (r >= a.n) return;
-    PartRow me;
-    if (part_row(a, r, me) != 1) return;
-    for (int32_t k = 0; k < K; ++k) {
-        const int32_t nc = nbr[static_cast<int64_t>(me.c) * K + k];
-        if (nc < 0 || nc >= me.c) continue;          // the pair is united from the side of the larger cell
-        int64_t lo = row_offsets[nc], last = row_offsets[nc + 1];
-        lo = lo < 0 ? 0 : lo;                        // offsets that do not describe the rows read no row outside them
-        last = last > a.n ? a.n : last;
-        int64_t hi = last;
-        while (lo < hi) {                            // the first row of nc with end >= start
-            const int64_t mid = lo + (hi - lo) / 2;
-            if (a.end[mid] < me.s) lo = mid + 1; else hi = mid;
-        }
-        for (int64_t j = lo; j < last && a.start[j] <= me.e; ++j) {
-            if (a.slot[j] != me.sl) continue;        // another object, or not selected
-            PartRow other;
-            if (part_row(a, j, other) != 1) continue;
-            const int32_t d0 = other.s > me.s ? other.s : me.s, d1 = other.e < me.e ? other.e : me.e;
-            for (int32_t t = d0; t <= d1; ++t)       // fit rows: both voxels are within [0, V)
-                unite(parent, static_cast<int32_t>(me.vox + (t - me.s)), static_cast<int32_t>(other.vox + (t - other.s)));
-        }
-    }
+    parts_link_row(a, r, row_offsets, nbr, K, parent);
 }
 
 __global__ __launch_bounds__(kPartThreads) void parts_flatten(int64_t V, int32_t* __restrict__ parent) {
     const int64_t v = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (v >= V) return;
-    int32_t x = static_cast<int32_t>(v);
-    for (int32_t p = parent_load(parent + x); p != x; p = parent_load(parent + x)) x = p;
-    __hip_atomic_store(parent + v, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    parts_flatten_voxel(v, parent);
 }
 
 __global__ __launch_bounds__(kPartThreads) void parts_reduce(PartRows a, const int64_t* __restrict__ wq,

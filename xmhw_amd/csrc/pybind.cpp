@@ -607,6 +607,25 @@ PYBIND11_MODULE(_xmhw_hip, m) {
        py::arg("C"), py::arg("nbr"), py::arg("K"), py::arg("wq"), py::arg("vox_off"), py::arg("V"), py::arg("time_start"),
        py::arg("offsets"), py::arg("n_slots"), py::arg("L"), py::arg("n_parts"), py::arg("cells_largest"),
        py::arg("area_largest_q"), py::arg("n_bad"), py::arg("stream") = 0);
+    m.def("object_genealogy", [](uintptr_t start, uintptr_t end, uintptr_t slot, uintptr_t cell_of_row, int64_t n,
+                                 uintptr_t row_offsets, int64_t C, uintptr_t nbr, int32_t K, uintptr_t vox_off, int64_t V,
+                                 uintptr_t time_start, uintptr_t offsets, int64_t n_slots, int64_t L, uintptr_t counts,
+                                 uintptr_t edges, int64_t edge_capacity, uintptr_t n_edges, uintptr_t n_bad,
+                                 uintptr_t overflow, uintptr_t stream) {
+        check(xmhw_object_genealogy(static_cast<const int32_t*>(vp(start)), static_cast<const int32_t*>(vp(end)),
+                                    static_cast<const int32_t*>(vp(slot)), static_cast<const int32_t*>(vp(cell_of_row)), n,
+                                    static_cast<const int64_t*>(vp(row_offsets)), C, static_cast<const int32_t*>(vp(nbr)), K,
+                                    static_cast<const int64_t*>(vp(vox_off)), V, static_cast<const int32_t*>(vp(time_start)),
+                                    static_cast<const int64_t*>(vp(offsets)), n_slots, L, static_cast<int32_t*>(vp(counts)),
+                                    static_cast<uint64_t*>(vp(edges)), edge_capacity, static_cast<int64_t*>(vp(n_edges)),
+                                    static_cast<int32_t*>(vp(n_bad)), static_cast<int32_t*>(vp(overflow)), vp(stream)));
+    }, py::arg("start"), py::arg("end"), py::arg("slot"), py::arg("cell_of_row"), py::arg("n"), py::arg("row_offsets"),
+       py::arg("C"), py::arg("nbr"), py::arg("K"), py::arg("vox_off"), py::arg("V"), py::arg("time_start"),
+       py::arg("offsets"), py::arg("n_slots"), py::arg("L"), py::arg("counts"), py::arg("edges"), py::arg("edge_capacity"),
+       py::arg("n_edges"), py::arg("n_bad"), py::arg("overflow"), py::arg("stream") = 0);
+    m.attr("GENEALOGY_VOXEL_BYTES") = XMHW_GENEALOGY_VOXEL_BYTES;
+    m.attr("GENEALOGY_SLOT_BYTES") = XMHW_GENEALOGY_SLOT_BYTES;
+    m.attr("GENEALOGY_FIELDS") = XMHW_GENEALOGY_FIELDS;
     m.attr("PARTS_VOXEL_BYTES") = XMHW_PARTS_VOXEL_BYTES;
     m.attr("TRACKS_TILE") = XMHW_TRACKS_TILE;
     m.attr("TRACK_INTENSITY_CHUNK") = XMHW_TRACK_INTENSITY_CHUNK;

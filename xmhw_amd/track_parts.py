@@ -36,9 +36,8 @@ Voxels.  Only rows of selected objects have voxels.  vox_off is the (n + 1,) exc
 the selected rows (an unselected row counts 0), V = vox_off[-1], and day t of row r is voxel vox_off[r] + t - start[r].
 The device keeps 16 bytes per voxel; V >= 2**31 is refused before anything is allocated.
 
-Not here: the genealogy -- which part of day t continues into which part of day t + 1, and the split and merge counts
-taken from it.  That needs the number of DISTINCT (part, part) pairs between two days, a deduplication this stage does
-not have.
+The genealogy -- which part of day t continues into which part of day t + 1, and the split and merge counts taken from
+it -- is mhw_track_genealogy() (track_genealogy.py), on the same voxels and the same union-find.
 
 Host side here (validation, selection, neighbour table, weights, voxel numbering, the derived fields); device side in
 csrc/kernels_parts.hip behind track_parts_device().
