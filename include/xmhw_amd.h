@@ -739,6 +739,46 @@ int xmhw_object_genealogy(const int32_t *start_dev, const int32_t *end_dev, cons
                           int32_t *counts_dev, uint64_t *edges_dev, int64_t edge_capacity, int64_t *n_edges_dev,
                           int32_t *n_bad_dev, int32_t *overflow_dev, void *stream);
 
+/* ---- mhw_track_shape(): the perimeter and the coast contact of every object on each of its days ------- *
+ * The rows, the ragged layout and row_offsets_dev are those of xmhw_object_parts (no weights, no voxels, no
+ * scratch).  Every cell has K = 4 faces, in the order dim 0 minus, dim 0 plus, dim 1 minus, dim 1 plus.
+ * faces_dev[C][4] int32 names what lies across each: the compact cell there (>= 0; it may be the same cell for two
+ * faces, on a wrapping dim of length 2), XMHW_SHAPE_FACE_COAST (a grid point that is no cell), XMHW_SHAPE_FACE_BORDER
+ * (no grid point) or XMHW_SHAPE_FACE_FOLDED (a wrapping dim of length 1: no face, nothing is counted).
+ * lq_dev[C][4] int64 >= 0 holds the lengths of the faces; the caller sizes them so that 4 * C * max(lq) < 2^63.
+ *
+ * The footprint of object i on day t is the set of cells holding a row of slot i with start <= t <= end.  A face of
+ * a footprint cell to a cell of the same footprint is shared and counts nothing; a face to any other cell is OPEN; a
+ * coast face is COAST, a border face BORDER.  Entry offsets[i] + (t - time_start[i]) receives, per class in the order
+ * of the XMHW_SHAPE_* indices, edges_dev[XMHW_SHAPE_CLASSES][L] int32 (the number of such faces) and
+ * perimeter_q_dev[XMHW_SHAPE_CLASSES][L] int64 (the sum of their lq), one array of L entries per class, and
+ * cells_edge_dev[L] int32 (the footprint cells with at least one open, coast or border face).
+ *
+ * Method, on `stream`: the seven arrays and *n_bad_dev zeroed by memsets; one launch, lane = row: coast and border
+ * faces are the same on all days of the row; for a face to a cell, the first row of that cell with end >= start is
+ * found by the binary search of xmhw_object_parts and a cursor moves on from there as the lane walks its days once
+ * (rows of a cell are in time order and disjoint); the row under the cursor covers the day iff it has the lane's slot,
+ * fits and has started.  The seven addends of a day are formed in registers; one integer atomic without a return
+ * value goes out per addend that is not zero, none on a day all of whose faces are shared.  Exact, and the same from
+ * run to run.
+ * A selected row whose days leave its object's entries or whose cell is outside [0, C) is left out (it neither adds
+ * nor covers) and counted in *n_bad_dev (int32; 0 for consistent inputs), as is once a row with a face value outside
+ * [XMHW_SHAPE_FACE_FOLDED, C), that face being passed over: nothing outside entries 0..L-1 is ever written, and
+ * row_offsets that do not describe the rows read no row outside [0, n).  K other than 4, or n, C, n_slots or L of
+ * 2^31 and more: XMHW_ERR_UNSUPPORTED.  Asynchronous on `stream`.                                            */
+#define XMHW_SHAPE_CLASSES 3
+#define XMHW_SHAPE_OPEN 0
+#define XMHW_SHAPE_COAST 1
+#define XMHW_SHAPE_BORDER 2
+#define XMHW_SHAPE_FACE_COAST (-1)
+#define XMHW_SHAPE_FACE_BORDER (-2)
+#define XMHW_SHAPE_FACE_FOLDED (-3)
+int xmhw_object_shape(const int32_t *start_dev, const int32_t *end_dev, const int32_t *slot_dev,
+                      const int32_t *cell_of_row_dev, int64_t n, const int64_t *row_offsets_dev, int64_t C,
+                      const int32_t *faces_dev, int32_t K, const int64_t *lq_dev, const int32_t *time_start_dev,
+                      const int64_t *offsets_dev, int64_t n_slots, int64_t L, int32_t *edges_dev,
+                      int64_t *perimeter_q_dev, int32_t *cells_edge_dev, int32_t *n_bad_dev, void *stream);
+
 /* ---- mhw_track_intensity(): the daily intensity and category series of the objects, ragged ----------- *
  * The one object stage that visits voxels: it joins the series, the climatology and the object partition.  The
  * ragged layout is that of xmhw_object_tracks: selected object i lives from time_start_dev[i] and owns the entries

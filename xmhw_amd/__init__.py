@@ -21,6 +21,7 @@ from .tracks import mhw_tracks, TrackDataset
 from .track_intensity import mhw_track_intensity, TrackIntensityDataset
 from .track_parts import mhw_track_parts, TrackPartsDataset
 from .track_genealogy import mhw_track_genealogy, TrackGenealogyDataset
+from .track_shape import mhw_track_shape, TrackShapeDataset, compactness
 from .ingest import open_series, threshold_file
 from .detrend import detrend, DetrendSpec, FitDataset
 
@@ -28,6 +29,7 @@ __all__ = ["threshold", "threshold_array", "GridSeries", "ClimDataset", "XmhwExc
            "add_doy", "get_calendar", "land_check", "detect", "threshold_detect", "EventDataset", "InterDataset",
            "climatology_series", "release_device_cache", "block_average", "BlockDataset", "mhw_rank", "mean_trend", "TrendDataset", "mhw_coverage",
            "CoverageDataset", "mhw_objects", "ObjectDataset", "mhw_tracks", "TrackDataset", "mhw_track_intensity",
-           "TrackIntensityDataset", "mhw_track_parts", "TrackPartsDataset", "mhw_track_genealogy", "TrackGenealogyDataset", "open_series",
+           "TrackIntensityDataset", "mhw_track_parts", "TrackPartsDataset", "mhw_track_genealogy", "TrackGenealogyDataset",
+           "mhw_track_shape", "TrackShapeDataset", "compactness", "open_series",
            "threshold_file", "detrend", "DetrendSpec", "FitDataset"]
 __version__ = "0.1.0"

@@ -2014,6 +2014,31 @@ int xmhw_object_genealogy(const int32_t* start, const int32_t* end, const int32_
     return XMHW_OK;
 }
 
+static_assert(xmhw::kShapeClasses == XMHW_SHAPE_CLASSES && xmhw::kShapeOpen == XMHW_SHAPE_OPEN &&
+                  xmhw::kShapeCoast == XMHW_SHAPE_COAST && xmhw::kShapeBorder == XMHW_SHAPE_BORDER &&
+                  xmhw::kShapeFaceCoast == XMHW_SHAPE_FACE_COAST && xmhw::kShapeFaceBorder == XMHW_SHAPE_FACE_BORDER &&
+                  xmhw::kShapeFaceFolded == XMHW_SHAPE_FACE_FOLDED,
+              "the shape constants of include/xmhw_amd.h and kernels.h differ");
+
+int xmhw_object_shape(const int32_t* start, const int32_t* end, const int32_t* slot, const int32_t* cell_of_row, int64_t n,
+                      const int64_t* row_offsets, int64_t C, const int32_t* faces, int32_t K, const int64_t* lq,
+                      const int32_t* time_start, const int64_t* offsets, int64_t n_slots, int64_t L, int32_t* edges,
+                      int64_t* perimeter_q, int32_t* cells_edge, int32_t* n_bad, void* stream) {
+    if (n < 0 || C < 0 || n_slots < 0 || L < 0) return fail(XMHW_ERR_INVALID, "bad n/C/n_slots/L");
+    if (K != 4) return fail(XMHW_ERR_UNSUPPORTED, "object_shape: a cell has K = 4 faces");
+    if (n > 0x7FFFFFFFll || C > 0x7FFFFFFFll || n_slots > 0x7FFFFFFFll || L > 0x7FFFFFFFll)
+        return fail(XMHW_ERR_UNSUPPORTED, "object_shape: 2^31 rows, cells, slots or series entries and more");
+    if (!n_bad || (L > 0 && (!edges || !perimeter_q || !cells_edge))) return fail(XMHW_ERR_INVALID, "NULL output buffer");
+    if (n > 0 && n_slots > 0 && L > 0 &&
+        (!start || !end || !slot || !cell_of_row || !row_offsets || !faces || !lq || !time_start || !offsets))
+        return fail(XMHW_ERR_INVALID, "NULL buffer");
+    const hipError_t e = xmhw::launch_object_shape(start, end, slot, cell_of_row, n, row_offsets, C, faces, lq, time_start, offsets,
+                                                   n_slots, L, edges, perimeter_q, cells_edge, n_bad,
+                                                   static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "object_shape launch");
+    return XMHW_OK;
+}
+
 int xmhw_set_track_intensity_combine(int32_t on) {
     if (on != 0 && on != 1) return fail(XMHW_ERR_INVALID, "on must be 0 or 1");
     g_track_intensity_combine = on;

@@ -334,6 +334,22 @@ hipError_t launch_object_genealogy(const int32_t* start, const int32_t* end, con
                                    int32_t* counts, uint64_t* edges, int64_t edge_capacity, int64_t* n_edges,
                                    int32_t* n_bad, int32_t* overflow, void* scratch, hipStream_t stream);
 
+// mhw_track_shape() (kernels_shape.hip): the outline of every selected object on each of its days, in the ragged layout
+// and on the rows of launch_object_parts (no voxels, no scratch).  faces[C][4] names what lies across the four faces of
+// every cell (dim 0 minus, dim 0 plus, dim 1 minus, dim 1 plus): a compact cell, or one of the kShapeFace* codes;
+// lq[C][4] int64 >= 0 are their lengths.  A face to a cell that holds a fit row of the same slot on the same day is
+// shared and counts nothing; any other is open.  Zeroes and fills edges[3][L] (int32) and perimeter_q[3][L] (int64),
+// one array of L per class in the order of the kShape* indices, and cells_edge[L] (int32, the footprint cells with at
+// least one counted face).  *n_bad counts the selected rows left out because their days or cell do not fit, and the
+// rows with a face value outside [kShapeFaceFolded, C) (0 for consistent inputs).
+constexpr int kShapeClasses = 3;
+constexpr int kShapeOpen = 0, kShapeCoast = 1, kShapeBorder = 2;
+constexpr int kShapeFaceCoast = -1, kShapeFaceBorder = -2, kShapeFaceFolded = -3;
+hipError_t launch_object_shape(const int32_t* start, const int32_t* end, const int32_t* slot, const int32_t* cell_of_row,
+                               int64_t n, const int64_t* row_offsets, int64_t C, const int32_t* faces, const int64_t* lq,
+                               const int32_t* time_start, const int64_t* offsets, int64_t n_slots, int64_t L, int32_t* edges,
+                               int64_t* perimeter_q, int32_t* cells_edge, int32_t* n_bad, hipStream_t stream);
+
 // mhw_track_intensity() (kernels_track_intensity.hip): the per-voxel pass over one slab of n compacted cells.  The slab's
 // table rows (start / end / slot, n_rows of them, the rows of cell c = row_offsets[c]..row_offsets[c + 1], in time
 // order) are walked together with the steps of a chunk of kTrackIntensityChunk steps; a voxel of a row whose slot is in

@@ -623,6 +623,25 @@ PYBIND11_MODULE(_xmhw_hip, m) {
        py::arg("C"), py::arg("nbr"), py::arg("K"), py::arg("vox_off"), py::arg("V"), py::arg("time_start"),
        py::arg("offsets"), py::arg("n_slots"), py::arg("L"), py::arg("counts"), py::arg("edges"), py::arg("edge_capacity"),
        py::arg("n_edges"), py::arg("n_bad"), py::arg("overflow"), py::arg("stream") = 0);
+    m.def("object_shape", [](uintptr_t start, uintptr_t end, uintptr_t slot, uintptr_t cell_of_row, int64_t n,
+                             uintptr_t row_offsets, int64_t C, uintptr_t faces, int32_t K, uintptr_t lq, uintptr_t time_start,
+                             uintptr_t offsets, int64_t n_slots, int64_t L, uintptr_t edges, uintptr_t perimeter_q,
+                             uintptr_t cells_edge, uintptr_t n_bad, uintptr_t stream) {
+        check(xmhw_object_shape(static_cast<const int32_t*>(vp(start)), static_cast<const int32_t*>(vp(end)),
+                                static_cast<const int32_t*>(vp(slot)), static_cast<const int32_t*>(vp(cell_of_row)), n,
+                                static_cast<const int64_t*>(vp(row_offsets)), C, static_cast<const int32_t*>(vp(faces)), K,
+                                static_cast<const int64_t*>(vp(lq)), static_cast<const int32_t*>(vp(time_start)),
+                                static_cast<const int64_t*>(vp(offsets)), n_slots, L, static_cast<int32_t*>(vp(edges)),
+                                static_cast<int64_t*>(vp(perimeter_q)), static_cast<int32_t*>(vp(cells_edge)),
+                                static_cast<int32_t*>(vp(n_bad)), vp(stream)));
+    }, py::arg("start"), py::arg("end"), py::arg("slot"), py::arg("cell_of_row"), py::arg("n"), py::arg("row_offsets"),
+       py::arg("C"), py::arg("faces"), py::arg("K"), py::arg("lq"), py::arg("time_start"), py::arg("offsets"),
+       py::arg("n_slots"), py::arg("L"), py::arg("edges"), py::arg("perimeter_q"), py::arg("cells_edge"), py::arg("n_bad"),
+       py::arg("stream") = 0);
+    m.attr("SHAPE_CLASSES") = XMHW_SHAPE_CLASSES;
+    m.attr("SHAPE_FACE_COAST") = XMHW_SHAPE_FACE_COAST;
+    m.attr("SHAPE_FACE_BORDER") = XMHW_SHAPE_FACE_BORDER;
+    m.attr("SHAPE_FACE_FOLDED") = XMHW_SHAPE_FACE_FOLDED;
     m.attr("GENEALOGY_VOXEL_BYTES") = XMHW_GENEALOGY_VOXEL_BYTES;
     m.attr("GENEALOGY_SLOT_BYTES") = XMHW_GENEALOGY_SLOT_BYTES;
     m.attr("GENEALOGY_FIELDS") = XMHW_GENEALOGY_FIELDS;
