@@ -599,6 +599,37 @@ int xmhw_coverage_accumulate_f64(const double *ts_dev, int64_t T, int64_t C, int
                                  const int64_t *wq_dev, const int32_t *region_dev, int32_t R,
                                  int64_t *cells_dev, int64_t *area_q_dev, void *stream);
 
+/* ---- region_series(): the area-weighted mean series of every region (box, basin, EEZ, index area) ---- *
+ * The reduction ACROSS cells that sums values.  For every step t of the dense series ts_dev (T, C), leading
+ * dimension ld, and every region r < R, ADDS into the contiguous accumulator acc_dev[T][R][3] (int64), over
+ * the cells c with region_dev[c] == r whose sample at t is not NaN:
+ *   acc[t][r][0] (n_valid) += 1
+ *   acc[t][r][1] (wsum_i)  += wi_dev[c]
+ *   acc[t][r][2] (xsum_q)  += wi_dev[c] * xq,  xq = rint(((double)ts[t][c] - x0) * 2^XMHW_REGION_SERIES_BITS)
+ * xq is computed in float64 exactly as written (the product by 2^16 is exact, rint rounds half to even), so
+ * numpy.rint((ts.astype(float64) - x0) * 65536.0) is the same integer for every sample.  xsum_q is signed, held
+ * in two's complement in the 64-bit adds.  A valid sample with |ts - x0| >= 2^7, or infinite, is left out of
+ * all three sums and counted in *n_range_dev (int64, ADDED to as well; 0 for data in range: pass x0 = 273.15
+ * for a series in kelvin).  region_dev[C] int32 in [-1, R): -1 = the cell counts nowhere (its samples are not
+ * read).  wi_dev[C] int64, 0 <= wi <= 2^ib with ib <= 61 - 16 - 7 - bit_length(cells of the whole grid) (not
+ * checked: it lives on the device): |xsum_q| <= C * 2^(ib + 23) < 2^61 whatever the data.
+ * The caller zeroes acc_dev and *n_range_dev before the first slab of cells: calls for consecutive slabs
+ * accumulate, on the same stream, without a read-back in between.  All sums are integer sums: the result is
+ * exact and does not depend on the order of the adds, the slabs or the launch geometry.
+ * R >= 1; R above XMHW_REGION_MAX_REGIONS: XMHW_ERR_UNSUPPORTED, before anything is touched.  Asynchronous on
+ * `stream`; nothing is launched for C == 0 or T == 0.  xmhw_set_region_wave_sum (process-wide; tests and
+ * measurements): how a wave sums its 64-bit terms, 1 = the sums of 8 steps together (the default), 0 = one
+ * wave sum per step.  Same results.                                                                   */
+#define XMHW_REGION_MAX_REGIONS 1024
+#define XMHW_REGION_SERIES_BITS 16
+int xmhw_set_region_wave_sum(int32_t variant);
+int xmhw_region_accumulate_f32(const float *ts_dev, int64_t T, int64_t C, int64_t ld, double x0,
+                               const int64_t *wi_dev, const int32_t *region_dev, int32_t R,
+                               int64_t *acc_dev /* [T][R][3] */, int64_t *n_range_dev, void *stream);
+int xmhw_region_accumulate_f64(const double *ts_dev, int64_t T, int64_t C, int64_t ld, double x0,
+                               const int64_t *wi_dev, const int32_t *region_dev, int32_t R,
+                               int64_t *acc_dev /* [T][R][3] */, int64_t *n_range_dev, void *stream);
+
 /* ---- mhw_objects(): the events of detect() grouped into objects connected in space and time -------- *
  * A table row r is a run of days start_dev[r]..end_dev[r] (inclusive positions along the time axis, int32)
  * in one ocean cell; the rows of cell c are offsets_dev[c]..offsets_dev[c+1] (offsets_dev[C] == n), in time

@@ -228,6 +228,47 @@ class CoverageDataset:
             attrs=dict(self.attrs, weight_unit=self.weight_unit))
 
 
+def grid_layout(temp, tdim):
+    """(coords, coord_attrs, dims, point, sdims, sshape, N) of a GridSeries / DataArray: the spatial dims in stacked
+    (sorted-name) order, their shape and the number of grid points (1 for a single-point series)."""
+    if _is_xarray(temp):
+        coords, coord_attrs = _from_xarray(temp)
+        dims = list(temp.dims)
+    else:
+        coords, coord_attrs, dims = dict(temp.coords), None, list(temp.dims)
+    if tdim not in dims:
+        raise XmhwException(f"{tdim} dimension not present, default"
+                            + "is 'time' or pass as tdim='time_dimension_name'")
+    point = len(dims) == 1
+    sdims = sorted(d for d in dims if d != tdim)
+    shape = tuple(temp.shape) if _is_xarray(temp) else tuple(np.shape(temp.values))
+    sshape = tuple(shape[dims.index(d)] for d in sdims)
+    N = int(np.prod(sshape, dtype=np.int64)) if not point else 1
+    return coords, coord_attrs, dims, point, sdims, sshape, N
+
+
+def region_ids(regions, dims, tdim, sdims, sshape, point, N, who):
+    """The ``regions`` argument on the whole grid, in stacked order: (found, rid, Rc) with ``found`` the sorted
+    non-negative labels, ``rid`` (N,) int32 the position of every cell's label in it (-1: negative label, the cell
+    counts nowhere) and Rc = max(len(found), 1).  ``who`` names the caller in the message of the cap."""
+    if regions is None:
+        labels = np.zeros(N, dtype=np.int64)
+    else:
+        regions = np.asarray(regions)
+        if regions.dtype.kind not in "iu":
+            raise XmhwException(f"regions should be an integer array, got {regions.dtype}")
+        labels = regions.astype(np.int64).reshape(-1) if point else \
+            gridweights.on_grid(regions, "regions", dims, tdim, sdims, sshape).astype(np.int64)
+        if labels.shape != (N,):
+            raise XmhwException("regions should have one entry per cell")
+    found = np.unique(labels[labels >= 0])                     # candidates: the labels on the whole grid
+    rid = np.where(labels >= 0, np.searchsorted(found, labels), -1).astype(np.int32)
+    Rc = max(int(found.shape[0]), 1)
+    if Rc > MAX_REGIONS:
+        raise XmhwException(f"{who} handles at most {MAX_REGIONS} regions, got {Rc}")
+    return found, rid, Rc
+
+
 def mhw_coverage(temp, th, se, weights=None, regions=None, tdim="time", minDuration=5, joinGaps=True, maxGap=2,
                  maxPadLength=None, coldSpells=False, tstep=False, anynans=False, _compute=None, max_batch_bytes=None):
     """Daily count and weighted area of the cells in each MHW category, by region.
@@ -246,36 +287,10 @@ def mhw_coverage(temp, th, se, weights=None, regions=None, tdim="time", minDurat
     area_q / total_q`` within ``quantisation_bound()`` of the unquantised ratio.  ``_compute``: a stand-in for
     coverage_cells() (host tests)."""
     from .detect import _detect
-    if _is_xarray(temp):
-        coords, coord_attrs = _from_xarray(temp)
-        dims = list(temp.dims)
-    else:
-        coords, dims = dict(temp.coords), list(temp.dims)
-    if tdim not in dims:
-        raise XmhwException(f"{tdim} dimension not present, default"
-                            + "is 'time' or pass as tdim='time_dimension_name'")
-    point = len(dims) == 1
-    sdims = sorted(d for d in dims if d != tdim)
-    shape = tuple(temp.shape) if _is_xarray(temp) else tuple(np.shape(temp.values))
-    sshape = tuple(shape[dims.index(d)] for d in sdims)
-    N = int(np.prod(sshape, dtype=np.int64)) if not point else 1
+    coords, coord_attrs, dims, point, sdims, sshape, N = grid_layout(temp, tdim)
     # weights and region labels on the whole grid, in stacked order
     wq, unit = quantise_weights(resolve_weights(weights, coords, dims, tdim, sdims, sshape, point))
-    if regions is None:
-        labels = np.zeros(N, dtype=np.int64)
-    else:
-        regions = np.asarray(regions)
-        if regions.dtype.kind not in "iu":
-            raise XmhwException(f"regions should be an integer array, got {regions.dtype}")
-        labels = regions.astype(np.int64).reshape(-1) if point else \
-            gridweights.on_grid(regions, "regions", dims, tdim, sdims, sshape).astype(np.int64)
-        if labels.shape != (N,):
-            raise XmhwException("regions should have one entry per cell")
-    found = np.unique(labels[labels >= 0])                     # candidates: the labels on the whole grid
-    rid = np.where(labels >= 0, np.searchsorted(found, labels), -1).astype(np.int32)
-    Rc = max(int(found.shape[0]), 1)
-    if Rc > MAX_REGIONS:
-        raise XmhwException(f"mhw_coverage handles at most {MAX_REGIONS} regions, got {Rc}")
+    found, rid, Rc = region_ids(regions, dims, tdim, sdims, sshape, point, N, "mhw_coverage")
     got = {}
 
     def on_cells(ts, sec, thc, doy, doys, minDuration, joinGaps, maxGap, coldSpells, intermediate, pad=None):

@@ -910,6 +910,25 @@ int coverage_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const do
     return XMHW_OK;
 }
 
+static std::atomic<int> g_region_wave_sum{1};   // region_accumulate sums 8 steps of a wave together (xmhw_set_region_wave_sum)
+
+template <typename T>
+int region_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, double x0, const int64_t* wi, const int32_t* region,
+                      int32_t R, int64_t* acc, int64_t* n_range, void* stream) {
+    if (Tn < 0 || C < 0 || ld < C) return fail(XMHW_ERR_INVALID, "bad T/C/ld");
+    if (Tn >= (int64_t{1} << 31)) return fail(XMHW_ERR_INVALID, "T too large");
+    if (R < 1) return fail(XMHW_ERR_INVALID, "R must be >= 1");
+    if (R > xmhw::kRegionMaxRegions)
+        return fail(XMHW_ERR_UNSUPPORTED, "region_accumulate: R above the cap of " + std::to_string(xmhw::kRegionMaxRegions) + " regions");
+    if (!(x0 == x0) || std::isinf(x0)) return fail(XMHW_ERR_INVALID, "x0 must be finite");
+    if (C == 0 || Tn == 0) return XMHW_OK;
+    if (!ts || !wi || !region || !acc || !n_range) return fail(XMHW_ERR_INVALID, "NULL buffer");
+    hipError_t e = xmhw::launch_region_accumulate<T>(ts, Tn, C, ld, x0, wi, region, R, acc, n_range, g_region_wave_sum.load(),
+                                                     static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "region_accumulate launch");
+    return XMHW_OK;
+}
+
 static std::atomic<int> g_track_intensity_combine{1};   // runs of equal entries summed in the wave (xmhw_set_track_intensity_combine)
 
 template <typename T>
@@ -1902,6 +1921,20 @@ int xmhw_coverage_accumulate_f64(const double* ts, int64_t T, int64_t C, int64_t
                                  int64_t* area_q, void* stream) {
     return coverage_accumulate<double>(ts, T, C, ld, seas, thresh, ldc, row_of_t, negate, bits, ldb, min_duration,
                                        join_gaps, max_gap, wq, region, R, cells, area_q, stream);
+}
+
+int xmhw_set_region_wave_sum(int32_t variant) {
+    if (variant != 0 && variant != 1) return fail(XMHW_ERR_INVALID, "variant must be 0 or 1");
+    g_region_wave_sum = variant;
+    return XMHW_OK;
+}
+int xmhw_region_accumulate_f32(const float* ts, int64_t T, int64_t C, int64_t ld, double x0, const int64_t* wi,
+                               const int32_t* region, int32_t R, int64_t* acc, int64_t* n_range, void* stream) {
+    return region_accumulate<float>(ts, T, C, ld, x0, wi, region, R, acc, n_range, stream);
+}
+int xmhw_region_accumulate_f64(const double* ts, int64_t T, int64_t C, int64_t ld, double x0, const int64_t* wi,
+                               const int32_t* region, int32_t R, int64_t* acc, int64_t* n_range, void* stream) {
+    return region_accumulate<double>(ts, T, C, ld, x0, wi, region, R, acc, n_range, stream);
 }
 
 int xmhw_event_objects(const int32_t* start, const int32_t* end, int64_t n, const int64_t* offsets, int64_t C,

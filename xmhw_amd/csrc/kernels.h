@@ -264,6 +264,17 @@ hipError_t launch_coverage_accumulate(const T* ts, int64_t Tn, int64_t C, int64_
                                       const uint64_t* inev, int64_t ldi, const int64_t* wq, const int32_t* region,
                                       int32_t R, int64_t* cells, int64_t* area_q, hipStream_t stream);
 
+// region_series() (kernels_region.hip): region_accumulate ADDS, for every step t and region r < R, over the cells c with
+// region[c] == r whose sample is not NaN: acc[t][r][0] += 1, acc[t][r][1] += wi[c], acc[t][r][2] += wi[c] *
+// rint(((double)ts[t][c] - x0) * 2^16); a valid sample with |ts - x0| >= 2^7 or infinite is left out and counted in
+// *n_range.  region[c] in [-1, R), -1 = the cell counts nowhere; R <= kRegionMaxRegions.  blocked selects how a wave sums:
+// 0 = one wave sum per step, 1 = the sums of 8 steps together (kernels_region.hip).  Same results.
+constexpr int kRegionMaxRegions = 1024;
+template <typename T>
+hipError_t launch_region_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, double x0, const int64_t* wi,
+                                    const int32_t* region, int32_t R, int64_t* acc, int64_t* n_range, int32_t blocked,
+                                    hipStream_t stream);
+
 // mhw_objects() (kernels_objects.hip): launch_event_objects groups the table rows (runs of days start..end in one cell,
 // rows of cell c = offsets[c]..offsets[c + 1], in time order) into connected components: rows of DIFFERENT cells are
 // linked iff one cell is among the other's K neighbours nbr[c][K] (-1: none) and start_a <= end_b + gap and start_b <=

@@ -558,6 +558,25 @@ PYBIND11_MODULE(_xmhw_hip, m) {
        py::arg("ldc"), py::arg("row_of_t"), py::arg("negate"), py::arg("bits"), py::arg("ldb"), py::arg("min_duration"),
        py::arg("join_gaps"), py::arg("max_gap"), py::arg("wq"), py::arg("region"), py::arg("R"), py::arg("cells"),
        py::arg("area_q"), py::arg("stream") = 0);
+    m.attr("REGION_MAX_REGIONS") = XMHW_REGION_MAX_REGIONS;
+    m.attr("REGION_SERIES_BITS") = XMHW_REGION_SERIES_BITS;
+    m.def("set_region_wave_sum", [](int variant) { check(xmhw_set_region_wave_sum(variant)); }, py::arg("variant"));
+    m.def("region_accumulate", [](uintptr_t ts, int itemsize, int64_t T, int64_t C, int64_t ld, double x0, uintptr_t wi,
+                                  uintptr_t region, int32_t R, uintptr_t acc, uintptr_t n_range, uintptr_t stream) {
+        py::gil_scoped_release r;
+        int rc = -1;
+        if (itemsize == 4)
+            rc = xmhw_region_accumulate_f32(static_cast<const float*>(vp(ts)), T, C, ld, x0, static_cast<const int64_t*>(vp(wi)),
+                                            static_cast<const int32_t*>(vp(region)), R, static_cast<int64_t*>(vp(acc)),
+                                            static_cast<int64_t*>(vp(n_range)), vp(stream));
+        else if (itemsize == 8)
+            rc = xmhw_region_accumulate_f64(static_cast<const double*>(vp(ts)), T, C, ld, x0, static_cast<const int64_t*>(vp(wi)),
+                                            static_cast<const int32_t*>(vp(region)), R, static_cast<int64_t*>(vp(acc)),
+                                            static_cast<int64_t*>(vp(n_range)), vp(stream));
+        if (rc == -1) throw InvalidError("itemsize must be 4 or 8");
+        check(rc);
+    }, py::arg("ts"), py::arg("itemsize"), py::arg("T"), py::arg("C"), py::arg("ld"), py::arg("x0"), py::arg("wi"),
+       py::arg("region"), py::arg("R"), py::arg("acc"), py::arg("n_range"), py::arg("stream") = 0);
     m.def("event_objects", [](uintptr_t start, uintptr_t end, int64_t n, uintptr_t offsets, int64_t C, uintptr_t nbr, int32_t K,
                               int32_t gap, uintptr_t cell_of_row, uintptr_t root, uintptr_t stream) {
         check(xmhw_event_objects(static_cast<const int32_t*>(vp(start)), static_cast<const int32_t*>(vp(end)), n,
