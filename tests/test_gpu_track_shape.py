@@ -8,10 +8,12 @@ import numpy as np
 import numpy.testing as npt
 import pytest
 
+import object_chain_raw as ocr
 import objects_cases as oc
 import track_parts_cases as pc
 import track_shape_cases as sc
 import track_shape_oracle as so
+from object_chain_raw import raw_shape as raw_stage
 
 pytestmark = pytest.mark.gpu
 
@@ -176,37 +178,8 @@ def test_land_grid_the_largest_object_alone(gpu, land):
     run(gpu, ds, obj, ids=[big], lengths=ln, tracks=False)
 
 
-def raw_stage(args):
-    """xmhw_object_shape on the arguments of track_shape_device(), nothing checked: (dict of the seven arrays, n_bad)"""
-    from xmhw_amd._lib import hip
-    from xmhw_amd.device import DeviceScope
-    dtypes = (np.int32, np.int32, np.int32, np.int32, np.int64, np.int32, np.int64, np.int32, np.int64)
-    args = [np.ascontiguousarray(a, dtype=t) for a, t in zip(args, dtypes)]
-    n, C, m, L = args[0].shape[0], args[5].shape[0], args[7].shape[0], int(args[8][-1])
-    h = hip()
-    with DeviceScope() as s:
-        d = [s.upload(a) for a in args]
-        d_edges, d_perim, d_cells, d_bad = s.alloc(12 * L), s.alloc(24 * L), s.alloc(4 * L), s.alloc(4)
-        h.object_shape(d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, n, d[4].ptr, C, d[5].ptr, 4, d[6].ptr, d[7].ptr, d[8].ptr, m, L,
-                       d_edges.ptr, d_perim.ptr, d_cells.ptr, d_bad.ptr)
-        h.stream_sync(0)
-        edges, perim = d_edges.to_array((3, L), np.int32), d_perim.to_array((3, L), np.int64)
-        out = {f"edges_{c}": edges[k] for k, c in enumerate(("open", "coast", "border"))}
-        out.update({f"perimeter_{c}_q": perim[k] for k, c in enumerate(("open", "coast", "border"))})
-        out["cells_edge"] = d_cells.to_array((L,), np.int32)
-        return out, int(d_bad.to_array((1,), np.int32)[0])
-
-
 def captured_arguments(ds, obj, **kw):
-    import xmhw_amd
-    seen = {}
-
-    def stage(*args):
-        seen["args"] = args
-        return so.stage_for(ds, obj)(*args)
-
-    xmhw_amd.mhw_track_shape(ds, obj, _compute=stage, **kw)
-    return [np.array(a) for a in seen["args"]]
+    return ocr.captured_arguments("shape", ds, obj, **kw)
 
 
 @pytest.mark.parametrize("which", ["both", "one"])

@@ -13,8 +13,8 @@
 //
 //   genealogy_init     lane = voxel / entry / table slot: parent[v] = v, the degrees and the six counts = 0, the table
 //                      emptied.
-//   genealogy_link     the union-find of kernels_parts.hip (parts_rows.h): lane = row, voxels of one day united.
-//   genealogy_flatten  lane = voxel: parent[v] = find(v).
+//   parts_link         the union-find of kernels_parts.hip, launched there by launch_parts_union() (object_rows.h): lane
+//   parts_flatten      = row, voxels of one day united; lane = voxel: parent[v] = find(v).
 //   genealogy_pairs    lane = row.  For every day t of the row but its last the key (root(vox(r, t)), root(vox(r, t + 1)));
 //                      where the next row holds the same cell and slot, is fit and starts on end + 1, the key across the
 //                      two rows too.  Each key is put into the table by linear probing from a mixed hash, one 64-bit
@@ -27,22 +27,21 @@
 //   genealogy_count    lane = row, walking its days as parts_count does: a voxel that is its own root adds to the six
 //                      counters of its entry from its two degrees; integer atomics without a return value.
 //
-// Rows that are not fit (parts_rows.h) are left out of every kernel and counted in *n_bad by genealogy_count.  Nothing
-// outside entries 0..L-1, voxels 0..V-1, table slots 0..cap-1 and edges 0..edge_capacity-1 is ever written.  Every count
+// Rows that are not fit (object_rows.h, fit_row<true>) are left out of every kernel and counted in *n_bad by
+// genealogy_count.  Nothing outside entries 0..L-1, voxels 0..V-1, table slots 0..cap-1 and edges 0..edge_capacity-1 is ever written.  Every count
 // is an integer sum and the set of edges is a set: exact, and the same under any schedule once the edges are sorted.
 #include "device_common.h"
 #include "kernels.h"
-#include "parts_rows.h"
+#include "object_rows.h"
 
 namespace xmhw {
 
 namespace {
 
-constexpr int kGenThreads = 256;
 using u64 = unsigned long long;
 constexpr u64 kEmpty = ~0ull;
 
-__global__ __launch_bounds__(kGenThreads) void genealogy_init(int64_t V, int32_t* __restrict__ parent,
+__global__ __launch_bounds__(kRowThreads) void genealogy_init(int64_t V, int32_t* __restrict__ parent,
                                                               int32_t* __restrict__ indeg, int32_t* __restrict__ outdeg,
                                                               int64_t L, int32_t* __restrict__ counts, int64_t cap,
                                                               u64* __restrict__ table) {
@@ -55,20 +54,6 @@ __global__ __launch_bounds__(kGenThreads) void genealogy_init(int64_t V, int32_t
     if (i < L)
         for (int f = 0; f < kGenealogyFields; ++f) counts[f * L + i] = 0;
     if (i < cap) table[i] = kEmpty;
-}
-
-__global__ __launch_bounds__(kGenThreads) void genealogy_link(PartRows a, const int64_t* __restrict__ row_offsets,
-                                                              const int32_t* __restrict__ nbr, int32_t K,
-                                                              int32_t* __restrict__ parent) {
-    const int64_t r = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (r >= a.n) return;
-    parts_link_row(a, r, row_offsets, nbr, K, parent);
-}
-
-__global__ __launch_bounds__(kGenThreads) void genealogy_flatten(int64_t V, int32_t* __restrict__ parent) {
-    const int64_t v = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (v >= V) return;
-    parts_flatten_voxel(v, parent);
 }
 
 // both roots are voxels of fit rows: within [0, V), below 2^31
@@ -91,14 +76,14 @@ __device__ __forceinline__ void put_pair(int32_t ra, int32_t rb, u64* __restrict
     atomicOr(overflow, 1);                           // a full table: the caller announced too few keys
 }
 
-__global__ __launch_bounds__(kGenThreads) void genealogy_pairs(PartRows a, const int32_t* __restrict__ parent,
+__global__ __launch_bounds__(kRowThreads) void genealogy_pairs(ObjectRows a, const int32_t* __restrict__ parent,
                                                                u64* __restrict__ table, int64_t cap,
                                                                int32_t* __restrict__ indeg, int32_t* __restrict__ outdeg,
                                                                int32_t* __restrict__ overflow) {
     const int64_t r = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (r >= a.n) return;
-    PartRow me;
-    if (part_row(a, r, me) != 1) return;
+    ObjectRow me;
+    if (fit_row<true>(a, r, me) != 1) return;
     const int64_t days = static_cast<int64_t>(me.e) - me.s + 1;
     int32_t ra = parent[me.vox];                     // a root is a voxel of a fit row of the same day: within [0, V)
     for (int64_t d = 1; d < days; ++d) {
@@ -107,12 +92,12 @@ __global__ __launch_bounds__(kGenThreads) void genealogy_pairs(PartRows a, const
         ra = rb;
     }
     if (r + 1 >= a.n || a.cell[r + 1] != me.c || a.slot[r + 1] != me.sl) return;
-    PartRow next;                                    // the same cell goes on in the next row without a free day
-    if (part_row(a, r + 1, next) != 1 || static_cast<int64_t>(next.s) != static_cast<int64_t>(me.e) + 1) return;
+    ObjectRow next;                                    // the same cell goes on in the next row without a free day
+    if (fit_row<true>(a, r + 1, next) != 1 || static_cast<int64_t>(next.s) != static_cast<int64_t>(me.e) + 1) return;
     put_pair(ra, parent[next.vox], table, cap, indeg, outdeg, overflow);
 }
 
-__global__ __launch_bounds__(kGenThreads) void genealogy_collect(const u64* __restrict__ table, int64_t cap,
+__global__ __launch_bounds__(kRowThreads) void genealogy_collect(const u64* __restrict__ table, int64_t cap,
                                                                  u64* __restrict__ edges, int64_t edge_capacity,
                                                                  u64* __restrict__ n_edges) {
     const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -130,14 +115,14 @@ __global__ __launch_bounds__(kGenThreads) void genealogy_collect(const u64* __re
     if (place < static_cast<u64>(edge_capacity)) edges[place] = key;
 }
 
-__global__ __launch_bounds__(kGenThreads) void genealogy_count(PartRows a, const int32_t* __restrict__ parent,
+__global__ __launch_bounds__(kRowThreads) void genealogy_count(ObjectRows a, const int32_t* __restrict__ parent,
                                                                const int32_t* __restrict__ indeg,
                                                                const int32_t* __restrict__ outdeg,
                                                                int32_t* __restrict__ counts, int32_t* __restrict__ n_bad) {
     const int64_t r = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (r >= a.n) return;
-    PartRow me;
-    const int fit = part_row(a, r, me);
+    ObjectRow me;
+    const int fit = fit_row<true>(a, r, me);
     if (fit < 0) atomicAdd(n_bad, 1);
     if (fit != 1) return;
     const int64_t days = static_cast<int64_t>(me.e) - me.s + 1;
@@ -154,8 +139,6 @@ __global__ __launch_bounds__(kGenThreads) void genealogy_count(PartRows a, const
         if (out >= 2) atomicAdd(at + kGenealogySplit * a.L, 1);
     }
 }
-
-inline unsigned blocks_for(int64_t items) { return static_cast<unsigned>((items + kGenThreads - 1) / kGenThreads); }
 
 }  // namespace
 
@@ -188,14 +171,13 @@ hipError_t launch_object_genealogy(const int32_t* start, const int32_t* end, con
     int32_t* outdeg = indeg + (V > 0 ? V : 0);
     int64_t items = V > L ? V : L;
     items = cap > items ? cap : items;
-    const dim3 b(kGenThreads);
+    const dim3 b(kRowThreads);
     hipLaunchKernelGGL(genealogy_init, dim3(blocks_for(items)), b, 0, stream, V, parent, indeg, outdeg, L, counts, cap, table);
     if (n > 0 && n_slots > 0 && L > 0) {
-        const PartRows rows{start, end, slot, cell_of_row, vox_off, time_start, offsets, n, C, n_slots, L, V};
+        const ObjectRows rows{start, end, slot, cell_of_row, time_start, offsets, n, C, n_slots, L, vox_off, V};
         const dim3 g(blocks_for(n));
         if (V > 0) {
-            hipLaunchKernelGGL(genealogy_link, g, b, 0, stream, rows, row_offsets, nbr, K, parent);
-            hipLaunchKernelGGL(genealogy_flatten, dim3(blocks_for(V)), b, 0, stream, V, parent);
+            launch_parts_union(rows, row_offsets, nbr, K, parent, V, stream);
             hipLaunchKernelGGL(genealogy_pairs, g, b, 0, stream, rows, static_cast<const int32_t*>(parent), table, cap, indeg,
                                outdeg, overflow);
             hipLaunchKernelGGL(genealogy_collect, dim3(blocks_for(cap)), b, 0, stream, static_cast<const u64*>(table), cap,

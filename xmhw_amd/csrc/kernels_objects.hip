@@ -26,13 +26,14 @@
 //   objects_finish   key -> float64 (NaN where no row had a value).
 #include "device_common.h"
 #include "kernels.h"
+#include "object_rows.h"                           // kRowThreads, blocks_for
 #include "union_find.h"                             // parent_load, find_root, unite
 
 namespace xmhw {
 
 namespace {
 
-constexpr int kObjThreads = 256;
+constexpr int kObjThreads = kRowThreads;
 constexpr int kObjChunks = 8;                       // chunks of 64 rows per wave in objects_reduce
 
 __global__ __launch_bounds__(kObjThreads) void objects_init(const int64_t* __restrict__ offsets, int64_t C, int64_t n,
@@ -208,8 +209,6 @@ __global__ __launch_bounds__(kObjThreads) void objects_finish(int64_t n_slots, u
     const double v = k ? key_f64(k) : make_nan();
     key[i] = static_cast<unsigned long long>(__double_as_longlong(v));
 }
-
-inline unsigned blocks_for(int64_t items) { return static_cast<unsigned>((items + kObjThreads - 1) / kObjThreads); }
 
 }  // namespace
 

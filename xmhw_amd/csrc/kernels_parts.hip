@@ -20,24 +20,23 @@
 //   parts_count    the same walk: a voxel that is its own root adds 1 to n_parts[e] and raises cells_largest[e] and
 //                  area_largest_q[e] (an unsigned 64-bit maximum: areas are >= 0) by atomic maxima.
 //
-// PartRows, part_row() and the bodies of parts_link and parts_flatten live in parts_rows.h, shared with
-// kernels_genealogy.hip.  A row is *fit* iff its slot is in [0, n_slots), its cell in [0, C), start <= end, its days lie within its object's
-// entries (which lie within 0..L-1) and its voxel numbers vox_off[r] .. vox_off[r + 1] - 1 are exactly its days within
-// [0, V).  A selected row that is not fit is left out of every kernel and counted in *n_bad by parts_count; nothing
-// outside entries 0..L-1 and voxels 0..V-1 is ever written.  Everything is an integer sum or maximum: exact, and the
-// same under any schedule.
+// The rows, the fit rule (fit_row<true>: with voxels) and the search of a neighbour cell's rows live in object_rows.h,
+// shared with the other stages of the object chain.  parts_link and parts_flatten are also the union-find of
+// kernels_genealogy.hip, which reaches them through launch_parts_union().  A selected row that is not fit is left out of
+// every kernel and counted in *n_bad by parts_count; nothing outside entries 0..L-1 and voxels 0..V-1 is ever written.
+// Everything is an integer sum or maximum: exact, and the same under any schedule.
 #include "device_common.h"
 #include "kernels.h"
-#include "parts_rows.h"
+#include "object_rows.h"
+#include "union_find.h"
 
 namespace xmhw {
 
 namespace {
 
-constexpr int kPartThreads = 256;
 using u64 = unsigned long long;
 
-__global__ __launch_bounds__(kPartThreads) void parts_init(int64_t V, int32_t* __restrict__ parent,
+__global__ __launch_bounds__(kRowThreads) void parts_init(int64_t V, int32_t* __restrict__ parent,
                                                            int32_t* __restrict__ cells, int64_t* __restrict__ area,
                                                            int64_t L, int32_t* __restrict__ n_parts,
                                                            int32_t* __restrict__ cells_largest,
@@ -55,27 +54,44 @@ __global__ __launch_bounds__(kPartThreads) void parts_init(int64_t V, int32_t* _
     }
 }
 
-__global__ __launch_bounds__(kPartThreads) void parts_link(PartRows a, const int64_t* __restrict__ row_offsets,
-                                                           const int32_t* __restrict__ nbr, int32_t K,
-                                                           int32_t* __restrict__ parent) {
+__global__ __launch_bounds__(kRowThreads) void parts_link(ObjectRows a, const int64_t* __restrict__ row_offsets,
+                                                          const int32_t* __restrict__ nbr, int32_t K,
+                                                          int32_t* __restrict__ parent) {
     const int64_t r = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (r >= a.n) return;
-    parts_link_row(a, r, row_offsets, nbr, K, parent);
+    ObjectRow me;
+    if (fit_row<true>(a, r, me) != 1) return;
+    for (int32_t k = 0; k < K; ++k) {
+        const int32_t nc = nbr[static_cast<int64_t>(me.c) * K + k];
+        if (nc < 0 || nc >= me.c) continue;          // the pair is united from the side of the larger cell
+        int64_t last = row_offsets[nc + 1];
+        const int64_t first = first_row_reaching(a.end, row_offsets[nc], last, a.n, me.s);
+        for (int64_t j = first; j < last && a.start[j] <= me.e; ++j) {
+            if (a.slot[j] != me.sl) continue;        // another object, or not selected
+            ObjectRow other;
+            if (fit_row<true>(a, j, other) != 1) continue;
+            const int32_t d0 = other.s > me.s ? other.s : me.s, d1 = other.e < me.e ? other.e : me.e;
+            for (int32_t t = d0; t <= d1; ++t)       // fit rows: both voxels are within [0, V)
+                unite(parent, static_cast<int32_t>(me.vox + (t - me.s)), static_cast<int32_t>(other.vox + (t - other.s)));
+        }
+    }
 }
 
-__global__ __launch_bounds__(kPartThreads) void parts_flatten(int64_t V, int32_t* __restrict__ parent) {
+__global__ __launch_bounds__(kRowThreads) void parts_flatten(int64_t V, int32_t* __restrict__ parent) {
     const int64_t v = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (v >= V) return;
-    parts_flatten_voxel(v, parent);
+    int32_t x = static_cast<int32_t>(v);
+    for (int32_t p = parent_load(parent + x); p != x; p = parent_load(parent + x)) x = p;
+    __hip_atomic_store(parent + v, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__global__ __launch_bounds__(kPartThreads) void parts_reduce(PartRows a, const int64_t* __restrict__ wq,
+__global__ __launch_bounds__(kRowThreads) void parts_reduce(ObjectRows a, const int64_t* __restrict__ wq,
                                                              const int32_t* __restrict__ parent,
                                                              int32_t* __restrict__ cells, u64* __restrict__ area) {
     const int64_t r = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (r >= a.n) return;
-    PartRow me;
-    if (part_row(a, r, me) != 1) return;
+    ObjectRow me;
+    if (fit_row<true>(a, r, me) != 1) return;
     const u64 w = static_cast<u64>(wq[me.c]);
     const int64_t days = static_cast<int64_t>(me.e) - me.s + 1;
     for (int64_t d = 0; d < days; ++d) {
@@ -85,15 +101,15 @@ __global__ __launch_bounds__(kPartThreads) void parts_reduce(PartRows a, const i
     }
 }
 
-__global__ __launch_bounds__(kPartThreads) void parts_count(PartRows a, const int32_t* __restrict__ parent,
+__global__ __launch_bounds__(kRowThreads) void parts_count(ObjectRows a, const int32_t* __restrict__ parent,
                                                             const int32_t* __restrict__ cells,
                                                             const u64* __restrict__ area, int32_t* __restrict__ n_parts,
                                                             int32_t* __restrict__ cells_largest,
                                                             u64* __restrict__ area_largest_q, int32_t* __restrict__ n_bad) {
     const int64_t r = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (r >= a.n) return;
-    PartRow me;
-    const int fit = part_row(a, r, me);
+    ObjectRow me;
+    const int fit = fit_row<true>(a, r, me);
     if (fit < 0) atomicAdd(n_bad, 1);
     if (fit != 1) return;
     const int64_t days = static_cast<int64_t>(me.e) - me.s + 1;
@@ -107,9 +123,13 @@ __global__ __launch_bounds__(kPartThreads) void parts_count(PartRows a, const in
     }
 }
 
-inline unsigned blocks_for(int64_t items) { return static_cast<unsigned>((items + kPartThreads - 1) / kPartThreads); }
-
 }  // namespace
+
+void launch_parts_union(const ObjectRows& rows, const int64_t* row_offsets, const int32_t* nbr, int32_t K, int32_t* parent,
+                        int64_t V, hipStream_t stream) {
+    hipLaunchKernelGGL(parts_link, dim3(blocks_for(rows.n)), dim3(kRowThreads), 0, stream, rows, row_offsets, nbr, K, parent);
+    hipLaunchKernelGGL(parts_flatten, dim3(blocks_for(V)), dim3(kRowThreads), 0, stream, V, parent);
+}
 
 size_t object_parts_scratch_bytes(int64_t V) { return static_cast<size_t>(kPartsVoxelBytes) * static_cast<size_t>(V > 0 ? V : 1); }
 
@@ -126,14 +146,13 @@ hipError_t launch_object_parts(const int32_t* start, const int32_t* end, const i
     int32_t* cells = parent + (V > 0 ? V : 0);
     const int64_t items = V > L ? V : L;
     if (items > 0)
-        hipLaunchKernelGGL(parts_init, dim3(blocks_for(items)), dim3(kPartThreads), 0, stream, V, parent, cells, area, L, n_parts,
+        hipLaunchKernelGGL(parts_init, dim3(blocks_for(items)), dim3(kRowThreads), 0, stream, V, parent, cells, area, L, n_parts,
                            cells_largest, area_largest_q);
     if (n > 0 && n_slots > 0 && L > 0) {
-        const PartRows rows{start, end, slot, cell_of_row, vox_off, time_start, offsets, n, C, n_slots, L, V};
-        const dim3 g(blocks_for(n)), b(kPartThreads);
+        const ObjectRows rows{start, end, slot, cell_of_row, time_start, offsets, n, C, n_slots, L, vox_off, V};
+        const dim3 g(blocks_for(n)), b(kRowThreads);
         if (V > 0) {
-            hipLaunchKernelGGL(parts_link, g, b, 0, stream, rows, row_offsets, nbr, K, parent);
-            hipLaunchKernelGGL(parts_flatten, dim3(blocks_for(V)), b, 0, stream, V, parent);
+            launch_parts_union(rows, row_offsets, nbr, K, parent, V, stream);
             hipLaunchKernelGGL(parts_reduce, g, b, 0, stream, rows, wq, static_cast<const int32_t*>(parent), cells,
                                reinterpret_cast<u64*>(area));
         }

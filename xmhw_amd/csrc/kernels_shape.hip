@@ -10,54 +10,28 @@
 //
 //   memsets        the seven arrays and *n_bad = 0.
 //   shape_walk     lane = row.  A coast or border face is the same on every day of the row.  For a face to a cell, a
-//                  cursor into the rows of that cell: it starts at the first row with end >= start_r (the binary search
-//                  of parts_link_row, row_offsets clamped to [0, n] as there) and moves on while the row under it ends
-//                  before the day; rows of a cell are in time order and disjoint, so the row under the cursor is the only
-//                  one that can cover the day.  It covers iff it has the lane's slot, is itself fit and has started.
+//                  cursor into the rows of that cell: it starts at the first row with end >= start_r
+//                  (first_row_reaching() of object_rows.h, row_offsets clamped to [0, n] there) and moves on while the
+//                  row under it ends before the day; rows of a cell are in time order and disjoint, so the row under
+//                  the cursor is the only one that can cover the day.  It covers iff it has the lane's slot, is itself fit and has started.
 //                  The lane walks its days once, forms the seven addends of a day in registers and issues one integer
 //                  atomic without a return value per addend that is not zero: a day on which every face is shared
 //                  issues none.
 //
-// A row is *fit* under the rule of parts_rows.h without its voxels: its slot is in [0, n_slots), its cell in [0, C),
-// start <= end, and its days lie within its object's entries (which lie within 0..L-1).  A selected row that is not fit
-// is left out -- it neither adds nor covers -- and counted in *n_bad; so is, once, a fit row one of whose faces holds a
+// A row is *fit* under the one rule of object_rows.h, without voxels (fit_row<false>): its slot is in [0, n_slots), its cell
+// in [0, C), start <= end, and its days lie within its object's entries (which lie within 0..L-1).  A selected row that
+// is not fit is left out -- it neither adds nor covers -- and counted in *n_bad; so is, once, a fit row one of whose faces holds a
 // value outside [kShapeFaceFolded, C) (that face is passed over).  Nothing outside entries 0..L-1 is ever written.
 // Everything is an integer sum: exact, and the same under any schedule.
 #include "device_common.h"
 #include "kernels.h"
+#include "object_rows.h"
 
 namespace xmhw {
 
 namespace {
 
-constexpr int kShapeThreads = 256;
 using u64 = unsigned long long;
-
-struct ShapeRows {
-    const int32_t *start, *end, *slot, *cell;
-    const int32_t* time_start;
-    const int64_t* offsets;
-    int64_t n, C, n_slots, L;
-};
-
-struct ShapeRow {
-    int32_t s, e, sl, c;
-    int64_t entry;                                   // the entry of day s
-};
-
-// part_row() of parts_rows.h without the voxels.  1: the row is fit and `row` describes it; 0: its slot is outside the
-// selection; -1: selected but not fit
-__device__ __forceinline__ int shape_row(const ShapeRows& a, int64_t r, ShapeRow& row) {
-    const int32_t sl = a.slot[r];
-    if (sl < 0 || sl >= a.n_slots) return 0;
-    const int32_t s = a.start[r], e = a.end[r], c = a.cell[r];
-    const int64_t o0 = a.offsets[sl], o1 = a.offsets[sl + 1], t0 = a.time_start[sl];
-    const int64_t days = static_cast<int64_t>(e) - s + 1;
-    const int64_t p0 = o0 + (static_cast<int64_t>(s) - t0);
-    if (c < 0 || c >= a.C || days < 1 || o0 < 0 || o1 > a.L || p0 < o0 || p0 + days > o1) return -1;
-    row = ShapeRow{s, e, sl, c, p0};
-    return 1;
-}
 
 // the rows of the cell across one face: [j, last) are those that can still cover a day of the lane's row
 struct ShapeCursor {
@@ -66,7 +40,7 @@ struct ShapeCursor {
     bool covers;                                     // it has the lane's slot and is fit
 };
 
-__device__ __forceinline__ void shape_cursor_load(const ShapeRows& a, int32_t slot, ShapeCursor& cur) {
+__device__ __forceinline__ void shape_cursor_load(const ObjectRows& a, int32_t slot, ShapeCursor& cur) {
     if (cur.j >= cur.last) {
         cur.s = cur.e = INT32_MAX;
         cur.covers = false;
@@ -74,19 +48,19 @@ __device__ __forceinline__ void shape_cursor_load(const ShapeRows& a, int32_t sl
     }
     cur.s = a.start[cur.j];
     cur.e = a.end[cur.j];
-    ShapeRow other;
-    cur.covers = a.slot[cur.j] == slot && shape_row(a, cur.j, other) == 1;
+    ObjectRow other;
+    cur.covers = a.slot[cur.j] == slot && fit_row<false>(a, cur.j, other) == 1;
 }
 
-__global__ __launch_bounds__(kShapeThreads) void shape_walk(ShapeRows a, const int64_t* __restrict__ row_offsets,
+__global__ __launch_bounds__(kRowThreads) void shape_walk(ObjectRows a, const int64_t* __restrict__ row_offsets,
                                                             const int32_t* __restrict__ faces,
                                                             const int64_t* __restrict__ lq, int32_t* __restrict__ edges,
                                                             u64* __restrict__ perimeter_q, int32_t* __restrict__ cells_edge,
                                                             int32_t* __restrict__ n_bad) {
     const int64_t r = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (r >= a.n) return;
-    ShapeRow me;
-    const int fit = shape_row(a, r, me);
+    ObjectRow me;
+    const int fit = fit_row<false>(a, r, me);
     if (fit < 0) atomicAdd(n_bad, 1);
     if (fit != 1) return;
     ShapeCursor cur[4];
@@ -108,15 +82,8 @@ __global__ __launch_bounds__(kShapeThreads) void shape_walk(ShapeRows a, const i
             n_border += 1;
             p_border += len[k];
         } else if (to_cell[k]) {
-            int64_t lo = row_offsets[f], last = row_offsets[f + 1];
-            last = last < 0 ? 0 : (last > a.n ? a.n : last);       // offsets that do not describe the rows read no row
-            lo = lo < 0 ? 0 : (lo > last ? last : lo);             // outside them: 0 <= lo <= last <= n
-            int64_t hi = last;
-            while (lo < hi) {                        // the first row of the cell with end >= start
-                const int64_t mid = lo + (hi - lo) / 2;
-                if (a.end[mid] < me.s) lo = mid + 1; else hi = mid;
-            }
-            cur[k].j = static_cast<int32_t>(lo);     // n < 2^31
+            int64_t last = row_offsets[f + 1];
+            cur[k].j = static_cast<int32_t>(first_row_reaching(a.end, row_offsets[f], last, a.n, me.s));     // n < 2^31
             cur[k].last = static_cast<int32_t>(last);
             shape_cursor_load(a, me.sl, cur[k]);
         } else if (f != kShapeFaceFolded) {
@@ -176,9 +143,8 @@ hipError_t launch_object_shape(const int32_t* start, const int32_t* end, const i
         if (e != hipSuccess) return e;
     }
     if (n > 0 && n_slots > 0 && L > 0) {
-        const ShapeRows rows{start, end, slot, cell_of_row, time_start, offsets, n, C, n_slots, L};
-        const unsigned blocks = static_cast<unsigned>((n + kShapeThreads - 1) / kShapeThreads);
-        hipLaunchKernelGGL(shape_walk, dim3(blocks), dim3(kShapeThreads), 0, stream, rows, row_offsets, faces, lq, edges,
+        const ObjectRows rows{start, end, slot, cell_of_row, time_start, offsets, n, C, n_slots, L, nullptr, 0};
+        hipLaunchKernelGGL(shape_walk, dim3(blocks_for(n)), dim3(kRowThreads), 0, stream, rows, row_offsets, faces, lq, edges,
                            reinterpret_cast<u64*>(perimeter_q), cells_edge, n_bad);
     }
     return hipGetLastError();

@@ -6,8 +6,9 @@
 //                    offsets[i] + start - time_start[i] and subtracts it at offsets[i] + end + 1 - time_start[i], which is
 //                    at most offsets[i + 1]: the first entry of the next object, or the sentinel entry L.  Integer
 //                    atomics without a return value: the result does not depend on the order.  A row whose slot is
-//                    outside [0, n_slots) does nothing; a row whose days leave its object's segment, or whose cell is
-//                    outside [0, C), is left out and counted in *n_bad (nothing is ever written outside 0..L).
+//                    outside [0, n_slots) does nothing; a selected row that is not fit (object_rows.h, fit_row<false>:
+//                    its days leave its object's segment, or its cell is outside [0, C)) is left out and counted in
+//                    *n_bad (nothing is ever written outside 0..L).
 //   tracks_tile_sums   block = one tile of kTile entries of one channel: the tile's sum.
 //   tracks_scan_tiles  block = one tile: inclusive scan in place, on top of the carry = the scanned sum of the tile in
 //                    front.  Thread = kItems consecutive entries; the thread totals are scanned within the wave by
@@ -20,33 +21,28 @@
 // prefix and every difference of two prefixes is within (-2^31, 2^31) -- and 64-bit in the levels of tile sums.
 #include "device_common.h"
 #include "kernels.h"
+#include "object_rows.h"
 
 namespace xmhw {
 
 namespace {
 
-constexpr int kTrkThreads = 256;
+constexpr int kTrkThreads = kRowThreads;
 constexpr int kTrkItems = kTracksTile / kTrkThreads;
 static_assert(kTrkItems * kTrkThreads == kTracksTile && kTrkItems == 4, "a thread owns four consecutive entries");
 using u64 = unsigned long long;
 
-__global__ __launch_bounds__(kTrkThreads) void tracks_scatter(
-    const int32_t* __restrict__ start, const int32_t* __restrict__ end, int64_t n, const int32_t* __restrict__ slot,
-    const int32_t* __restrict__ cell_of_row, int64_t C, const int64_t* __restrict__ vec, int64_t ldv,
-    const int32_t* __restrict__ time_start, const int64_t* __restrict__ offsets, int64_t n_slots,
-    int64_t L, int32_t* __restrict__ cnt, u64* __restrict__ sums, int64_t ld, int32_t* __restrict__ n_bad) {
+__global__ __launch_bounds__(kTrkThreads) void tracks_scatter(ObjectRows a, const int64_t* __restrict__ vec, int64_t ldv,
+                                                              int32_t* __restrict__ cnt, u64* __restrict__ sums, int64_t ld,
+                                                              int32_t* __restrict__ n_bad) {
     const int64_t r = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (r >= n) return;
-    const int32_t i = slot[r];
-    if (i < 0 || i >= n_slots) return;
-    const int32_t c = cell_of_row[r];
-    const int64_t o0 = offsets[i], o1 = offsets[i + 1], t0 = time_start[i];
-    const int64_t p0 = o0 + (static_cast<int64_t>(start[r]) - t0);
-    const int64_t p1 = o0 + (static_cast<int64_t>(end[r]) + 1 - t0);
-    if (c < 0 || c >= C || p0 < o0 || p1 <= p0 || p1 > o1 || o0 < 0 || o1 > L) {    // entries 0..L only
-        atomicAdd(n_bad, 1);
-        return;
-    }
+    if (r >= a.n) return;
+    ObjectRow me;
+    const int fit = fit_row<false>(a, r, me);
+    if (fit < 0) atomicAdd(n_bad, 1);
+    if (fit != 1) return;
+    const int32_t c = me.c;
+    const int64_t p0 = me.entry, p1 = me.entry + (static_cast<int64_t>(me.e) - me.s + 1);    // p1 <= offsets[i + 1] <= L
     u64 v[4];                                        // the four loads in flight together, ahead of the atomics
 #pragma unroll
     for (int k = 0; k < 4; ++k) v[k] = static_cast<u64>(vec[k * ldv + c]);
@@ -171,8 +167,8 @@ hipError_t launch_object_tracks(const int32_t* start, const int32_t* end, int64_
     if (e == hipSuccess) e = hipMemsetAsync(n_bad, 0, sizeof(int32_t), stream);
     if (e != hipSuccess) return e;
     if (n > 0 && n_slots > 0 && L > 0) {
-        hipLaunchKernelGGL(tracks_scatter, dim3(static_cast<unsigned>((n + kTrkThreads - 1) / kTrkThreads)), dim3(kTrkThreads), 0,
-                           stream, start, end, n, slot, cell_of_row, C, vec, ldv, time_start, offsets, n_slots, L, n_cells,
+        const ObjectRows rows{start, end, slot, cell_of_row, time_start, offsets, n, C, n_slots, L, nullptr, 0};
+        hipLaunchKernelGGL(tracks_scatter, dim3(blocks_for(n)), dim3(kTrkThreads), 0, stream, rows, vec, ldv, n_cells,
                            reinterpret_cast<u64*>(sums), ld, n_bad);
         scan_level(n_cells, sums, ld, L + 1, scratch, stream);
     }

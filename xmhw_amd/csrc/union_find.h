@@ -1,5 +1,5 @@
-// union_find.h -- the lock-free union-find shared by kernels_objects.hip (on table rows) and, through parts_rows.h, by
-// kernels_parts.hip and kernels_genealogy.hip (on the voxels of one day).  parent[x] <= x always, so a tree's root is
+// union_find.h -- the lock-free union-find shared by kernels_objects.hip (on table rows) and kernels_parts.hip (on the
+// voxels of one day; kernels_genealogy.hip runs that one through launch_parts_union() of object_rows.h).  parent[x] <= x always, so a tree's root is
 // its smallest member under any schedule.  find_root() reads with relaxed agent-scope atomic loads and shortens the path
 // behind it (any value ever stored in parent[x] is an ancestor of x).  unite() puts the larger root under the smaller by
 // a compare-and-swap that succeeds only while the target is still its own parent; on failure both ends are found again.

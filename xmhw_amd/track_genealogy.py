@@ -51,17 +51,16 @@ fields); device side in csrc/kernels_genealogy.hip behind track_genealogy_device
 """
 import numpy as np
 
-from ._lib import hip
-from .detect import EventDataset
-from .device import DeviceScope, as_xmhw_errors
 from .exception import XmhwException
 from .objects import neighbour_table
+from .track_common import ChainDataset, Selection, device_stage, stage_inputs
 from .track_parts import voxel_offsets
-from .tracks import checked_selection, selection_layout
 
 COUNT_FIELDS = ("n_parts", "n_links", "n_born", "n_merged", "n_ended", "n_split")       # XMHW_GENEALOGY_* order
 EDGE_FIELDS = ("edge_track", "edge_pos", "edge_from", "edge_to")
 STAGE_FIELDS = COUNT_FIELDS + EDGE_FIELDS
+_INPUTS = dict(start=np.int32, end=np.int32, slot=np.int32, cell=np.int32, row_offsets=np.int64, nbr=np.int32, vox_off=np.int64,
+               time_start=np.int32, offsets=np.int64)
 VOXEL_BYTES = 12                # XMHW_GENEALOGY_VOXEL_BYTES (include/xmhw_amd.h)
 SLOT_BYTES = 8                  # XMHW_GENEALOGY_SLOT_BYTES
 
@@ -107,15 +106,8 @@ def track_genealogy_device(start, end, slot, cell, row_offsets, nbr, vox_off, ti
     STAGE_FIELDS: the six COUNT_FIELDS (L,) int32, L = offsets[-1], and the E edges sorted by (edge_track, edge_pos,
     edge_from, edge_to), all int32, edge_from / edge_to being the smallest COMPACT cell of the two parts
     (mhw_track_genealogy() turns them into labels with cell_index)."""
-    start = np.ascontiguousarray(start, dtype=np.int32)
-    end = np.ascontiguousarray(end, dtype=np.int32)
-    slot = np.ascontiguousarray(slot, dtype=np.int32)
-    cell = np.ascontiguousarray(cell, dtype=np.int32)
-    row_offsets = np.ascontiguousarray(row_offsets, dtype=np.int64)
-    nbr = np.ascontiguousarray(nbr, dtype=np.int32)
-    vox_off = np.ascontiguousarray(vox_off, dtype=np.int64)
-    time_start = np.ascontiguousarray(time_start, dtype=np.int32)
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    start, end, slot, cell, row_offsets, nbr, vox_off, time_start, offsets = a = stage_inputs(
+        _INPUTS, start, end, slot, cell, row_offsets, nbr, vox_off, time_start, offsets)
     n, m = start.shape[0], time_start.shape[0]
     L = int(offsets[-1])
     if L == 0 or n == 0 or m == 0:
@@ -125,14 +117,10 @@ def track_genealogy_device(start, end, slot, cell, row_offsets, nbr, vox_off, ti
         raise XmhwException("the neighbour table, the row offsets and the voxel offsets do not fit the rows and cells")
     V = int(vox_off[-1])
     cap = edge_capacity(start, end, slot, cell)
-    if max(n, m, L, V, C, cap) >= 1 << 31:
-        raise XmhwException(f"mhw_track_genealogy handles fewer than 2**31 rows, objects, series entries and voxels, got {n}, "
-                            f"{m}, {L}, {V}: select fewer objects with ids=")
-    h = hip()
     F = len(COUNT_FIELDS)
-    with DeviceScope() as s:
-        with as_xmhw_errors(also="Unsupported", hint="select fewer objects with ids="):
-            d = [s.upload(a) for a in (start, end, slot, cell, row_offsets, nbr, vox_off, time_start, offsets)]
+    with device_stage(a, (n, m, L, V, C, cap), f"mhw_track_genealogy handles fewer than 2**31 rows, objects, series entries and "
+                      f"voxels, got {n}, {m}, {L}, {V}") as (h, s, d, launch):
+        with launch:
             d_counts, d_edges = s.alloc(4 * F * L), s.alloc(8 * max(cap, 1))
             d_ne, d_bad, d_over = s.alloc(8), s.alloc(4), s.alloc(4)
             h.object_genealogy(d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, n, d[4].ptr, C, d[5].ptr, nbr.shape[1], d[6].ptr, V,
@@ -154,7 +142,7 @@ def track_genealogy_device(start, end, slot, cell, row_offsets, nbr, vox_off, ti
     return out
 
 
-class TrackGenealogyDataset:
+class TrackGenealogyDataset(ChainDataset):
     """What mhw_track_genealogy() returns, as plain arrays, aligned with the TrackDataset / TrackPartsDataset of the same
     ``ids``: m objects, L = offsets[-1] entries; entry offsets[i] + (t - time_start[i]) belongs to object ids[i] on time
     position t.
@@ -171,54 +159,25 @@ class TrackGenealogyDataset:
     _SERIES = ("pos",) + COUNT_FIELDS
     _PER_OBJECT = ("ids", "time_start", "time_end", "duration", "n_splits", "n_merges", "n_births", "n_ends", "n_nodes",
                    "n_edges")
+    _ATTRS = ("neighbours", "periodic")
 
     def __init__(self, fields, time, sdims, sshape, neighbours, periodic, n_voxels, attrs=None):
-        for k, v in fields.items():
-            setattr(self, k, v)
-        self.time, self.sdims, self.sshape = np.asarray(time), tuple(sdims), tuple(sshape)
+        super().__init__(fields, time, sdims, sshape, attrs)
         self.neighbours, self.periodic, self.n_voxels = int(neighbours), periodic, int(n_voxels)
-        self.attrs = dict(attrs or {})
-
-    @property
-    def n_selected(self):
-        return int(self.ids.shape[0])
-
-    time_stamps = EventDataset.time_stamps
-
-    def _position(self, i, who):
-        i = int(i)
-        if not 0 <= i < self.n_selected:
-            raise XmhwException(f"{who}() takes a position in [0, {self.n_selected}), got {i}")
-        return i
-
-    def series(self, i):
-        """The slices of the i-th selected object: a dict of its series plus ``time``, the stamps of its days."""
-        i = self._position(i, "series")
-        sl = slice(int(self.offsets[i]), int(self.offsets[i + 1]))
-        out = {k: getattr(self, k)[sl] for k in self._SERIES}
-        out["time"] = self.time_stamps(out["pos"])
-        return out
 
     def edges(self, i):
         """The edges of the i-th selected object: a dict of its slices of the four edge arrays plus ``time``, the stamps
         of the later days."""
-        i = self._position(i, "edges")
-        sl = slice(int(self.edge_offsets[i]), int(self.edge_offsets[i + 1]))
+        sl = self._span(i, "edges", self.edge_offsets)
         out = {k: getattr(self, k)[sl] for k in EDGE_FIELDS}
         out["time"] = self.time_stamps(out["edge_pos"])
         return out
 
-    def to_xarray(self):
-        import xarray as xr
-        data = {k: (("obs",), getattr(self, k)) for k in self._SERIES}
-        data["time"] = (("obs",), self.time_stamps(self.pos))
-        for k in EDGE_FIELDS:
-            data[k] = (("edge",), getattr(self, k))
-        for k in self._PER_OBJECT:
-            data["object_id" if k == "ids" else k] = (("track",), getattr(self, k))
-        data["offsets"] = (("track_edge",), self.offsets)
+    def _variables(self):
+        data = super()._variables()
+        data.update({k: (("edge",), getattr(self, k)) for k in EDGE_FIELDS})
         data["edge_offsets"] = (("track_edge",), self.edge_offsets)
-        return xr.Dataset(data, attrs=dict(self.attrs, neighbours=self.neighbours, periodic=self.periodic or ""))
+        return data
 
 
 def mhw_track_genealogy(mhw, obj, ids=None, neighbours=None, _compute=None):
@@ -231,34 +190,26 @@ def mhw_track_genealogy(mhw, obj, ids=None, neighbours=None, _compute=None):
     Returns a TrackGenealogyDataset (module docstring: the definition and the identities; class docstring: the fields).
     Every number is an integer count and the edges are sorted: exact, and the same from run to run.  ``_compute``: a
     stand-in for track_genealogy_device() (host tests)."""
-    sshape, object_of_row, ids = checked_selection(mhw, obj, ids, "mhw_track_genealogy")
-    if neighbours not in (None, 4, 8):
-        raise XmhwException(f"neighbours should be None, 4 or 8, got {neighbours!r}")
-    if obj.connectivity not in (6, 26):
-        raise XmhwException(f"obj.connectivity should be 6 or 26, got {obj.connectivity!r}")
-    if obj.periodic is not None and obj.periodic not in mhw.sdims:
-        raise XmhwException(f"obj.periodic should be None or one of {mhw.sdims}, got {obj.periodic!r}: obj does not belong "
-                            "to mhw")
-    K = int(neighbours) if neighbours is not None else (4 if obj.connectivity == 6 else 8)
-    m = ids.shape[0]
-    view = mhw.compact_view()
-    cell_index, start, end = (view[k] for k in ("cell_index", "start", "end"))
+    sel = Selection(mhw, obj, ids, "mhw_track_genealogy")
+    K = sel.neighbours_k(neighbours)
+    axis = sel.periodic_axis()
+    sshape, m = sel.sshape, sel.m
+    sel.view()
+    cell_index = sel.cell_index
     if (np.diff(cell_index) <= 0).any():               # the smallest compact cell of a part is then its smallest grid index
         raise XmhwException("mhw.cell_index should ascend, as detect() returns it")
-    t0, t1, dur, offsets, slot = selection_layout(obj, ids, object_of_row, start, end)
-    L = int(offsets[-1])
-    vox_off = voxel_offsets(start, end, slot)          # refuses V >= 2**31: nothing of size L or V exists yet
+    sel.layout()
+    L, t0, offsets = sel.L, sel.time_start, sel.offsets
+    vox_off = voxel_offsets(sel.start, sel.end, sel.slot)     # refuses V >= 2**31: nothing of size L or V exists yet
     V = int(vox_off[-1])
     if L == 0:
-        got = {k: np.zeros(0, dtype=np.int32) for k in STAGE_FIELDS}
+        got = sel.no_entries(dict.fromkeys(STAGE_FIELDS, np.int32))
     else:
-        axis = None if obj.periodic is None else mhw.sdims.index(obj.periodic)
         nbr = neighbour_table(cell_index, sshape, 6 if K == 4 else 26, axis)
-        got = (_compute or track_genealogy_device)(start, end, slot, view["cell_of_row"].astype(np.int32), view["offsets"], nbr,
+        got = (_compute or track_genealogy_device)(sel.start, sel.end, sel.slot, sel.cell_of_row, sel.row_offsets, nbr,
                                                    vox_off, t0, offsets)
-    f = {k: np.ascontiguousarray(got[k], dtype=np.int32) for k in STAGE_FIELDS}
-    if any(f[k].shape != (L,) for k in COUNT_FIELDS):
-        raise XmhwException(f"track genealogy stage returned arrays that do not fit {L} entries")
+    edges = {k: np.ascontiguousarray(got[k], dtype=np.int32) for k in EDGE_FIELDS}
+    f = dict(sel.stage_arrays(got, dict.fromkeys(COUNT_FIELDS, np.int32), "track genealogy"), **edges)
     E = f["edge_track"].shape[0]
     if any(f[k].shape != (E,) for k in EDGE_FIELDS):
         raise XmhwException("track genealogy stage returned edge arrays of different lengths")
@@ -279,8 +230,7 @@ def mhw_track_genealogy(mhw, obj, ids=None, neighbours=None, _compute=None):
         raise XmhwException("track genealogy stage returned edges that do not fit its n_links")
     f.update(edge_track=track, edge_pos=pos, edge_from=a, edge_to=b)
     f["edge_offsets"] = np.concatenate([[0], np.cumsum(np.bincount(track, minlength=m))]).astype(np.int64)
-    f.update(ids=ids, offsets=offsets, time_start=t0, time_end=t1, duration=dur.astype(np.int32))
-    f["pos"] = (np.arange(L, dtype=np.int64) - np.repeat(first - t0, dur)).astype(np.int32)
+    f.update(sel.common_fields(), pos=sel.pos())
     if m:
         total = {k: np.add.reduceat(f[k].astype(np.int64), first) for k in ("n_parts", "n_born", "n_merged", "n_ended", "n_split")}
         f["n_splits"], f["n_merges"], f["n_nodes"] = total["n_split"], total["n_merged"], total["n_parts"]

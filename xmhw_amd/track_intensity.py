@@ -43,12 +43,14 @@ from .device import DeviceScope, as_xmhw_errors
 from .exception import XmhwException
 from .gridweights import quantise_weights, resolve_weights, weights_label
 from .objects import ObjectDataset
+from .track_common import ChainDataset, Selection
 from .tracks import TrackDataset
 
 INTENSITY_BITS = 16             # XMHW_TRACK_INTENSITY_BITS (include/xmhw_amd.h)
 RANGE_BITS = 7                  # |a| < 2**7
 CATEGORIES = ("moderate", "strong", "severe", "extreme")
 STAGE_FIELDS = ("n_valid", "wsum_i", "isum_q", "intensity_max", "cat_cells")
+_STAGE = dict(n_valid=np.int32, wsum_i=np.int64, isum_q=np.int64, intensity_max=np.float64, cat_cells=(np.int32, 4))
 _COLD_TEXT = "cold events were detected"
 
 
@@ -57,52 +59,11 @@ def intensity_bits(weight_bits, n_ocean):
     return int(min(int(weight_bits), 61 - INTENSITY_BITS - RANGE_BITS - int(n_ocean).bit_length()))
 
 
-class _Rows:
-    """The selection as the device stage takes it: the table rows (start, end, slot; int32) with the (C + 1,) int64
-    offsets of the cells' rows, and the ragged layout (time_start (m,) int32, offsets (m + 1,) int64)."""
-
-    def __init__(self, start, end, slot, row_offsets, time_start, offsets):
-        self.start = np.ascontiguousarray(start, dtype=np.int32)
-        self.end = np.ascontiguousarray(end, dtype=np.int32)
-        self.slot = np.ascontiguousarray(slot, dtype=np.int32)
-        self.row_offsets = np.ascontiguousarray(row_offsets, dtype=np.int64)
-        self.time_start = np.ascontiguousarray(time_start, dtype=np.int32)
-        self.offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        self.m, self.L = self.time_start.shape[0], int(self.offsets[-1])
-        if max(self.start.shape[0], self.m, self.L) >= 1 << 31:
-            raise XmhwException(f"mhw_track_intensity handles fewer than 2**31 rows, objects and series entries, got "
-                                f"{self.start.shape[0]}, {self.m}, {self.L}: select fewer objects with ids= in mhw_tracks()")
-
-
 def selection_rows(mhw, obj, tr):
-    """The _Rows of the selection of ``tr``: the rows of ``mhw`` with the position of their object in ``tr.ids`` (-1: not
-    selected) and the ragged layout of ``tr``, checked against ``obj``."""
-    # the selection and its layout: those of tr, checked against obj
-    n = mhw.n_events
-    object_of_row = np.asarray(obj.object, dtype=np.int64)
-    m_all = obj.n_objects
-    if object_of_row.shape != (n,) or (n and (object_of_row.min() < 0 or object_of_row.max() >= m_all)):
-        raise XmhwException("obj.object should hold one object id per table row: obj does not belong to mhw")
-    ids = np.asarray(tr.ids, dtype=np.int64)
-    m = ids.shape[0]
-    if m and (ids.min() < 0 or ids.max() >= m_all or np.unique(ids).shape[0] != m):
-        raise XmhwException("tr.ids should be distinct object ids of obj: tr does not belong to obj")
-    t0 = np.ascontiguousarray(tr.time_start, dtype=np.int32)
-    offsets = np.ascontiguousarray(tr.offsets, dtype=np.int64)
-    dur = np.asarray(obj.time_end, dtype=np.int64)[ids] - np.asarray(obj.time_start, dtype=np.int64)[ids] + 1
-    if (offsets.shape != (m + 1,) or not np.array_equal(t0, np.asarray(obj.time_start)[ids])
-            or not np.array_equal(np.diff(offsets), dur) or offsets[0] != 0):
-        raise XmhwException("tr.time_start and tr.offsets are not those of its objects in obj: tr does not belong to obj")
-    L = int(offsets[-1])
-    if L >= 1 << 31:
-        raise XmhwException(f"the series of the {m} selected objects hold {L} entries, 2**31 and more: select fewer "
-                            "objects with ids= in mhw_tracks()")
-    view = mhw.compact_view()
-    C = view["C"]
-    position = np.full(m_all, -1, dtype=np.int32)
-    position[ids] = np.arange(m, dtype=np.int32)
-    slot = position[object_of_row] if n else np.zeros(0, dtype=np.int32)
-    return _Rows(view["start"], view["end"], slot, view["offsets"], t0, offsets)
+    """The Selection (track_common.py) of ``tr``: the rows of ``mhw`` (start, end, slot; int32: the position of their object
+    in ``tr.ids``, -1: not selected) with the (C + 1,) int64 row_offsets of the cells' rows, and the ragged layout of ``tr``
+    (time_start (m,) int32, offsets (m + 1,) int64, m, L), checked against ``obj``."""
+    return Selection.of_tracks(mhw, obj, tr, "mhw_track_intensity")
 
 
 class _Accumulators:
@@ -157,8 +118,8 @@ class _Accumulators:
 
 
 def track_intensity_cells(ts, seas, thresh, doy, doys, rows, wi, coldSpells=False, max_batch_bytes=64 << 30, pad=None):
-    """The device stage for a dense (T, C) host series (arguments as coverage.coverage_cells): ``rows`` the _Rows of the
-    selection, ``wi`` (C,) int64 weights.  Returns a dict of STAGE_FIELDS plus the counters n_range and n_bad.  Cells go
+    """The device stage for a dense (T, C) host series (arguments as coverage.coverage_cells): ``rows`` the selection_rows()
+    of the selection, ``wi`` (C,) int64 weights.  Returns a dict of STAGE_FIELDS plus the counters n_range and n_bad.  Cells go
     through the device in batches below max_batch_bytes; the sums are integers, so the batch size does not change a bit."""
     from .detect_front import _check_inputs
     ts, seas, thresh, row_of_t = _check_inputs(ts, seas, thresh, doy, doys)
@@ -255,7 +216,7 @@ def track_intensity_grid(stacked, anynans, seas, thresh, doy, doys, rows, wi, ke
         clim.free()
 
 
-class TrackIntensityDataset:
+class TrackIntensityDataset(ChainDataset):
     """What mhw_track_intensity() returns, as plain arrays, aligned with the TrackDataset it was given: m objects, L =
     offsets[-1] entries; entry offsets[i] + (t - time_start[i]) belongs to object ids[i] on time position t.
 
@@ -272,30 +233,20 @@ class TrackIntensityDataset:
 
     _SERIES = ("pos", "n_valid", "wsum_i", "isum_q", "intensity_mean", "intensity_max")
     _PER_OBJECT = ("ids", "time_start", "time_end", "duration", "intensity_cumulative", "intensity_peak", "pos_peak")
+    _ATTRS = ("intensity_bits", "intensity_weight_bits")
+    _COORDS = {"category": list(CATEGORIES)}
+    intensity_bits = INTENSITY_BITS
 
     def __init__(self, fields, time, sdims, sshape, intensity_weight_bits, n_ocean, attrs=None):
-        for k, v in fields.items():
-            setattr(self, k, v)
-        self.time, self.sdims, self.sshape = np.asarray(time), tuple(sdims), tuple(sshape)
+        super().__init__(fields, time, sdims, sshape, attrs)
         self.intensity_weight_bits, self.n_ocean = int(intensity_weight_bits), int(n_ocean)
         self.category = CATEGORIES
-        self.attrs = dict(attrs or {})
-
-    @property
-    def n_selected(self):
-        return int(self.ids.shape[0])
-
-    time_stamps = EventDataset.time_stamps
 
     def series(self, i):
         """The slices of the i-th selected object: a dict of its series (cat_cells as (4, days)) plus ``time``."""
-        i = int(i)
-        if not 0 <= i < self.n_selected:
-            raise XmhwException(f"series() takes a position in [0, {self.n_selected}), got {i}")
-        sl = slice(int(self.offsets[i]), int(self.offsets[i + 1]))
-        out = {k: getattr(self, k)[sl] for k in self._SERIES}
-        out["cat_cells"] = self.cat_cells[:, sl]
-        out["time"] = self.time_stamps(out["pos"])
+        out = super().series(i)
+        time = out.pop("time")                         # cat_cells comes in front of time, as it always did
+        out.update(cat_cells=self.cat_cells[:, self._span(i)], time=time)
         return out
 
     def quantisation_bound(self):
@@ -314,16 +265,8 @@ class TrackIntensityDataset:
             b = self.n_valid.astype(np.float64) * 2.0 ** RANGE_BITS / self.wsum_i.astype(np.float64)
         return np.where(self.wsum_i > 0, b + 2.0 ** -(INTENSITY_BITS + 1) + 2.0 ** -44, np.nan)
 
-    def to_xarray(self):
-        import xarray as xr
-        data = {k: (("obs",), getattr(self, k)) for k in self._SERIES}
-        data["cat_cells"] = (("category", "obs"), self.cat_cells)
-        data["time"] = (("obs",), self.time_stamps(self.pos))
-        for k in self._PER_OBJECT:
-            data["object_id" if k == "ids" else k] = (("track",), getattr(self, k))
-        data["offsets"] = (("track_edge",), self.offsets)
-        return xr.Dataset(data, coords={"category": list(CATEGORIES)},
-                          attrs=dict(self.attrs, intensity_bits=INTENSITY_BITS, intensity_weight_bits=self.intensity_weight_bits))
+    def _variables(self):
+        return dict(super()._variables(), cat_cells=(("category", "obs"), self.cat_cells))
 
 
 def mhw_track_intensity(temp, th, se, mhw, obj, tr, weights=None, tdim="time", maxPadLength=None, coldSpells=False,
@@ -375,14 +318,12 @@ def mhw_track_intensity(temp, th, se, mhw, obj, tr, weights=None, tdim="time", m
     if np.asarray(mhw.time).shape[0] != T:
         raise XmhwException(f"temp has {T} time steps, the detection {np.asarray(mhw.time).shape[0]}")
     rows = selection_rows(mhw, obj, tr)
-    view = mhw.compact_view()
-    C, t0, offsets = view["C"], rows.time_start, rows.offsets
-    m, L = rows.m, rows.L
+    C = rows.C
     ib = intensity_bits(obj.weight_bits, C)
     if ib < 1:
         raise XmhwException(f"a grid of {sshape} with {C} ocean cells leaves no bits for the intensity weights")
     w = resolve_weights(weights, mhw.coords, list(sdims), None, list(sdims), sshape)
-    wi = quantise_weights(w, ib)[0][view["cell_index"]]
+    wi = quantise_weights(w, ib)[0][rows.cell_index]
     keep_want = np.asarray(mhw.keep, dtype=bool).reshape(-1)
     got = {}
 
@@ -416,28 +357,18 @@ def mhw_track_intensity(temp, th, se, mhw, obj, tr, weights=None, tdim="time", m
         raise XmhwException(f"{st['n_range']} voxels hold an anomaly of 2**{RANGE_BITS} and more in magnitude: are temp, th "
                             "and se in the same units, and se the climatology of temp?")
     f = dict(ids=tr.ids, offsets=tr.offsets, time_start=tr.time_start, time_end=tr.time_end, duration=tr.duration, pos=tr.pos)
-    f["n_valid"] = np.ascontiguousarray(st["n_valid"], dtype=np.int32)
-    f["wsum_i"], f["isum_q"] = (np.ascontiguousarray(st[k], dtype=np.int64) for k in ("wsum_i", "isum_q"))
-    f["intensity_max"] = np.ascontiguousarray(st["intensity_max"], dtype=np.float64)
-    f["cat_cells"] = np.ascontiguousarray(st["cat_cells"], dtype=np.int32)
-    if any(f[k].shape != (L,) for k in STAGE_FIELDS[:4]) or f["cat_cells"].shape != (4, L):
-        raise XmhwException(f"track intensity stage returned arrays that do not fit {L} entries")
+    f.update(rows.stage_arrays(st, _STAGE, "track intensity"))
     with np.errstate(divide="ignore", invalid="ignore"):
         mean = f["isum_q"].astype(np.float64) / (f["wsum_i"].astype(np.float64) * 2.0 ** INTENSITY_BITS)
     f["intensity_mean"] = np.where(f["wsum_i"] > 0, mean, np.nan)
-    first = offsets[:-1]
-    if m:
-        durs = np.diff(offsets)
-        f["intensity_cumulative"] = np.add.reduceat(np.where(np.isnan(f["intensity_mean"]), 0.0, f["intensity_mean"]), first)
-        low = np.where(np.isnan(f["intensity_max"]), -np.inf, f["intensity_max"])
-        peak = np.maximum.reduceat(low, first)
-        at = np.where(low == np.repeat(peak, durs), np.arange(L, dtype=np.int64), L)
-        has = np.isfinite(peak)
-        f["intensity_peak"] = np.where(has, peak, np.nan)
-        f["pos_peak"] = np.where(has, np.minimum.reduceat(at, first) - first + t0, -1).astype(np.int32)
+    if rows.m:
+        f["intensity_cumulative"] = np.add.reduceat(np.where(np.isnan(f["intensity_mean"]), 0.0, f["intensity_mean"]),
+                                                    rows.offsets[:-1])
     else:
-        f["intensity_cumulative"], f["intensity_peak"] = np.zeros(0), np.zeros(0)
-        f["pos_peak"] = np.zeros(0, dtype=np.int32)
+        f["intensity_cumulative"] = np.zeros(0)
+    peak, pos = rows.first_max(np.where(np.isnan(f["intensity_max"]), -np.inf, f["intensity_max"]))
+    has = np.isfinite(peak)
+    f["intensity_peak"], f["pos_peak"] = np.where(has, peak, np.nan), np.where(has, pos, -1).astype(np.int32)
     attrs = {"weights": weights_label(weights)}
     if params is not None:
         attrs["xmhw_parameters"] = params

@@ -44,16 +44,15 @@ csrc/kernels_parts.hip behind track_parts_device().
 """
 import numpy as np
 
-from ._lib import hip
-from .detect import EventDataset
-from .device import DeviceScope, as_xmhw_errors
 from .exception import XmhwException
 from .gridweights import quantise_weights, resolve_weights, weights_label
 from .objects import neighbour_table
-from .tracks import checked_selection, selection_layout
+from .track_common import ChainDataset, Selection, device_stage, stage_inputs
 
 STAGE_FIELDS = ("n_parts", "cells_largest", "area_largest_q")
 _DTYPES = dict(n_parts=np.int32, cells_largest=np.int32, area_largest_q=np.int64)
+_INPUTS = dict(start=np.int32, end=np.int32, slot=np.int32, cell=np.int32, row_offsets=np.int64, nbr=np.int32, wq=np.int64,
+               vox_off=np.int64, time_start=np.int32, offsets=np.int64)
 VOXEL_BYTES = 16                # XMHW_PARTS_VOXEL_BYTES (include/xmhw_amd.h)
 
 
@@ -76,16 +75,8 @@ def track_parts_device(start, end, slot, cell, row_offsets, nbr, wq, vox_off, ti
     object in the selection or -1; cell (n,) int32, the row's compact cell; row_offsets (C + 1,) int64, the rows of every
     cell; nbr (C, K) int32; wq (C,) int64; vox_off (n + 1,) int64 (voxel_offsets()); time_start (m,) int32 and offsets
     (m + 1,) int64 of the selection.  Returns a dict of STAGE_FIELDS, (L,) each, L = offsets[-1]."""
-    start = np.ascontiguousarray(start, dtype=np.int32)
-    end = np.ascontiguousarray(end, dtype=np.int32)
-    slot = np.ascontiguousarray(slot, dtype=np.int32)
-    cell = np.ascontiguousarray(cell, dtype=np.int32)
-    row_offsets = np.ascontiguousarray(row_offsets, dtype=np.int64)
-    nbr = np.ascontiguousarray(nbr, dtype=np.int32)
-    wq = np.ascontiguousarray(wq, dtype=np.int64)
-    vox_off = np.ascontiguousarray(vox_off, dtype=np.int64)
-    time_start = np.ascontiguousarray(time_start, dtype=np.int32)
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    start, end, slot, cell, row_offsets, nbr, wq, vox_off, time_start, offsets = a = stage_inputs(
+        _INPUTS, start, end, slot, cell, row_offsets, nbr, wq, vox_off, time_start, offsets)
     n, m, C = start.shape[0], time_start.shape[0], wq.shape[0]
     L = int(offsets[-1])
     if L == 0 or n == 0 or m == 0:
@@ -93,13 +84,9 @@ def track_parts_device(start, end, slot, cell, row_offsets, nbr, wq, vox_off, ti
     if nbr.ndim != 2 or nbr.shape[0] != C or row_offsets.shape != (C + 1,) or vox_off.shape != (n + 1,):
         raise XmhwException("the neighbour table, the row offsets and the voxel offsets do not fit the rows and cells")
     V = int(vox_off[-1])
-    if max(n, m, L, V, C) >= 1 << 31:
-        raise XmhwException(f"mhw_track_parts handles fewer than 2**31 rows, objects, series entries and voxels, got {n}, "
-                            f"{m}, {L}, {V}: select fewer objects with ids=")
-    h = hip()
-    with DeviceScope() as s:
-        with as_xmhw_errors(also="Unsupported", hint="select fewer objects with ids="):
-            d = [s.upload(a) for a in (start, end, slot, cell, row_offsets, nbr, wq, vox_off, time_start, offsets)]
+    with device_stage(a, (n, m, L, V, C), f"mhw_track_parts handles fewer than 2**31 rows, objects, series entries and voxels, "
+                      f"got {n}, {m}, {L}, {V}") as (h, s, d, launch):
+        with launch:
             d_np, d_cl, d_al, d_bad = s.alloc(4 * L), s.alloc(4 * L), s.alloc(8 * L), s.alloc(4)
             h.object_parts(d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, n, d[4].ptr, C, d[5].ptr, nbr.shape[1], d[6].ptr, d[7].ptr, V,
                            d[8].ptr, d[9].ptr, m, L, d_np.ptr, d_cl.ptr, d_al.ptr, d_bad.ptr)
@@ -113,7 +100,7 @@ def track_parts_device(start, end, slot, cell, row_offsets, nbr, wq, vox_off, ti
     return out
 
 
-class TrackPartsDataset:
+class TrackPartsDataset(ChainDataset):
     """What mhw_track_parts() returns, as plain arrays, aligned with the TrackDataset of the same ``ids``: m objects, L =
     offsets[-1] entries; entry offsets[i] + (t - time_start[i]) belongs to object ids[i] on time position t.
 
@@ -130,40 +117,12 @@ class TrackPartsDataset:
 
     _SERIES = ("pos", "n_parts", "cells_largest", "area_largest_q", "area_largest")
     _PER_OBJECT = ("ids", "time_start", "time_end", "duration", "n_parts_max", "pos_n_parts_max", "days_split")
+    _ATTRS = ("neighbours", "periodic", "weight_unit", "weight_bits")
 
     def __init__(self, fields, time, sdims, sshape, neighbours, periodic, weight_bits, weight_unit, n_voxels, attrs=None):
-        for k, v in fields.items():
-            setattr(self, k, v)
-        self.time, self.sdims, self.sshape = np.asarray(time), tuple(sdims), tuple(sshape)
+        super().__init__(fields, time, sdims, sshape, attrs)
         self.neighbours, self.periodic = int(neighbours), periodic
         self.weight_bits, self.weight_unit, self.n_voxels = int(weight_bits), float(weight_unit), int(n_voxels)
-        self.attrs = dict(attrs or {})
-
-    @property
-    def n_selected(self):
-        return int(self.ids.shape[0])
-
-    time_stamps = EventDataset.time_stamps
-
-    def series(self, i):
-        """The slices of the i-th selected object: a dict of its series plus ``time``, the stamps of its days."""
-        i = int(i)
-        if not 0 <= i < self.n_selected:
-            raise XmhwException(f"series() takes a position in [0, {self.n_selected}), got {i}")
-        sl = slice(int(self.offsets[i]), int(self.offsets[i + 1]))
-        out = {k: getattr(self, k)[sl] for k in self._SERIES}
-        out["time"] = self.time_stamps(out["pos"])
-        return out
-
-    def to_xarray(self):
-        import xarray as xr
-        data = {k: (("obs",), getattr(self, k)) for k in self._SERIES}
-        data["time"] = (("obs",), self.time_stamps(self.pos))
-        for k in self._PER_OBJECT:
-            data["object_id" if k == "ids" else k] = (("track",), getattr(self, k))
-        data["offsets"] = (("track_edge",), self.offsets)
-        return xr.Dataset(data, attrs=dict(self.attrs, neighbours=self.neighbours, periodic=self.periodic or "",
-                                           weight_unit=self.weight_unit, weight_bits=self.weight_bits))
 
 
 def mhw_track_parts(mhw, obj, ids=None, weights=None, neighbours=None, _compute=None):
@@ -176,50 +135,31 @@ def mhw_track_parts(mhw, obj, ids=None, weights=None, neighbours=None, _compute=
     Returns a TrackPartsDataset (module docstring: the definition and the identities; class docstring: the fields).
     Every number is an integer sum or maximum: exact, and the same from run to run.  ``_compute``: a stand-in for
     track_parts_device() (host tests)."""
-    sshape, object_of_row, ids = checked_selection(mhw, obj, ids, "mhw_track_parts")
-    if neighbours not in (None, 4, 8):
-        raise XmhwException(f"neighbours should be None, 4 or 8, got {neighbours!r}")
-    if obj.connectivity not in (6, 26):
-        raise XmhwException(f"obj.connectivity should be 6 or 26, got {obj.connectivity!r}")
-    if obj.periodic is not None and obj.periodic not in mhw.sdims:
-        raise XmhwException(f"obj.periodic should be None or one of {mhw.sdims}, got {obj.periodic!r}: obj does not belong "
-                            "to mhw")
-    K = int(neighbours) if neighbours is not None else (4 if obj.connectivity == 6 else 8)
-    m = ids.shape[0]
-    sdims = list(mhw.sdims)
+    sel = Selection(mhw, obj, ids, "mhw_track_parts")
+    K = sel.neighbours_k(neighbours)
+    axis = sel.periodic_axis()
+    sshape, sdims = sel.sshape, list(mhw.sdims)
     w = resolve_weights(weights, mhw.coords, sdims, None, sdims, sshape)
-    view = mhw.compact_view()
-    C, cell_index, start, end = (view[k] for k in ("C", "cell_index", "start", "end"))
+    sel.view()
     bits = obj.weight_bits
     wq, unit = quantise_weights(w, bits)
-    t0, t1, dur, offsets, slot = selection_layout(obj, ids, object_of_row, start, end)
-    L = int(offsets[-1])
-    vox_off = voxel_offsets(start, end, slot)          # refuses V >= 2**31: nothing of size L or V exists yet
+    sel.layout()
+    L = sel.L
+    vox_off = voxel_offsets(sel.start, sel.end, sel.slot)     # refuses V >= 2**31: nothing of size L or V exists yet
     V = int(vox_off[-1])
     if L == 0:
-        got = {k: np.zeros(0, dtype=_DTYPES[k]) for k in STAGE_FIELDS}
+        got = sel.no_entries(_DTYPES)
     else:
-        axis = None if obj.periodic is None else mhw.sdims.index(obj.periodic)
-        nbr = neighbour_table(cell_index, sshape, 6 if K == 4 else 26, axis)
-        got = (_compute or track_parts_device)(start, end, slot, view["cell_of_row"].astype(np.int32), view["offsets"], nbr,
-                                               wq[cell_index], vox_off, t0, offsets)
-    f = {k: np.ascontiguousarray(got[k], dtype=_DTYPES[k]) for k in STAGE_FIELDS}
-    if any(f[k].shape != (L,) for k in STAGE_FIELDS):
-        raise XmhwException(f"track parts stage returned arrays that do not fit {L} entries")
+        nbr = neighbour_table(sel.cell_index, sshape, 6 if K == 4 else 26, axis)
+        got = (_compute or track_parts_device)(sel.start, sel.end, sel.slot, sel.cell_of_row, sel.row_offsets, nbr,
+                                               wq[sel.cell_index], vox_off, sel.time_start, sel.offsets)
+    f = sel.stage_arrays(got, _DTYPES, "track parts")
     if L and f["n_parts"].min() < 1:
         raise XmhwException(f"{int((f['n_parts'] < 1).sum())} days of the selected objects hold no cell: obj does not belong "
                             "to mhw")
-    f.update(ids=ids, offsets=offsets, time_start=t0, time_end=t1, duration=dur.astype(np.int32))
-    first = offsets[:-1]
-    f["pos"] = (np.arange(L, dtype=np.int64) - np.repeat(first - t0, dur)).astype(np.int32)
+    f.update(sel.common_fields(), pos=sel.pos())
     f["area_largest"] = f["area_largest_q"] * unit
-    if m:
-        pmax = np.maximum.reduceat(f["n_parts"], first)
-        at = np.where(f["n_parts"] == np.repeat(pmax, dur), np.arange(L, dtype=np.int64), L)
-        f["n_parts_max"] = pmax.astype(np.int32)
-        f["pos_n_parts_max"] = (np.minimum.reduceat(at, first) - first + t0).astype(np.int32)
-        f["days_split"] = np.add.reduceat((f["n_parts"] > 1).astype(np.int32), first).astype(np.int32)
-    else:
-        f["n_parts_max"] = f["pos_n_parts_max"] = f["days_split"] = np.zeros(0, dtype=np.int32)
+    f["n_parts_max"], f["pos_n_parts_max"] = sel.first_max(f["n_parts"])
+    f["days_split"] = sel.count_days(f["n_parts"] > 1)
     attrs = {"weights": weights_label(weights)}
     return TrackPartsDataset(f, mhw.time, mhw.sdims, sshape, K, obj.periodic, bits, unit, V, attrs)

@@ -57,18 +57,18 @@ behind track_shape_device().
 """
 import numpy as np
 
-from ._lib import hip
-from .detect import EventDataset
-from .device import DeviceScope, as_xmhw_errors
 from .exception import XmhwException
 from .objects import _DIAGONAL
-from .tracks import EARTH_RADIUS_KM, TrackDataset, _latlon, checked_selection, selection_layout
+from .track_common import ChainDataset, Selection, device_stage, stage_inputs
+from .tracks import EARTH_RADIUS_KM, TrackDataset, _latlon
 
 CLASSES = ("open", "coast", "border")                                   # XMHW_SHAPE_* order
 STAGE_FIELDS = ("edges_open", "edges_coast", "edges_border", "perimeter_open_q", "perimeter_coast_q", "perimeter_border_q",
                 "cells_edge")
 _DTYPES = dict(edges_open=np.int32, edges_coast=np.int32, edges_border=np.int32, perimeter_open_q=np.int64,
                perimeter_coast_q=np.int64, perimeter_border_q=np.int64, cells_edge=np.int32)
+_INPUTS = dict(start=np.int32, end=np.int32, slot=np.int32, cell=np.int32, row_offsets=np.int64, faces=np.int32, lq=np.int64,
+               time_start=np.int32, offsets=np.int64)
 FACE_COAST, FACE_BORDER, FACE_FOLDED = -1, -2, -3                       # XMHW_SHAPE_FACE_* (include/xmhw_amd.h)
 ENTRY_BYTES = 40
 
@@ -183,28 +183,17 @@ def track_shape_device(start, end, slot, cell, row_offsets, faces, lq, time_star
     object in the selection or -1; cell (n,) int32, the row's compact cell; row_offsets (C + 1,) int64, the rows of every
     cell; faces (C, 4) int32 (face_table()); lq (C, 4) int64; time_start (m,) int32 and offsets (m + 1,) int64 of the
     selection.  Returns a dict of STAGE_FIELDS, (L,) each, L = offsets[-1]."""
-    start = np.ascontiguousarray(start, dtype=np.int32)
-    end = np.ascontiguousarray(end, dtype=np.int32)
-    slot = np.ascontiguousarray(slot, dtype=np.int32)
-    cell = np.ascontiguousarray(cell, dtype=np.int32)
-    row_offsets = np.ascontiguousarray(row_offsets, dtype=np.int64)
-    faces = np.ascontiguousarray(faces, dtype=np.int32)
-    lq = np.ascontiguousarray(lq, dtype=np.int64)
-    time_start = np.ascontiguousarray(time_start, dtype=np.int32)
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    start, end, slot, cell, row_offsets, faces, lq, time_start, offsets = a = stage_inputs(
+        _INPUTS, start, end, slot, cell, row_offsets, faces, lq, time_start, offsets)
     n, m, C = start.shape[0], time_start.shape[0], faces.shape[0]
     L = int(offsets[-1])
     if L == 0 or n == 0 or m == 0:
         return {k: np.zeros(L, dtype=_DTYPES[k]) for k in STAGE_FIELDS}
     if faces.shape != (C, 4) or lq.shape != (C, 4) or row_offsets.shape != (C + 1,):
         raise XmhwException("the face table, the face lengths and the row offsets do not fit the cells")
-    if max(n, m, L, C) >= 1 << 31:
-        raise XmhwException(f"mhw_track_shape handles fewer than 2**31 rows, objects, series entries and cells, got {n}, {m}, "
-                            f"{L}, {C}: select fewer objects with ids=")
-    h = hip()
-    with DeviceScope() as s:
-        with as_xmhw_errors(also="Unsupported", hint="select fewer objects with ids="):
-            d = [s.upload(a) for a in (start, end, slot, cell, row_offsets, faces, lq, time_start, offsets)]
+    with device_stage(a, (n, m, L, C), f"mhw_track_shape handles fewer than 2**31 rows, objects, series entries and cells, got "
+                      f"{n}, {m}, {L}, {C}") as (h, s, d, launch):
+        with launch:
             d_edges, d_perim, d_cells, d_bad = s.alloc(4 * 3 * L), s.alloc(8 * 3 * L), s.alloc(4 * L), s.alloc(4)
             h.object_shape(d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, n, d[4].ptr, C, d[5].ptr, 4, d[6].ptr, d[7].ptr, d[8].ptr, m, L,
                            d_edges.ptr, d_perim.ptr, d_cells.ptr, d_bad.ptr)
@@ -220,7 +209,7 @@ def track_shape_device(start, end, slot, cell, row_offsets, faces, lq, time_star
     return out
 
 
-class TrackShapeDataset:
+class TrackShapeDataset(ChainDataset):
     """What mhw_track_shape() returns, as plain arrays, aligned with the TrackDataset of the same ``ids``: m objects, L =
     offsets[-1] entries; entry offsets[i] + (t - time_start[i]) belongs to object ids[i] on time position t.
 
@@ -241,39 +230,11 @@ class TrackShapeDataset:
     _SERIES = ("pos",) + STAGE_FIELDS + ("edges_exposed", "perimeter_q", "perimeter_open", "perimeter_coast", "perimeter_border",
                                          "perimeter", "coast_fraction")
     _PER_OBJECT = ("ids", "time_start", "time_end", "duration", "perimeter_max", "pos_perimeter_max", "days_coastal")
+    _ATTRS = ("periodic", "length_unit", "length_bits")
 
     def __init__(self, fields, time, sdims, sshape, periodic, length_bits, length_unit, attrs=None):
-        for k, v in fields.items():
-            setattr(self, k, v)
-        self.time, self.sdims, self.sshape = np.asarray(time), tuple(sdims), tuple(sshape)
+        super().__init__(fields, time, sdims, sshape, attrs)
         self.periodic, self.length_bits, self.length_unit = periodic, int(length_bits), float(length_unit)
-        self.attrs = dict(attrs or {})
-
-    @property
-    def n_selected(self):
-        return int(self.ids.shape[0])
-
-    time_stamps = EventDataset.time_stamps
-
-    def series(self, i):
-        """The slices of the i-th selected object: a dict of its series plus ``time``, the stamps of its days."""
-        i = int(i)
-        if not 0 <= i < self.n_selected:
-            raise XmhwException(f"series() takes a position in [0, {self.n_selected}), got {i}")
-        sl = slice(int(self.offsets[i]), int(self.offsets[i + 1]))
-        out = {k: getattr(self, k)[sl] for k in self._SERIES}
-        out["time"] = self.time_stamps(out["pos"])
-        return out
-
-    def to_xarray(self):
-        import xarray as xr
-        data = {k: (("obs",), getattr(self, k)) for k in self._SERIES}
-        data["time"] = (("obs",), self.time_stamps(self.pos))
-        for k in self._PER_OBJECT:
-            data["object_id" if k == "ids" else k] = (("track",), getattr(self, k))
-        data["offsets"] = (("track_edge",), self.offsets)
-        return xr.Dataset(data, attrs=dict(self.attrs, periodic=self.periodic or "", length_unit=self.length_unit,
-                                           length_bits=self.length_bits))
 
 
 def mhw_track_shape(mhw, obj, ids=None, lengths=None, _compute=None):
@@ -287,31 +248,25 @@ def mhw_track_shape(mhw, obj, ids=None, lengths=None, _compute=None):
     Returns a TrackShapeDataset (module docstring: the definition and the identities; class docstring: the fields).
     Every number of the stage is an integer sum: exact, and the same from run to run.  ``_compute``: a stand-in for
     track_shape_device() (host tests)."""
-    sshape, object_of_row, ids = checked_selection(mhw, obj, ids, "mhw_track_shape")
-    if obj.periodic is not None and obj.periodic not in mhw.sdims:
-        raise XmhwException(f"obj.periodic should be None or one of {mhw.sdims}, got {obj.periodic!r}: obj does not belong "
-                            "to mhw")
-    m = ids.shape[0]
+    sel = Selection(mhw, obj, ids, "mhw_track_shape")
+    axis = sel.periodic_axis()
+    sshape = sel.sshape
     ln = resolve_lengths(lengths, mhw.coords, mhw.sdims, sshape)      # every refusal of lengths= before anything of size L
-    view = mhw.compact_view()
-    C, cell_index, start, end = (view[k] for k in ("C", "cell_index", "start", "end"))
-    bits = length_bits(C)
+    sel.view()
+    bits = length_bits(sel.C)
     lq, unit = quantise_lengths(ln, bits)
-    t0, t1, dur, offsets, slot = selection_layout(obj, ids, object_of_row, start, end)
-    L = int(offsets[-1])
-    axis = None if obj.periodic is None else mhw.sdims.index(obj.periodic)
+    sel.layout()
+    L = sel.L
     if L == 0:
-        got = {k: np.zeros(0, dtype=_DTYPES[k]) for k in STAGE_FIELDS}
+        got = sel.no_entries(_DTYPES)
     else:
-        faces = face_table(cell_index, sshape, axis)
-        got = (_compute or track_shape_device)(start, end, slot, view["cell_of_row"].astype(np.int32), view["offsets"], faces,
-                                               lq.reshape(-1, 4)[cell_index], t0, offsets)
+        faces = face_table(sel.cell_index, sshape, axis)
+        got = (_compute or track_shape_device)(sel.start, sel.end, sel.slot, sel.cell_of_row, sel.row_offsets, faces,
+                                               lq.reshape(-1, 4)[sel.cell_index], sel.time_start, sel.offsets)
     try:
-        f = {k: np.ascontiguousarray(got[k], dtype=_DTYPES[k]) for k in STAGE_FIELDS}
+        f = sel.stage_arrays(got, _DTYPES, "track shape")
     except (KeyError, TypeError, ValueError):
         raise XmhwException(f"track shape stage should return the arrays {STAGE_FIELDS}") from None
-    if any(f[k].shape != (L,) for k in STAGE_FIELDS):
-        raise XmhwException(f"track shape stage returned arrays that do not fit {L} entries")
     exposed = f["edges_open"].astype(np.int64) + f["edges_coast"] + f["edges_border"]
     # an object has no empty day, and the outermost cells of a footprint along a dim that does not wrap have a face that
     # is not shared: two such faces per dim that does not wrap
@@ -319,9 +274,7 @@ def mhw_track_shape(mhw, obj, ids=None, lengths=None, _compute=None):
     if L and (exposed.min() < least or f["cells_edge"].min() < 1):
         raise XmhwException(f"{int(((exposed < least) | (f['cells_edge'] < 1)).sum())} days of the selected objects hold no "
                             "cell: obj does not belong to mhw")
-    f.update(ids=ids, offsets=offsets, time_start=t0, time_end=t1, duration=dur.astype(np.int32))
-    first = offsets[:-1]
-    f["pos"] = (np.arange(L, dtype=np.int64) - np.repeat(first - t0, dur)).astype(np.int32)
+    f.update(sel.common_fields(), pos=sel.pos())
     f["edges_exposed"] = exposed.astype(np.int32)
     f["perimeter_q"] = f["perimeter_open_q"] + f["perimeter_coast_q"] + f["perimeter_border_q"]
     for c in CLASSES:
@@ -330,15 +283,9 @@ def mhw_track_shape(mhw, obj, ids=None, lengths=None, _compute=None):
     wet = f["perimeter_open_q"] + f["perimeter_coast_q"]
     with np.errstate(divide="ignore", invalid="ignore"):
         f["coast_fraction"] = np.where(wet > 0, f["perimeter_coast_q"] / wet.astype(np.float64), np.nan)
-    if m:
-        pmax = np.maximum.reduceat(f["perimeter_q"], first)
-        at = np.where(f["perimeter_q"] == np.repeat(pmax, dur), np.arange(L, dtype=np.int64), L)
-        f["perimeter_max"] = pmax * unit
-        f["pos_perimeter_max"] = (np.minimum.reduceat(at, first) - first + t0).astype(np.int32)
-        f["days_coastal"] = np.add.reduceat((f["edges_coast"] > 0).astype(np.int32), first).astype(np.int32)
-    else:
-        f["perimeter_max"] = np.zeros(0, dtype=np.float64)
-        f["pos_perimeter_max"] = f["days_coastal"] = np.zeros(0, dtype=np.int32)
+    pmax, f["pos_perimeter_max"] = sel.first_max(f["perimeter_q"])
+    f["perimeter_max"] = pmax * unit
+    f["days_coastal"] = sel.count_days(f["edges_coast"] > 0)
     attrs = {"lengths": lengths_label(lengths)}
     return TrackShapeDataset(f, mhw.time, mhw.sdims, sshape, obj.periodic, bits, unit, attrs)
 

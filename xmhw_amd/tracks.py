@@ -33,16 +33,15 @@ integers); device side in csrc/kernels_tracks.hip behind tracks_device().
 """
 import numpy as np
 
-from ._lib import hip
-from .detect import EventDataset
-from .device import DeviceScope, as_xmhw_errors
 from .exception import XmhwException
 from .gridweights import LAT_NAMES, LON_NAMES, quantise_weights, resolve_weights, weights_label
-from .objects import ObjectDataset
+from .track_common import ChainDataset, Selection, device_stage, stage_inputs
 
 EARTH_RADIUS_KM = 6371.0088
 UNIT_BITS = 20
 _SQRT3 = 3.0 ** 0.5
+_INPUTS = dict(start=np.int32, end=np.int32, slot=np.int32, cell=np.int32, vec=np.int64, time_start=np.int32, offsets=np.int64)
+_STAGE = dict(n_cells=np.int32, sums=(np.int64, 4))
 
 
 def tracks_device(start, end, slot, cell, vec, time_start, offsets):
@@ -50,25 +49,14 @@ def tracks_device(start, end, slot, cell, vec, time_start, offsets):
     row's object in the selection or -1; cell (n,) int32, the row's compact cell; vec (4, C) int64, the addends of
     every cell; time_start (m,) int32 and offsets (m + 1,) int64 of the selection.  Returns ``n_cells`` (L,) int32 and
     ``sums`` (4, L) int64, L = offsets[-1]."""
-    start = np.ascontiguousarray(start, dtype=np.int32)
-    end = np.ascontiguousarray(end, dtype=np.int32)
-    slot = np.ascontiguousarray(slot, dtype=np.int32)
-    cell = np.ascontiguousarray(cell, dtype=np.int32)
-    vec = np.ascontiguousarray(vec, dtype=np.int64)
-    time_start = np.ascontiguousarray(time_start, dtype=np.int32)
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    start, end, slot, cell, vec, time_start, offsets = a = stage_inputs(_INPUTS, start, end, slot, cell, vec, time_start, offsets)
     n, m, C = start.shape[0], time_start.shape[0], vec.shape[1]
     L = int(offsets[-1])
     if L == 0 or n == 0 or m == 0:
         return dict(n_cells=np.zeros(L, dtype=np.int32), sums=np.zeros((4, L), dtype=np.int64))
-    if max(n, m, L + 1) >= 1 << 31:
-        raise XmhwException(f"mhw_tracks handles fewer than 2**31 rows, objects and series entries, got {n}, {m}, "
-                            f"{L + 1}: select fewer objects with ids=")
-    h = hip()
-    with DeviceScope() as s:
-        with as_xmhw_errors(also="Unsupported", hint="select fewer objects with ids="):
-            d_start, d_end, d_slot, d_cell, d_vec, d_ts, d_off = (s.upload(a) for a in (start, end, slot, cell, vec,
-                                                                                        time_start, offsets))
+    with device_stage(a, (n, m, L + 1), f"mhw_tracks handles fewer than 2**31 rows, objects and series entries, got {n}, {m}, "
+                      f"{L + 1}") as (h, s, (d_start, d_end, d_slot, d_cell, d_vec, d_ts, d_off), launch):
+        with launch:
             d_cnt, d_sums, d_bad = s.alloc(4 * (L + 1)), s.alloc(8 * 4 * (L + 1)), s.alloc(4)
             h.object_tracks(d_start.ptr, d_end.ptr, n, d_slot.ptr, d_cell.ptr, C, d_vec.ptr, C, d_ts.ptr, d_off.ptr, m, L,
                             d_cnt.ptr, d_sums.ptr, L + 1, d_bad.ptr)
@@ -83,7 +71,7 @@ def tracks_device(start, end, slot, cell, vec, time_start, offsets):
     return dict(n_cells=np.ascontiguousarray(cnt[:L]), sums=np.ascontiguousarray(sums[:, :L]))
 
 
-class TrackDataset:
+class TrackDataset(ChainDataset):
     """What mhw_tracks() returns, as plain arrays.  m objects selected, L = offsets[-1] = the sum of their durations;
     entry offsets[i] + (t - time_start[i]) of a series belongs to object ids[i] on time position t.
 
@@ -109,31 +97,13 @@ class TrackDataset:
     mode "sphere" | "index", weight_bits, weight_unit, moment_bits (mb), n_ocean (C)."""
 
     def __init__(self, fields, time, sdims, sshape, mode, weight_bits, weight_unit, moment_bits, n_ocean, attrs=None):
-        for k, v in fields.items():
-            setattr(self, k, v)
-        self.time, self.sdims, self.sshape = np.asarray(time), tuple(sdims), tuple(sshape)
+        super().__init__(fields, time, sdims, sshape, attrs)
         self.mode, self.weight_bits, self.weight_unit = mode, int(weight_bits), float(weight_unit)
         self.moment_bits, self.n_ocean = int(moment_bits), int(n_ocean)
-        self.attrs = dict(attrs or {})
 
     _SERIES = ("pos", "n_cells", "area_q", "area", "mx", "my", "mz", "wsum", "lat", "lon", "ci", "cj")
     _PER_OBJECT = ("ids", "time_start", "time_end", "duration", "area_max_q", "area_max", "pos_area_max", "path_km")
-
-    @property
-    def n_selected(self):
-        return int(self.ids.shape[0])
-
-    time_stamps = EventDataset.time_stamps
-
-    def series(self, i):
-        """The slices of the i-th selected object: a dict of its series plus ``time``, the stamps of its days."""
-        i = int(i)
-        if not 0 <= i < self.n_selected:
-            raise XmhwException(f"series() takes a position in [0, {self.n_selected}), got {i}")
-        sl = slice(int(self.offsets[i]), int(self.offsets[i + 1]))
-        out = {k: getattr(self, k)[sl] for k in self._SERIES if getattr(self, k) is not None}
-        out["time"] = self.time_stamps(out["pos"])
-        return out
+    _ATTRS = ("mode", "weight_unit", "weight_bits", "moment_bits")
 
     def quantisation_bound(self):
         """(L,) float64: how far the centre computed from the integers can lie from the centre computed from the
@@ -164,17 +134,6 @@ class TrackDataset:
         out[ok] = np.degrees(np.arcsin(B[ok] / (M[ok] - B[ok])))
         out[np.isnan(self.lat)] = np.nan
         return out
-
-    def to_xarray(self):
-        import xarray as xr
-        data = {k: (("obs",), getattr(self, k)) for k in self._SERIES if getattr(self, k) is not None}
-        data["time"] = (("obs",), self.time_stamps(self.pos))
-        for k in self._PER_OBJECT:
-            if getattr(self, k) is not None:
-                data["object_id" if k == "ids" else k] = (("track",), getattr(self, k))
-        data["offsets"] = (("track_edge",), self.offsets)
-        return xr.Dataset(data, attrs=dict(self.attrs, mode=self.mode, weight_unit=self.weight_unit,
-                                           weight_bits=self.weight_bits, moment_bits=self.moment_bits))
 
 
 def _latlon(coords, sdims):
@@ -211,65 +170,6 @@ def moment_bits(weight_bits, n_ocean, index_extent=None):
     return int(min(int(weight_bits), 61 - ubits - int(n_ocean).bit_length()))
 
 
-def checked_selection(mhw, obj, ids, who):
-    """The checks every stage of the object chain makes of ``mhw``, ``obj`` and ``ids`` (``who``: the function's name
-    in the messages).  Returns (sshape, the object of every table row as int64, ids as (m,) int32)."""
-    if not isinstance(mhw, EventDataset):
-        raise XmhwException(f"{who} expects the EventDataset returned by xmhw_amd.detect()")
-    if not isinstance(obj, ObjectDataset):
-        raise XmhwException(f"{who} expects the ObjectDataset returned by xmhw_amd.mhw_objects()")
-    if mhw.point:
-        raise XmhwException(f"{who} needs a grid: a single-point series has no objects")
-    if len(mhw.sdims) != 2:
-        raise XmhwException(f"{who} handles two spatial dims, got {mhw.sdims}")
-    n = mhw.n_events
-    sshape = tuple(int(v) for v in mhw.sshape)
-    if np.asarray(obj.object).shape != (n,) or tuple(obj.sshape) != sshape:
-        raise XmhwException(f"obj.object should have one entry per table row ({n}) on the grid {sshape}: "
-                            "obj does not belong to mhw")
-    m_all = obj.n_objects
-    object_of_row = np.asarray(obj.object, dtype=np.int64)
-    if n and (object_of_row.min() < 0 or object_of_row.max() >= m_all):
-        raise XmhwException("obj.object holds ids outside [0, n_objects)")
-    if ids is None:
-        ids = np.arange(m_all, dtype=np.int32)
-    else:
-        ids = np.asarray(ids)
-        if ids.ndim != 1 or (ids.size and ids.dtype.kind not in "iu"):
-            raise XmhwException("ids should be None or a 1-D integer array of object ids")
-        ids = ids.astype(np.int64)
-        if ids.size and (ids.min() < 0 or ids.max() >= m_all):
-            raise XmhwException(f"ids should be in [0, {m_all})")
-        if np.unique(ids).shape[0] != ids.shape[0]:
-            raise XmhwException("ids should be distinct")
-        ids = ids.astype(np.int32)
-    return sshape, object_of_row, ids
-
-
-def selection_layout(obj, ids, object_of_row, start, end):
-    """The ragged layout of the selection ``ids`` and the rows that fill it: (time_start (m,) int32, time_end (m,) int32,
-    duration (m,) int64, offsets (m + 1,) int64, slot (n,) int32 = the position of every row's object in ``ids`` or -1)."""
-    m, m_all = ids.shape[0], obj.n_objects
-    # the selection: where its objects start, how long they live, which rows are theirs
-    t0 = np.ascontiguousarray(np.asarray(obj.time_start, dtype=np.int32)[ids])
-    t1 = np.ascontiguousarray(np.asarray(obj.time_end, dtype=np.int32)[ids])
-    dur = t1.astype(np.int64) - t0 + 1
-    if m and dur.min() < 1:
-        raise XmhwException("obj holds an object that ends before it starts")
-    offsets = np.concatenate([[0], np.cumsum(dur)]).astype(np.int64)
-    L = int(offsets[-1])
-    if L + 1 >= 1 << 31:
-        raise XmhwException(f"the series of the {m} selected objects hold {L} entries, 2**31 - 1 and more: select fewer "
-                            "objects with ids=")
-    position = np.full(m_all, -1, dtype=np.int32)
-    position[ids] = np.arange(m, dtype=np.int32)
-    slot = position[object_of_row]
-    sel = slot >= 0
-    if sel.any() and ((start[sel] < t0[slot[sel]]).any() or (end[sel] > t1[slot[sel]]).any()):
-        raise XmhwException("a table row lies outside the days of its object: obj does not belong to mhw")
-    return t0, t1, dur, offsets, slot
-
-
 def mhw_tracks(mhw, obj, ids=None, weights=None, _compute=None):
     """The daily series of the objects of mhw_objects(): cells, area and centre on every day of every object.
 
@@ -280,13 +180,13 @@ def mhw_tracks(mhw, obj, ids=None, weights=None, _compute=None):
 
     Returns a TrackDataset (module docstring: the definition; class docstring: the fields).  Every series is a sum
     of integers: exact, and the same from run to run.  ``_compute``: a stand-in for tracks_device() (host tests)."""
-    sshape, object_of_row, ids = checked_selection(mhw, obj, ids, "mhw_tracks")
-    m = ids.shape[0]
+    sel = Selection(mhw, obj, ids, "mhw_tracks")
+    sshape = sel.sshape
     N = int(np.prod(sshape, dtype=np.int64))
     sdims = list(mhw.sdims)
     w = resolve_weights(weights, mhw.coords, sdims, None, sdims, sshape)
-    view = mhw.compact_view()
-    C, cell_index, start, end = (view[k] for k in ("C", "cell_index", "start", "end"))
+    sel.view()
+    C, cell_index = sel.C, sel.cell_index
     names = _latlon(mhw.coords, sdims)
     mode = "sphere" if names else "index"
     if mode == "index" and obj.periodic is not None:
@@ -304,21 +204,15 @@ def mhw_tracks(mhw, obj, ids=None, weights=None, _compute=None):
     else:
         i, j = np.divmod(np.arange(N, dtype=np.int64), sshape[1])
         vec = np.stack([wq, wm * i, wm * j, wm])[:, cell_index]
-    t0, t1, dur, offsets, slot = selection_layout(obj, ids, object_of_row, start, end)
-    L = int(offsets[-1])
-    cell_of_row = view["cell_of_row"].astype(np.int32)
+    sel.layout()
+    L, offsets = sel.L, sel.offsets
     if L == 0:
-        got = dict(n_cells=np.zeros(0, dtype=np.int32), sums=np.zeros((4, 0), dtype=np.int64))
+        got = sel.no_entries(_STAGE)
     else:
-        got = (_compute or tracks_device)(start, end, slot, cell_of_row, vec, t0, offsets)
-    n_cells = np.ascontiguousarray(got["n_cells"], dtype=np.int32)
-    sums = np.ascontiguousarray(got["sums"], dtype=np.int64)
-    if n_cells.shape != (L,) or sums.shape != (4, L):
-        raise XmhwException(f"tracks stage returned arrays that do not fit {L} entries")
-    f = dict(ids=ids, offsets=offsets, time_start=t0, time_end=t1, duration=dur.astype(np.int32), n_cells=n_cells,
-             area_q=sums[0], mx=sums[1], my=sums[2])
-    first = offsets[:-1]
-    f["pos"] = (np.arange(L, dtype=np.int64) - np.repeat(first - t0, dur)).astype(np.int32)
+        got = (_compute or tracks_device)(sel.start, sel.end, sel.slot, sel.cell_of_row, vec, sel.time_start, offsets)
+    got = sel.stage_arrays(got, _STAGE, "tracks")
+    sums = got["sums"]
+    f = dict(sel.common_fields(), n_cells=got["n_cells"], area_q=sums[0], mx=sums[1], my=sums[2], pos=sel.pos())
     f["area"] = f["area_q"] * unit
     f.update(lat=None, lon=None, ci=None, cj=None, wsum=None, path_km=None)
     if names:
@@ -339,13 +233,7 @@ def mhw_tracks(mhw, obj, ids=None, weights=None, _compute=None):
             ws = f["wsum"].astype(np.float64)
             f["ci"] = np.where(ws > 0, f["mx"] / ws, np.nan)
             f["cj"] = np.where(ws > 0, f["my"] / ws, np.nan)
-    if m:
-        amax = np.maximum.reduceat(f["area_q"], first)
-        at = np.where(f["area_q"] == np.repeat(amax, dur), np.arange(L, dtype=np.int64), L)
-        f["area_max_q"] = amax
-        f["pos_area_max"] = (np.minimum.reduceat(at, first) - first + t0).astype(np.int32)
-    else:
-        f["area_max_q"], f["pos_area_max"] = np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int32)
+    f["area_max_q"], f["pos_area_max"] = sel.first_max(f["area_q"])
     f["area_max"] = f["area_max_q"] * unit
     attrs = {"weights": weights_label(weights)}
     return TrackDataset(f, mhw.time, mhw.sdims, sshape, mode, bits, unit, mb, C, attrs)
