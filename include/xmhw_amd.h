@@ -866,6 +866,59 @@ int xmhw_track_intensity_accumulate_f64(const double *ts_dev, int64_t T, int64_t
                                         int64_t *n_range_dev, int64_t *n_bad_dev, void *stream);
 int xmhw_track_intensity_finish(int64_t L, double *intensity_max_dev, void *stream);
 
+/* ---- mhw_days_by(): per-cell MHW days and intensity by class of time steps --------------------------- *
+ * The reduction over TIME that keeps the cell: xmhw_coverage_accumulate_* turned by ninety degrees.  Inputs are those
+ * of xmhw_coverage_accumulate_* plus class_of_t_host[T], one int32 class label per step in [-1, K): month, season,
+ * year, phase of a climate mode ...; -1 = the step counts nowhere.  A step t of cell c is IN AN EVENT iff detect()
+ * labels it (the walk of xmhw_events_from_bits on bits_dev; gap days of joined events included).  With x = the sample
+ * as float64 (negated when negate != 0), seas / thresh re-expanded by row_of_t_host:
+ *   a   = x - seas                                  (the expression of xmhw_event_stats_*)
+ *   cat = floor(1 + (x - thresh)/(thresh - seas))   (the per-step category of mhw_df())
+ * For every class k and cell c, over the in-event steps with class_of_t[t] == k:
+ *   days[k][0..3][c]      int32    steps with cat == 1, == 2, == 3, >= 4 (moderate, strong, severe, extreme)
+ *   days[k][4][c]         int32    all in-event steps (event)
+ *   days[k][5][c]         int32    n_valid: in-event steps whose a is not NaN and |a| < 2^7
+ *   isum_q[k][c]          int64    sum of rint(a * 2^XMHW_TRACK_INTENSITY_BITS) over the valid steps
+ *   intensity_max[k][c]   float64  max a over the valid steps, NaN if there are none
+ * An in-event step with a not NaN and |a| >= 2^7 (or infinite) is left out of n_valid, isum_q and intensity_max, is
+ * still counted in days[k][0..4][c], and is counted in *n_range_dev (int64; 0 for a series in the units of its
+ * climatology).  |isum_q| < 2^31 * 2^23: int64 cannot overflow.  intensity_max goes through the order-preserving 64-bit
+ * key and an integer atomic maximum (key 0 = none; -0.0 counts as 0.0).  Cells are the fastest axis of every output:
+ * days_dev is int32 [K][XMHW_CLASS_DAYS_CHANNELS][ldo], isum_q_dev int64 [K][ldo], intensity_max_dev float64 [K][ldo],
+ * ldo >= C; columns past C are never touched, and a slab addresses its columns by pointer offset, as with the
+ * climatologies.  Everything is an integer sum or a maximum: the result is exact and does not depend on the time
+ * blocks, the slabs, the launch geometry or the schedule.
+ *
+ *  1. xmhw_class_days_init zeroes columns 0..C-1 of the accumulators and the counter.
+ *  2. xmhw_class_days_accumulate_* handles one slab of C cells and ADDS into the accumulators: calls for consecutive
+ *     slabs follow each other on one stream without a read-back.  bits_dev are the words of xmhw_exceed_bits_* for the
+ *     same slab (ldb >= C); the in-event bitmap lives in the stream's scratch buffer, as in xmhw_coverage_accumulate_*.
+ *     Lane = cell, workgroup = 256 cells x a block of steps; a lane keeps the addends of the current class in
+ *     registers and issues integer atomics without a return value when the class changes and at the end of its block.
+ *  3. xmhw_class_days_finish turns the keys into float64.
+ * All three are asynchronous on `stream`; nothing is launched for C == 0.  K < 1 or K > XMHW_CLASS_DAYS_MAX_CLASSES:
+ * XMHW_ERR_UNSUPPORTED, before anything is touched.  T or C of 2^31 and more: XMHW_ERR_UNSUPPORTED.  A label outside
+ * [-1, K): XMHW_ERR_INVALID, checked on the host copy before any launch.  xmhw_set_class_days_block (process-wide;
+ * tests and measurements): the steps a workgroup takes per block, 0 = automatic.  Same results for every value.   */
+#define XMHW_CLASS_DAYS_MAX_CLASSES 1024
+#define XMHW_CLASS_DAYS_CHANNELS 6
+int xmhw_set_class_days_block(int32_t steps);
+int xmhw_class_days_init(int32_t K, int64_t C, int32_t *days_dev, int64_t *isum_q_dev, double *intensity_max_dev,
+                         int64_t ldo, int64_t *n_range_dev, void *stream);
+int xmhw_class_days_accumulate_f32(const float *ts_dev, int64_t T, int64_t C, int64_t ld, const double *seas_dev,
+                                   const double *thresh_dev, int64_t ldc, const int32_t *row_of_t_host,
+                                   int32_t negate, const uint64_t *bits_dev, int64_t ldb, int32_t min_duration,
+                                   int32_t join_gaps, int32_t max_gap, const int32_t *class_of_t_host, int32_t K,
+                                   int32_t *days_dev, int64_t *isum_q_dev, double *intensity_max_dev, int64_t ldo,
+                                   int64_t *n_range_dev, void *stream);
+int xmhw_class_days_accumulate_f64(const double *ts_dev, int64_t T, int64_t C, int64_t ld, const double *seas_dev,
+                                   const double *thresh_dev, int64_t ldc, const int32_t *row_of_t_host,
+                                   int32_t negate, const uint64_t *bits_dev, int64_t ldb, int32_t min_duration,
+                                   int32_t join_gaps, int32_t max_gap, const int32_t *class_of_t_host, int32_t K,
+                                   int32_t *days_dev, int64_t *isum_q_dev, double *intensity_max_dev, int64_t ldo,
+                                   int64_t *n_range_dev, void *stream);
+int xmhw_class_days_finish(int32_t K, int64_t C, double *intensity_max_dev, int64_t ldo, void *stream);
+
 /* ---- the sharded path: cells split across the GPUs of a node, ONE gather at the end ------- *
  * Replaces the reference's collect, dask.compute(climls) + xr.concat(dim='cell')
  * (xmhw/xmhw.py:197, :210-211).  Cells are independent (xmhw/xmhw.py:184-196), so rank r runs the

@@ -961,6 +961,51 @@ int track_intensity_accumulate(const T* ts, int64_t Tn, int64_t n, int64_t ld, c
     return XMHW_OK;
 }
 
+static std::atomic<int> g_class_days_block{0};   // steps a workgroup takes per block, 0 = automatic (xmhw_set_class_days_block)
+
+static int class_days_check_k(int32_t K) {
+    if (K < 1 || K > xmhw::kClassDaysMaxClasses)
+        return fail(XMHW_ERR_UNSUPPORTED, "class_days: K must be in [1, " + std::to_string(xmhw::kClassDaysMaxClasses) + "]");
+    return XMHW_OK;
+}
+
+template <typename T>
+int class_days_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* seas, const double* thresh,
+                          int64_t ldc, const int32_t* row_of_t, int32_t negate, const uint64_t* bits, int64_t ldb,
+                          int32_t min_duration, int32_t join_gaps, int32_t max_gap, const int32_t* class_of_t, int32_t K,
+                          int32_t* days, int64_t* isum_q, double* intensity_max, int64_t ldo, int64_t* n_range,
+                          void* stream) {
+    if (class_days_check_k(K) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (Tn > 0x7FFFFFFFll || C > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "class_days: 2^31 steps or cells and more");
+    if (Tn <= 0 || C < 0 || ld < C || ldc < C || ldb < C || ldo < C) return fail(XMHW_ERR_INVALID, "bad T/C/ld/ldc/ldb/ldo");
+    if (min_duration < 1 || max_gap < 0) return fail(XMHW_ERR_INVALID, "bad minDuration/maxGap");
+    if (!class_of_t) return fail(XMHW_ERR_INVALID, "NULL class_of_t");
+    for (int64_t t = 0; t < Tn; ++t)
+        if (class_of_t[t] < -1 || class_of_t[t] >= K) return fail(XMHW_ERR_INVALID, "class_of_t outside [-1, K)");
+    if (C == 0) return XMHW_OK;
+    if (!ts || !seas || !thresh || !row_of_t || !bits || !days || !isum_q || !intensity_max || !n_range)
+        return fail(XMHW_ERR_INVALID, "NULL buffer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipError_t e = hipSuccess;
+    const RowsRef rows = cached_rows(row_of_t, Tn, &e);
+    if (!rows) return hip_fail(e, "row table upload");
+    const RowsRef classes = cached_rows(class_of_t, Tn, &e);       // the same content-keyed cache: one more int32[T] table
+    if (!classes) return hip_fail(e, "class table upload");
+    // the per-day in-event bitmap lives in this stream's scratch buffer: (T + 63) / 64 words per cell
+    const int64_t W = (Tn + 63) / 64;
+    void* sp = nullptr;
+    ScratchRef scratch_keep;
+    e = scratch_get(st, sizeof(uint64_t) * static_cast<size_t>(W) * static_cast<size_t>(C), &sp, &scratch_keep);
+    if (e != hipSuccess) return hip_fail(e, "scratch allocation");
+    uint64_t* inev = static_cast<uint64_t*>(sp);
+    e = xmhw::launch_event_day_bits(bits, Tn, C, ldb, min_duration, join_gaps, max_gap, inev, C, st);
+    if (e != hipSuccess) return hip_fail(e, "event_day_bits launch");
+    e = xmhw::launch_class_days_accumulate<T>(ts, Tn, C, ld, seas, thresh, ldc, rows->d_rows, classes->d_rows, K, negate, inev,
+                                              C, g_class_days_block.load(), days, isum_q, intensity_max, ldo, n_range, st);
+    if (e != hipSuccess) return hip_fail(e, "class_days_accumulate launch");
+    return XMHW_OK;
+}
+
 template <typename T>
 int event_stats_sparse(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* seas, const double* thresh,
                        int64_t ldc, const int32_t* row_of_t, int32_t negate, int64_t n_events, double* table,
@@ -2117,6 +2162,48 @@ int xmhw_track_intensity_finish(int64_t L, double* intensity_max, void* stream) 
     if (!intensity_max) return fail(XMHW_ERR_INVALID, "NULL output buffer");
     hipError_t e = xmhw::launch_track_intensity_finish(L, intensity_max, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hip_fail(e, "track_intensity_finish launch");
+    return XMHW_OK;
+}
+
+int xmhw_set_class_days_block(int32_t steps) {
+    if (steps < 0) return fail(XMHW_ERR_INVALID, "steps must be >= 0");
+    g_class_days_block = steps;
+    return XMHW_OK;
+}
+int xmhw_class_days_init(int32_t K, int64_t C, int32_t* days, int64_t* isum_q, double* intensity_max, int64_t ldo,
+                         int64_t* n_range, void* stream) {
+    if (class_days_check_k(K) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (C > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "class_days: 2^31 cells and more");
+    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
+    if (!n_range || (C > 0 && (!days || !isum_q || !intensity_max))) return fail(XMHW_ERR_INVALID, "NULL output buffer");
+    hipError_t e = xmhw::launch_class_days_init(K, C, days, isum_q, intensity_max, ldo, n_range, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "class_days_init");
+    return XMHW_OK;
+}
+int xmhw_class_days_accumulate_f32(const float* ts, int64_t T, int64_t C, int64_t ld, const double* seas, const double* thresh,
+                                   int64_t ldc, const int32_t* row_of_t, int32_t negate, const uint64_t* bits, int64_t ldb,
+                                   int32_t min_duration, int32_t join_gaps, int32_t max_gap, const int32_t* class_of_t,
+                                   int32_t K, int32_t* days, int64_t* isum_q, double* intensity_max, int64_t ldo,
+                                   int64_t* n_range, void* stream) {
+    return class_days_accumulate<float>(ts, T, C, ld, seas, thresh, ldc, row_of_t, negate, bits, ldb, min_duration, join_gaps,
+                                        max_gap, class_of_t, K, days, isum_q, intensity_max, ldo, n_range, stream);
+}
+int xmhw_class_days_accumulate_f64(const double* ts, int64_t T, int64_t C, int64_t ld, const double* seas, const double* thresh,
+                                   int64_t ldc, const int32_t* row_of_t, int32_t negate, const uint64_t* bits, int64_t ldb,
+                                   int32_t min_duration, int32_t join_gaps, int32_t max_gap, const int32_t* class_of_t,
+                                   int32_t K, int32_t* days, int64_t* isum_q, double* intensity_max, int64_t ldo,
+                                   int64_t* n_range, void* stream) {
+    return class_days_accumulate<double>(ts, T, C, ld, seas, thresh, ldc, row_of_t, negate, bits, ldb, min_duration, join_gaps,
+                                         max_gap, class_of_t, K, days, isum_q, intensity_max, ldo, n_range, stream);
+}
+int xmhw_class_days_finish(int32_t K, int64_t C, double* intensity_max, int64_t ldo, void* stream) {
+    if (class_days_check_k(K) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (C > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "class_days: 2^31 cells and more");
+    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
+    if (C == 0) return XMHW_OK;
+    if (!intensity_max) return fail(XMHW_ERR_INVALID, "NULL output buffer");
+    hipError_t e = xmhw::launch_class_days_finish(K, C, intensity_max, ldo, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "class_days_finish launch");
     return XMHW_OK;
 }
 

@@ -385,6 +385,28 @@ hipError_t launch_track_intensity_accumulate(const T* ts, int64_t Tn, int64_t n,
                                              int32_t combine_runs, hipStream_t stream);
 hipError_t launch_track_intensity_finish(int64_t L, double* intensity_max, hipStream_t stream);
 
+// mhw_days_by() (kernels_class.hip): the reduction over TIME that keeps the cell.  For every class k < K of time steps
+// (class_of_t[t] in [-1, K), -1 = the step counts nowhere) and cell c, over the in-event steps of the bitmap inev
+// (launch_event_day_bits) with class_of_t[t] == k, class_days_accumulate ADDS to days[k][0..3][c] the steps of category
+// 1, 2, 3, >= 4, to days[k][4][c] all of them, to days[k][5][c] those with a valid anomaly a = x - seas (not NaN,
+// |a| < 2^7), to isum_q[k][c] the sum of rint(a * 2^kClassDaysBits) over the valid ones, and raises the 64-bit key of
+// their largest a kept in intensity_max[k][c] (launch_class_days_init zeroes them; launch_class_days_finish turns the keys
+// into float64, NaN for none).  Cells are the fastest axis, leading dimension ldo >= C.  *n_range counts the in-event
+// steps with a not NaN and |a| >= 2^7.  row_of_t and class_of_t are DEVICE arrays here.  block_steps: the steps a workgroup
+// takes per block, 0 = automatic; same results for every value.
+constexpr int kClassDaysMaxClasses = 1024;
+constexpr int kClassDaysChannels = 6;
+constexpr int kClassDaysBits = 16;
+hipError_t launch_class_days_init(int32_t K, int64_t C, int32_t* days, int64_t* isum_q, double* intensity_max, int64_t ldo,
+                                  int64_t* n_range, hipStream_t stream);
+template <typename T>
+hipError_t launch_class_days_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* seas,
+                                        const double* thresh, int64_t ldc, const int32_t* row_of_t,
+                                        const int32_t* class_of_t, int32_t K, int32_t negate, const uint64_t* inev,
+                                        int64_t ldi, int64_t block_steps, int32_t* days, int64_t* isum_q,
+                                        double* intensity_max, int64_t ldo, int64_t* n_range, hipStream_t stream);
+hipError_t launch_class_days_finish(int32_t K, int64_t C, double* intensity_max, int64_t ldo, hipStream_t stream);
+
 // file bytes -> samples (kernels_ingest.hip): raw_type = item size of the stored type (2 int16, 4 float32,
 // 8 float64), swap = the file is big-endian, optional scale/offset (CF packing) and fill value -> NaN
 hipError_t launch_encode_i16(const float* in, int64_t rows, int64_t cols, int64_t ld_in, int16_t* out, int64_t ld_out,

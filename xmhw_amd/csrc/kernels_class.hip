@@ -1,0 +1,203 @@
+// kernels_class.hip -- mhw_days_by(): per cell and per CLASS of time steps (month, season, year, phase of a climate
+// mode: class_of_t[t] in [-1, K), -1 = the step counts nowhere), the number of in-event steps by category and the
+// sum / maximum of their anomaly.  mhw_coverage()'s kernel turned by ninety degrees: reduce over time, keep the cell.
+// For every class k and cell c, over the in-event steps t (the bitmap of event_day_bits, kernels_coverage.hip) with
+// class_of_t[t] == k, x = the sample as float64 (negated for cold spells), a = x - seas[row(t)] (the expression of
+// event_stats), cat = floor(1 + (x - thresh) / (thresh - seas)):
+//   days[k][0..3][c]     steps with cat == 1, == 2, == 3, >= 4
+//   days[k][4][c]        all in-event steps
+//   days[k][5][c]        n_valid: in-event steps with a not NaN and |a| < 2^7
+//   isum_q[k][c]         sum of rint(a * 2^16) over the valid steps
+//   key[k][c]            the largest order-preserving key of a + 0.0 over the valid steps (device_common.h), 0 = none
+// A step with a not NaN and |a| >= 2^7 (or infinite) stays in days[k][0..4] and is counted in *n_range.
+//
+//   class_days_accumulate  lane = cell, consecutive lanes on consecutive cells (a wave reads 256 contiguous bytes of a
+//                     float32 row), a workgroup = 256 cells x a block of `tb` steps.  class_of_t[t] and row_of_t[t] are
+//                     uniform over the wave.  A lane keeps the eight addends of the CURRENT class in registers while the
+//                     class stays the same and flushes them when it changes and at the end of the block: calendar
+//                     classes come in runs of ~30 and more steps, so flushes are rare; a class that changes every step
+//                     flushes every step and is still exact.  Flushes are integer atomics without a return value, issued
+//                     for non-zero addends only, coalesced (cells are the fastest axis of every output).  The in-event
+//                     word of 64 steps is read once per word; only in-event lanes read their sample and climatology
+//                     rows; a step whose class is -1, or on which no lane of the wave is in an event, reads nothing.
+//                     Everything is an integer sum or a maximum: the result does not depend on the block length, the
+//                     slabs, the launch geometry or the schedule.  No kernel waits for another workgroup.
+//   class_days_finish      key -> float64 (NaN where no step had a value).
+#include "device_common.h"
+#include "kernels.h"
+
+namespace xmhw {
+
+namespace {
+
+constexpr int kCdThreads = 256;
+using u64 = unsigned long long;
+
+struct CdOut {
+    int32_t* days;                                   // [K][6][ldo]
+    u64 *isum, *key;                                 // [K][ldo]
+    int64_t ldo;
+    u64* n_range;
+};
+
+// the addends of one lane for the current class
+struct CdAcc {
+    int32_t n[kClassDaysChannels];
+    u64 is, key;
+    __device__ __forceinline__ void clear() {
+#pragma unroll
+        for (int j = 0; j < kClassDaysChannels; ++j) n[j] = 0;
+        is = 0;
+        key = 0;
+    }
+};
+
+__device__ __forceinline__ void flush(const CdOut& o, int32_t k, int64_t c, CdAcc& v) {
+    if (v.n[4] == 0) return;                         // every addend belongs to an in-event step
+    int32_t* d = o.days + (static_cast<int64_t>(k) * kClassDaysChannels) * o.ldo + c;
+#pragma unroll
+    for (int j = 0; j < kClassDaysChannels; ++j)
+        if (v.n[j]) atomicAdd(d + j * o.ldo, v.n[j]);
+    const int64_t p = static_cast<int64_t>(k) * o.ldo + c;
+    if (v.is) atomicAdd(o.isum + p, v.is);
+    if (v.key) atomicMax(o.key + p, v.key);
+    v.clear();
+}
+
+template <typename T>
+__global__ __launch_bounds__(kCdThreads) void class_days_accumulate(
+    const T* __restrict__ ts, int64_t Tn, int64_t C, int64_t ld, const double* __restrict__ seas,
+    const double* __restrict__ thresh, int64_t ldc, const int32_t* __restrict__ row_of_t,
+    const int32_t* __restrict__ class_of_t, int32_t K, int32_t negate, const uint64_t* __restrict__ inev, int64_t ldi,
+    int64_t tb, CdOut out) {
+    const int64_t c = static_cast<int64_t>(blockIdx.x) * kCdThreads + threadIdx.x;
+    const bool live = c < C;
+    const int64_t nblk = (Tn + tb - 1) / tb;
+    CdAcc v;
+    v.clear();
+    u64 n_range = 0;
+    for (int64_t blk = blockIdx.y; blk < nblk; blk += gridDim.y) {
+        const int64_t t0 = blk * tb;
+        const int64_t t1 = Tn - t0 > tb ? t0 + tb : Tn;
+        int32_t kcur = -1;                           // the class the addends belong to (uniform over the wave)
+        int64_t wi = -1;
+        uint64_t word = 0;
+        for (int64_t t = t0; t < t1; ++t) {
+            const int32_t k = class_of_t[t];
+            if (k < 0 || k >= K) continue;           // counts nowhere (labels are checked on the host): reads nothing
+            if ((t >> 6) != wi) {
+                wi = t >> 6;
+                word = live ? inev[wi * ldi + c] : 0;
+            }
+            const bool ev = (word >> (t & 63)) & 1;
+            if (__ballot(ev) == 0) continue;         // uniform over the wave: the row of samples is not read
+            if (k != kcur) {
+                if (kcur >= 0) flush(out, kcur, c, v);
+                kcur = k;
+            }
+            if (!ev) continue;
+            const int64_t r = row_of_t[t];
+            double x = static_cast<double>(ts[t * ld + c]);
+            if (negate) x = -x;
+            const double se = seas[r * ldc + c], th = thresh[r * ldc + c];
+            const double a = x - se;
+            const double cat = floor(1.0 + (x - th) / (th - se));           // NaN compares false everywhere
+            v.n[0] += cat == 1.0;
+            v.n[1] += cat == 2.0;
+            v.n[2] += cat == 3.0;
+            v.n[3] += cat >= 4.0;
+            v.n[4] += 1;
+            if (a == a) {
+                if (!(fabs(a) < 128.0)) {
+                    ++n_range;
+                } else {
+                    v.n[5] += 1;
+                    v.is += static_cast<u64>(static_cast<int64_t>(rint(a * 65536.0)));
+                    const u64 key = f64_key(a + 0.0);                       // -0.0 counts as 0.0
+                    v.key = key > v.key ? key : v.key;
+                }
+            }
+        }
+        if (kcur >= 0) flush(out, kcur, c, v);
+    }
+    if (n_range) atomicAdd(out.n_range, n_range);
+}
+
+__global__ __launch_bounds__(kCdThreads) void class_days_finish(int32_t K, int64_t C, int64_t ldo, u64* __restrict__ key) {
+    const int64_t c = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    for (int32_t k = blockIdx.y; k < K; k += gridDim.y) {
+        const int64_t p = static_cast<int64_t>(k) * ldo + c;
+        const u64 q = key[p];
+        const double v = q ? key_f64(q) : make_nan();
+        key[p] = static_cast<u64>(__double_as_longlong(v));
+    }
+}
+
+hipError_t zero_rows(void* p, size_t item, int64_t rows, int64_t C, int64_t ldo, hipStream_t stream) {
+    if (rows <= 0 || C <= 0) return hipSuccess;
+    return ldo == C ? hipMemsetAsync(p, 0, item * static_cast<size_t>(rows) * static_cast<size_t>(C), stream)
+                    : hipMemset2DAsync(p, item * static_cast<size_t>(ldo), 0, item * static_cast<size_t>(C),
+                                       static_cast<size_t>(rows), stream);
+}
+
+}  // namespace
+
+hipError_t launch_class_days_init(int32_t K, int64_t C, int32_t* days, int64_t* isum_q, double* intensity_max, int64_t ldo,
+                                  int64_t* n_range, hipStream_t stream) {
+    hipError_t e = hipMemsetAsync(n_range, 0, sizeof(int64_t), stream);
+    if (e == hipSuccess) e = zero_rows(days, sizeof(int32_t), static_cast<int64_t>(K) * kClassDaysChannels, C, ldo, stream);
+    if (e == hipSuccess) e = zero_rows(isum_q, sizeof(int64_t), K, C, ldo, stream);
+    if (e == hipSuccess) e = zero_rows(intensity_max, sizeof(double), K, C, ldo, stream);      // key 0: no value yet
+    return e;
+}
+
+int64_t class_days_auto_block(int64_t Tn, int64_t C) {
+    // Long blocks keep the flushes rare; a slab too small to fill the chip with one block per 256 cells splits the
+    // time axis until about 2048 workgroups exist, in blocks of whole 64-step words and of 256 steps at least.
+    const int64_t gx = (C + kCdThreads - 1) / kCdThreads;
+    int64_t nblk = (2048 + gx - 1) / gx;
+    const int64_t most = (Tn + 255) / 256;
+    if (nblk > most) nblk = most;
+    if (nblk < 1) nblk = 1;
+    const int64_t tb = (Tn + nblk - 1) / nblk;
+    return (tb + 63) / 64 * 64;
+}
+
+template <typename T>
+hipError_t launch_class_days_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* seas,
+                                        const double* thresh, int64_t ldc, const int32_t* row_of_t,
+                                        const int32_t* class_of_t, int32_t K, int32_t negate, const uint64_t* inev,
+                                        int64_t ldi, int64_t block_steps, int32_t* days, int64_t* isum_q,
+                                        double* intensity_max, int64_t ldo, int64_t* n_range, hipStream_t stream) {
+    if (C <= 0 || Tn <= 0 || K <= 0) return hipSuccess;
+    const int64_t tb = block_steps > 0 ? block_steps : class_days_auto_block(Tn, C);
+    const CdOut out{days, reinterpret_cast<u64*>(isum_q), reinterpret_cast<u64*>(intensity_max), ldo,
+                    reinterpret_cast<u64*>(n_range)};
+    const int64_t gx = (C + kCdThreads - 1) / kCdThreads;
+    int64_t gy = (Tn + tb - 1) / tb;
+    if (gy > 65535) gy = 65535;                      // the kernel strides over the blocks
+    hipLaunchKernelGGL(class_days_accumulate<T>, dim3(static_cast<unsigned>(gx), static_cast<unsigned>(gy)),
+                       dim3(kCdThreads), 0, stream, ts, Tn, C, ld, seas, thresh, ldc, row_of_t, class_of_t, K, negate, inev,
+                       ldi, tb, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_class_days_finish(int32_t K, int64_t C, double* intensity_max, int64_t ldo, hipStream_t stream) {
+    if (K <= 0 || C <= 0) return hipSuccess;
+    const int64_t gx = (C + kCdThreads - 1) / kCdThreads;
+    hipLaunchKernelGGL(class_days_finish, dim3(static_cast<unsigned>(gx), static_cast<unsigned>(K < 1024 ? K : 1024)),
+                       dim3(kCdThreads), 0, stream, K, C, ldo, reinterpret_cast<u64*>(intensity_max));
+    return hipGetLastError();
+}
+
+template hipError_t launch_class_days_accumulate<float>(const float*, int64_t, int64_t, int64_t, const double*,
+                                                        const double*, int64_t, const int32_t*, const int32_t*, int32_t,
+                                                        int32_t, const uint64_t*, int64_t, int64_t, int32_t*, int64_t*,
+                                                        double*, int64_t, int64_t*, hipStream_t);
+template hipError_t launch_class_days_accumulate<double>(const double*, int64_t, int64_t, int64_t, const double*,
+                                                         const double*, int64_t, const int32_t*, const int32_t*, int32_t,
+                                                         int32_t, const uint64_t*, int64_t, int64_t, int32_t*, int64_t*,
+                                                         double*, int64_t, int64_t*, hipStream_t);
+
+}  // namespace xmhw

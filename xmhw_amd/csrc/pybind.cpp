@@ -710,6 +710,44 @@ PYBIND11_MODULE(_xmhw_hip, m) {
     m.def("track_intensity_finish", [](int64_t L, uintptr_t intensity_max, uintptr_t stream) {
         check(xmhw_track_intensity_finish(L, static_cast<double*>(vp(intensity_max)), vp(stream)));
     }, py::arg("L"), py::arg("intensity_max"), py::arg("stream") = 0);
+    m.attr("CLASS_DAYS_MAX_CLASSES") = XMHW_CLASS_DAYS_MAX_CLASSES;
+    m.attr("CLASS_DAYS_CHANNELS") = XMHW_CLASS_DAYS_CHANNELS;
+    m.def("set_class_days_block", [](int steps) { check(xmhw_set_class_days_block(steps)); }, py::arg("steps"));
+    m.def("class_days_init", [](int32_t K, int64_t C, uintptr_t days, uintptr_t isum_q, uintptr_t intensity_max, int64_t ldo,
+                                uintptr_t n_range, uintptr_t stream) {
+        check(xmhw_class_days_init(K, C, static_cast<int32_t*>(vp(days)), static_cast<int64_t*>(vp(isum_q)),
+                                   static_cast<double*>(vp(intensity_max)), ldo, static_cast<int64_t*>(vp(n_range)), vp(stream)));
+    }, py::arg("K"), py::arg("C"), py::arg("days"), py::arg("isum_q"), py::arg("intensity_max"), py::arg("ldo"),
+       py::arg("n_range"), py::arg("stream") = 0);
+    m.def("class_days_accumulate", [](uintptr_t ts, int itemsize, int64_t T, int64_t C, int64_t ld, uintptr_t seas,
+                                      uintptr_t thresh, int64_t ldc, i32arr row_of_t, int negate, uintptr_t bits, int64_t ldb,
+                                      int min_duration, int join_gaps, int max_gap, i32arr class_of_t, int32_t K,
+                                      uintptr_t days, uintptr_t isum_q, uintptr_t intensity_max, int64_t ldo,
+                                      uintptr_t n_range, uintptr_t stream) {
+        if (row_of_t.size() != T) throw InvalidError("row_of_t length must equal T");
+        if (class_of_t.size() != T) throw InvalidError("class_of_t length must equal T");
+        if (itemsize != 4 && itemsize != 8) throw InvalidError("itemsize must be 4 or 8");
+        py::gil_scoped_release r;
+        const auto f64 = [](uintptr_t p) { return static_cast<double*>(vp(p)); };
+        if (itemsize == 4)
+            check(xmhw_class_days_accumulate_f32(static_cast<const float*>(vp(ts)), T, C, ld, f64(seas), f64(thresh), ldc,
+                                                 row_of_t.data(), negate, static_cast<const uint64_t*>(vp(bits)), ldb,
+                                                 min_duration, join_gaps, max_gap, class_of_t.data(), K,
+                                                 static_cast<int32_t*>(vp(days)), static_cast<int64_t*>(vp(isum_q)),
+                                                 f64(intensity_max), ldo, static_cast<int64_t*>(vp(n_range)), vp(stream)));
+        else
+            check(xmhw_class_days_accumulate_f64(f64(ts), T, C, ld, f64(seas), f64(thresh), ldc, row_of_t.data(), negate,
+                                                 static_cast<const uint64_t*>(vp(bits)), ldb, min_duration, join_gaps, max_gap,
+                                                 class_of_t.data(), K, static_cast<int32_t*>(vp(days)),
+                                                 static_cast<int64_t*>(vp(isum_q)), f64(intensity_max), ldo,
+                                                 static_cast<int64_t*>(vp(n_range)), vp(stream)));
+    }, py::arg("ts"), py::arg("itemsize"), py::arg("T"), py::arg("C"), py::arg("ld"), py::arg("seas"), py::arg("thresh"),
+       py::arg("ldc"), py::arg("row_of_t"), py::arg("negate"), py::arg("bits"), py::arg("ldb"), py::arg("min_duration"),
+       py::arg("join_gaps"), py::arg("max_gap"), py::arg("class_of_t"), py::arg("K"), py::arg("days"), py::arg("isum_q"),
+       py::arg("intensity_max"), py::arg("ldo"), py::arg("n_range"), py::arg("stream") = 0);
+    m.def("class_days_finish", [](int32_t K, int64_t C, uintptr_t intensity_max, int64_t ldo, uintptr_t stream) {
+        check(xmhw_class_days_finish(K, C, static_cast<double*>(vp(intensity_max)), ldo, vp(stream)));
+    }, py::arg("K"), py::arg("C"), py::arg("intensity_max"), py::arg("ldo"), py::arg("stream") = 0);
     m.def("block_trend_ols", [](uintptr_t y, int32_t nstat, int32_t nb, int64_t C, int64_t ld, uintptr_t x, uintptr_t tcrit,
                                 uintptr_t out, int64_t ldo, uintptr_t stream) {
         check(xmhw_block_trend_ols(static_cast<const double*>(vp(y)), nstat, nb, C, ld, static_cast<const double*>(vp(x)),

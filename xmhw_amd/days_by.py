@@ -1,0 +1,398 @@
+"""mhw_days_by(): per cell and per CLASS of time steps, how often the cell was in a heatwave, in which category, and how
+hot it was -- seasonality maps of MHW days (classes = months or seasons), days counted in the year they fall in and the
+highest category reached per year (Hobday et al. 2018, fig. 2), MHW occurrence by phase of a climate mode (Holbrook et
+al. 2019: El Nino / La Nina / neutral days, see classes_from_events()).  mhw_coverage() and region_series() sum ACROSS
+cells and keep the time axis; block_average(), mean_trend() and mhw_rank() reduce the event table and attribute a whole
+event to the year it starts in.  This is the reduction over TIME that keeps the cell, and it cannot come from the table:
+the per-step category and the anomaly are not constant along a row.  One streaming pass over the resident series, the
+climatology and the in-event bitmap (csrc/kernels_class.hip).
+
+The definition.  Inputs are those of mhw_coverage() plus ``class_of_t``: one int32 label per time step in [-1, K); -1
+means the step counts nowhere.  A step t of cell c is *in an event* iff detect() labels it (mhw_filter() + join_gaps();
+gap days of joined events included, exactly as in mhw_coverage()).  For each sample, with x = float64(ts[t, c]), negated
+under coldSpells, and the climatology rows of t:
+    a   = x - seas[row(t), c]                          (the expression of xmhw_event_stats_*)
+    cat = floor(1 + (x - thresh) / (thresh - seas))    (the per-step category of mhw_df())
+For every class k and cell c, over the in-event steps with class_of_t[t] == k:
+    days[k, 0..3, c] (int32)   steps with cat == 1, == 2, == 3, >= 4 (moderate, strong, severe, extreme)
+    days[k, 4, c]    (int32)   all in-event steps (event)
+    days[k, 5, c]    (int32)   n_valid: in-event steps whose a is not NaN and |a| < 2**7 (the rule of mhw_track_intensity())
+    isum_q[k, c]     (int64)   sum of rint(a * 2**16) over the valid steps        (INTENSITY_BITS = 16)
+    intensity_max[k, c] (float64)  max a over the valid steps, NaN if there are none (-0.0 counts as 0.0): an integer
+                     maximum of the order-preserving 64-bit key, exact and independent of the schedule.
+An in-event step with a not NaN and |a| >= 2**7 is left out of n_valid, isum_q and intensity_max, is still counted in
+days[k, 0..4, c], and is counted in n_range; mhw_days_by() raises if n_range > 0.  |isum_q| < 2**31 * 2**23: int64 cannot
+overflow.  Everything is an integer sum or a maximum, so the result does not depend on the time blocks, the slabs, the
+launch geometry or the schedule.
+
+Host side here (validation, class labels, slabs, land); device side in csrc/kernels_class.hip behind class_days_cells()
+(a compact host series) and class_days_grid() (a stacked grid, masked and compacted on the device slab by slab, as
+coverage_grid()).
+"""
+import numpy as np
+
+from . import calendar as cal
+from ._lib import hip
+from .api import GridSeries, _from_xarray, _is_xarray
+from .coverage import CATEGORIES, grid_layout
+from .device import DeviceScope, as_xmhw_errors
+from .exception import XmhwException
+
+MAX_CLASSES = 1024              # XMHW_CLASS_DAYS_MAX_CLASSES (include/xmhw_amd.h)
+CHANNELS = 6                    # XMHW_CLASS_DAYS_CHANNELS: CATEGORIES, then n_valid
+INTENSITY_BITS = 16             # XMHW_TRACK_INTENSITY_BITS
+RANGE_BITS = 7                  # |a| < 2**7
+NAMED_CLASSES = ("all", "month", "season", "year")
+_RANGE_TEXT = ("in-event samples lie 2**7 and more from their climatology (or are infinite): is the series in kelvin "
+               "and the climatology in degrees Celsius?")
+
+
+def _check_classes(T, classes, K):
+    classes = np.asarray(classes)
+    if classes.dtype.kind not in "iu":
+        raise XmhwException(f"classes should be an integer array, got {classes.dtype}")
+    if classes.shape != (T,):
+        raise XmhwException(f"classes should have one entry per time step ({T}), got shape {classes.shape}")
+    K = int(K)
+    if K < 1:
+        raise XmhwException("K should be >= 1")
+    if K > MAX_CLASSES:
+        raise XmhwException(f"mhw_days_by handles at most {MAX_CLASSES} classes, got {K}")
+    if T and (classes.min() < -1 or classes.max() >= K):
+        raise XmhwException("class labels should be in [-1, K)")
+    return np.ascontiguousarray(classes, dtype=np.int32), K
+
+
+class _Accumulators:
+    """The device accumulators of one call: days int32 (K, 6, C), isum_q int64 (K, C), intensity_max (K, C) used as the
+    key array, and the range counter.  Initialised; they live across the slabs, each slab adds into its own column range,
+    and they are read back once."""
+
+    def __init__(self, h, K, C):
+        self.h, self.K, self.C = h, K, C
+        n = max(K * C, 1)
+        self._scope = s = DeviceScope()
+        try:
+            self.days, self.isum, self.imax, self.count = s.alloc(4 * CHANNELS * n), s.alloc(8 * n), s.alloc(8 * n), s.alloc(8)
+            with as_xmhw_errors(also="Unsupported"):
+                h.class_days_init(K, C, self.days.ptr, self.isum.ptr, self.imax.ptr, C, self.count.ptr)
+        except BaseException:
+            s.free()
+            raise
+
+    def add_slab(self, d_ts, isz, T, n, ld, se_ptr, th_ptr, ldc, D, rows, neg, minDuration, joinGaps, maxGap, classes, k0):
+        """One slab of n cells already on the device, columns k0..k0+n-1 of the accumulators: exceedance bits, then the
+        reduction ADDS."""
+        W = (T + 63) // 64
+        with DeviceScope() as s:
+            d_bits = s.alloc(8 * W * n)
+            with as_xmhw_errors(also="Unsupported"):
+                self.h.exceed_bits(d_ts.ptr, isz, T, n, ld, th_ptr, ldc, D, rows, neg, d_bits.ptr, n)
+                self.h.class_days_accumulate(d_ts.ptr, isz, T, n, ld, se_ptr, th_ptr, ldc, rows, neg, d_bits.ptr, n,
+                                             int(minDuration), int(bool(joinGaps)), int(maxGap), classes, self.K,
+                                             self.days.ptr + 4 * k0, self.isum.ptr + 8 * k0, self.imax.ptr + 8 * k0, self.C,
+                                             self.count.ptr)
+            self.h.stream_sync(0)                       # d_bits is freed on the way out
+
+    def result(self):
+        K, C = self.K, self.C
+        with as_xmhw_errors(also="Unsupported"):
+            self.h.class_days_finish(K, C, self.imax.ptr, C)
+        self.h.stream_sync(0)
+        if C == 0:
+            return (np.zeros((K, CHANNELS, 0), np.int32), np.zeros((K, 0), np.int64), np.zeros((K, 0), np.float64)), 0
+        out = (self.days.to_array((K, CHANNELS, C), np.int32), self.isum.to_array((K, C), np.int64),
+               self.imax.to_array((K, C), np.float64))
+        return out, int(self.count.to_array((1,), np.int64)[0])
+
+    def free(self):
+        self._scope.free()
+
+
+def _report(n_range, counters):
+    if counters is not None:
+        counters["n_range"] = int(n_range)
+    elif n_range:
+        raise XmhwException(f"{int(n_range)} {_RANGE_TEXT}")
+
+
+def class_days_cells(ts, seas, thresh, doy, doys, classes, K, minDuration=5, joinGaps=True, maxGap=2, coldSpells=False,
+                     max_batch_bytes=64 << 30, pad=None, counters=None):
+    """The device stage for a dense (T, C) series (arguments as detect_front.detect_cells): classes (T,) int labels in
+    [-1, K).  Returns (days int32 (K, 6, C), isum_q int64 (K, C), intensity_max float64 (K, C)).  Cells go through the
+    device in batches below max_batch_bytes, as in coverage_cells(); the sums are integers, so the batch size does not
+    change a single bit.  Raises if a sample is out of range (module docstring); with ``counters`` (a dict) it stores
+    ``n_range`` there instead."""
+    from .detect_front import _check_inputs
+    ts, seas, thresh, rows = _check_inputs(ts, seas, thresh, doy, doys)
+    T, C = ts.shape
+    D = thresh.shape[0]
+    classes, K = _check_classes(T, classes, K)
+    h = hip()
+    isz = ts.dtype.itemsize
+    neg = int(bool(coldSpells))
+    per_cell = T * (isz + 1) + T // 4 + 2 * D * 8 + 64
+    batch = int(max(1, min(C, max_batch_bytes // max(per_cell, 1))))
+    acc = _Accumulators(h, K, C)
+    try:
+        for c0 in range(0, C, batch):
+            c1 = min(C, c0 + batch)
+            n = c1 - c0
+            with DeviceScope() as s:
+                d_ts = s.upload(np.ascontiguousarray(ts[:, c0:c1]))
+                if pad is not None:
+                    pad.apply(d_ts.ptr, isz, T, n)
+                d_se = s.upload(np.ascontiguousarray(seas[:, c0:c1]))
+                d_th = s.upload(np.ascontiguousarray(thresh[:, c0:c1]))
+                acc.add_slab(d_ts, isz, T, n, n, d_se.ptr, d_th.ptr, n, D, rows, neg, minDuration, joinGaps, maxGap, classes,
+                             c0)
+        out, n_range = acc.result()
+    finally:
+        acc.free()
+    _report(n_range, counters)
+    return out
+
+
+def class_days_grid(stacked, anynans, seas, thresh, doy, doys, classes, K, minDuration=5, joinGaps=True, maxGap=2,
+                    coldSpells=False, max_batch_bytes=None, clim_stacked=False, pad=None, counters=None):
+    """class_days_cells() for an UNCOMPACTED stacked host series (T, N), float or a packed int16 view, as coverage_grid():
+    the land mask and the compaction run on the device slab by slab, the climatologies are compacted there as well
+    (clim_stacked) and pair up with the series' survivors by position.  The accumulators live across the slabs and each
+    slab writes its own column range.  Returns (days, isum_q, intensity_max, keep[N]) over the ocean cells."""
+    from .detect_front import _check_inputs, _rows_as_they_are
+    from .device import _grid_batch, compact_columns, device_itemsize, is_packed, native_float
+    T, N = stacked.shape
+    if not is_packed(stacked):
+        stacked = np.ascontiguousarray(native_float(stacked))
+    seas, thresh = _rows_as_they_are(seas), _rows_as_they_are(thresh)
+    if seas.ndim != 2 or thresh.ndim != 2 or seas.shape[0] != thresh.shape[0]:
+        raise XmhwException("seas and thresh must be (D, cells) arrays")
+    D = thresh.shape[0]
+    sample_dtype = stacked.decoded_dtype if is_packed(stacked) else stacked.dtype
+    _, _, _, rows = _check_inputs(np.zeros((T, 1), dtype=sample_dtype), seas[:, :1], thresh[:, :1], doy, doys)
+    classes, K = _check_classes(T, classes, K)
+    h = hip()
+    isz = device_itemsize(stacked)
+    neg = int(bool(coldSpells))
+    keeps = []
+    acc = None
+    clim = DeviceScope()
+    k0 = 0
+    try:
+        if clim_stacked:
+            d_th, keep_th = compact_columns(thresh, 0, thresh.shape[1], anynans)
+            clim.adopt(d_th)
+            d_se, keep_se = compact_columns(seas, 0, seas.shape[1], anynans)
+            clim.adopt(d_se)
+            C, Cse = int(keep_th.sum()), int(keep_se.sum())
+            if C == 0 or Cse == 0:
+                raise XmhwException("All points of grid are either land or NaN")
+        else:
+            d_th, d_se = clim.upload(thresh), clim.upload(seas)
+            C, Cse = thresh.shape[1], seas.shape[1]
+        if C != Cse:
+            raise XmhwException(f"th and se do not have the same ocean cells: {C}, {Cse}")
+        acc = _Accumulators(h, K, C)
+        cb = _grid_batch(stacked, max_batch_bytes, per_cell_extra=6 * D * 8 + T // 4 + 64)
+        for lo in range(0, N, cb):
+            hi = min(N, lo + cb)
+            d_ts, keep = compact_columns(stacked, lo, hi, anynans)
+            keeps.append(keep)
+            n = int(keep.sum())
+            if d_ts is None:
+                continue
+            with DeviceScope() as s:
+                s.adopt(d_ts)
+                if pad is not None:
+                    pad.apply(d_ts.ptr, isz, T, n)
+                if k0 + n > C:
+                    raise XmhwException(f"temp has more ocean cells than th and se ({C})")
+                acc.add_slab(d_ts, isz, T, n, n, d_se.ptr + 8 * k0, d_th.ptr + 8 * k0, C, D, rows, neg, minDuration,
+                             joinGaps, maxGap, classes, k0)
+            k0 += n
+        keep = np.concatenate(keeps) if keeps else np.zeros(0, dtype=bool)
+        if not keep.any():
+            raise XmhwException("All points of grid are either land or NaN")
+        if k0 != C:
+            raise XmhwException(f"temp has {k0} ocean cells, th and se have {C}")
+        (days, isum, imax), n_range = acc.result()
+    finally:
+        if acc is not None:
+            acc.free()
+        clim.free()
+    _report(n_range, counters)
+    return days, isum, imax, keep
+
+
+def class_labels(classes, time):
+    """The ``classes`` argument as labels per time step: an integer array of length T as it is, or a named form taken from
+    a datetime64 time axis -- "all" (one class 0), "month" (1..12), "season" (DJF, MAM, JJA, SON = 0..3), "year" (the
+    calendar year)."""
+    time = np.asarray(time)
+    T = time.shape[0]
+    if isinstance(classes, str):
+        if classes not in NAMED_CLASSES:
+            raise XmhwException(f"classes should be an integer array or one of {NAMED_CLASSES}, got {classes!r}")
+        if classes == "all":
+            return np.zeros(T, dtype=np.int64)
+        if time.dtype.kind != "M":
+            raise XmhwException(f"classes={classes!r} needs a datetime64 time coordinate, got {time.dtype}: pass the class "
+                                "of every time step as an integer array instead")
+        year, month, _, _ = cal._fields(time)
+        if classes == "month":
+            return month.astype(np.int64)
+        if classes == "season":
+            return (month % 12) // 3
+        return year.astype(np.int64)
+    labels = np.asarray(classes)
+    if labels.dtype.kind not in "iu":
+        raise XmhwException(f"classes should be an integer array, got {labels.dtype}")
+    if labels.shape != (T,):
+        raise XmhwException(f"classes should have one entry per time step ({T}), got shape {labels.shape}")
+    return labels.astype(np.int64)
+
+
+def classes_from_events(T, *event_datasets):
+    """Class labels from the events of single-point series: class 0 everywhere, class i + 1 on the steps index_start ..
+    index_end of the i-th EventDataset; a later dataset wins where two overlap.  With the warm and the cold-spell
+    detect() of a Nino-3.4 ``region_series().series()`` this gives neutral / El Nino / La Nina days."""
+    from .detect import EventDataset
+    T = int(T)
+    out = np.zeros(T, dtype=np.int32)
+    for i, ev in enumerate(event_datasets):
+        if not isinstance(ev, EventDataset):
+            raise XmhwException("classes_from_events expects the EventDatasets returned by xmhw_amd.detect()")
+        if not ev.point:
+            raise XmhwException("classes_from_events expects events of single-point series (e.g. of region_series().series()), "
+                                "got a gridded dataset")
+        if np.asarray(ev.time).shape[0] != T:
+            raise XmhwException(f"event dataset {i} has {np.asarray(ev.time).shape[0]} time steps, expected {T}")
+        rows = ev.compact_view()
+        for s, e in zip(rows["start"], rows["end"]):
+            if e >= T:
+                raise XmhwException("index_end outside the time axis")
+            out[int(s):int(e) + 1] = i + 1
+    return out
+
+
+class ClassDaysDataset:
+    """What mhw_days_by() returns, as plain arrays over (klass, [category,] *spatial dims).
+
+    klass (K,) the class labels (sorted non-negative labels found), n_steps (K,) the time steps of each class;
+    category = coverage.CATEGORIES (moderate, strong, severe, extreme, event);
+    days int32 (K, 5, ...), n_valid int32 (K, ...), isum_q int64 (K, ...), intensity_max float64 (K, ...);
+    frequency = days[event] / n_steps; intensity_mean = isum_q / (n_valid * 2**16), NaN where n_valid == 0;
+    category_max int8 (K, ...), 0..4: the highest category with a non-zero day count (0: none).
+    Land: grid lines without an ocean cell are dropped, as in BlockDataset; float fields are NaN on the remaining land
+    cells, integer fields are 0 there and come with the boolean ``keep`` (...) mask of the ocean cells."""
+
+    def __init__(self, klass, n_steps, days, n_valid, isum_q, intensity_max, keep, sdims, coords, tdim="time", attrs=None):
+        self.klass, self.n_steps, self.category = np.asarray(klass), np.asarray(n_steps), CATEGORIES
+        self.days, self.n_valid, self.isum_q, self.intensity_max = days, n_valid, isum_q, intensity_max
+        self.keep, self.sdims, self.coords = keep, tuple(sdims), dict(coords)
+        self.tdim, self.attrs = tdim, dict(attrs or {})
+        bshape = (-1,) + (1,) * (days.ndim - 2)
+        land = ~np.broadcast_to(keep, n_valid.shape)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            self.frequency = days[:, 4].astype(np.float64) / self.n_steps.astype(np.float64).reshape(bshape)
+            self.intensity_mean = isum_q.astype(np.float64) / (n_valid.astype(np.float64) * float(1 << INTENSITY_BITS))
+        self.intensity_mean[n_valid == 0] = np.nan
+        self.frequency[land] = np.nan
+        cmax = np.zeros(n_valid.shape, dtype=np.int8)
+        for j in range(4):
+            cmax[days[:, j] > 0] = j + 1
+        self.category_max = cmax
+
+    @staticmethod
+    def quantisation_bound():
+        """Bound on |intensity_mean - the float64 mean of a over the valid steps| from the fixed point alone: every
+        rint(a * 2**16) / 2**16 is within 2**-17 of its a (the product by 2**16 is exact), so the exact ratio isum_q /
+        (n_valid * 2**16) is within 2**-17 of the true mean.  In float64, n_valid * 2**16 is exact, isum_q (below 2**54
+        in magnitude) converts with a relative error of 2**-53 at most, and the one division rounds by half an ulp: on
+        a mean below 2**7 that is less than 2**-46 + 2**-47.  2**-17 + 2**-45 covers all of it."""
+        return 2.0 ** -17 + 2.0 ** -45
+
+    def to_xarray(self):
+        import xarray as xr
+        cell = ("klass",) + self.sdims
+        return xr.Dataset(
+            {"days": (("klass", "category") + self.sdims, self.days), "n_valid": (cell, self.n_valid),
+             "isum_q": (cell, self.isum_q), "intensity_max": (cell, self.intensity_max),
+             "frequency": (cell, self.frequency), "intensity_mean": (cell, self.intensity_mean),
+             "category_max": (cell, self.category_max), "n_steps": (("klass",), self.n_steps),
+             "keep": (self.sdims, self.keep)},
+            coords=dict({"klass": self.klass, "category": list(CATEGORIES)}, **{d: self.coords[d] for d in self.sdims}),
+            attrs=self.attrs)
+
+
+def mhw_days_by(temp, th, se, classes="month", tdim="time", minDuration=5, joinGaps=True, maxGap=2, maxPadLength=None,
+                coldSpells=False, tstep=False, anynans=False, _compute=None, max_batch_bytes=None):
+    """Per cell and per class of time steps: MHW days by category, and the mean and maximum anomaly of those days.
+
+    ``temp``, ``th``, ``se`` and the options shared with detect() mean and validate what they do there and in
+    mhw_coverage() (same exceptions, land masking and positional pairing of series and climatology cells).
+    ``classes``: an integer array with one label per time step, or "all", "month" (1..12), "season" (DJF, MAM, JJA, SON
+    = 0..3) or "year", taken from a datetime64 time coordinate.  Negative labels count nowhere; the classes of the
+    result are the sorted non-negative labels found (at most MAX_CLASSES).  classes_from_events() builds the labels of
+    the phases of a climate mode from detect() on an index series.
+
+    Returns a ClassDaysDataset.  Raises if an in-event sample lies 2**7 and more from its climatology.  ``_compute``: a
+    stand-in for class_days_cells() (host tests)."""
+    from .detect import _alive_axes, _compress_grid, _detect
+    coords, coord_attrs, dims, point, sdims, sshape, N = grid_layout(temp, tdim)
+    time = np.asarray(coords[tdim])
+    T = time.shape[0]
+    labels = class_labels(classes, time)
+    found = np.unique(labels[labels >= 0])
+    K = max(int(found.shape[0]), 1)
+    if K > MAX_CLASSES:
+        raise XmhwException(f"mhw_days_by handles at most {MAX_CLASSES} classes, got {K}")
+    kid = np.where(labels >= 0, np.searchsorted(found, labels), -1).astype(np.int32)
+    n_steps = np.bincount(kid[kid >= 0], minlength=K).astype(np.int64)
+    got, counters = {}, {}
+
+    def on_cells(ts, sec, thc, doy, doys, minDuration, joinGaps, maxGap, coldSpells, intermediate, pad=None):
+        stage = _compute or class_days_cells
+        extra = {} if pad is None else {"pad": pad}
+        if max_batch_bytes is not None and _compute is None:
+            extra["max_batch_bytes"] = max_batch_bytes
+        got["out"] = stage(ts, sec, thc, doy, doys, kid, K, minDuration, joinGaps, maxGap, coldSpells, counters=counters,
+                           **extra)
+        return dict(table=np.zeros((0, 31)), offsets=np.zeros(ts.shape[1] + 1, dtype=np.int64), inter=None)
+
+    def on_grid(stacked, anynans_, sec, thc, doy, doys, minDuration, joinGaps, maxGap, coldSpells, intermediate,
+                clim_stacked=False, pad=None):
+        *out, keep = class_days_grid(stacked, anynans_, sec, thc, doy, doys, kid, K, minDuration, joinGaps, maxGap,
+                                     coldSpells, max_batch_bytes=max_batch_bytes, clim_stacked=clim_stacked, pad=pad,
+                                     counters=counters)
+        got["out"] = tuple(out)
+        return dict(table=np.zeros((0, 31)), offsets=np.zeros(int(keep.sum()) + 1, dtype=np.int64), inter=None, keep=keep)
+
+    series = GridSeries(temp.values, dims, coords, coord_attrs=coord_attrs) if _is_xarray(temp) else temp
+    as_series = lambda a: GridSeries(a.values, a.dims, _from_xarray(a)[0]) if _is_xarray(a) else a   # noqa: E731
+    mhw = _detect(series, as_series(th), as_series(se), on_cells, tdim, minDuration, joinGaps, maxGap, maxPadLength,
+                  coldSpells, False, anynans, tstep, grid_compute=None if _compute is not None else on_grid)
+    if counters.get("n_range", 0):
+        raise XmhwException(f"{counters['n_range']} {_RANGE_TEXT}")
+    keep = np.asarray(mhw.keep, dtype=bool)
+    C = int(keep.sum())
+    days6, isum, imax = (np.asarray(a) for a in got["out"])
+    if days6.shape != (K, CHANNELS, C) or isum.shape != (K, C) or imax.shape != (K, C):
+        raise XmhwException(f"class stage returned {days6.shape}, {isum.shape}, {imax.shape}, expected "
+                            f"{(K, CHANNELS, C)}, {(K, C)}, {(K, C)}")
+    klass = found if found.shape[0] else np.zeros(1, dtype=np.int64)
+    attrs = {"classes": classes if isinstance(classes, str) else "array", "xmhw_parameters": mhw.attrs["xmhw_parameters"]}
+    if point:
+        return ClassDaysDataset(klass, n_steps, days6[:, :5, 0].astype(np.int32), days6[:, 5, 0].astype(np.int32),
+                                isum[:, 0].astype(np.int64), imax[:, 0].astype(np.float64), np.array(True), (), {}, tdim, attrs)
+    alive = _alive_axes(keep, sshape)
+
+    def on_grid_shape(a, fill, dtype):
+        full = np.full(a.shape[:-1] + (N,), fill, dtype=dtype)
+        full[..., mhw.cell_index] = a
+        return np.ascontiguousarray(_compress_grid(full.reshape(a.shape[:-1] + tuple(sshape)), alive, a.ndim - 1))
+
+    out_coords = {d: np.asarray(coords[d])[m] for d, m in zip(sdims, alive)}
+    return ClassDaysDataset(klass, n_steps, on_grid_shape(days6[:, :5], 0, np.int32), on_grid_shape(days6[:, 5], 0, np.int32),
+                            on_grid_shape(isum, 0, np.int64), on_grid_shape(imax, np.nan, np.float64),
+                            _compress_grid(keep.reshape(sshape), alive, 0), sdims, out_coords, tdim, attrs)
