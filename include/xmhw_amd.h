@@ -147,7 +147,7 @@ int xmhw_plan_kernel_ms(xmhw_plan *plan, int32_t calls_back, float *ms);
 int xmhw_plan_narrowed(xmhw_plan *plan, int32_t *narrowed_out);
 int xmhw_plan_set_chunks(xmhw_plan *plan, int32_t nchunks); /* 0 = auto         */
 /* how many chunks of the doy axis a launch over C cells is cut into (the automatic choice or the forced one):
- * every workgroup walks D / nchunks rows with output + 2w warm-up rows (csrc/capi.cpp: auto_chunks)     */
+ * every workgroup walks D / nchunks rows with output + 2w warm-up rows (csrc/route.cpp: ring_chunks)    */
 int xmhw_plan_chunks_in_use(const xmhw_plan *plan, int64_t C, int32_t *nchunks);
 /* host copy of the ring kernel's step table for inspection:
  * table[nsteps][ntracks_padded] (see csrc/plan.h for the encoding)            */
@@ -233,6 +233,21 @@ int xmhw_plan_ring2_in_use(const xmhw_plan *plan, int32_t *variant);
  * 8 = the second-generation kernel on 8 lanes per cell (only with XMHW_RING3_F64=0), 12 = on 16 lanes per cell
  * (other records up to 96 tracks), or -1 (generic kernel).  w = 5.                              */
 int xmhw_plan_f64_mode(const xmhw_plan *plan, int32_t *variant);
+/* the whole route of one xmhw_clim_raw_f32 (elem_bytes 4) / _f64 (8) call with quantile q over C cells: what the
+ * entries above report, and what the call launches, come from this one answer.  Needs no device (like
+ * xmhw_plan_layout_in_use it assumes one that may run the sorted-list kernel).  out receives XMHW_ROUTE_WORDS values:
+ *   [0]  XMHW_OK, or XMHW_ERR_UNSUPPORTED: the call would be refused (no launches)
+ *   [1]  the number of launches (at most 3), queued in this order
+ *   [2 + 7 i ...], i < 3 (zeros past the last launch):
+ *        family (XMHW_ROUTE_*), layout (XMHW_LAYOUT_*; RING1 for the round-1 and generic kernels), lanes per cell,
+ *        tracks per lane, narrows (float64 samples read as float32 behind the probe; stops at the first lossy sample),
+ *        gated (runs only if the narrowing launch before it gave up), counters (takes the debug pass counters)
+ *   [23] chunks of the doy axis of the ring launches (xmhw_plan_chunks_in_use)
+ *   [24] pieces of the sorted-list kernel (xmhw_plan_sorted_info; 0: not instantiated for this plan)              */
+enum { XMHW_ROUTE_GENERIC = 0, XMHW_ROUTE_RING1 = 1, XMHW_ROUTE_RING2 = 2, XMHW_ROUTE_RING3 = 3, XMHW_ROUTE_RING4 = 4,
+       XMHW_ROUTE_SORTED = 5 };
+#define XMHW_ROUTE_WORDS 25
+int xmhw_plan_route(const xmhw_plan *plan, int32_t elem_bytes, double q, int64_t C, int32_t *out, int32_t n);
 
 /* ---- the hot path ------------------------------------------------------ *
  * xmhw_clim_raw_*: for every cell, the pooled linear-interpolated quantile

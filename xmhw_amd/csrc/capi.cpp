@@ -17,11 +17,11 @@
 #include <mutex>
 #include <new>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 #include "kernels.h"
 #include "plan.h"
+#include "route.h"
 
 namespace {
 
@@ -51,249 +51,54 @@ namespace {
     } while (0)
 
 constexpr int kSubs = 8;
-// the sorted-list kernel keeps the K largest keys of a row-list, K sized for the top tenth of the pool (four times a list's
-// average share): quantiles from here up -- and, mirrored (the K smallest keys: round 6), from 1 - that down.  In between a
-// list's share outgrows K and too many cell-rows would be recomputed: those calls run on the ring layout.
-constexpr double kSortedMinQ = 0.85;
-inline bool sorted_serves(double q) { return q >= kSortedMinQ || q <= 1.0 - kSortedMinQ; }
 
 }  // namespace
 
+// the plan's device arrays apart from the ring step tables: changed under the plan's mutex only; a call works on the copy
+// it took there
+struct PlanDevice {
+    int32_t* row_ptr = nullptr;             // generic kernel: CSR of centres per row
+    int32_t* centres = nullptr;
+    uint32_t* sflags = nullptr;             // host.step_flags()
+    xmhw::DevChunk* chunks = nullptr;       // ring chunks: one array, re-cut when the chunk count changes
+    int32_t nchunks = 0;
+    unsigned long long* stats = nullptr;    // debug: ring kernel pass counters (xmhw_plan_debug_stats)
+    uint32_t* narrow_flag = nullptr;        // float64 input: set when a sample is not float32-representable
+    // sorted-list kernel (kernels_sorted.hip): its table (2 lanes per cell), flags and chunks, which depend on the pieces
+    uint32_t* table_s = nullptr;
+    uint32_t* sflags_s = nullptr;
+    xmhw::DevSortedChunk* chunks_s = nullptr;
+    int32_t nchunks_s = 0;
+};
+
 struct xmhw_plan {
     xmhw::Plan host;
+    xmhw::RouteSettings settings = xmhw::route_defaults();
     // device state (lazy, per current device at first use)
     std::mutex mu;
     bool uploaded = false;
-    int32_t yps = 0;          // ring kernel years-per-lane (0: ring not available)
-    int32_t subs = 0;         // ... and its lanes per cell (8, or 16 for records of 49..96 tracks)
-    int32_t nchunks = 0;
-    uint32_t* d_table = nullptr;
-    int32_t yps2 = 0;         // second-generation float32 ring kernel (kernels_ring2.hip), 0: not available
-    int32_t subs2 = 0;        // ... and its lanes per cell (8, or 4 for variant 7)
-    int32_t ring2_variant = -2;   // -2: auto (0 or 7, whichever pads fewer tracks); -1: off (round-1 kernel); 0..7: see kernels_ring2.hip
-    uint32_t* d_table2 = nullptr;
-    uint32_t* d_sflags = nullptr;
-    int32_t yps64 = 0;        // 64-bit mode on 16 lanes per cell, short records: tracks per lane (1..3), 0: none
-    uint32_t* d_table64 = nullptr;   // ... and its step table
-    xmhw::DevChunk* d_chunks = nullptr;
-    int32_t* d_row_ptr = nullptr;
-    int32_t* d_centres = nullptr;
-    unsigned long long* d_stats = nullptr;  // debug: ring kernel pass counters (xmhw_plan_debug_stats)
-    uint32_t* d_tablex = nullptr;           // the 64-bit mode's own table (8 or 4 lanes) when the float32 layout is another one
-    int32_t ypsx = 0, subsx = 0;
-    uint32_t* d_narrow_flag = nullptr;      // float64 input: set when a sample is not float32-representable
-    bool narrowing = true;                  // xmhw_plan_set_narrowing
-    // sorted-list kernel (kernels_sorted.hip): its table (2 lanes per cell), the chunks of the regular rows it serves,
-    // the chunks of the other rows (they stay on the ring kernel), the bitmap of cell-rows it hands to the generic kernel
-    int32_t yps_s = 0;
-    uint32_t* d_table_s = nullptr;
-    xmhw::DevSortedChunk* d_chunks_s = nullptr;
-    uint32_t* d_sflags_s = nullptr;
-    xmhw::DevChunk* d_chunks_i = nullptr;
-    int32_t nchunks_s = 0, nchunks_i = 0;
-    int64_t sorted_pieces = -1;             // the number of pieces the sorted chunks were cut into
-    int32_t sorted_built = 0;               // chunks in d_chunks_s (nchunks_s = that, or 0 while the plan is not sorted-usable)
+    PlanDevice dev;
+    // ring step tables: (lanes per cell, tracks per lane) -> host.ring_table() on the device.  Filled on first use, kept
+    // until the plan is destroyed: a launch in flight never loses its table.
+    std::map<std::pair<int32_t, int32_t>, uint32_t*> tables;
+    int32_t chunks_cut = 0;                 // the chunk count dev.chunks were cut for
+    int32_t yps_s = 0;                      // sorted-list kernel: the tracks per lane and pieces its arrays were built for
+    int64_t sorted_pieces = -1;
     // optional timing of the main kernel of every raw-climatology call (xmhw_plan_set_timing): a ring of event pairs
     bool timing = false;
     hipEvent_t tev[32] = {};
     uint64_t tcalls = 0;
 
     ~xmhw_plan() {
-        if (d_stats) (void)hipFree(d_stats);
         for (hipEvent_t e : tev) if (e) (void)hipEventDestroy(e);
-        if (d_table_s) (void)hipFree(d_table_s);
-        if (d_chunks_s) (void)hipFree(d_chunks_s);
-        if (d_sflags_s) (void)hipFree(d_sflags_s);
-        if (d_chunks_i) (void)hipFree(d_chunks_i);
-        if (d_narrow_flag) (void)hipFree(d_narrow_flag);
-        if (d_tablex) (void)hipFree(d_tablex);
-        if (d_table) (void)hipFree(d_table);
-        if (d_table64) (void)hipFree(d_table64);
-        if (d_table2) (void)hipFree(d_table2);
-        if (d_sflags) (void)hipFree(d_sflags);
-        if (d_chunks) (void)hipFree(d_chunks);
-        if (d_row_ptr) (void)hipFree(d_row_ptr);
-        if (d_centres) (void)hipFree(d_centres);
+        for (auto& kv : tables) if (kv.second) (void)hipFree(kv.second);
+        for (void* p : std::initializer_list<void*>{dev.row_ptr, dev.centres, dev.sflags, dev.chunks, dev.stats,
+                                                    dev.narrow_flag, dev.table_s, dev.sflags_s, dev.chunks_s})
+            if (p) (void)hipFree(p);
     }
 };
 
 namespace {
-
-int32_t ring2_resolved(const xmhw_plan* p);
-int32_t ring2_legacy(const xmhw_plan* p);
-
-// float64 samples on the second-generation kernel's 64-bit mode: which layout, if any.  The float32 layout of
-// the plan (8 or 4 lanes per cell) as long as a lane holds at most 4 tracks (44 keys and their low words fit the
-// registers); otherwise, and for short records, 16 lanes per cell (variant 12, the table of the 16-lane rings).
-struct X64Choice { int32_t variant = -1, yps = 0; };
-X64Choice x64_choice(const xmhw_plan* p) {
-    static const bool on = [] { const char* v = std::getenv("XMHW_RING2_F64"); return !(v && v[0] == '0'); }();
-    X64Choice c;
-    if (!on || p->ring2_variant == -1) return c;
-    // 8 lanes per cell: low words in registers up to 4 tracks per lane (9..32 tracks), in LDS at 5 and 6 (33..48) ...
-    const int32_t y8 = xmhw::ring2_pick_yps(p->host.w, p->host.ntracks, 8);
-    static const bool lds_on = [] { const char* v = std::getenv("XMHW_RING2_F64_LDS"); return !(v && v[0] == '0'); }();
-    // (the third-generation kernel's 64-bit mode where both rings fit its registers: up to 5 tracks per lane = 9..40
-    // tracks, layout 20; XMHW_RING3_F64=0 keeps the second-generation kernel)
-    static const bool r3_on = [] { const char* v = std::getenv("XMHW_RING3_F64"); return !(v && v[0] == '0'); }();
-    // (13..20 tracks: the 4-lane layout of the float32 path, 16 cells per wave, on the plan's own table;
-    // XMHW_RING3_F64_LANES=8 keeps the 8-lane layout)
-    static const bool r3_4 = [] { const char* v = std::getenv("XMHW_RING3_F64_LANES"); return !(v && v[0] == '8'); }();
-    if (r3_on && r3_4) {
-        const int32_t y4 = xmhw::ring3_pick_yps(p->host.w, p->host.ntracks, 4);
-        if (y4 > 0 && xmhw::ring3_x64_supported(p->host.w, y4, 4)) {
-            c.variant = 21;
-            c.yps = y4;
-            return c;
-        }
-    }
-    if (r3_on && y8 > 0 && xmhw::ring3_pick_yps(p->host.w, p->host.ntracks, 8) == y8 &&
-        xmhw::ring3_x64_supported(p->host.w, y8, 8)) {
-        c.variant = 20;
-        c.yps = y8;
-        return c;
-    }
-    if (y8 > 0 && (y8 <= 4 || lds_on) && xmhw::ring2_x64_supported(p->host.w, y8, 8)) {
-        c.variant = 8;
-        c.yps = y8;
-        return c;
-    }
-    // ... 16 lanes per cell for longer and for very short records (the table of the 16-lane rings)
-    const int32_t y16 = xmhw::ring2_pick_yps(p->host.w, p->host.ntracks, 12);
-    // (its table: the plan's own ring2 table where the float32 layout is the same 16 lanes, the 16-lane table kept for
-    // the 64-bit mode otherwise)
-    if (y16 > 0 && y16 <= 6 && xmhw::ring2_x64_supported(p->host.w, y16, 12)) {
-        c.variant = 12;
-        c.yps = y16;
-    }
-    return c;
-}
-bool x64_usable(const xmhw_plan* p) { return x64_choice(p).variant >= 0; }
-
-int32_t resolve_kernel(const xmhw_plan* p, int elem_bytes) {
-    if (p->host.kernel_choice == XMHW_KERNEL_GENERIC) return XMHW_KERNEL_GENERIC;
-    if (elem_bytes == 8) {
-        // float64: the second-generation kernel's 64-bit mode where it is instantiated (w = 5, up to 96 tracks),
-        // the generic kernel otherwise.  The round-1 float64 ring (kernels_ring64.hip) is gone: round 2's
-        // randomised cross-check found it returning wrong rows on clustered doubles and it was never repaired;
-        // an explicit XMHW_KERNEL_RING request on a plan the 64-bit mode does not cover is refused
-        // (XMHW_ERR_UNSUPPORTED) instead of being served by a kernel known to be wrong.
-        const bool x64 = x64_usable(p);
-        if (p->host.kernel_choice == XMHW_KERNEL_RING) return x64 ? XMHW_KERNEL_RING : -1;
-        return x64 ? XMHW_KERNEL_RING : XMHW_KERNEL_GENERIC;
-    }
-    const int32_t yps = xmhw::ring_pick(p->host.w, p->host.ntracks, elem_bytes, nullptr);
-    if (p->host.kernel_choice == XMHW_KERNEL_RING) return yps ? XMHW_KERNEL_RING : -1;
-    return yps ? XMHW_KERNEL_RING : XMHW_KERNEL_GENERIC;
-}
-
-int32_t auto_chunks(const xmhw_plan* p, int64_t C) {
-    if (p->host.nchunks_req > 0) return std::min(p->host.nchunks_req, p->host.D);
-    // enough waves to fill 256 CUs x 16 waves a few times over; each chunk
-    // re-reads 2w rows per track and cold-starts its bracket, so keep them long
-    int64_t waves = (C + 7) / 8;
-    int64_t want = (4 * 4096 + waves - 1) / std::max<int64_t>(waves, 1);
-    {
-        // the third-generation kernel runs two waves per SIMD (2,048 at a time) of 16 or 8 cells: twice that many
-        // waves in all is enough, and every further chunk costs its warm-up rows (1 degree grid, 64,800 cells: 3.67 ms
-        // with 1 or 2 chunks, 3.87 with 3, 4.16 with 6).
-        // The model behind it (round 4): a workgroup is 2 waves, a CU holds 4, the chip 1,024 at a time.  With n chunks
-        // a grid is W = n * ceil(C / 32) workgroups of (D / n + 2w) rows each and runs in about
-        // ceil(W / 1024) * (D / n + 2w) row-times.  The 1 degree grid (2,025 workgroups per chunk, D = 366): n = 1
-        // -> 2 rounds x 376 = 752; n = 2 -> 4 x 193 = 772; n = 3 -> 6 x 132 = 792; n = 6 -> 12 x 71 = 852 --
-        // the measured order.  One or two chunks fill the last round to 99 %: there is no tail to remove, and what
-        // keeps this grid at 11 % of the roofline against 15 % for the 40-year one is the record, not the grid:
-        // 30 tracks pad to 32 (6 % idle ring slots) and the per-row costs that do not depend on the number of
-        // tracks (walk, sort, epilogue, row overhead: ~40 % of a row) are spread over 120 bytes of samples per
-        // cell-row instead of 160.
-        const int32_t v = ring2_resolved(p);
-        if (v >= 20) {
-            const int64_t cpw = 64 / xmhw::ring2_subs(v);
-            waves = (C + cpw - 1) / cpw;
-            want = (4096 + waves - 1) / std::max<int64_t>(waves, 1);
-        }
-    }
-    want = std::max<int64_t>(1, std::min<int64_t>(want, p->host.D / 24));
-    return static_cast<int32_t>(std::max<int64_t>(want, 1));
-}
-
-// the ring2 variant float32 input runs on: the requested one, or (auto) 8 lanes per cell unless the
-// 4-lane layout pads fewer tracks (20 tracks: 4 x 5 exactly against 8 x 3 = 24) and does not spill;
-// both with the lanes' lists merged into a wider window (variants 8 and 10: measured 3-4 % faster than
-// the plain 0 and 7)
-int32_t ring2_legacy(const xmhw_plan* p) {
-    const int32_t y8 = xmhw::ring2_pick_yps(p->host.w, p->host.ntracks, 8);
-    const int32_t y4 = xmhw::ring2_pick_yps(p->host.w, p->host.ntracks, 10);
-    if (y4 && y4 <= 8 && (!y8 || y4 * 4 < y8 * 8)) return 10;
-    if (!y8 && xmhw::ring2_pick_yps(p->host.w, p->host.ntracks, 12) >= 4) return 12;
-    return 8;
-}
-
-int32_t ring2_resolved(const xmhw_plan* p) {
-    if (p->ring2_variant != -2 && p->ring2_variant != XMHW_LAYOUT_SORTED) return p->ring2_variant;
-    // the third-generation kernel (kernels_ring3.hip) on 4 lanes per cell where a lane holds at least 4 tracks
-    // (w = 5, 13..48 tracks).  1,036,800 cells, daily (tools/bench_ring2.py --years, counters on): 40 tracks 57.6 ms
-    // against 80 ms for the second-generation layouts, 24 tracks 41.8 against 59.8, 20 tracks 38.3 against 44.0,
-    // 16 tracks 34.5 against 35.3; 12 tracks 31.0 against 29.7 -- with so few keys per lane its per-row overheads
-    // (histogram, walk, sort) outweigh the cheaper selection.  The 6-hourly share of configs[4] (20 tracks): 116 against
-    // 130 ms.
-    // ... on 2 lanes per cell (32 cells per wave) for records of 9..24 tracks: 518,400 cells daily, counters on: 13
-    // tracks 12.4 against 17.7 ms on 4 lanes, 18 tracks 14.6 / 19.5, 22 tracks 17.5 / 21.3, 24 tracks 20.4 / 21.1; the
-    // 6-hourly share of configs[4] (20 tracks, 405,000 cells): 48.1 / 58.9
-    if (xmhw::ring3_pick_yps(p->host.w, p->host.ntracks, 2) >= 5) return 22;
-    if (xmhw::ring3_pick_yps(p->host.w, p->host.ntracks, 4) >= 4) return 21;
-    // ... and on 8 lanes per cell for longer records (49..88 tracks, 7..11 per lane) instead of the second-generation
-    // kernel's 16-lane layout: 259,200 cells daily, counters on: 50 tracks 24.9 against 36.6 ms, 65 tracks 31.6 / 45.1,
-    // 85 tracks 42.8 / 51.0; 96 tracks (12 per lane, 256 registers) 53.5 / 52.0 -- those stay where they were
-    {
-        const int32_t y8 = xmhw::ring3_pick_yps(p->host.w, p->host.ntracks, 8);
-        if (y8 >= 7 && y8 <= 11) return 20;
-    }
-    return ring2_legacy(p);
-}
-
-// float64 input that is really float32 (decoded archives): which ring2 variant narrows it, and on which of the
-// plan's tables.  The third-generation kernel narrows on the layouts the automatic choice uses (4..12 tracks per lane
-// at 4 lanes per cell); any other plan whose float32 layout is variant 20 / 21 narrows on the second-generation
-// kernel: its table is the plan's own when the lane layout is the same (4 lanes: variant 10), the 64-bit mode's
-// 8-lane table otherwise.
-struct NarrowChoice { int32_t variant = -1, yps = 0; const uint32_t* table = nullptr; };
-NarrowChoice narrow_choice(const xmhw_plan* p) {
-    NarrowChoice c;
-    int32_t v = ring2_resolved(p);
-    if (v < 0) return c;
-    if (v >= 20 && p->yps2 && p->subs2 == xmhw::ring2_subs(v) &&
-        xmhw::ring2_narrowing_supported(p->host.w, p->yps2, v)) {
-        c.variant = v;
-        c.yps = p->yps2;
-        c.table = p->d_table2;
-        return c;
-    }
-    if (v >= 20) v = ring2_legacy(p);
-    const int32_t subs = xmhw::ring2_subs(v);
-    const int32_t yps = xmhw::ring2_pick_yps(p->host.w, p->host.ntracks, v);
-    if (!yps || !xmhw::ring2_narrowing_supported(p->host.w, yps, v)) return c;
-    const uint32_t* t = nullptr;
-    if (p->subs2 == subs && p->yps2 == yps) t = p->d_table2;
-    else if (p->subsx == subs && p->ypsx == yps) t = p->d_tablex;
-    if (!t) return c;
-    c.variant = v;
-    c.yps = yps;
-    c.table = t;
-    return c;
-}
-
-// The sorted-list kernel serves float32 input of plans with w = 5 whose record it is instantiated for, under the
-// automatic layout choice or XMHW_LAYOUT_SORTED (environment XMHW_SORTED=0 turns it off); the rows it cannot serve
-// (plan.h: sorted_segments) need the ring kernel.
-bool sorted_usable(const xmhw_plan* p) {
-    static const bool on = [] { const char* v = std::getenv("XMHW_SORTED"); return !(v && v[0] == '0'); }();
-    if (!on && p->ring2_variant != XMHW_LAYOUT_SORTED) return false;
-    if (p->ring2_variant != -2 && p->ring2_variant != XMHW_LAYOUT_SORTED) return false;
-    if (p->host.kernel_choice == XMHW_KERNEL_GENERIC) return false;
-    if (xmhw::sorted_pick_yps(p->host.w, p->host.ntracks) == 0) return false;
-    return resolve_kernel(p, 4) == XMHW_KERNEL_RING;
-}
 
 // The sorted-list kernel's lists rely on LDS reads outside the workgroup's allocation returning 0 (kernels_sorted.hip).
 // Checked once per device of this process before the kernel is used there; a device that answers otherwise keeps the ring
@@ -318,133 +123,189 @@ int sorted_device_ok() {
     return state[dev];
 }
 
+// the route of a call on the current device (the device is probed only where the sorted-list kernel would run) ...
+xmhw::Route call_route(const xmhw_plan* p, int elem_bytes, double q) {
+    xmhw::Route r = xmhw::resolve_route(p->host, p->settings, elem_bytes, q, true);
+    if (r.n && r.launch[0].family == xmhw::Family::Sorted && sorted_device_ok() != 1)
+        r = xmhw::resolve_route(p->host, p->settings, elem_bytes, q, false);
+    return r;
+}
+// ... and what the introspection entries report from: no device needed, one that passes the probe assumed; float32 at a
+// quantile the sorted-list kernel serves, so that the first launch names the plan's float32 kernel
+xmhw::Route plan_route(const xmhw_plan* p, int elem_bytes, double q = 1.0) {
+    return xmhw::resolve_route(p->host, p->settings, elem_bytes, q, true);
+}
+
+// a vector -> device memory, allocated at most once: a failed upload can be retried without leaking
+template <typename E>
+hipError_t put(E** dst, const std::vector<E>& v) {
+    const bool fresh = *dst == nullptr;
+    hipError_t e = fresh ? hipMalloc(reinterpret_cast<void**>(dst), sizeof(E) * v.size()) : hipSuccess;
+    if (e != hipSuccess) { *dst = nullptr; return e; }
+    e = hipMemcpy(*dst, v.data(), sizeof(E) * v.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess && fresh) { (void)hipFree(*dst); *dst = nullptr; }
+    return e;
+}
+
+// what the launches of one call take: copied out under the plan's lock, used after it is released
+struct Ready {
+    PlanDevice dev;
+    const uint32_t* table[3] = {};          // the step table of every launch (NULL: the generic kernel)
+    hipEvent_t t0 = nullptr, t1 = nullptr;  // the call's timing events (NULL: not timed)
+};
+
 // tables and chunks of the sorted-list kernel (under the plan's lock)
-int upload_sorted(xmhw_plan* p, int64_t C) {
-    const xmhw::Plan& h = p->host;
-    if (!sorted_usable(p) || sorted_device_ok() != 1) { p->nchunks_s = 0; return XMHW_OK; }
-    const int32_t yps = xmhw::sorted_pick_yps(h.w, h.ntracks);
-    const int64_t waves = (C + 31) / 32;
-    // the kernel's own chunks and table rows (plan.h: sorted_plan); a small grid is cut into more pieces so that it still
-    // fills the chip (7 waves per CU; every piece pays R - 1 warm-up rows).  The tables depend on (tracks per lane, pieces)
-    // only: the slabs of one threshold() call -- a different cell count each -- share them.
-    const int64_t pieces = h.nchunks_req > 0 ? h.nchunks_req : (1536 + waves - 1) / std::max<int64_t>(waves, 1);
-    if (!p->d_table_s || p->yps_s != yps || p->sorted_pieces != pieces) {
-        HIP_TRY(hipDeviceSynchronize());
-        for (void** q : {reinterpret_cast<void**>(&p->d_table_s), reinterpret_cast<void**>(&p->d_sflags_s),
-                         reinterpret_cast<void**>(&p->d_chunks_s), reinterpret_cast<void**>(&p->d_chunks_i)})
-            if (*q) { HIP_TRY(hipFree(*q)); *q = nullptr; }
-        const xmhw::Plan::SortedPlan sp = h.sorted_plan(2 * yps, 24, pieces);
-        p->sorted_built = 0;
-        p->nchunks_i = 0;
-        if (!sp.chunks.empty()) {
-            // longest chunk first: workgroups start in the order of their index, blockIdx.y = the chunk, so the launch ends
-            // with the short chunks (a 40-year daily plan: rows [60, 366), then [0, 59), then the Feb-29 row) instead of a
-            // tail of 316-row waves
-            std::vector<xmhw::DevSortedChunk> cs(sp.chunks.size());
-            for (size_t i = 0; i < cs.size(); ++i) cs[i] = {sp.chunks[i].warm_start, sp.chunks[i].begin, sp.chunks[i].end, sp.chunks[i].trow0};
-            std::stable_sort(cs.begin(), cs.end(), [](const xmhw::DevSortedChunk& a, const xmhw::DevSortedChunk& b) {
-                return a.end - a.warm_start > b.end - b.warm_start;
-            });
-            HIP_TRY(hipMalloc(&p->d_table_s, sizeof(uint32_t) * sp.table.size()));
-            HIP_TRY(hipMemcpy(p->d_table_s, sp.table.data(), sizeof(uint32_t) * sp.table.size(), hipMemcpyHostToDevice));
-            HIP_TRY(hipMalloc(&p->d_sflags_s, sizeof(uint32_t) * sp.flags.size()));
-            HIP_TRY(hipMemcpy(p->d_sflags_s, sp.flags.data(), sizeof(uint32_t) * sp.flags.size(), hipMemcpyHostToDevice));
-            HIP_TRY(hipMalloc(&p->d_chunks_s, sizeof(xmhw::DevSortedChunk) * cs.size()));
-            HIP_TRY(hipMemcpy(p->d_chunks_s, cs.data(), sizeof(xmhw::DevSortedChunk) * cs.size(), hipMemcpyHostToDevice));
-            p->sorted_built = static_cast<int32_t>(cs.size());
-        }
-        p->yps_s = yps;
-        p->sorted_pieces = pieces;
-    }
-    p->nchunks_s = p->sorted_built;
+int ensure_sorted(xmhw_plan* p, const xmhw::Launch& l, int64_t pieces) {
+    PlanDevice& d = p->dev;
+    if (d.table_s && p->yps_s == l.tpl && p->sorted_pieces == pieces) return XMHW_OK;
+    HIP_TRY(hipDeviceSynchronize());
+    for (void** q : {reinterpret_cast<void**>(&d.table_s), reinterpret_cast<void**>(&d.sflags_s),
+                     reinterpret_cast<void**>(&d.chunks_s)})
+        if (*q) { HIP_TRY(hipFree(*q)); *q = nullptr; }
+    // the kernel's own chunks and table rows (plan.h: sorted_plan).  The tables depend on (tracks per lane, pieces) only:
+    // the slabs of one threshold() call -- a different cell count each -- share them.
+    const xmhw::Plan::SortedPlan sp = p->host.sorted_plan(l.lanes * l.tpl, 24, pieces);
+    if (sp.chunks.empty()) return fail(XMHW_ERR_UNSUPPORTED, "the sorted-list kernel has no chunks for this plan");
+    // longest chunk first: workgroups start in the order of their index, blockIdx.y = the chunk, so the launch ends
+    // with the short chunks (a 40-year daily plan: rows [60, 366), then [0, 59), then the Feb-29 row) instead of a
+    // tail of 316-row waves
+    std::vector<xmhw::DevSortedChunk> cs(sp.chunks.size());
+    for (size_t i = 0; i < cs.size(); ++i) cs[i] = {sp.chunks[i].warm_start, sp.chunks[i].begin, sp.chunks[i].end, sp.chunks[i].trow0};
+    std::stable_sort(cs.begin(), cs.end(), [](const xmhw::DevSortedChunk& a, const xmhw::DevSortedChunk& b) {
+        return a.end - a.warm_start > b.end - b.warm_start;
+    });
+    p->sorted_pieces = -1;
+    HIP_TRY(put(&d.table_s, sp.table));
+    HIP_TRY(put(&d.sflags_s, sp.flags));
+    HIP_TRY(put(&d.chunks_s, cs));
+    d.nchunks_s = static_cast<int32_t>(cs.size());
+    p->yps_s = l.tpl;
+    p->sorted_pieces = pieces;
     return XMHW_OK;
 }
 
-int upload(xmhw_plan* p, int64_t C) {
+// everything on the device that the route's launches over C cells need, uploaded or re-cut where it is missing
+int ensure(xmhw_plan* p, const xmhw::Route& route, int64_t C, bool timed, Ready* out) {
     std::lock_guard<std::mutex> lock(p->mu);
-    {
-        const int rc = upload_sorted(p, C);
-        if (rc != XMHW_OK) return rc;
-    }
-    const int32_t nchunks = auto_chunks(p, C);
-    const X64Choice xc0 = x64_choice(p);
-    const int32_t xsubs0 = xc0.variant == 21 ? 4 : 8;
-    const bool need_x = (xc0.variant == 8 || xc0.variant == 20 || xc0.variant == 21) &&
-                        !(p->subs2 == xsubs0 && p->yps2 == xc0.yps);
-    if (p->uploaded && nchunks == p->nchunks &&
-        p->subs2 == xmhw::ring2_subs(ring2_resolved(p)) &&
-        p->yps2 == (ring2_resolved(p) >= 0 ? xmhw::ring2_pick_yps(p->host.w, p->host.ntracks, ring2_resolved(p)) : 0) &&
-        (!need_x || (p->ypsx == xc0.yps && p->subsx == xsubs0)))
-        return XMHW_OK;
     const xmhw::Plan& h = p->host;
+    PlanDevice& d = p->dev;
     if (!p->uploaded) {
-        // every table is allocated at most once: a failed upload can be retried without leaking
-        auto put = [](auto** dst, const auto& v) -> hipError_t {
-            using E = typename std::remove_reference<decltype(v)>::type::value_type;
-            if (*dst == nullptr) {
-                hipError_t e = hipMalloc(reinterpret_cast<void**>(dst), sizeof(E) * v.size());
-                if (e != hipSuccess) { *dst = nullptr; return e; }
-            }
-            return hipMemcpy(*dst, v.data(), sizeof(E) * v.size(), hipMemcpyHostToDevice);
-        };
-        HIP_TRY(put(&p->d_row_ptr, h.row_ptr));
-        HIP_TRY(put(&p->d_centres, h.centres));
-        p->yps = xmhw::ring_pick(h.w, h.ntracks, 4, &p->subs);
-        if (p->yps) HIP_TRY(put(&p->d_table, h.ring_table(p->subs, p->yps)));
-        HIP_TRY(put(&p->d_sflags, h.step_flags()));
-        {
-            const int32_t y16 = xmhw::ring2_pick_yps(h.w, h.ntracks, 12);
-            p->yps64 = (y16 >= 1 && y16 <= 6) ? y16 : 0;      // (also for 49..96 tracks: their float32 layout may be another)
-        }
-        if (p->yps64) HIP_TRY(put(&p->d_table64, h.ring_table(16, p->yps64)));
+        HIP_TRY(put(&d.row_ptr, h.row_ptr));
+        HIP_TRY(put(&d.centres, h.centres));
+        HIP_TRY(put(&d.sflags, h.step_flags()));
+        p->uploaded = true;
     }
-    // the second-generation ring kernel's table depends on the variant's lanes per cell
-    {
-        const int32_t v2 = ring2_resolved(p);
-        const int32_t subs2 = xmhw::ring2_subs(v2);
-        const int32_t yps2 = v2 >= 0 ? xmhw::ring2_pick_yps(h.w, h.ntracks, v2) : 0;
-        if (yps2 != p->yps2 || subs2 != p->subs2) {
-            if (p->d_table2) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(p->d_table2)); p->d_table2 = nullptr; }
-            p->yps2 = yps2;
-            p->subs2 = subs2;
-            if (yps2) {
-                const std::vector<uint32_t> t2 = h.ring_table(subs2, yps2);
-                HIP_TRY(hipMalloc(&p->d_table2, sizeof(uint32_t) * t2.size()));
-                HIP_TRY(hipMemcpy(p->d_table2, t2.data(), sizeof(uint32_t) * t2.size(), hipMemcpyHostToDevice));
-            }
+    bool ring = false;
+    for (int32_t i = 0; i < route.n; ++i) {
+        const xmhw::Launch& l = route.launch[i];
+        if (l.family == xmhw::Family::Generic) continue;
+        if (l.narrows && !d.narrow_flag) HIP_TRY(hipMalloc(&d.narrow_flag, sizeof(uint32_t)));
+        if (l.family == xmhw::Family::Sorted) {
+            const int rc = ensure_sorted(p, l, xmhw::sorted_pieces(h, route, C));
+            if (rc != XMHW_OK) return rc;
+            out->table[i] = d.table_s;
+            continue;
         }
+        ring = true;
+        uint32_t*& table = p->tables[{l.lanes, l.tpl}];
+        if (!table) HIP_TRY(put(&table, h.ring_table(l.lanes, l.tpl)));
+        out->table[i] = table;
     }
-    {
-        // the 64-bit mode's own table (8 lanes, or 4 for short records), when the float32 layout of this plan is a
-        // different one
-        const X64Choice xc = x64_choice(p);
-        const int32_t xsubs = xc.variant == 21 ? 4 : 8;
-        if ((xc.variant == 8 || xc.variant == 20 || xc.variant == 21) && !(p->subs2 == xsubs && p->yps2 == xc.yps) &&
-            !(p->ypsx == xc.yps && p->subsx == xsubs)) {
-            if (p->d_tablex) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(p->d_tablex)); p->d_tablex = nullptr; }
-            const std::vector<uint32_t> tx = h.ring_table(xsubs, xc.yps);
-            HIP_TRY(hipMalloc(&p->d_tablex, sizeof(uint32_t) * tx.size()));
-            HIP_TRY(hipMemcpy(p->d_tablex, tx.data(), sizeof(uint32_t) * tx.size(), hipMemcpyHostToDevice));
-            p->ypsx = xc.yps;
-            p->subsx = xsubs;
-        }
-    }
-    if (p->yps || p->yps64 || p->yps2) {
-        std::vector<xmhw::Chunk> ch = h.make_chunks(nchunks);
+    const int32_t cut = xmhw::ring_chunks(h, route, C);
+    if (ring && (!d.chunks || cut != p->chunks_cut)) {
+        const std::vector<xmhw::Chunk> ch = h.make_chunks(cut);
         std::vector<xmhw::DevChunk> dch(ch.size());
         for (size_t i = 0; i < ch.size(); ++i) dch[i] = {ch[i].warm_start, ch[i].begin, ch[i].end};
-        if (p->d_chunks) { HIP_TRY(hipFree(p->d_chunks)); p->d_chunks = nullptr; }
-        HIP_TRY(hipMalloc(&p->d_chunks, sizeof(xmhw::DevChunk) * dch.size()));
-        HIP_TRY(hipMemcpy(p->d_chunks, dch.data(), sizeof(xmhw::DevChunk) * dch.size(),
-                          hipMemcpyHostToDevice));
-        p->nchunks = static_cast<int32_t>(dch.size());
-    } else {
-        p->nchunks = nchunks;
+        if (d.chunks) { HIP_TRY(hipFree(d.chunks)); d.chunks = nullptr; }
+        HIP_TRY(put(&d.chunks, dch));
+        p->chunks_cut = cut;
+        d.nchunks = static_cast<int32_t>(dch.size());
     }
-    p->uploaded = true;
+    if (timed && p->timing) {
+        const int slot = static_cast<int>(p->tcalls % 16);
+        for (int i = 0; i < 2; ++i)
+            if (!p->tev[2 * slot + i]) HIP_TRY(hipEventCreate(&p->tev[2 * slot + i]));
+        out->t0 = p->tev[2 * slot];
+        out->t1 = p->tev[2 * slot + 1];
+        p->tcalls++;
+    }
+    out->dev = d;
     return XMHW_OK;
 }
 
+// the call's main kernel between its two timing events (xmhw_plan_set_timing)
+template <typename F>
+hipError_t timed_launch(const Ready& rd, hipStream_t st, F launch) {
+    hipError_t e = rd.t0 ? hipEventRecord(rd.t0, st) : hipSuccess;
+    if (e == hipSuccess) e = launch();
+    if (e == hipSuccess && rd.t1) e = hipEventRecord(rd.t1, st);
+    return e;
+}
+
+// float64 input through a float32 ring kernel: the probe clears and sets the narrow flag, the kernel reads the samples
+// narrowed and leaves at the first lossy one (the round-1 launcher queues its own probe)
+hipError_t launch_narrowing(const xmhw::Plan& h, const xmhw::Launch& l, const PlanDevice& rd, const uint32_t* table,
+                            const double* ts, int64_t C, int64_t ld, double q, int negate, double* thresh, double* seas,
+                            int64_t ldo, hipStream_t st) {
+    if (l.family == xmhw::Family::Ring1)
+        return xmhw::launch_ring_f32_narrowing(ts, h.T, C, ld, table, h.step_min, rd.chunks, rd.nchunks, h.w, l.tpl, l.lanes,
+                                               q, negate, thresh, seas, ldo, st, rd.stats, rd.narrow_flag);
+    const hipError_t e = xmhw::launch_narrow_probe(ts, h.T, C, ld, rd.narrow_flag, st);
+    if (e != hipSuccess) return e;
+    if (l.family == xmhw::Family::Ring2)
+        return xmhw::launch_ring2_f32_narrowing(ts, C, ld, h.T, table, rd.sflags, h.step_min, rd.chunks, rd.nchunks, h.w,
+                                                l.tpl, h.ntracks, l.layout, q, negate, thresh, seas, ldo, st, rd.narrow_flag);
+    if (l.family == xmhw::Family::Ring3)
+        return xmhw::launch_ring3_f32_narrowing(ts, C, ld, h.T, table, rd.sflags, h.step_min, rd.chunks, rd.nchunks, h.w,
+                                                l.tpl, l.lanes, h.ntracks, q, negate, thresh, seas, ldo, st, rd.narrow_flag);
+    return hipErrorInvalidValue;
+}
+
+template <typename T>
+hipError_t launch_one(const xmhw::Plan& h, const xmhw::Launch& l, const PlanDevice& rd, const uint32_t* table, const T* ts,
+                      int64_t C, int64_t ld, double q, int negate, double* thresh, double* seas, int64_t ldo,
+                      hipStream_t st) {
+    using xmhw::Family;
+    const uint32_t* run_flag = l.gated ? rd.narrow_flag : nullptr;
+    unsigned long long* stats = l.counters ? rd.stats : nullptr;
+    if (l.family == Family::Generic)
+        return xmhw::launch_generic<T>(ts, h.T, C, ld, rd.row_ptr, rd.centres, h.D, h.w, q, negate, thresh, seas, ldo, st,
+                                       run_flag);
+    if constexpr (sizeof(T) == 4) {
+        switch (l.family) {
+            case Family::Sorted:
+                return xmhw::launch_sorted_f32(ts, C, ld, h.T, table, rd.sflags_s, rd.chunks_s, rd.nchunks_s, h.w, l.tpl,
+                                               h.ntracks, q, negate, thresh, seas, ldo, st, stats);
+            case Family::Ring1:
+                return xmhw::launch_ring_f32(ts, C, ld, table, h.step_min, rd.chunks, rd.nchunks, h.w, l.tpl, l.lanes, q,
+                                             negate, thresh, seas, ldo, st, stats);
+            case Family::Ring2:
+                return xmhw::launch_ring2_f32(ts, C, ld, h.T, table, rd.sflags, h.step_min, rd.chunks, rd.nchunks, h.w, l.tpl,
+                                              h.ntracks, l.layout, q, negate, thresh, seas, ldo, st, stats);
+            case Family::Ring3:
+                return xmhw::launch_ring3_f32(ts, C, ld, h.T, table, rd.sflags, h.step_min, rd.chunks, rd.nchunks, h.w, l.tpl,
+                                              l.lanes, h.ntracks, q, negate, thresh, seas, ldo, st, stats);
+#ifdef XMHW_RING4
+            case Family::Ring4:
+                return xmhw::launch_ring4_f32(ts, C, ld, h.T, table, rd.sflags, h.step_min, rd.chunks, rd.nchunks, h.w, l.tpl,
+                                              l.lanes, h.ntracks, q, negate, thresh, seas, ldo, st, stats);
+#endif
+            default: return hipErrorInvalidValue;
+        }
+    } else {
+        if (l.narrows) return launch_narrowing(h, l, rd, table, ts, C, ld, q, negate, thresh, seas, ldo, st);
+        // genuinely float64 samples: the 64-bit mode (runs only if the narrowing launch before it flagged a sample)
+        if (l.family == Family::Ring2)
+            return xmhw::launch_ring2_f64(ts, C, ld, h.T, table, rd.sflags, h.step_min, rd.chunks, rd.nchunks, h.w, l.tpl,
+                                          h.ntracks, l.layout, q, negate, thresh, seas, ldo, st, run_flag);
+        if (l.family == Family::Ring3)
+            return xmhw::launch_ring3_f64(ts, C, ld, h.T, table, rd.sflags, h.step_min, rd.chunks, rd.nchunks, h.w, l.tpl,
+                                          l.lanes, h.ntracks, q, negate, thresh, seas, ldo, st, run_flag);
+        return hipErrorInvalidValue;
+    }
+}
+
+// resolve -> ensure -> launch
 template <typename T>
 int clim_raw(xmhw_plan* plan, const T* ts, int64_t C, int64_t ld, double q, int negate,
              double* thresh, double* seas, int64_t ldo, void* stream) {
@@ -453,126 +314,18 @@ int clim_raw(xmhw_plan* plan, const T* ts, int64_t C, int64_t ld, double q, int 
     if (!(q >= 0.0 && q <= 1.0)) return fail(XMHW_ERR_INVALID, "quantile must be in [0, 1]");
     if (C == 0) return XMHW_OK;
     if (!ts || !thresh || !seas) return fail(XMHW_ERR_INVALID, "NULL device buffer");
-    const int32_t kernel = resolve_kernel(plan, sizeof(T));
-    if (kernel < 0)
-        return fail(XMHW_ERR_UNSUPPORTED, "ring kernel not available for this window/track count/dtype");
-    int rc = upload(plan, C);
+    const xmhw::Route route = call_route(plan, sizeof(T), q);
+    if (route.unsupported) return fail(XMHW_ERR_UNSUPPORTED, route.unsupported);
+    // (timed: the main kernel of a float32 call -- the sorted-list or the ring kernel)
+    Ready rd;
+    const int rc = ensure(plan, route, C, sizeof(T) == 4 && route.launch[0].family != xmhw::Family::Generic, &rd);
     if (rc != XMHW_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const xmhw::Plan& h = plan->host;
-    hipError_t e;
-    if (kernel == XMHW_KERNEL_RING) {
-        if constexpr (sizeof(T) == 4) {
-            // float32: the sorted-list kernel on the regular rows (high percentiles: a list keeps its K largest keys),
-            // the ring kernel on the others, the generic kernel on the cell-rows the sorted kernel flagged
-            const bool sorted = plan->nchunks_s > 0 && sorted_serves(q);
-            const xmhw::DevChunk* rchunks = sorted ? plan->d_chunks_i : plan->d_chunks;
-            const int32_t rn = sorted ? plan->nchunks_i : plan->nchunks;
-            unsigned long long* rstats = sorted ? nullptr : plan->d_stats;
-            e = hipSuccess;
-            hipEvent_t t0 = nullptr, t1 = nullptr;
-            if (plan->timing) {
-                const int slot = static_cast<int>(plan->tcalls % 16);
-                for (int i = 0; i < 2; ++i)
-                    if (!plan->tev[2 * slot + i]) HIP_TRY(hipEventCreate(&plan->tev[2 * slot + i]));
-                t0 = plan->tev[2 * slot];
-                t1 = plan->tev[2 * slot + 1];
-                plan->tcalls++;
-            }
-            if (sorted) {
-                if (t0) e = hipEventRecord(t0, st);
-                if (e == hipSuccess)
-                    e = xmhw::launch_sorted_f32(reinterpret_cast<const float*>(ts), C, ld, h.T, plan->d_table_s,
-                                                plan->d_sflags_s, plan->d_chunks_s, plan->nchunks_s, h.w,
-                                                plan->yps_s, h.ntracks, q, negate, thresh, seas, ldo, st, plan->d_stats);
-                if (e == hipSuccess && t1) e = hipEventRecord(t1, st);
-            } else if (t0) {
-                e = hipEventRecord(t0, st);
-            }
-            if (e != hipSuccess) {
-            } else if (rn == 0) {
-            } else
-            if (plan->yps2 && ring2_resolved(plan) >= 0 && xmhw::ring2_f32_supported(h.w, plan->yps2, ring2_resolved(plan)))
-                e = xmhw::launch_ring2_f32(reinterpret_cast<const float*>(ts), C, ld, h.T, plan->d_table2, plan->d_sflags,
-                                           h.step_min, rchunks, rn, h.w, plan->yps2, h.ntracks,
-                                           ring2_resolved(plan), q, negate, thresh, seas, ldo, st, rstats);
-            else
-            e = xmhw::launch_ring_f32(reinterpret_cast<const float*>(ts), C, ld, plan->d_table,
-                                      h.step_min, rchunks, rn, h.w, plan->yps, plan->subs, q,
-                                      negate, thresh, seas, ldo, st, rstats);
-            if (e == hipSuccess && !sorted && t1) e = hipEventRecord(t1, st);
-        } else {
-            // float64 input: if every sample is float32-representable (decoded int16 / float32
-            // archives) the float32 kernel gives the same pools at 2.7x the rate.  All decisions are
-            // taken on the device so that the call stays asynchronous: probe -> narrowing float32
-            // kernel (stops at the first lossy sample) -> float64 kernel (runs only if flagged).
-            const uint32_t* run_flag = nullptr;
-            e = hipSuccess;
-            const NarrowChoice nc = narrow_choice(plan);
-            if (plan->narrowing && nc.variant >= 0) {
-                // the second-generation kernel narrows too (the shipped layouts)
-                if (!plan->d_narrow_flag) HIP_TRY(hipMalloc(&plan->d_narrow_flag, sizeof(uint32_t)));
-                e = xmhw::launch_narrow_probe(reinterpret_cast<const double*>(ts), h.T, C, ld, plan->d_narrow_flag, st);
-                if (e == hipSuccess)
-                    e = xmhw::launch_ring2_f32_narrowing(reinterpret_cast<const double*>(ts), C, ld, h.T, nc.table,
-                                                         plan->d_sflags, h.step_min, plan->d_chunks, plan->nchunks, h.w,
-                                                         nc.yps, h.ntracks, nc.variant, q, negate, thresh, seas, ldo, st,
-                                                         plan->d_narrow_flag);
-                run_flag = plan->d_narrow_flag;
-            } else if (plan->narrowing && plan->yps) {
-                if (!plan->d_narrow_flag) HIP_TRY(hipMalloc(&plan->d_narrow_flag, sizeof(uint32_t)));
-                e = xmhw::launch_ring_f32_narrowing(reinterpret_cast<const double*>(ts), h.T, C, ld, plan->d_table,
-                                                    h.step_min, plan->d_chunks, plan->nchunks, h.w, plan->yps,
-                                                    plan->subs, q, negate, thresh, seas, ldo, st, plan->d_stats,
-                                                    plan->d_narrow_flag);
-                run_flag = plan->d_narrow_flag;
-            }
-            // genuinely float64 samples: the second-generation kernel's 64-bit mode (resolve_kernel() returned
-            // XMHW_KERNEL_RING only because it is instantiated for this plan)
-            if (e == hipSuccess) {
-                const X64Choice xc = x64_choice(plan);
-                if (xc.variant >= 0)
-                    e = xmhw::launch_ring2_f64(reinterpret_cast<const double*>(ts), C, ld, h.T,
-                                               xc.variant == 12 ? ((plan->subs2 == 16 && plan->yps2 == xc.yps) ? plan->d_table2 : plan->d_table64)
-                                               : (plan->subs2 == (xc.variant == 21 ? 4 : 8) && plan->yps2 == xc.yps) ? plan->d_table2
-                                               : plan->d_tablex,
-                                               plan->d_sflags,
-                                               h.step_min, plan->d_chunks, plan->nchunks, h.w, xc.yps, h.ntracks, xc.variant,
-                                               q, negate, thresh, seas, ldo, st, run_flag);
-                else
-                    return fail(XMHW_ERR_UNSUPPORTED, "no float64 ring kernel for this plan");
-            }
-        }
-    } else {
-        const uint32_t* run_flag = nullptr;
-        e = hipSuccess;
-        if constexpr (sizeof(T) == 8) {
-            // no float64 ring for this plan (e.g. a record of more than 48 tracks), but the float32 ring
-            // covers it: float32-representable data still takes the fast kernel, the generic one
-            // runs only if the narrowing gave up
-            const NarrowChoice nc = narrow_choice(plan);
-            if (plan->narrowing && nc.variant >= 0 && plan->host.kernel_choice == XMHW_KERNEL_AUTO) {
-                if (!plan->d_narrow_flag) HIP_TRY(hipMalloc(&plan->d_narrow_flag, sizeof(uint32_t)));
-                e = xmhw::launch_narrow_probe(reinterpret_cast<const double*>(ts), h.T, C, ld, plan->d_narrow_flag, st);
-                if (e == hipSuccess)
-                    e = xmhw::launch_ring2_f32_narrowing(reinterpret_cast<const double*>(ts), C, ld, h.T, nc.table,
-                                                         plan->d_sflags, h.step_min, plan->d_chunks, plan->nchunks, h.w,
-                                                         nc.yps, h.ntracks, nc.variant, q, negate, thresh, seas, ldo, st,
-                                                         plan->d_narrow_flag);
-                run_flag = plan->d_narrow_flag;
-            } else if (plan->narrowing && plan->yps && plan->host.kernel_choice == XMHW_KERNEL_AUTO) {
-                if (!plan->d_narrow_flag) HIP_TRY(hipMalloc(&plan->d_narrow_flag, sizeof(uint32_t)));
-                e = xmhw::launch_ring_f32_narrowing(reinterpret_cast<const double*>(ts), h.T, C, ld, plan->d_table,
-                                                    h.step_min, plan->d_chunks, plan->nchunks, h.w, plan->yps,
-                                                    plan->subs, q, negate, thresh, seas, ldo, st, plan->d_stats,
-                                                    plan->d_narrow_flag);
-                run_flag = plan->d_narrow_flag;
-            }
-        }
-        if (e == hipSuccess)
-            e = xmhw::launch_generic<T>(ts, h.T, C, ld, plan->d_row_ptr, plan->d_centres, h.D, h.w, q,
-                                        negate, thresh, seas, ldo, st, run_flag);
-    }
+    hipError_t e = hipSuccess;
+    for (int32_t i = 0; i < route.n && e == hipSuccess; ++i)
+        e = timed_launch(rd, st, [&] {
+            return launch_one<T>(plan->host, route.launch[i], rd.dev, rd.table[i], ts, C, ld, q, negate, thresh, seas, ldo, st);
+        });
     if (e != hipSuccess) return hip_fail(e, "kernel launch");
     return XMHW_OK;
 }
@@ -1340,19 +1093,6 @@ int xmhw_event_elapsed_ms(void* start, void* stop, float* ms) {
     return XMHW_OK;
 }
 
-namespace {
-// the layouts this build instantiates (include/xmhw_amd.h: XMHW_LAYOUT_*)
-bool layout_compiled(int32_t layout) {
-    switch (layout) {
-        case -2: case -1: case 8: case 10: case 12: case 20: case 21: case 22: case XMHW_LAYOUT_SORTED: return true;
-#ifdef XMHW_RING4
-        case 30: case 31: case 32: return true;
-#endif
-        default: return false;
-    }
-}
-}  // namespace
-
 int xmhw_plan_create(const int32_t* doy_host, int64_t T, int32_t window_half_width, xmhw_plan** plan) {
     if (!plan) return fail(XMHW_ERR_INVALID, "plan is NULL");
     *plan = nullptr;
@@ -1367,22 +1107,22 @@ int xmhw_plan_create(const int32_t* doy_host, int64_t T, int32_t window_half_wid
     // (the environment sets the default layout of new plans; a number this build does not have is ignored)
     if (const char* v = std::getenv("XMHW_RING2")) {
         const int32_t lay = std::atoi(v);
-        if (layout_compiled(lay) && (lay != XMHW_LAYOUT_SORTED || xmhw::sorted_pick_yps(p->host.w, p->host.ntracks) != 0))
-            p->ring2_variant = lay;
+        if (xmhw::layout_compiled(lay) && (lay != XMHW_LAYOUT_SORTED || xmhw::sorted_pick_yps(p->host.w, p->host.ntracks) != 0))
+            p->settings.layout = lay;
     }
     *plan = p;
     return XMHW_OK;
 }
 int xmhw_plan_set_layout(xmhw_plan* plan, int32_t layout) {
     if (!plan) return fail(XMHW_ERR_INVALID, "plan is NULL");
-    if (!layout_compiled(layout))
+    if (!xmhw::layout_compiled(layout))
         return fail(XMHW_ERR_UNSUPPORTED,
                     "layout must be one of the XMHW_LAYOUT_* constants this library was built with: -2 (auto), -1, 8, 10, 12, "
                     "20, 21, 22, 40 (the plain second-generation layouts 0..7, 9, 11 left the build in round 4; 30..32 need "
                     "make RING4=1)");
     if (layout == XMHW_LAYOUT_SORTED && xmhw::sorted_pick_yps(plan->host.w, plan->host.ntracks) == 0)
         return fail(XMHW_ERR_UNSUPPORTED, "the sorted-list kernel is not instantiated for this window / record length");
-    plan->ring2_variant = layout;
+    plan->settings.layout = layout;
     return XMHW_OK;
 }
 int xmhw_sorted_device_ok(int32_t* holds) {
@@ -1394,11 +1134,8 @@ int xmhw_sorted_device_ok(int32_t* holds) {
 }
 int xmhw_plan_layout_in_use(const xmhw_plan* plan, int32_t* layout) {
     if (!plan || !layout) return fail(XMHW_ERR_INVALID, "NULL argument");
-    if (sorted_usable(plan)) { *layout = XMHW_LAYOUT_SORTED; return XMHW_OK; }
-    const int32_t v2 = ring2_resolved(plan);
-    const bool ring = resolve_kernel(plan, 4) == XMHW_KERNEL_RING;
-    const int32_t y2 = v2 >= 0 ? xmhw::ring2_pick_yps(plan->host.w, plan->host.ntracks, v2) : 0;
-    *layout = (ring && y2 > 0 && xmhw::ring2_f32_supported(plan->host.w, y2, v2)) ? v2 : -1;
+    const xmhw::Route r = plan_route(plan, 4);
+    *layout = r.n ? r.launch[0].layout : -1;
     return XMHW_OK;
 }
 // deprecated aliases (rounds 2 and 3)
@@ -1406,7 +1143,8 @@ int xmhw_plan_set_ring2(xmhw_plan* plan, int32_t variant) { return xmhw_plan_set
 int xmhw_plan_ring2_in_use(const xmhw_plan* plan, int32_t* variant) { return xmhw_plan_layout_in_use(plan, variant); }
 int xmhw_plan_f64_mode(const xmhw_plan* plan, int32_t* variant) {
     if (!plan || !variant) return fail(XMHW_ERR_INVALID, "NULL argument");
-    *variant = resolve_kernel(plan, 8) == XMHW_KERNEL_RING ? x64_choice(plan).variant : -1;
+    const xmhw::Route r = plan_route(plan, 8);      // (the last launch: the 64-bit mode, or the generic kernel)
+    *variant = r.n ? r.launch[r.n - 1].layout : -1;
     return XMHW_OK;
 }
 int xmhw_plan_destroy(xmhw_plan* plan) {
@@ -1418,7 +1156,10 @@ int xmhw_plan_info(const xmhw_plan* plan, int32_t* D, int32_t* ntracks, int32_t*
     if (!plan) return fail(XMHW_ERR_INVALID, "plan is NULL");
     if (D) *D = plan->host.D;
     if (ntracks) *ntracks = plan->host.ntracks;
-    if (kernel) *kernel = resolve_kernel(plan, 4);
+    if (kernel) {
+        const xmhw::Route r = plan_route(plan, 4);
+        *kernel = !r.n ? -1 : r.launch[0].family == xmhw::Family::Generic ? XMHW_KERNEL_GENERIC : XMHW_KERNEL_RING;
+    }
     if (nsteps) *nsteps = plan->host.nsteps;
     if (step_min) *step_min = plan->host.step_min;
     return XMHW_OK;
@@ -1432,7 +1173,7 @@ int xmhw_plan_set_kernel(xmhw_plan* plan, int32_t kernel) {
     if (!plan) return fail(XMHW_ERR_INVALID, "plan is NULL");
     if (kernel < XMHW_KERNEL_AUTO || kernel > XMHW_KERNEL_GENERIC)
         return fail(XMHW_ERR_INVALID, "unknown kernel selector");
-    plan->host.kernel_choice = kernel;
+    plan->settings.kernel_choice = kernel;
     return XMHW_OK;
 }
 int xmhw_plan_set_timing(xmhw_plan* plan, int32_t enable) {
@@ -1452,15 +1193,15 @@ int xmhw_plan_kernel_ms(xmhw_plan* plan, int32_t calls_back, float* ms) {
 }
 int xmhw_plan_set_narrowing(xmhw_plan* plan, int32_t enable) {
     if (!plan) return fail(XMHW_ERR_INVALID, "plan is NULL");
-    plan->narrowing = enable != 0;
+    plan->settings.narrowing = enable != 0;
     return XMHW_OK;
 }
 int xmhw_plan_narrowed(xmhw_plan* plan, int32_t* narrowed_out) {
     if (!plan || !narrowed_out) return fail(XMHW_ERR_INVALID, "NULL argument");
     *narrowed_out = 0;
-    if (!plan->d_narrow_flag) return XMHW_OK;
+    if (!plan->dev.narrow_flag) return XMHW_OK;
     uint32_t flag = 1;
-    HIP_TRY(hipMemcpy(&flag, plan->d_narrow_flag, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&flag, plan->dev.narrow_flag, sizeof(uint32_t), hipMemcpyDeviceToHost));
     *narrowed_out = flag == 0 ? 1 : 0;
     return XMHW_OK;
 }
@@ -1473,23 +1214,42 @@ int xmhw_plan_set_chunks(xmhw_plan* plan, int32_t nchunks) {
 int xmhw_plan_chunks_in_use(const xmhw_plan* plan, int64_t C, int32_t* nchunks) {
     if (!plan || !nchunks) return fail(XMHW_ERR_INVALID, "NULL argument");
     if (C < 0) return fail(XMHW_ERR_INVALID, "bad C");
-    *nchunks = auto_chunks(plan, std::max<int64_t>(C, 1));
+    *nchunks = xmhw::ring_chunks(plan->host, plan_route(plan, 4), std::max<int64_t>(C, 1));
+    return XMHW_OK;
+}
+int xmhw_plan_route(const xmhw_plan* plan, int32_t elem_bytes, double q, int64_t C, int32_t* out, int32_t n) {
+    if (!plan || !out) return fail(XMHW_ERR_INVALID, "NULL argument");
+    if (elem_bytes != 4 && elem_bytes != 8) return fail(XMHW_ERR_INVALID, "elem_bytes must be 4 or 8");
+    if (C < 0) return fail(XMHW_ERR_INVALID, "bad C");
+    if (n < XMHW_ROUTE_WORDS) return fail(XMHW_ERR_INVALID, "out holds fewer than XMHW_ROUTE_WORDS values");
+    const xmhw::Route r = plan_route(plan, elem_bytes, q);
+    std::fill(out, out + XMHW_ROUTE_WORDS, 0);
+    out[0] = r.unsupported ? XMHW_ERR_UNSUPPORTED : XMHW_OK;
+    out[1] = r.n;
+    for (int32_t i = 0; i < r.n; ++i) {
+        const xmhw::Launch& l = r.launch[i];
+        const int32_t v[7] = {static_cast<int32_t>(l.family), l.layout, l.lanes, l.tpl, l.narrows, l.gated, l.counters};
+        std::copy(v, v + 7, out + 2 + 7 * i);
+    }
+    out[23] = xmhw::ring_chunks(plan->host, r, std::max<int64_t>(C, 1));
+    out[24] = xmhw::sorted_pick_yps(plan->host.w, plan->host.ntracks) == 0
+                  ? 0 : static_cast<int32_t>(xmhw::sorted_pieces(plan->host, r, C));
     return XMHW_OK;
 }
 int xmhw_debug_stats_available(void) { return xmhw::ring_stats_built() ? 1 : 0; }
 int xmhw_plan_debug_stats_n(xmhw_plan* plan, int enable, uint64_t* out, int32_t n) {
     if (!plan) return fail(XMHW_ERR_INVALID, "plan is NULL");
     if (out && n <= 0) return fail(XMHW_ERR_INVALID, "n must be > 0");
-    if (enable && !plan->d_stats) {
-        HIP_TRY(hipMalloc(&plan->d_stats, 16 * sizeof(unsigned long long)));
-        HIP_TRY(hipMemset(plan->d_stats, 0, 16 * sizeof(unsigned long long)));
+    if (enable && !plan->dev.stats) {
+        HIP_TRY(hipMalloc(&plan->dev.stats, 16 * sizeof(unsigned long long)));
+        HIP_TRY(hipMemset(plan->dev.stats, 0, 16 * sizeof(unsigned long long)));
     }
     if (out) {
-        if (!plan->d_stats) return fail(XMHW_ERR_INVALID, "stats not enabled");
+        if (!plan->dev.stats) return fail(XMHW_ERR_INVALID, "stats not enabled");
         unsigned long long all[16];
         HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipMemcpy(all, plan->d_stats, sizeof(all), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemset(plan->d_stats, 0, sizeof(all)));
+        HIP_TRY(hipMemcpy(all, plan->dev.stats, sizeof(all), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemset(plan->dev.stats, 0, sizeof(all)));
         for (int32_t i = 0; i < std::min<int32_t>(n, 16); ++i) out[i] = all[i];
     }
     return XMHW_OK;
@@ -1519,10 +1279,7 @@ int xmhw_plan_sorted_info(const xmhw_plan* plan, int64_t C, int32_t* keys_per_li
     if (k == 0) return fail(XMHW_ERR_UNSUPPORTED, "the sorted-list kernel is not instantiated for this window / record length");
     if (keys_per_list) *keys_per_list = k;
     if (lds_bytes_per_wave) *lds_bytes_per_wave = xmhw::sorted_lds_bytes(plan->host.w, plan->host.ntracks);
-    if (pieces) {
-        const int64_t waves = (std::max<int64_t>(C, 1) + 31) / 32;
-        *pieces = static_cast<int32_t>(plan->host.nchunks_req > 0 ? plan->host.nchunks_req : (1536 + waves - 1) / waves);
-    }
+    if (pieces) *pieces = static_cast<int32_t>(xmhw::sorted_pieces(plan->host, plan_route(plan, 4), C));
     return XMHW_OK;
 }
 
@@ -1568,10 +1325,9 @@ int xmhw_clim_raw_i16(xmhw_plan* plan, const int16_t* codes, int64_t C, int64_t 
     if (C == 0) return XMHW_OK;
     if (!codes || !thresh || !seas) return fail(XMHW_ERR_INVALID, "NULL device buffer");
     // the codes are read in place by the sorted-list kernel and its recomputation only: the plans and quantiles those
-    // serve (w = 5, 9..48 tracks, quantile >= 0.85).  Anything else: xmhw_decode() + xmhw_clim_raw_f32 / _f64.
-    int rc = upload(plan, C);
-    if (rc != XMHW_OK) return rc;
-    if (!(plan->nchunks_s > 0 && sorted_serves(q)))
+    // serve (w = 5, 9..48 tracks, quantile >= 0.85 or <= 0.15).  Anything else: xmhw_decode() + xmhw_clim_raw_f32 / _f64.
+    const xmhw::Route route = call_route(plan, 4, q);
+    if (!route.n || route.launch[0].family != xmhw::Family::Sorted)
         return fail(XMHW_ERR_UNSUPPORTED, "packed input runs on the sorted-list kernel only (w = 5, 9..48 tracks, quantile >= 0.85 or <= 0.15): "
                                          "decode the series (xmhw_decode) and call xmhw_clim_raw_f32 / _f64");
     xmhw::PackedI16 pk;
@@ -1595,23 +1351,15 @@ int xmhw_clim_raw_i16(xmhw_plan* plan, const int16_t* codes, int64_t C, int64_t 
         kneg = (negate ? 1 : 0) ^ (scale_factor < 0.0 ? 1 : 0);
     }
     pk.key_neg = kneg;
+    Ready rd;
+    const int rc = ensure(plan, route, C, true, &rd);
+    if (rc != XMHW_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const xmhw::Plan& h = plan->host;
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    if (plan->timing) {
-        const int slot = static_cast<int>(plan->tcalls % 16);
-        for (int i = 0; i < 2; ++i)
-            if (!plan->tev[2 * slot + i]) HIP_TRY(hipEventCreate(&plan->tev[2 * slot + i]));
-        t0 = plan->tev[2 * slot];
-        t1 = plan->tev[2 * slot + 1];
-        plan->tcalls++;
-    }
-    hipError_t e = hipSuccess;
-    if (t0) e = hipEventRecord(t0, st);
-    if (e == hipSuccess)
-        e = xmhw::launch_sorted_i16(codes, pk, C, ld, h.T, plan->d_table_s, plan->d_sflags_s, plan->d_chunks_s, plan->nchunks_s,
-                                    h.w, plan->yps_s, h.ntracks, q, kneg, thresh, seas, ldo, st);
-    if (e == hipSuccess && t1) e = hipEventRecord(t1, st);
+    const hipError_t e = timed_launch(rd, st, [&] {
+        return xmhw::launch_sorted_i16(codes, pk, C, ld, h.T, rd.table[0], rd.dev.sflags_s, rd.dev.chunks_s, rd.dev.nchunks_s, h.w,
+                                       route.launch[0].tpl, h.ntracks, q, kneg, thresh, seas, ldo, st);
+    });
     if (e != hipSuccess) return hip_fail(e, "packed climatology launch");
     return XMHW_OK;
 }

@@ -44,8 +44,8 @@ hipError_t launch_ring_f32(const float* ts, int64_t C, int64_t ld, const uint32_
                            double* seas, int64_t ldo, hipStream_t stream,
                            unsigned long long* stats = nullptr);
 
-// second-generation float32 ring kernel (kernels_ring2.hip): 8 lanes per cell, tracks dealt y-major;
-// variant bit 0 = 8-bit SAD probes, bit 1 = extraction skips empty ring positions
+// second-generation float32 ring kernel (kernels_ring2.hip): tracks dealt y-major; variant = its layouts 8 / 10 / 12
+// (8 / 4 / 16 lanes per cell; route.cpp maps every layout number to its kernel generation and lanes)
 int32_t ring2_pick_yps(int32_t w, int32_t ntracks, int32_t variant);   // tracks per lane, 0 if not instantiated
 bool ring2_narrowing_supported(int32_t w, int32_t yps, int32_t variant);   // float64 -> float32 narrowing instantiation exists
 hipError_t launch_narrow_probe(const double* ts, int64_t Tn, int64_t C, int64_t ld, uint32_t* narrow_flag, hipStream_t stream);
@@ -61,7 +61,6 @@ hipError_t launch_ring2_f64(const double* ts, int64_t C, int64_t ld, int64_t Tn,
                             int32_t w, int32_t yps, int32_t ntracks, int32_t variant, double q, int negate,
                             double* thresh, double* seas, int64_t ldo, hipStream_t stream, const uint32_t* run_flag);
 bool ring_stats_built();                                                // the counter twins exist (-DXMHW_RING_STATS)
-int32_t ring2_subs(int32_t variant);                                    // lanes per cell of that variant
 hipError_t launch_ring2_f32(const float* ts, int64_t C, int64_t ld, int64_t Tn, const uint32_t* table,
                             const uint32_t* sflags, int32_t step_min, const DevChunk* chunks, int32_t nchunks,
                             int32_t w, int32_t yps, int32_t ntracks, int32_t variant, double q, int negate,
@@ -69,7 +68,7 @@ hipError_t launch_ring2_f32(const float* ts, int64_t C, int64_t ld, int64_t Tn, 
                             unsigned long long* stats = nullptr);
 
 // third-generation float32 ring kernel (kernels_ring3.hip): per-cell histogram in LDS + band compaction;
-// 8 or 4 lanes per cell (ring2 variants 20 and 21), w = 5
+// 8, 4 or 2 lanes per cell (layouts 20, 21 and 22), w = 5
 int32_t ring3_pick_yps(int32_t w, int32_t ntracks, int32_t subs);
 bool ring3_supported(int32_t w, int32_t yps, int32_t subs);
 hipError_t launch_ring3_f32(const float* ts, int64_t C, int64_t ld, int64_t Tn, const uint32_t* table,
@@ -97,7 +96,7 @@ hipError_t launch_sorted_i16(const int16_t* codes, const PackedI16& pk, int64_t 
                              int64_t ldo, hipStream_t stream);
 
 // fourth-generation float32 ring kernel (kernels_ring4.hip): a windowed key store in LDS instead of histogram + band
-// compaction; same lane layouts and step tables as the third generation (ring2 variants 30 / 31 / 32 = 8 / 4 / 2 lanes)
+// compaction; same lane layouts and step tables as the third generation (layouts 30 / 31 / 32 = 8 / 4 / 2 lanes)
 int32_t ring4_pick_yps(int32_t w, int32_t ntracks, int32_t subs);
 bool ring4_supported(int32_t w, int32_t yps, int32_t subs);
 bool ring4_stats_built();

@@ -1216,8 +1216,8 @@ struct Ring2Entry { int w, yps, subs, variant; Ring2Kernel fn, fn_stats; Ring2Ke
 #define XMHW_R2N(W, Y, S, V, PB, JX, JM) {W, Y, S, V, clim_ring2_f32<W, Y, PB, JX, JM, S, false>, XMHW_R2S(W, Y, PB, JX, JM, S), \
                                           clim_ring2_f32<W, Y, PB, JX, JM, S, false, double>,             \
                                           clim_ring2_f32<W, Y, PB, JX, JM, S, false, double, 1>}
-// (narrowing only: the 64-bit mode would spill heavily at 66 or more keys per lane; those plans keep the
-// round-1 float64 kernel)
+// (narrowing only: the 64-bit mode would spill heavily at 66 or more keys per lane; genuinely float64 samples of
+// those plans run on another layout's 64-bit mode)
 #define XMHW_R2M(W, Y, S, V, PB, JX, JM) {W, Y, S, V, clim_ring2_f32<W, Y, PB, JX, JM, S, false>, XMHW_R2S(W, Y, PB, JX, JM, S), \
                                           clim_ring2_f32<W, Y, PB, JX, JM, S, false, double>, nullptr}
 // 16 lanes per cell, 64-bit mode only (variant 12): genuinely float64 samples of plans with more keys per lane
@@ -1267,36 +1267,21 @@ const Ring2Entry kRing2[] = {
 #undef XMHW_R2M
 #undef XMHW_R2X
 #undef XMHW_R2L
-const Ring2Entry* find_ring2(int32_t w, int32_t yps, int32_t subs, int32_t variant) {
+// (a variant has one lane count: its entries differ in the tracks per lane only)
+const Ring2Entry* find_ring2(int32_t w, int32_t yps, int32_t variant) {
     for (const auto& e : kRing2)
-        if (e.w == w && e.yps == yps && e.subs == subs && e.variant == variant) return &e;
+        if (e.w == w && e.yps == yps && e.variant == variant) return &e;
     return nullptr;
 }
 }  // namespace
 
-// variants 20 / 21 / 22: the third-generation kernel (kernels_ring3.hip) on 8 / 4 / 2 lanes per cell; 30 / 31 / 32: the
-// round-4 key-store experiment (kernels_ring4.hip, built with `make RING4=1` only: profiles/r4_store_experiment.txt)
-int32_t ring2_subs(int32_t variant) {
-    if (variant >= 20) return variant % 10 == 2 ? 2 : variant % 10 == 1 ? 4 : 8;
-    return variant == 12 ? 16 : (variant == 7 || variant >= 9) ? 4 : 8;
-}
-
 int32_t ring2_pick_yps(int32_t w, int32_t ntracks, int32_t variant) {
-    const int32_t subs = ring2_subs(variant);
-#ifdef XMHW_RING4
-    if (variant >= 30) return ring4_pick_yps(w, ntracks, subs);
-#else
-    if (variant >= 30) return 0;
-#endif
-    if (variant >= 20) return ring3_pick_yps(w, ntracks, subs);
-    int32_t best = 0;
+    const Ring2Entry* best = nullptr;
     for (const auto& e : kRing2)
-        if (e.w == w && e.variant == (variant < 0 ? 8 : variant) && e.subs == subs && e.yps * subs >= ntracks &&
-            (best == 0 || e.yps < best))
-            best = e.yps;
+        if (e.w == w && e.variant == variant && e.yps * e.subs >= ntracks && (!best || e.yps < best->yps)) best = &e;
     // padding may only sit in the last slot of a lane
-    if (best && (best - 1) * subs >= ntracks) return 0;
-    return best;
+    if (best && (best->yps - 1) * best->subs >= ntracks) return 0;
+    return best ? best->yps : 0;
 }
 
 hipError_t launch_ring2_f32(const float* ts, int64_t C, int64_t ld, int64_t Tn, const uint32_t* table,
@@ -1304,21 +1289,10 @@ hipError_t launch_ring2_f32(const float* ts, int64_t C, int64_t ld, int64_t Tn, 
                             int32_t w, int32_t yps, int32_t ntracks, int32_t variant, double q, int negate,
                             double* thresh, double* seas, int64_t ldo, hipStream_t stream,
                             unsigned long long* stats) {
-    const int32_t subs = ring2_subs(variant);
-#ifdef XMHW_RING4
-    if (variant >= 30)
-        return launch_ring4_f32(ts, C, ld, Tn, table, sflags, step_min, chunks, nchunks, w, yps, subs, ntracks, q, negate,
-                                thresh, seas, ldo, stream, stats);
-#else
-    if (variant >= 30) return hipErrorInvalidValue;
-#endif
-    if (variant >= 20)
-        return launch_ring3_f32(ts, C, ld, Tn, table, sflags, step_min, chunks, nchunks, w, yps, subs, ntracks, q, negate,
-                                thresh, seas, ldo, stream, stats);
-    const Ring2Entry* e = find_ring2(w, yps, subs, variant);
+    const Ring2Entry* e = find_ring2(w, yps, variant);
     if (!e || !e->fn) return hipErrorInvalidValue;
     if (C <= 0 || nchunks <= 0) return hipSuccess;
-    const int64_t cells_per_block = (64 / subs) * kWaves2;
+    const int64_t cells_per_block = (64 / e->subs) * kWaves2;
     dim3 grid(static_cast<unsigned>((C + cells_per_block - 1) / cells_per_block), static_cast<unsigned>(nchunks));
     const bool twin = stats != nullptr && e->fn_stats != nullptr;
     hipLaunchKernelGGL(twin ? e->fn_stats : e->fn, grid, dim3(64 * kWaves2), 0, stream, ts, C, ld, Tn, table, sflags, step_min,
@@ -1328,18 +1302,12 @@ hipError_t launch_ring2_f32(const float* ts, int64_t C, int64_t ld, int64_t Tn, 
 }
 
 bool ring2_f32_supported(int32_t w, int32_t yps, int32_t variant) {
-#ifdef XMHW_RING4
-    if (variant >= 30) return ring4_supported(w, yps, ring2_subs(variant));
-#else
-    if (variant >= 30) return false;
-#endif
-    if (variant >= 20) return ring3_supported(w, yps, ring2_subs(variant));
-    const Ring2Entry* e = find_ring2(w, yps, ring2_subs(variant), variant);
+    const Ring2Entry* e = find_ring2(w, yps, variant);
     return e != nullptr && e->fn != nullptr;
 }
 
 bool ring2_x64_supported(int32_t w, int32_t yps, int32_t variant) {
-    const Ring2Entry* e = find_ring2(w, yps, ring2_subs(variant), variant);
+    const Ring2Entry* e = find_ring2(w, yps, variant);
     return e != nullptr && e->fn_x64 != nullptr;
 }
 
@@ -1349,15 +1317,10 @@ hipError_t launch_ring2_f64(const double* ts, int64_t C, int64_t ld, int64_t Tn,
                             const uint32_t* sflags, int32_t step_min, const DevChunk* chunks, int32_t nchunks,
                             int32_t w, int32_t yps, int32_t ntracks, int32_t variant, double q, int negate,
                             double* thresh, double* seas, int64_t ldo, hipStream_t stream, const uint32_t* run_flag) {
-    const int32_t subs = ring2_subs(variant);
-    if (variant >= 30) return hipErrorInvalidValue;
-    if (variant >= 20)
-        return launch_ring3_f64(ts, C, ld, Tn, table, sflags, step_min, chunks, nchunks, w, yps, subs, ntracks, q, negate,
-                                thresh, seas, ldo, stream, run_flag);
-    const Ring2Entry* e = find_ring2(w, yps, subs, variant);
+    const Ring2Entry* e = find_ring2(w, yps, variant);
     if (!e || !e->fn_x64) return hipErrorInvalidValue;
     if (C <= 0 || nchunks <= 0) return hipSuccess;
-    const int64_t cells_per_block = (64 / subs) * kWaves2;
+    const int64_t cells_per_block = (64 / e->subs) * kWaves2;
     dim3 grid(static_cast<unsigned>((C + cells_per_block - 1) / cells_per_block), static_cast<unsigned>(nchunks));
     hipLaunchKernelGGL(e->fn_x64, grid, dim3(64 * kWaves2), 0, stream, ts, C, ld, Tn, table, sflags, step_min, chunks, q,
                        negate, ntracks, thresh, seas, ldo, static_cast<unsigned long long*>(nullptr),
@@ -1366,9 +1329,7 @@ hipError_t launch_ring2_f64(const double* ts, int64_t C, int64_t ld, int64_t Tn,
 }
 
 bool ring2_narrowing_supported(int32_t w, int32_t yps, int32_t variant) {
-    if (variant >= 30) return false;
-    if (variant >= 20) return ring3_narrowing_supported(w, yps, ring2_subs(variant));
-    const Ring2Entry* e = find_ring2(w, yps, ring2_subs(variant), variant);
+    const Ring2Entry* e = find_ring2(w, yps, variant);
     return e != nullptr && e->fn_narrow != nullptr;
 }
 
@@ -1379,15 +1340,10 @@ hipError_t launch_ring2_f32_narrowing(const double* ts, int64_t C, int64_t ld, i
                                       int32_t nchunks, int32_t w, int32_t yps, int32_t ntracks, int32_t variant,
                                       double q, int negate, double* thresh, double* seas, int64_t ldo,
                                       hipStream_t stream, uint32_t* narrow_flag) {
-    const int32_t subs = ring2_subs(variant);
-    if (variant >= 30) return hipErrorInvalidValue;
-    if (variant >= 20)
-        return launch_ring3_f32_narrowing(ts, C, ld, Tn, table, sflags, step_min, chunks, nchunks, w, yps, subs, ntracks, q,
-                                          negate, thresh, seas, ldo, stream, narrow_flag);
-    const Ring2Entry* e = find_ring2(w, yps, subs, variant);
+    const Ring2Entry* e = find_ring2(w, yps, variant);
     if (!e || !e->fn_narrow || !narrow_flag) return hipErrorInvalidValue;
     if (C <= 0 || nchunks <= 0) return hipSuccess;
-    const int64_t cells_per_block = (64 / subs) * kWaves2;
+    const int64_t cells_per_block = (64 / e->subs) * kWaves2;
     dim3 grid(static_cast<unsigned>((C + cells_per_block - 1) / cells_per_block), static_cast<unsigned>(nchunks));
     hipLaunchKernelGGL(e->fn_narrow, grid, dim3(64 * kWaves2), 0, stream, ts, C, ld, Tn, table, sflags, step_min, chunks, q,
                        negate, ntracks, thresh, seas, ldo, static_cast<unsigned long long*>(nullptr), narrow_flag);

@@ -136,33 +136,6 @@ std::vector<Chunk> Plan::make_chunks(int32_t nchunks) const {
     return out;
 }
 
-std::vector<Plan::Segment> Plan::sorted_segments() const {
-    const std::vector<uint32_t> tab = ring_table(1, ntracks);      // [step][track]
-    std::vector<uint8_t> regular(static_cast<size_t>(D), 1);
-    for (int32_t s = 0; s < D; ++s) {
-        bool ok = true;
-        for (int32_t k = 0; k < ntracks && ok; ++k) {
-            bool any_valid = false;
-            for (int32_t j = s - (R - 1); j <= s; ++j) {
-                const uint32_t e = tab[static_cast<size_t>(j - step_min) * ntracks + k];
-                if ((e >> 1) == kCodeHold) ok = false;
-                any_valid = any_valid || (e >> 1) >= 2u;
-            }
-            const uint32_t es = tab[static_cast<size_t>(s - step_min) * ntracks + k];
-            if (any_valid && !(es & 1u)) ok = false;
-        }
-        regular[s] = ok ? 1 : 0;
-    }
-    std::vector<Segment> out;
-    for (int32_t s = 0; s < D;) {
-        int32_t e = s;
-        while (e < D && regular[e] == regular[s]) ++e;
-        out.push_back({s, e, regular[s] != 0});
-        s = e;
-    }
-    return out;
-}
-
 Plan::SortedPlan Plan::sorted_plan(int32_t ntp, int32_t min_rows_per_piece, int64_t pieces_wanted) const {
     SortedPlan out;
     if (ntracks > ntp || D <= 0) return out;

@@ -48,7 +48,6 @@ struct Plan {
     int32_t max_centres = 0;         // max centres in a row
     int32_t step_min = 0;            // -(R-1)
     int32_t nsteps = 0;              // D + R - 1
-    int32_t kernel_choice = 0;       // XMHW_KERNEL_* requested (0 auto)
     int32_t nchunks_req = 0;         // 0 auto
 
     std::string error;
@@ -65,13 +64,8 @@ struct Plan {
     std::vector<Chunk> make_chunks(int32_t nchunks) const;
     // first step a ring kernel must execute so that every track has pushed R-1 samples before row `begin`
     int32_t warm_start_for(int32_t begin) const;
-    // Rows the sorted-list kernel (kernels_sorted.hip) can serve.  Its pool is the union of the R last ROW-LISTS
-    // (what all tracks pushed at one step), so row s is REGULAR iff for every real track no step in [s-R+1, s] is a
-    // HOLD and a track that pushed a valid sample in that span is part of the row's pool.  Returns the maximal runs
-    // of rows, alternating, in ascending order.
-    struct Segment { int32_t begin, end; bool regular; };
-    std::vector<Segment> sorted_segments() const;
-    // The sorted-list kernel's own chunks and step table.  The row axis is cut wherever the set of tracks that are part
+    // The sorted-list kernel's (kernels_sorted.hip) own chunks and step table.  Its pool is the union of the R last
+    // ROW-LISTS (what all tracks pushed at one step).  The row axis is cut wherever the set of tracks that are part
     // of the pool changes (a held step -- doy 60 in the non-leap years --, the first / last centre of a partial year);
     // inside a chunk that set S is constant and every track of S pushes at every row.  A chunk gets its OWN table rows
     // (warm-up + output rows): a track of S warms up with its R-1 last pushes before the chunk (held steps skipped, so

@@ -171,7 +171,12 @@ PYBIND11_MODULE(_xmhw_hip, m) {
     m.def("sorted_device_ok", []() { int32_t v = 0; check(xmhw_sorted_device_ok(&v)); return v != 0; });
     m.def("plan_ring2_in_use", [](uintptr_t p) { int32_t v = -1; check(xmhw_plan_ring2_in_use(pp(p), &v)); return v; });
     m.def("plan_f64_mode", [](uintptr_t p) { int32_t v = -1; check(xmhw_plan_f64_mode(pp(p), &v)); return v; });
-    m.def("plan_set_ring2", [](uintptr_t p, int variant) { check(xmhw_plan_set_ring2(pp(p), variant)); });
+    m.def("plan_route", [](uintptr_t p, int elem_bytes, double q, int64_t C) {
+        py::array_t<int32_t> out(XMHW_ROUTE_WORDS);
+        check(xmhw_plan_route(pp(p), elem_bytes, q, C, out.mutable_data(), XMHW_ROUTE_WORDS));
+        return out;
+    });
+    m.def("plan_set_ring2",[](uintptr_t p, int variant) { check(xmhw_plan_set_ring2(pp(p), variant)); });
 
     m.def("clim_raw", [](uintptr_t plan, uintptr_t ts, int itemsize, int64_t C, int64_t ld, double q, int negate,
                          uintptr_t th, uintptr_t se, int64_t ldo, uintptr_t stream) {

@@ -230,6 +230,8 @@ def _ptr(b):
 # include/xmhw_amd.h: XMHW_LAYOUT_*
 LAYOUTS = {"auto": -2, "ring1": -1, "ring2_8lane": 8, "ring2_4lane": 10, "ring2_16lane": 12,
            "ring3_8lane": 20, "ring3_4lane": 21, "ring3_2lane": 22, "sorted": 40}
+# include/xmhw_amd.h: XMHW_ROUTE_*
+ROUTE_FAMILIES = ("generic", "ring1", "ring2", "ring3", "ring4", "sorted")
 
 
 class Plan:
@@ -271,6 +273,19 @@ class Plan:
         """layout variant of the 64-bit mode float64 samples will run on (-1: generic kernel)"""
         return int(self._h.plan_f64_mode(self.handle))
 
+    def route(self, dtype, q, C=1):
+        """what a clim_raw() of `dtype` samples with quantile q over C cells launches (xmhw_plan_route): a dict with
+        `launches`, a list of dicts (family, layout, lanes, tracks_per_lane, narrows, gated, counters) in launch order,
+        `chunks` and `sorted_pieces`; `supported` False (and no launches) where the call would be refused"""
+        r = [int(v) for v in self._h.plan_route(self.handle, np.dtype(dtype).itemsize, float(q), int(C))]
+        keys = ("family", "layout", "lanes", "tracks_per_lane", "narrows", "gated", "counters")
+        launches = [dict(zip(keys, r[2 + 7 * i:9 + 7 * i])) for i in range(r[1])]
+        for la in launches:
+            la["family"] = ROUTE_FAMILIES[la["family"]]
+            for k in keys[4:]:
+                la[k] = bool(la[k])
+        return {"supported": r[0] == 0, "launches": launches, "chunks": r[23], "sorted_pieces": r[24]}
+
     def narrowed(self):
         """True if the last float64 clim_raw() of this plan ran on the float32 ring kernel (every
         sample float32-representable)."""
@@ -289,6 +304,11 @@ class Plan:
             self.destroy()
         except Exception:
             pass
+
+
+def _first_family(route):
+    """the kernel family of a Plan.route()'s first launch (None: the call would be refused)"""
+    return route["launches"][0]["family"] if route["launches"] else None
 
 
 def clim_raw(plan, ts_dev, itemsize, C, q, negate, thresh_dev, seas_dev, ld=None, ldo=None, stream=0):
@@ -839,7 +859,7 @@ def calc_clim_grid_device(stacked, doy, anynans, pctile, windowHalfWidth, smooth
         # decode pass.  Not with maxPadLength (interpolation needs decoded samples) nor when detect() will want the decoded
         # series next (resident).  XMHW_PACKED_DIRECT=0 turns it off.
         direct = (is_packed(stacked) and stacked.dtype.kind == "i" and stacked.dtype.itemsize == 2 and pad is None
-                  and resident is None and kernel == "auto" and (pctile / 100.0 >= 0.85 or pctile / 100.0 <= 0.15) and plan.layout_in_use() == LAYOUTS["sorted"]
+                  and resident is None and kernel == "auto" and _first_family(plan.route(np.float32, pctile / 100.0)) == "sorted"
                   and _os.environ.get("XMHW_PACKED_DIRECT", "1") != "0")
         recipe = packed_recipe(stacked) if direct else None
         # slab k+1 is uploaded (and decoded) by a second thread while slab k computes
