@@ -934,6 +934,58 @@ int xmhw_class_days_accumulate_f64(const double *ts_dev, int64_t T, int64_t C, i
                                    int64_t *n_range_dev, void *stream);
 int xmhw_class_days_finish(int32_t K, int64_t C, double *intensity_max_dev, int64_t ldo, void *stream);
 
+/* ---- mhw_cooccurrence(): per-cell joint event days of two detections, by class of time steps and lag ---- *
+ * Compound extremes (joint frequency, likelihood multiplication factor) and verification (the 2x2 contingency table
+ * per cell and lead) reduce to the same integers.
+ * Two event tables A and B lie on the same time axis of T steps.  For column c and step t, A[t][c] = 1 iff some table
+ * row of that cell has start <= t <= end (gap days of joined events included, as detect() stores them).  B is defined
+ * the same way.  For a lag l (any int32) the pair (t, l) is VALID iff 0 <= t + l < T.  Then:
+ *   Bl[t] = B[t + l] on valid pairs and 0 otherwise.
+ *   J[t]  = A[t] & Bl[t], with J[-1] = 0.
+ * class_of_t[T] holds int32 labels in [-1, K); -1 counts nowhere.  A pair belongs to the class of t, which is A's step.
+ * For every class k, lag index i and column c, summed over the valid pairs with class_of_t[t] == k:
+ *   counts[k][i][0][c]   both     A[t] & Bl[t]
+ *   counts[k][i][1][c]   a_only   A[t] & ~Bl[t]
+ *   counts[k][i][2][c]   b_only   ~A[t] & Bl[t]
+ *   counts[k][i][3][c]   onsets   J[t] & ~J[t-1]: the first steps of joint runs
+ * The onset test looks at t - 1 whatever the class of t - 1 is.  `neither` is not computed on the device: it is
+ * n_pairs[k][i] - both - a_only - b_only, where n_pairs (the number of valid pairs of class k) is computed on the host
+ * from the labels and the lag.  All counts are int32 and <= T < 2^31.  A lag with |l| >= T gives zeros everywhere.
+ * Everything is an integer sum: the result is exact and does not depend on the time blocks, the lag groups, the slabs
+ * or the schedule.
+ *
+ *  1. xmhw_event_table_bits turns a table into a bitmap, one bit per sample, word-major and cells-minor (the layout of
+ *     xmhw_exceed_bits_*): column j is filled from rows offsets[cell[j]] .. offsets[cell[j] + 1] of start_dev / end_dev
+ *     (cell may skip and reorder table cells) and written as bits[w * ldb + j], w < W = ceil(T / 64).  Every word of
+ *     columns 0..C-1 is written, zero where there is no event: whatever the buffer held before is gone.  The bits at
+ *     t >= T of the last word are 0; columns >= C are never touched.  Lane = column: a lane owns its column, so plain
+ *     vector stores and no atomics.  The caller guarantees 0 <= start <= end < T and rows of a cell in time order (by
+ *     start), as detect() stores them; the kernel relies on it.
+ *  2. xmhw_cooccur_init zeroes columns 0..C-1 of the accumulator counts_dev, int32 [K][L][XMHW_COOCCUR_CHANNELS][ldo].
+ *  3. xmhw_cooccur_accumulate handles one slab of C cells and ADDS: calls for consecutive slabs follow each other on one
+ *     stream without a read-back, and a slab addresses its columns by pointer offset.  a_bits_dev / b_bits_dev are
+ *     bitmaps of step 1 (lda, ldb >= C; bits at t >= T zero).  Lane = cell, workgroup = 256 cells x a block of whole
+ *     64-step words, grid.z = a group of at most 8 lags; the labels become a per-word segment list on the device, cached
+ *     by content; the addends of the current class stay in registers and leave as integer atomics without a return value
+ *     when the class changes and at the end of the block.  L = 64 is eight passes over the bitmaps.
+ * ldo >= C; columns past C are never touched.  Refusals happen before anything is touched: K < 1,
+ * K > XMHW_COOCCUR_MAX_CLASSES, L < 1, L > XMHW_COOCCUR_MAX_LAGS, or T / C of 2^31 and more: XMHW_ERR_UNSUPPORTED.  A
+ * label outside [-1, K): XMHW_ERR_INVALID, checked on the host copy.  Nothing is launched for C == 0 or T == 0.  All calls
+ * are asynchronous on `stream`.  xmhw_set_cooccur_block (process-wide; tests and measurements): the words a workgroup
+ * takes per block, 0 = automatic.  Same results for every value.                                                     */
+#define XMHW_COOCCUR_MAX_CLASSES 1024
+#define XMHW_COOCCUR_MAX_LAGS    64
+#define XMHW_COOCCUR_CHANNELS    4
+int xmhw_event_table_bits(const int32_t *start_dev, const int32_t *end_dev, const int64_t *offsets_dev,
+                          const int64_t *cell_dev /* [C] */, int64_t C, int64_t T,
+                          uint64_t *bits_dev, int64_t ldb, void *stream);
+int xmhw_set_cooccur_block(int32_t words);            /* tests and measurements; 0 = automatic */
+int xmhw_cooccur_init(int32_t K, int32_t L, int64_t C, int32_t *counts_dev, int64_t ldo, void *stream);
+int xmhw_cooccur_accumulate(const uint64_t *a_bits_dev, int64_t lda, const uint64_t *b_bits_dev, int64_t ldb,
+                            int64_t T, int64_t C, const int32_t *class_of_t_host, int32_t K,
+                            const int32_t *lags_host, int32_t L,
+                            int32_t *counts_dev /* [K][L][4][ldo] */, int64_t ldo, void *stream);
+
 /* ---- the sharded path: cells split across the GPUs of a node, ONE gather at the end ------- *
  * Replaces the reference's collect, dask.compute(climls) + xr.concat(dim='cell')
  * (xmhw/xmhw.py:197, :210-211).  Cells are independent (xmhw/xmhw.py:184-196), so rank r runs the

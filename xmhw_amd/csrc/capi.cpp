@@ -392,9 +392,13 @@ struct RowsEntry {
     int device = 0;
     int32_t* d_rows = nullptr;
     std::map<std::pair<int64_t, int>, ChunkTables> chunks;      // (D, tile) -> tables
+    void* d_segs = nullptr;                                     // class labels: the per-word segment list (cooccur_segments)
+    int32_t *seg_off = nullptr, *seg_class = nullptr;
+    uint64_t* seg_mask = nullptr;
     uint64_t stamp = 0;
     ~RowsEntry() {
         if (d_rows) (void)hipFree(d_rows);
+        if (d_segs) (void)hipFree(d_segs);
         for (auto& kv : chunks)
             for (int32_t* p : {kv.second.tile_begin, kv.second.t0, kv.second.i0, kv.second.n})
                 if (p) (void)hipFree(p);
@@ -757,6 +761,56 @@ int class_days_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const 
                                               C, g_class_days_block.load(), days, isum_q, intensity_max, ldo, n_range, st);
     if (e != hipSuccess) return hip_fail(e, "class_days_accumulate launch");
     return XMHW_OK;
+}
+
+static std::atomic<int> g_cooccur_block{0};      // words a workgroup takes per block, 0 = automatic (xmhw_set_cooccur_block)
+
+static int cooccur_check_shape(int32_t K, int32_t L, int64_t Tn, int64_t C) {
+    if (K < 1 || K > xmhw::kCooccurMaxClasses)
+        return fail(XMHW_ERR_UNSUPPORTED, "cooccur: K must be in [1, " + std::to_string(xmhw::kCooccurMaxClasses) + "]");
+    if (L < 1 || L > xmhw::kCooccurMaxLags)
+        return fail(XMHW_ERR_UNSUPPORTED, "cooccur: L must be in [1, " + std::to_string(xmhw::kCooccurMaxLags) + "]");
+    if (Tn > 0x7FFFFFFFll || C > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "cooccur: 2^31 steps or cells and more");
+    return XMHW_OK;
+}
+
+// The class labels as the segment list of the accumulate kernel, built and uploaded once per label table (it hangs on
+// the table's entry of the content-keyed cache): seg_off[W + 1], then per segment -- a run of one non-negative class
+// inside one 64-step word -- its class and the mask of its bits.  One allocation: masks, offsets, classes.
+static hipError_t cooccur_segments(const RowsRef& classes, int64_t Tn) {
+    std::lock_guard<std::mutex> lock(g_cache_mu);
+    if (classes->d_segs) return hipSuccess;
+    const std::vector<int32_t>& k = classes->host;
+    const int64_t W = (Tn + 63) / 64;
+    std::vector<int32_t> off(static_cast<size_t>(W) + 1, 0), cls;
+    std::vector<uint64_t> mask;
+    for (int64_t w = 0; w < W; ++w) {
+        const int64_t t1 = std::min<int64_t>(Tn, w * 64 + 64);
+        for (int64_t t = w * 64; t < t1;) {
+            if (k[t] < 0) { ++t; continue; }
+            uint64_t m = 0;
+            const int32_t c = k[t];
+            for (; t < t1 && k[t] == c; ++t) m |= uint64_t{1} << (t & 63);
+            cls.push_back(c);
+            mask.push_back(m);
+        }
+        off[static_cast<size_t>(w) + 1] = static_cast<int32_t>(cls.size());
+    }
+    const size_t n = cls.size();
+    const size_t b_mask = sizeof(uint64_t) * n, b_off = sizeof(int32_t) * off.size(), b_cls = sizeof(int32_t) * n;
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, b_mask + b_off + b_cls + 8);
+    if (e != hipSuccess) return e;
+    char* base = static_cast<char*>(p);
+    if (n) e = hipMemcpy(base, mask.data(), b_mask, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(base + b_mask, off.data(), b_off, hipMemcpyHostToDevice);
+    if (e == hipSuccess && n) e = hipMemcpy(base + b_mask + b_off, cls.data(), b_cls, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(p); return e; }
+    classes->d_segs = p;
+    classes->seg_mask = reinterpret_cast<uint64_t*>(base);
+    classes->seg_off = reinterpret_cast<int32_t*>(base + b_mask);
+    classes->seg_class = reinterpret_cast<int32_t*>(base + b_mask + b_off);
+    return hipSuccess;
 }
 
 template <typename T>
@@ -1952,6 +2006,54 @@ int xmhw_class_days_finish(int32_t K, int64_t C, double* intensity_max, int64_t 
     if (!intensity_max) return fail(XMHW_ERR_INVALID, "NULL output buffer");
     hipError_t e = xmhw::launch_class_days_finish(K, C, intensity_max, ldo, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hip_fail(e, "class_days_finish launch");
+    return XMHW_OK;
+}
+
+int xmhw_event_table_bits(const int32_t* start, const int32_t* end, const int64_t* offsets, const int64_t* cell, int64_t C,
+                          int64_t T, uint64_t* bits, int64_t ldb, void* stream) {
+    if (T > 0x7FFFFFFFll || C > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "event_table_bits: 2^31 steps or cells and more");
+    if (T < 0 || C < 0 || ldb < C) return fail(XMHW_ERR_INVALID, "bad T/C/ldb");
+    if (C == 0 || T == 0) return XMHW_OK;
+    if (!offsets || !cell || !bits) return fail(XMHW_ERR_INVALID, "NULL buffer");
+    hipError_t e = xmhw::launch_event_table_bits(start, end, offsets, cell, C, T, bits, ldb, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "event_table_bits launch");
+    return XMHW_OK;
+}
+int xmhw_set_cooccur_block(int32_t words) {
+    if (words < 0) return fail(XMHW_ERR_INVALID, "words must be >= 0");
+    g_cooccur_block = words;
+    return XMHW_OK;
+}
+int xmhw_cooccur_init(int32_t K, int32_t L, int64_t C, int32_t* counts, int64_t ldo, void* stream) {
+    if (cooccur_check_shape(K, L, 0, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
+    if (C == 0) return XMHW_OK;
+    if (!counts) return fail(XMHW_ERR_INVALID, "NULL output buffer");
+    hipError_t e = xmhw::launch_cooccur_init(K, L, C, counts, ldo, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "cooccur_init");
+    return XMHW_OK;
+}
+int xmhw_cooccur_accumulate(const uint64_t* a_bits, int64_t lda, const uint64_t* b_bits, int64_t ldb, int64_t T, int64_t C,
+                            const int32_t* class_of_t, int32_t K, const int32_t* lags, int32_t L, int32_t* counts,
+                            int64_t ldo, void* stream) {
+    if (cooccur_check_shape(K, L, T, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (T < 0 || C < 0 || lda < C || ldb < C || ldo < C) return fail(XMHW_ERR_INVALID, "bad T/C/lda/ldb/ldo");
+    if (!lags || (T > 0 && !class_of_t)) return fail(XMHW_ERR_INVALID, "NULL class_of_t or lags");
+    for (int64_t t = 0; t < T; ++t)
+        if (class_of_t[t] < -1 || class_of_t[t] >= K) return fail(XMHW_ERR_INVALID, "class_of_t outside [-1, K)");
+    if (C == 0 || T == 0) return XMHW_OK;
+    if (!a_bits || !b_bits || !counts) return fail(XMHW_ERR_INVALID, "NULL buffer");
+    hipError_t e = hipSuccess;
+    const RowsRef classes = cached_rows(class_of_t, T, &e);         // the content-keyed cache of int32 tables
+    if (!classes) return hip_fail(e, "class table upload");
+    e = cooccur_segments(classes, T);
+    if (e != hipSuccess) return hip_fail(e, "segment table upload");
+    const RowsRef lag_table = cached_rows(lags, L, &e);
+    if (!lag_table) return hip_fail(e, "lag table upload");
+    e = xmhw::launch_cooccur_accumulate(a_bits, lda, b_bits, ldb, T, C, classes->seg_off, classes->seg_class, classes->seg_mask,
+                                        lag_table->d_rows, L, g_cooccur_block.load(), counts, ldo,
+                                        static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "cooccur_accumulate launch");
     return XMHW_OK;
 }
 

@@ -406,6 +406,26 @@ hipError_t launch_class_days_accumulate(const T* ts, int64_t Tn, int64_t C, int6
                                         double* intensity_max, int64_t ldo, int64_t* n_range, hipStream_t stream);
 hipError_t launch_class_days_finish(int32_t K, int64_t C, double* intensity_max, int64_t ldo, hipStream_t stream);
 
+// mhw_cooccurrence() (kernels_cooccur.hip): the joint event days of two detections per cell, class of time steps and lag.
+// launch_event_table_bits rasterises an event table into the one-bit-per-sample, word-major, cells-minor bitmap of
+// launch_exceed_bits: column j takes the rows offsets[cell[j]] .. offsets[cell[j] + 1] (in time order, 0 <= start <= end
+// < Tn), every word of columns 0..C-1 is written, the bits at t >= Tn are 0.  launch_cooccur_accumulate ADDS to
+// counts[k][i][0..3][c] (both, a_only, b_only, onsets; leading dimension ldo >= C) the valid pairs (t, lags[i]) of class k:
+// the classes arrive as the per-word segment list seg_off[W + 1], seg_class[], seg_mask[] (a segment = a run of one
+// non-negative class inside one 64-step word), lags[L] and the segments are DEVICE arrays here.  block_words: the words a
+// workgroup takes per block, 0 = automatic; same results for every value.
+constexpr int kCooccurMaxClasses = 1024;
+constexpr int kCooccurMaxLags = 64;
+constexpr int kCooccurChannels = 4;
+constexpr int kCooccurLagGroup = 8;
+hipError_t launch_event_table_bits(const int32_t* start, const int32_t* end, const int64_t* offsets, const int64_t* cell,
+                                   int64_t C, int64_t Tn, uint64_t* bits, int64_t ldb, hipStream_t stream);
+hipError_t launch_cooccur_init(int32_t K, int32_t L, int64_t C, int32_t* counts, int64_t ldo, hipStream_t stream);
+hipError_t launch_cooccur_accumulate(const uint64_t* a_bits, int64_t lda, const uint64_t* b_bits, int64_t ldb, int64_t Tn,
+                                     int64_t C, const int32_t* seg_off, const int32_t* seg_class, const uint64_t* seg_mask,
+                                     const int32_t* lags, int32_t L, int64_t block_words, int32_t* counts, int64_t ldo,
+                                     hipStream_t stream);
+
 // file bytes -> samples (kernels_ingest.hip): raw_type = item size of the stored type (2 int16, 4 float32,
 // 8 float64), swap = the file is big-endian, optional scale/offset (CF packing) and fill value -> NaN
 hipError_t launch_encode_i16(const float* in, int64_t rows, int64_t cols, int64_t ld_in, int16_t* out, int64_t ld_out,

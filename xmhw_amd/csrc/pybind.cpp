@@ -753,6 +753,31 @@ PYBIND11_MODULE(_xmhw_hip, m) {
     m.def("class_days_finish", [](int32_t K, int64_t C, uintptr_t intensity_max, int64_t ldo, uintptr_t stream) {
         check(xmhw_class_days_finish(K, C, static_cast<double*>(vp(intensity_max)), ldo, vp(stream)));
     }, py::arg("K"), py::arg("C"), py::arg("intensity_max"), py::arg("ldo"), py::arg("stream") = 0);
+    m.attr("COOCCUR_MAX_CLASSES") = XMHW_COOCCUR_MAX_CLASSES;
+    m.attr("COOCCUR_MAX_LAGS") = XMHW_COOCCUR_MAX_LAGS;
+    m.attr("COOCCUR_CHANNELS") = XMHW_COOCCUR_CHANNELS;
+    m.def("event_table_bits", [](uintptr_t start, uintptr_t end, uintptr_t offsets, uintptr_t cell, int64_t C, int64_t T,
+                                 uintptr_t bits, int64_t ldb, uintptr_t stream) {
+        check(xmhw_event_table_bits(static_cast<const int32_t*>(vp(start)), static_cast<const int32_t*>(vp(end)),
+                                    static_cast<const int64_t*>(vp(offsets)), static_cast<const int64_t*>(vp(cell)), C, T,
+                                    static_cast<uint64_t*>(vp(bits)), ldb, vp(stream)));
+    }, py::arg("start"), py::arg("end"), py::arg("offsets"), py::arg("cell"), py::arg("C"), py::arg("T"), py::arg("bits"),
+       py::arg("ldb"), py::arg("stream") = 0);
+    m.def("set_cooccur_block", [](int words) { check(xmhw_set_cooccur_block(words)); }, py::arg("words"));
+    m.def("cooccur_init", [](int32_t K, int32_t L, int64_t C, uintptr_t counts, int64_t ldo, uintptr_t stream) {
+        check(xmhw_cooccur_init(K, L, C, static_cast<int32_t*>(vp(counts)), ldo, vp(stream)));
+    }, py::arg("K"), py::arg("L"), py::arg("C"), py::arg("counts"), py::arg("ldo"), py::arg("stream") = 0);
+    m.def("cooccur_accumulate", [](uintptr_t a_bits, int64_t lda, uintptr_t b_bits, int64_t ldb, int64_t T, int64_t C,
+                                   i32arr class_of_t, int32_t K, i32arr lags, uintptr_t counts, int64_t ldo,
+                                   uintptr_t stream) {
+        if (class_of_t.size() != T) throw InvalidError("class_of_t length must equal T");
+        const int32_t L = static_cast<int32_t>(lags.size() > 0x7FFFFFFF ? 0x7FFFFFFF : lags.size());
+        py::gil_scoped_release r;
+        check(xmhw_cooccur_accumulate(static_cast<const uint64_t*>(vp(a_bits)), lda, static_cast<const uint64_t*>(vp(b_bits)),
+                                      ldb, T, C, class_of_t.data(), K, lags.data(), L, static_cast<int32_t*>(vp(counts)), ldo,
+                                      vp(stream)));
+    }, py::arg("a_bits"), py::arg("lda"), py::arg("b_bits"), py::arg("ldb"), py::arg("T"), py::arg("C"),
+       py::arg("class_of_t"), py::arg("K"), py::arg("lags"), py::arg("counts"), py::arg("ldo"), py::arg("stream") = 0);
     m.def("block_trend_ols", [](uintptr_t y, int32_t nstat, int32_t nb, int64_t C, int64_t ld, uintptr_t x, uintptr_t tcrit,
                                 uintptr_t out, int64_t ldo, uintptr_t stream) {
         check(xmhw_block_trend_ols(static_cast<const double*>(vp(y)), nstat, nb, C, ld, static_cast<const double*>(vp(x)),
