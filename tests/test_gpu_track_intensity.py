@@ -227,7 +227,7 @@ def test_slabs_do_not_change_a_bit(gpu, monkeypatch):
     tr = xmhw_amd.mhw_tracks(mhw, obj)
     calls = []
     add_slab = gpu._Accumulators.add_slab
-    monkeypatch.setattr(gpu._Accumulators, "add_slab", lambda self, *a, **k: (calls.append(a[3]), add_slab(self, *a, **k))[1])
+    monkeypatch.setattr(gpu._Accumulators, "add_slab", lambda self, *a, **k: (calls.append(a[0].n), add_slab(self, *a, **k))[1])
     one = xmhw_amd.mhw_track_intensity(g["temp"], g["th"], g["se"], mhw, obj, tr)
     assert len(calls) == 1
     many = xmhw_amd.mhw_track_intensity(g["temp"], g["th"], g["se"], mhw, obj, tr, max_batch_bytes=2_000_000)

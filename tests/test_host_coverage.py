@@ -194,3 +194,49 @@ def test_point_series_and_cold_spells(oisst):
     mhwc = _detect(g, thc_, sec_, oracle_detect_cells, coldSpells=True)
     assert cold.cells[..., 4].sum() == mhwc.table[:, mhwc.columns.index("duration")].sum() > 0
     assert not np.array_equal(cold.cells, mhw_coverage(g, *clims(oisst), _compute=co.coverage_cells).cells)
+
+
+def test_dense_ids():
+    from xmhw_amd.series_stage import dense_ids
+    # labels with gaps, negative labels count nowhere
+    labels = np.array([7, -3, 2, 7, 100, -1, 2], dtype=np.int64)
+    found, ids, K = dense_ids(labels, 3, "mhw_coverage", "regions")
+    npt.assert_array_equal(found, [2, 7, 100])
+    npt.assert_array_equal(ids, [1, -1, 0, 1, 2, -1, 0])
+    assert ids.dtype == np.int32 and K == 3                   # the cap exactly met
+    with pytest.raises(XmhwException, match="mhw_coverage handles at most 2 regions, got 3"):
+        dense_ids(labels, 2, "mhw_coverage", "regions")       # ... and exceeded by one
+    with pytest.raises(XmhwException, match="mhw_days_by handles at most 2 classes, got 3"):
+        dense_ids(labels, 2, "mhw_days_by", "classes")
+    # no non-negative label: nothing found, every id -1, one (empty) class
+    found, ids, K = dense_ids(np.array([-1, -5, -1], dtype=np.int64), 1, "x", "regions")
+    assert found.shape == (0,) and K == 1
+    npt.assert_array_equal(ids, [-1, -1, -1])
+    found, ids, K = dense_ids(np.zeros(0, dtype=np.int64), 1, "x", "regions")
+    assert found.shape == (0,) and ids.shape == (0,) and K == 1
+
+
+def test_regions_of_result():
+    from xmhw_amd.series_stage import dense_ids, regions_of_result
+    labels = np.array([5, 5, 9, 9, 2, -1, 2, 40], dtype=np.int64)
+    keep = np.array([True, False, False, False, True, True, True, True])     # region 9 has only land cells
+    w = np.array([3, 1000, 1000, 1000, 4, 1000, 0, 1 << 31], dtype=np.int64)
+    found, rid, Rc = dense_ids(labels, 1024, "x", "regions")
+    sel, ncells, total, region = regions_of_result(keep, rid, w, found)
+    npt.assert_array_equal(found, [2, 5, 9, 40])
+    npt.assert_array_equal(sel, [True, True, False, True])
+    npt.assert_array_equal(region, [2, 5, 40])
+    npt.assert_array_equal(ncells, [2, 1, 1])
+    npt.assert_array_equal(total, [4, 3, 1 << 31])
+    assert ncells.dtype == np.int64 and total.dtype == np.int64 and Rc == 4
+    # a plain loop gives the same
+    for j, r in enumerate(region):
+        mine = [i for i in range(8) if keep[i] and labels[i] == r]
+        assert ncells[j] == len(mine) and total[j] == sum(int(w[i]) for i in mine)
+    # every cell excluded: one empty region 0, nothing to select
+    found, rid, Rc = dense_ids(np.full(8, -1, dtype=np.int64), 1024, "x", "regions")
+    sel, ncells, total, region = regions_of_result(keep, rid, w, found)
+    assert sel is None and Rc == 1
+    npt.assert_array_equal(region, [0])
+    npt.assert_array_equal(ncells, [0])
+    npt.assert_array_equal(total, [0])

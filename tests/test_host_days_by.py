@@ -276,3 +276,31 @@ def test_stage_argument_errors():
             _check_classes(5, cls, K)
     got, K = _check_classes(5, np.array([0, -1, 2, 2, 1]), 3)
     assert got.dtype == np.int32 and K == 3
+
+
+@pytest.mark.parametrize("lead", [(3,), (2, 3, 4)])
+def test_cells_to_grid_against_a_loop(lead):
+    """(..., C) per-cell values back on a 4 x 5 grid whose line 2 and column 3 hold no ocean cell: leading shapes of rank 1
+    and 3, against a plain loop over the cells"""
+    from xmhw_amd.series_stage import cells_to_grid, grid_frame
+    sshape, sdims = (4, 5), ("lat", "lon")
+    keep = np.random.default_rng(1).random(20) < 0.7
+    keep.reshape(sshape)[2, :] = False
+    keep.reshape(sshape)[:, 3] = False
+    keep[0] = True
+    cell_index = np.nonzero(keep)[0]
+    coords = {"lat": np.arange(4) * 10.0, "lon": np.arange(5) * 2.0, "time": np.arange(3)}
+    alive, out_coords, keep_grid = grid_frame(keep, sdims, sshape, coords)
+    rows, cols = [i for i in range(4) if keep.reshape(sshape)[i].any()], [j for j in range(5) if keep.reshape(sshape)[:, j].any()]
+    assert 2 not in rows and 3 not in cols
+    npt.assert_array_equal(out_coords["lat"], coords["lat"][rows])
+    npt.assert_array_equal(out_coords["lon"], coords["lon"][cols])
+    npt.assert_array_equal(keep_grid, keep.reshape(sshape)[np.ix_(rows, cols)])
+    a = np.random.default_rng(2).integers(1, 1000, lead + (cell_index.shape[0],))
+    for fill, dtype in ((0, np.int32), (np.nan, np.float64)):
+        got = cells_to_grid(a, cell_index, 20, sshape, alive, fill, dtype)
+        want = np.full(lead + (len(rows), len(cols)), fill, dtype=dtype)
+        for k, c in enumerate(cell_index):
+            want[..., rows.index(c // 5), cols.index(c % 5)] = a[..., k]
+        assert got.dtype == dtype and got.flags.c_contiguous
+        npt.assert_array_equal(got, want)

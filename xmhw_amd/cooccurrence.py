@@ -32,6 +32,7 @@ from ._lib import hip
 from .days_by import class_labels
 from .device import DeviceScope, as_xmhw_errors, device_budget_bytes
 from .exception import XmhwException
+from .series_stage import cells_to_grid, check_class_ids, dense_ids, grid_frame
 
 MAX_CLASSES = 1024              # XMHW_COOCCUR_MAX_CLASSES (include/xmhw_amd.h)
 MAX_LAGS = 64                   # XMHW_COOCCUR_MAX_LAGS
@@ -54,18 +55,6 @@ def _check_lags(lags):
     if np.unique(arr).shape[0] != arr.shape[0]:
         raise XmhwException("lags should be distinct")
     return np.ascontiguousarray(arr, dtype=np.int32)
-
-
-def _check_labels(T, classes, K):
-    classes = np.asarray(classes)
-    if classes.dtype.kind not in "iu" or classes.shape != (T,):
-        raise XmhwException(f"classes should be an integer array with one entry per time step ({T})")
-    K = int(K)
-    if not 1 <= K <= MAX_CLASSES:
-        raise XmhwException(f"mhw_cooccurrence handles 1 to {MAX_CLASSES} classes, got {K}")
-    if T and (classes.min() < -1 or classes.max() >= K):
-        raise XmhwException("class labels should be in [-1, K)")
-    return np.ascontiguousarray(classes, dtype=np.int32), K
 
 
 def check_view(view, cells, T, what):
@@ -107,7 +96,7 @@ def cooccur_tables(view_a, view_b, cells_a, cells_b, T, classes, K, lags, max_ba
     max_batch_bytes: each uploads the contiguous row range of each table that covers its cells (offsets rebased), is
     rasterised into two bitmaps and ADDS into the accumulator, which lives across the slabs and is read back once."""
     T = int(T)
-    classes, K = _check_labels(T, classes, K)
+    classes, K = check_class_ids(T, classes, K, MAX_CLASSES, "mhw_cooccurrence")
     lags = _check_lags(lags)
     L = lags.shape[0]
     cells_a, cells_b = check_view(view_a, cells_a, T, "a"), check_view(view_b, cells_b, T, "b")
@@ -240,7 +229,7 @@ def mhw_cooccurrence(a, b, classes="all", lags=(0,), max_batch_bytes=None, _comp
     observation and B the forecast: hit_rate = both / (both + a_only).
 
     Returns a CooccurrenceDataset.  ``_compute``: a stand-in for cooccur_tables() (host tests)."""
-    from .detect import EventDataset, _alive_axes, _compress_grid
+    from .detect import EventDataset
     if not isinstance(a, EventDataset) or not isinstance(b, EventDataset):
         raise XmhwException("mhw_cooccurrence expects the two EventDatasets returned by xmhw_amd.detect()")
     if bool(a.point) != bool(b.point):
@@ -253,12 +242,7 @@ def mhw_cooccurrence(a, b, classes="all", lags=(0,), max_batch_bytes=None, _comp
         raise XmhwException(f"a and b have {T} and {np.asarray(b.time).shape[0]} time steps")
     if not _same_axis(time, b.time):
         raise XmhwException("a and b do not have the same time axis")
-    labels = class_labels(classes, time)
-    found = np.unique(labels[labels >= 0])
-    K = max(int(found.shape[0]), 1)
-    if K > MAX_CLASSES:
-        raise XmhwException(f"mhw_cooccurrence handles at most {MAX_CLASSES} classes, got {K}")
-    kid = np.where(labels >= 0, np.searchsorted(found, labels), -1).astype(np.int32)
+    found, kid, K = dense_ids(class_labels(classes, time), MAX_CLASSES, "mhw_cooccurrence", "classes")
     lags = _check_lags(lags)
     L = lags.shape[0]
     view_a = a.compact_view()
@@ -293,13 +277,6 @@ def mhw_cooccurrence(a, b, classes="all", lags=(0,), max_batch_bytes=None, _comp
     N = int(np.prod(sshape))
     keep = np.zeros(N, dtype=bool)
     keep[common] = True
-    alive = _alive_axes(keep, sshape)
-
-    def on_grid_shape(x):
-        full = np.zeros(x.shape[:-1] + (N,), dtype=np.int32)
-        full[..., common] = x
-        return np.ascontiguousarray(_compress_grid(full.reshape(x.shape[:-1] + sshape), alive, x.ndim - 1))
-
-    out_coords = {d: np.asarray(a.coords[d])[m] for d, m in zip(a.sdims, alive) if d in a.coords}
-    return CooccurrenceDataset(klass, lags, n_pairs, *(on_grid_shape(counts[:, :, j]) for j in range(CHANNELS)),
-                               _compress_grid(keep.reshape(sshape), alive, 0), a.sdims, out_coords, attrs)
+    alive, out_coords, keep_grid = grid_frame(keep, a.sdims, sshape, a.coords)
+    return CooccurrenceDataset(klass, lags, n_pairs, *(cells_to_grid(counts[:, :, j], common, N, sshape, alive, 0, np.int32)
+                                                       for j in range(CHANNELS)), keep_grid, a.sdims, out_coords, attrs)

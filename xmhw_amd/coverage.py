@@ -29,10 +29,11 @@ import numpy as np
 
 from . import gridweights
 from ._lib import hip
-from .api import GridSeries, _from_xarray, _is_xarray
 from .device import DeviceScope, as_xmhw_errors
 from .exception import XmhwException
 from .gridweights import quantise_weights, resolve_weights, weights_label     # (quantise_weights: imported from here too)
+from .series_stage import (check_weighted_cells, dense_ids, grid_layout, regions_of_result, run, walk_cells,     # noqa: F401
+                           walk_grid)                              # (grid_layout: imported from here too)
 
 CATEGORIES = ("moderate", "strong", "severe", "extreme", "event")
 WEIGHT_ONE = 1 << 31            # the quantised value of the largest weight
@@ -40,47 +41,42 @@ MAX_REGIONS = 1024              # XMHW_COVERAGE_MAX_REGIONS (include/xmhw_amd.h)
 
 
 def _check_cells(C, wq, region, R):
-    wq = np.ascontiguousarray(wq, dtype=np.int64)
-    region = np.ascontiguousarray(region, dtype=np.int32)
-    if wq.shape != (C,) or region.shape != (C,):
-        raise XmhwException("wq and region should have one entry per cell")
-    if C and (wq.min() < 0 or wq.max() > WEIGHT_ONE):
-        raise XmhwException("quantised weights should be in [0, 2**31]")
-    R = int(R)
-    if R < 1:
-        raise XmhwException("R should be >= 1")
-    if C and (region.min() < -1 or region.max() >= R):
-        raise XmhwException("region ids should be in [-1, R)")
-    if R > MAX_REGIONS:
-        raise XmhwException(f"mhw_coverage handles at most {MAX_REGIONS} regions, got {R}")
-    return wq, region, R
-
-
-def _accumulate_device(h, d_ts, isz, se_ptr, th_ptr, ldc, D, rows, T, n, neg, minDuration, joinGaps, maxGap, d_wq, d_reg,
-                       R, d_cells, d_area, ld=None):
-    """One slab of n cells already on the device (series d_ts, leading dimension ld; climatologies at their
-    column offset, leading dimension ldc): exceedance bits, then the reduction ADDS into d_cells / d_area."""
-    ld = n if ld is None else ld
-    W = (T + 63) // 64
-    with DeviceScope() as s:
-        d_bits = s.alloc(8 * W * n)
-        with as_xmhw_errors(also="Unsupported"):
-            h.exceed_bits(d_ts.ptr, isz, T, n, ld, th_ptr, ldc, D, rows, neg, d_bits.ptr, n)
-            h.coverage_accumulate(d_ts.ptr, isz, T, n, ld, se_ptr, th_ptr, ldc, rows, neg, d_bits.ptr, n, int(minDuration),
-                                  int(bool(joinGaps)), int(maxGap), d_wq.ptr, d_reg.ptr, R, d_cells.ptr, d_area.ptr)
-        h.stream_sync(0)                                # d_bits is freed on the way out
+    return check_weighted_cells(C, wq, region, R, MAX_REGIONS, "mhw_coverage", "wq")
 
 
 class _Accumulators:
-    """The (T, R, 5) int64 device accumulators, zeroed; read back once at the end."""
+    """One call's arguments and its (T, R, 5) int64 device accumulators: zeroed by begin(), every slab ADDS, read back
+    once at the end."""
 
-    def __init__(self, h, T, R):
-        self.h, self.shape = h, (T, R, len(CATEGORIES))
-        nbytes = 8 * T * R * len(CATEGORIES)
+    def __init__(self, wq, region, R, minDuration, joinGaps, maxGap, coldSpells):
+        self.h, self.wq, self.region, self.R = hip(), wq, region, R
+        self.filter = (int(minDuration), int(bool(joinGaps)), int(maxGap))
+        self.neg = int(bool(coldSpells))
         self._scope = DeviceScope()
+
+    def begin(self, T, C):
+        """T steps; wq and region hold C entries"""
+        self.wq, self.region, self.R = _check_cells(C, self.wq, self.region, self.R)
+        self.shape = (T, self.R, len(CATEGORIES))
+        nbytes = 8 * T * self.R * len(CATEGORIES)
         self.cells, self.area = self._scope.alloc(nbytes), self._scope.alloc(nbytes)
-        h.memset(self.cells.ptr, 0, nbytes)
-        h.memset(self.area.ptr, 0, nbytes)
+        self.h.memset(self.cells.ptr, 0, nbytes)
+        self.h.memset(self.area.ptr, 0, nbytes)
+
+    def add_slab(self, slab):
+        """One slab (series_stage.Slab): its cells' weights and region ids, exceedance bits, then the reduction."""
+        d_ts, T, n = slab.d_ts, slab.T, slab.n
+        W = (T + 63) // 64
+        with DeviceScope() as s:
+            d_wq, d_reg = s.upload(slab.take(self.wq)), s.upload(slab.take(self.region))
+            d_bits = s.alloc(8 * W * n)
+            with as_xmhw_errors(also="Unsupported"):
+                self.h.exceed_bits(d_ts.ptr, slab.isz, T, n, slab.ld, slab.th_ptr, slab.ldc, slab.D, slab.rows, self.neg,
+                                   d_bits.ptr, n)
+                self.h.coverage_accumulate(d_ts.ptr, slab.isz, T, n, slab.ld, slab.se_ptr, slab.th_ptr, slab.ldc, slab.rows,
+                                           self.neg, d_bits.ptr, n, *self.filter, d_wq.ptr, d_reg.ptr, self.R, self.cells.ptr,
+                                           self.area.ptr)
+            self.h.stream_sync(0)                       # the slab's buffers are freed on the way out
 
     def result(self):
         self.h.stream_sync(0)
@@ -96,30 +92,10 @@ def coverage_cells(ts, seas, thresh, doy, doys, wq, region, R, minDuration=5, jo
     quantised weights in [0, 2**31], region (C,) ids in [-1, R) (-1: the cell counts nowhere).
     Returns (cells, area_q), both int64 (T, R, 5), columns CATEGORIES.  Cells go through the device in batches
     below max_batch_bytes; the sums are integers, so the batch size does not change a single bit."""
-    from .detect_front import _check_inputs
-    ts, seas, thresh, rows = _check_inputs(ts, seas, thresh, doy, doys)
-    T, C = ts.shape
-    D = thresh.shape[0]
-    wq, region, R = _check_cells(C, wq, region, R)
-    h = hip()
-    isz = ts.dtype.itemsize
-    neg = int(bool(coldSpells))
-    per_cell = T * (isz + 1) + T // 4 + 2 * D * 8 + 64
-    batch = int(max(1, min(C, max_batch_bytes // max(per_cell, 1))))
-    acc = _Accumulators(h, T, R)
+    acc = _Accumulators(wq, region, R, minDuration, joinGaps, maxGap, coldSpells)
     try:
-        for c0 in range(0, C, batch):
-            c1 = min(C, c0 + batch)
-            n = c1 - c0
-            with DeviceScope() as s:
-                d_ts = s.upload(np.ascontiguousarray(ts[:, c0:c1]))
-                if pad is not None:
-                    pad.apply(d_ts.ptr, isz, T, n)
-                d_se = s.upload(np.ascontiguousarray(seas[:, c0:c1]))
-                d_th = s.upload(np.ascontiguousarray(thresh[:, c0:c1]))
-                d_wq, d_reg = s.upload(wq[c0:c1]), s.upload(region[c0:c1])
-                _accumulate_device(h, d_ts, isz, d_se.ptr, d_th.ptr, n, D, rows, T, n, neg, minDuration, joinGaps, maxGap,
-                                   d_wq, d_reg, R, acc.cells, acc.area)
+        walk_cells(ts, seas, thresh, doy, doys, lambda T, isz, D: T * (isz + 1) + T // 4 + 2 * D * 8 + 64, max_batch_bytes,
+                   pad, acc.add_slab, acc.begin)
         return acc.result()
     finally:
         acc.free()
@@ -128,70 +104,16 @@ def coverage_cells(ts, seas, thresh, doy, doys, wq, region, R, minDuration=5, jo
 def coverage_grid(stacked, anynans, seas, thresh, doy, doys, wq, region, R, minDuration=5, joinGaps=True, maxGap=2,
                   coldSpells=False, max_batch_bytes=None, clim_stacked=False, pad=None):
     """coverage_cells() for an UNCOMPACTED stacked host series (T, N), as detect_front.detect_grid: the land mask
-    and the compaction run on the device slab by slab, the climatologies are compacted there as well
-    (clim_stacked) and pair up with the series' survivors by position.  wq / region have N entries (the whole
+    and the compaction run on the device slab by slab (series_stage.walk_grid).  wq / region have N entries (the whole
     grid) and are compacted by each slab's `keep`.  Returns (cells, area_q, keep[N])."""
-    from .detect_front import _check_inputs, _rows_as_they_are
-    from .device import _grid_batch, compact_columns, device_itemsize, is_packed, native_float
-    T, N = stacked.shape
-    if not is_packed(stacked):
-        stacked = np.ascontiguousarray(native_float(stacked))
-    seas, thresh = _rows_as_they_are(seas), _rows_as_they_are(thresh)
-    if seas.ndim != 2 or thresh.ndim != 2 or seas.shape[0] != thresh.shape[0]:
-        raise XmhwException("seas and thresh must be (D, cells) arrays")
-    D = thresh.shape[0]
-    sample_dtype = stacked.decoded_dtype if is_packed(stacked) else stacked.dtype
-    _, _, _, rows = _check_inputs(np.zeros((T, 1), dtype=sample_dtype), seas[:, :1], thresh[:, :1], doy, doys)
-    wq, region, R = _check_cells(N, wq, region, R)
-    h = hip()
-    isz = device_itemsize(stacked)
-    neg = int(bool(coldSpells))
-    keeps = []
-    acc = _Accumulators(h, T, R)
-    clim = DeviceScope()
-    k0 = 0
+    acc = _Accumulators(wq, region, R, minDuration, joinGaps, maxGap, coldSpells)
     try:
-        if clim_stacked:
-            d_th, keep_th = compact_columns(thresh, 0, thresh.shape[1], anynans)
-            clim.adopt(d_th)
-            d_se, keep_se = compact_columns(seas, 0, seas.shape[1], anynans)
-            clim.adopt(d_se)
-            C, Cse = int(keep_th.sum()), int(keep_se.sum())
-            if C == 0 or Cse == 0:
-                raise XmhwException("All points of grid are either land or NaN")
-        else:
-            d_th, d_se = clim.upload(thresh), clim.upload(seas)
-            C, Cse = thresh.shape[1], seas.shape[1]
-        if C != Cse:
-            raise XmhwException(f"th and se do not have the same ocean cells: {C}, {Cse}")
-        cb = _grid_batch(stacked, max_batch_bytes, per_cell_extra=6 * D * 8 + T // 4 + 64)
-        for lo in range(0, N, cb):
-            hi = min(N, lo + cb)
-            d_ts, keep = compact_columns(stacked, lo, hi, anynans)
-            keeps.append(keep)
-            n = int(keep.sum())
-            if d_ts is None:
-                continue
-            with DeviceScope() as s:
-                s.adopt(d_ts)
-                if pad is not None:
-                    pad.apply(d_ts.ptr, isz, T, n)
-                if k0 + n > C:
-                    raise XmhwException(f"temp has more ocean cells than th and se ({C})")
-                d_wq, d_reg = s.upload(wq[lo:hi][keep]), s.upload(region[lo:hi][keep])
-                _accumulate_device(h, d_ts, isz, d_se.ptr + 8 * k0, d_th.ptr + 8 * k0, C, D, rows, T, n, neg, minDuration,
-                                   joinGaps, maxGap, d_wq, d_reg, R, acc.cells, acc.area)
-            k0 += n
-        keep = np.concatenate(keeps) if keeps else np.zeros(0, dtype=bool)
-        if not keep.any():
-            raise XmhwException("All points of grid are either land or NaN")
-        if k0 != C:
-            raise XmhwException(f"temp has {k0} ocean cells, th and se have {C}")
-        cells, area = acc.result()
-        return cells, area, keep
+        acc.begin(*stacked.shape)
+        keep = walk_grid(stacked, anynans, seas, thresh, doy, doys, lambda T, D: 6 * D * 8 + T // 4 + 64, max_batch_bytes,
+                         clim_stacked, pad, acc.add_slab)
+        return acc.result() + (keep,)
     finally:
         acc.free()
-        clim.free()
 
 
 class CoverageDataset:
@@ -228,25 +150,6 @@ class CoverageDataset:
             attrs=dict(self.attrs, weight_unit=self.weight_unit))
 
 
-def grid_layout(temp, tdim):
-    """(coords, coord_attrs, dims, point, sdims, sshape, N) of a GridSeries / DataArray: the spatial dims in stacked
-    (sorted-name) order, their shape and the number of grid points (1 for a single-point series)."""
-    if _is_xarray(temp):
-        coords, coord_attrs = _from_xarray(temp)
-        dims = list(temp.dims)
-    else:
-        coords, coord_attrs, dims = dict(temp.coords), None, list(temp.dims)
-    if tdim not in dims:
-        raise XmhwException(f"{tdim} dimension not present, default"
-                            + "is 'time' or pass as tdim='time_dimension_name'")
-    point = len(dims) == 1
-    sdims = sorted(d for d in dims if d != tdim)
-    shape = tuple(temp.shape) if _is_xarray(temp) else tuple(np.shape(temp.values))
-    sshape = tuple(shape[dims.index(d)] for d in sdims)
-    N = int(np.prod(sshape, dtype=np.int64)) if not point else 1
-    return coords, coord_attrs, dims, point, sdims, sshape, N
-
-
 def region_ids(regions, dims, tdim, sdims, sshape, point, N, who):
     """The ``regions`` argument on the whole grid, in stacked order: (found, rid, Rc) with ``found`` the sorted
     non-negative labels, ``rid`` (N,) int32 the position of every cell's label in it (-1: negative label, the cell
@@ -261,12 +164,7 @@ def region_ids(regions, dims, tdim, sdims, sshape, point, N, who):
             gridweights.on_grid(regions, "regions", dims, tdim, sdims, sshape).astype(np.int64)
         if labels.shape != (N,):
             raise XmhwException("regions should have one entry per cell")
-    found = np.unique(labels[labels >= 0])                     # candidates: the labels on the whole grid
-    rid = np.where(labels >= 0, np.searchsorted(found, labels), -1).astype(np.int32)
-    Rc = max(int(found.shape[0]), 1)
-    if Rc > MAX_REGIONS:
-        raise XmhwException(f"{who} handles at most {MAX_REGIONS} regions, got {Rc}")
-    return found, rid, Rc
+    return dense_ids(labels, MAX_REGIONS, who, "regions")     # candidates: the labels on the whole grid
 
 
 def mhw_coverage(temp, th, se, weights=None, regions=None, tdim="time", minDuration=5, joinGaps=True, maxGap=2,
@@ -286,55 +184,31 @@ def mhw_coverage(temp, th, se, weights=None, regions=None, tdim="time", minDurat
     extreme, event (event >= the sum of the four: gap days of joined events are in none of them), ``fraction =
     area_q / total_q`` within ``quantisation_bound()`` of the unquantised ratio.  ``_compute``: a stand-in for
     coverage_cells() (host tests)."""
-    from .detect import _detect
-    coords, coord_attrs, dims, point, sdims, sshape, N = grid_layout(temp, tdim)
+    layout = grid_layout(temp, tdim)
+    coords, _, dims, point, sdims, sshape, N = layout
     # weights and region labels on the whole grid, in stacked order
     wq, unit = quantise_weights(resolve_weights(weights, coords, dims, tdim, sdims, sshape, point))
     found, rid, Rc = region_ids(regions, dims, tdim, sdims, sshape, point, N, "mhw_coverage")
-    got = {}
+    got = []
 
-    def on_cells(ts, sec, thc, doy, doys, minDuration, joinGaps, maxGap, coldSpells, intermediate, pad=None):
-        # _detect() has masked and compacted on the host (point series, or a stand-in device stage)
-        from .landmask import keep_mask, stack_cells
-        if point:
-            keep = np.array([True])
-        else:
-            vals = temp.values
-            keep = keep_mask(stack_cells(np.asarray(vals), dims, tdim)[0], anynans)
-        stage = _compute or coverage_cells
-        extra = {} if pad is None else {"pad": pad}
-        if max_batch_bytes is not None and _compute is None:
-            extra["max_batch_bytes"] = max_batch_bytes
-        got["cells"], got["area"] = stage(ts, sec, thc, doy, doys, wq[keep], rid[keep], Rc, minDuration, joinGaps, maxGap,
-                                          coldSpells, **extra)
-        return dict(table=np.zeros((0, 31)), offsets=np.zeros(ts.shape[1] + 1, dtype=np.int64), inter=None)
+    def on_cells(host_keep, ts, sec, thc, doy, doys, *options, **extra):
+        keep = host_keep()
+        got.extend((_compute or coverage_cells)(ts, sec, thc, doy, doys, wq[keep], rid[keep], Rc, *options, **extra))
 
-    def on_grid(stacked, anynans_, sec, thc, doy, doys, minDuration, joinGaps, maxGap, coldSpells, intermediate,
-                clim_stacked=False, pad=None):
-        got["cells"], got["area"], keep = coverage_grid(stacked, anynans_, sec, thc, doy, doys, wq, rid, Rc, minDuration,
-                                                        joinGaps, maxGap, coldSpells, max_batch_bytes=max_batch_bytes,
-                                                        clim_stacked=clim_stacked, pad=pad)
-        return dict(table=np.zeros((0, 31)), offsets=np.zeros(int(keep.sum()) + 1, dtype=np.int64), inter=None, keep=keep)
+    def on_grid(stacked, anynans_, sec, thc, doy, doys, *options, **extra):
+        *out, keep = coverage_grid(stacked, anynans_, sec, thc, doy, doys, wq, rid, Rc, *options, **extra)
+        got.extend(out)
+        return keep
 
-    series = GridSeries(temp.values, dims, coords, coord_attrs=coord_attrs) if _is_xarray(temp) else temp
-    as_series = lambda a: GridSeries(a.values, a.dims, _from_xarray(a)[0]) if _is_xarray(a) else a   # noqa: E731
-    mhw = _detect(series, as_series(th), as_series(se), on_cells, tdim, minDuration, joinGaps, maxGap, maxPadLength,
-                  coldSpells, False, anynans, tstep, grid_compute=None if _compute is not None else on_grid)
-    keep = np.asarray(mhw.keep, dtype=bool)
-    cells, area = np.asarray(got["cells"]), np.asarray(got["area"])
+    mhw = run(temp, th, se, layout, tdim, on_cells, on_grid, maxPadLength, coldSpells, tstep, anynans, _compute,
+              max_batch_bytes, minDuration, joinGaps, maxGap)
+    cells, area = (np.asarray(a) for a in got)
     T = np.asarray(coords[tdim]).shape[0]
     if cells.shape != (T, Rc, len(CATEGORIES)) or area.shape != cells.shape:
         raise XmhwException(f"coverage stage returned {cells.shape}, expected {(T, Rc, len(CATEGORIES))}")
-    # the regions of the result: the labels found on OCEAN cells
-    ocean = keep & (rid >= 0)
-    ncells = np.bincount(rid[ocean], minlength=Rc).astype(np.int64)
-    total_q = np.zeros(Rc, dtype=np.int64)
-    np.add.at(total_q, rid[ocean], wq[ocean])
-    if found.shape[0]:
-        sel = ncells > 0
-        cells, area, ncells, total_q, region = cells[:, sel], area[:, sel], ncells[sel], total_q[sel], found[sel]
-    else:
-        region = np.zeros(1, dtype=np.int64)                    # every cell excluded: one empty region
+    sel, ncells, total_q, region = regions_of_result(np.asarray(mhw.keep, dtype=bool), rid, wq, found)
+    if sel is not None:
+        cells, area = cells[:, sel], area[:, sel]
     attrs = {"weights": weights_label(weights), "xmhw_parameters": mhw.attrs["xmhw_parameters"]}
     return CoverageDataset(np.asarray(coords[tdim]), region, np.ascontiguousarray(cells), np.ascontiguousarray(area),
                            total_q, ncells, unit, tdim=tdim, attrs=attrs)

@@ -33,10 +33,10 @@ import numpy as np
 
 from . import calendar as cal
 from ._lib import hip
-from .api import GridSeries, _from_xarray, _is_xarray
-from .coverage import CATEGORIES, grid_layout
+from .coverage import CATEGORIES
 from .device import DeviceScope, as_xmhw_errors
 from .exception import XmhwException
+from .series_stage import cells_to_grid, check_class_ids, dense_ids, grid_frame, grid_layout, run, walk_cells, walk_grid
 
 MAX_CLASSES = 1024              # XMHW_CLASS_DAYS_MAX_CLASSES (include/xmhw_amd.h)
 CHANNELS = 6                    # XMHW_CLASS_DAYS_CHANNELS: CATEGORIES, then n_valid
@@ -48,48 +48,42 @@ _RANGE_TEXT = ("in-event samples lie 2**7 and more from their climatology (or ar
 
 
 def _check_classes(T, classes, K):
-    classes = np.asarray(classes)
-    if classes.dtype.kind not in "iu":
-        raise XmhwException(f"classes should be an integer array, got {classes.dtype}")
-    if classes.shape != (T,):
-        raise XmhwException(f"classes should have one entry per time step ({T}), got shape {classes.shape}")
-    K = int(K)
-    if K < 1:
-        raise XmhwException("K should be >= 1")
-    if K > MAX_CLASSES:
-        raise XmhwException(f"mhw_days_by handles at most {MAX_CLASSES} classes, got {K}")
-    if T and (classes.min() < -1 or classes.max() >= K):
-        raise XmhwException("class labels should be in [-1, K)")
-    return np.ascontiguousarray(classes, dtype=np.int32), K
+    return check_class_ids(T, classes, K, MAX_CLASSES, "mhw_days_by")
 
 
 class _Accumulators:
-    """The device accumulators of one call: days int32 (K, 6, C), isum_q int64 (K, C), intensity_max (K, C) used as the
-    key array, and the range counter.  Initialised; they live across the slabs, each slab adds into its own column range,
-    and they are read back once."""
+    """One call's arguments and its device accumulators: days int32 (K, 6, C), isum_q int64 (K, C), intensity_max (K, C)
+    used as the key array, and the range counter.  Initialised by begin(); they live across the slabs, each slab adds
+    into its own column range, and they are read back once."""
 
-    def __init__(self, h, K, C):
-        self.h, self.K, self.C = h, K, C
-        n = max(K * C, 1)
-        self._scope = s = DeviceScope()
-        try:
-            self.days, self.isum, self.imax, self.count = s.alloc(4 * CHANNELS * n), s.alloc(8 * n), s.alloc(8 * n), s.alloc(8)
-            with as_xmhw_errors(also="Unsupported"):
-                h.class_days_init(K, C, self.days.ptr, self.isum.ptr, self.imax.ptr, C, self.count.ptr)
-        except BaseException:
-            s.free()
-            raise
+    def __init__(self, classes, K, minDuration, joinGaps, maxGap, coldSpells):
+        self.h, self.classes, self.K, self.C = hip(), classes, K, None
+        self.filter = (int(minDuration), int(bool(joinGaps)), int(maxGap))
+        self.neg = int(bool(coldSpells))
+        self._scope = DeviceScope()
 
-    def add_slab(self, d_ts, isz, T, n, ld, se_ptr, th_ptr, ldc, D, rows, neg, minDuration, joinGaps, maxGap, classes, k0):
-        """One slab of n cells already on the device, columns k0..k0+n-1 of the accumulators: exceedance bits, then the
-        reduction ADDS."""
+    def begin(self, T, C):
+        """T steps, C ocean cells"""
+        self.classes, self.K = _check_classes(T, self.classes, self.K)
+        n = max(self.K * C, 1)
+        s = self._scope
+        self.days, self.isum, self.imax, self.count = s.alloc(4 * CHANNELS * n), s.alloc(8 * n), s.alloc(8 * n), s.alloc(8)
+        with as_xmhw_errors(also="Unsupported"):
+            self.h.class_days_init(self.K, C, self.days.ptr, self.isum.ptr, self.imax.ptr, C, self.count.ptr)
+        self.C = C
+
+    def add_slab(self, slab):
+        """One slab (series_stage.Slab), columns k0..k0+n-1 of the accumulators: exceedance bits, then the reduction
+        ADDS."""
+        d_ts, T, n, k0 = slab.d_ts, slab.T, slab.n, slab.k0
         W = (T + 63) // 64
         with DeviceScope() as s:
             d_bits = s.alloc(8 * W * n)
             with as_xmhw_errors(also="Unsupported"):
-                self.h.exceed_bits(d_ts.ptr, isz, T, n, ld, th_ptr, ldc, D, rows, neg, d_bits.ptr, n)
-                self.h.class_days_accumulate(d_ts.ptr, isz, T, n, ld, se_ptr, th_ptr, ldc, rows, neg, d_bits.ptr, n,
-                                             int(minDuration), int(bool(joinGaps)), int(maxGap), classes, self.K,
+                self.h.exceed_bits(d_ts.ptr, slab.isz, T, n, slab.ld, slab.th_ptr, slab.ldc, slab.D, slab.rows, self.neg,
+                                   d_bits.ptr, n)
+                self.h.class_days_accumulate(d_ts.ptr, slab.isz, T, n, slab.ld, slab.se_ptr, slab.th_ptr, slab.ldc, slab.rows,
+                                             self.neg, d_bits.ptr, n, *self.filter, self.classes, self.K,
                                              self.days.ptr + 4 * k0, self.isum.ptr + 8 * k0, self.imax.ptr + 8 * k0, self.C,
                                              self.count.ptr)
             self.h.stream_sync(0)                       # d_bits is freed on the way out
@@ -123,29 +117,10 @@ def class_days_cells(ts, seas, thresh, doy, doys, classes, K, minDuration=5, joi
     device in batches below max_batch_bytes, as in coverage_cells(); the sums are integers, so the batch size does not
     change a single bit.  Raises if a sample is out of range (module docstring); with ``counters`` (a dict) it stores
     ``n_range`` there instead."""
-    from .detect_front import _check_inputs
-    ts, seas, thresh, rows = _check_inputs(ts, seas, thresh, doy, doys)
-    T, C = ts.shape
-    D = thresh.shape[0]
-    classes, K = _check_classes(T, classes, K)
-    h = hip()
-    isz = ts.dtype.itemsize
-    neg = int(bool(coldSpells))
-    per_cell = T * (isz + 1) + T // 4 + 2 * D * 8 + 64
-    batch = int(max(1, min(C, max_batch_bytes // max(per_cell, 1))))
-    acc = _Accumulators(h, K, C)
+    acc = _Accumulators(classes, K, minDuration, joinGaps, maxGap, coldSpells)
     try:
-        for c0 in range(0, C, batch):
-            c1 = min(C, c0 + batch)
-            n = c1 - c0
-            with DeviceScope() as s:
-                d_ts = s.upload(np.ascontiguousarray(ts[:, c0:c1]))
-                if pad is not None:
-                    pad.apply(d_ts.ptr, isz, T, n)
-                d_se = s.upload(np.ascontiguousarray(seas[:, c0:c1]))
-                d_th = s.upload(np.ascontiguousarray(thresh[:, c0:c1]))
-                acc.add_slab(d_ts, isz, T, n, n, d_se.ptr, d_th.ptr, n, D, rows, neg, minDuration, joinGaps, maxGap, classes,
-                             c0)
+        walk_cells(ts, seas, thresh, doy, doys, lambda T, isz, D: T * (isz + 1) + T // 4 + 2 * D * 8 + 64, max_batch_bytes,
+                   pad, acc.add_slab, acc.begin)
         out, n_range = acc.result()
     finally:
         acc.free()
@@ -156,72 +131,18 @@ def class_days_cells(ts, seas, thresh, doy, doys, classes, K, minDuration=5, joi
 def class_days_grid(stacked, anynans, seas, thresh, doy, doys, classes, K, minDuration=5, joinGaps=True, maxGap=2,
                     coldSpells=False, max_batch_bytes=None, clim_stacked=False, pad=None, counters=None):
     """class_days_cells() for an UNCOMPACTED stacked host series (T, N), float or a packed int16 view, as coverage_grid():
-    the land mask and the compaction run on the device slab by slab, the climatologies are compacted there as well
-    (clim_stacked) and pair up with the series' survivors by position.  The accumulators live across the slabs and each
-    slab writes its own column range.  Returns (days, isum_q, intensity_max, keep[N]) over the ocean cells."""
-    from .detect_front import _check_inputs, _rows_as_they_are
-    from .device import _grid_batch, compact_columns, device_itemsize, is_packed, native_float
-    T, N = stacked.shape
-    if not is_packed(stacked):
-        stacked = np.ascontiguousarray(native_float(stacked))
-    seas, thresh = _rows_as_they_are(seas), _rows_as_they_are(thresh)
-    if seas.ndim != 2 or thresh.ndim != 2 or seas.shape[0] != thresh.shape[0]:
-        raise XmhwException("seas and thresh must be (D, cells) arrays")
-    D = thresh.shape[0]
-    sample_dtype = stacked.decoded_dtype if is_packed(stacked) else stacked.dtype
-    _, _, _, rows = _check_inputs(np.zeros((T, 1), dtype=sample_dtype), seas[:, :1], thresh[:, :1], doy, doys)
-    classes, K = _check_classes(T, classes, K)
-    h = hip()
-    isz = device_itemsize(stacked)
-    neg = int(bool(coldSpells))
-    keeps = []
-    acc = None
-    clim = DeviceScope()
-    k0 = 0
+    the land mask and the compaction run on the device slab by slab (series_stage.walk_grid).  The accumulators live
+    across the slabs and each slab writes its own column range.  Returns (days, isum_q, intensity_max, keep[N]) over the
+    ocean cells."""
+    acc = _Accumulators(classes, K, minDuration, joinGaps, maxGap, coldSpells)
     try:
-        if clim_stacked:
-            d_th, keep_th = compact_columns(thresh, 0, thresh.shape[1], anynans)
-            clim.adopt(d_th)
-            d_se, keep_se = compact_columns(seas, 0, seas.shape[1], anynans)
-            clim.adopt(d_se)
-            C, Cse = int(keep_th.sum()), int(keep_se.sum())
-            if C == 0 or Cse == 0:
-                raise XmhwException("All points of grid are either land or NaN")
-        else:
-            d_th, d_se = clim.upload(thresh), clim.upload(seas)
-            C, Cse = thresh.shape[1], seas.shape[1]
-        if C != Cse:
-            raise XmhwException(f"th and se do not have the same ocean cells: {C}, {Cse}")
-        acc = _Accumulators(h, K, C)
-        cb = _grid_batch(stacked, max_batch_bytes, per_cell_extra=6 * D * 8 + T // 4 + 64)
-        for lo in range(0, N, cb):
-            hi = min(N, lo + cb)
-            d_ts, keep = compact_columns(stacked, lo, hi, anynans)
-            keeps.append(keep)
-            n = int(keep.sum())
-            if d_ts is None:
-                continue
-            with DeviceScope() as s:
-                s.adopt(d_ts)
-                if pad is not None:
-                    pad.apply(d_ts.ptr, isz, T, n)
-                if k0 + n > C:
-                    raise XmhwException(f"temp has more ocean cells than th and se ({C})")
-                acc.add_slab(d_ts, isz, T, n, n, d_se.ptr + 8 * k0, d_th.ptr + 8 * k0, C, D, rows, neg, minDuration,
-                             joinGaps, maxGap, classes, k0)
-            k0 += n
-        keep = np.concatenate(keeps) if keeps else np.zeros(0, dtype=bool)
-        if not keep.any():
-            raise XmhwException("All points of grid are either land or NaN")
-        if k0 != C:
-            raise XmhwException(f"temp has {k0} ocean cells, th and se have {C}")
-        (days, isum, imax), n_range = acc.result()
+        keep = walk_grid(stacked, anynans, seas, thresh, doy, doys, lambda T, D: 6 * D * 8 + T // 4 + 64, max_batch_bytes,
+                         clim_stacked, pad, acc.add_slab, begin=acc.begin)
+        out, n_range = acc.result()
     finally:
-        if acc is not None:
-            acc.free()
-        clim.free()
+        acc.free()
     _report(n_range, counters)
-    return days, isum, imax, keep
+    return out + (keep,)
 
 
 def class_labels(classes, time):
@@ -338,45 +259,28 @@ def mhw_days_by(temp, th, se, classes="month", tdim="time", minDuration=5, joinG
 
     Returns a ClassDaysDataset.  Raises if an in-event sample lies 2**7 and more from its climatology.  ``_compute``: a
     stand-in for class_days_cells() (host tests)."""
-    from .detect import _alive_axes, _compress_grid, _detect
-    coords, coord_attrs, dims, point, sdims, sshape, N = grid_layout(temp, tdim)
+    layout = grid_layout(temp, tdim)
+    coords, _, _, point, sdims, sshape, N = layout
     time = np.asarray(coords[tdim])
-    T = time.shape[0]
-    labels = class_labels(classes, time)
-    found = np.unique(labels[labels >= 0])
-    K = max(int(found.shape[0]), 1)
-    if K > MAX_CLASSES:
-        raise XmhwException(f"mhw_days_by handles at most {MAX_CLASSES} classes, got {K}")
-    kid = np.where(labels >= 0, np.searchsorted(found, labels), -1).astype(np.int32)
+    found, kid, K = dense_ids(class_labels(classes, time), MAX_CLASSES, "mhw_days_by", "classes")
     n_steps = np.bincount(kid[kid >= 0], minlength=K).astype(np.int64)
-    got, counters = {}, {}
+    got, counters = [], {}
 
-    def on_cells(ts, sec, thc, doy, doys, minDuration, joinGaps, maxGap, coldSpells, intermediate, pad=None):
-        stage = _compute or class_days_cells
-        extra = {} if pad is None else {"pad": pad}
-        if max_batch_bytes is not None and _compute is None:
-            extra["max_batch_bytes"] = max_batch_bytes
-        got["out"] = stage(ts, sec, thc, doy, doys, kid, K, minDuration, joinGaps, maxGap, coldSpells, counters=counters,
-                           **extra)
-        return dict(table=np.zeros((0, 31)), offsets=np.zeros(ts.shape[1] + 1, dtype=np.int64), inter=None)
+    def on_cells(host_keep, ts, sec, thc, doy, doys, *options, **extra):
+        got.extend((_compute or class_days_cells)(ts, sec, thc, doy, doys, kid, K, *options, counters=counters, **extra))
 
-    def on_grid(stacked, anynans_, sec, thc, doy, doys, minDuration, joinGaps, maxGap, coldSpells, intermediate,
-                clim_stacked=False, pad=None):
-        *out, keep = class_days_grid(stacked, anynans_, sec, thc, doy, doys, kid, K, minDuration, joinGaps, maxGap,
-                                     coldSpells, max_batch_bytes=max_batch_bytes, clim_stacked=clim_stacked, pad=pad,
-                                     counters=counters)
-        got["out"] = tuple(out)
-        return dict(table=np.zeros((0, 31)), offsets=np.zeros(int(keep.sum()) + 1, dtype=np.int64), inter=None, keep=keep)
+    def on_grid(stacked, anynans_, sec, thc, doy, doys, *options, **extra):
+        *out, keep = class_days_grid(stacked, anynans_, sec, thc, doy, doys, kid, K, *options, counters=counters, **extra)
+        got.extend(out)
+        return keep
 
-    series = GridSeries(temp.values, dims, coords, coord_attrs=coord_attrs) if _is_xarray(temp) else temp
-    as_series = lambda a: GridSeries(a.values, a.dims, _from_xarray(a)[0]) if _is_xarray(a) else a   # noqa: E731
-    mhw = _detect(series, as_series(th), as_series(se), on_cells, tdim, minDuration, joinGaps, maxGap, maxPadLength,
-                  coldSpells, False, anynans, tstep, grid_compute=None if _compute is not None else on_grid)
+    mhw = run(temp, th, se, layout, tdim, on_cells, on_grid, maxPadLength, coldSpells, tstep, anynans, _compute,
+              max_batch_bytes, minDuration, joinGaps, maxGap)
     if counters.get("n_range", 0):
         raise XmhwException(f"{counters['n_range']} {_RANGE_TEXT}")
     keep = np.asarray(mhw.keep, dtype=bool)
     C = int(keep.sum())
-    days6, isum, imax = (np.asarray(a) for a in got["out"])
+    days6, isum, imax = (np.asarray(a) for a in got)
     if days6.shape != (K, CHANNELS, C) or isum.shape != (K, C) or imax.shape != (K, C):
         raise XmhwException(f"class stage returned {days6.shape}, {isum.shape}, {imax.shape}, expected "
                             f"{(K, CHANNELS, C)}, {(K, C)}, {(K, C)}")
@@ -385,14 +289,8 @@ def mhw_days_by(temp, th, se, classes="month", tdim="time", minDuration=5, joinG
     if point:
         return ClassDaysDataset(klass, n_steps, days6[:, :5, 0].astype(np.int32), days6[:, 5, 0].astype(np.int32),
                                 isum[:, 0].astype(np.int64), imax[:, 0].astype(np.float64), np.array(True), (), {}, tdim, attrs)
-    alive = _alive_axes(keep, sshape)
-
-    def on_grid_shape(a, fill, dtype):
-        full = np.full(a.shape[:-1] + (N,), fill, dtype=dtype)
-        full[..., mhw.cell_index] = a
-        return np.ascontiguousarray(_compress_grid(full.reshape(a.shape[:-1] + tuple(sshape)), alive, a.ndim - 1))
-
-    out_coords = {d: np.asarray(coords[d])[m] for d, m in zip(sdims, alive)}
+    alive, out_coords, keep_grid = grid_frame(keep, sdims, sshape, coords)
+    on_grid_shape = lambda a, fill, dtype: cells_to_grid(a, mhw.cell_index, N, sshape, alive, fill, dtype)    # noqa: E731
     return ClassDaysDataset(klass, n_steps, on_grid_shape(days6[:, :5], 0, np.int32), on_grid_shape(days6[:, 5], 0, np.int32),
-                            on_grid_shape(isum, 0, np.int64), on_grid_shape(imax, np.nan, np.float64),
-                            _compress_grid(keep.reshape(sshape), alive, 0), sdims, out_coords, tdim, attrs)
+                            on_grid_shape(isum, 0, np.int64), on_grid_shape(imax, np.nan, np.float64), keep_grid, sdims,
+                            out_coords, tdim, attrs)

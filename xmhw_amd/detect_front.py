@@ -259,6 +259,7 @@ def detect_grid(stacked, anynans, seas, thresh, doy, doys, minDuration=5, joinGa
     array and mask rule): its compacted device slabs are used instead of a second upload."""
     import time as _time
     from .device import ResidentSeries, _grid_batch, _trace, apply_recipe, compact_columns, decode_through_device, device_itemsize, is_packed
+    from .series_stage import climatologies_on_device
     _t_all = _time.perf_counter()
     rkey = ResidentSeries.key_of(stacked, anynans) if resident is not None else None
     T, N = stacked.shape
@@ -343,20 +344,7 @@ def detect_grid(stacked, anynans, seas, thresh, doy, doys, minDuration=5, joinGa
     keeps, tables, counts_all = [], [], []
     k0 = 0
     with DeviceScope() as clim, DeviceScope() as waiting:
-        # the climatologies are small next to the series: whole on the device, compacted there if needed
-        if clim_stacked:
-            d_th, keep_th = compact_columns(thresh, 0, thresh.shape[1], anynans)
-            clim.adopt(d_th)
-            d_se, keep_se = compact_columns(seas, 0, seas.shape[1], anynans)
-            clim.adopt(d_se)
-            C, Cse = int(keep_th.sum()), int(keep_se.sum())
-            if C == 0 or Cse == 0:
-                raise XmhwException("All points of grid are either land or NaN")
-        else:
-            d_th, d_se = clim.upload(thresh), clim.upload(seas)
-            C, Cse = thresh.shape[1], seas.shape[1]
-        if C != Cse:
-            raise XmhwException(f"th and se do not have the same ocean cells: {C}, {Cse}")
+        d_se, d_th, C = climatologies_on_device(clim, seas, thresh, anynans, clim_stacked)
         cb = _grid_batch(stacked, max_batch_bytes, per_cell_extra=6 * D * 8 + T // 8 + 64)
         c0, c1 = (0, N) if columns is None else (int(columns[0]), int(columns[1]))
         slabs = [(lo, min(c1, lo + cb)) for lo in range(c0, c1, cb)]

@@ -27,10 +27,11 @@ import numpy as np
 
 from ._lib import hip
 from .api import GridSeries, _is_xarray
-from .coverage import grid_layout, region_ids
+from .coverage import region_ids
 from .device import DeviceScope, as_xmhw_errors
 from .exception import XmhwException
 from .gridweights import quantise_weights, resolve_weights, weights_label
+from .series_stage import check_weighted_cells, grid_layout, regions_of_result
 
 SERIES_BITS = 16                # XMHW_REGION_SERIES_BITS (include/xmhw_amd.h)
 RANGE_BITS = 7                  # |ts - offset| < 2**7
@@ -48,19 +49,7 @@ def weight_bits(n_ocean):
 
 
 def _check_cells(C, wi, region, R, offset):
-    wi = np.ascontiguousarray(wi, dtype=np.int64)
-    region = np.ascontiguousarray(region, dtype=np.int32)
-    if wi.shape != (C,) or region.shape != (C,):
-        raise XmhwException("wi and region should have one entry per cell")
-    if C and (wi.min() < 0 or wi.max() > 1 << MAX_WEIGHT_BITS):
-        raise XmhwException("quantised weights should be in [0, 2**31]")
-    R = int(R)
-    if R < 1:
-        raise XmhwException("R should be >= 1")
-    if C and (region.min() < -1 or region.max() >= R):
-        raise XmhwException("region ids should be in [-1, R)")
-    if R > MAX_REGIONS:
-        raise XmhwException(f"region_series handles at most {MAX_REGIONS} regions, got {R}")
+    wi, region, R = check_weighted_cells(C, wi, region, R, MAX_REGIONS, "region_series", "wi")
     offset = float(offset)
     if not np.isfinite(offset):
         raise XmhwException(f"offset should be a finite number, got {offset}")
@@ -294,16 +283,9 @@ def region_series(temp, weights=None, regions=None, tdim="time", offset=0.0, any
         raise XmhwException(f"{int(n_range)} samples lie 2**{RANGE_BITS} and more from offset={offset} (or are infinite): "
                             "pass offset=273.15 for a series in kelvin")
     ib = weight_bits(int(keep.sum()))
-    # the regions of the result: the labels found on OCEAN cells
-    ocean = keep & (rid >= 0)
-    ncells = np.bincount(rid[ocean], minlength=Rc).astype(np.int64)
-    total_i = np.zeros(Rc, dtype=np.int64)
-    np.add.at(total_i, rid[ocean], wi[ocean])
-    if found.shape[0]:
-        sel = ncells > 0
-        acc, ncells, total_i, region = acc[:, sel], ncells[sel], total_i[sel], found[sel]
-    else:
-        region = np.zeros(1, dtype=np.int64)                    # every cell excluded: one empty region
+    sel, ncells, total_i, region = regions_of_result(keep, rid, wi, found)
+    if sel is not None:
+        acc = acc[:, sel]
     if _is_xarray(temp):
         enc, tattrs = dict(getattr(temp[tdim], "encoding", {}) or {}), dict(temp[tdim].attrs)
         sattrs = dict(temp.attrs)

@@ -37,12 +37,12 @@ device slab by slab, as coverage_grid()).
 import numpy as np
 
 from ._lib import hip
-from .api import GridSeries, _from_xarray, _is_xarray
 from .detect import EventDataset
 from .device import DeviceScope, as_xmhw_errors
 from .exception import XmhwException
 from .gridweights import quantise_weights, resolve_weights, weights_label
 from .objects import ObjectDataset
+from .series_stage import grid_layout, run, walk_cells, walk_grid
 from .track_common import ChainDataset, Selection
 from .tracks import TrackDataset
 
@@ -67,39 +67,45 @@ def selection_rows(mhw, obj, tr):
 
 
 class _Accumulators:
-    """The device accumulators of one call, initialised; they persist across the slabs and are read back once."""
+    """One call's arguments and its device accumulators: initialised by begin(); they persist across the slabs and are
+    read back once."""
 
-    def __init__(self, h, rows):
-        self.h, self.L, self.m = h, rows.L, rows.m
+    def __init__(self, rows, wi, coldSpells):
+        self.h, self.rows, self.wi, self.neg = hip(), rows, wi, int(bool(coldSpells))
+        self.L, self.m = rows.L, rows.m
+        self._scope = DeviceScope()
+
+    def begin(self, T=None, C=None):
+        """C: the cells of a dense series, which the table and the weights have to match"""
+        rows, s = self.rows, self._scope
+        if C is not None and (rows.row_offsets.shape != (C + 1,) or np.shape(self.wi) != (C,)):
+            raise XmhwException("the table does not have one block of rows per ocean cell of temp: mhw does not belong to temp")
         L = max(self.L, 1)
-        self._scope = s = DeviceScope()
-        try:
-            self.n_valid, self.wsum, self.isum, self.imax = s.alloc(4 * L), s.alloc(8 * L), s.alloc(8 * L), s.alloc(8 * L)
-            self.cat, self.count = s.alloc(4 * 4 * L), s.alloc(16)
-            self.time_start, self.offsets = s.upload(rows.time_start), s.upload(rows.offsets)
-            with as_xmhw_errors(also="Unsupported", hint="select fewer objects with ids= in mhw_tracks()"):
-                h.track_intensity_init(self.L, *self._out())
-        except BaseException:
-            s.free()
-            raise
+        self.n_valid, self.wsum, self.isum, self.imax = s.alloc(4 * L), s.alloc(8 * L), s.alloc(8 * L), s.alloc(8 * L)
+        self.cat, self.count = s.alloc(4 * 4 * L), s.alloc(16)
+        self.time_start, self.offsets = s.upload(rows.time_start), s.upload(rows.offsets)
+        with as_xmhw_errors(also="Unsupported", hint="select fewer objects with ids= in mhw_tracks()"):
+            self.h.track_intensity_init(self.L, *self._out())
 
     def _out(self):
         return (self.n_valid.ptr, self.wsum.ptr, self.isum.ptr, self.imax.ptr, self.cat.ptr, max(self.L, 1),
                 self.count.ptr, self.count.ptr + 8)
 
-    def add_slab(self, d_ts, isz, T, n, ld, se_ptr, th_ptr, ldc, D, row_of_t, neg, rows, k0, wi):
-        """the slab of compact cells k0..k0 + n - 1, its series already on the device: upload its rows, queue the pass"""
+    def add_slab(self, slab):
+        """One slab (series_stage.Slab), the compact cells k0..k0 + n - 1: upload its rows, queue the pass"""
+        rows, k0, n = self.rows, slab.k0, slab.n
         r0, r1 = int(rows.row_offsets[k0]), int(rows.row_offsets[k0 + n])
         if r1 == r0 or self.L == 0 or self.m == 0:
             return
         with DeviceScope() as s:
             d_start, d_end, d_slot = (s.upload(a[r0:r1]) for a in (rows.start, rows.end, rows.slot))
             d_roff = s.upload(rows.row_offsets[k0:k0 + n + 1] - r0)
-            d_wi = s.upload(np.ascontiguousarray(wi[k0:k0 + n], dtype=np.int64))
+            d_wi = s.upload(np.ascontiguousarray(self.wi[k0:k0 + n], dtype=np.int64))
             with as_xmhw_errors(also="Unsupported", hint="select fewer objects with ids= in mhw_tracks()"):
-                self.h.track_intensity_accumulate(d_ts.ptr, isz, T, n, ld, se_ptr, th_ptr, ldc, D, row_of_t, neg, d_start.ptr,
-                                                  d_end.ptr, d_slot.ptr, r1 - r0, d_roff.ptr, d_wi.ptr, self.time_start.ptr,
-                                                  self.offsets.ptr, self.m, self.L, *self._out())
+                self.h.track_intensity_accumulate(slab.d_ts.ptr, slab.isz, slab.T, n, slab.ld, slab.se_ptr, slab.th_ptr,
+                                                  slab.ldc, slab.D, slab.rows, self.neg, d_start.ptr, d_end.ptr, d_slot.ptr,
+                                                  r1 - r0, d_roff.ptr, d_wi.ptr, self.time_start.ptr, self.offsets.ptr,
+                                                  self.m, self.L, *self._out())
             self.h.stream_sync(0)                       # the slab's rows are freed on the way out
 
     def result(self):
@@ -121,27 +127,10 @@ def track_intensity_cells(ts, seas, thresh, doy, doys, rows, wi, coldSpells=Fals
     """The device stage for a dense (T, C) host series (arguments as coverage.coverage_cells): ``rows`` the selection_rows()
     of the selection, ``wi`` (C,) int64 weights.  Returns a dict of STAGE_FIELDS plus the counters n_range and n_bad.  Cells go
     through the device in batches below max_batch_bytes; the sums are integers, so the batch size does not change a bit."""
-    from .detect_front import _check_inputs
-    ts, seas, thresh, row_of_t = _check_inputs(ts, seas, thresh, doy, doys)
-    T, C = ts.shape
-    D = thresh.shape[0]
-    if rows.row_offsets.shape != (C + 1,) or np.shape(wi) != (C,):
-        raise XmhwException("the table does not have one block of rows per ocean cell of temp: mhw does not belong to temp")
-    h = hip()
-    isz = ts.dtype.itemsize
-    per_cell = T * isz + 2 * D * 8 + 64
-    batch = int(max(1, min(C, max_batch_bytes // max(per_cell, 1))))
-    acc = _Accumulators(h, rows)
+    acc = _Accumulators(rows, wi, coldSpells)
     try:
-        for c0 in range(0, C, batch):
-            n = min(C, c0 + batch) - c0
-            with DeviceScope() as s:
-                d_ts = s.upload(np.ascontiguousarray(ts[:, c0:c0 + n]))
-                if pad is not None:
-                    pad.apply(d_ts.ptr, isz, T, n)
-                d_se = s.upload(np.ascontiguousarray(seas[:, c0:c0 + n]))
-                d_th = s.upload(np.ascontiguousarray(thresh[:, c0:c0 + n]))
-                acc.add_slab(d_ts, isz, T, n, n, d_se.ptr, d_th.ptr, n, D, row_of_t, int(bool(coldSpells)), rows, c0, wi)
+        walk_cells(ts, seas, thresh, doy, doys, lambda T, isz, D: T * isz + 2 * D * 8 + 64, max_batch_bytes, pad, acc.add_slab,
+                   acc.begin)
         return acc.result()
     finally:
         acc.free()
@@ -150,70 +139,24 @@ def track_intensity_cells(ts, seas, thresh, doy, doys, rows, wi, coldSpells=Fals
 def track_intensity_grid(stacked, anynans, seas, thresh, doy, doys, rows, wi, keep_want, coldSpells=False,
                          max_batch_bytes=None, clim_stacked=False, pad=None):
     """track_intensity_cells() for an UNCOMPACTED stacked host series (T, N), as coverage.coverage_grid: the land mask and
-    the compaction run on the device slab by slab, the climatologies are compacted there as well and pair up with the
-    series' survivors by position.  ``keep_want`` (N,) bool: the land mask of the detection; a slab whose mask differs
-    is refused before it is used.  Returns (the stage dict, keep[N])."""
-    from .detect_front import _check_inputs, _rows_as_they_are
-    from .device import _grid_batch, compact_columns, device_itemsize, is_packed, native_float
-    T, N = stacked.shape
-    if not is_packed(stacked):
-        stacked = np.ascontiguousarray(native_float(stacked))
-    seas, thresh = _rows_as_they_are(seas), _rows_as_they_are(thresh)
-    if seas.ndim != 2 or thresh.ndim != 2 or seas.shape[0] != thresh.shape[0]:
-        raise XmhwException("seas and thresh must be (D, cells) arrays")
-    D = thresh.shape[0]
-    sample_dtype = stacked.decoded_dtype if is_packed(stacked) else stacked.dtype
-    _, _, _, row_of_t = _check_inputs(np.zeros((T, 1), dtype=sample_dtype), seas[:, :1], thresh[:, :1], doy, doys)
+    the compaction run on the device slab by slab (series_stage.walk_grid).  ``keep_want`` (N,) bool: the land mask of the
+    detection; a slab whose mask differs is refused before it is used.  Returns (the stage dict, keep[N])."""
+    N = stacked.shape[1]
     if keep_want.shape != (N,):
         raise XmhwException(f"temp has {N} grid points, the detection {keep_want.shape[0]}: mhw does not belong to temp")
-    h = hip()
-    isz = device_itemsize(stacked)
-    keeps = []
-    acc = _Accumulators(h, rows)
-    clim = DeviceScope()
-    k0 = 0
+
+    def check_keep(lo, hi, keep):
+        if not np.array_equal(keep, keep_want[lo:hi]):
+            raise XmhwException("the land mask of temp differs from mhw.keep: mhw does not belong to temp")
+
+    acc = _Accumulators(rows, wi, coldSpells)
     try:
-        if clim_stacked:
-            d_th, keep_th = compact_columns(thresh, 0, thresh.shape[1], anynans)
-            clim.adopt(d_th)
-            d_se, keep_se = compact_columns(seas, 0, seas.shape[1], anynans)
-            clim.adopt(d_se)
-            C, Cse = int(keep_th.sum()), int(keep_se.sum())
-            if C == 0 or Cse == 0:
-                raise XmhwException("All points of grid are either land or NaN")
-        else:
-            d_th, d_se = clim.upload(thresh), clim.upload(seas)
-            C, Cse = thresh.shape[1], seas.shape[1]
-        if C != Cse:
-            raise XmhwException(f"th and se do not have the same ocean cells: {C}, {Cse}")
-        cb = _grid_batch(stacked, max_batch_bytes, per_cell_extra=6 * D * 8 + 64)
-        for lo in range(0, N, cb):
-            hi = min(N, lo + cb)
-            d_ts, keep = compact_columns(stacked, lo, hi, anynans)
-            keeps.append(keep)
-            n = int(keep.sum())
-            with DeviceScope() as s:
-                s.adopt(d_ts)
-                if not np.array_equal(keep, keep_want[lo:hi]):
-                    raise XmhwException("the land mask of temp differs from mhw.keep: mhw does not belong to temp")
-                if d_ts is None:
-                    continue
-                if pad is not None:
-                    pad.apply(d_ts.ptr, isz, T, n)
-                if k0 + n > C:
-                    raise XmhwException(f"temp has more ocean cells than th and se ({C})")
-                acc.add_slab(d_ts, isz, T, n, n, d_se.ptr + 8 * k0, d_th.ptr + 8 * k0, C, D, row_of_t, int(bool(coldSpells)),
-                             rows, k0, wi)
-            k0 += n
-        keep = np.concatenate(keeps) if keeps else np.zeros(0, dtype=bool)
-        if not keep.any():
-            raise XmhwException("All points of grid are either land or NaN")
-        if k0 != C:
-            raise XmhwException(f"temp has {k0} ocean cells, th and se have {C}")
+        acc.begin()
+        keep = walk_grid(stacked, anynans, seas, thresh, doy, doys, lambda T, D: 6 * D * 8 + 64, max_batch_bytes,
+                         clim_stacked, pad, acc.add_slab, check_keep=check_keep)
         return acc.result(), keep
     finally:
         acc.free()
-        clim.free()
 
 
 class TrackIntensityDataset(ChainDataset):
@@ -283,7 +226,6 @@ def mhw_track_intensity(temp, th, se, mhw, obj, tr, weights=None, tdim="time", m
     Returns a TrackIntensityDataset (module docstring: the definition; class docstring: the fields).  Every integer is
     a sum of integers and the maximum is an integer maximum: exact, and the same from run to run and for every
     ``max_batch_bytes``.  ``_compute``: a stand-in for track_intensity_cells() (host tests)."""
-    from .detect import _detect
     if not isinstance(mhw, EventDataset):
         raise XmhwException("mhw_track_intensity expects the EventDataset returned by xmhw_amd.detect()")
     if not isinstance(obj, ObjectDataset):
@@ -298,19 +240,11 @@ def mhw_track_intensity(temp, th, se, mhw, obj, tr, weights=None, tdim="time", m
     params = mhw.attrs.get("xmhw_parameters")
     if params is not None and (_COLD_TEXT in params) != bool(coldSpells):
         raise XmhwException(f"coldSpells={bool(coldSpells)} differs from the detection's recorded parameters")
-    if _is_xarray(temp):
-        coords, coord_attrs = _from_xarray(temp)
-        dims = list(temp.dims)
-    else:
-        coords, dims = dict(temp.coords), list(temp.dims)
-    if tdim not in dims:
-        raise XmhwException(f"{tdim} dimension not present, default"
-                            + "is 'time' or pass as tdim='time_dimension_name'")
-    if len(dims) == 1:
+    layout = grid_layout(temp, tdim)
+    coords, _, _, point, sdims, sshape, _ = layout
+    if point:
         raise XmhwException("mhw_track_intensity needs a grid: a single-point series has no objects")
-    sdims = sorted(d for d in dims if d != tdim)
-    shape = tuple(temp.shape) if _is_xarray(temp) else tuple(np.shape(temp.values))
-    sshape = tuple(int(shape[dims.index(d)]) for d in sdims)
+    sshape = tuple(int(v) for v in sshape)
     if tuple(mhw.sdims) != tuple(sdims) or tuple(int(v) for v in mhw.sshape) != sshape:
         raise XmhwException(f"temp is on the grid {dict(zip(sdims, sshape))}, the detection on "
                             f"{dict(zip(mhw.sdims, mhw.sshape))}: mhw does not belong to temp")
@@ -327,28 +261,18 @@ def mhw_track_intensity(temp, th, se, mhw, obj, tr, weights=None, tdim="time", m
     keep_want = np.asarray(mhw.keep, dtype=bool).reshape(-1)
     got = {}
 
-    def on_cells(ts, sec, thc, doy, doys, minDuration, joinGaps, maxGap, coldSpells, intermediate, pad=None):
+    def on_cells(host_keep, ts, sec, thc, doy, doys, minDuration, joinGaps, maxGap, coldSpells, **extra):
         # _detect() has masked and compacted on the host (a stand-in device stage)
-        from .landmask import keep_mask, stack_cells
-        keep = keep_mask(stack_cells(np.asarray(temp.values), dims, tdim)[0], anynans)
-        if not np.array_equal(keep, keep_want):
+        if not np.array_equal(host_keep(), keep_want):
             raise XmhwException("the land mask of temp differs from mhw.keep: mhw does not belong to temp")
-        extra = {} if pad is None else {"pad": pad}
-        if max_batch_bytes is not None and _compute is None:
-            extra["max_batch_bytes"] = max_batch_bytes
         got["stage"] = (_compute or track_intensity_cells)(ts, sec, thc, doy, doys, rows, wi, coldSpells, **extra)
-        return dict(table=np.zeros((0, 31)), offsets=np.zeros(ts.shape[1] + 1, dtype=np.int64), inter=None)
 
-    def on_grid(stacked, anynans_, sec, thc, doy, doys, minDuration, joinGaps, maxGap, coldSpells, intermediate,
-                clim_stacked=False, pad=None):
+    def on_grid(stacked, anynans_, sec, thc, doy, doys, minDuration, joinGaps, maxGap, coldSpells, **extra):
         got["stage"], keep = track_intensity_grid(stacked, anynans_, sec, thc, doy, doys, rows, wi, keep_want, coldSpells,
-                                                  max_batch_bytes=max_batch_bytes, clim_stacked=clim_stacked, pad=pad)
-        return dict(table=np.zeros((0, 31)), offsets=np.zeros(int(keep.sum()) + 1, dtype=np.int64), inter=None, keep=keep)
+                                                  **extra)
+        return keep
 
-    series = GridSeries(temp.values, dims, coords, coord_attrs=coord_attrs) if _is_xarray(temp) else temp
-    as_series = lambda a: GridSeries(a.values, a.dims, _from_xarray(a)[0]) if _is_xarray(a) else a   # noqa: E731
-    _detect(series, as_series(th), as_series(se), on_cells, tdim, 5, True, 2, maxPadLength, coldSpells, False, anynans, tstep,
-            grid_compute=None if _compute is not None else on_grid)
+    run(temp, th, se, layout, tdim, on_cells, on_grid, maxPadLength, coldSpells, tstep, anynans, _compute, max_batch_bytes)
     st = got["stage"]
     if st.get("n_bad"):
         raise XmhwException(f"{st['n_bad']} voxels of table rows do not lie within their object's days: obj or tr does "
