@@ -986,6 +986,78 @@ int xmhw_cooccur_accumulate(const uint64_t *a_bits_dev, int64_t lda, const uint6
                             const int32_t *lags_host, int32_t L,
                             int32_t *counts_dev /* [K][L][4][ldo] */, int64_t ldo, void *stream);
 
+/* ---- mhw_displacement(): the thermal displacement of every MHW cell-day (Jacox et al. 2020) ---- *
+ * For a grid point in an event on a given day: the distance to the nearest grid point whose sample of that day is no
+ * warmer than the event point's own climatology -- how far an organism would have to move to stay at its usual
+ * temperature.  The first stage whose cells look at the field around them.
+ * The grid is (ny, nx), longitude the fast axis, point p = j * nx + i.  Offsets and distances: a source at (j, i) and a
+ * destination at (j', i') have dj = j' - j and di = i' - i, or, on a periodic grid, di = (i' - i) mod nx, minus nx if
+ * that exceeds nx / 2 (integer division).  In float64, with the latitudes phi, phi' and dlam = di * dlon in radians:
+ *     h       = sin^2((phi' - phi) / 2) + cos phi cos phi' sin^2(dlam / 2), clipped to [0, 1]
+ *     dist_m  = rint(1000 radius 2 asin(sqrt(h)))
+ *     north_m = rint(1000 radius (phi' - phi))
+ *     east_m  = rint(1000 radius cos((phi + phi') / 2) dlam)      (the mid-latitude zonal component)
+ * all three functions of (j, dj, di) alone.  The HOST makes, per grid row j, the list of all (dj, di) with
+ * 0 <= j + dj < ny, di admissible and dist_m <= rint(1000 max_distance), sorted ascending by (dist_m, dj, di); the first
+ * entry is (0, 0).  The lists arrive as CSR: list_off_dev[ny + 1] int64, the packed stream djdi_dev[] (dj << 16 |
+ * di & 0xFFFF, both int16) and dist_m_dev[], north_m_dev[], east_m_dev[] int32.  dist_m < 2^25.
+ * A SOURCE is a cell-day (c, t) in an event: bit t of column c of bits_dev is set, the bitmap of xmhw_event_table_bits
+ * over the C compact (ocean) cells and all T steps.  cell_of_point_dev[ny * nx] int32 maps a grid point to its compact
+ * cell (-1: land); basin_dev[ny * nx] int32 (or NULL) holds a basin label per grid point, and a source with a negative
+ * label is skipped and counted nowhere.  With x(t, p) = float64(ts[t][p]), negated when `negate`, the target of a source
+ * is g = seas_dev[row_of_t[t]][c], and the grid point p = (j + dj, i + di) QUALIFIES iff x(t, p) is not NaN (land is NaN
+ * in the uncompacted grid), x(t, p) <= g and, with a basin map, basin[p] == basin[source].  A point outside a
+ * non-periodic grid does not qualify; a source with NaN g finds nothing.  The source itself is candidate 0.  The result
+ * of a source is the FIRST qualifying entry of its row's list: the minimum of (dist_m, dj, di) over all qualifying
+ * points within reach.  Per class k = class_of_t[t] (-1 counts nowhere) and compact cell c:
+ *     n_days int32 [K][ldo]    the sources,          n_found int32 [K][ldo]    those that found an entry,
+ *     sum_m, sum_north_m, sum_east_m int64 [K][ldo]  the sums of the found entries' dist_m, north_m, east_m,
+ *     max_m int32 [K][ldo]     the largest dist_m found, 0 if none,
+ * and per call *n_visited_dev int64: the sum over the sources of the list entries that source alone had to look at --
+ * the position found plus one, or the whole list length; entries outside the grid included -- defined per source, not
+ * per wave, so it does not depend on the schedule.  At most 2^31 steps of less than 2^25 each: int64 cannot overflow.
+ * Everything is an integer sum or maximum: the result does not depend on the time blocks, the launch geometry or the
+ * schedule.
+ *  1. xmhw_displacement_init zeroes columns 0..C-1 of the accumulators and *n_visited_dev.
+ *  2. xmhw_displacement_accumulate_* takes the UNCOMPACTED series block ts_dev[nt][ld] (ld >= ny * nx) of the steps
+ *     t0 .. t0 + nt - 1, any nt >= 1 with t0 + nt <= T, and ADDS: calls for consecutive blocks follow each other on one
+ *     stream without a read-back.  row_of_t_host and class_of_t_host hold all T steps (uploaded once, cached by
+ *     content).  Lane = grid point; a wave = 64 consecutive longitudes of one grid row, so it shares one candidate list
+ *     and reads 64 consecutive samples per entry; the lanes still searching walk the list together and drop out as they
+ *     find; the addends of the current class stay in registers and leave as integer atomics without a return value
+ *     when the class changes and at the end of the block.  Every loop is bounded by a list length or the block's steps.
+ *     Every index is checked on the device where it is formed, whatever the tables hold.
+ * There is no finish call: nothing is kept in an encoded form.  ldo >= C; columns past C are never touched.  Refusals
+ * happen before anything is touched: K < 1, K > XMHW_DISPLACEMENT_MAX_CLASSES, T or C of 2^31 and more, ny or nx above
+ * XMHW_DISPLACEMENT_MAX_AXIS: XMHW_ERR_UNSUPPORTED.  A label outside [-1, K) or a row outside [0, D): XMHW_ERR_INVALID,
+ * checked on the host copies.  Nothing is launched for C == 0.  All calls are asynchronous on `stream`.
+ * xmhw_set_displacement_block (process-wide; tests and measurements): the steps a workgroup takes per block,
+ * 0 = automatic.  Same results for every value.                                                                      */
+#define XMHW_DISPLACEMENT_MAX_CLASSES 1024
+#define XMHW_DISPLACEMENT_MAX_AXIS    32767
+int xmhw_set_displacement_block(int32_t steps);       /* tests and measurements; 0 = automatic */
+int xmhw_displacement_init(int32_t K, int64_t C, int32_t *n_days_dev, int32_t *n_found_dev, int64_t *sum_m_dev,
+                           int64_t *sum_north_m_dev, int64_t *sum_east_m_dev, int32_t *max_m_dev, int64_t ldo,
+                           int64_t *n_visited_dev, void *stream);
+int xmhw_displacement_accumulate_f32(const float *ts_dev, int64_t ld, int64_t t0, int64_t nt, int64_t T, int32_t ny,
+                                     int32_t nx, int32_t periodic, const double *seas_dev, int64_t ldc, int64_t D,
+                                     const int32_t *row_of_t_host, int32_t negate, const uint64_t *bits_dev, int64_t ldb,
+                                     const int32_t *cell_of_point_dev, int64_t C, const int32_t *basin_dev,
+                                     const int64_t *list_off_dev, const int32_t *djdi_dev, const int32_t *dist_m_dev,
+                                     const int32_t *north_m_dev, const int32_t *east_m_dev, int64_t n_entries,
+                                     const int32_t *class_of_t_host, int32_t K, int32_t *n_days_dev, int32_t *n_found_dev,
+                                     int64_t *sum_m_dev, int64_t *sum_north_m_dev, int64_t *sum_east_m_dev,
+                                     int32_t *max_m_dev, int64_t ldo, int64_t *n_visited_dev, void *stream);
+int xmhw_displacement_accumulate_f64(const double *ts_dev, int64_t ld, int64_t t0, int64_t nt, int64_t T, int32_t ny,
+                                     int32_t nx, int32_t periodic, const double *seas_dev, int64_t ldc, int64_t D,
+                                     const int32_t *row_of_t_host, int32_t negate, const uint64_t *bits_dev, int64_t ldb,
+                                     const int32_t *cell_of_point_dev, int64_t C, const int32_t *basin_dev,
+                                     const int64_t *list_off_dev, const int32_t *djdi_dev, const int32_t *dist_m_dev,
+                                     const int32_t *north_m_dev, const int32_t *east_m_dev, int64_t n_entries,
+                                     const int32_t *class_of_t_host, int32_t K, int32_t *n_days_dev, int32_t *n_found_dev,
+                                     int64_t *sum_m_dev, int64_t *sum_north_m_dev, int64_t *sum_east_m_dev,
+                                     int32_t *max_m_dev, int64_t ldo, int64_t *n_visited_dev, void *stream);
+
 /* ---- the sharded path: cells split across the GPUs of a node, ONE gather at the end ------- *
  * Replaces the reference's collect, dask.compute(climls) + xr.concat(dim='cell')
  * (xmhw/xmhw.py:197, :210-211).  Cells are independent (xmhw/xmhw.py:184-196), so rank r runs the

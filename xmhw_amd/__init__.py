@@ -25,6 +25,7 @@ from .track_shape import mhw_track_shape, TrackShapeDataset, compactness
 from .region_series import region_series, RegionSeriesDataset
 from .days_by import mhw_days_by, ClassDaysDataset, classes_from_events
 from .cooccurrence import mhw_cooccurrence, CooccurrenceDataset
+from .displacement import mhw_displacement, displacement_offsets, DisplacementDataset, DisplacementTable
 from .ingest import open_series, threshold_file
 from .detrend import detrend, DetrendSpec, FitDataset
 
@@ -34,6 +35,7 @@ __all__ = ["threshold", "threshold_array", "GridSeries", "ClimDataset", "XmhwExc
            "CoverageDataset", "mhw_objects", "ObjectDataset", "mhw_tracks", "TrackDataset", "mhw_track_intensity",
            "TrackIntensityDataset", "mhw_track_parts", "TrackPartsDataset", "mhw_track_genealogy", "TrackGenealogyDataset",
            "mhw_track_shape", "TrackShapeDataset", "compactness", "region_series", "RegionSeriesDataset", "mhw_days_by", "ClassDaysDataset",
-           "classes_from_events", "mhw_cooccurrence", "CooccurrenceDataset", "open_series",
+           "classes_from_events", "mhw_cooccurrence", "CooccurrenceDataset", "mhw_displacement", "displacement_offsets",
+           "DisplacementDataset", "DisplacementTable", "open_series",
            "threshold_file", "detrend", "DetrendSpec", "FitDataset"]
 __version__ = "0.1.0"

@@ -813,6 +813,57 @@ static hipError_t cooccur_segments(const RowsRef& classes, int64_t Tn) {
     return hipSuccess;
 }
 
+static std::atomic<int> g_displacement_block{0};  // steps a workgroup takes per block, 0 = automatic (xmhw_set_displacement_block)
+
+static int displacement_check_shape(int32_t K, int64_t C) {
+    if (K < 1 || K > xmhw::kDisplacementMaxClasses)
+        return fail(XMHW_ERR_UNSUPPORTED,
+                    "displacement: K must be in [1, " + std::to_string(xmhw::kDisplacementMaxClasses) + "]");
+    if (C > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "displacement: 2^31 cells and more");
+    return XMHW_OK;
+}
+
+template <typename T>
+int displacement_accumulate(const T* ts, int64_t ld, int64_t t0, int64_t nt, int64_t Tn, int32_t ny, int32_t nx,
+                            int32_t periodic, const double* seas, int64_t ldc, int64_t D, const int32_t* row_of_t,
+                            int32_t negate, const uint64_t* bits, int64_t ldb, const int32_t* cell_of_point, int64_t C,
+                            const int32_t* basin, const int64_t* list_off, const int32_t* djdi, const int32_t* dist_m,
+                            const int32_t* north_m, const int32_t* east_m, int64_t n_entries, const int32_t* class_of_t,
+                            int32_t K, int32_t* n_days, int32_t* n_found, int64_t* sum_m, int64_t* sum_north_m,
+                            int64_t* sum_east_m, int32_t* max_m, int64_t ldo, int64_t* n_visited, void* stream) {
+    if (displacement_check_shape(K, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (Tn > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "displacement: 2^31 steps and more");
+    if (ny > xmhw::kDisplacementMaxAxis || nx > xmhw::kDisplacementMaxAxis)
+        return fail(XMHW_ERR_UNSUPPORTED, "displacement: a grid axis of 2^15 points and more");
+    if (ny < 1 || nx < 1) return fail(XMHW_ERR_INVALID, "bad ny/nx");
+    const int64_t N = static_cast<int64_t>(ny) * nx;
+    if (Tn <= 0 || t0 < 0 || nt < 1 || nt > Tn - t0) return fail(XMHW_ERR_INVALID, "bad T/t0/nt");
+    if (C < 0 || C > N || ld < N || ldc < C || ldb < C || ldo < C || D < 1 || n_entries < 0)
+        return fail(XMHW_ERR_INVALID, "bad C/ld/ldc/ldb/ldo/D/n_entries");
+    if (!class_of_t || !row_of_t) return fail(XMHW_ERR_INVALID, "NULL class_of_t or row_of_t");
+    for (int64_t t = 0; t < Tn; ++t) {
+        if (class_of_t[t] < -1 || class_of_t[t] >= K) return fail(XMHW_ERR_INVALID, "class_of_t outside [-1, K)");
+        if (row_of_t[t] < 0 || row_of_t[t] >= D) return fail(XMHW_ERR_INVALID, "row_of_t outside [0, D)");
+    }
+    if (C == 0) return XMHW_OK;
+    if (!ts || !seas || !bits || !cell_of_point || !list_off) return fail(XMHW_ERR_INVALID, "NULL buffer");
+    if (n_entries > 0 && (!djdi || !dist_m || !north_m || !east_m)) return fail(XMHW_ERR_INVALID, "NULL list buffer");
+    if (!n_days || !n_found || !sum_m || !sum_north_m || !sum_east_m || !max_m || !n_visited)
+        return fail(XMHW_ERR_INVALID, "NULL output buffer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipError_t e = hipSuccess;
+    const RowsRef rows = cached_rows(row_of_t, Tn, &e);
+    if (!rows) return hip_fail(e, "row table upload");
+    const RowsRef classes = cached_rows(class_of_t, Tn, &e);       // the same content-keyed cache: one more int32[T] table
+    if (!classes) return hip_fail(e, "class table upload");
+    e = xmhw::launch_displacement_accumulate<T>(ts, ld, t0, nt, ny, nx, periodic != 0, seas, ldc, rows->d_rows, negate != 0,
+                                                bits, ldb, cell_of_point, C, basin, list_off, djdi, dist_m, north_m, east_m,
+                                                n_entries, classes->d_rows, K, g_displacement_block.load(), n_days, n_found,
+                                                sum_m, sum_north_m, sum_east_m, max_m, ldo, n_visited, st);
+    if (e != hipSuccess) return hip_fail(e, "displacement_accumulate launch");
+    return XMHW_OK;
+}
+
 template <typename T>
 int event_stats_sparse(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* seas, const double* thresh,
                        int64_t ldc, const int32_t* row_of_t, int32_t negate, int64_t n_events, double* table,
@@ -2056,6 +2107,38 @@ int xmhw_cooccur_accumulate(const uint64_t* a_bits, int64_t lda, const uint64_t*
     if (e != hipSuccess) return hip_fail(e, "cooccur_accumulate launch");
     return XMHW_OK;
 }
+
+int xmhw_set_displacement_block(int32_t steps) {
+    if (steps < 0) return fail(XMHW_ERR_INVALID, "steps must be >= 0");
+    g_displacement_block = steps;
+    return XMHW_OK;
+}
+int xmhw_displacement_init(int32_t K, int64_t C, int32_t* n_days, int32_t* n_found, int64_t* sum_m, int64_t* sum_north_m,
+                           int64_t* sum_east_m, int32_t* max_m, int64_t ldo, int64_t* n_visited, void* stream) {
+    if (displacement_check_shape(K, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
+    if (!n_visited || (C > 0 && (!n_days || !n_found || !sum_m || !sum_north_m || !sum_east_m || !max_m)))
+        return fail(XMHW_ERR_INVALID, "NULL output buffer");
+    hipError_t e = xmhw::launch_displacement_init(K, C, n_days, n_found, sum_m, sum_north_m, sum_east_m, max_m, ldo, n_visited,
+                                                  static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "displacement_init");
+    return XMHW_OK;
+}
+#define XMHW_DISPLACEMENT_ENTRY(NAME, T)                                                                                 \
+    int NAME(const T* ts, int64_t ld, int64_t t0, int64_t nt, int64_t Tn, int32_t ny, int32_t nx, int32_t periodic,      \
+             const double* seas, int64_t ldc, int64_t D, const int32_t* row_of_t, int32_t negate, const uint64_t* bits,  \
+             int64_t ldb, const int32_t* cell_of_point, int64_t C, const int32_t* basin, const int64_t* list_off,        \
+             const int32_t* djdi, const int32_t* dist_m, const int32_t* north_m, const int32_t* east_m, int64_t n_entries, \
+             const int32_t* class_of_t, int32_t K, int32_t* n_days, int32_t* n_found, int64_t* sum_m,                    \
+             int64_t* sum_north_m, int64_t* sum_east_m, int32_t* max_m, int64_t ldo, int64_t* n_visited, void* stream) { \
+        return displacement_accumulate<T>(ts, ld, t0, nt, Tn, ny, nx, periodic, seas, ldc, D, row_of_t, negate, bits, ldb, \
+                                          cell_of_point, C, basin, list_off, djdi, dist_m, north_m, east_m, n_entries,   \
+                                          class_of_t, K, n_days, n_found, sum_m, sum_north_m, sum_east_m, max_m, ldo,    \
+                                          n_visited, stream);                                                            \
+    }
+XMHW_DISPLACEMENT_ENTRY(xmhw_displacement_accumulate_f32, float)
+XMHW_DISPLACEMENT_ENTRY(xmhw_displacement_accumulate_f64, double)
+#undef XMHW_DISPLACEMENT_ENTRY
 
 int xmhw_synth_sst_f32(float* ts, int64_t T, int64_t C, int64_t ld, int64_t cell0, uint64_t seed,
                        double nan_frac, void* stream) {

@@ -426,6 +426,32 @@ hipError_t launch_cooccur_accumulate(const uint64_t* a_bits, int64_t lda, const 
                                      const int32_t* lags, int32_t L, int64_t block_words, int32_t* counts, int64_t ldo,
                                      hipStream_t stream);
 
+// mhw_displacement() (kernels_displacement.hip): the thermal displacement of every MHW cell-day.  The series is the
+// UNCOMPACTED block ts[nt][ld] of the steps t0 .. t0 + nt - 1 on the (ny, nx) grid, longitude fastest; inev is the
+// in-event bitmap of launch_event_table_bits over the C compact cells and ALL steps; cell_of_point[ny * nx] maps a grid
+// point to its compact cell (-1: land), basin[ny * nx] (or NULL) holds its basin label (negative: no source).  Row j's
+// candidates are the entries list_off[j] .. list_off[j + 1] - 1 of djdi[] (dj << 16 | di & 0xFFFF), dist_m[], north_m[],
+// east_m[], sorted by (dist_m, dj, di).  launch_displacement_accumulate ADDS, per class k of the step and compact cell c,
+// the sources to n_days[k][c], those that found a qualifying entry to n_found[k][c], the entry's dist_m, north_m, east_m
+// to sum_m, sum_north_m, sum_east_m[k][c], raises max_m[k][c] to its dist_m and adds the entries every source looked at
+// to *n_visited (launch_displacement_init zeroes all of them).  row_of_t and class_of_t are DEVICE arrays over all steps
+// here.  block_steps: the steps a workgroup takes per block, 0 = automatic; same results for every value.
+constexpr int kDisplacementMaxClasses = 1024;
+constexpr int kDisplacementMaxAxis = 32767;          // dj and di are packed as int16
+hipError_t launch_displacement_init(int32_t K, int64_t C, int32_t* n_days, int32_t* n_found, int64_t* sum_m,
+                                    int64_t* sum_north_m, int64_t* sum_east_m, int32_t* max_m, int64_t ldo,
+                                    int64_t* n_visited, hipStream_t stream);
+template <typename T>
+hipError_t launch_displacement_accumulate(const T* ts, int64_t ld, int64_t t0, int64_t nt, int32_t ny, int32_t nx,
+                                          int32_t periodic, const double* seas, int64_t ldc, const int32_t* row_of_t,
+                                          int32_t negate, const uint64_t* inev, int64_t ldi, const int32_t* cell_of_point,
+                                          int64_t C, const int32_t* basin, const int64_t* list_off, const int32_t* djdi,
+                                          const int32_t* dist_m, const int32_t* north_m, const int32_t* east_m,
+                                          int64_t n_entries, const int32_t* class_of_t, int32_t K, int64_t block_steps,
+                                          int32_t* n_days, int32_t* n_found, int64_t* sum_m, int64_t* sum_north_m,
+                                          int64_t* sum_east_m, int32_t* max_m, int64_t ldo, int64_t* n_visited,
+                                          hipStream_t stream);
+
 // file bytes -> samples (kernels_ingest.hip): raw_type = item size of the stored type (2 int16, 4 float32,
 // 8 float64), swap = the file is big-endian, optional scale/offset (CF packing) and fill value -> NaN
 hipError_t launch_encode_i16(const float* in, int64_t rows, int64_t cols, int64_t ld_in, int16_t* out, int64_t ld_out,

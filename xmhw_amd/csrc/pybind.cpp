@@ -778,6 +778,53 @@ PYBIND11_MODULE(_xmhw_hip, m) {
                                       vp(stream)));
     }, py::arg("a_bits"), py::arg("lda"), py::arg("b_bits"), py::arg("ldb"), py::arg("T"), py::arg("C"),
        py::arg("class_of_t"), py::arg("K"), py::arg("lags"), py::arg("counts"), py::arg("ldo"), py::arg("stream") = 0);
+    m.attr("DISPLACEMENT_MAX_CLASSES") = XMHW_DISPLACEMENT_MAX_CLASSES;
+    m.attr("DISPLACEMENT_MAX_AXIS") = XMHW_DISPLACEMENT_MAX_AXIS;
+    m.def("set_displacement_block", [](int steps) { check(xmhw_set_displacement_block(steps)); }, py::arg("steps"));
+    m.def("displacement_init", [](int32_t K, int64_t C, uintptr_t n_days, uintptr_t n_found, uintptr_t sum_m,
+                                  uintptr_t sum_north_m, uintptr_t sum_east_m, uintptr_t max_m, int64_t ldo,
+                                  uintptr_t n_visited, uintptr_t stream) {
+        const auto i32 = [](uintptr_t p) { return static_cast<int32_t*>(vp(p)); };
+        const auto i64 = [](uintptr_t p) { return static_cast<int64_t*>(vp(p)); };
+        check(xmhw_displacement_init(K, C, i32(n_days), i32(n_found), i64(sum_m), i64(sum_north_m), i64(sum_east_m),
+                                     i32(max_m), ldo, i64(n_visited), vp(stream)));
+    }, py::arg("K"), py::arg("C"), py::arg("n_days"), py::arg("n_found"), py::arg("sum_m"), py::arg("sum_north_m"),
+       py::arg("sum_east_m"), py::arg("max_m"), py::arg("ldo"), py::arg("n_visited"), py::arg("stream") = 0);
+    m.def("displacement_accumulate", [](uintptr_t ts, int itemsize, int64_t ld, int64_t t0, int64_t nt, int64_t T, int32_t ny,
+                                        int32_t nx, int periodic, uintptr_t seas, int64_t ldc, int64_t D, i32arr row_of_t,
+                                        int negate, uintptr_t bits, int64_t ldb, uintptr_t cell_of_point, int64_t C,
+                                        uintptr_t basin, uintptr_t list_off, uintptr_t djdi, uintptr_t dist_m,
+                                        uintptr_t north_m, uintptr_t east_m, int64_t n_entries, i32arr class_of_t, int32_t K,
+                                        uintptr_t n_days, uintptr_t n_found, uintptr_t sum_m, uintptr_t sum_north_m,
+                                        uintptr_t sum_east_m, uintptr_t max_m, int64_t ldo, uintptr_t n_visited,
+                                        uintptr_t stream) {
+        if (row_of_t.size() != T) throw InvalidError("row_of_t length must equal T");
+        if (class_of_t.size() != T) throw InvalidError("class_of_t length must equal T");
+        if (itemsize != 4 && itemsize != 8) throw InvalidError("itemsize must be 4 or 8");
+        py::gil_scoped_release r;
+        const auto i32 = [](uintptr_t p) { return static_cast<int32_t*>(vp(p)); };
+        const auto i64 = [](uintptr_t p) { return static_cast<int64_t*>(vp(p)); };
+        const auto f64 = [](uintptr_t p) { return static_cast<double*>(vp(p)); };
+        if (itemsize == 4)
+            check(xmhw_displacement_accumulate_f32(static_cast<const float*>(vp(ts)), ld, t0, nt, T, ny, nx, periodic, f64(seas),
+                                                   ldc, D, row_of_t.data(), negate, static_cast<const uint64_t*>(vp(bits)), ldb,
+                                                   i32(cell_of_point), C, i32(basin), i64(list_off), i32(djdi), i32(dist_m),
+                                                   i32(north_m), i32(east_m), n_entries, class_of_t.data(), K, i32(n_days),
+                                                   i32(n_found), i64(sum_m), i64(sum_north_m), i64(sum_east_m), i32(max_m), ldo,
+                                                   i64(n_visited), vp(stream)));
+        else
+            check(xmhw_displacement_accumulate_f64(f64(ts), ld, t0, nt, T, ny, nx, periodic, f64(seas), ldc, D, row_of_t.data(),
+                                                   negate, static_cast<const uint64_t*>(vp(bits)), ldb, i32(cell_of_point), C,
+                                                   i32(basin), i64(list_off), i32(djdi), i32(dist_m), i32(north_m), i32(east_m),
+                                                   n_entries, class_of_t.data(), K, i32(n_days), i32(n_found), i64(sum_m),
+                                                   i64(sum_north_m), i64(sum_east_m), i32(max_m), ldo, i64(n_visited),
+                                                   vp(stream)));
+    }, py::arg("ts"), py::arg("itemsize"), py::arg("ld"), py::arg("t0"), py::arg("nt"), py::arg("T"), py::arg("ny"),
+       py::arg("nx"), py::arg("periodic"), py::arg("seas"), py::arg("ldc"), py::arg("D"), py::arg("row_of_t"),
+       py::arg("negate"), py::arg("bits"), py::arg("ldb"), py::arg("cell_of_point"), py::arg("C"), py::arg("basin"),
+       py::arg("list_off"), py::arg("djdi"), py::arg("dist_m"), py::arg("north_m"), py::arg("east_m"), py::arg("n_entries"),
+       py::arg("class_of_t"), py::arg("K"), py::arg("n_days"), py::arg("n_found"), py::arg("sum_m"), py::arg("sum_north_m"),
+       py::arg("sum_east_m"), py::arg("max_m"), py::arg("ldo"), py::arg("n_visited"), py::arg("stream") = 0);
     m.def("block_trend_ols", [](uintptr_t y, int32_t nstat, int32_t nb, int64_t C, int64_t ld, uintptr_t x, uintptr_t tcrit,
                                 uintptr_t out, int64_t ldo, uintptr_t stream) {
         check(xmhw_block_trend_ols(static_cast<const double*>(vp(y)), nstat, nb, C, ld, static_cast<const double*>(vp(x)),
