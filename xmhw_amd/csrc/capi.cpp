@@ -444,12 +444,12 @@ RowsRef cached_rows(const int32_t* row_of_t, int64_t Tn, hipError_t* err) {
 }
 
 // scratch memory per (device, stream): grows on demand (the only synchronising moment), never shrinks.  A caller
-// keeps the ScratchRef for the length of its call: a buffer that another thread on the same stream outgrows meanwhile
-// is freed only when its last holder is done.
+// keeps the ScratchRef for the length of its call -- scratch->get() is its buffer: a buffer that another thread on the
+// same stream outgrows meanwhile is freed only when its last holder is done.
 using ScratchRef = std::shared_ptr<void>;
 struct Scratch { ScratchRef ptr; size_t cap = 0; };
 std::map<std::pair<int, void*>, Scratch> g_scratch;
-hipError_t scratch_get(hipStream_t st, size_t bytes, void** out, ScratchRef* keep) {
+hipError_t scratch_get(hipStream_t st, size_t bytes, ScratchRef* keep) {
     std::lock_guard<std::mutex> lock(g_cache_mu);
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
@@ -468,7 +468,6 @@ hipError_t scratch_get(hipStream_t st, size_t bytes, void** out, ScratchRef* kee
         sc.ptr = ScratchRef(p, [](void* q) { (void)hipFree(q); });
         sc.cap = bytes;
     }
-    *out = sc.ptr.get();
     *keep = sc.ptr;
     return hipSuccess;
 }
@@ -477,6 +476,48 @@ void release_cached_tables() {
     (void)hipDeviceSynchronize();
     g_rows_cache.clear();
     g_scratch.clear();
+}
+
+// ---- the steps the stage entries share ----------------------------------------------------------
+// Each is one call in the entry, in the entry's own order: which refusal wins when two apply, and which zero-size return
+// comes before which NULL check, is part of the ABI (tests/test_host_entry_refusals.py).
+
+// the status of an entry's last HIP call as the entry's own
+int status_of(hipError_t e, const char* what) { return e == hipSuccess ? XMHW_OK : hip_fail(e, what); }
+
+// an int32 host table on the device (cached_rows); the caller holds *table until its launches are queued
+int upload_table(const int32_t* host, int64_t n, const char* what, RowsRef* table) {
+    hipError_t e = hipSuccess;
+    *table = cached_rows(host, n, &e);
+    return *table ? XMHW_OK : hip_fail(e, what);
+}
+
+// `bytes` of this stream's scratch buffer; the caller holds *scratch until its launches are queued
+int claim_scratch(hipStream_t st, size_t bytes, ScratchRef* scratch) {
+    return status_of(scratch_get(st, bytes, scratch), "scratch allocation");
+}
+
+// the first step whose label lies outside [lo, hi), or n
+int64_t first_outside(const int32_t* labels, int64_t n, int64_t lo, int64_t hi) {
+    int64_t t = 0;
+    while (t < n && labels[t] >= lo && labels[t] < hi) ++t;
+    return t;
+}
+int check_labels(const int32_t* labels, int64_t n, int64_t lo, int64_t hi, const char* message) {
+    return first_outside(labels, n, lo, hi) < n ? fail(XMHW_ERR_INVALID, message) : XMHW_OK;
+}
+constexpr const char* kRowsOutside = "row_of_t outside [0, D)";
+constexpr const char* kClassesOutside = "class_of_t outside [-1, K)";
+
+// the event-day bitmap of this call in this stream's scratch buffer: (T + 63) / 64 words per cell, leading dimension C
+int event_day_bitmap(const uint64_t* bits, int64_t Tn, int64_t C, int64_t ldb, int32_t min_duration, int32_t join_gaps,
+                     int32_t max_gap, hipStream_t st, ScratchRef* scratch, const uint64_t** inev) {
+    const int64_t W = (Tn + 63) / 64;
+    if (int rc = claim_scratch(st, sizeof(uint64_t) * static_cast<size_t>(W) * static_cast<size_t>(C), scratch)) return rc;
+    uint64_t* words = static_cast<uint64_t*>(scratch->get());
+    *inev = words;
+    return status_of(xmhw::launch_event_day_bits(bits, Tn, C, ldb, min_duration, join_gaps, max_gap, words, C, st),
+                     "event_day_bits launch");
 }
 
 template <typename T>
@@ -490,13 +531,11 @@ int detect_events(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* 
     if (!ts || !thresh || !row_of_t || !events || !start || !end)
         return fail(XMHW_ERR_INVALID, "NULL buffer");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipError_t e = hipSuccess;
-    const RowsRef rows = cached_rows(row_of_t, Tn, &e);
-    if (!rows) return hip_fail(e, "row table upload");
-    e = xmhw::launch_detect<T>(ts, Tn, C, ld, thresh, ldt, rows->d_rows, min_duration, join_gaps, max_gap, negate,
-                               events, start, end, bthresh, ldo, nevents, st);
-    if (e != hipSuccess) return hip_fail(e, "detect_events launch");
-    return XMHW_OK;
+    RowsRef rows;
+    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
+    return status_of(xmhw::launch_detect<T>(ts, Tn, C, ld, thresh, ldt, rows->d_rows, min_duration, join_gaps, max_gap,
+                                            negate, events, start, end, bthresh, ldo, nevents, st),
+                     "detect_events launch");
 }
 
 template <typename T>
@@ -508,12 +547,11 @@ int event_stats(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* se
     if (!ts || !seas || !thresh || !row_of_t || !events || !offsets)
         return fail(XMHW_ERR_INVALID, "NULL buffer");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipError_t e = hipSuccess;
-    const RowsRef rows = cached_rows(row_of_t, Tn, &e);
-    if (!rows) return hip_fail(e, "row table upload");
-    e = xmhw::launch_event_stats<T>(ts, Tn, C, ld, seas, thresh, ldc, rows->d_rows, negate, events, ldo, offsets, table, st);
-    if (e != hipSuccess) return hip_fail(e, "event_stats launch");
-    return XMHW_OK;
+    RowsRef rows;
+    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
+    return status_of(xmhw::launch_event_stats<T>(ts, Tn, C, ld, seas, thresh, ldc, rows->d_rows, negate, events, ldo,
+                                                 offsets, table, st),
+                     "event_stats launch");
 }
 
 static std::atomic<int> g_exceed_kernel{0};   // 0 auto, 1 per-step kernel, 2 tiled kernel (xmhw_set_exceed_kernel)
@@ -557,13 +595,11 @@ int exceed_bits(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* th
     if (Tn >= (int64_t{1} << 31)) return fail(XMHW_ERR_INVALID, "T too large");
     if (C == 0) return XMHW_OK;
     if (!ts || !thresh || !row_of_t || !bits) return fail(XMHW_ERR_INVALID, "NULL buffer");
-    for (int64_t t = 0; t < Tn; ++t)
-        if (row_of_t[t] < 0 || row_of_t[t] >= D) return fail(XMHW_ERR_INVALID, "row_of_t outside [0, D)");
+    if (int rc = check_labels(row_of_t, Tn, 0, D, kRowsOutside)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     constexpr int kTile = sizeof(T) == 4 ? 64 : 32;
-    hipError_t e = hipSuccess;
-    const RowsRef rows = cached_rows(row_of_t, Tn, &e);
-    if (!rows) return hip_fail(e, "row table upload");
+    RowsRef rows;
+    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
     // chunk tables of the tiled kernel: built and uploaded once per (row table, D, tile)
     ChunkTables* ct = nullptr;
     {
@@ -581,6 +617,7 @@ int exceed_bits(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* th
                 if (err == hipSuccess && !v.empty()) err = hipMemcpy(*dst, v.data(), sizeof(int32_t) * v.size(), hipMemcpyHostToDevice);
                 return err;
             };
+            hipError_t e = hipSuccess;
             for (auto pr : {std::make_pair(&t.tile_begin, &ch.tile_begin), std::make_pair(&t.t0, &ch.t0),
                             std::make_pair(&t.i0, &ch.i0), std::make_pair(&t.n, &ch.n)})
                 if (e == hipSuccess) e = put(pr.first, *pr.second);
@@ -597,22 +634,20 @@ int exceed_bits(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* th
     const bool tiled = mode == 2 || (mode == 0 && ct->nchunks * kTile <= 4 * Tn && C >= 131072);
     const int64_t W = (Tn + 63) / 64;
     float* thf = nullptr;
-    ScratchRef scratch_keep;
+    ScratchRef scratch;
     if constexpr (sizeof(T) == 4) {
         // float32 series: compare against the float32 floor of the thresholds (same results, see
         // kernels_events.hip), 4 instead of 8 bytes per threshold.  Only the addressed (D, C) region is
         // converted: `thresh` may point into a wider array (column block k0 of a (D, ldt) climatology),
         // where D * ldt elements would overrun it.  The copy lives in this stream's scratch buffer.
-        void* sp = nullptr;
-        e = scratch_get(st, sizeof(float) * static_cast<size_t>(D) * static_cast<size_t>(C), &sp, &scratch_keep);
-        if (e != hipSuccess) return hip_fail(e, "scratch allocation");
-        thf = static_cast<float*>(sp);
-        e = xmhw::launch_floor_to_f32(thresh, D, C, ldt, thf, C, st);
-        if (e != hipSuccess) return hip_fail(e, "floor_to_f32 launch");
+        if (int rc = claim_scratch(st, sizeof(float) * static_cast<size_t>(D) * static_cast<size_t>(C), &scratch)) return rc;
+        thf = static_cast<float*>(scratch.get());
+        if (int rc = status_of(xmhw::launch_floor_to_f32(thresh, D, C, ldt, thf, C, st), "floor_to_f32 launch")) return rc;
     }
     const int64_t ldtf = sizeof(T) == 4 ? C : ldt;   // leading dimension of the thresholds the kernels read
     if (tiled) {
-        e = ldb == C ? hipMemsetAsync(bits, 0, sizeof(uint64_t) * static_cast<size_t>(W) * static_cast<size_t>(C), st)
+        hipError_t e =
+            ldb == C ? hipMemsetAsync(bits, 0, sizeof(uint64_t) * static_cast<size_t>(W) * static_cast<size_t>(C), st)
                      : hipMemset2DAsync(bits, sizeof(uint64_t) * static_cast<size_t>(ldb), 0,
                                         sizeof(uint64_t) * static_cast<size_t>(C), static_cast<size_t>(W), st);
         if (e == hipSuccess) {
@@ -623,15 +658,16 @@ int exceed_bits(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* th
                 e = xmhw::launch_exceed_bits_tiled<double, double, 32>(ts, C, ld, thresh, ldt, D, ct->tile_begin, ct->ntiles,
                                                                        ct->t0, ct->i0, ct->n, negate, bits, ldb, st);
         }
-        if (e != hipSuccess) return hip_fail(e, "exceed_bits_tiled launch");
-        return XMHW_OK;
+        return status_of(e, "exceed_bits_tiled launch");
     }
     if constexpr (sizeof(T) == 4)
-        e = xmhw::launch_exceed_bits<float, float>(ts, Tn, C, ld, thf, ldtf, rows->d_rows, negate, bits, ldb, st);
+        return status_of(xmhw::launch_exceed_bits<float, float>(ts, Tn, C, ld, thf, ldtf, rows->d_rows, negate, bits, ldb,
+                                                                st),
+                         "exceed_bits launch");
     else
-        e = xmhw::launch_exceed_bits<double, double>(ts, Tn, C, ld, thresh, ldt, rows->d_rows, negate, bits, ldb, st);
-    if (e != hipSuccess) return hip_fail(e, "exceed_bits launch");
-    return XMHW_OK;
+        return status_of(xmhw::launch_exceed_bits<double, double>(ts, Tn, C, ld, thresh, ldt, rows->d_rows, negate, bits,
+                                                                  ldb, st),
+                         "exceed_bits launch");
 }
 
 template <typename T>
@@ -649,22 +685,14 @@ int coverage_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const do
     if (!ts || !seas || !thresh || !row_of_t || !bits || !wq || !region || !cells || !area_q)
         return fail(XMHW_ERR_INVALID, "NULL buffer");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipError_t e = hipSuccess;
-    const RowsRef rows = cached_rows(row_of_t, Tn, &e);
-    if (!rows) return hip_fail(e, "row table upload");
-    // the per-day in-event bitmap lives in this stream's scratch buffer: (T + 63) / 64 words per cell
-    const int64_t W = (Tn + 63) / 64;
-    void* sp = nullptr;
-    ScratchRef scratch_keep;
-    e = scratch_get(st, sizeof(uint64_t) * static_cast<size_t>(W) * static_cast<size_t>(C), &sp, &scratch_keep);
-    if (e != hipSuccess) return hip_fail(e, "scratch allocation");
-    uint64_t* inev = static_cast<uint64_t*>(sp);
-    e = xmhw::launch_event_day_bits(bits, Tn, C, ldb, min_duration, join_gaps, max_gap, inev, C, st);
-    if (e != hipSuccess) return hip_fail(e, "event_day_bits launch");
-    e = xmhw::launch_coverage_accumulate<T>(ts, Tn, C, ld, seas, thresh, ldc, rows->d_rows, negate, inev, C, wq, region, R,
-                                     cells, area_q, st);
-    if (e != hipSuccess) return hip_fail(e, "coverage_accumulate launch");
-    return XMHW_OK;
+    RowsRef rows;
+    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
+    ScratchRef scratch;
+    const uint64_t* inev = nullptr;
+    if (int rc = event_day_bitmap(bits, Tn, C, ldb, min_duration, join_gaps, max_gap, st, &scratch, &inev)) return rc;
+    return status_of(xmhw::launch_coverage_accumulate<T>(ts, Tn, C, ld, seas, thresh, ldc, rows->d_rows, negate, inev, C, wq,
+                                                         region, R, cells, area_q, st),
+                     "coverage_accumulate launch");
 }
 
 static std::atomic<int> g_region_wave_sum{1};   // region_accumulate sums 8 steps of a wave together (xmhw_set_region_wave_sum)
@@ -680,10 +708,9 @@ int region_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, double x0,
     if (!(x0 == x0) || std::isinf(x0)) return fail(XMHW_ERR_INVALID, "x0 must be finite");
     if (C == 0 || Tn == 0) return XMHW_OK;
     if (!ts || !wi || !region || !acc || !n_range) return fail(XMHW_ERR_INVALID, "NULL buffer");
-    hipError_t e = xmhw::launch_region_accumulate<T>(ts, Tn, C, ld, x0, wi, region, R, acc, n_range, g_region_wave_sum.load(),
-                                                     static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "region_accumulate launch");
-    return XMHW_OK;
+    return status_of(xmhw::launch_region_accumulate<T>(ts, Tn, C, ld, x0, wi, region, R, acc, n_range,
+                                                       g_region_wave_sum.load(), static_cast<hipStream_t>(stream)),
+                     "region_accumulate launch");
 }
 
 static std::atomic<int> g_track_intensity_combine{1};   // runs of equal entries summed in the wave (xmhw_set_track_intensity_combine)
@@ -704,18 +731,16 @@ int track_intensity_accumulate(const T* ts, int64_t Tn, int64_t n, int64_t ld, c
         return fail(XMHW_ERR_INVALID, "NULL buffer");
     if (!n_valid || !wsum_i || !isum_q || !intensity_max || !cat_cells || !n_range || !n_bad)
         return fail(XMHW_ERR_INVALID, "NULL output buffer");
-    for (int64_t t = 0; t < Tn; ++t)
-        if (row_of_t[t] < 0 || row_of_t[t] >= D) return fail(XMHW_ERR_INVALID, "row_of_t outside [0, D)");
+    if (int rc = check_labels(row_of_t, Tn, 0, D, kRowsOutside)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipError_t e = hipSuccess;
-    const RowsRef rows = cached_rows(row_of_t, Tn, &e);
-    if (!rows) return hip_fail(e, "row table upload");
-    e = xmhw::launch_track_intensity_accumulate<T>(ts, Tn, n, ld, seas, thresh, ldc, rows->d_rows, negate, start, end, slot,
-                                                   n_rows, row_offsets, wi, time_start, offsets, n_slots, L, n_valid, wsum_i,
-                                                   isum_q, intensity_max, cat_cells, ldcat, n_range, n_bad,
-                                                   g_track_intensity_combine.load(), st);
-    if (e != hipSuccess) return hip_fail(e, "track_intensity_accumulate launch");
-    return XMHW_OK;
+    RowsRef rows;
+    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
+    return status_of(xmhw::launch_track_intensity_accumulate<T>(ts, Tn, n, ld, seas, thresh, ldc, rows->d_rows, negate,
+                                                                start, end, slot, n_rows, row_offsets, wi, time_start,
+                                                                offsets, n_slots, L, n_valid, wsum_i, isum_q, intensity_max,
+                                                                cat_cells, ldcat, n_range, n_bad,
+                                                                g_track_intensity_combine.load(), st),
+                     "track_intensity_accumulate launch");
 }
 
 static std::atomic<int> g_class_days_block{0};   // steps a workgroup takes per block, 0 = automatic (xmhw_set_class_days_block)
@@ -737,30 +762,22 @@ int class_days_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const 
     if (Tn <= 0 || C < 0 || ld < C || ldc < C || ldb < C || ldo < C) return fail(XMHW_ERR_INVALID, "bad T/C/ld/ldc/ldb/ldo");
     if (min_duration < 1 || max_gap < 0) return fail(XMHW_ERR_INVALID, "bad minDuration/maxGap");
     if (!class_of_t) return fail(XMHW_ERR_INVALID, "NULL class_of_t");
-    for (int64_t t = 0; t < Tn; ++t)
-        if (class_of_t[t] < -1 || class_of_t[t] >= K) return fail(XMHW_ERR_INVALID, "class_of_t outside [-1, K)");
+    if (int rc = check_labels(class_of_t, Tn, -1, K, kClassesOutside)) return rc;
     if (C == 0) return XMHW_OK;
     if (!ts || !seas || !thresh || !row_of_t || !bits || !days || !isum_q || !intensity_max || !n_range)
         return fail(XMHW_ERR_INVALID, "NULL buffer");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipError_t e = hipSuccess;
-    const RowsRef rows = cached_rows(row_of_t, Tn, &e);
-    if (!rows) return hip_fail(e, "row table upload");
-    const RowsRef classes = cached_rows(class_of_t, Tn, &e);       // the same content-keyed cache: one more int32[T] table
-    if (!classes) return hip_fail(e, "class table upload");
-    // the per-day in-event bitmap lives in this stream's scratch buffer: (T + 63) / 64 words per cell
-    const int64_t W = (Tn + 63) / 64;
-    void* sp = nullptr;
-    ScratchRef scratch_keep;
-    e = scratch_get(st, sizeof(uint64_t) * static_cast<size_t>(W) * static_cast<size_t>(C), &sp, &scratch_keep);
-    if (e != hipSuccess) return hip_fail(e, "scratch allocation");
-    uint64_t* inev = static_cast<uint64_t*>(sp);
-    e = xmhw::launch_event_day_bits(bits, Tn, C, ldb, min_duration, join_gaps, max_gap, inev, C, st);
-    if (e != hipSuccess) return hip_fail(e, "event_day_bits launch");
-    e = xmhw::launch_class_days_accumulate<T>(ts, Tn, C, ld, seas, thresh, ldc, rows->d_rows, classes->d_rows, K, negate, inev,
-                                              C, g_class_days_block.load(), days, isum_q, intensity_max, ldo, n_range, st);
-    if (e != hipSuccess) return hip_fail(e, "class_days_accumulate launch");
-    return XMHW_OK;
+    RowsRef rows;
+    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
+    RowsRef classes;                                   // the same content-keyed cache: one more int32[T] table
+    if (int rc = upload_table(class_of_t, Tn, "class table upload", &classes)) return rc;
+    ScratchRef scratch;
+    const uint64_t* inev = nullptr;
+    if (int rc = event_day_bitmap(bits, Tn, C, ldb, min_duration, join_gaps, max_gap, st, &scratch, &inev)) return rc;
+    return status_of(xmhw::launch_class_days_accumulate<T>(ts, Tn, C, ld, seas, thresh, ldc, rows->d_rows, classes->d_rows,
+                                                           K, negate, inev, C, g_class_days_block.load(), days, isum_q,
+                                                           intensity_max, ldo, n_range, st),
+                     "class_days_accumulate launch");
 }
 
 static std::atomic<int> g_cooccur_block{0};      // words a workgroup takes per block, 0 = automatic (xmhw_set_cooccur_block)
@@ -841,27 +858,27 @@ int displacement_accumulate(const T* ts, int64_t ld, int64_t t0, int64_t nt, int
     if (C < 0 || C > N || ld < N || ldc < C || ldb < C || ldo < C || D < 1 || n_entries < 0)
         return fail(XMHW_ERR_INVALID, "bad C/ld/ldc/ldb/ldo/D/n_entries");
     if (!class_of_t || !row_of_t) return fail(XMHW_ERR_INVALID, "NULL class_of_t or row_of_t");
-    for (int64_t t = 0; t < Tn; ++t) {
-        if (class_of_t[t] < -1 || class_of_t[t] >= K) return fail(XMHW_ERR_INVALID, "class_of_t outside [-1, K)");
-        if (row_of_t[t] < 0 || row_of_t[t] >= D) return fail(XMHW_ERR_INVALID, "row_of_t outside [0, D)");
-    }
+    // the two tables are judged step by step: the one with the earlier bad label is named, class_of_t where both are bad
+    // at one step
+    const int64_t bad_class = first_outside(class_of_t, Tn, -1, K);
+    if (int rc = check_labels(row_of_t, bad_class, 0, D, kRowsOutside)) return rc;
+    if (bad_class < Tn) return fail(XMHW_ERR_INVALID, kClassesOutside);
     if (C == 0) return XMHW_OK;
     if (!ts || !seas || !bits || !cell_of_point || !list_off) return fail(XMHW_ERR_INVALID, "NULL buffer");
     if (n_entries > 0 && (!djdi || !dist_m || !north_m || !east_m)) return fail(XMHW_ERR_INVALID, "NULL list buffer");
     if (!n_days || !n_found || !sum_m || !sum_north_m || !sum_east_m || !max_m || !n_visited)
         return fail(XMHW_ERR_INVALID, "NULL output buffer");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipError_t e = hipSuccess;
-    const RowsRef rows = cached_rows(row_of_t, Tn, &e);
-    if (!rows) return hip_fail(e, "row table upload");
-    const RowsRef classes = cached_rows(class_of_t, Tn, &e);       // the same content-keyed cache: one more int32[T] table
-    if (!classes) return hip_fail(e, "class table upload");
-    e = xmhw::launch_displacement_accumulate<T>(ts, ld, t0, nt, ny, nx, periodic != 0, seas, ldc, rows->d_rows, negate != 0,
-                                                bits, ldb, cell_of_point, C, basin, list_off, djdi, dist_m, north_m, east_m,
-                                                n_entries, classes->d_rows, K, g_displacement_block.load(), n_days, n_found,
-                                                sum_m, sum_north_m, sum_east_m, max_m, ldo, n_visited, st);
-    if (e != hipSuccess) return hip_fail(e, "displacement_accumulate launch");
-    return XMHW_OK;
+    RowsRef rows;
+    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
+    RowsRef classes;                                   // the same content-keyed cache: one more int32[T] table
+    if (int rc = upload_table(class_of_t, Tn, "class table upload", &classes)) return rc;
+    return status_of(xmhw::launch_displacement_accumulate<T>(ts, ld, t0, nt, ny, nx, periodic != 0, seas, ldc, rows->d_rows,
+                                                             negate != 0, bits, ldb, cell_of_point, C, basin, list_off, djdi,
+                                                             dist_m, north_m, east_m, n_entries, classes->d_rows, K,
+                                                             g_displacement_block.load(), n_days, n_found, sum_m,
+                                                             sum_north_m, sum_east_m, max_m, ldo, n_visited, st),
+                     "displacement_accumulate launch");
 }
 
 template <typename T>
@@ -872,12 +889,11 @@ int event_stats_sparse(const T* ts, int64_t Tn, int64_t C, int64_t ld, const dou
     if (n_events == 0) return XMHW_OK;
     if (!ts || !seas || !thresh || !row_of_t || !table) return fail(XMHW_ERR_INVALID, "NULL buffer");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipError_t e = hipSuccess;
-    const RowsRef rows = cached_rows(row_of_t, Tn, &e);
-    if (!rows) return hip_fail(e, "row table upload");
-    e = xmhw::launch_event_stats_sparse<T>(ts, Tn, ld, seas, thresh, ldc, rows->d_rows, negate, n_events, table, st);
-    if (e != hipSuccess) return hip_fail(e, "event_stats_sparse launch");
-    return XMHW_OK;
+    RowsRef rows;
+    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
+    return status_of(xmhw::launch_event_stats_sparse<T>(ts, Tn, ld, seas, thresh, ldc, rows->d_rows, negate, n_events, table,
+                                                        st),
+                     "event_stats_sparse launch");
 }
 
 template <typename T>
@@ -889,13 +905,11 @@ int event_intermediate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const dou
     if (C == 0) return XMHW_OK;
     if (!ts || !seas || !thresh || !row_of_t || !events || !out || !dur) return fail(XMHW_ERR_INVALID, "NULL buffer");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipError_t e = hipSuccess;
-    const RowsRef rows = cached_rows(row_of_t, Tn, &e);
-    if (!rows) return hip_fail(e, "row table upload");
-    e = xmhw::launch_event_intermediate<T>(ts, Tn, C, ld, seas, thresh, ldc, rows->d_rows, negate, events, ldo, out, ldv, dur,
-                                           st);
-    if (e != hipSuccess) return hip_fail(e, "event_intermediate launch");
-    return XMHW_OK;
+    RowsRef rows;
+    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
+    return status_of(xmhw::launch_event_intermediate<T>(ts, Tn, C, ld, seas, thresh, ldc, rows->d_rows, negate, events, ldo,
+                                                        out, ldv, dur, st),
+                     "event_intermediate launch");
 }
 
 template <typename T>
@@ -930,22 +944,19 @@ int clim_host(const T* ts, const int32_t* doy, int64_t Tn, int64_t C, int32_t D,
     return rc;
 }
 
-}  // namespace
-
 template <typename T>
-static int block_time(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* cats, int64_t ldcat,
-                      const int32_t* bin_of_t, int32_t nbins, double* out, int64_t ldo, void* stream) {
+int block_time(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* cats, int64_t ldcat,
+               const int32_t* bin_of_t, int32_t nbins, double* out, int64_t ldo, void* stream) {
     if (C < 0 || Tn <= 0 || nbins <= 0 || ldo < C || ld < C || (cats && ldcat < C)) return fail(XMHW_ERR_INVALID, "bad C/T/nbins/ld");
     if (C == 0) return XMHW_OK;
     if (!ts || !bin_of_t || !out) return fail(XMHW_ERR_INVALID, "NULL buffer");
-    hipError_t e = xmhw::launch_block_time<T>(ts, Tn, C, ld, cats, ldcat, bin_of_t, nbins, out, ldo,
-                                              static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "block_time launch");
-    return XMHW_OK;
+    return status_of(xmhw::launch_block_time<T>(ts, Tn, C, ld, cats, ldcat, bin_of_t, nbins, out, ldo,
+                                                static_cast<hipStream_t>(stream)),
+                     "block_time launch");
 }
 
-static int fit_args(const void* ts, int64_t Tn, int64_t C, int64_t ld, const double* basis, int32_t P, const double* coef,
-                    int64_t ldc) {
+int fit_args(const void* ts, int64_t Tn, int64_t C, int64_t ld, const double* basis, int32_t P, const double* coef,
+             int64_t ldc) {
     if (Tn < 0 || C < 0) return fail(XMHW_ERR_INVALID, "bad T/C");
     if (P < 1) return fail(XMHW_ERR_INVALID, "P must be >= 1");
     if (P > XMHW_FIT_MAX_TERMS)
@@ -959,33 +970,33 @@ static int fit_args(const void* ts, int64_t Tn, int64_t C, int64_t ld, const dou
 }
 
 template <typename T>
-static int series_fit(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* basis, int32_t P, const uint8_t* weight,
-                      int32_t min_valid, double* coef, int64_t ldc, int32_t* nvalid, void* stream) {
+int series_fit(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* basis, int32_t P, const uint8_t* weight,
+               int32_t min_valid, double* coef, int64_t ldc, int32_t* nvalid, void* stream) {
     if (int rc = fit_args(ts, Tn, C, ld, basis, P, coef, ldc)) return rc;
     if (C == 0 || Tn == 0) return XMHW_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    void* sp = nullptr;
-    ScratchRef scratch_keep;
     const size_t gram_bytes = sizeof(double) * xmhw::kFitGramWords;      // then one flag byte per cell
-    hipError_t e = scratch_get(st, gram_bytes + static_cast<size_t>(C), &sp, &scratch_keep);
-    if (e != hipSuccess) return hip_fail(e, "scratch allocation");
-    e = xmhw::launch_series_fit<T>(ts, Tn, C, ld, basis, P, weight, min_valid > P ? min_valid : P, static_cast<double*>(sp),
-                                   static_cast<uint8_t*>(sp) + gram_bytes, coef, ldc, nvalid, st);
-    if (e != hipSuccess) return hip_fail(e, "series_fit launch");
-    return XMHW_OK;
+    ScratchRef scratch;
+    if (int rc = claim_scratch(st, gram_bytes + static_cast<size_t>(C), &scratch)) return rc;
+    void* sp = scratch.get();
+    return status_of(xmhw::launch_series_fit<T>(ts, Tn, C, ld, basis, P, weight, min_valid > P ? min_valid : P,
+                                                static_cast<double*>(sp), static_cast<uint8_t*>(sp) + gram_bytes, coef, ldc,
+                                                nvalid, st),
+                     "series_fit launch");
 }
 
 template <typename T>
-static int series_remove(T* ts, int64_t Tn, int64_t C, int64_t ld, const double* basis, int32_t P, int32_t R,
-                         const double* coef, int64_t ldc, void* stream) {
+int series_remove(T* ts, int64_t Tn, int64_t C, int64_t ld, const double* basis, int32_t P, int32_t R,
+                  const double* coef, int64_t ldc, void* stream) {
     if (int rc = fit_args(ts, Tn, C, ld, basis, P, coef, ldc)) return rc;
     if (R < 1 || R > P) return fail(XMHW_ERR_INVALID, "R must be in [1, P]");
     if (C == 0 || Tn == 0) return XMHW_OK;
     if ((Tn + 63) / 64 > 65535) return fail(XMHW_ERR_UNSUPPORTED, "T too large for one launch");
-    hipError_t e = xmhw::launch_series_remove<T>(ts, Tn, C, ld, basis, P, R, coef, ldc, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "series_remove launch");
-    return XMHW_OK;
+    return status_of(xmhw::launch_series_remove<T>(ts, Tn, C, ld, basis, P, R, coef, ldc, static_cast<hipStream_t>(stream)),
+                     "series_remove launch");
 }
+
+}  // namespace
 
 extern "C" {
 
@@ -1111,10 +1122,9 @@ int xmhw_encode_i16(const float* in_dev, int64_t rows, int64_t cols, int64_t ld_
     if (fill_code < -32768 || fill_code > 32767) return fail(XMHW_ERR_INVALID, "fill_code is not an int16");
     if (rows == 0 || cols == 0) return XMHW_OK;
     if (!in_dev || !out_dev) return fail(XMHW_ERR_INVALID, "NULL device buffer");
-    hipError_t e = xmhw::launch_encode_i16(in_dev, rows, cols, ld_in, out_dev, ld_out, scale_factor, add_offset, fill_code,
-                                           static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "encode launch");
-    return XMHW_OK;
+    return status_of(xmhw::launch_encode_i16(in_dev, rows, cols, ld_in, out_dev, ld_out, scale_factor, add_offset, fill_code,
+                                             static_cast<hipStream_t>(stream)),
+                     "encode launch");
 }
 int xmhw_read_rows(int fd, int64_t file_offset, int64_t row_pitch, int64_t row_bytes, int64_t rows, void* dst_host) {
     // pread() copies from the page cache (or the disk) straight into the caller's buffer -- for the ingest
@@ -1148,9 +1158,8 @@ int xmhw_pad_gaps(void* ts_dev, int itemsize, int64_t T, int64_t C, int64_t ld, 
     if (!(max_gap == max_gap)) return fail(XMHW_ERR_INVALID, "max_gap is NaN");
     if (T == 0 || C == 0) return XMHW_OK;
     if (!ts_dev || !x_dev) return fail(XMHW_ERR_INVALID, "NULL device buffer");
-    hipError_t e = xmhw::launch_pad_gaps(ts_dev, itemsize, T, C, ld, x_dev, max_gap, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "pad_gaps launch");
-    return XMHW_OK;
+    return status_of(xmhw::launch_pad_gaps(ts_dev, itemsize, T, C, ld, x_dev, max_gap, static_cast<hipStream_t>(stream)),
+                     "pad_gaps launch");
 }
 int xmhw_memset(void* dst, int value, size_t bytes, void* stream) {
     if (bytes == 0) return XMHW_OK;
@@ -1482,18 +1491,13 @@ int xmhw_clim_finish(const xmhw_plan* plan, const double* thresh_in, const doubl
     if (thresh_in == thresh_out || seas_in == seas_out)
         return fail(XMHW_ERR_INVALID, "in and out may not alias");
     const xmhw::Plan& h = plan->host;
-    void* flags = nullptr;      // per-column "has an absent group" flags of the one-pass finish kernel
-    ScratchRef scratch_keep;
-    if (smooth && smooth_width == 31) {
-        hipError_t se = scratch_get(static_cast<hipStream_t>(stream), static_cast<size_t>(C), &flags, &scratch_keep);
-        if (se != hipSuccess) return hip_fail(se, "scratch allocation");
-    }
-    hipError_t e = xmhw::launch_finish(thresh_in, seas_in, C, ldo, h.D, row_index(h, 59), row_index(h, 60),
-                                       row_index(h, 61), feb29_fix, smooth, smooth ? smooth_width : 1,
-                                       thresh_out, seas_out, static_cast<hipStream_t>(stream),
-                                       static_cast<uint8_t*>(flags));
-    if (e != hipSuccess) return hip_fail(e, "clim_finish launch");
-    return XMHW_OK;
+    ScratchRef flags;           // per-column "has an absent group" flags of the one-pass finish kernel
+    if (smooth && smooth_width == 31)
+        if (int rc = claim_scratch(static_cast<hipStream_t>(stream), static_cast<size_t>(C), &flags)) return rc;
+    return status_of(xmhw::launch_finish(thresh_in, seas_in, C, ldo, h.D, row_index(h, 59), row_index(h, 60),
+                                         row_index(h, 61), feb29_fix, smooth, smooth ? smooth_width : 1, thresh_out,
+                                         seas_out, static_cast<hipStream_t>(stream), static_cast<uint8_t*>(flags.get())),
+                     "clim_finish launch");
 }
 
 int xmhw_clim_f32(const float* ts, const int32_t* doy, int64_t T, int64_t C, int32_t D, int32_t w,
@@ -1522,16 +1526,14 @@ int xmhw_clim_host_f64(const double* ts, const int32_t* doy, int64_t T, int64_t 
 int xmhw_land_mask_f32(const float* ts, int64_t T, int64_t C, int64_t ld, int anynans, uint8_t* keep,
                        void* stream) {
     if (C < 0 || ld < C || T <= 0) return fail(XMHW_ERR_INVALID, "bad T/C/ld");
-    hipError_t e = xmhw::launch_land_mask<float>(ts, T, C, ld, anynans, keep, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "land_mask launch");
-    return XMHW_OK;
+    return status_of(xmhw::launch_land_mask<float>(ts, T, C, ld, anynans, keep, static_cast<hipStream_t>(stream)),
+                     "land_mask launch");
 }
 int xmhw_land_mask_f64(const double* ts, int64_t T, int64_t C, int64_t ld, int anynans, uint8_t* keep,
                        void* stream) {
     if (C < 0 || ld < C || T <= 0) return fail(XMHW_ERR_INVALID, "bad T/C/ld");
-    hipError_t e = xmhw::launch_land_mask<double>(ts, T, C, ld, anynans, keep, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "land_mask launch");
-    return XMHW_OK;
+    return status_of(xmhw::launch_land_mask<double>(ts, T, C, ld, anynans, keep, static_cast<hipStream_t>(stream)),
+                     "land_mask launch");
 }
 
 int xmhw_land_mask_i16(const int16_t* codes, int64_t T, int64_t C, int64_t ld, int big_endian, int has_fill,
@@ -1542,47 +1544,40 @@ int xmhw_land_mask_i16(const int16_t* codes, int64_t T, int64_t C, int64_t ld, i
     if (!codes || !keep) return fail(XMHW_ERR_INVALID, "NULL device buffer");
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (!has_fill) {           // no code means "missing": every cell stays
-        hipError_t e = hipMemsetAsync(keep, 1, static_cast<size_t>(C), st);
-        if (e != hipSuccess) return hip_fail(e, "land_mask memset");
-        return XMHW_OK;
+        return status_of(hipMemsetAsync(keep, 1, static_cast<size_t>(C), st), "land_mask memset");
     }
     uint16_t raw = static_cast<uint16_t>(static_cast<int16_t>(fill_code));
     if (big_endian) raw = static_cast<uint16_t>((raw >> 8) | (raw << 8));
-    hipError_t e = xmhw::launch_land_mask_i16(codes, T, C, ld, static_cast<int16_t>(raw), anynans, keep, st);
-    if (e != hipSuccess) return hip_fail(e, "land_mask launch");
-    return XMHW_OK;
+    return status_of(xmhw::launch_land_mask_i16(codes, T, C, ld, static_cast<int16_t>(raw), anynans, keep, st),
+                     "land_mask launch");
 }
 int xmhw_gather_cells_i16(const int16_t* in, int64_t rows, int64_t ld_in, const int64_t* index, int64_t n,
                           int16_t* out, int64_t ld_out, void* stream) {
     if (rows < 0 || n < 0 || ld_out < n) return fail(XMHW_ERR_INVALID, "bad rows/n/ld_out");
-    hipError_t e = xmhw::launch_gather_cells<int16_t>(in, rows, ld_in, index, n, out, ld_out,
-                                                      static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "gather_cells launch");
-    return XMHW_OK;
+    return status_of(xmhw::launch_gather_cells<int16_t>(in, rows, ld_in, index, n, out, ld_out,
+                                                        static_cast<hipStream_t>(stream)),
+                     "gather_cells launch");
 }
 int xmhw_gather_cells_f32(const float* in, int64_t rows, int64_t ld_in, const int64_t* index, int64_t n,
                           float* out, int64_t ld_out, void* stream) {
     if (rows < 0 || n < 0 || ld_out < n) return fail(XMHW_ERR_INVALID, "bad rows/n/ld_out");
-    hipError_t e = xmhw::launch_gather_cells<float>(in, rows, ld_in, index, n, out, ld_out,
-                                                    static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "gather_cells launch");
-    return XMHW_OK;
+    return status_of(xmhw::launch_gather_cells<float>(in, rows, ld_in, index, n, out, ld_out,
+                                                      static_cast<hipStream_t>(stream)),
+                     "gather_cells launch");
 }
 int xmhw_gather_cells_f64(const double* in, int64_t rows, int64_t ld_in, const int64_t* index, int64_t n,
                           double* out, int64_t ld_out, void* stream) {
     if (rows < 0 || n < 0 || ld_out < n) return fail(XMHW_ERR_INVALID, "bad rows/n/ld_out");
-    hipError_t e = xmhw::launch_gather_cells<double>(in, rows, ld_in, index, n, out, ld_out,
-                                                     static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "gather_cells launch");
-    return XMHW_OK;
+    return status_of(xmhw::launch_gather_cells<double>(in, rows, ld_in, index, n, out, ld_out,
+                                                       static_cast<hipStream_t>(stream)),
+                     "gather_cells launch");
 }
 int xmhw_scatter_cells_f64(const double* in, int64_t rows, int64_t ld_in, const int64_t* index, int64_t n,
                            double* out, int64_t ld_out, void* stream) {
     if (rows < 0 || n < 0 || ld_in < n) return fail(XMHW_ERR_INVALID, "bad rows/n/ld_in");
-    hipError_t e = xmhw::launch_scatter_cells(in, rows, ld_in, index, n, out, ld_out, ld_out,
-                                              static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "scatter_cells launch");
-    return XMHW_OK;
+    return status_of(xmhw::launch_scatter_cells(in, rows, ld_in, index, n, out, ld_out, ld_out,
+                                                static_cast<hipStream_t>(stream)),
+                     "scatter_cells launch");
 }
 
 int xmhw_detect_events_f32(const float* ts, int64_t T, int64_t C, int64_t ld, const double* thresh, int64_t ldt,
@@ -1604,31 +1599,18 @@ int xmhw_count_events(const int32_t* start, int64_t T, int64_t C, int64_t ldo, i
     if (T <= 0 || C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad T/C/ldo");
     if (C == 0) return XMHW_OK;
     if (!start || !nevents) return fail(XMHW_ERR_INVALID, "NULL buffer");
-    hipError_t e = xmhw::launch_count_events(start, T, C, ldo, nevents, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "count_events launch");
-    return XMHW_OK;
+    return status_of(xmhw::launch_count_events(start, T, C, ldo, nevents, static_cast<hipStream_t>(stream)),
+                     "count_events launch");
 }
 int xmhw_event_stats_f32(const float* ts, int64_t T, int64_t C, int64_t ld, const double* seas,
                          const double* thresh, int64_t ldc, const int32_t* row_of_t, int32_t negate,
                          const int32_t* events, int64_t ldo, const int64_t* offsets, double* table, void* stream) {
     return event_stats<float>(ts, T, C, ld, seas, thresh, ldc, row_of_t, negate, events, ldo, offsets, table, stream);
 }
-int xmhw_release_cached_tables(void) {
-    release_cached_tables();
-    return XMHW_OK;
-}
-int xmhw_offsets_from_counts(const int32_t* counts_dev, int64_t n, int64_t* offsets_dev, void* stream) {
-    if (n < 0) return fail(XMHW_ERR_INVALID, "n must be >= 0");
-    if (!offsets_dev || (n > 0 && !counts_dev)) return fail(XMHW_ERR_INVALID, "NULL buffer");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    void* sp = nullptr;
-    ScratchRef scratch_keep;
-    const int64_t nblocks = (n + 1023) / 1024;
-    hipError_t e = scratch_get(st, sizeof(int64_t) * static_cast<size_t>(nblocks + 1), &sp, &scratch_keep);
-    if (e != hipSuccess) return hip_fail(e, "scratch allocation");
-    e = xmhw::launch_offsets_from_counts(counts_dev, n, offsets_dev, static_cast<int64_t*>(sp), st);
-    if (e != hipSuccess) return hip_fail(e, "offsets_from_counts launch");
-    return XMHW_OK;
+int xmhw_event_stats_f64(const double* ts, int64_t T, int64_t C, int64_t ld, const double* seas,
+                         const double* thresh, int64_t ldc, const int32_t* row_of_t, int32_t negate,
+                         const int32_t* events, int64_t ldo, const int64_t* offsets, double* table, void* stream) {
+    return event_stats<double>(ts, T, C, ld, seas, thresh, ldc, row_of_t, negate, events, ldo, offsets, table, stream);
 }
 int xmhw_set_exceed_kernel(int32_t mode) {
     if (mode < 0 || mode > 2) return fail(XMHW_ERR_INVALID, "mode must be 0 (auto), 1 (per-step) or 2 (tiled)");
@@ -1652,10 +1634,9 @@ int xmhw_events_from_bits(const uint64_t* bits, int64_t T, int64_t C, int64_t ld
     if (C == 0) return XMHW_OK;
     if (!bits || (!offsets && !nevents) || (offsets && !table)) return fail(XMHW_ERR_INVALID, "NULL buffer");
     if (min_duration < 1 || max_gap < 0) return fail(XMHW_ERR_INVALID, "bad minDuration/maxGap");
-    hipError_t e = xmhw::launch_events_from_bits(bits, T, C, ldb, min_duration, join_gaps, max_gap, offsets,
-                                                 nevents, table, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "events_from_bits launch");
-    return XMHW_OK;
+    return status_of(xmhw::launch_events_from_bits(bits, T, C, ldb, min_duration, join_gaps, max_gap, offsets, nevents,
+                                                   table, static_cast<hipStream_t>(stream)),
+                     "events_from_bits launch");
 }
 int xmhw_event_stats_sparse_f32(const float* ts, int64_t T, int64_t C, int64_t ld, const double* seas,
                                 const double* thresh, int64_t ldc, const int32_t* row_of_t, int32_t negate,
@@ -1681,10 +1662,19 @@ int xmhw_event_intermediate_f64(const double* ts, int64_t T, int64_t C, int64_t 
     return event_intermediate<double>(ts, T, C, ld, seas, thresh, ldc, row_of_t, negate, events, ldo, out, ldv, dur,
                                       stream);
 }
-int xmhw_event_stats_f64(const double* ts, int64_t T, int64_t C, int64_t ld, const double* seas,
-                         const double* thresh, int64_t ldc, const int32_t* row_of_t, int32_t negate,
-                         const int32_t* events, int64_t ldo, const int64_t* offsets, double* table, void* stream) {
-    return event_stats<double>(ts, T, C, ld, seas, thresh, ldc, row_of_t, negate, events, ldo, offsets, table, stream);
+int xmhw_release_cached_tables(void) {
+    release_cached_tables();
+    return XMHW_OK;
+}
+int xmhw_offsets_from_counts(const int32_t* counts_dev, int64_t n, int64_t* offsets_dev, void* stream) {
+    if (n < 0) return fail(XMHW_ERR_INVALID, "n must be >= 0");
+    if (!offsets_dev || (n > 0 && !counts_dev)) return fail(XMHW_ERR_INVALID, "NULL buffer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int64_t nblocks = (n + 1023) / 1024;
+    ScratchRef scratch;
+    if (int rc = claim_scratch(st, sizeof(int64_t) * static_cast<size_t>(nblocks + 1), &scratch)) return rc;
+    return status_of(xmhw::launch_offsets_from_counts(counts_dev, n, offsets_dev, static_cast<int64_t*>(scratch.get()), st),
+                     "offsets_from_counts launch");
 }
 
 int xmhw_block_events(const double* table, const int64_t* offsets, int64_t C, const int32_t* bin_of_t, int64_t T,
@@ -1693,10 +1683,9 @@ int xmhw_block_events(const double* table, const int64_t* offsets, int64_t C, co
     if (mtime_column < 0 || mtime_column >= xmhw::kEventColumns) return fail(XMHW_ERR_INVALID, "bad mtime column");
     if (C == 0) return XMHW_OK;
     if (!table || !offsets || !bin_of_t || !out) return fail(XMHW_ERR_INVALID, "NULL buffer");
-    hipError_t e = xmhw::launch_block_events(table, offsets, C, bin_of_t, T, nbins, mtime_column, out, ldo,
-                                             static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "block_events launch");
-    return XMHW_OK;
+    return status_of(xmhw::launch_block_events(table, offsets, C, bin_of_t, T, nbins, mtime_column, out, ldo,
+                                               static_cast<hipStream_t>(stream)),
+                     "block_events launch");
 }
 int xmhw_block_time_f32(const float* ts, int64_t T, int64_t C, int64_t ld, const double* cats, int64_t ldcat,
                         const int32_t* bin_of_t, int32_t nbins, double* out, int64_t ldo, void* stream) {
@@ -1722,11 +1711,10 @@ int xmhw_event_rank(const double* table, int64_t ld_table, const int64_t* offset
     // scratch: item counts (int32, C), item offsets (int64, C + 1), the scan's block sums, the item counter
     const size_t n_counts = static_cast<size_t>(C + 1) & ~size_t{1};
     const size_t n_sums = static_cast<size_t>((C + 1023) / 1024 + 1);
-    void* sp = nullptr;
-    ScratchRef scratch_keep;
-    hipError_t e = scratch_get(st, sizeof(int32_t) * n_counts + sizeof(int64_t) * (static_cast<size_t>(C) + 2 + n_sums), &sp,
-                               &scratch_keep);
-    if (e != hipSuccess) return hip_fail(e, "scratch allocation");
+    ScratchRef scratch;
+    const size_t bytes = sizeof(int32_t) * n_counts + sizeof(int64_t) * (static_cast<size_t>(C) + 2 + n_sums);
+    if (int rc = claim_scratch(st, bytes, &scratch)) return rc;
+    void* sp = scratch.get();
     int32_t* counts = static_cast<int32_t*>(sp);
     int64_t* item_off = reinterpret_cast<int64_t*>(counts + n_counts);
     int64_t* sums = item_off + C + 1;
@@ -1746,8 +1734,9 @@ int xmhw_event_rank(const double* table, int64_t ld_table, const int64_t* offset
         }
         rc.ncols = static_cast<int32_t>(b - a);
         rc.span = cols[b - 1].first - rc.cmin + 1;
-        e = xmhw::launch_event_rank(table, ld_table, offsets, C, rc, n_years, rank, rp, ld_out, counts, item_off, sums, next_item, st);
-        if (e != hipSuccess) return hip_fail(e, "event_rank launch");
+        const hipError_t e = xmhw::launch_event_rank(table, ld_table, offsets, C, rc, n_years, rank, rp, ld_out, counts, item_off,
+                                                     sums, next_item, st);
+        if (int err = status_of(e, "event_rank launch")) return err;
         a = b;
     }
     return XMHW_OK;
@@ -1770,9 +1759,8 @@ int xmhw_block_trend_ols(const double* y, int32_t nstat, int32_t nb, int64_t C, 
     if (nstat == 0 || C == 0) return XMHW_OK;
     if (nb >= 3 && !tcrit) return fail(XMHW_ERR_INVALID, "NULL tcrit table");
     if (static_cast<int64_t>(nstat) * ((C + 63) / 64) > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "nstat * C too large for one launch");
-    hipError_t e = xmhw::launch_trend_ols(y, nstat, nb, C, ld, x, tcrit, out, ldo, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "trend_ols launch");
-    return XMHW_OK;
+    return status_of(xmhw::launch_trend_ols(y, nstat, nb, C, ld, x, tcrit, out, ldo, static_cast<hipStream_t>(stream)),
+                     "trend_ols launch");
 }
 
 int xmhw_block_trend_theil_sen(const double* y, int32_t nstat, int32_t nb, int64_t C, int64_t ld, const double* x,
@@ -1782,9 +1770,8 @@ int xmhw_block_trend_theil_sen(const double* y, int32_t nstat, int32_t nb, int64
         return fail(XMHW_ERR_UNSUPPORTED, "Theil-Sen trend: nb above the cap of " + std::to_string(xmhw::kTrendMaxBlocks) + " blocks");
     if (nstat == 0 || C == 0) return XMHW_OK;
     if (static_cast<int64_t>(nstat) * ((C + 15) / 16) > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "nstat * C too large for one launch");
-    hipError_t e = xmhw::launch_trend_theil_sen(y, nstat, nb, C, ld, x, out, ldo, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "trend_theil_sen launch");
-    return XMHW_OK;
+    return status_of(xmhw::launch_trend_theil_sen(y, nstat, nb, C, ld, x, out, ldo, static_cast<hipStream_t>(stream)),
+                     "trend_theil_sen launch");
 }
 
 int xmhw_series_fit_f32(const float* ts, int64_t T, int64_t C, int64_t ld, const double* basis, int32_t P,
@@ -1843,10 +1830,9 @@ int xmhw_event_objects(const int32_t* start, const int32_t* end, int64_t n, cons
     if (n == 0) return XMHW_OK;
     if (C == 0) return fail(XMHW_ERR_INVALID, "rows without cells");
     if (!start || !end || !offsets || !nbr || !cell_of_row || !root) return fail(XMHW_ERR_INVALID, "NULL buffer");
-    hipError_t e = xmhw::launch_event_objects(start, end, n, offsets, C, nbr, K, gap, cell_of_row, root,
-                                              static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "event_objects launch");
-    return XMHW_OK;
+    return status_of(xmhw::launch_event_objects(start, end, n, offsets, C, nbr, K, gap, cell_of_row, root,
+                                                static_cast<hipStream_t>(stream)),
+                     "event_objects launch");
 }
 
 int xmhw_object_reduce(const int32_t* start, const int32_t* end, const double* imax, int64_t n, const int32_t* cell_of_row,
@@ -1859,11 +1845,10 @@ int xmhw_object_reduce(const int32_t* start, const int32_t* end, const double* i
     if (!n_events || !n_cells || !time_start || !time_end || !cell_days || !area_days_q || !intensity_max || !peak_row)
         return fail(XMHW_ERR_INVALID, "NULL output buffer");
     if (n > 0 && (!start || !end || !imax || !cell_of_row || !offsets || !wq || !slot)) return fail(XMHW_ERR_INVALID, "NULL buffer");
-    hipError_t e = xmhw::launch_object_reduce(start, end, imax, n, cell_of_row, offsets, wq, slot, n_slots, n_events, n_cells,
-                                              time_start, time_end, cell_days, area_days_q, intensity_max, peak_row,
-                                              static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "object_reduce launch");
-    return XMHW_OK;
+    return status_of(xmhw::launch_object_reduce(start, end, imax, n, cell_of_row, offsets, wq, slot, n_slots, n_events,
+                                                n_cells, time_start, time_end, cell_days, area_days_q, intensity_max,
+                                                peak_row, static_cast<hipStream_t>(stream)),
+                     "object_reduce launch");
 }
 
 int xmhw_object_tracks(const int32_t* start, const int32_t* end, int64_t n, const int32_t* slot, const int32_t* cell_of_row,
@@ -1877,14 +1862,12 @@ int xmhw_object_tracks(const int32_t* start, const int32_t* end, int64_t n, cons
     if (n > 0 && n_slots > 0 && L > 0 && (!start || !end || !slot || !cell_of_row || !vec || !time_start || !offsets))
         return fail(XMHW_ERR_INVALID, "NULL buffer");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    void* sp = nullptr;                              // the levels of tile sums live in this stream's scratch buffer
-    ScratchRef scratch_keep;
-    hipError_t e = scratch_get(st, xmhw::object_tracks_scratch_bytes(L + 1), &sp, &scratch_keep);
-    if (e != hipSuccess) return hip_fail(e, "scratch allocation");
-    e = xmhw::launch_object_tracks(start, end, n, slot, cell_of_row, C, vec, ldv, time_start, offsets, n_slots, L, n_cells, sums,
-                                   ld, n_bad, static_cast<int64_t*>(sp), st);
-    if (e != hipSuccess) return hip_fail(e, "object_tracks launch");
-    return XMHW_OK;
+    // the levels of tile sums live in this stream's scratch buffer
+    ScratchRef scratch;
+    if (int rc = claim_scratch(st, xmhw::object_tracks_scratch_bytes(L + 1), &scratch)) return rc;
+    return status_of(xmhw::launch_object_tracks(start, end, n, slot, cell_of_row, C, vec, ldv, time_start, offsets, n_slots,
+                                                L, n_cells, sums, ld, n_bad, static_cast<int64_t*>(scratch.get()), st),
+                     "object_tracks launch");
 }
 
 int xmhw_object_parts(const int32_t* start, const int32_t* end, const int32_t* slot, const int32_t* cell_of_row, int64_t n,
@@ -1901,14 +1884,13 @@ int xmhw_object_parts(const int32_t* start, const int32_t* end, const int32_t* s
         (!start || !end || !slot || !cell_of_row || !row_offsets || !nbr || !wq || !vox_off || !time_start || !offsets))
         return fail(XMHW_ERR_INVALID, "NULL buffer");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    void* sp = nullptr;                              // parent, cells and area of every voxel live in this stream's scratch buffer
-    ScratchRef scratch_keep;
-    hipError_t e = scratch_get(st, xmhw::object_parts_scratch_bytes(V), &sp, &scratch_keep);
-    if (e != hipSuccess) return hip_fail(e, "scratch allocation");
-    e = xmhw::launch_object_parts(start, end, slot, cell_of_row, n, row_offsets, C, nbr, K, wq, vox_off, V, time_start, offsets,
-                                  n_slots, L, n_parts, cells_largest, area_largest_q, n_bad, sp, st);
-    if (e != hipSuccess) return hip_fail(e, "object_parts launch");
-    return XMHW_OK;
+    // parent, cells and area of every voxel live in this stream's scratch buffer
+    ScratchRef scratch;
+    if (int rc = claim_scratch(st, xmhw::object_parts_scratch_bytes(V), &scratch)) return rc;
+    return status_of(xmhw::launch_object_parts(start, end, slot, cell_of_row, n, row_offsets, C, nbr, K, wq, vox_off, V,
+                                               time_start, offsets, n_slots, L, n_parts, cells_largest, area_largest_q,
+                                               n_bad, scratch.get(), st),
+                     "object_parts launch");
 }
 
 static_assert(xmhw::kGenealogyVoxelBytes == XMHW_GENEALOGY_VOXEL_BYTES && xmhw::kGenealogySlotBytes == XMHW_GENEALOGY_SLOT_BYTES &&
@@ -1935,14 +1917,13 @@ int xmhw_object_genealogy(const int32_t* start, const int32_t* end, const int32_
         (!start || !end || !slot || !cell_of_row || !row_offsets || !nbr || !vox_off || !time_start || !offsets))
         return fail(XMHW_ERR_INVALID, "NULL buffer");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    void* sp = nullptr;                              // the hash set and parent, indeg, outdeg of every voxel: this stream's scratch
-    ScratchRef scratch_keep;
-    hipError_t e = scratch_get(st, xmhw::object_genealogy_scratch_bytes(V, edge_capacity), &sp, &scratch_keep);
-    if (e != hipSuccess) return hip_fail(e, "scratch allocation");
-    e = xmhw::launch_object_genealogy(start, end, slot, cell_of_row, n, row_offsets, C, nbr, K, vox_off, V, time_start, offsets,
-                                      n_slots, L, counts, edges, edge_capacity, n_edges, n_bad, overflow, sp, st);
-    if (e != hipSuccess) return hip_fail(e, "object_genealogy launch");
-    return XMHW_OK;
+    // the hash set and parent, indeg, outdeg of every voxel: this stream's scratch
+    ScratchRef scratch;
+    if (int rc = claim_scratch(st, xmhw::object_genealogy_scratch_bytes(V, edge_capacity), &scratch)) return rc;
+    return status_of(xmhw::launch_object_genealogy(start, end, slot, cell_of_row, n, row_offsets, C, nbr, K, vox_off, V,
+                                                   time_start, offsets, n_slots, L, counts, edges, edge_capacity, n_edges,
+                                                   n_bad, overflow, scratch.get(), st),
+                     "object_genealogy launch");
 }
 
 static_assert(xmhw::kShapeClasses == XMHW_SHAPE_CLASSES && xmhw::kShapeOpen == XMHW_SHAPE_OPEN &&
@@ -1963,11 +1944,10 @@ int xmhw_object_shape(const int32_t* start, const int32_t* end, const int32_t* s
     if (n > 0 && n_slots > 0 && L > 0 &&
         (!start || !end || !slot || !cell_of_row || !row_offsets || !faces || !lq || !time_start || !offsets))
         return fail(XMHW_ERR_INVALID, "NULL buffer");
-    const hipError_t e = xmhw::launch_object_shape(start, end, slot, cell_of_row, n, row_offsets, C, faces, lq, time_start, offsets,
-                                                   n_slots, L, edges, perimeter_q, cells_edge, n_bad,
-                                                   static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "object_shape launch");
-    return XMHW_OK;
+    return status_of(xmhw::launch_object_shape(start, end, slot, cell_of_row, n, row_offsets, C, faces, lq, time_start,
+                                               offsets, n_slots, L, edges, perimeter_q, cells_edge, n_bad,
+                                               static_cast<hipStream_t>(stream)),
+                     "object_shape launch");
 }
 
 int xmhw_set_track_intensity_combine(int32_t on) {
@@ -1981,10 +1961,9 @@ int xmhw_track_intensity_init(int64_t L, int32_t* n_valid, int64_t* wsum_i, int6
     if (L > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "track_intensity: 2^31 series entries and more");
     if (!n_range || !n_bad || (L > 0 && (!n_valid || !wsum_i || !isum_q || !intensity_max || !cat_cells)))
         return fail(XMHW_ERR_INVALID, "NULL output buffer");
-    hipError_t e = xmhw::launch_track_intensity_init(L, n_valid, wsum_i, isum_q, intensity_max, cat_cells, ldcat, n_range, n_bad,
-                                                     static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "track_intensity_init");
-    return XMHW_OK;
+    return status_of(xmhw::launch_track_intensity_init(L, n_valid, wsum_i, isum_q, intensity_max, cat_cells, ldcat, n_range,
+                                                       n_bad, static_cast<hipStream_t>(stream)),
+                     "track_intensity_init");
 }
 int xmhw_track_intensity_accumulate_f32(const float* ts, int64_t T, int64_t n, int64_t ld, const double* seas,
                                         const double* thresh, int64_t ldc, int64_t D, const int32_t* row_of_t, int32_t negate,
@@ -2013,9 +1992,8 @@ int xmhw_track_intensity_finish(int64_t L, double* intensity_max, void* stream) 
     if (L > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "track_intensity: 2^31 series entries and more");
     if (L == 0) return XMHW_OK;
     if (!intensity_max) return fail(XMHW_ERR_INVALID, "NULL output buffer");
-    hipError_t e = xmhw::launch_track_intensity_finish(L, intensity_max, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "track_intensity_finish launch");
-    return XMHW_OK;
+    return status_of(xmhw::launch_track_intensity_finish(L, intensity_max, static_cast<hipStream_t>(stream)),
+                     "track_intensity_finish launch");
 }
 
 int xmhw_set_class_days_block(int32_t steps) {
@@ -2029,9 +2007,9 @@ int xmhw_class_days_init(int32_t K, int64_t C, int32_t* days, int64_t* isum_q, d
     if (C > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "class_days: 2^31 cells and more");
     if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
     if (!n_range || (C > 0 && (!days || !isum_q || !intensity_max))) return fail(XMHW_ERR_INVALID, "NULL output buffer");
-    hipError_t e = xmhw::launch_class_days_init(K, C, days, isum_q, intensity_max, ldo, n_range, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "class_days_init");
-    return XMHW_OK;
+    return status_of(xmhw::launch_class_days_init(K, C, days, isum_q, intensity_max, ldo, n_range,
+                                                  static_cast<hipStream_t>(stream)),
+                     "class_days_init");
 }
 int xmhw_class_days_accumulate_f32(const float* ts, int64_t T, int64_t C, int64_t ld, const double* seas, const double* thresh,
                                    int64_t ldc, const int32_t* row_of_t, int32_t negate, const uint64_t* bits, int64_t ldb,
@@ -2055,9 +2033,8 @@ int xmhw_class_days_finish(int32_t K, int64_t C, double* intensity_max, int64_t 
     if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
     if (C == 0) return XMHW_OK;
     if (!intensity_max) return fail(XMHW_ERR_INVALID, "NULL output buffer");
-    hipError_t e = xmhw::launch_class_days_finish(K, C, intensity_max, ldo, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "class_days_finish launch");
-    return XMHW_OK;
+    return status_of(xmhw::launch_class_days_finish(K, C, intensity_max, ldo, static_cast<hipStream_t>(stream)),
+                     "class_days_finish launch");
 }
 
 int xmhw_event_table_bits(const int32_t* start, const int32_t* end, const int64_t* offsets, const int64_t* cell, int64_t C,
@@ -2066,9 +2043,9 @@ int xmhw_event_table_bits(const int32_t* start, const int32_t* end, const int64_
     if (T < 0 || C < 0 || ldb < C) return fail(XMHW_ERR_INVALID, "bad T/C/ldb");
     if (C == 0 || T == 0) return XMHW_OK;
     if (!offsets || !cell || !bits) return fail(XMHW_ERR_INVALID, "NULL buffer");
-    hipError_t e = xmhw::launch_event_table_bits(start, end, offsets, cell, C, T, bits, ldb, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "event_table_bits launch");
-    return XMHW_OK;
+    return status_of(xmhw::launch_event_table_bits(start, end, offsets, cell, C, T, bits, ldb,
+                                                   static_cast<hipStream_t>(stream)),
+                     "event_table_bits launch");
 }
 int xmhw_set_cooccur_block(int32_t words) {
     if (words < 0) return fail(XMHW_ERR_INVALID, "words must be >= 0");
@@ -2080,9 +2057,7 @@ int xmhw_cooccur_init(int32_t K, int32_t L, int64_t C, int32_t* counts, int64_t 
     if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
     if (C == 0) return XMHW_OK;
     if (!counts) return fail(XMHW_ERR_INVALID, "NULL output buffer");
-    hipError_t e = xmhw::launch_cooccur_init(K, L, C, counts, ldo, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "cooccur_init");
-    return XMHW_OK;
+    return status_of(xmhw::launch_cooccur_init(K, L, C, counts, ldo, static_cast<hipStream_t>(stream)), "cooccur_init");
 }
 int xmhw_cooccur_accumulate(const uint64_t* a_bits, int64_t lda, const uint64_t* b_bits, int64_t ldb, int64_t T, int64_t C,
                             const int32_t* class_of_t, int32_t K, const int32_t* lags, int32_t L, int32_t* counts,
@@ -2090,22 +2065,18 @@ int xmhw_cooccur_accumulate(const uint64_t* a_bits, int64_t lda, const uint64_t*
     if (cooccur_check_shape(K, L, T, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
     if (T < 0 || C < 0 || lda < C || ldb < C || ldo < C) return fail(XMHW_ERR_INVALID, "bad T/C/lda/ldb/ldo");
     if (!lags || (T > 0 && !class_of_t)) return fail(XMHW_ERR_INVALID, "NULL class_of_t or lags");
-    for (int64_t t = 0; t < T; ++t)
-        if (class_of_t[t] < -1 || class_of_t[t] >= K) return fail(XMHW_ERR_INVALID, "class_of_t outside [-1, K)");
+    if (int rc = check_labels(class_of_t, T, -1, K, kClassesOutside)) return rc;
     if (C == 0 || T == 0) return XMHW_OK;
     if (!a_bits || !b_bits || !counts) return fail(XMHW_ERR_INVALID, "NULL buffer");
-    hipError_t e = hipSuccess;
-    const RowsRef classes = cached_rows(class_of_t, T, &e);         // the content-keyed cache of int32 tables
-    if (!classes) return hip_fail(e, "class table upload");
-    e = cooccur_segments(classes, T);
-    if (e != hipSuccess) return hip_fail(e, "segment table upload");
-    const RowsRef lag_table = cached_rows(lags, L, &e);
-    if (!lag_table) return hip_fail(e, "lag table upload");
-    e = xmhw::launch_cooccur_accumulate(a_bits, lda, b_bits, ldb, T, C, classes->seg_off, classes->seg_class, classes->seg_mask,
-                                        lag_table->d_rows, L, g_cooccur_block.load(), counts, ldo,
-                                        static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "cooccur_accumulate launch");
-    return XMHW_OK;
+    RowsRef classes;                                   // the content-keyed cache of int32 tables
+    if (int rc = upload_table(class_of_t, T, "class table upload", &classes)) return rc;
+    if (int rc = status_of(cooccur_segments(classes, T), "segment table upload")) return rc;
+    RowsRef lag_table;
+    if (int rc = upload_table(lags, L, "lag table upload", &lag_table)) return rc;
+    return status_of(xmhw::launch_cooccur_accumulate(a_bits, lda, b_bits, ldb, T, C, classes->seg_off, classes->seg_class,
+                                                     classes->seg_mask, lag_table->d_rows, L, g_cooccur_block.load(), counts,
+                                                     ldo, static_cast<hipStream_t>(stream)),
+                     "cooccur_accumulate launch");
 }
 
 int xmhw_set_displacement_block(int32_t steps) {
@@ -2119,50 +2090,57 @@ int xmhw_displacement_init(int32_t K, int64_t C, int32_t* n_days, int32_t* n_fou
     if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
     if (!n_visited || (C > 0 && (!n_days || !n_found || !sum_m || !sum_north_m || !sum_east_m || !max_m)))
         return fail(XMHW_ERR_INVALID, "NULL output buffer");
-    hipError_t e = xmhw::launch_displacement_init(K, C, n_days, n_found, sum_m, sum_north_m, sum_east_m, max_m, ldo, n_visited,
-                                                  static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "displacement_init");
-    return XMHW_OK;
+    return status_of(xmhw::launch_displacement_init(K, C, n_days, n_found, sum_m, sum_north_m, sum_east_m, max_m, ldo,
+                                                    n_visited, static_cast<hipStream_t>(stream)),
+                     "displacement_init");
 }
-#define XMHW_DISPLACEMENT_ENTRY(NAME, T)                                                                                 \
-    int NAME(const T* ts, int64_t ld, int64_t t0, int64_t nt, int64_t Tn, int32_t ny, int32_t nx, int32_t periodic,      \
-             const double* seas, int64_t ldc, int64_t D, const int32_t* row_of_t, int32_t negate, const uint64_t* bits,  \
-             int64_t ldb, const int32_t* cell_of_point, int64_t C, const int32_t* basin, const int64_t* list_off,        \
-             const int32_t* djdi, const int32_t* dist_m, const int32_t* north_m, const int32_t* east_m, int64_t n_entries, \
-             const int32_t* class_of_t, int32_t K, int32_t* n_days, int32_t* n_found, int64_t* sum_m,                    \
-             int64_t* sum_north_m, int64_t* sum_east_m, int32_t* max_m, int64_t ldo, int64_t* n_visited, void* stream) { \
-        return displacement_accumulate<T>(ts, ld, t0, nt, Tn, ny, nx, periodic, seas, ldc, D, row_of_t, negate, bits, ldb, \
-                                          cell_of_point, C, basin, list_off, djdi, dist_m, north_m, east_m, n_entries,   \
-                                          class_of_t, K, n_days, n_found, sum_m, sum_north_m, sum_east_m, max_m, ldo,    \
-                                          n_visited, stream);                                                            \
-    }
-XMHW_DISPLACEMENT_ENTRY(xmhw_displacement_accumulate_f32, float)
-XMHW_DISPLACEMENT_ENTRY(xmhw_displacement_accumulate_f64, double)
-#undef XMHW_DISPLACEMENT_ENTRY
+int xmhw_displacement_accumulate_f32(const float* ts, int64_t ld, int64_t t0, int64_t nt, int64_t T, int32_t ny, int32_t nx,
+                                     int32_t periodic, const double* seas, int64_t ldc, int64_t D, const int32_t* row_of_t,
+                                     int32_t negate, const uint64_t* bits, int64_t ldb, const int32_t* cell_of_point,
+                                     int64_t C, const int32_t* basin, const int64_t* list_off, const int32_t* djdi,
+                                     const int32_t* dist_m, const int32_t* north_m, const int32_t* east_m, int64_t n_entries,
+                                     const int32_t* class_of_t, int32_t K, int32_t* n_days, int32_t* n_found, int64_t* sum_m,
+                                     int64_t* sum_north_m, int64_t* sum_east_m, int32_t* max_m, int64_t ldo,
+                                     int64_t* n_visited, void* stream) {
+    return displacement_accumulate<float>(ts, ld, t0, nt, T, ny, nx, periodic, seas, ldc, D, row_of_t, negate, bits, ldb,
+                                          cell_of_point, C, basin, list_off, djdi, dist_m, north_m, east_m, n_entries,
+                                          class_of_t, K, n_days, n_found, sum_m, sum_north_m, sum_east_m, max_m, ldo,
+                                          n_visited, stream);
+}
+int xmhw_displacement_accumulate_f64(const double* ts, int64_t ld, int64_t t0, int64_t nt, int64_t T, int32_t ny, int32_t nx,
+                                     int32_t periodic, const double* seas, int64_t ldc, int64_t D, const int32_t* row_of_t,
+                                     int32_t negate, const uint64_t* bits, int64_t ldb, const int32_t* cell_of_point,
+                                     int64_t C, const int32_t* basin, const int64_t* list_off, const int32_t* djdi,
+                                     const int32_t* dist_m, const int32_t* north_m, const int32_t* east_m, int64_t n_entries,
+                                     const int32_t* class_of_t, int32_t K, int32_t* n_days, int32_t* n_found, int64_t* sum_m,
+                                     int64_t* sum_north_m, int64_t* sum_east_m, int32_t* max_m, int64_t ldo,
+                                     int64_t* n_visited, void* stream) {
+    return displacement_accumulate<double>(ts, ld, t0, nt, T, ny, nx, periodic, seas, ldc, D, row_of_t, negate, bits, ldb,
+                                           cell_of_point, C, basin, list_off, djdi, dist_m, north_m, east_m, n_entries,
+                                           class_of_t, K, n_days, n_found, sum_m, sum_north_m, sum_east_m, max_m, ldo,
+                                           n_visited, stream);
+}
 
 int xmhw_synth_sst_f32(float* ts, int64_t T, int64_t C, int64_t ld, int64_t cell0, uint64_t seed,
                        double nan_frac, void* stream) {
     if (C < 0 || ld < C || T <= 0) return fail(XMHW_ERR_INVALID, "bad T/C/ld");
-    hipError_t e = xmhw::launch_synth<float>(ts, T, C, ld, cell0, seed, nan_frac, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "synth launch");
-    return XMHW_OK;
+    return status_of(xmhw::launch_synth<float>(ts, T, C, ld, cell0, seed, nan_frac, static_cast<hipStream_t>(stream)),
+                     "synth launch");
 }
 int xmhw_synth_sst_ex_f32(float* ts, int64_t T, int64_t C, int64_t ld, int64_t cell0, uint64_t seed, double nan_frac,
                           double quant, double ice_frac, double rho, int64_t ice_patch, void* stream) {
     if (!ts || T < 0 || C < 0 || ld < C) return fail(XMHW_ERR_INVALID, "bad argument");
     if (!(rho >= 0.0 && rho < 1.0) || quant < 0.0 || ice_frac < 0.0 || ice_frac > 1.0)
         return fail(XMHW_ERR_INVALID, "rho must be in [0, 1), quant >= 0, ice_frac in [0, 1]");
-    hipError_t e = xmhw::launch_synth_ex<float>(ts, T, C, ld, cell0, seed, nan_frac, quant, ice_frac, rho, ice_patch,
-                                                static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "synth launch");
-    return XMHW_OK;
+    return status_of(xmhw::launch_synth_ex<float>(ts, T, C, ld, cell0, seed, nan_frac, quant, ice_frac, rho, ice_patch,
+                                                  static_cast<hipStream_t>(stream)),
+                     "synth launch");
 }
 int xmhw_synth_sst_f64(double* ts, int64_t T, int64_t C, int64_t ld, int64_t cell0, uint64_t seed,
                        double nan_frac, void* stream) {
     if (C < 0 || ld < C || T <= 0) return fail(XMHW_ERR_INVALID, "bad T/C/ld");
-    hipError_t e = xmhw::launch_synth<double>(ts, T, C, ld, cell0, seed, nan_frac, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return hip_fail(e, "synth launch");
-    return XMHW_OK;
+    return status_of(xmhw::launch_synth<double>(ts, T, C, ld, cell0, seed, nan_frac, static_cast<hipStream_t>(stream)),
+                     "synth launch");
 }
 
 }  // extern "C"
