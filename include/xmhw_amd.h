@@ -1058,6 +1058,91 @@ int xmhw_displacement_accumulate_f64(const double *ts_dev, int64_t ld, int64_t t
                                      int64_t *sum_m_dev, int64_t *sum_north_m_dev, int64_t *sum_east_m_dev,
                                      int32_t *max_m_dev, int64_t ldo, int64_t *n_visited_dev, void *stream);
 
+/* ---- heat_stress(): accumulated thermal stress (degree heating weeks) and the class sums of the series ---- *
+ * The Degree Heating Week of NOAA Coral Reef Watch (Liu et al. 2014; Skirving et al. 2020): how much heat has piled up
+ * in a cell over the last W steps.  The first stage with a window along time; one streaming pass over the series, and a
+ * second, smaller one for its baseline, the Maximum Monthly Mean, which is made of per-class sums of the plain series.
+ *
+ * CLASS SUMS.  class_of_t_host[T]: one int32 label per step in [-1, K); -1 = the step counts nowhere.  For every class
+ * k and cell c, over the steps of class k, with d = float64(sample) - x0:
+ *   n_valid[k][c]         int32    steps whose d is not NaN and |d| < 2^7
+ *   sum_q[k][c]           int64    sum of rint(d * 2^XMHW_HEAT_STRESS_BITS) over those steps
+ * Any other non-NaN d (|d| >= 2^7 or infinite) is left out and counted in *n_range_dev (int64).  The class mean is
+ * x0 + sum_q / n_valid / 2^16; |sum_q| < 2^31 * 2^23: int64 cannot overflow.
+ *
+ * HEAT STRESS.  base_dev is float64 [D][ldb] with row_of_t_host[T] in [0, D): D = 1 is a constant per cell (the MMM),
+ * D = 366 a climatology of threshold().  With x = the sample as float64 and b = base[row_of_t[t]][c], both negated when
+ * negate != 0, and h = x - b:
+ *   the step is HOT iff h == h, h >= h0 and h < 2^7             (2^-16 <= h0 < 2^7)
+ *   q(t) = int64(rint(h * 2^16)) on hot steps, 0 otherwise
+ *   S(t) = the sum of q(i) over max(0, t - W + 1) <= i <= t     (1 <= W <= 255: S < 2^31)
+ * A step with h >= 2^7 or infinite is not hot and is counted in *n_range_dev, whatever its class (0 for a series in the
+ * units of its baseline).  A step of class -1 feeds the window of later steps but is reduced nowhere.  For every class
+ * k and cell c, over the steps t with class_of_t[t] == k:
+ *   counts[k][0][c]       int32    steps with h not NaN
+ *   counts[k][1][c]       int32    hot steps
+ *   counts[k][2 + l][c]   int32    steps with S(t) >= level_q_host[l], l < L (int64, strictly ascending); the channels
+ *                                  2 + L .. XMHW_HEAT_STRESS_CHANNELS - 1 stay 0
+ *   hsum_q[k][c]          int64    sum of q(t): the degree heating days of the class
+ *   peak_q[k][c]          int32    max S(t)
+ *   peak_t[k][c]          int32    the smallest t that attains peak_q
+ * and, whatever the class of the step, for the J snapshot steps at_host[j] (strictly ascending, in [0, T)):
+ *   snap_q[j][c]          int32    S(at[j])
+ * A class without steps gives peak_q = 0 and peak_t = -1.  The peak is an order-independent 64-bit integer maximum of
+ * the key S << 32 | ~t (low word), kept in peak_key_dev (int64 [K][ldo], 0 = no step yet).  Units: level_q =
+ * rint(level * unit * 2^16) and DHW = S / (unit * 2^16); Coral Reef Watch's product is W = 84 daily steps, h0 = 1.0,
+ * unit = 7, levels 4 and 8.  Everything is an integer sum or an integer maximum: the result is exact and does not depend
+ * on the time blocks, the slabs, the launch geometry or the schedule.  Cells are the fastest axis of every output:
+ * counts_dev is int32 [K][XMHW_HEAT_STRESS_CHANNELS][ldo], snap_q_dev int32 [J][ldo], the others [K][ldo], ldo >= C;
+ * columns past C are never touched, and a slab addresses its columns by pointer offset, as in xmhw_class_days_*.
+ *
+ *  1. xmhw_class_sums_init / xmhw_heat_stress_init zero columns 0..C-1 of the accumulators and the counter.
+ *  2. xmhw_class_sums_accumulate_* / xmhw_heat_stress_accumulate_* handle one slab of C cells and ADDS into the
+ *     accumulators; the snapshots are plain stores.  Lane = cell, workgroup = 256 cells x a block of steps; a lane keeps
+ *     the addends of the current class in registers and issues integer atomics without a return value when the class
+ *     changes and at the end of its block.  A block that starts at t0 > 0 first rebuilds the window from the steps
+ *     t0 - W + 1 .. t0 - 1; the step that leaves the window is re-derived from its sample (csrc/kernels_stress.hip).
+ *  3. xmhw_heat_stress_finish splits the keys into peak_q_dev and peak_t_dev.
+ * All are asynchronous on `stream`.  Refusals, in this order and before the first HIP call: K < 1 or
+ * K > XMHW_HEAT_STRESS_MAX_CLASSES, W outside [1, XMHW_HEAT_STRESS_MAX_WINDOW], L > XMHW_HEAT_STRESS_MAX_LEVELS,
+ * J > XMHW_HEAT_STRESS_MAX_SNAPSHOTS, T or C of 2^31 and more: XMHW_ERR_UNSUPPORTED.  A bad T, C, D, L, J or leading
+ * dimension, h0 outside [2^-16, 2^7) (or NaN; x0 not finite for the class sums), a NULL host table, a label outside
+ * [-1, K), a row outside [0, D), levels not strictly ascending, snapshot steps not strictly ascending or outside
+ * [0, T): XMHW_ERR_INVALID.  Then nothing is launched for C == 0; then a NULL device buffer is XMHW_ERR_INVALID.
+ * xmhw_set_heat_stress_block (process-wide; tests and measurements): the steps a workgroup of either accumulate kernel
+ * takes per block, 0 = automatic.  Same results for every value.                                                      */
+#define XMHW_HEAT_STRESS_MAX_CLASSES   1024
+#define XMHW_HEAT_STRESS_CHANNELS      8
+#define XMHW_HEAT_STRESS_MAX_LEVELS    6
+#define XMHW_HEAT_STRESS_MAX_SNAPSHOTS 64
+#define XMHW_HEAT_STRESS_MAX_WINDOW    255
+#define XMHW_HEAT_STRESS_BITS          16
+int xmhw_set_heat_stress_block(int32_t steps);        /* tests and measurements; 0 = automatic */
+int xmhw_class_sums_init(int32_t K, int64_t C, int32_t *n_valid_dev, int64_t *sum_q_dev, int64_t ldo,
+                         int64_t *n_range_dev, void *stream);
+int xmhw_class_sums_accumulate_f32(const float *ts_dev, int64_t T, int64_t C, int64_t ld, double x0,
+                                   const int32_t *class_of_t_host, int32_t K, int32_t *n_valid_dev, int64_t *sum_q_dev,
+                                   int64_t ldo, int64_t *n_range_dev, void *stream);
+int xmhw_class_sums_accumulate_f64(const double *ts_dev, int64_t T, int64_t C, int64_t ld, double x0,
+                                   const int32_t *class_of_t_host, int32_t K, int32_t *n_valid_dev, int64_t *sum_q_dev,
+                                   int64_t ldo, int64_t *n_range_dev, void *stream);
+int xmhw_heat_stress_init(int32_t K, int64_t C, int32_t *counts_dev, int64_t *hsum_q_dev, int64_t *peak_key_dev,
+                          int64_t ldo, int64_t *n_range_dev, void *stream);
+int xmhw_heat_stress_accumulate_f32(const float *ts_dev, int64_t T, int64_t C, int64_t ld, const double *base_dev,
+                                    int64_t ldb, int64_t D, const int32_t *row_of_t_host, int32_t negate, int32_t W,
+                                    double h0, const int32_t *class_of_t_host, int32_t K, const int64_t *level_q_host,
+                                    int32_t L, const int32_t *at_host, int32_t J, int32_t *counts_dev,
+                                    int64_t *hsum_q_dev, int64_t *peak_key_dev, int32_t *snap_q_dev, int64_t ldo,
+                                    int64_t *n_range_dev, void *stream);
+int xmhw_heat_stress_accumulate_f64(const double *ts_dev, int64_t T, int64_t C, int64_t ld, const double *base_dev,
+                                    int64_t ldb, int64_t D, const int32_t *row_of_t_host, int32_t negate, int32_t W,
+                                    double h0, const int32_t *class_of_t_host, int32_t K, const int64_t *level_q_host,
+                                    int32_t L, const int32_t *at_host, int32_t J, int32_t *counts_dev,
+                                    int64_t *hsum_q_dev, int64_t *peak_key_dev, int32_t *snap_q_dev, int64_t ldo,
+                                    int64_t *n_range_dev, void *stream);
+int xmhw_heat_stress_finish(int32_t K, int64_t C, const int64_t *peak_key_dev, int32_t *peak_q_dev, int32_t *peak_t_dev,
+                            int64_t ldo, void *stream);
+
 /* ---- the sharded path: cells split across the GPUs of a node, ONE gather at the end ------- *
  * Replaces the reference's collect, dask.compute(climls) + xr.concat(dim='cell')
  * (xmhw/xmhw.py:197, :210-211).  Cells are independent (xmhw/xmhw.py:184-196), so rank r runs the

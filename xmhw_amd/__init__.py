@@ -26,6 +26,7 @@ from .region_series import region_series, RegionSeriesDataset
 from .days_by import mhw_days_by, ClassDaysDataset, classes_from_events
 from .cooccurrence import mhw_cooccurrence, CooccurrenceDataset
 from .displacement import mhw_displacement, displacement_offsets, DisplacementDataset, DisplacementTable
+from .heat_stress import heat_stress, maximum_monthly_mean, degree_heating_weeks, HeatStressDataset, MonthlyMeanDataset
 from .ingest import open_series, threshold_file
 from .detrend import detrend, DetrendSpec, FitDataset
 
@@ -36,6 +37,7 @@ __all__ = ["threshold", "threshold_array", "GridSeries", "ClimDataset", "XmhwExc
            "TrackIntensityDataset", "mhw_track_parts", "TrackPartsDataset", "mhw_track_genealogy", "TrackGenealogyDataset",
            "mhw_track_shape", "TrackShapeDataset", "compactness", "region_series", "RegionSeriesDataset", "mhw_days_by", "ClassDaysDataset",
            "classes_from_events", "mhw_cooccurrence", "CooccurrenceDataset", "mhw_displacement", "displacement_offsets",
-           "DisplacementDataset", "DisplacementTable", "open_series",
+           "DisplacementDataset", "DisplacementTable", "heat_stress", "maximum_monthly_mean", "degree_heating_weeks",
+           "HeatStressDataset", "MonthlyMeanDataset", "open_series",
            "threshold_file", "detrend", "DetrendSpec", "FitDataset"]
 __version__ = "0.1.0"

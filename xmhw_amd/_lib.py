@@ -5,6 +5,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _mod = None
+_stress = None
 _err = None
 
 
@@ -26,6 +27,19 @@ def hip():
     except ImportError as e:  # pragma: no cover - build problem
         raise HipExtensionMissing(f"cannot import xmhw_amd._xmhw_hip: {e}") from e
     return _mod
+
+
+def hip_stress():
+    """Return the pybind11 module ``xmhw_amd._xmhw_hip_stress`` (the bindings of heat_stress(); DESIGN.md, "Entry
+    layer") behind the same out-of-memory retry, or raise.  It raises the exception classes of ``_xmhw_hip``."""
+    global _stress
+    if _stress is None:
+        hip()
+        try:
+            _stress = _RetryOnNoMem(importlib.import_module("xmhw_amd._xmhw_hip_stress"))
+        except ImportError as e:  # pragma: no cover - build problem
+            raise HipExtensionMissing(f"cannot import xmhw_amd._xmhw_hip_stress: {e}") from e
+    return _stress
 
 
 class _RetryOnNoMem:

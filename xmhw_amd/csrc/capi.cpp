@@ -881,6 +881,76 @@ int displacement_accumulate(const T* ts, int64_t ld, int64_t t0, int64_t nt, int
                      "displacement_accumulate launch");
 }
 
+static std::atomic<int> g_heat_stress_block{0};   // steps a workgroup takes per block, 0 = automatic (xmhw_set_heat_stress_block)
+
+static int heat_stress_check_shape(const char* who, int32_t K, int64_t Tn, int64_t C) {
+    if (K < 1 || K > xmhw::kHeatStressMaxClasses)
+        return fail(XMHW_ERR_UNSUPPORTED,
+                    std::string(who) + ": K must be in [1, " + std::to_string(xmhw::kHeatStressMaxClasses) + "]");
+    if (Tn > 0x7FFFFFFFll || C > 0x7FFFFFFFll)
+        return fail(XMHW_ERR_UNSUPPORTED, std::string(who) + ": 2^31 steps or cells and more");
+    return XMHW_OK;
+}
+
+template <typename T>
+int class_sums_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, double x0, const int32_t* class_of_t, int32_t K,
+                          int32_t* n_valid, int64_t* sum_q, int64_t ldo, int64_t* n_range, void* stream) {
+    if (heat_stress_check_shape("class_sums", K, Tn, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (Tn <= 0 || C < 0 || ld < C || ldo < C) return fail(XMHW_ERR_INVALID, "bad T/C/ld/ldo");
+    if (!std::isfinite(x0)) return fail(XMHW_ERR_INVALID, "x0 must be finite");
+    if (!class_of_t) return fail(XMHW_ERR_INVALID, "NULL class_of_t");
+    if (int rc = check_labels(class_of_t, Tn, -1, K, kClassesOutside)) return rc;
+    if (C == 0) return XMHW_OK;
+    if (!ts || !n_valid || !sum_q || !n_range) return fail(XMHW_ERR_INVALID, "NULL buffer");
+    RowsRef classes;
+    if (int rc = upload_table(class_of_t, Tn, "class table upload", &classes)) return rc;
+    return status_of(xmhw::launch_class_sums_accumulate<T>(ts, Tn, C, ld, x0, classes->d_rows, K, g_heat_stress_block.load(),
+                                                           n_valid, sum_q, ldo, n_range, static_cast<hipStream_t>(stream)),
+                     "class_sums_accumulate launch");
+}
+
+template <typename T>
+int heat_stress_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* base, int64_t ldb, int64_t D,
+                           const int32_t* row_of_t, int32_t negate, int32_t W, double h0, const int32_t* class_of_t,
+                           int32_t K, const int64_t* level_q, int32_t L, const int32_t* at, int32_t J, int32_t* counts,
+                           int64_t* hsum_q, int64_t* peak_key, int32_t* snap_q, int64_t ldo, int64_t* n_range,
+                           void* stream) {
+    if (heat_stress_check_shape("heat_stress", K, Tn, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (W < 1 || W > xmhw::kHeatStressMaxWindow)
+        return fail(XMHW_ERR_UNSUPPORTED, "heat_stress: W must be in [1, " + std::to_string(xmhw::kHeatStressMaxWindow) + "]");
+    if (L > xmhw::kHeatStressMaxLevels)
+        return fail(XMHW_ERR_UNSUPPORTED, "heat_stress: at most " + std::to_string(xmhw::kHeatStressMaxLevels) + " levels");
+    if (J > xmhw::kHeatStressMaxSnapshots)
+        return fail(XMHW_ERR_UNSUPPORTED,
+                    "heat_stress: at most " + std::to_string(xmhw::kHeatStressMaxSnapshots) + " snapshot steps");
+    if (Tn <= 0 || C < 0 || ld < C || ldb < C || ldo < C || D < 1 || L < 0 || J < 0)
+        return fail(XMHW_ERR_INVALID, "bad T/C/ld/ldb/ldo/D/L/J");
+    if (!(h0 >= 1.0 / 65536.0 && h0 < 128.0)) return fail(XMHW_ERR_INVALID, "h0 outside [2^-16, 2^7)");
+    if (!class_of_t || !row_of_t || (L > 0 && !level_q) || (J > 0 && !at)) return fail(XMHW_ERR_INVALID, "NULL host table");
+    if (int rc = check_labels(class_of_t, Tn, -1, K, kClassesOutside)) return rc;
+    if (int rc = check_labels(row_of_t, Tn, 0, D, kRowsOutside)) return rc;
+    for (int32_t l = 1; l < L; ++l)
+        if (level_q[l] <= level_q[l - 1]) return fail(XMHW_ERR_INVALID, "level_q not strictly ascending");
+    for (int32_t j = 0; j < J; ++j)
+        if (at[j] < 0 || at[j] >= Tn || (j > 0 && at[j] <= at[j - 1]))
+            return fail(XMHW_ERR_INVALID, "snapshot steps not strictly ascending in [0, T)");
+    if (C == 0) return XMHW_OK;
+    if (!ts || !base || !counts || !hsum_q || !peak_key || !n_range || (J > 0 && !snap_q))
+        return fail(XMHW_ERR_INVALID, "NULL buffer");
+    RowsRef rows;
+    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
+    RowsRef classes;                                   // the same content-keyed cache: one more int32[T] table
+    if (int rc = upload_table(class_of_t, Tn, "class table upload", &classes)) return rc;
+    RowsRef steps;                                     // ... and the snapshot steps, int32[J]
+    if (J > 0)
+        if (int rc = upload_table(at, J, "snapshot table upload", &steps)) return rc;
+    return status_of(xmhw::launch_heat_stress_accumulate<T>(ts, Tn, C, ld, base, ldb, D, rows->d_rows, negate, W, h0,
+                                                            classes->d_rows, K, level_q, L, J > 0 ? steps->d_rows : nullptr, J,
+                                                            g_heat_stress_block.load(), counts, hsum_q, peak_key, snap_q, ldo,
+                                                            n_range, static_cast<hipStream_t>(stream)),
+                     "heat_stress_accumulate launch");
+}
+
 template <typename T>
 int event_stats_sparse(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* seas, const double* thresh,
                        int64_t ldc, const int32_t* row_of_t, int32_t negate, int64_t n_events, double* table,
@@ -2119,6 +2189,61 @@ int xmhw_displacement_accumulate_f64(const double* ts, int64_t ld, int64_t t0, i
                                            cell_of_point, C, basin, list_off, djdi, dist_m, north_m, east_m, n_entries,
                                            class_of_t, K, n_days, n_found, sum_m, sum_north_m, sum_east_m, max_m, ldo,
                                            n_visited, stream);
+}
+
+int xmhw_set_heat_stress_block(int32_t steps) {
+    if (steps < 0) return fail(XMHW_ERR_INVALID, "steps must be >= 0");
+    g_heat_stress_block = steps;
+    return XMHW_OK;
+}
+int xmhw_class_sums_init(int32_t K, int64_t C, int32_t* n_valid, int64_t* sum_q, int64_t ldo, int64_t* n_range, void* stream) {
+    if (heat_stress_check_shape("class_sums", K, 1, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
+    if (!n_range || (C > 0 && (!n_valid || !sum_q))) return fail(XMHW_ERR_INVALID, "NULL output buffer");
+    return status_of(xmhw::launch_class_sums_init(K, C, n_valid, sum_q, ldo, n_range, static_cast<hipStream_t>(stream)),
+                     "class_sums_init");
+}
+int xmhw_class_sums_accumulate_f32(const float* ts, int64_t T, int64_t C, int64_t ld, double x0, const int32_t* class_of_t,
+                                   int32_t K, int32_t* n_valid, int64_t* sum_q, int64_t ldo, int64_t* n_range, void* stream) {
+    return class_sums_accumulate<float>(ts, T, C, ld, x0, class_of_t, K, n_valid, sum_q, ldo, n_range, stream);
+}
+int xmhw_class_sums_accumulate_f64(const double* ts, int64_t T, int64_t C, int64_t ld, double x0, const int32_t* class_of_t,
+                                   int32_t K, int32_t* n_valid, int64_t* sum_q, int64_t ldo, int64_t* n_range, void* stream) {
+    return class_sums_accumulate<double>(ts, T, C, ld, x0, class_of_t, K, n_valid, sum_q, ldo, n_range, stream);
+}
+int xmhw_heat_stress_init(int32_t K, int64_t C, int32_t* counts, int64_t* hsum_q, int64_t* peak_key, int64_t ldo,
+                          int64_t* n_range, void* stream) {
+    if (heat_stress_check_shape("heat_stress", K, 1, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
+    if (!n_range || (C > 0 && (!counts || !hsum_q || !peak_key))) return fail(XMHW_ERR_INVALID, "NULL output buffer");
+    return status_of(xmhw::launch_heat_stress_init(K, C, counts, hsum_q, peak_key, ldo, n_range,
+                                                   static_cast<hipStream_t>(stream)),
+                     "heat_stress_init");
+}
+int xmhw_heat_stress_accumulate_f32(const float* ts, int64_t T, int64_t C, int64_t ld, const double* base, int64_t ldb,
+                                    int64_t D, const int32_t* row_of_t, int32_t negate, int32_t W, double h0,
+                                    const int32_t* class_of_t, int32_t K, const int64_t* level_q, int32_t L, const int32_t* at,
+                                    int32_t J, int32_t* counts, int64_t* hsum_q, int64_t* peak_key, int32_t* snap_q,
+                                    int64_t ldo, int64_t* n_range, void* stream) {
+    return heat_stress_accumulate<float>(ts, T, C, ld, base, ldb, D, row_of_t, negate, W, h0, class_of_t, K, level_q, L, at, J,
+                                         counts, hsum_q, peak_key, snap_q, ldo, n_range, stream);
+}
+int xmhw_heat_stress_accumulate_f64(const double* ts, int64_t T, int64_t C, int64_t ld, const double* base, int64_t ldb,
+                                    int64_t D, const int32_t* row_of_t, int32_t negate, int32_t W, double h0,
+                                    const int32_t* class_of_t, int32_t K, const int64_t* level_q, int32_t L, const int32_t* at,
+                                    int32_t J, int32_t* counts, int64_t* hsum_q, int64_t* peak_key, int32_t* snap_q,
+                                    int64_t ldo, int64_t* n_range, void* stream) {
+    return heat_stress_accumulate<double>(ts, T, C, ld, base, ldb, D, row_of_t, negate, W, h0, class_of_t, K, level_q, L, at, J,
+                                          counts, hsum_q, peak_key, snap_q, ldo, n_range, stream);
+}
+int xmhw_heat_stress_finish(int32_t K, int64_t C, const int64_t* peak_key, int32_t* peak_q, int32_t* peak_t, int64_t ldo,
+                            void* stream) {
+    if (heat_stress_check_shape("heat_stress", K, 1, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
+    if (C == 0) return XMHW_OK;
+    if (!peak_key || !peak_q || !peak_t) return fail(XMHW_ERR_INVALID, "NULL buffer");
+    return status_of(xmhw::launch_heat_stress_finish(K, C, peak_key, peak_q, peak_t, ldo, static_cast<hipStream_t>(stream)),
+                     "heat_stress_finish launch");
 }
 
 int xmhw_synth_sst_f32(float* ts, int64_t T, int64_t C, int64_t ld, int64_t cell0, uint64_t seed,

@@ -452,6 +452,40 @@ hipError_t launch_displacement_accumulate(const T* ts, int64_t ld, int64_t t0, i
                                           int64_t* sum_east_m, int32_t* max_m, int64_t ldo, int64_t* n_visited,
                                           hipStream_t stream);
 
+// heat_stress() (kernels_stress.hip): accumulated thermal stress and the class sums of the plain series.
+// launch_class_sums_accumulate ADDS, per class k of the step and cell c, the steps with d = sample - x0 not NaN and
+// |d| < 2^7 to n_valid[k][c] and rint(d * 2^kHeatStressBits) to sum_q[k][c]; other non-NaN d are counted in *n_range.
+// launch_heat_stress_accumulate forms q(t) = rint(h * 2^kHeatStressBits) on the hot steps (h = sample - base[row_of_t[t]],
+// both negated under `negate`, h0 <= h < 2^7) and S(t) = the sum of q over the W steps that end at t, and ADDS per class
+// and cell: counts[k][0][c] steps with h not NaN, [1] hot steps, [2 + l] steps with S >= level_q[l]; hsum_q[k][c] the sum
+// of q; raises peak_key[k][c] to S << 32 | ~t; stores S(at[j]) to snap_q[j][c]; counts the steps with h >= 2^7 or infinite
+// in *n_range.  launch_heat_stress_finish splits the keys into peak_q and peak_t (0 and -1 for a class without steps).
+// Cells are the fastest axis, leading dimension ldo >= C.  row_of_t, class_of_t and at are DEVICE arrays, level_q a HOST
+// array here.  block_steps: the steps a workgroup takes per block, 0 = automatic; same results for every value.
+constexpr int kHeatStressMaxClasses = 1024;
+constexpr int kHeatStressChannels = 8;
+constexpr int kHeatStressMaxLevels = 6;
+constexpr int kHeatStressMaxSnapshots = 64;
+constexpr int kHeatStressMaxWindow = 255;
+constexpr int kHeatStressBits = 16;
+hipError_t launch_class_sums_init(int32_t K, int64_t C, int32_t* n_valid, int64_t* sum_q, int64_t ldo, int64_t* n_range,
+                                  hipStream_t stream);
+template <typename T>
+hipError_t launch_class_sums_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, double x0, const int32_t* class_of_t,
+                                        int32_t K, int64_t block_steps, int32_t* n_valid, int64_t* sum_q, int64_t ldo,
+                                        int64_t* n_range, hipStream_t stream);
+hipError_t launch_heat_stress_init(int32_t K, int64_t C, int32_t* counts, int64_t* hsum_q, int64_t* peak_key, int64_t ldo,
+                                   int64_t* n_range, hipStream_t stream);
+template <typename T>
+hipError_t launch_heat_stress_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* base, int64_t ldb,
+                                         int64_t D, const int32_t* row_of_t, int32_t negate, int32_t W, double h0,
+                                         const int32_t* class_of_t, int32_t K, const int64_t* level_q, int32_t L,
+                                         const int32_t* at, int32_t J, int64_t block_steps, int32_t* counts, int64_t* hsum_q,
+                                         int64_t* peak_key, int32_t* snap_q, int64_t ldo, int64_t* n_range,
+                                         hipStream_t stream);
+hipError_t launch_heat_stress_finish(int32_t K, int64_t C, const int64_t* peak_key, int32_t* peak_q, int32_t* peak_t,
+                                     int64_t ldo, hipStream_t stream);
+
 // file bytes -> samples (kernels_ingest.hip): raw_type = item size of the stored type (2 int16, 4 float32,
 // 8 float64), swap = the file is big-endian, optional scale/offset (CF packing) and fill value -> NaN
 hipError_t launch_encode_i16(const float* in, int64_t rows, int64_t cols, int64_t ld_in, int16_t* out, int64_t ld_out,
