@@ -32,7 +32,7 @@ from ._lib import hip
 from .days_by import class_labels
 from .device import DeviceScope, as_xmhw_errors, device_budget_bytes
 from .exception import XmhwException
-from .series_stage import cells_to_grid, check_class_ids, dense_ids, grid_frame
+from .series_stage import CellFrame, check_class_ids, dense_ids
 
 MAX_CLASSES = 1024              # XMHW_COOCCUR_MAX_CLASSES (include/xmhw_amd.h)
 MAX_LAGS = 64                   # XMHW_COOCCUR_MAX_LAGS
@@ -270,13 +270,8 @@ def mhw_cooccurrence(a, b, classes="all", lags=(0,), max_batch_bytes=None, _comp
     klass = found if found.shape[0] else np.zeros(1, dtype=np.int64)
     attrs = {"classes": classes if isinstance(classes, str) else "array",
              "xmhw_parameters_a": a.attrs.get("xmhw_parameters", ""), "xmhw_parameters_b": b.attrs.get("xmhw_parameters", "")}
-    if a.point:
-        return CooccurrenceDataset(klass, lags, n_pairs, *(counts[:, :, j, 0] for j in range(CHANNELS)), np.array(True), (), {},
-                                   attrs)
-    sshape = tuple(a.sshape)
-    N = int(np.prod(sshape))
-    keep = np.zeros(N, dtype=bool)
+    keep = np.zeros(1 if a.point else int(np.prod(tuple(a.sshape))), dtype=bool)
     keep[common] = True
-    alive, out_coords, keep_grid = grid_frame(keep, a.sdims, sshape, a.coords)
-    return CooccurrenceDataset(klass, lags, n_pairs, *(cells_to_grid(counts[:, :, j], common, N, sshape, alive, 0, np.int32)
-                                                       for j in range(CHANNELS)), keep_grid, a.sdims, out_coords, attrs)
+    f = CellFrame(keep, common, a.point, a.sdims, a.sshape, a.coords)
+    return CooccurrenceDataset(klass, lags, n_pairs, *(f.place(counts[:, :, j], 0, np.int32) for j in range(CHANNELS)), f.keep,
+                               f.sdims, f.coords, attrs)

@@ -384,6 +384,17 @@ hipError_t launch_track_intensity_accumulate(const T* ts, int64_t Tn, int64_t n,
                                              int32_t combine_runs, hipStream_t stream);
 hipError_t launch_track_intensity_finish(int64_t L, double* intensity_max, hipStream_t stream);
 
+// The frame of a class reduction: the kernels below that reduce over TIME and keep the cell (class_days_accumulate,
+// class_sums_accumulate, heat_stress_accumulate; displacement_accumulate with a grid point and cooccur_accumulate with
+// 64-step words in the place of the cell and the step).  Lane = cell, consecutive lanes on consecutive cells; a workgroup
+// is 256 cells x a block of steps (stage_blocks.h has the block lengths); class_of_t[t] and row_of_t[t] are uniform over
+// the wave.  A lane keeps the addends of the CURRENT class in registers while the class stays the same and flushes them
+// when it changes and at the end of the block.  Flushes are integer atomics without a return value, issued for non-zero
+// addends only, coalesced (cells are the fastest axis of every output).  Everything is an integer sum or a maximum: the
+// result does not depend on the block length, the slabs, the launch geometry or the schedule.  No kernel waits for another
+// workgroup.  stage_reduce.h holds the pieces: the in-event bitmap cursor, the category of a step, the fixed point of the
+// sums, the run of a class, the range of a block (DESIGN.md 3.7 says which kernel takes which, and why).
+//
 // mhw_days_by() (kernels_class.hip): the reduction over TIME that keeps the cell.  For every class k < K of time steps
 // (class_of_t[t] in [-1, K), -1 = the step counts nowhere) and cell c, over the in-event steps of the bitmap inev
 // (launch_event_day_bits) with class_of_t[t] == k, class_days_accumulate ADDS to days[k][0..3][c] the steps of category
@@ -405,6 +416,9 @@ hipError_t launch_class_days_accumulate(const T* ts, int64_t Tn, int64_t C, int6
                                         int64_t ldi, int64_t block_steps, int32_t* days, int64_t* isum_q,
                                         double* intensity_max, int64_t ldo, int64_t* n_range, hipStream_t stream);
 hipError_t launch_class_days_finish(int32_t K, int64_t C, double* intensity_max, int64_t ldo, hipStream_t stream);
+// the finish of every float maximum kept as an order-preserving key (kernels_class.hip): keys -> float64, 0 -> NaN, in
+// place, over rows x cols with leading dimension ld (rows <= 65535)
+hipError_t launch_keys_to_f64(double* key, int64_t rows, int64_t cols, int64_t ld, hipStream_t stream);
 
 // mhw_cooccurrence() (kernels_cooccur.hip): the joint event days of two detections per cell, class of time steps and lag.
 // launch_event_table_bits rasterises an event table into the one-bit-per-sample, word-major, cells-minor bitmap of

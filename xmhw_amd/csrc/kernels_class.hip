@@ -11,20 +11,15 @@
 //   key[k][c]            the largest order-preserving key of a + 0.0 over the valid steps (device_common.h), 0 = none
 // A step with a not NaN and |a| >= 2^7 (or infinite) stays in days[k][0..4] and is counted in *n_range.
 //
-//   class_days_accumulate  lane = cell, consecutive lanes on consecutive cells (a wave reads 256 contiguous bytes of a
-//                     float32 row), a workgroup = 256 cells x a block of `tb` steps.  class_of_t[t] and row_of_t[t] are
-//                     uniform over the wave.  A lane keeps the eight addends of the CURRENT class in registers while the
-//                     class stays the same and flushes them when it changes and at the end of the block: calendar
-//                     classes come in runs of ~30 and more steps, so flushes are rare; a class that changes every step
-//                     flushes every step and is still exact.  Flushes are integer atomics without a return value, issued
-//                     for non-zero addends only, coalesced (cells are the fastest axis of every output).  The in-event
-//                     word of 64 steps is read once per word; only in-event lanes read their sample and climatology
-//                     rows; a step whose class is -1, or on which no lane of the wave is in an event, reads nothing.
-//                     Everything is an integer sum or a maximum: the result does not depend on the block length, the
-//                     slabs, the launch geometry or the schedule.  No kernel waits for another workgroup.
-//   class_days_finish      key -> float64 (NaN where no step had a value).
-#include "device_common.h"
-#include "kernels.h"
+//   class_days_accumulate  the frame of a class reduction (kernels.h), eight addends per lane (a wave reads 256
+//                     contiguous bytes of a float32 row).  Calendar classes come in runs of ~30 and more steps, so
+//                     flushes are rare; a class that changes every step flushes every step and is still exact.  The
+//                     in-event word of 64 steps is read once per word; only in-event lanes read their sample and
+//                     climatology rows; a step whose class is -1, or on which no lane of the wave is in an event, reads
+//                     nothing.
+//   keys_to_f64       key -> float64 (NaN where no step, voxel or row had a value), in place: the finish of this stage,
+//                     of mhw_track_intensity() and of mhw_objects() (launch_keys_to_f64, kernels.h).
+#include "stage_reduce.h"
 
 namespace xmhw {
 
@@ -101,18 +96,18 @@ __global__ __launch_bounds__(kCdThreads) void class_days_accumulate(
             if (negate) x = -x;
             const double se = seas[r * ldc + c], th = thresh[r * ldc + c];
             const double a = x - se;
-            const double cat = floor(1.0 + (x - th) / (th - se));           // NaN compares false everywhere
+            const double cat = step_category(x, th, se);
             v.n[0] += cat == 1.0;
             v.n[1] += cat == 2.0;
             v.n[2] += cat == 3.0;
             v.n[3] += cat >= 4.0;
             v.n[4] += 1;
             if (a == a) {
-                if (!(fabs(a) < 128.0)) {
+                if (!(fabs(a) < kFixedRange)) {
                     ++n_range;
                 } else {
                     v.n[5] += 1;
-                    v.is += static_cast<u64>(static_cast<int64_t>(rint(a * 65536.0)));
+                    v.is += static_cast<u64>(fixed_value(a));
                     const u64 key = f64_key(a + 0.0);                       // -0.0 counts as 0.0
                     v.key = key > v.key ? key : v.key;
                 }
@@ -123,25 +118,25 @@ __global__ __launch_bounds__(kCdThreads) void class_days_accumulate(
     if (n_range) atomicAdd(out.n_range, n_range);
 }
 
-__global__ __launch_bounds__(kCdThreads) void class_days_finish(int32_t K, int64_t C, int64_t ldo, u64* __restrict__ key) {
-    const int64_t c = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    for (int32_t k = blockIdx.y; k < K; k += gridDim.y) {
-        const int64_t p = static_cast<int64_t>(k) * ldo + c;
-        const u64 q = key[p];
-        const double v = q ? key_f64(q) : make_nan();
-        key[p] = static_cast<u64>(__double_as_longlong(v));
-    }
-}
-
-hipError_t zero_rows(void* p, size_t item, int64_t rows, int64_t C, int64_t ldo, hipStream_t stream) {
-    if (rows <= 0 || C <= 0) return hipSuccess;
-    return ldo == C ? hipMemsetAsync(p, 0, item * static_cast<size_t>(rows) * static_cast<size_t>(C), stream)
-                    : hipMemset2DAsync(p, item * static_cast<size_t>(ldo), 0, item * static_cast<size_t>(C),
-                                       static_cast<size_t>(rows), stream);
+// keys -> float64, 0 -> NaN, in place: row blockIdx.y of `rows` rows of `cols` keys, leading dimension ld
+__global__ __launch_bounds__(kCdThreads) void keys_to_f64(int64_t cols, int64_t ld, u64* __restrict__ key) {
+    const int64_t c = static_cast<int64_t>(blockIdx.x) * kCdThreads + threadIdx.x;
+    if (c >= cols) return;
+    const int64_t p = static_cast<int64_t>(blockIdx.y) * ld + c;
+    const u64 q = key[p];
+    const double v = q ? key_f64(q) : make_nan();
+    key[p] = static_cast<u64>(__double_as_longlong(v));
 }
 
 }  // namespace
+
+hipError_t launch_keys_to_f64(double* key, int64_t rows, int64_t cols, int64_t ld, hipStream_t stream) {
+    if (rows <= 0 || cols <= 0) return hipSuccess;
+    if (rows > kStageMaxBlocks) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(keys_to_f64, dim3(static_cast<unsigned>(ceil_div(cols, kCdThreads)), static_cast<unsigned>(rows)),
+                       dim3(kCdThreads), 0, stream, cols, ld, reinterpret_cast<u64*>(key));
+    return hipGetLastError();
+}
 
 hipError_t launch_class_days_init(int32_t K, int64_t C, int32_t* days, int64_t* isum_q, double* intensity_max, int64_t ldo,
                                   int64_t* n_range, hipStream_t stream) {
@@ -150,18 +145,6 @@ hipError_t launch_class_days_init(int32_t K, int64_t C, int32_t* days, int64_t* 
     if (e == hipSuccess) e = zero_rows(isum_q, sizeof(int64_t), K, C, ldo, stream);
     if (e == hipSuccess) e = zero_rows(intensity_max, sizeof(double), K, C, ldo, stream);      // key 0: no value yet
     return e;
-}
-
-int64_t class_days_auto_block(int64_t Tn, int64_t C) {
-    // Long blocks keep the flushes rare; a slab too small to fill the chip with one block per 256 cells splits the
-    // time axis until about 2048 workgroups exist, in blocks of whole 64-step words and of 256 steps at least.
-    const int64_t gx = (C + kCdThreads - 1) / kCdThreads;
-    int64_t nblk = (2048 + gx - 1) / gx;
-    const int64_t most = (Tn + 255) / 256;
-    if (nblk > most) nblk = most;
-    if (nblk < 1) nblk = 1;
-    const int64_t tb = (Tn + nblk - 1) / nblk;
-    return (tb + 63) / 64 * 64;
 }
 
 template <typename T>
@@ -174,21 +157,14 @@ hipError_t launch_class_days_accumulate(const T* ts, int64_t Tn, int64_t C, int6
     const int64_t tb = block_steps > 0 ? block_steps : class_days_auto_block(Tn, C);
     const CdOut out{days, reinterpret_cast<u64*>(isum_q), reinterpret_cast<u64*>(intensity_max), ldo,
                     reinterpret_cast<u64*>(n_range)};
-    const int64_t gx = (C + kCdThreads - 1) / kCdThreads;
-    int64_t gy = (Tn + tb - 1) / tb;
-    if (gy > 65535) gy = 65535;                      // the kernel strides over the blocks
-    hipLaunchKernelGGL(class_days_accumulate<T>, dim3(static_cast<unsigned>(gx), static_cast<unsigned>(gy)),
-                       dim3(kCdThreads), 0, stream, ts, Tn, C, ld, seas, thresh, ldc, row_of_t, class_of_t, K, negate, inev,
-                       ldi, tb, out);
+    hipLaunchKernelGGL(class_days_accumulate<T>, stage_grid(C, kCdThreads, Tn, tb), dim3(kCdThreads), 0, stream, ts, Tn, C,
+                       ld, seas, thresh, ldc, row_of_t, class_of_t, K, negate, inev, ldi, tb, out);
     return hipGetLastError();
 }
 
 hipError_t launch_class_days_finish(int32_t K, int64_t C, double* intensity_max, int64_t ldo, hipStream_t stream) {
     if (K <= 0 || C <= 0) return hipSuccess;
-    const int64_t gx = (C + kCdThreads - 1) / kCdThreads;
-    hipLaunchKernelGGL(class_days_finish, dim3(static_cast<unsigned>(gx), static_cast<unsigned>(K < 1024 ? K : 1024)),
-                       dim3(kCdThreads), 0, stream, K, C, ldo, reinterpret_cast<u64*>(intensity_max));
-    return hipGetLastError();
+    return launch_keys_to_f64(intensity_max, K, C, ldo, stream);       // K <= kClassDaysMaxClasses rows
 }
 
 template hipError_t launch_class_days_accumulate<float>(const float*, int64_t, int64_t, int64_t, const double*,

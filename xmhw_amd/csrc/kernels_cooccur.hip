@@ -43,8 +43,7 @@
 //                      path: atomics also where a workgroup owns all of T, as in kernels_class.hip (a second path would
 //                      need its own tests for nothing measurable).  No LDS, no cross-lane traffic, no scratch, and
 //                      nothing waits for another workgroup.
-#include "device_common.h"
-#include "kernels.h"
+#include "stage_reduce.h"
 
 namespace xmhw {
 
@@ -138,8 +137,7 @@ __global__ __launch_bounds__(kCoThreads) void cooccur_accumulate(
 #pragma unroll
         for (int ch = 0; ch < kCooccurChannels; ++ch) acc[i][ch] = 0;
     for (int64_t blk = blockIdx.y; blk < nblk; blk += gridDim.y) {
-        const int64_t w0 = blk * g.wb;
-        const int64_t w1 = g.W - w0 > g.wb ? w0 + g.wb : g.W;
+        const auto [w0, w1] = block_range(blk, g.wb, g.W);
         // the state at the block's first word: per lag the word B[w0 + q] and the top bit of J[w0 - 1]
         u64 bnext[kCooccurLagGroup];
         uint32_t carry = 0;                          // bit i: J's last bit of the previous word under lag i
@@ -224,21 +222,7 @@ hipError_t launch_event_table_bits(const int32_t* start, const int32_t* end, con
 }
 
 hipError_t launch_cooccur_init(int32_t K, int32_t L, int64_t C, int32_t* counts, int64_t ldo, hipStream_t stream) {
-    const int64_t rows = static_cast<int64_t>(K) * L * kCooccurChannels;
-    if (rows <= 0 || C <= 0) return hipSuccess;
-    return ldo == C ? hipMemsetAsync(counts, 0, sizeof(int32_t) * static_cast<size_t>(rows) * static_cast<size_t>(C), stream)
-                    : hipMemset2DAsync(counts, sizeof(int32_t) * static_cast<size_t>(ldo), 0,
-                                       sizeof(int32_t) * static_cast<size_t>(C), static_cast<size_t>(rows), stream);
-}
-
-int64_t cooccur_auto_block(int64_t W, int64_t C, int32_t L) {
-    // One block over W keeps the flushes rare and needs no first-word loads; a slab whose workgroups x lag groups do not
-    // fill the chip splits the word axis until about 2048 workgroups exist.
-    const int64_t wg = (C + kCoThreads - 1) / kCoThreads * ((L + kCooccurLagGroup - 1) / kCooccurLagGroup);
-    if (wg >= 2048 || W <= 1) return W > 0 ? W : 1;
-    int64_t nblk = (2048 + wg - 1) / wg;
-    if (nblk > W) nblk = W;
-    return (W + nblk - 1) / nblk;
+    return zero_rows(counts, sizeof(int32_t), static_cast<int64_t>(K) * L * kCooccurChannels, C, ldo, stream);
 }
 
 hipError_t launch_cooccur_accumulate(const uint64_t* a_bits, int64_t lda, const uint64_t* b_bits, int64_t ldb, int64_t Tn,
@@ -247,15 +231,12 @@ hipError_t launch_cooccur_accumulate(const uint64_t* a_bits, int64_t lda, const 
                                      hipStream_t stream) {
     if (C <= 0 || Tn <= 0 || L <= 0) return hipSuccess;
     const int64_t W = (Tn + 63) / 64;
-    int64_t wb = block_words > 0 ? block_words : cooccur_auto_block(W, C, L);
+    const int64_t gz = ceil_div(L, kCooccurLagGroup);
+    int64_t wb = block_words > 0 ? block_words : cooccur_auto_block(W, C, gz);
     if (wb > W) wb = W;
     const CoShape g{lda, ldb, Tn, W, C, wb, ldo, L};
-    const int64_t gx = (C + kCoThreads - 1) / kCoThreads;
-    int64_t gy = (W + wb - 1) / wb;
-    if (gy > 65535) gy = 65535;                      // the kernel strides over the blocks
-    const int64_t gz = (L + kCooccurLagGroup - 1) / kCooccurLagGroup;
-    hipLaunchKernelGGL(cooccur_accumulate, dim3(static_cast<unsigned>(gx), static_cast<unsigned>(gy), static_cast<unsigned>(gz)),
-                       dim3(kCoThreads), 0, stream, a_bits, b_bits, seg_off, seg_class, seg_mask, lags, counts, g);
+    hipLaunchKernelGGL(cooccur_accumulate, stage_grid(C, kCoThreads, W, wb, gz), dim3(kCoThreads), 0, stream, a_bits, b_bits,
+                       seg_off, seg_class, seg_mask, lags, counts, g);
     return hipGetLastError();
 }
 

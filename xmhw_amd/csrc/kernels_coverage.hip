@@ -18,9 +18,8 @@
 //                        would not hold one step) the wave leader adds to global memory directly - the
 //                        addresses are then spread over the regions.
 // All sums are integers: the result does not depend on the order of the adds, the tiling or the slabs.
-#include "device_common.h"
+#include "stage_reduce.h"
 #include "event_walk.h"
-#include "kernels.h"
 
 namespace xmhw {
 
@@ -104,8 +103,7 @@ __global__ __launch_bounds__(kCovThreads) void coverage_accumulate(
                     double x = static_cast<double>(ts[t * ld + c]);
                     if (negate) x = -x;
                     const double se = seas[r * ldc + c], th = thresh[r * ldc + c];
-                    const double cat = floor(1.0 + (x - th) / (th - se));   // NaN compares false everywhere
-                    k = cat == 1.0 ? 0 : cat == 2.0 ? 1 : cat == 3.0 ? 2 : cat >= 4.0 ? 3 : -1;
+                    k = category_index(step_category(x, th, se)) - 1;
                 }
                 while (todo) {                                               // once per region among the in-event lanes
                     const int leader = __builtin_ctzll(todo);
@@ -154,10 +152,7 @@ __global__ __launch_bounds__(kCovThreads) void coverage_accumulate(
 hipError_t launch_event_day_bits(const uint64_t* bits, int64_t Tn, int64_t C, int64_t ldb, int32_t min_duration,
                                  int32_t join_gaps, int32_t max_gap, uint64_t* inev, int64_t ldi, hipStream_t stream) {
     if (C <= 0 || Tn <= 0) return hipSuccess;
-    const size_t W = static_cast<size_t>((Tn + 63) / 64);
-    hipError_t e = ldi == C ? hipMemsetAsync(inev, 0, sizeof(uint64_t) * W * static_cast<size_t>(C), stream)
-                            : hipMemset2DAsync(inev, sizeof(uint64_t) * static_cast<size_t>(ldi), 0,
-                                               sizeof(uint64_t) * static_cast<size_t>(C), W, stream);
+    const hipError_t e = zero_rows(inev, sizeof(uint64_t), (Tn + 63) / 64, C, ldi, stream);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(event_day_bits, dim3(static_cast<unsigned>((C + 255) / 256)), dim3(256), 0, stream, bits, Tn, C,
                        ldb, min_duration, join_gaps, max_gap, inev, ldi);
@@ -180,10 +175,7 @@ hipError_t launch_coverage_accumulate(const T* ts, int64_t Tn, int64_t C, int64_
     // a workgroup walks several tiles of cells so that its LDS block is flushed once for all of them; small
     // grids keep one tile per workgroup to fill the chip
     const int32_t tiles = C >= 65536 ? 8 : 1;
-    const int64_t gx = (C + static_cast<int64_t>(kCovThreads) * tiles - 1) / (static_cast<int64_t>(kCovThreads) * tiles);
-    int64_t gy = (Tn + tb - 1) / tb;
-    if (gy > 65535) gy = 65535;                                               // the kernel strides over the blocks
-    hipLaunchKernelGGL(coverage_accumulate<T>, dim3(static_cast<unsigned>(gx), static_cast<unsigned>(gy)),
+    hipLaunchKernelGGL(coverage_accumulate<T>, stage_grid(C, static_cast<int64_t>(kCovThreads) * tiles, Tn, tb),
                        dim3(kCovThreads), 0, stream, ts, Tn, C, ld, seas, thresh, ldc, row_of_t, negate, inev, ldi, wq,
                        region, R, tb, tiles, use_lds, reinterpret_cast<unsigned long long*>(cells),
                        reinterpret_cast<unsigned long long*>(area_q));

@@ -17,8 +17,6 @@
 //   max_m[k][c]   int32   the largest dist_m found, 0 if none
 //   *n_visited    int64   over all sources, the entries the source alone had to look at: the position found plus one,
 //                         or the whole list length (entries outside the grid included; a NaN target counts the list)
-// Everything is an integer sum or maximum: the result does not depend on the time blocks, the launch geometry or the
-// schedule.
 //
 //   displacement_accumulate  lane = grid point, a wave = 64 consecutive longitudes of ONE grid row, so the wave shares
 //                     one candidate list and for a fixed entry its lanes read 64 consecutive samples of one day (one
@@ -28,15 +26,14 @@
 //                     The list arrives 64 entries at a time: one coalesced load, lane s holding entry s, handed round
 //                     with v_readlane -- no dependent scalar load per entry.  The lanes still searching (a ballot) walk
 //                     the list together and drop out as they find; the walk ends when none is left or the list is
-//                     exhausted.  The addends of the current class stay in registers (kernels_class.hip) and leave as
-//                     integer atomics without a return value, non-zero ones only, when the class changes and at the
-//                     end of a block of steps.  Every loop is bounded by a list length or the block's steps: nothing
-//                     spins, nothing waits for another wave.  No LDS, no scratch.
+//                     exhausted.  The addends of the current class stay in registers and leave as in the frame of a
+//                     class reduction (kernels.h), whose lane = cell is a lane = grid point here.  Every loop is
+//                     bounded by a list length or the block's steps: nothing spins, nothing waits for another wave.
+//                     No LDS, no scratch.
 //                     Every index is checked where it is formed: an entry whose row leaves the grid is skipped, list
 //                     bounds are clamped to the stream's length, a cell id outside [0, C) is no source -- whatever the
 //                     tables hold, no access leaves its buffer.
-#include "device_common.h"
-#include "kernels.h"
+#include "stage_reduce.h"
 
 namespace xmhw {
 
@@ -111,19 +108,13 @@ __global__ __launch_bounds__(kDpThreads) void displacement_accumulate(
     v.clear();
     u64 visited = 0;
     for (int64_t blk = blockIdx.y; blk < nblk; blk += gridDim.y) {
-        const int64_t ta = g.t0 + blk * g.tb;
-        const int64_t tz = g.t0 + g.nt - ta > g.tb ? ta + g.tb : g.t0 + g.nt;
+        const auto [ta, tz] = block_range(blk, g.tb, g.nt, g.t0);
         int32_t kcur = -1;                           // the class the addends belong to (uniform over the wave)
-        int64_t wi = -1;
-        uint64_t word = 0;
+        EventBits bits;
         for (int64_t t = ta; t < tz; ++t) {
             const int32_t k = class_of_t[t];
             if (k < 0 || k >= g.K) continue;         // counts nowhere (labels are checked on the host): reads nothing
-            if ((t >> 6) != wi) {
-                wi = t >> 6;
-                word = src ? inev[wi * g.ldi + c] : 0;
-            }
-            const bool ev = (word >> (t & 63)) & 1;
+            const bool ev = bits.at(inev, g.ldi, c, src, t);
             if (__ballot(ev) == 0) continue;         // uniform over the wave: no source on this step
             if (k != kcur) {
                 if (kcur >= 0) flush(out, g.ldo, kcur, c, v);
@@ -183,13 +174,6 @@ __global__ __launch_bounds__(kDpThreads) void displacement_accumulate(
     if (lane == 0 && visited) atomicAdd(out.n_visited, visited);
 }
 
-hipError_t zero_rows(void* p, size_t item, int64_t rows, int64_t C, int64_t ldo, hipStream_t stream) {
-    if (rows <= 0 || C <= 0) return hipSuccess;
-    return ldo == C ? hipMemsetAsync(p, 0, item * static_cast<size_t>(rows) * static_cast<size_t>(C), stream)
-                    : hipMemset2DAsync(p, item * static_cast<size_t>(ldo), 0, item * static_cast<size_t>(C),
-                                       static_cast<size_t>(rows), stream);
-}
-
 }  // namespace
 
 hipError_t launch_displacement_init(int32_t K, int64_t C, int32_t* n_days, int32_t* n_found, int64_t* sum_m,
@@ -201,16 +185,6 @@ hipError_t launch_displacement_init(int32_t K, int64_t C, int32_t* n_days, int32
     for (int64_t* p : {sum_m, sum_north_m, sum_east_m})
         if (e == hipSuccess) e = zero_rows(p, sizeof(int64_t), K, C, ldo, stream);
     return e;
-}
-
-int64_t displacement_auto_block(int64_t nt, int64_t ny, int64_t nx) {
-    // One block over the steps keeps the flushes rare; a grid whose waves do not fill the chip splits the steps until
-    // about 2048 workgroups exist.
-    const int64_t wg = (ny * ((nx + 63) / 64) + kDpWaves - 1) / kDpWaves;
-    if (wg >= 2048 || nt <= 1) return nt > 0 ? nt : 1;
-    int64_t nblk = (2048 + wg - 1) / wg;
-    if (nblk > nt) nblk = nt;
-    return (nt + nblk - 1) / nblk;
 }
 
 template <typename T>
@@ -230,12 +204,8 @@ hipError_t launch_displacement_accumulate(const T* ts, int64_t ld, int64_t t0, i
     const DpOut out{n_days, n_found, max_m, reinterpret_cast<u64*>(sum_m), reinterpret_cast<u64*>(sum_north_m),
                     reinterpret_cast<u64*>(sum_east_m), reinterpret_cast<u64*>(n_visited)};
     const int64_t waves = static_cast<int64_t>(ny) * ((static_cast<int64_t>(nx) + 63) / 64);
-    const int64_t gx = (waves + kDpWaves - 1) / kDpWaves;
-    int64_t gy = (nt + tb - 1) / tb;
-    if (gy > 65535) gy = 65535;                      // the kernel strides over the blocks
-    hipLaunchKernelGGL(displacement_accumulate<T>, dim3(static_cast<unsigned>(gx), static_cast<unsigned>(gy)),
-                       dim3(kDpThreads), 0, stream, ts, seas, row_of_t, class_of_t, inev, cell_of_point, basin, list_off,
-                       djdi, dist_m, north_m, east_m, g, out);
+    hipLaunchKernelGGL(displacement_accumulate<T>, stage_grid(waves, kDpWaves, nt, tb), dim3(kDpThreads), 0, stream, ts, seas,
+                       row_of_t, class_of_t, inev, cell_of_point, basin, list_off, djdi, dist_m, north_m, east_m, g, out);
     return hipGetLastError();
 }
 

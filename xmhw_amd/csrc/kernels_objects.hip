@@ -23,7 +23,7 @@
 //                    float maximum is an integer maximum of the order-preserving key of device_common.h.
 //   objects_peak     the smallest row whose key equals its object's maximum (a read in front of the atomic minimum:
 //                    rows arrive roughly in order, so a large tie does not queue on one address).
-//   objects_finish   key -> float64 (NaN where no row had a value).
+//   the finish       key -> float64 (NaN where no row had a value): launch_keys_to_f64 (kernels.h).
 #include "device_common.h"
 #include "kernels.h"
 #include "object_rows.h"                           // kRowThreads, blocks_for
@@ -202,14 +202,6 @@ __global__ __launch_bounds__(kObjThreads) void objects_peak(const double* __rest
     if (row < __hip_atomic_load(peak_row + sl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(peak_row + sl, row);
 }
 
-__global__ __launch_bounds__(kObjThreads) void objects_finish(int64_t n_slots, unsigned long long* __restrict__ key) {
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i >= n_slots) return;
-    const unsigned long long k = key[i];
-    const double v = k ? key_f64(k) : make_nan();
-    key[i] = static_cast<unsigned long long>(__double_as_longlong(v));
-}
-
 }  // namespace
 
 hipError_t launch_event_objects(const int32_t* start, const int32_t* end, int64_t n, const int64_t* offsets, int64_t C,
@@ -250,8 +242,7 @@ hipError_t launch_object_reduce(const int32_t* start, const int32_t* end, const 
         hipLaunchKernelGGL(objects_peak, dim3(blocks_for(n)), dim3(kObjThreads), 0, stream, imax, n, slot, n_slots, key,
                            reinterpret_cast<uint32_t*>(peak_row));
     }
-    hipLaunchKernelGGL(objects_finish, dim3(blocks_for(n_slots)), dim3(kObjThreads), 0, stream, n_slots, key);
-    return hipGetLastError();
+    return launch_keys_to_f64(intensity_max, 1, n_slots, n_slots, stream);
 }
 
 }  // namespace xmhw

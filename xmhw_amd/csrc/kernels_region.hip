@@ -22,8 +22,7 @@
 //                      that hold a step's total (A, B) or all lanes (C) add to global memory directly.
 //                      *n_range is summed in the workgroup and added once per workgroup when non-zero.
 // All sums are integers: the result does not depend on the order of the adds, the tiling or the slabs.
-#include "device_common.h"
-#include "kernels.h"
+#include "stage_reduce.h"
 
 namespace xmhw {
 
@@ -161,12 +160,12 @@ __global__ __launch_bounds__(kRegThreads) void region_accumulate(const T* __rest
                 for (int u = 0; u < kRegUnroll; ++u) {
                     const double d = static_cast<double>(xv[u]) - x0;
                     bool ok = live && d == d;                                // NaN: not a sample
-                    if (ok && !(fabs(d) < 128.0)) {                          // +-inf included
+                    if (ok && !(fabs(d) < kFixedRange)) {                    // +-inf included
                         ++out_of_range;
                         ok = false;
                     }
                     // |xq| <= 2^23: w * xq from 32-bit halves, exact modulo 2^64 (xq's upper half is its sign)
-                    const int32_t xq = ok ? static_cast<int32_t>(rint(d * 65536.0)) : 0;
+                    const int32_t xq = ok ? static_cast<int32_t>(rint(d * kFixedOne)) : 0;
                     const uint32_t xl = static_cast<uint32_t>(xq);
                     uint32_t hi = xq < 0 ? 0u - wl : 0u;
                     if (wide) hi += wh * xl;                                 // uniform
@@ -277,10 +276,7 @@ hipError_t launch_region_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t 
     // a workgroup walks several tiles of cells so that its LDS block is flushed once for all of them; small
     // grids keep one tile per workgroup to fill the chip (as coverage_accumulate)
     const int32_t tiles = C >= 65536 ? 8 : 1;
-    const int64_t gx = (C + static_cast<int64_t>(kRegThreads) * tiles - 1) / (static_cast<int64_t>(kRegThreads) * tiles);
-    int64_t gy = (Tn + tb - 1) / tb;
-    if (gy > 65535) gy = 65535;                                               // the kernel strides over the blocks
-    const dim3 grid(static_cast<unsigned>(gx), static_cast<unsigned>(gy)), block(kRegThreads);
+    const dim3 grid = stage_grid(C, static_cast<int64_t>(kRegThreads) * tiles, Tn, tb), block(kRegThreads);
     u64* a = reinterpret_cast<u64*>(acc);
     u64* nr = reinterpret_cast<u64*>(n_range);
     if (blocked)

@@ -19,11 +19,8 @@
 // and snap_q[j][c] = S(at[j]) whatever the class of that step.  A step of class -1 feeds the window and is reduced nowhere.
 //
 //   class_sums_accumulate, heat_stress_accumulate
-//                     the frame of class_days_accumulate (kernels_class.hip) without the event bitmap: lane = cell,
-//                     consecutive lanes on consecutive cells, a workgroup = 256 cells x a block of `tb` steps, class_of_t
-//                     and row_of_t uniform over the wave.  A lane keeps the addends of the CURRENT class in registers and
-//                     flushes them when the class changes and at the end of the block: integer atomics without a return
-//                     value, for non-zero addends only, coalesced.  A run of class -1 changes no class and costs no flush.
+//                     the frame of a class reduction (kernels.h) without the event bitmap; no barrier, no scratch.  A
+//                     run of class -1 changes no class and costs no flush.
 //                     The samples of several steps are requested together before the first of them is used: eight in
 //                     registers for the class sums; 64 B per lane (16 float32 or 8 float64 steps) for the stress kernel,
 //                     parked in the lane's own column of a 16 KB LDS stage and walked by a loop that is not unrolled --
@@ -48,11 +45,8 @@
 //                     block is at least 16 W steps (warm-up share below 1/16) and 256 steps, and about 4096 steps at
 //                     most: measured faster than one block over the whole series (heat_stress_auto_block).
 //   snapshots         plain stores by the block that owns the step.
-// Everything is an integer sum or an integer maximum: the result does not depend on the block length, the slabs, the
-// launch geometry or the schedule.  No kernel waits for another workgroup; no barrier, no scratch.
 //   heat_stress_finish     key -> peak_q = key >> 32, peak_t = ~key (low word); key 0 -> 0 and -1.
-#include "device_common.h"
-#include "kernels.h"
+#include "stage_reduce.h"
 
 namespace xmhw {
 
@@ -89,10 +83,10 @@ __global__ __launch_bounds__(kHsThreads) void class_sums_accumulate(const T* __r
     const int64_t nblk = (Tn + tb - 1) / tb;
     int32_t n = 0;
     u64 s = 0, n_range = 0;
+    const auto flush_class = [&](int32_t k) { cs_flush(out, k, c, n, s); };
     for (int64_t blk = blockIdx.y; blk < nblk; blk += gridDim.y) {
-        const int64_t t0 = blk * tb;
-        const int64_t t1 = Tn - t0 > tb ? t0 + tb : Tn;
-        int32_t kcur = -1;                           // the class the addends belong to (uniform over the wave)
+        const auto [t0, t1] = block_range(blk, tb, Tn);
+        ClassRun run;
         for (int64_t tc = t0; tc < t1; tc += kHsBatch) {
             int32_t kk[kHsBatch];
             T x[kHsBatch];
@@ -107,22 +101,17 @@ __global__ __launch_bounds__(kHsThreads) void class_sums_accumulate(const T* __r
             for (int u = 0; u < kHsBatch; ++u) {
                 const int32_t k = kk[u];
                 if (k < 0) continue;
-                if (k != kcur) {
-                    if (kcur >= 0) cs_flush(out, kcur, c, n, s);
-                    kcur = k;
-                }
+                run.enter(k, flush_class);
                 const double d = static_cast<double>(x[u]) - x0;
-                if (d == d) {
-                    if (fabs(d) < 128.0) {
-                        n += 1;
-                        s += static_cast<u64>(static_cast<int64_t>(rint(d * 65536.0)));
-                    } else {
-                        ++n_range;
-                    }
+                const int fixed = fixed_state(d);
+                if (fixed < 0) ++n_range;
+                if (fixed > 0) {
+                    n += 1;
+                    s += static_cast<u64>(fixed_value(d));
                 }
             }
         }
-        if (kcur >= 0) cs_flush(out, kcur, c, n, s);
+        run.leave(flush_class);
     }
     if (n_range) atomicAdd(out.n_range, n_range);
 }
@@ -191,7 +180,7 @@ __device__ __forceinline__ double hs_h(const HsIn<T>& in, T sample, double b0, i
     return x - b;
 }
 __device__ __forceinline__ int32_t hs_q(double h, double h0) {
-    return (h >= h0 && h < 128.0) ? static_cast<int32_t>(rint(h * 65536.0)) : 0;      // NaN compares false
+    return (h >= h0 && h < kFixedRange) ? static_cast<int32_t>(rint(h * kFixedOne)) : 0;      // NaN compares false
 }
 template <typename T>
 __device__ __forceinline__ int32_t hs_q_at(const HsIn<T>& in, double b0, int64_t t, int64_t c) {
@@ -219,8 +208,7 @@ __global__ __launch_bounds__(kHsThreads) void heat_stress_accumulate(HsIn<T> in,
     v.clear();
     u64 n_range = 0;
     for (int32_t blk = blockIdx.y; blk < nblk; blk += gridDim.y) {
-        const int32_t t0 = blk * bs;
-        const int32_t t1 = Ts - t0 > bs ? t0 + bs : Ts;
+        const auto [t0, t1] = block_range<int32_t>(blk, bs, Ts);
         // the part of S(t0) before the block: the steps t0 - W + 1 .. t0 - 1
         int32_t S = 0;
         for (int32_t i = t0 - W + 1 > 0 ? t0 - W + 1 : 0; i < t0; ++i) S += hs_q_at(in, b0, i, c);
@@ -244,7 +232,7 @@ __global__ __launch_bounds__(kHsThreads) void heat_stress_accumulate(HsIn<T> in,
                 // the step that leaves the window; S == 0 here means that every q of the window is 0, that one included
                 if (t > t0 && t >= W && S > 0) S -= hs_q_at(in, b0, t - W, c);
                 S += q;
-                if (valid && !(h < 128.0 && h > -INFINITY)) ++n_range;        // h >= 2^7 or infinite
+                if (valid && !(h < kFixedRange && h > -INFINITY)) ++n_range;  // h >= 2^7 or infinite
                 if (j < J && at[j] == t) {
                     out.snap[static_cast<int64_t>(j) * out.ldo + c] = S;
                     ++j;
@@ -281,39 +269,7 @@ __global__ __launch_bounds__(kHsThreads) void heat_stress_finish(int32_t K, int6
     }
 }
 
-hipError_t zero_rows(void* p, size_t item, int64_t rows, int64_t C, int64_t ldo, hipStream_t stream) {
-    if (rows <= 0 || C <= 0) return hipSuccess;
-    return ldo == C ? hipMemsetAsync(p, 0, item * static_cast<size_t>(rows) * static_cast<size_t>(C), stream)
-                    : hipMemset2DAsync(p, item * static_cast<size_t>(ldo), 0, item * static_cast<size_t>(C),
-                                       static_cast<size_t>(rows), stream);
-}
-
-// the grid of 256 cells x blocks of tb steps (the kernels stride over the blocks past 65535)
-dim3 stress_grid(int64_t Tn, int64_t C, int64_t tb) {
-    const int64_t gx = (C + kHsThreads - 1) / kHsThreads;
-    int64_t gy = (Tn + tb - 1) / tb;
-    if (gy > 65535) gy = 65535;
-    return dim3(static_cast<unsigned>(gx), static_cast<unsigned>(gy));
-}
-
 }  // namespace
-
-int64_t heat_stress_auto_block(int64_t Tn, int64_t C, int32_t W) {
-    // A block pays W - 1 warm-up steps: blocks of 16 W steps and more keep that share below 1/16, and of 256 steps and
-    // more keep the flushes rare.  Blocks of about 4096 steps measured faster than one block over 14,610 steps on a grid
-    // that fills the chip by its cells alone (profiles/r24_heat_stress_bench.json: the workgroups finish more evenly),
-    // so that is the most a block takes; a slab too small to fill the chip with such blocks splits the time axis
-    // further, until about 2048 workgroups exist.
-    const int64_t gx = (C + kHsThreads - 1) / kHsThreads;
-    const int64_t least = 16 * static_cast<int64_t>(W) > 256 ? 16 * static_cast<int64_t>(W) : 256;
-    const int64_t cap = least > 4096 ? least : 4096;
-    int64_t nblk = (2048 + gx - 1) / gx;
-    if (nblk < (Tn + cap - 1) / cap) nblk = (Tn + cap - 1) / cap;
-    const int64_t most = Tn / least;
-    if (nblk > most) nblk = most;
-    if (nblk < 1) nblk = 1;
-    return (Tn + nblk - 1) / nblk;
-}
 
 hipError_t launch_class_sums_init(int32_t K, int64_t C, int32_t* n_valid, int64_t* sum_q, int64_t ldo, int64_t* n_range,
                                   hipStream_t stream) {
@@ -330,8 +286,8 @@ hipError_t launch_class_sums_accumulate(const T* ts, int64_t Tn, int64_t C, int6
     if (C <= 0 || Tn <= 0 || K <= 0) return hipSuccess;
     const int64_t tb = block_steps > 0 ? block_steps : heat_stress_auto_block(Tn, C, 1);
     const CsOut out{n_valid, reinterpret_cast<u64*>(sum_q), ldo, reinterpret_cast<u64*>(n_range)};
-    hipLaunchKernelGGL(class_sums_accumulate<T>, stress_grid(Tn, C, tb), dim3(kHsThreads), 0, stream, ts, Tn, C, ld, x0,
-                       class_of_t, K, tb, out);
+    hipLaunchKernelGGL(class_sums_accumulate<T>, stage_grid(C, kHsThreads, Tn, tb), dim3(kHsThreads), 0, stream, ts, Tn, C,
+                       ld, x0, class_of_t, K, tb, out);
     return hipGetLastError();
 }
 
@@ -360,8 +316,8 @@ hipError_t launch_heat_stress_accumulate(const T* ts, int64_t Tn, int64_t C, int
         lv.q[l] = static_cast<int32_t>(level_q[l] > INT32_MAX ? INT32_MAX : level_q[l] < INT32_MIN ? INT32_MIN : level_q[l]);
     const HsOut out{counts, reinterpret_cast<u64*>(hsum_q), reinterpret_cast<u64*>(peak_key), snap_q, ldo,
                     reinterpret_cast<u64*>(n_range)};
-    hipLaunchKernelGGL(heat_stress_accumulate<T>, stress_grid(Tn, C, tb), dim3(kHsThreads), 0, stream, in, Tn, C, W,
-                       class_of_t, K, lv, at, J, tb, out);
+    hipLaunchKernelGGL(heat_stress_accumulate<T>, stage_grid(C, kHsThreads, Tn, tb), dim3(kHsThreads), 0, stream, in, Tn, C,
+                       W, class_of_t, K, lv, at, J, tb, out);
     return hipGetLastError();
 }
 

@@ -20,9 +20,8 @@
 //                     workgroup.  A voxel with |a| >= 2^7 or infinite is left out and counted (*n_range); a voxel of a
 //                     row whose days leave its object's entries is left out and counted (*n_bad): nothing outside
 //                     entries 0..L-1 is ever written.
-//   track_intensity_finish      key -> float64 (NaN where no voxel had a value).
-#include "device_common.h"
-#include "kernels.h"
+//   the finish                  key -> float64 (NaN where no voxel had a value): launch_keys_to_f64 (kernels.h).
+#include "stage_reduce.h"
 
 namespace xmhw {
 
@@ -122,15 +121,15 @@ __global__ __launch_bounds__(kTiThreads) void track_intensity_accumulate(
                     const double se = seas[r * ldc + c], th = thresh[r * ldc + c];
                     const double a = x - se;
                     if (a == a) {
-                        if (!(fabs(a) < 128.0)) {
+                        if (!(fabs(a) < kFixedRange)) {
                             atomicAdd(out.n_range, u64{1});
                         } else {
                             p = base + t;
-                            const double cat = floor(1.0 + (x - th) / (th - se));   // NaN compares false everywhere
+                            const double cat = step_category(x, th, se);
                             const int k = cat == 1.0 ? 1 : cat == 2.0 ? 2 : cat == 3.0 ? 3 : cat >= 4.0 ? 4 : 0;
                             v.cnt = 1 | (k ? u64{1} << (8 * k) : 0);
                             v.w = w;
-                            v.is = w * static_cast<u64>(static_cast<int64_t>(rint(a * 65536.0)));
+                            v.is = w * static_cast<u64>(fixed_value(a));
                             v.key = f64_key(a + 0.0);                              // -0.0 counts as 0.0
                         }
                     }
@@ -154,14 +153,6 @@ __global__ __launch_bounds__(kTiThreads) void track_intensity_accumulate(
             if (p >= 0 && (lane == 63 || next != p)) flush(out, p, v);             // the last lane of a run holds its total
         }
     }
-}
-
-__global__ __launch_bounds__(kTiThreads) void track_intensity_finish(int64_t L, u64* __restrict__ key) {
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i >= L) return;
-    const u64 k = key[i];
-    const double v = k ? key_f64(k) : make_nan();
-    key[i] = static_cast<u64>(__double_as_longlong(v));
 }
 
 }  // namespace
@@ -194,10 +185,7 @@ hipError_t launch_track_intensity_accumulate(const T* ts, int64_t Tn, int64_t n,
     const TiAcc out{n_valid, reinterpret_cast<u64*>(wsum_i), reinterpret_cast<u64*>(isum_q),
                     reinterpret_cast<u64*>(intensity_max), cat_cells, ldcat, reinterpret_cast<u64*>(n_range),
                     reinterpret_cast<u64*>(n_bad)};
-    const int64_t gx = (n + kTiThreads - 1) / kTiThreads;
-    int64_t gy = (Tn + kTrackIntensityChunk - 1) / kTrackIntensityChunk;
-    if (gy > 65535) gy = 65535;                      // the kernel strides over the chunks
-    const dim3 grid(static_cast<unsigned>(gx), static_cast<unsigned>(gy)), block(kTiThreads);
+    const dim3 grid = stage_grid(n, kTiThreads, Tn, kTrackIntensityChunk), block(kTiThreads);
     if (combine_runs)
         hipLaunchKernelGGL((track_intensity_accumulate<T, true>), grid, block, 0, stream, ts, Tn, n, ld, seas, thresh, ldc,
                            row_of_t, negate, start, end, slot, n_rows, row_offsets, wi, time_start, offsets, n_slots, L, out);
@@ -209,9 +197,7 @@ hipError_t launch_track_intensity_accumulate(const T* ts, int64_t Tn, int64_t n,
 
 hipError_t launch_track_intensity_finish(int64_t L, double* intensity_max, hipStream_t stream) {
     if (L <= 0) return hipSuccess;
-    hipLaunchKernelGGL(track_intensity_finish, dim3(static_cast<unsigned>((L + kTiThreads - 1) / kTiThreads)), dim3(kTiThreads), 0,
-                       stream, L, reinterpret_cast<u64*>(intensity_max));
-    return hipGetLastError();
+    return launch_keys_to_f64(intensity_max, 1, L, L, stream);
 }
 
 #define XMHW_TI_INSTANCE(T)                                                                                             \

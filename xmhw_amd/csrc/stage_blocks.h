@@ -1,0 +1,67 @@
+// stage_blocks.h -- how the stage kernels split their block axis (time steps, or 64-step words): plain integer
+// arithmetic without a device type, so that a host program can include it (tests/c/stage_blocks.cpp pins every value).
+//
+// A stage kernel is launched as workgroups x blocks: grid.x covers the cells (or waves of grid points), grid.y the
+// blocks of the axis, and the kernel strides over the blocks that grid.y cannot hold.  Long blocks keep the flushes of
+// a class reduction rare (kernels.h, "The frame of a class reduction"); a slab too small to fill the chip with one block
+// per workgroup splits the axis until about kStageWorkgroups workgroups exist.
+#pragma once
+#include <stdint.h>
+
+namespace xmhw {
+
+constexpr int kStageThreads = 256;                   // the workgroup of every stage kernel
+constexpr int64_t kStageWorkgroups = 2048;           // split the block axis until about this many workgroups exist
+constexpr int64_t kStageMaxBlocks = 65535;           // grid.y at most: the kernels stride over the blocks
+
+static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// grid.y of a strided block kernel
+static inline int64_t stage_blocks(int64_t extent, int64_t block) {
+    const int64_t n = ceil_div(extent, block);
+    return n > kStageMaxBlocks ? kStageMaxBlocks : n;
+}
+
+// The automatic block length of an axis of `extent` items under `wg` workgroups per block: as many blocks as bring the
+// launch to about kStageWorkgroups workgroups; more where a block would exceed about `cap` items (0: no cap); never
+// more than `most`, the blocks that the axis allows (it is what states a stage's least block); one at least.  The
+// block is the axis divided evenly, rounded up to a multiple of `round`.
+static inline int64_t stage_auto_block(int64_t extent, int64_t wg, int64_t most, int64_t cap, int64_t round) {
+    int64_t nblk = ceil_div(kStageWorkgroups, wg);
+    if (cap > 0 && nblk < ceil_div(extent, cap)) nblk = ceil_div(extent, cap);
+    if (nblk > most) nblk = most;
+    if (nblk < 1) nblk = 1;
+    return ceil_div(ceil_div(extent, nblk), round) * round;
+}
+
+// mhw_days_by().  Long blocks keep the flushes rare; a slab too small to fill the chip with one block per 256 cells splits
+// the time axis until about 2048 workgroups exist, in blocks of whole 64-step words and of 256 steps at least.  (The count
+// of 256-step blocks is rounded up, so an axis a little longer than a multiple of 256 may get blocks a little shorter.)
+static inline int64_t class_days_auto_block(int64_t Tn, int64_t C) {
+    return stage_auto_block(Tn, ceil_div(C, kStageThreads), ceil_div(Tn, 256), 0, 64);
+}
+
+// heat_stress() and its class sums (W = 1).  A block pays W - 1 warm-up steps: blocks of 16 W steps and more keep that
+// share below 1/16, and of 256 steps and more keep the flushes rare.  Blocks of about 4096 steps measured faster than one
+// block over 14,610 steps on a grid that fills the chip by its cells alone (profiles/r24_heat_stress_bench.json: the
+// workgroups finish more evenly), so that is the most a block takes; a slab too small to fill the chip with such blocks
+// splits the time axis further, until about 2048 workgroups exist.
+static inline int64_t heat_stress_auto_block(int64_t Tn, int64_t C, int32_t W) {
+    const int64_t least = 16 * static_cast<int64_t>(W) > 256 ? 16 * static_cast<int64_t>(W) : 256;
+    return stage_auto_block(Tn, ceil_div(C, kStageThreads), Tn / least, least > 4096 ? least : 4096, 1);
+}
+
+// mhw_displacement(): a workgroup is four waves of 64 longitudes of one grid row.  One block over the steps keeps the
+// flushes rare; a grid whose waves do not fill the chip splits the steps until about 2048 workgroups exist.
+static inline int64_t displacement_auto_block(int64_t nt, int64_t ny, int64_t nx) {
+    return nt > 0 ? stage_auto_block(nt, ceil_div(ny * ceil_div(nx, 64), kStageThreads / 64), nt, 0, 1) : 1;
+}
+
+// mhw_cooccurrence(): the axis is the W words of the bitmaps, a workgroup takes one lag group (grid.z).  One block over W
+// keeps the flushes rare and needs no first-word loads; a slab whose workgroups x lag groups do not fill the chip splits
+// the word axis until about 2048 workgroups exist.
+static inline int64_t cooccur_auto_block(int64_t W, int64_t C, int64_t lag_groups) {
+    return W > 0 ? stage_auto_block(W, ceil_div(C, kStageThreads) * lag_groups, W, 0, 1) : 1;
+}
+
+}  // namespace xmhw

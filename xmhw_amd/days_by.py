@@ -36,7 +36,7 @@ from ._lib import hip
 from .coverage import CATEGORIES
 from .device import DeviceScope, as_xmhw_errors
 from .exception import XmhwException
-from .series_stage import cells_to_grid, check_class_ids, dense_ids, grid_frame, grid_layout, run, walk_cells, walk_grid
+from .series_stage import CellFrame, check_class_ids, dense_ids, grid_layout, run, walk_cells, walk_grid, walk_stage
 
 MAX_CLASSES = 1024              # XMHW_CLASS_DAYS_MAX_CLASSES (include/xmhw_amd.h)
 CHANNELS = 6                    # XMHW_CLASS_DAYS_CHANNELS: CATEGORIES, then n_valid
@@ -103,13 +103,6 @@ class _Accumulators:
         self._scope.free()
 
 
-def _report(n_range, counters):
-    if counters is not None:
-        counters["n_range"] = int(n_range)
-    elif n_range:
-        raise XmhwException(f"{int(n_range)} {_RANGE_TEXT}")
-
-
 def class_days_cells(ts, seas, thresh, doy, doys, classes, K, minDuration=5, joinGaps=True, maxGap=2, coldSpells=False,
                      max_batch_bytes=64 << 30, pad=None, counters=None):
     """The device stage for a dense (T, C) series (arguments as detect_front.detect_cells): classes (T,) int labels in
@@ -118,14 +111,9 @@ def class_days_cells(ts, seas, thresh, doy, doys, classes, K, minDuration=5, joi
     change a single bit.  Raises if a sample is out of range (module docstring); with ``counters`` (a dict) it stores
     ``n_range`` there instead."""
     acc = _Accumulators(classes, K, minDuration, joinGaps, maxGap, coldSpells)
-    try:
-        walk_cells(ts, seas, thresh, doy, doys, lambda T, isz, D: T * (isz + 1) + T // 4 + 2 * D * 8 + 64, max_batch_bytes,
-                   pad, acc.add_slab, acc.begin)
-        out, n_range = acc.result()
-    finally:
-        acc.free()
-    _report(n_range, counters)
-    return out
+    per_cell = lambda T, isz, D: T * (isz + 1) + T // 4 + 2 * D * 8 + 64                               # noqa: E731
+    return walk_stage(acc, lambda a: walk_cells(ts, seas, thresh, doy, doys, per_cell, max_batch_bytes, pad, a.add_slab,
+                                                a.begin), _RANGE_TEXT, counters)[0]
 
 
 def class_days_grid(stacked, anynans, seas, thresh, doy, doys, classes, K, minDuration=5, joinGaps=True, maxGap=2,
@@ -135,13 +123,9 @@ def class_days_grid(stacked, anynans, seas, thresh, doy, doys, classes, K, minDu
     across the slabs and each slab writes its own column range.  Returns (days, isum_q, intensity_max, keep[N]) over the
     ocean cells."""
     acc = _Accumulators(classes, K, minDuration, joinGaps, maxGap, coldSpells)
-    try:
-        keep = walk_grid(stacked, anynans, seas, thresh, doy, doys, lambda T, D: 6 * D * 8 + T // 4 + 64, max_batch_bytes,
-                         clim_stacked, pad, acc.add_slab, begin=acc.begin)
-        out, n_range = acc.result()
-    finally:
-        acc.free()
-    _report(n_range, counters)
+    out, keep = walk_stage(acc, lambda a: walk_grid(stacked, anynans, seas, thresh, doy, doys,
+                                                    lambda T, D: 6 * D * 8 + T // 4 + 64, max_batch_bytes, clim_stacked, pad,
+                                                    a.add_slab, begin=a.begin), _RANGE_TEXT, counters)
     return out + (keep,)
 
 
@@ -278,19 +262,14 @@ def mhw_days_by(temp, th, se, classes="month", tdim="time", minDuration=5, joinG
               max_batch_bytes, minDuration, joinGaps, maxGap)
     if counters.get("n_range", 0):
         raise XmhwException(f"{counters['n_range']} {_RANGE_TEXT}")
-    keep = np.asarray(mhw.keep, dtype=bool)
-    C = int(keep.sum())
+    f = CellFrame(mhw.keep, mhw.cell_index, point, sdims, sshape, coords)
+    C = f.C
     days6, isum, imax = (np.asarray(a) for a in got)
     if days6.shape != (K, CHANNELS, C) or isum.shape != (K, C) or imax.shape != (K, C):
         raise XmhwException(f"class stage returned {days6.shape}, {isum.shape}, {imax.shape}, expected "
                             f"{(K, CHANNELS, C)}, {(K, C)}, {(K, C)}")
     klass = found if found.shape[0] else np.zeros(1, dtype=np.int64)
     attrs = {"classes": classes if isinstance(classes, str) else "array", "xmhw_parameters": mhw.attrs["xmhw_parameters"]}
-    if point:
-        return ClassDaysDataset(klass, n_steps, days6[:, :5, 0].astype(np.int32), days6[:, 5, 0].astype(np.int32),
-                                isum[:, 0].astype(np.int64), imax[:, 0].astype(np.float64), np.array(True), (), {}, tdim, attrs)
-    alive, out_coords, keep_grid = grid_frame(keep, sdims, sshape, coords)
-    on_grid_shape = lambda a, fill, dtype: cells_to_grid(a, mhw.cell_index, N, sshape, alive, fill, dtype)    # noqa: E731
-    return ClassDaysDataset(klass, n_steps, on_grid_shape(days6[:, :5], 0, np.int32), on_grid_shape(days6[:, 5], 0, np.int32),
-                            on_grid_shape(isum, 0, np.int64), on_grid_shape(imax, np.nan, np.float64), keep_grid, sdims,
-                            out_coords, tdim, attrs)
+    return ClassDaysDataset(klass, n_steps, f.place(days6[:, :5], 0, np.int32), f.place(days6[:, 5], 0, np.int32),
+                            f.place(isum, 0, np.int64), f.place(imax, np.nan, np.float64), f.keep, f.sdims, f.coords, tdim,
+                            attrs)

@@ -50,8 +50,7 @@ from ._lib import hip
 from .days_by import class_labels
 from .device import DeviceScope, as_xmhw_errors, device_budget_bytes, is_packed, native_float
 from .exception import XmhwException
-from .series_stage import (LAND_TEXT, cells_to_grid, check_class_ids, climatologies_on_device, dense_ids, grid_frame,
-                           grid_layout, run)
+from .series_stage import LAND_TEXT, CellFrame, check_class_ids, climatologies_on_device, dense_ids, grid_layout, run
 
 MAX_CLASSES = 1024              # XMHW_DISPLACEMENT_MAX_CLASSES (include/xmhw_amd.h)
 MAX_AXIS = 32767                # XMHW_DISPLACEMENT_MAX_AXIS: dj and di travel as int16
@@ -529,8 +528,8 @@ def mhw_displacement(temp, th, se, mhw, classes="all", max_distance=1000.0, peri
 
     res = run(temp, th, se, layout, tdim, on_cells, on_grid, None, coldSpells, tstep, anynans, _compute, max_batch_bytes)
     st = got["stage"]
-    keep = np.asarray(res.keep, dtype=bool)
-    C = int(keep.sum())
+    f = CellFrame(res.keep, res.cell_index, False, sdims, sshape, coords)
+    C = f.C
     fields = {}
     for name, dtype in _STAGE.items():
         a = np.asarray(st[name])
@@ -541,7 +540,5 @@ def mhw_displacement(temp, th, se, mhw, classes="all", max_distance=1000.0, peri
     attrs = {"classes": classes if isinstance(classes, str) else "array", "max_distance_km": float(max_distance),
              "periodic": periodic, "radius_km": float(radius), "n_visited": int(st["n_visited"]),
              "n_sources": int(fields["n_days"].sum()), "xmhw_parameters": res.attrs["xmhw_parameters"]}
-    alive, out_coords, keep_grid = grid_frame(keep, sdims, sshape, coords)
-    on_grid_shape = lambda a, dtype: cells_to_grid(a, res.cell_index, N, sshape, alive, 0, dtype)          # noqa: E731
-    return DisplacementDataset(klass, n_steps, {n: on_grid_shape(fields[n], d) for n, d in _STAGE.items()}, keep_grid, sdims,
-                               out_coords, tdim, attrs)
+    return DisplacementDataset(klass, n_steps, {n: f.place(fields[n], 0, d) for n, d in _STAGE.items()}, f.keep, f.sdims,
+                               f.coords, tdim, attrs)

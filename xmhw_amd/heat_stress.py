@@ -43,7 +43,7 @@ from .api import GridSeries, _from_xarray, _is_xarray
 from .days_by import class_labels
 from .device import DeviceScope, as_xmhw_errors
 from .exception import XmhwException
-from .series_stage import cells_to_grid, check_class_ids, dense_ids, grid_frame, grid_layout, run, walk_cells, walk_grid
+from .series_stage import CellFrame, check_class_ids, dense_ids, grid_layout, run, walk_cells, walk_grid, walk_stage
 
 MAX_CLASSES = 1024              # XMHW_HEAT_STRESS_MAX_CLASSES (include/xmhw_amd.h)
 CHANNELS = 8                    # XMHW_HEAT_STRESS_CHANNELS: n_valid, n_hot, then the levels
@@ -136,13 +136,6 @@ def snapshot_steps(at, time):
 
 # ---- the device stages -------------------------------------------------------------------------------
 
-def _report(n_range, counters, text):
-    if counters is not None:
-        counters["n_range"] = int(n_range)
-    elif n_range:
-        raise XmhwException(f"{int(n_range)} {text}")
-
-
 class _StressAccumulators:
     """One call's arguments and its device accumulators: counts int32 (K, 8, C), hsum_q int64 (K, C), the peak keys
     (K, C), snap_q int32 (J, C) and the range counter.  Initialised by begin(); they live across the slabs, each slab
@@ -233,16 +226,6 @@ class _SumsAccumulators:
         self._scope.free()
 
 
-def _walk(acc, walker, text, counters):
-    try:
-        keep = walker(acc)
-        out, n_range = acc.result()
-    finally:
-        acc.free()
-    _report(n_range, counters, text)
-    return out, keep
-
-
 def _bytes_per_cell(T, isz, D):
     return T * isz + 2 * D * 8 + 64
 
@@ -256,8 +239,8 @@ def heat_stress_cells(ts, base, doy, doys, classes, K, window, h0, level_q, at, 
     change a single bit.  Raises if a sample is out of range (module docstring); with ``counters`` (a dict) it stores
     ``n_range`` there instead."""
     acc = _StressAccumulators(classes, K, window, h0, level_q, at, coldSpells)
-    out, _ = _walk(acc, lambda a: walk_cells(ts, base, base, doy, doys, _bytes_per_cell, max_batch_bytes, pad, a.add_slab,
-                                             a.begin), _RANGE_TEXT, counters)
+    out, _ = walk_stage(acc, lambda a: walk_cells(ts, base, base, doy, doys, _bytes_per_cell, max_batch_bytes, pad,
+                                                  a.add_slab, a.begin), _RANGE_TEXT, counters)
     return out
 
 
@@ -267,9 +250,9 @@ def heat_stress_grid(stacked, anynans, base, doy, doys, classes, K, window, h0, 
     and the compaction run on the device slab by slab (series_stage.walk_grid).  Returns the five arrays over the ocean
     cells and keep[N]."""
     acc = _StressAccumulators(classes, K, window, h0, level_q, at, coldSpells)
-    out, keep = _walk(acc, lambda a: walk_grid(stacked, anynans, base, base, doy, doys, lambda T, D: 4 * D * 8 + 64,
-                                               max_batch_bytes, clim_stacked, pad, a.add_slab, begin=a.begin),
-                      _RANGE_TEXT, counters)
+    out, keep = walk_stage(acc, lambda a: walk_grid(stacked, anynans, base, base, doy, doys, lambda T, D: 4 * D * 8 + 64,
+                                                    max_batch_bytes, clim_stacked, pad, a.add_slab, begin=a.begin),
+                           _RANGE_TEXT, counters)
     return out + (keep,)
 
 
@@ -278,8 +261,8 @@ def class_sums_cells(ts, classes, K, x0=0.0, max_batch_bytes=64 << 30, pad=None,
     ts = np.asarray(ts)
     zero, steps = np.zeros((1, ts.shape[1])), np.zeros(ts.shape[0], dtype=np.int64)
     acc = _SumsAccumulators(classes, K, x0)
-    out, _ = _walk(acc, lambda a: walk_cells(ts, zero, zero, steps, steps[:1], _bytes_per_cell, max_batch_bytes, pad,
-                                             a.add_slab, a.begin), _SUMS_RANGE_TEXT, counters)
+    out, _ = walk_stage(acc, lambda a: walk_cells(ts, zero, zero, steps, steps[:1], _bytes_per_cell, max_batch_bytes, pad,
+                                                  a.add_slab, a.begin), _SUMS_RANGE_TEXT, counters)
     return out
 
 
@@ -290,35 +273,13 @@ def class_sums_grid(stacked, anynans, land, classes, K, x0=0.0, max_batch_bytes=
     keep[N])."""
     steps = np.zeros(stacked.shape[0], dtype=np.int64)
     acc = _SumsAccumulators(classes, K, x0)
-    out, keep = _walk(acc, lambda a: walk_grid(stacked, anynans, land, land, steps, steps[:1], lambda T, D: 4 * D * 8 + 64,
-                                               max_batch_bytes, clim_stacked, pad, a.add_slab, begin=a.begin),
-                      _SUMS_RANGE_TEXT, counters)
+    out, keep = walk_stage(acc, lambda a: walk_grid(stacked, anynans, land, land, steps, steps[:1],
+                                                    lambda T, D: 4 * D * 8 + 64, max_batch_bytes, clim_stacked, pad,
+                                                    a.add_slab, begin=a.begin), _SUMS_RANGE_TEXT, counters)
     return out + (keep,)
 
 
 # ---- results -----------------------------------------------------------------------------------------
-
-class _CellFrame:
-    """Per-cell results on the grid of the call: a single point, or the grid with its dead lines dropped and the land
-    cells filled (ClassDaysDataset's handling)."""
-
-    def __init__(self, mhw, layout):
-        coords, _, _, self.point, sdims, sshape, self.N = layout
-        self.keep_cells = np.asarray(mhw.keep, dtype=bool)
-        self.C = int(self.keep_cells.sum())
-        self.cell_index, self.sshape = mhw.cell_index, sshape
-        if self.point:
-            self.sdims, self.coords, self.keep = (), {}, np.array(True)
-        else:
-            self.alive, self.coords, self.keep = grid_frame(self.keep_cells, sdims, sshape, coords)
-            self.sdims = tuple(sdims)
-
-    def place(self, a, fill, dtype):
-        a = np.asarray(a)
-        if self.point:
-            return a[..., 0].astype(dtype)
-        return cells_to_grid(a, self.cell_index, self.N, self.sshape, self.alive, fill, dtype)
-
 
 class MonthlyMeanDataset:
     """What maximum_monthly_mean() returns: mmm float64 (...), monthly_mean float64 (12, ...), n_valid int32 (12, ...),
@@ -469,7 +430,7 @@ def heat_stress(temp, base, window=84, min_hotspot=1.0, unit=7.0, levels=(4.0, 8
               max_batch_bytes)
     if counters.get("n_range", 0):
         raise XmhwException(f"{counters['n_range']} {_RANGE_TEXT}")
-    f = _CellFrame(mhw, layout)
+    f = CellFrame(mhw.keep, mhw.cell_index, point, sdims, sshape, coords)
     J, L = steps.shape[0], level_q.shape[0]
     counts, hsum, pq, pt, snap = (np.asarray(a) for a in got)
     want = ((K, CHANNELS, f.C), (K, f.C), (K, f.C), (K, f.C), (J, f.C))
@@ -543,7 +504,7 @@ def maximum_monthly_mean(temp, period=None, tdim="time", offset=0.0, anynans=Fal
     mhw = run(temp, land, land, layout, tdim, on_cells, on_grid, None, False, False, anynans, _compute, max_batch_bytes)
     if counters.get("n_range", 0):
         raise XmhwException(f"{counters['n_range']} {_SUMS_RANGE_TEXT}")
-    f = _CellFrame(mhw, layout)
+    f = CellFrame(mhw.keep, mhw.cell_index, point, sdims, sshape, coords)
     nv, sq = (np.asarray(a) for a in got)
     if nv.shape != (12, f.C) or sq.shape != (12, f.C):
         raise XmhwException(f"class-sums stage returned {nv.shape}, {sq.shape}, expected {(12, f.C)}")

@@ -8,7 +8,10 @@ method on top of the things that exist once, here:
 * run()                     the one shim around detect._detect();
 * dense_ids(), check_class_ids(), check_weighted_cells()    labels and the stage-side checks of per-cell arguments;
 * regions_of_result()       the regions found on ocean cells (mhw_coverage(), region_series());
-* grid_frame(), cells_to_grid()     per-cell results back on the grid (mhw_days_by(), mhw_cooccurrence());
+* walk_stage(), report_range()      one stage call around its accumulators, and its out-of-range count (mhw_days_by(),
+                            heat_stress());
+* CellFrame, grid_frame(), cells_to_grid()      per-cell results back on the grid (mhw_days_by(), mhw_cooccurrence(),
+                            mhw_displacement(), heat_stress());
 * grid_layout()             the spatial layout of a GridSeries / DataArray.
 """
 from collections import namedtuple
@@ -259,6 +262,51 @@ def regions_of_result(keep, rid, w, found):
         return None, ncells, total, np.zeros(1, dtype=np.int64)
     sel = ncells > 0
     return sel, ncells[sel], total[sel], found[sel]
+
+
+def report_range(n_range, counters, text):
+    """What a stage does with its count of samples outside the fixed-point range: into ``counters`` (a dict) when the
+    caller collects it, otherwise an exception worded by ``text``."""
+    if counters is not None:
+        counters["n_range"] = int(n_range)
+    elif n_range:
+        raise XmhwException(f"{int(n_range)} {text}")
+
+
+def walk_stage(acc, walker, text, counters):
+    """One stage call around its accumulators (begin(), add_slab(), result() -> (arrays, n_range), free()):
+    ``walker(acc)`` sends the slabs through them and returns keep[N] or None; the accumulators are freed whatever
+    happens, then the range count is reported.  Returns (arrays, keep)."""
+    try:
+        keep = walker(acc)
+        out, n_range = acc.result()
+    finally:
+        acc.free()
+    report_range(n_range, counters, text)
+    return out, keep
+
+
+class CellFrame:
+    """Per-cell results on the grid of a call: a single point, or the grid with its dead lines dropped (grid_frame())
+    and the land cells filled (cells_to_grid()).  keep (N,): the ocean cells; cell_index: the grid point of every cell
+    of the arrays that place() takes.  sdims, coords and keep are those of the result."""
+
+    def __init__(self, keep, cell_index, point, sdims, sshape, coords):
+        self.point, self.cell_index, self.sshape = point, cell_index, tuple(sshape)
+        self.C = int(np.asarray(keep, dtype=bool).sum())
+        if point:
+            self.sdims, self.coords, self.keep = (), {}, np.array(True)
+        else:
+            self.N = int(np.prod(self.sshape, dtype=np.int64))
+            self.alive, self.coords, self.keep = grid_frame(np.asarray(keep, dtype=bool), sdims, self.sshape, coords)
+            self.sdims = tuple(sdims)
+
+    def place(self, a, fill, dtype):
+        """(..., C) values of the cells as (..., *grid) of ``dtype``, ``fill`` on land"""
+        a = np.asarray(a)
+        if self.point:
+            return a[..., 0].astype(dtype)
+        return cells_to_grid(a, self.cell_index, self.N, self.sshape, self.alive, fill, dtype)
 
 
 def grid_frame(keep, sdims, sshape, coords):
