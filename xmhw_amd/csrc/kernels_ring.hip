@@ -609,6 +609,7 @@ const RingEntry* find_ring(int32_t w, int32_t yps, int32_t subs) {
 
 // a sparse look at a float64 series (32 rows spread over the time axis, every cell) before the
 // narrowing kernel is tried: genuinely float64 data is recognised here at no cost
+// (the rows it reads are restated by probe_rows() of tests/narrowing_cases.py: the two move together)
 __global__ __launch_bounds__(256) void narrow_probe(const double* __restrict__ ts, int64_t Tn, int64_t C,
                                                     int64_t ld, uint32_t* __restrict__ flag) {
     const int64_t c = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;

@@ -386,6 +386,17 @@ __global__ __launch_bounds__(256, 2) void clim_ring2_f32(
         else return ringlo[y][k];
     };
     double lsum = 0.0;        // sum of the valid samples in this lane's rings (all tracks)
+    // 64-bit mode: what the additions to lsum rounded away (Knuth's two-sum, exact, one sample at a time), so that the
+    // lane's sum is lsum + lerr.  A finite double that dwarfs the rest of the pool (1e300 next to 15) absorbs the
+    // running sum while it is in the ring and, without this term, leaves a sum short of everything it absorbed once it
+    // is evicted: the mean of every later row of the chunk was off by percents.  (float32 samples keep the plain sum.)
+    double lerr = 0.0;
+    auto lsum_add = [&](double a) __attribute__((always_inline)) {
+        const double t = lsum + a;
+        const double bv = t - lsum;
+        lerr += (lsum - (t - bv)) + (a - bv);
+        lsum = t;
+    };
     uint32_t nval = 0;        // number of valid keys in this lane's rings (all tracks)
 
     // Sample addressing.  The step table (plan.h) names the time step every track pushes at every step;
@@ -579,18 +590,23 @@ __global__ __launch_bounds__(256, 2) void clim_ring2_f32(
                     di = static_cast<double>(__uint_as_float(bi));
                     dq = static_cast<double>(__uint_as_float(bo));
                 }
-                din = y == 0 ? di : din + di;
-                dout = y == 0 ? dq : dout + dq;
+                if constexpr (kX64) {
+                    lsum_add(di);
+                    lsum_add(-dq);
+                } else {
+                    din = y == 0 ? di : din + di;
+                    dout = y == 0 ? dq : dout + dq;
+                }
                 if constexpr (!PROBE8) dF += (kin[y] <= pc ? 1u : 0u) - (kout[y] <= pc ? 1u : 0u);
             }
-            lsum += din - dout;
+            if constexpr (!kX64) lsum += din - dout;
         } else {
 #pragma unroll
             for (int y = 0; y < YPS; ++y) {
                 // a held track contributes kin == kout: nothing changes
                 if constexpr (kX64) {
-                    lsum += value_of_key64(kin[y], kin_lo[y]);
-                    lsum -= value_of_key64(kout[y], kout_lo[y]);
+                    lsum_add(value_of_key64(kin[y], kin_lo[y]));
+                    lsum_add(-value_of_key64(kout[y], kout_lo[y]));
                 } else {
                     lsum += value_of_key(kin[y]);
                     lsum -= value_of_key(kout[y]);
@@ -643,7 +659,7 @@ __global__ __launch_bounds__(256, 2) void clim_ring2_f32(
             double total;
             if (wallc) {
                 n = cell_sum<SUBS>(nval);
-                total = cell_sum<SUBS>(lsum);
+                total = cell_sum<SUBS>(kX64 ? lsum + lerr : lsum);
             } else {
                 // Feb-29 style rows: only the counted tracks are pooled; count and sum them afresh
                 uint32_t nl = 0;
@@ -681,7 +697,10 @@ __global__ __launch_bounds__(256, 2) void clim_ring2_f32(
                     t += ty;
                     tl += ((cmask >> y) & 1u) ? ty : 0.0;
                 }
+                // (a plain sum: should a huge finite sample share the ring with the infinity, it swallows the lane's other
+                // samples here as it did in the running sum before lerr; the two-sum, one sample at a time, spills)
                 lsum = t;
+                lerr = 0.0;
                 total = cell_sum<SUBS>(tl);
             }
             if constexpr (!PROBE8) Fc += cell_sum<SUBS>(dF);

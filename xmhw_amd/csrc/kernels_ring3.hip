@@ -188,6 +188,21 @@ __global__ __launch_bounds__(64 * waves3(SUBS, X64 ? 8 : 4), 2) void clim_ring3_
         else return value_of_key3(opaque3(ring[y][k]));
     };
     double lsum = 0.0;       // (kRowSum: the CELL's running total, uniform over its lanes)
+    // 64-bit mode: what the additions to lsum rounded away (Knuth's two-sum, exact), so that the total is lsum + lerr.
+    // A finite double that dwarfs the rest of the pool (1e300 next to 15) absorbs the running total while it is in the
+    // ring and, without this term, leaves a total short of everything it absorbed once it is evicted: the mean of every
+    // later row of the chunk was off by percents.  (float32 samples keep the plain sum.)
+    double lerr = 0.0;
+    auto lsum_add = [&](double a) __attribute__((always_inline)) {
+        if constexpr (X64) {
+            const double t = lsum + a;
+            const double bv = t - lsum;
+            lerr += (lsum - (t - bv)) + (a - bv);
+            lsum = t;
+        } else {
+            lsum += a;
+        }
+    };
     uint32_t nval = 0;
     double* const rowsum = reinterpret_cast<double*>(lds + kRsBase) + (kRowSum ? (wave * CPWAVE + cw) * R : 0);
     if constexpr (kRowSum) {
@@ -429,7 +444,12 @@ __global__ __launch_bounds__(64 * waves3(SUBS, X64 ? 8 : 4), 2) void clim_ring3_
             const double cell_in = csum<SUBS>(din);
             const double cell_out = rowsum[m];
             rowsum[m] = cell_in;
-            lsum += cell_in - cell_out;
+            if constexpr (X64) {
+                lsum_add(cell_in);
+                lsum_add(-cell_out);
+            } else {
+                lsum += cell_in - cell_out;
+            }
         } else
         if (fast) {
             // (the pushed samples are summed as they are, the sum changes sign for cold spells: one instruction
@@ -488,7 +508,7 @@ __global__ __launch_bounds__(64 * waves3(SUBS, X64 ? 8 : 4), 2) void clim_ring3_
             double total;
             if (wallc) {
                 n = csum<SUBS>(nval);
-                if constexpr (kRowSum) total = lsum;
+                if constexpr (kRowSum) total = X64 ? lsum + lerr : lsum;
                 else total = csum<SUBS>(lsum);
             } else {
                 uint32_t nl = 0;
@@ -524,6 +544,8 @@ __global__ __launch_bounds__(64 * waves3(SUBS, X64 ? 8 : 4), 2) void clim_ring3_
                     // (a non-finite total: an infinity in the ring, or one that has just left it -- the cell's total and
                     // its row sums are taken from the rings again)
                     double tc = 0.0;
+                    lsum = 0.0;
+                    lerr = 0.0;
 #pragma unroll
                     for (int k = 0; k < R; ++k) {
                         double v = 0.0;
@@ -531,9 +553,9 @@ __global__ __launch_bounds__(64 * waves3(SUBS, X64 ? 8 : 4), 2) void clim_ring3_
                         for (int y = 0; y < YPS; ++y) v = opaque3d(v + val_at(y, k));
                         v = csum<SUBS>(v);
                         rowsum[k] = v;
-                        tc += v;
+                        tc += v;             // (this row's total: the plain sum, +-inf where an infinity is in the ring)
+                        lsum_add(v);         // (64-bit mode: a huge row sum must not swallow the others)
                     }
-                    lsum = tc;
                     total = wallc ? tc : csum<SUBS>(tl);
                 } else {
                 lsum = t;
@@ -1214,7 +1236,8 @@ __global__ __launch_bounds__(64 * waves3(SUBS, X64 ? 8 : 4), 2) void clim_ring3_
         if (rs_stale) {
             // the held tracks' keys have moved one slot up: the row sums (and, from them, the total) are taken from the
             // rings again
-            double tc = 0.0;
+            lsum = 0.0;
+            lerr = 0.0;
 #pragma unroll
             for (int k = 0; k < R; ++k) {
                 double v = 0.0;
@@ -1222,9 +1245,8 @@ __global__ __launch_bounds__(64 * waves3(SUBS, X64 ? 8 : 4), 2) void clim_ring3_
                 for (int y = 0; y < YPS; ++y) v = opaque3d(v + val_at(y, k));
                 v = csum<SUBS>(v);
                 rowsum[k] = v;
-                tc += v;
+                lsum_add(v);                 // (64-bit mode: a huge row sum must not swallow the others)
             }
-            lsum = tc;
             rs_stale = false;
         }
     }
