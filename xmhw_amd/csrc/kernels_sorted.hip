@@ -56,6 +56,7 @@
 #include "kernels.h"
 #include "packed_src.h"
 #include "plan.h"
+#include "sorted_count.h"
 #include "sortnet_gen.h"
 
 namespace xmhw {
@@ -98,6 +99,21 @@ __device__ __forceinline__ uint32_t mad_i24(uint32_t a, int32_t b, uint32_t c) {
 }
 __device__ __forceinline__ uint32_t umin(uint32_t a, uint32_t b) { return a < b ? a : b; }
 __device__ __forceinline__ uint32_t umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
+__device__ __forceinline__ uint32_t max3u(uint32_t a, uint32_t b, uint32_t c) { return umax(umax(a, b), c); }      // (one v_max3_u32)
+
+// Three-input bit operations (v_bitop3_b32: one instruction of the fast issue class, 3.4 cycles against a select's 4.8).
+// Truth tables over (A, B, C), bit index = A * 4 + B * 2 + C.
+#define XMHW_BITOP3(a, b, c, tt) static_cast<uint32_t>(__builtin_amdgcn_bitop3_b32(static_cast<int32_t>(a), static_cast<int32_t>(b), static_cast<int32_t>(c), tt))
+// m ? a : b, bit by bit (m: all ones or 0)
+__device__ __forceinline__ uint32_t bit_sel(uint32_t m, uint32_t a, uint32_t b) { return XMHW_BITOP3(m, a, b, 0xCA); }
+__device__ __forceinline__ uint32_t bit_and(uint32_t a, uint32_t b) { return XMHW_BITOP3(a, b, b, 0xC0); }                      // a & b
+__device__ __forceinline__ uint32_t bit_and_or(uint32_t a, uint32_t b, uint32_t c) { return XMHW_BITOP3(a, b, c, 0xEA); }      // (a & b) | c
+__device__ __forceinline__ uint32_t bit_xor_and(uint32_t a, uint32_t b, uint32_t c) { return XMHW_BITOP3(a, b, c, 0x28); }     // (a ^ b) & c
+__device__ __forceinline__ uint32_t bit_xor_masked(uint32_t a, uint32_t b, uint32_t c) { return XMHW_BITOP3(a, b, c, 0x78); }  // a ^ (b & c)
+// the value the SECOND lane of the cell holds, in both lanes (quad_perm [1, 1, 3, 3])
+__device__ __forceinline__ uint32_t from_sub1(uint32_t v) {
+    return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0xF5, 0xF, 0xF, true));
+}
 
 // key of a non-NaN float in two instructions (v_ashrrev, v_bitop3): (sign | 0x80000000) ^ bits; NEG: the key of the
 // NEGATED sample, (~sign & 0x7FFFFFFF) ^ bits (the sign mask s of the sample itself, C = 0x80000000: ~s & ~C ^ bits)
@@ -632,7 +648,6 @@ __device__ __forceinline__ void sorted_body(
         // ---- 3. the new list replaces the list in slot m ----------------------------------------------------------
         const int m_sub = m >= NL ? 1 : 0;
         const int mj = __builtin_amdgcn_readfirstlane(m - m_sub * NL);
-        const bool own_m = sub == m_sub;
         // (this lane's first rank of list m: lane 0 holds ranks 0 .. K/2-1, lane 1 the rest)
         const uint32_t base_m = lcell + static_cast<uint32_t>(m) * LSTRIDE + static_cast<uint32_t>(sub * KH) * RSTRIDE;
 #pragma unroll
@@ -640,33 +655,28 @@ __device__ __forceinline__ void sorted_body(
             // (EXT: lane 1's last keys -- ranks KL .. K - 1 -- are not for LDS: the rows behind the lists stay 0)
             if (EXT == 0 || i < KH - EXT || sub == 0) lds_st(base_m + static_cast<uint32_t>(i) * RSTRIDE, u[i]);
         }
+        // Who owns slot m is one bit per lane and which of the own slots it is, is scalar: every "the owner takes the new value,
+        // everybody else keeps what they hold" below is ONE three-input bit operation against a mask of all ones or 0 (the fast
+        // issue class; a select is of the slow one) -- the lane mask `own`, and per own slot the SCALAR mask sm[j].
+        // (all ones in the lanes of the sub that owns slot m; kept opaque: left a condition the compiler turns every use of it
+        // back into a select)
+        uint32_t own = (static_cast<uint32_t>(sub) ^ static_cast<uint32_t>(m_sub)) - 1u;
+        asm volatile("" : "+v"(own));
+        uint32_t sm[NL];
+#pragma unroll
+        for (int j = 0; j < NL; ++j)
+            asm volatile("s_cmp_eq_u32 %1, %2\n\ts_cselect_b32 %0, -1, 0" : "=s"(sm[j]) : "s"(mj), "n"(j) : "scc");
         // what leaves: the evicted list's share of the top set, its valid keys, its sum
-        uint32_t c_old = 0, nv_old = 0;
-        // (P[slot]: a chain of selects under scalar conditions)
-        bool is_slot[NL];
-#pragma unroll
-        for (int j = 0; j < NL; ++j) {
-            int mj_ = mj;
-            asm volatile("" : "+s"(mj_));
-            is_slot[j] = mj_ == j;
-        }
         const uint32_t nvm = TV[24 + mj];
-        {
-            uint32_t Pm = P[0];
+        uint32_t Pm = bit_and(P[0], sm[0]);           // (P[slot]: the one own pointer whose scalar mask is set)
 #pragma unroll
-            for (int j = 1; j < NL; ++j) Pm = is_slot[j] ? P[j] : Pm;
-            if (own_m) {
-                c_old = Pm;
-                nv_old = nvm;
-            }
-        }
-        // what comes: keys above the carried boundary join the top set
-        uint32_t c_new = 0;
-#pragma unroll
-        for (int i = 0; i < KH; ++i) c_new += (u[i] > B) ? 1u : 0u;
+        for (int j = 1; j < NL; ++j) Pm = bit_and_or(P[j], sm[j], Pm);
+        // what comes: keys above the carried boundary join the top set (the run is sorted: sorted_count.h)
+        uint32_t c_new = count_above_desc<KH>(u, B);
+        uint32_t c_old, nv_old;
         {
             uint32_t pk = (c_new << 16) | nvin;
-            uint32_t po = (c_old << 16) | nv_old;
+            uint32_t po = ((Pm << 16) | nvm) & own;
             pk += swp(pk);
             po += swp(po);
             c_new = umin(pk >> 16, static_cast<uint32_t>(KL));      // (the pointer counts LDS ranks)
@@ -677,25 +687,28 @@ __device__ __forceinline__ void sorted_body(
         din += swp(din);
         Ctop += c_new - c_old;
         n += nvin - nv_old;
+        {
+            // (the owner's pointer of slot m becomes c_new: P[j] ^= (c_new ^ P[slot]) & own & sm[j])
+            const uint32_t dP = bit_xor_and(c_new, Pm, own);
 #pragma unroll
-        for (int j = 0; j < NL; ++j) P[j] = (own_m && is_slot[j]) ? c_new : P[j];
+            for (int j = 0; j < NL; ++j) P[j] = bit_xor_masked(P[j], dP, sm[j]);
+        }
         // (the lanes that do not own slot m write back what they hold)
-        TV[24 + mj] = own_m ? nvin : nvm;
+        TV[24 + mj] = bit_sel(own, nvin, nvm);
         if constexpr (EXT > 0) {
-            // (ranks KL .. K - 1 are lane 1's last keys; the lane that owns slot m keeps them)
+            // (ranks KL .. K - 1 are lane 1's last keys; the lane that owns slot m keeps them: both lanes of the cell read lane 1's)
 #pragma unroll
             for (int e_ = 0; e_ < EXT; ++e_) {
-                const uint32_t r_ = swp(u[KH - EXT + e_]);
-                const uint32_t mine = sub ? u[KH - EXT + e_] : r_;
+                const uint32_t mine = from_sub1(u[KH - EXT + e_]);
                 const uint32_t old_ = TV[12 + 6 * e_ + mj];
-                TV[12 + 6 * e_ + mj] = own_m ? mine : old_;
+                TV[12 + 6 * e_ + mj] = bit_sel(own, mine, old_);
             }
         }
         {
             const uint64_t db = static_cast<uint64_t>(__double_as_longlong(din));
             const uint32_t ol_ = TV[2 * mj], oh_ = TV[2 * mj + 1];
-            TV[2 * mj] = own_m ? static_cast<uint32_t>(db) : ol_;
-            TV[2 * mj + 1] = own_m ? static_cast<uint32_t>(db >> 32) : oh_;
+            TV[2 * mj] = bit_sel(own, static_cast<uint32_t>(db), ol_);
+            TV[2 * mj + 1] = bit_sel(own, static_cast<uint32_t>(db >> 32), oh_);
         }
         {
             // the pool's total: the 11 list sums added in slot order, every row (a running total would round differently
@@ -1014,12 +1027,18 @@ __device__ __forceinline__ void sorted_body(
             // them) and it lies above the boundary.  Such keys join (pv[j] of list j, largest first) and as many keys -- the
             // smallest of the enlarged set, one by one: LDS heads or register keys -- leave.  Ctop keeps counting LDS keys
             // only, so the next row starts from the same kind of state.
-            // (what every row pays: is some saturated list's first register key above the boundary? -- twelve compares and
-            // scalar logic, no branch per list)
+            // (what every row pays: is ANY own list saturated?  A pointer is at most KL, so the largest of the six says it: two
+            // three-input maxima, a maximum and ONE compare; the common row has no saturated list in the whole wave and leaves
+            // here on a scalar test.  Only the others ask, list by list, whether a saturated list's first register key lies
+            // above the boundary -- twelve compares and scalar logic, no branch per list)
+            const uint32_t pmax = umax(max3u(P[0], P[1], P[2]), max3u(P[3], P[4], P[5]));
             bool anyx = false;
+            if (wave_any(pmax >= static_cast<uint32_t>(KL))) {
 #pragma unroll
-            for (int j = 0; j < NL; ++j) anyx = anyx | ((P[j] == static_cast<uint32_t>(KL)) & (XMHW_EX(0, j) > a_lo));
-            if (XMHW_COLD(wave_any(anyx & !flag))) {
+                for (int j = 0; j < NL; ++j) anyx = anyx | ((P[j] == static_cast<uint32_t>(KL)) & (XMHW_EX(0, j) > a_lo));
+                anyx = wave_any(anyx & !flag);
+            }
+            if (XMHW_COLD(anyx)) {
                 asm volatile("" ::: "memory");
                 uint32_t pv[NL];
                 uint32_t need = 0;
