@@ -1143,6 +1143,71 @@ int xmhw_heat_stress_accumulate_f64(const double *ts_dev, int64_t T, int64_t C, 
 int xmhw_heat_stress_finish(int32_t K, int64_t C, const int64_t *peak_key_dev, int32_t *peak_q_dev, int32_t *peak_t_dev,
                             int64_t ldo, void *stream);
 
+/* ---- index_regression(): lagged regression and correlation maps of the anomalies on climate indices ---- *
+ * What drives the heatwaves of a cell: for every cell the SST anomaly is regressed on an index (Nino-3.4, a basin
+ * mean ...) that leads by 0, 30, 60 ... steps, per class of time steps (Holbrook et al. 2019; Sen Gupta et al. 2020).
+ * One streaming pass over the series, and the first stage whose per-sample work is a product with a SECOND series: a
+ * small matrix product, cells x time against time x predictors, in exact 64-bit integers.
+ *
+ * ts_dev[T][ld] is the series; base_dev is float64 [D][ldb] with row_of_t_host[T] in [0, D): D = 1 is a constant per
+ * cell, D = 366 the `seas` of threshold().  class_of_t_host[T]: one int32 label per step in [-1, K); -1 = the step counts
+ * nowhere (and is not read).  zq_host is the predictor table, int32 [T][J], step-major, in fixed point already, with
+ * |zq| < 2^XMHW_INDEX_REGRESS_PREDICTOR_BITS (the caller chooses its scale; a lagged predictor is a column of its own).
+ * With a = float64(sample) - base[row_of_t[t]][c]:
+ *   the step is VALID iff a == a and |a| < 2^7
+ *   q(t) = int64(rint(a * 2^XMHW_INDEX_REGRESS_BITS)) on valid steps
+ * Any other non-NaN a (|a| >= 2^7 or infinite) of a step with a class is left out everywhere and counted in
+ * *n_range_dev (int64).  For every class k and cell c:
+ *   n[k][c]        int32   over the valid steps of class k: their count
+ *   sa[k][c]       int64   ... the sum of q
+ *   saa[k][c]      int64   ... the sum of q^2
+ *   n1[k][c]       int32   over the valid steps t >= 1 of class k whose step t - 1 is valid and of class k as well:
+ *                          their count
+ *   saa1[k][c]     int64   ... the sum of q(t) q(t - 1): with n1, the lag-1 autocorrelation of the cell
+ *   saz[k][j][c]   int64   over the valid steps of class k: the sum of q(t) zq[t][j]
+ *   mz[k][j][c]    int64   over the steps of class k that are NOT valid (NaN or out of range): the sum of zq[t][j]
+ *   mzz[k][j][c]   int64   ... the sum of zq[t][j]^2
+ * mz and mzz are deficits: the caller computes the sums of zq and zq^2 over all steps of a class once, and a cell's own
+ * sums over its valid steps are those minus its deficits.  T < 2^17 keeps every sum below 2^63 (2^17 * 2^23 * 2^23).
+ * Everything is an integer sum: the result is exact and does not depend on the time blocks, the slabs, the launch
+ * geometry or the schedule.  Cells are the fastest axis of every output: saz, mz and mzz are [K][J][ldo], the others
+ * [K][ldo], ldo >= C; columns past C are never touched, and a slab addresses its columns by pointer offset, as in
+ * xmhw_heat_stress_*.
+ *
+ *  1. xmhw_index_regress_init zeroes columns 0..C-1 of the accumulators and the counter.
+ *  2. xmhw_index_regress_accumulate_* handles one slab of C cells and ADDS into the accumulators.  Lane = cell,
+ *     workgroup = 256 cells x a block of steps; a lane keeps the addends of the current class in registers (one 64-bit
+ *     multiply-add per predictor and step) and issues integer atomics without a return value when the class changes and
+ *     at the end of its block; a step that is not valid issues its deficits directly.  A block that starts at t0 > 0
+ *     reads step t0 - 1 once for the lag-1 pair (csrc/kernels_regress.hip).
+ * Both are asynchronous on `stream`.  Refusals, in this order and before the first HIP call: K < 1 or
+ * K > XMHW_INDEX_REGRESS_MAX_CLASSES, J < 1 or J > XMHW_INDEX_REGRESS_MAX_PREDICTORS, T of 2^17 and more, C of 2^31 and
+ * more: XMHW_ERR_UNSUPPORTED.  A bad T, C, D or leading dimension, a NULL host table, a label outside [-1, K), a row
+ * outside [0, D), a predictor outside (-2^23, 2^23): XMHW_ERR_INVALID.  Then nothing is launched for C == 0; then a NULL
+ * device buffer is XMHW_ERR_INVALID.
+ * xmhw_set_index_regress_block (process-wide; tests and measurements): the steps a workgroup takes per block,
+ * 0 = automatic.  Same results for every value.                                                                      */
+#define XMHW_INDEX_REGRESS_MAX_PREDICTORS 32
+#define XMHW_INDEX_REGRESS_MAX_CLASSES    64
+#define XMHW_INDEX_REGRESS_MAX_STEPS      131072     /* T below it */
+#define XMHW_INDEX_REGRESS_BITS           16
+#define XMHW_INDEX_REGRESS_RANGE_BITS     7
+#define XMHW_INDEX_REGRESS_PREDICTOR_BITS 23
+int xmhw_set_index_regress_block(int32_t steps);      /* tests and measurements; 0 = automatic */
+int xmhw_index_regress_init(int32_t K, int32_t J, int64_t C, int32_t *n_dev, int64_t *sa_dev, int64_t *saa_dev,
+                            int32_t *n1_dev, int64_t *saa1_dev, int64_t *saz_dev, int64_t *mz_dev, int64_t *mzz_dev,
+                            int64_t ldo, int64_t *n_range_dev, void *stream);
+int xmhw_index_regress_accumulate_f32(const float *ts_dev, int64_t T, int64_t C, int64_t ld, const double *base_dev,
+                                      int64_t ldb, int64_t D, const int32_t *row_of_t_host, const int32_t *class_of_t_host,
+                                      int32_t K, const int32_t *zq_host, int32_t J, int32_t *n_dev, int64_t *sa_dev,
+                                      int64_t *saa_dev, int32_t *n1_dev, int64_t *saa1_dev, int64_t *saz_dev,
+                                      int64_t *mz_dev, int64_t *mzz_dev, int64_t ldo, int64_t *n_range_dev, void *stream);
+int xmhw_index_regress_accumulate_f64(const double *ts_dev, int64_t T, int64_t C, int64_t ld, const double *base_dev,
+                                      int64_t ldb, int64_t D, const int32_t *row_of_t_host, const int32_t *class_of_t_host,
+                                      int32_t K, const int32_t *zq_host, int32_t J, int32_t *n_dev, int64_t *sa_dev,
+                                      int64_t *saa_dev, int32_t *n1_dev, int64_t *saa1_dev, int64_t *saz_dev,
+                                      int64_t *mz_dev, int64_t *mzz_dev, int64_t ldo, int64_t *n_range_dev, void *stream);
+
 /* ---- the sharded path: cells split across the GPUs of a node, ONE gather at the end ------- *
  * Replaces the reference's collect, dask.compute(climls) + xr.concat(dim='cell')
  * (xmhw/xmhw.py:197, :210-211).  Cells are independent (xmhw/xmhw.py:184-196), so rank r runs the

@@ -27,6 +27,7 @@ from .days_by import mhw_days_by, ClassDaysDataset, classes_from_events
 from .cooccurrence import mhw_cooccurrence, CooccurrenceDataset
 from .displacement import mhw_displacement, displacement_offsets, DisplacementDataset, DisplacementTable
 from .heat_stress import heat_stress, maximum_monthly_mean, degree_heating_weeks, HeatStressDataset, MonthlyMeanDataset
+from .index_regression import index_regression, IndexRegressionDataset
 from .ingest import open_series, threshold_file
 from .detrend import detrend, DetrendSpec, FitDataset
 
@@ -38,6 +39,6 @@ __all__ = ["threshold", "threshold_array", "GridSeries", "ClimDataset", "XmhwExc
            "mhw_track_shape", "TrackShapeDataset", "compactness", "region_series", "RegionSeriesDataset", "mhw_days_by", "ClassDaysDataset",
            "classes_from_events", "mhw_cooccurrence", "CooccurrenceDataset", "mhw_displacement", "displacement_offsets",
            "DisplacementDataset", "DisplacementTable", "heat_stress", "maximum_monthly_mean", "degree_heating_weeks",
-           "HeatStressDataset", "MonthlyMeanDataset", "open_series",
+           "HeatStressDataset", "MonthlyMeanDataset", "index_regression", "IndexRegressionDataset", "open_series",
            "threshold_file", "detrend", "DetrendSpec", "FitDataset"]
 __version__ = "0.1.0"

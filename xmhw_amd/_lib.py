@@ -6,6 +6,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _mod = None
 _stress = None
+_regress = None
 _err = None
 
 
@@ -40,6 +41,19 @@ def hip_stress():
         except ImportError as e:  # pragma: no cover - build problem
             raise HipExtensionMissing(f"cannot import xmhw_amd._xmhw_hip_stress: {e}") from e
     return _stress
+
+
+def hip_regress():
+    """Return the pybind11 module ``xmhw_amd._xmhw_hip_regress`` (the bindings of index_regression()), loaded as
+    hip_stress() loads its module, or raise.  It raises the exception classes of ``_xmhw_hip``."""
+    global _regress
+    if _regress is None:
+        hip()
+        try:
+            _regress = _RetryOnNoMem(importlib.import_module("xmhw_amd._xmhw_hip_regress"))
+        except ImportError as e:  # pragma: no cover - build problem
+            raise HipExtensionMissing(f"cannot import xmhw_amd._xmhw_hip_regress: {e}") from e
+    return _regress
 
 
 class _RetryOnNoMem:

@@ -951,6 +951,52 @@ int heat_stress_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const
                      "heat_stress_accumulate launch");
 }
 
+static std::atomic<int> g_index_regress_block{0};   // steps a workgroup takes per block, 0 = automatic (xmhw_set_index_regress_block)
+
+static int index_regress_check_shape(int32_t K, int32_t J, int64_t Tn, int64_t C) {
+    if (K < 1 || K > xmhw::kIndexRegressMaxClasses)
+        return fail(XMHW_ERR_UNSUPPORTED,
+                    "index_regress: K must be in [1, " + std::to_string(xmhw::kIndexRegressMaxClasses) + "]");
+    if (J < 1 || J > xmhw::kIndexRegressMaxPredictors)
+        return fail(XMHW_ERR_UNSUPPORTED,
+                    "index_regress: J must be in [1, " + std::to_string(xmhw::kIndexRegressMaxPredictors) + "]");
+    if (Tn >= xmhw::kIndexRegressMaxSteps) return fail(XMHW_ERR_UNSUPPORTED, "index_regress: 2^17 steps and more");
+    if (C > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "index_regress: 2^31 cells and more");
+    return XMHW_OK;
+}
+
+template <typename T>
+int index_regress_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* base, int64_t ldb, int64_t D,
+                             const int32_t* row_of_t, const int32_t* class_of_t, int32_t K, const int32_t* zq, int32_t J,
+                             int32_t* n, int64_t* sa, int64_t* saa, int32_t* n1, int64_t* saa1, int64_t* saz, int64_t* mz,
+                             int64_t* mzz, int64_t ldo, int64_t* n_range, void* stream) {
+    if (index_regress_check_shape(K, J, Tn, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (Tn <= 0 || C < 0 || ld < C || ldb < C || ldo < C || D < 1) return fail(XMHW_ERR_INVALID, "bad T/C/ld/ldb/ldo/D");
+    if (!class_of_t || !row_of_t || !zq) return fail(XMHW_ERR_INVALID, "NULL host table");
+    if (int rc = check_labels(class_of_t, Tn, -1, K, kClassesOutside)) return rc;
+    if (int rc = check_labels(row_of_t, Tn, 0, D, kRowsOutside)) return rc;
+    constexpr int32_t zlim = 1 << xmhw::kIndexRegressPredictorBits;
+    if (int rc = check_labels(zq, Tn * J, -zlim + 1, zlim, "zq outside (-2^23, 2^23)")) return rc;
+    if (C == 0) return XMHW_OK;
+    if (!ts || !base || !n || !sa || !saa || !n1 || !saa1 || !saz || !mz || !mzz || !n_range)
+        return fail(XMHW_ERR_INVALID, "NULL buffer");
+    RowsRef rows;
+    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
+    RowsRef classes;                                   // the same content-keyed cache: one more int32[T] table
+    if (int rc = upload_table(class_of_t, Tn, "class table upload", &classes)) return rc;
+    // ... and the predictors, step-major, J padded with zero columns to the kernel's group: int32[T][G]
+    const int G = xmhw::index_regress_group(J);
+    std::vector<int32_t> padded(static_cast<size_t>(Tn) * G, 0);
+    for (int64_t t = 0; t < Tn; ++t) std::copy(zq + t * J, zq + (t + 1) * J, padded.begin() + t * G);
+    RowsRef predictors;
+    if (int rc = upload_table(padded.data(), Tn * G, "predictor table upload", &predictors)) return rc;
+    return status_of(xmhw::launch_index_regress_accumulate<T>(ts, Tn, C, ld, base, ldb, D, rows->d_rows, classes->d_rows, K,
+                                                              predictors->d_rows, J, g_index_regress_block.load(), n, sa, saa,
+                                                              n1, saa1, saz, mz, mzz, ldo, n_range,
+                                                              static_cast<hipStream_t>(stream)),
+                     "index_regress_accumulate launch");
+}
+
 template <typename T>
 int event_stats_sparse(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* seas, const double* thresh,
                        int64_t ldc, const int32_t* row_of_t, int32_t negate, int64_t n_events, double* table,
@@ -2244,6 +2290,38 @@ int xmhw_heat_stress_finish(int32_t K, int64_t C, const int64_t* peak_key, int32
     if (!peak_key || !peak_q || !peak_t) return fail(XMHW_ERR_INVALID, "NULL buffer");
     return status_of(xmhw::launch_heat_stress_finish(K, C, peak_key, peak_q, peak_t, ldo, static_cast<hipStream_t>(stream)),
                      "heat_stress_finish launch");
+}
+
+int xmhw_set_index_regress_block(int32_t steps) {
+    if (steps < 0) return fail(XMHW_ERR_INVALID, "steps must be >= 0");
+    g_index_regress_block = steps;
+    return XMHW_OK;
+}
+int xmhw_index_regress_init(int32_t K, int32_t J, int64_t C, int32_t* n, int64_t* sa, int64_t* saa, int32_t* n1, int64_t* saa1,
+                            int64_t* saz, int64_t* mz, int64_t* mzz, int64_t ldo, int64_t* n_range, void* stream) {
+    if (index_regress_check_shape(K, J, 1, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
+    if (!n_range || (C > 0 && (!n || !sa || !saa || !n1 || !saa1 || !saz || !mz || !mzz)))
+        return fail(XMHW_ERR_INVALID, "NULL output buffer");
+    return status_of(xmhw::launch_index_regress_init(K, J, C, n, sa, saa, n1, saa1, saz, mz, mzz, ldo, n_range,
+                                                     static_cast<hipStream_t>(stream)),
+                     "index_regress_init");
+}
+int xmhw_index_regress_accumulate_f32(const float* ts, int64_t T, int64_t C, int64_t ld, const double* base, int64_t ldb,
+                                      int64_t D, const int32_t* row_of_t, const int32_t* class_of_t, int32_t K,
+                                      const int32_t* zq, int32_t J, int32_t* n, int64_t* sa, int64_t* saa, int32_t* n1,
+                                      int64_t* saa1, int64_t* saz, int64_t* mz, int64_t* mzz, int64_t ldo, int64_t* n_range,
+                                      void* stream) {
+    return index_regress_accumulate<float>(ts, T, C, ld, base, ldb, D, row_of_t, class_of_t, K, zq, J, n, sa, saa, n1, saa1,
+                                           saz, mz, mzz, ldo, n_range, stream);
+}
+int xmhw_index_regress_accumulate_f64(const double* ts, int64_t T, int64_t C, int64_t ld, const double* base, int64_t ldb,
+                                      int64_t D, const int32_t* row_of_t, const int32_t* class_of_t, int32_t K,
+                                      const int32_t* zq, int32_t J, int32_t* n, int64_t* sa, int64_t* saa, int32_t* n1,
+                                      int64_t* saa1, int64_t* saz, int64_t* mz, int64_t* mzz, int64_t ldo, int64_t* n_range,
+                                      void* stream) {
+    return index_regress_accumulate<double>(ts, T, C, ld, base, ldb, D, row_of_t, class_of_t, K, zq, J, n, sa, saa, n1, saa1,
+                                            saz, mz, mzz, ldo, n_range, stream);
 }
 
 int xmhw_synth_sst_f32(float* ts, int64_t T, int64_t C, int64_t ld, int64_t cell0, uint64_t seed,

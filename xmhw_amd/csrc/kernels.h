@@ -385,8 +385,8 @@ hipError_t launch_track_intensity_accumulate(const T* ts, int64_t Tn, int64_t n,
 hipError_t launch_track_intensity_finish(int64_t L, double* intensity_max, hipStream_t stream);
 
 // The frame of a class reduction: the kernels below that reduce over TIME and keep the cell (class_days_accumulate,
-// class_sums_accumulate, heat_stress_accumulate; displacement_accumulate with a grid point and cooccur_accumulate with
-// 64-step words in the place of the cell and the step).  Lane = cell, consecutive lanes on consecutive cells; a workgroup
+// class_sums_accumulate, heat_stress_accumulate, index_regress_accumulate; displacement_accumulate with a grid point and
+// cooccur_accumulate with 64-step words in the place of the cell and the step).  Lane = cell, consecutive lanes on consecutive cells; a workgroup
 // is 256 cells x a block of steps (stage_blocks.h has the block lengths); class_of_t[t] and row_of_t[t] are uniform over
 // the wave.  A lane keeps the addends of the CURRENT class in registers while the class stays the same and flushes them
 // when it changes and at the end of the block.  Flushes are integer atomics without a return value, issued for non-zero
@@ -499,6 +499,32 @@ hipError_t launch_heat_stress_accumulate(const T* ts, int64_t Tn, int64_t C, int
                                          hipStream_t stream);
 hipError_t launch_heat_stress_finish(int32_t K, int64_t C, const int64_t* peak_key, int32_t* peak_q, int32_t* peak_t,
                                      int64_t ldo, hipStream_t stream);
+
+// index_regression() (kernels_regress.hip): the sums behind lagged regression maps of anomalies on indices.  With
+// a = sample - base[row_of_t[t]][c], the step VALID iff a is not NaN and |a| < 2^7, q = rint(a * 2^kIndexRegressBits) on
+// valid steps, and the predictor row zq[t][0..J) of the step, launch_index_regress_accumulate ADDS per class k of the step
+// and cell c: over the valid steps n[k][c] += 1, sa += q, saa += q^2, saz[k][j][c] += q * zq[t][j]; over the valid steps
+// whose step t - 1 is valid and of class k as well n1 += 1, saa1 += q(t) q(t - 1); over the steps of class k that are NOT
+// valid mz[k][j][c] += zq[t][j], mzz[k][j][c] += zq[t][j]^2; and counts the non-NaN a with |a| >= 2^7 of the steps with a
+// class in *n_range.  Cells are the fastest axis, leading dimension ldo >= C.  row_of_t and class_of_t are DEVICE arrays
+// here, and so is zq: int32 [T][G], step-major, G = index_regress_group(J) columns of which those past J are zero.
+// block_steps: the steps a workgroup takes per block, 0 = automatic; same results for every value.
+constexpr int kIndexRegressMaxPredictors = 32;
+constexpr int kIndexRegressMaxClasses = 64;
+constexpr int kIndexRegressMaxSteps = 1 << 17;       // T below it: 2^17 * 2^23 * 2^23 = 2^63
+constexpr int kIndexRegressBits = 16;
+constexpr int kIndexRegressPredictorBits = 23;       // |zq| < 2^23
+// the predictor columns of the kernel instantiation that takes J predictors: 4, 8, 16 or 32
+inline int index_regress_group(int32_t J) { return J <= 4 ? 4 : J <= 8 ? 8 : J <= 16 ? 16 : 32; }
+hipError_t launch_index_regress_init(int32_t K, int32_t J, int64_t C, int32_t* n, int64_t* sa, int64_t* saa, int32_t* n1,
+                                     int64_t* saa1, int64_t* saz, int64_t* mz, int64_t* mzz, int64_t ldo, int64_t* n_range,
+                                     hipStream_t stream);
+template <typename T>
+hipError_t launch_index_regress_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* base, int64_t ldb,
+                                           int64_t D, const int32_t* row_of_t, const int32_t* class_of_t, int32_t K,
+                                           const int32_t* zq, int32_t J, int64_t block_steps, int32_t* n, int64_t* sa,
+                                           int64_t* saa, int32_t* n1, int64_t* saa1, int64_t* saz, int64_t* mz, int64_t* mzz,
+                                           int64_t ldo, int64_t* n_range, hipStream_t stream);
 
 // file bytes -> samples (kernels_ingest.hip): raw_type = item size of the stored type (2 int16, 4 float32,
 // 8 float64), swap = the file is big-endian, optional scale/offset (CF packing) and fill value -> NaN

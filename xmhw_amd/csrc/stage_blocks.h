@@ -51,6 +51,15 @@ static inline int64_t heat_stress_auto_block(int64_t Tn, int64_t C, int32_t W) {
     return stage_auto_block(Tn, ceil_div(C, kStageThreads), Tn / least, least > 4096 ? least : 4096, 1);
 }
 
+// index_regression().  A block pays one step again (the lag-1 pair of its first step) and one flush, so short blocks are
+// cheap, and they measured faster than long ones at every grid size (profiles/r27_index_regress_bench.json: 512 steps
+// beat 4096 by 12 % at 32 predictors on a grid that fills the chip by its cells alone -- at 4 waves per SIMD the
+// workgroups finish more evenly -- and 256 steps beat 512 only on a small slab): blocks of about 512 steps at most and of
+// 256 at least; a slab too small to fill the chip with such blocks splits the time axis until about 2048 workgroups exist.
+static inline int64_t index_regress_auto_block(int64_t Tn, int64_t C) {
+    return stage_auto_block(Tn, ceil_div(C, kStageThreads), Tn / 256, 512, 1);
+}
+
 // mhw_displacement(): a workgroup is four waves of 64 longitudes of one grid row.  One block over the steps keeps the
 // flushes rare; a grid whose waves do not fill the chip splits the steps until about 2048 workgroups exist.
 static inline int64_t displacement_auto_block(int64_t nt, int64_t ny, int64_t nx) {
