@@ -1208,6 +1208,61 @@ int xmhw_index_regress_accumulate_f64(const double *ts_dev, int64_t T, int64_t C
                                       int64_t *saa_dev, int32_t *n1_dev, int64_t *saa1_dev, int64_t *saz_dev,
                                       int64_t *mz_dev, int64_t *mzz_dev, int64_t ldo, int64_t *n_range_dev, void *stream);
 
+/* ---- mhw_composite(): event-centred composites (superposed epoch analysis) of a field, per cell ---- *
+ * What a field looks like 30 days before every heatwave onset of a cell, at the peak, 20 days after the end (Holbrook et
+ * al. 2019; Sen Gupta et al. 2020): the first stage whose per-sample work is keyed by the distance to an event of the
+ * lane's own cell.
+ *
+ * ts_dev[T][ld] is the series (the SST anomaly's series itself, or wind stress, heat flux, mixed-layer depth on the same
+ * cells); base_dev is float64 [Dr][ldb] with row_of_t_host[T] in [0, Dr): Dr = 1 is a constant per cell, read once.
+ * anchor_bits_dev is the anchor bitmap in the layout of xmhw_event_table_bits (bits[w * lda + c], bits at t >= T zero;
+ * table rows with start == end make it the anchor rasteriser).  class_of_t_host[T]: one int32 label per step in [-1, K).
+ * before >= 0 and after >= 0 with D = before + after + 1 <= XMHW_COMPOSITE_MAX_OFFSETS; shift in
+ * [0, XMHW_COMPOSITE_MAX_SHIFT].  For every cell c, every anchor step s of c with k = class_of_t[s] >= 0 and every offset
+ * d in [-before, after] with 0 <= s + d < T:
+ *   a = (float64(ts[s + d][c]) - base[row_of_t[s + d]][c]) * 2^-shift       (the scaling is exact)
+ *   a NaN adds nothing; |a| >= 2^7 or infinite adds 1 to *n_range_dev (int64); otherwise
+ *   q = int64(rint(a * 2^XMHW_COMPOSITE_BITS)) and, with i = d + before,
+ *   n[k][i][c] += 1 (int32), s[k][i][c] += q (int64), ss[k][i][c] += q^2 (int64).
+ * The class is that of the ANCHOR step, not of the sample: an event belongs to the season or ENSO phase of its onset.
+ * Anchors of class -1 count nowhere, n_range included.  shift exists because the 2^7 range is an SST range: heat flux in
+ * W m^-2 needs shift = 4 or so, and the resolution becomes 2^(shift - 16).  T < 2^17, |q| <= 2^23, q^2 <= 2^46 and at most
+ * T anchors per entry: every sum stays inside 64 bits.  Everything is an integer sum: the result is exact and does not
+ * depend on the time blocks, the slabs, the launch geometry or the schedule.  The outputs are [K][D][ldo], ldo >= C;
+ * columns past C are never touched, and a slab addresses its columns by pointer offset.
+ *
+ *  1. xmhw_composite_init zeroes columns 0..C-1 of the accumulators and the counter.
+ *  2. xmhw_composite_accumulate_* handles one slab of C cells and ADDS into the accumulators.  Lane = cell, workgroup =
+ *     256 cells x a block of steps; a lane carries a window of D bits (bit i: an anchor at step t + before - i), a step
+ *     on which no lane of a wave has a bit set requests no sample, and every set bit issues its three integer atomics
+ *     without a return value.  A block builds its window from bitmap words alone (csrc/kernels_composite.hip).
+ * Both are asynchronous on `stream`.  Refusals, in this order and before the first HIP call: before or after < 0, K < 1 or
+ * K > XMHW_COMPOSITE_MAX_CLASSES, D > XMHW_COMPOSITE_MAX_OFFSETS, shift outside [0, XMHW_COMPOSITE_MAX_SHIFT], T of 2^17
+ * and more, C of 2^31 and more: XMHW_ERR_UNSUPPORTED.  A bad T, C, Dr or leading dimension, a NULL host table, a label
+ * outside [-1, K), a row outside [0, Dr): XMHW_ERR_INVALID.  Then nothing is launched for C == 0 or T == 0; then a NULL
+ * device buffer is XMHW_ERR_INVALID.
+ * xmhw_set_composite_block (process-wide; tests and measurements): the steps a workgroup takes per block, 0 = automatic.
+ * Same results for every value.                                                                                       */
+#define XMHW_COMPOSITE_MAX_OFFSETS 128
+#define XMHW_COMPOSITE_MAX_CLASSES 64
+#define XMHW_COMPOSITE_MAX_STEPS   131072            /* T below it */
+#define XMHW_COMPOSITE_BITS        16
+#define XMHW_COMPOSITE_RANGE_BITS  7
+#define XMHW_COMPOSITE_MAX_SHIFT   24
+int xmhw_set_composite_block(int32_t steps);          /* tests and measurements; 0 = automatic */
+int xmhw_composite_init(int32_t K, int32_t D, int64_t C, int32_t *n_dev, int64_t *s_dev, int64_t *ss_dev, int64_t ldo,
+                        int64_t *n_range_dev, void *stream);
+int xmhw_composite_accumulate_f32(const float *ts_dev, int64_t T, int64_t C, int64_t ld, const double *base_dev, int64_t ldb,
+                                  int64_t Dr, const int32_t *row_of_t_host, int32_t shift, const uint64_t *anchor_bits_dev,
+                                  int64_t lda, const int32_t *class_of_t_host, int32_t K, int32_t before, int32_t after,
+                                  int32_t *n_dev, int64_t *s_dev, int64_t *ss_dev, int64_t ldo, int64_t *n_range_dev,
+                                  void *stream);
+int xmhw_composite_accumulate_f64(const double *ts_dev, int64_t T, int64_t C, int64_t ld, const double *base_dev,
+                                  int64_t ldb, int64_t Dr, const int32_t *row_of_t_host, int32_t shift,
+                                  const uint64_t *anchor_bits_dev, int64_t lda, const int32_t *class_of_t_host, int32_t K,
+                                  int32_t before, int32_t after, int32_t *n_dev, int64_t *s_dev, int64_t *ss_dev,
+                                  int64_t ldo, int64_t *n_range_dev, void *stream);
+
 /* ---- the sharded path: cells split across the GPUs of a node, ONE gather at the end ------- *
  * Replaces the reference's collect, dask.compute(climls) + xr.concat(dim='cell')
  * (xmhw/xmhw.py:197, :210-211).  Cells are independent (xmhw/xmhw.py:184-196), so rank r runs the

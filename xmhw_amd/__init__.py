@@ -28,6 +28,7 @@ from .cooccurrence import mhw_cooccurrence, CooccurrenceDataset
 from .displacement import mhw_displacement, displacement_offsets, DisplacementDataset, DisplacementTable
 from .heat_stress import heat_stress, maximum_monthly_mean, degree_heating_weeks, HeatStressDataset, MonthlyMeanDataset
 from .index_regression import index_regression, IndexRegressionDataset
+from .composite import mhw_composite, CompositeDataset
 from .ingest import open_series, threshold_file
 from .detrend import detrend, DetrendSpec, FitDataset
 
@@ -39,6 +40,7 @@ __all__ = ["threshold", "threshold_array", "GridSeries", "ClimDataset", "XmhwExc
            "mhw_track_shape", "TrackShapeDataset", "compactness", "region_series", "RegionSeriesDataset", "mhw_days_by", "ClassDaysDataset",
            "classes_from_events", "mhw_cooccurrence", "CooccurrenceDataset", "mhw_displacement", "displacement_offsets",
            "DisplacementDataset", "DisplacementTable", "heat_stress", "maximum_monthly_mean", "degree_heating_weeks",
-           "HeatStressDataset", "MonthlyMeanDataset", "index_regression", "IndexRegressionDataset", "open_series",
+           "HeatStressDataset", "MonthlyMeanDataset", "index_regression", "IndexRegressionDataset", "mhw_composite",
+           "CompositeDataset", "open_series",
            "threshold_file", "detrend", "DetrendSpec", "FitDataset"]
 __version__ = "0.1.0"

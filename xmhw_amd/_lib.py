@@ -7,6 +7,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _mod = None
 _stress = None
 _regress = None
+_composite = None
 _err = None
 
 
@@ -54,6 +55,19 @@ def hip_regress():
         except ImportError as e:  # pragma: no cover - build problem
             raise HipExtensionMissing(f"cannot import xmhw_amd._xmhw_hip_regress: {e}") from e
     return _regress
+
+
+def hip_composite():
+    """Return the pybind11 module ``xmhw_amd._xmhw_hip_composite`` (the bindings of mhw_composite()), loaded as
+    hip_stress() loads its module, or raise.  It raises the exception classes of ``_xmhw_hip``."""
+    global _composite
+    if _composite is None:
+        hip()
+        try:
+            _composite = _RetryOnNoMem(importlib.import_module("xmhw_amd._xmhw_hip_composite"))
+        except ImportError as e:  # pragma: no cover - build problem
+            raise HipExtensionMissing(f"cannot import xmhw_amd._xmhw_hip_composite: {e}") from e
+    return _composite
 
 
 class _RetryOnNoMem:

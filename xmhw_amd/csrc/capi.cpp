@@ -997,6 +997,46 @@ int index_regress_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, con
                      "index_regress_accumulate launch");
 }
 
+static std::atomic<int> g_composite_block{0};   // steps a workgroup takes per block, 0 = automatic (xmhw_set_composite_block)
+
+static int composite_check_shape(int32_t K, int64_t D, int32_t shift, int64_t Tn, int64_t C) {
+    if (K < 1 || K > xmhw::kCompositeMaxClasses)
+        return fail(XMHW_ERR_UNSUPPORTED, "composite: K must be in [1, " + std::to_string(xmhw::kCompositeMaxClasses) + "]");
+    if (D < 1 || D > xmhw::kCompositeMaxOffsets)
+        return fail(XMHW_ERR_UNSUPPORTED,
+                    "composite: before + after + 1 must be in [1, " + std::to_string(xmhw::kCompositeMaxOffsets) + "]");
+    if (shift < 0 || shift > xmhw::kCompositeMaxShift)
+        return fail(XMHW_ERR_UNSUPPORTED, "composite: shift must be in [0, " + std::to_string(xmhw::kCompositeMaxShift) + "]");
+    if (Tn >= xmhw::kCompositeMaxSteps) return fail(XMHW_ERR_UNSUPPORTED, "composite: 2^17 steps and more");
+    if (C > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "composite: 2^31 cells and more");
+    return XMHW_OK;
+}
+
+template <typename T>
+int composite_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* base, int64_t ldb, int64_t Dr,
+                         const int32_t* row_of_t, int32_t shift, const uint64_t* anchor_bits, int64_t lda,
+                         const int32_t* class_of_t, int32_t K, int32_t before, int32_t after, int32_t* n, int64_t* s,
+                         int64_t* ss, int64_t ldo, int64_t* n_range, void* stream) {
+    if (before < 0 || after < 0) return fail(XMHW_ERR_UNSUPPORTED, "composite: before and after must be >= 0");
+    if (composite_check_shape(K, static_cast<int64_t>(before) + after + 1, shift, Tn, C) != XMHW_OK)
+        return XMHW_ERR_UNSUPPORTED;
+    if (Tn < 0 || C < 0 || ld < C || ldb < C || lda < C || ldo < C || Dr < 1)
+        return fail(XMHW_ERR_INVALID, "bad T/C/ld/ldb/lda/ldo/D");
+    if (Tn > 0 && (!class_of_t || !row_of_t)) return fail(XMHW_ERR_INVALID, "NULL host table");
+    if (int rc = check_labels(class_of_t, Tn, -1, K, kClassesOutside)) return rc;
+    if (int rc = check_labels(row_of_t, Tn, 0, Dr, kRowsOutside)) return rc;
+    if (C == 0 || Tn == 0) return XMHW_OK;
+    if (!ts || !base || !anchor_bits || !n || !s || !ss || !n_range) return fail(XMHW_ERR_INVALID, "NULL buffer");
+    RowsRef rows;
+    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
+    RowsRef classes;                                   // the same content-keyed cache: one more int32[T] table
+    if (int rc = upload_table(class_of_t, Tn, "class table upload", &classes)) return rc;
+    return status_of(xmhw::launch_composite_accumulate<T>(ts, Tn, C, ld, base, ldb, Dr, rows->d_rows, shift, anchor_bits, lda,
+                                                          classes->d_rows, K, before, after, g_composite_block.load(), n, s,
+                                                          ss, ldo, n_range, static_cast<hipStream_t>(stream)),
+                     "composite_accumulate launch");
+}
+
 template <typename T>
 int event_stats_sparse(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* seas, const double* thresh,
                        int64_t ldc, const int32_t* row_of_t, int32_t negate, int64_t n_events, double* table,
@@ -2322,6 +2362,34 @@ int xmhw_index_regress_accumulate_f64(const double* ts, int64_t T, int64_t C, in
                                       void* stream) {
     return index_regress_accumulate<double>(ts, T, C, ld, base, ldb, D, row_of_t, class_of_t, K, zq, J, n, sa, saa, n1, saa1,
                                             saz, mz, mzz, ldo, n_range, stream);
+}
+
+int xmhw_set_composite_block(int32_t steps) {
+    if (steps < 0) return fail(XMHW_ERR_INVALID, "steps must be >= 0");
+    g_composite_block = steps;
+    return XMHW_OK;
+}
+int xmhw_composite_init(int32_t K, int32_t D, int64_t C, int32_t* n, int64_t* s, int64_t* ss, int64_t ldo, int64_t* n_range,
+                        void* stream) {
+    if (composite_check_shape(K, D, 0, 1, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
+    if (!n_range || (C > 0 && (!n || !s || !ss))) return fail(XMHW_ERR_INVALID, "NULL output buffer");
+    return status_of(xmhw::launch_composite_init(K, D, C, n, s, ss, ldo, n_range, static_cast<hipStream_t>(stream)),
+                     "composite_init");
+}
+int xmhw_composite_accumulate_f32(const float* ts, int64_t T, int64_t C, int64_t ld, const double* base, int64_t ldb,
+                                  int64_t Dr, const int32_t* row_of_t, int32_t shift, const uint64_t* anchor_bits, int64_t lda,
+                                  const int32_t* class_of_t, int32_t K, int32_t before, int32_t after, int32_t* n, int64_t* s,
+                                  int64_t* ss, int64_t ldo, int64_t* n_range, void* stream) {
+    return composite_accumulate<float>(ts, T, C, ld, base, ldb, Dr, row_of_t, shift, anchor_bits, lda, class_of_t, K, before,
+                                       after, n, s, ss, ldo, n_range, stream);
+}
+int xmhw_composite_accumulate_f64(const double* ts, int64_t T, int64_t C, int64_t ld, const double* base, int64_t ldb,
+                                  int64_t Dr, const int32_t* row_of_t, int32_t shift, const uint64_t* anchor_bits, int64_t lda,
+                                  const int32_t* class_of_t, int32_t K, int32_t before, int32_t after, int32_t* n, int64_t* s,
+                                  int64_t* ss, int64_t ldo, int64_t* n_range, void* stream) {
+    return composite_accumulate<double>(ts, T, C, ld, base, ldb, Dr, row_of_t, shift, anchor_bits, lda, class_of_t, K, before,
+                                        after, n, s, ss, ldo, n_range, stream);
 }
 
 int xmhw_synth_sst_f32(float* ts, int64_t T, int64_t C, int64_t ld, int64_t cell0, uint64_t seed,

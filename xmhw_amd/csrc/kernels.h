@@ -385,7 +385,8 @@ hipError_t launch_track_intensity_accumulate(const T* ts, int64_t Tn, int64_t n,
 hipError_t launch_track_intensity_finish(int64_t L, double* intensity_max, hipStream_t stream);
 
 // The frame of a class reduction: the kernels below that reduce over TIME and keep the cell (class_days_accumulate,
-// class_sums_accumulate, heat_stress_accumulate, index_regress_accumulate; displacement_accumulate with a grid point and
+// class_sums_accumulate, heat_stress_accumulate, index_regress_accumulate, composite_accumulate -- which keeps no addends
+// and adds every (anchor, offset) pair directly; displacement_accumulate with a grid point and
 // cooccur_accumulate with 64-step words in the place of the cell and the step).  Lane = cell, consecutive lanes on consecutive cells; a workgroup
 // is 256 cells x a block of steps (stage_blocks.h has the block lengths); class_of_t[t] and row_of_t[t] are uniform over
 // the wave.  A lane keeps the addends of the CURRENT class in registers while the class stays the same and flushes them
@@ -525,6 +526,29 @@ hipError_t launch_index_regress_accumulate(const T* ts, int64_t Tn, int64_t C, i
                                            const int32_t* zq, int32_t J, int64_t block_steps, int32_t* n, int64_t* sa,
                                            int64_t* saa, int32_t* n1, int64_t* saa1, int64_t* saz, int64_t* mz, int64_t* mzz,
                                            int64_t ldo, int64_t* n_range, hipStream_t stream);
+
+// mhw_composite() (kernels_composite.hip): event-centred composites of a field, per cell.  anchor_bits is a bitmap of
+// launch_event_table_bits whose set bits are the anchor steps of every cell (leading dimension lda).  With
+// D = before + after + 1, for every cell c, anchor step s of c with k = class_of_t[s] >= 0 and offset d in [-before, after]
+// with 0 <= s + d < Tn, and a = (sample(s + d) - base[row_of_t[s + d]][c]) * 2^-shift: launch_composite_accumulate ADDS,
+// with i = d + before and for an a that is not NaN and |a| < 2^7, 1 to n[k][i][c], q = rint(a * 2^kCompositeBits) to
+// s[k][i][c] and q^2 to ss[k][i][c]; any other non-NaN a adds 1 to *n_range.  The class is that of the anchor step.  Cells
+// are the fastest axis, leading dimension ldo >= C; the outputs are [K][D][ldo].  row_of_t and class_of_t are DEVICE arrays
+// here.  block_steps: the steps a workgroup takes per block, 0 = automatic; same results for every value.
+constexpr int kCompositeMaxOffsets = 128;            // D at most: a window of two words
+constexpr int kCompositeMaxClasses = 64;
+constexpr int kCompositeMaxSteps = 1 << 17;          // T below it, the cap of index_regression(): 2^17 * 2^46 = 2^63
+constexpr int kCompositeBits = 16;
+constexpr int kCompositeRangeBits = 7;
+constexpr int kCompositeMaxShift = 24;
+hipError_t launch_composite_init(int32_t K, int32_t D, int64_t C, int32_t* n, int64_t* s, int64_t* ss, int64_t ldo,
+                                 int64_t* n_range, hipStream_t stream);
+template <typename T>
+hipError_t launch_composite_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* base, int64_t ldb,
+                                       int64_t Dr, const int32_t* row_of_t, int32_t shift, const uint64_t* anchor_bits,
+                                       int64_t lda, const int32_t* class_of_t, int32_t K, int32_t before, int32_t after,
+                                       int64_t block_steps, int32_t* n, int64_t* s, int64_t* ss, int64_t ldo,
+                                       int64_t* n_range, hipStream_t stream);
 
 // file bytes -> samples (kernels_ingest.hip): raw_type = item size of the stored type (2 int16, 4 float32,
 // 8 float64), swap = the file is big-endian, optional scale/offset (CF packing) and fill value -> NaN

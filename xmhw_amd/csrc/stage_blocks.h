@@ -60,6 +60,18 @@ static inline int64_t index_regress_auto_block(int64_t Tn, int64_t C) {
     return stage_auto_block(Tn, ceil_div(C, kStageThreads), Tn / 256, 512, 1);
 }
 
+// mhw_composite(), D = before + after + 1 offsets.  A block builds its window from three bitmap words at most and reads no
+// sample for it, and nothing is flushed at its end, so short blocks are cheap: the rule of index_regression() -- blocks of
+// about 512 steps at most and of 256 at least; a slab too small to fill the chip with such blocks splits the time axis
+// until about 2048 workgroups exist.  Measured (profiles/r28_composite_bench.json, r28_composite_blocks_small.json): on
+// a grid that fills the chip by its cells alone the block length moves the time by 4 % at most (111 .. 116 ms from 256
+// steps to one block, D = 61: the atomics bind, not the walk); on a slab of 65,536 cells blocks of 256 and 512 steps
+// beat 4,096 by 18 % and one block by 43 %.  D does not enter: the warm-up costs the same for every window.
+static inline int64_t composite_auto_block(int64_t Tn, int64_t C, int64_t D) {
+    (void)D;
+    return stage_auto_block(Tn, ceil_div(C, kStageThreads), Tn / 256, 512, 1);
+}
+
 // mhw_displacement(): a workgroup is four waves of 64 longitudes of one grid row.  One block over the steps keeps the
 // flushes rare; a grid whose waves do not fill the chip splits the steps until about 2048 workgroups exist.
 static inline int64_t displacement_auto_block(int64_t nt, int64_t ny, int64_t nx) {
