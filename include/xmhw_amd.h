@@ -1263,6 +1263,65 @@ int xmhw_composite_accumulate_f64(const double *ts_dev, int64_t T, int64_t C, in
                                   int32_t before, int32_t after, int32_t *n_dev, int64_t *s_dev, int64_t *ss_dev,
                                   int64_t ldo, int64_t *n_range_dev, void *stream);
 
+/* ---- lag_correlation(): per-cell lagged auto- and cross-correlation ---- *
+ * The memory of the anomaly of a cell (autocorrelation function, e-folding time, integral time scale, effective sample
+ * size: Holbrook et al. 2019; Jacox et al. 2022) and the lagged correlation of two fields in the same cell (net heat flux,
+ * wind stress or mixed-layer depth against the SST anomaly): the first stage that multiplies a sample by the lane's own
+ * past, or by the past of a second resident series.
+ *
+ * x_dev[T][ldx] and y_dev[T][ldy] are two series of the same float type; y_dev may be the very buffer of x_dev
+ * (autocorrelation), with the same bits as a separate copy.  base_x_dev[Dr][ldbx] and base_y_dev[Dr][ldby] are float64 with
+ * ONE row_of_t_host[T] in [0, Dr): Dr = 1 is a constant per cell, read once.  shift_x, shift_y in
+ * [0, XMHW_LAG_CORR_MAX_SHIFT]; class_of_t_host[T]: one int32 label per step in [-1, K), K <= XMHW_LAG_CORR_MAX_CLASSES;
+ * max_lag = L in [0, XMHW_LAG_CORR_MAX_LAG]; T < 2^17, C < 2^31.
+ *   ax(t) = (float64(x[t][c]) - base_x[row_of_t[t]][c]) * 2^-shift_x, likewise ay       (the scaling is exact)
+ *   a value is VALID iff it is not NaN and |a| < 2^XMHW_LAG_CORR_RANGE_BITS; q = int64(rint(a * 2^XMHW_LAG_CORR_BITS)).
+ * For every cell c, every step t with k = class_of_t[t] >= 0, every lag l in [0, L] with t - l >= 0, and ax(t) and
+ * ay(t - l) both valid:
+ *   n  [k][l][c] += 1 (int32)        sx [k][l][c] += qx(t)          sy [k][l][c] += qy(t - l)
+ *   sxx[k][l][c] += qx(t)^2          syy[k][l][c] += qy(t - l)^2    sxy[k][l][c] += qx(t) qy(t - l)      (all int64)
+ * The class of a pair is that of its LATER step; the earlier step may be of any class, -1 included.  All six sums run
+ * over the valid pairs alone (pairwise deletion), so Pearson's r of every lag is a true correlation.  |q| <= 2^23,
+ * products <= 2^46, fewer than 2^17 pairs per entry: everything stays inside 64 bits.  n_range_dev[2] (int64): [0] counts
+ * the steps of class >= 0 at which ax is not NaN and out of range, [1] the steps of any class at which ay is; each step
+ * once, whatever the blocks.  x is not read on steps of class -1.  Everything is an integer sum: the result is exact and
+ * does not depend on the time blocks, the slabs, the launch geometry or the schedule.  The outputs are [K][L + 1][ldo],
+ * ldo >= C; columns past C are never touched, and a slab addresses its columns by pointer offset.
+ *
+ *  1. xmhw_lag_corr_init zeroes columns 0..C-1 of the accumulators and the two counters.
+ *  2. xmhw_lag_corr_accumulate_* handles one slab of C cells and ADDS into the accumulators: two calls on disjoint column
+ *     ranges equal one.  Lane = cell, workgroup = 256 cells x a block of steps x a group of 8 or 16 lags; qy of the last steps
+ *     in an LDS ring of 16 / 32 / 64 slots per lane, their validity in a 64-bit mask; a block rebuilds both from the
+ *     max_lag steps before it (csrc/kernels_lagcorr.hip, csrc/lag_ring.h).
+ * Both are asynchronous on `stream`.  Refusals, in this order and before the first HIP call: K < 1 or
+ * K > XMHW_LAG_CORR_MAX_CLASSES, max_lag outside [0, XMHW_LAG_CORR_MAX_LAG], a shift outside [0, XMHW_LAG_CORR_MAX_SHIFT],
+ * T of 2^17 and more, C of 2^31 and more: XMHW_ERR_UNSUPPORTED.  A bad T, C, Dr or leading dimension, a NULL host table, a
+ * label outside [-1, K), a row outside [0, Dr): XMHW_ERR_INVALID.  Then nothing is launched for C == 0 or T == 0; then a
+ * NULL device buffer is XMHW_ERR_INVALID.
+ * xmhw_set_lag_corr_block (process-wide; tests and measurements): the steps a workgroup takes per block, 0 = automatic,
+ * a negative value is XMHW_ERR_INVALID.  Same results for every value.                                               */
+#define XMHW_LAG_CORR_MAX_LAG      63
+#define XMHW_LAG_CORR_MAX_CLASSES  64
+#define XMHW_LAG_CORR_MAX_STEPS    131072            /* T below it */
+#define XMHW_LAG_CORR_BITS         16
+#define XMHW_LAG_CORR_RANGE_BITS   7
+#define XMHW_LAG_CORR_MAX_SHIFT    24
+int xmhw_set_lag_corr_block(int32_t steps);           /* tests and measurements; 0 = automatic */
+int xmhw_lag_corr_init(int32_t K, int32_t max_lag, int64_t C, int32_t *n_dev, int64_t *sx_dev, int64_t *sy_dev,
+                       int64_t *sxx_dev, int64_t *syy_dev, int64_t *sxy_dev, int64_t ldo, int64_t *n_range_dev, void *stream);
+int xmhw_lag_corr_accumulate_f32(const float *x_dev, int64_t ldx, const float *y_dev, int64_t ldy, int64_t T, int64_t C,
+                                 const double *base_x_dev, int64_t ldbx, const double *base_y_dev, int64_t ldby, int64_t Dr,
+                                 const int32_t *row_of_t_host, int32_t shift_x, int32_t shift_y,
+                                 const int32_t *class_of_t_host, int32_t K, int32_t max_lag, int32_t *n_dev, int64_t *sx_dev,
+                                 int64_t *sy_dev, int64_t *sxx_dev, int64_t *syy_dev, int64_t *sxy_dev, int64_t ldo,
+                                 int64_t *n_range_dev, void *stream);
+int xmhw_lag_corr_accumulate_f64(const double *x_dev, int64_t ldx, const double *y_dev, int64_t ldy, int64_t T, int64_t C,
+                                 const double *base_x_dev, int64_t ldbx, const double *base_y_dev, int64_t ldby, int64_t Dr,
+                                 const int32_t *row_of_t_host, int32_t shift_x, int32_t shift_y,
+                                 const int32_t *class_of_t_host, int32_t K, int32_t max_lag, int32_t *n_dev, int64_t *sx_dev,
+                                 int64_t *sy_dev, int64_t *sxx_dev, int64_t *syy_dev, int64_t *sxy_dev, int64_t ldo,
+                                 int64_t *n_range_dev, void *stream);
+
 /* ---- the sharded path: cells split across the GPUs of a node, ONE gather at the end ------- *
  * Replaces the reference's collect, dask.compute(climls) + xr.concat(dim='cell')
  * (xmhw/xmhw.py:197, :210-211).  Cells are independent (xmhw/xmhw.py:184-196), so rank r runs the

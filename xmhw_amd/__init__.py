@@ -29,6 +29,7 @@ from .displacement import mhw_displacement, displacement_offsets, DisplacementDa
 from .heat_stress import heat_stress, maximum_monthly_mean, degree_heating_weeks, HeatStressDataset, MonthlyMeanDataset
 from .index_regression import index_regression, IndexRegressionDataset
 from .composite import mhw_composite, CompositeDataset
+from .lag_correlation import lag_correlation, LagCorrelationDataset
 from .ingest import open_series, threshold_file
 from .detrend import detrend, DetrendSpec, FitDataset
 
@@ -41,6 +42,6 @@ __all__ = ["threshold", "threshold_array", "GridSeries", "ClimDataset", "XmhwExc
            "classes_from_events", "mhw_cooccurrence", "CooccurrenceDataset", "mhw_displacement", "displacement_offsets",
            "DisplacementDataset", "DisplacementTable", "heat_stress", "maximum_monthly_mean", "degree_heating_weeks",
            "HeatStressDataset", "MonthlyMeanDataset", "index_regression", "IndexRegressionDataset", "mhw_composite",
-           "CompositeDataset", "open_series",
+           "CompositeDataset", "lag_correlation", "LagCorrelationDataset", "open_series",
            "threshold_file", "detrend", "DetrendSpec", "FitDataset"]
 __version__ = "0.1.0"

@@ -8,6 +8,7 @@ _mod = None
 _stress = None
 _regress = None
 _composite = None
+_lagcorr = None
 _err = None
 
 
@@ -68,6 +69,19 @@ def hip_composite():
         except ImportError as e:  # pragma: no cover - build problem
             raise HipExtensionMissing(f"cannot import xmhw_amd._xmhw_hip_composite: {e}") from e
     return _composite
+
+
+def hip_lagcorr():
+    """Return the pybind11 module ``xmhw_amd._xmhw_hip_lagcorr`` (the bindings of lag_correlation()), loaded as
+    hip_stress() loads its module, or raise.  It raises the exception classes of ``_xmhw_hip``."""
+    global _lagcorr
+    if _lagcorr is None:
+        hip()
+        try:
+            _lagcorr = _RetryOnNoMem(importlib.import_module("xmhw_amd._xmhw_hip_lagcorr"))
+        except ImportError as e:  # pragma: no cover - build problem
+            raise HipExtensionMissing(f"cannot import xmhw_amd._xmhw_hip_lagcorr: {e}") from e
+    return _lagcorr
 
 
 class _RetryOnNoMem:

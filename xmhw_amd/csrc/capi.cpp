@@ -1037,6 +1037,45 @@ int composite_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const d
                      "composite_accumulate launch");
 }
 
+static std::atomic<int> g_lag_corr_block{0};    // steps a workgroup takes per block, 0 = automatic (xmhw_set_lag_corr_block)
+
+static int lag_corr_check_shape(int32_t K, int32_t L, int32_t shift_x, int32_t shift_y, int64_t Tn, int64_t C) {
+    if (K < 1 || K > xmhw::kLagCorrMaxClasses)
+        return fail(XMHW_ERR_UNSUPPORTED, "lag_corr: K must be in [1, " + std::to_string(xmhw::kLagCorrMaxClasses) + "]");
+    if (L < 0 || L > xmhw::kLagCorrMaxLag)
+        return fail(XMHW_ERR_UNSUPPORTED, "lag_corr: max_lag must be in [0, " + std::to_string(xmhw::kLagCorrMaxLag) + "]");
+    if (shift_x < 0 || shift_x > xmhw::kLagCorrMaxShift || shift_y < 0 || shift_y > xmhw::kLagCorrMaxShift)
+        return fail(XMHW_ERR_UNSUPPORTED, "lag_corr: shifts must be in [0, " + std::to_string(xmhw::kLagCorrMaxShift) + "]");
+    if (Tn >= xmhw::kLagCorrMaxSteps) return fail(XMHW_ERR_UNSUPPORTED, "lag_corr: 2^17 steps and more");
+    if (C > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "lag_corr: 2^31 cells and more");
+    return XMHW_OK;
+}
+
+template <typename T>
+int lag_corr_accumulate(const T* x, int64_t ldx, const T* y, int64_t ldy, int64_t Tn, int64_t C, const double* base_x,
+                        int64_t ldbx, const double* base_y, int64_t ldby, int64_t Dr, const int32_t* row_of_t, int32_t shift_x,
+                        int32_t shift_y, const int32_t* class_of_t, int32_t K, int32_t max_lag, int32_t* n, int64_t* sx,
+                        int64_t* sy, int64_t* sxx, int64_t* syy, int64_t* sxy, int64_t ldo, int64_t* n_range, void* stream) {
+    if (lag_corr_check_shape(K, max_lag, shift_x, shift_y, Tn, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (Tn < 0 || C < 0 || ldx < C || ldy < C || ldbx < C || ldby < C || ldo < C || Dr < 1)
+        return fail(XMHW_ERR_INVALID, "bad T/C/ldx/ldy/ldbx/ldby/ldo/D");
+    if (Tn > 0 && (!class_of_t || !row_of_t)) return fail(XMHW_ERR_INVALID, "NULL host table");
+    if (int rc = check_labels(class_of_t, Tn, -1, K, kClassesOutside)) return rc;
+    if (int rc = check_labels(row_of_t, Tn, 0, Dr, kRowsOutside)) return rc;
+    if (C == 0 || Tn == 0) return XMHW_OK;
+    if (!x || !y || !base_x || !base_y || !n || !sx || !sy || !sxx || !syy || !sxy || !n_range)
+        return fail(XMHW_ERR_INVALID, "NULL buffer");
+    RowsRef rows;
+    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
+    RowsRef classes;                                   // the same content-keyed cache: one more int32[T] table
+    if (int rc = upload_table(class_of_t, Tn, "class table upload", &classes)) return rc;
+    return status_of(xmhw::launch_lag_corr_accumulate<T>(x, ldx, y, ldy, Tn, C, base_x, ldbx, base_y, ldby, Dr, rows->d_rows,
+                                                         shift_x, shift_y, classes->d_rows, K, max_lag,
+                                                         g_lag_corr_block.load(), n, sx, sy, sxx, syy, sxy, ldo, n_range,
+                                                         static_cast<hipStream_t>(stream)),
+                     "lag_corr_accumulate launch");
+}
+
 template <typename T>
 int event_stats_sparse(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* seas, const double* thresh,
                        int64_t ldc, const int32_t* row_of_t, int32_t negate, int64_t n_events, double* table,
@@ -2390,6 +2429,37 @@ int xmhw_composite_accumulate_f64(const double* ts, int64_t T, int64_t C, int64_
                                   int64_t* ss, int64_t ldo, int64_t* n_range, void* stream) {
     return composite_accumulate<double>(ts, T, C, ld, base, ldb, Dr, row_of_t, shift, anchor_bits, lda, class_of_t, K, before,
                                         after, n, s, ss, ldo, n_range, stream);
+}
+
+int xmhw_set_lag_corr_block(int32_t steps) {
+    if (steps < 0) return fail(XMHW_ERR_INVALID, "steps must be >= 0");
+    g_lag_corr_block = steps;
+    return XMHW_OK;
+}
+int xmhw_lag_corr_init(int32_t K, int32_t max_lag, int64_t C, int32_t* n, int64_t* sx, int64_t* sy, int64_t* sxx, int64_t* syy,
+                       int64_t* sxy, int64_t ldo, int64_t* n_range, void* stream) {
+    if (lag_corr_check_shape(K, max_lag, 0, 0, 1, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
+    if (!n_range || (C > 0 && (!n || !sx || !sy || !sxx || !syy || !sxy))) return fail(XMHW_ERR_INVALID, "NULL output buffer");
+    return status_of(xmhw::launch_lag_corr_init(K, max_lag, C, n, sx, sy, sxx, syy, sxy, ldo, n_range,
+                                                static_cast<hipStream_t>(stream)),
+                     "lag_corr_init");
+}
+int xmhw_lag_corr_accumulate_f32(const float* x, int64_t ldx, const float* y, int64_t ldy, int64_t T, int64_t C,
+                                 const double* base_x, int64_t ldbx, const double* base_y, int64_t ldby, int64_t Dr,
+                                 const int32_t* row_of_t, int32_t shift_x, int32_t shift_y, const int32_t* class_of_t, int32_t K,
+                                 int32_t max_lag, int32_t* n, int64_t* sx, int64_t* sy, int64_t* sxx, int64_t* syy, int64_t* sxy,
+                                 int64_t ldo, int64_t* n_range, void* stream) {
+    return lag_corr_accumulate<float>(x, ldx, y, ldy, T, C, base_x, ldbx, base_y, ldby, Dr, row_of_t, shift_x, shift_y,
+                                      class_of_t, K, max_lag, n, sx, sy, sxx, syy, sxy, ldo, n_range, stream);
+}
+int xmhw_lag_corr_accumulate_f64(const double* x, int64_t ldx, const double* y, int64_t ldy, int64_t T, int64_t C,
+                                 const double* base_x, int64_t ldbx, const double* base_y, int64_t ldby, int64_t Dr,
+                                 const int32_t* row_of_t, int32_t shift_x, int32_t shift_y, const int32_t* class_of_t, int32_t K,
+                                 int32_t max_lag, int32_t* n, int64_t* sx, int64_t* sy, int64_t* sxx, int64_t* syy, int64_t* sxy,
+                                 int64_t ldo, int64_t* n_range, void* stream) {
+    return lag_corr_accumulate<double>(x, ldx, y, ldy, T, C, base_x, ldbx, base_y, ldby, Dr, row_of_t, shift_x, shift_y,
+                                       class_of_t, K, max_lag, n, sx, sy, sxx, syy, sxy, ldo, n_range, stream);
 }
 
 int xmhw_synth_sst_f32(float* ts, int64_t T, int64_t C, int64_t ld, int64_t cell0, uint64_t seed,

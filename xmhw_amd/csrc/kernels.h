@@ -385,7 +385,7 @@ hipError_t launch_track_intensity_accumulate(const T* ts, int64_t Tn, int64_t n,
 hipError_t launch_track_intensity_finish(int64_t L, double* intensity_max, hipStream_t stream);
 
 // The frame of a class reduction: the kernels below that reduce over TIME and keep the cell (class_days_accumulate,
-// class_sums_accumulate, heat_stress_accumulate, index_regress_accumulate, composite_accumulate -- which keeps no addends
+// class_sums_accumulate, heat_stress_accumulate, index_regress_accumulate, lag_corr_accumulate, composite_accumulate -- which keeps no addends
 // and adds every (anchor, offset) pair directly; displacement_accumulate with a grid point and
 // cooccur_accumulate with 64-step words in the place of the cell and the step).  Lane = cell, consecutive lanes on consecutive cells; a workgroup
 // is 256 cells x a block of steps (stage_blocks.h has the block lengths); class_of_t[t] and row_of_t[t] are uniform over
@@ -549,6 +549,27 @@ hipError_t launch_composite_accumulate(const T* ts, int64_t Tn, int64_t C, int64
                                        int64_t lda, const int32_t* class_of_t, int32_t K, int32_t before, int32_t after,
                                        int64_t block_steps, int32_t* n, int64_t* s, int64_t* ss, int64_t ldo,
                                        int64_t* n_range, hipStream_t stream);
+
+// lag_correlation() (kernels_lagcorr.hip, lag_ring.h): per cell, class of the LATER step and lag l in [0, L], the sums over
+// the pairs (qx(t), qy(t - l)) whose two anomalies are valid -- n int32, sx, sy, sxx, syy, sxy int64, [K][L + 1][ldo],
+// ADDED; the definition is in include/xmhw_amd.h, "lag_correlation()".  y may be x.  n_range[0] counts the steps of class
+// >= 0 whose ax is not NaN and out of range, n_range[1] the steps of any class whose ay is.  row_of_t and class_of_t are
+// DEVICE arrays here.  block_steps: the steps a workgroup takes per block, 0 = automatic; same results for every value.
+constexpr int kLagCorrMaxLag = 63;                   // one validity bit per lag in a 64-bit mask
+constexpr int kLagCorrMaxClasses = 64;
+constexpr int kLagCorrMaxSteps = 1 << 17;            // T below it: 2^17 * 2^46 = 2^63
+constexpr int kLagCorrBits = 16;
+constexpr int kLagCorrRangeBits = 7;
+constexpr int kLagCorrMaxShift = 24;
+hipError_t launch_lag_corr_init(int32_t K, int32_t L, int64_t C, int32_t* n, int64_t* sx, int64_t* sy, int64_t* sxx,
+                                int64_t* syy, int64_t* sxy, int64_t ldo, int64_t* n_range, hipStream_t stream);
+template <typename T>
+hipError_t launch_lag_corr_accumulate(const T* x, int64_t ldx, const T* y, int64_t ldy, int64_t Tn, int64_t C,
+                                      const double* base_x, int64_t ldbx, const double* base_y, int64_t ldby, int64_t Dr,
+                                      const int32_t* row_of_t, int32_t shift_x, int32_t shift_y, const int32_t* class_of_t,
+                                      int32_t K, int32_t L, int64_t block_steps, int32_t* n, int64_t* sx, int64_t* sy,
+                                      int64_t* sxx, int64_t* syy, int64_t* sxy, int64_t ldo, int64_t* n_range,
+                                      hipStream_t stream);
 
 // file bytes -> samples (kernels_ingest.hip): raw_type = item size of the stored type (2 int16, 4 float32,
 // 8 float64), swap = the file is big-endian, optional scale/offset (CF packing) and fill value -> NaN

@@ -72,6 +72,22 @@ static inline int64_t composite_auto_block(int64_t Tn, int64_t C, int64_t D) {
     return stage_auto_block(Tn, ceil_div(C, kStageThreads), Tn / 256, 512, 1);
 }
 
+// lag_correlation(), lags 0 .. L in groups of kLagCorrGroup (grid.z).  A block clears its ring and reads the L steps before
+// it again, for every lag group, and reduces nothing from them: blocks of 16 L steps and more keep that share below 1/16,
+// and of 256 steps and more keep the flushes rare.  Long blocks measured faster on a grid that fills the chip by its cells
+// alone (profiles/r29_lag_corr_bench.json: blocks of 4,096 steps beat 512 by 2 % at 32 lags and by 4 % at 64 and 256 by
+// 6 % and 10 %; one block over 14,610 steps is 2 % slower than 4,096), so about 4,096 steps is the most a block takes, as
+// in heat_stress(); a slab whose workgroups x lag groups do not fill the chip with such blocks splits the time axis
+// further, until about 2048 workgroups exist.
+constexpr int kLagCorrGroup = 8;                     // lags per workgroup up to 8 lags: 11 registers of addends each
+constexpr int kLagCorrWideGroup = 16;                // ... and from 9 lags on: half the passes at half the occupancy
+static inline int64_t lag_corr_group(int64_t L) { return L >= kLagCorrGroup ? kLagCorrWideGroup : kLagCorrGroup; }
+static inline int64_t lag_corr_groups(int64_t L) { return L / lag_corr_group(L) + 1; }
+static inline int64_t lag_corr_auto_block(int64_t Tn, int64_t C, int64_t L) {
+    const int64_t least = 16 * L > 256 ? 16 * L : 256;
+    return stage_auto_block(Tn, ceil_div(C, kStageThreads) * lag_corr_groups(L), Tn / least, least > 4096 ? least : 4096, 1);
+}
+
 // mhw_displacement(): a workgroup is four waves of 64 longitudes of one grid row.  One block over the steps keeps the
 // flushes rare; a grid whose waves do not fill the chip splits the steps until about 2048 workgroups exist.
 static inline int64_t displacement_auto_block(int64_t nt, int64_t ny, int64_t nx) {
