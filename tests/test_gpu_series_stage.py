@@ -2,21 +2,33 @@
 one of them all land, land in the first and in the last, climatologies compacted on the host or on the device (there on
 the smaller grid threshold() hands over), with and without maxPadLength.  Every leg equals the dense stage on the
 host-compacted inputs in one batch and the oracle, bit for bit; every refusal keeps its text and leaks no buffer.
+The stages whose accumulators are sliced by column through series_stage.Accumulators -- heat_stress_grid(),
+class_sums_grid(), regress_grid(), composite_grid() and lag_corr_grid() -- walk the same five slabs (k0 != 0, a skipped
+slab, a ragged last slab, C < N), without padding, and meet the same two references.
 
 The shape.  T = 203 (no multiple of 64: the last bit word is ragged), N = 240 float32 grid points, D = 37.  A slab cell
 costs device._grid_batch() 203 * 4 * 3 + 203 * 4 (raw, decoded and compacted copy; the next slab's upload) plus the
 stage's own extra, 6 * 37 * 8 + 203 // 4 + 64 for coverage and class days (5138 in all) and 6 * 37 * 8 + 64 for track
-intensity (5088): a budget of 50 such cells gives the slabs [0, 50), [50, 100), [100, 150), [150, 200), [200, 240)."""
+intensity (5088): a budget of 50 such cells gives the slabs [0, 50), [50, 100), [100, 150), [150, 200), [200, 240).
+The column-sliced stages add 4 * Dr * 8 + 64 for a base of Dr rows (37, or the one land row of the class sums), the
+composite T // 8 more for its anchor bitmap and the lag correlation 2 * 203 * 4 for the second field."""
 import functools
 
 import numpy as np
 import numpy.testing as npt
 import pytest
 
+import composite_cases as cpc
+import composite_oracle as cpo
 import coverage_cases as cc
 import coverage_oracle as co
 import days_by_cases as dc
 import days_by_oracle as dbo
+import heat_stress_cases as hc
+import heat_stress_oracle as ho
+import index_regression_cases as irc
+import index_regression_oracle as iro
+import lag_correlation_oracle as lco
 import pad_oracle as po
 import track_intensity_cases as tc
 import track_intensity_oracle as tio
@@ -25,7 +37,9 @@ pytestmark = pytest.mark.gpu
 
 T, NY, NX, D, SLAB = 203, 12, 20, 37, 50
 N = NY * NX
-EXTRA = {"coverage": 6 * D * 8 + T // 4 + 64, "days_by": 6 * D * 8 + T // 4 + 64, "track_intensity": 6 * D * 8 + 64}
+EXTRA = {"coverage": 6 * D * 8 + T // 4 + 64, "days_by": 6 * D * 8 + T // 4 + 64, "track_intensity": 6 * D * 8 + 64,
+         "heat_stress": 4 * D * 8 + 64, "class_sums": 4 * 1 * 8 + 64, "regress": 4 * D * 8 + 64,
+         "composite": 4 * D * 8 + T // 8 + 64, "lag_corr": 4 * D * 8 + 64 + 2 * T * 4}
 BUDGET = {k: (T * 4 * 3 + T * 4 + v) * SLAB for k, v in EXTRA.items()}
 TIME = np.datetime64("2001-01-01") + np.arange(T).astype("timedelta64[D]")
 R = 3
@@ -205,6 +219,172 @@ def test_track_intensity_grid_over_five_slabs(gpu, pad3, stacked, padded):
     assert got["n_range"] == 0 and got["n_bad"] == 0
     tio.same_integers(got, track_intensity_cells(c["ts_c"], c["seas_c"], c["thresh_c"], c["doy"], c["doys"], rows, wi, pad=pad))
     tio.same_integers(got, intensity_want(padded))
+
+
+# ---- the stages with column-sliced accumulators ----
+
+CLIMS = [pytest.param(False, id="compact"), pytest.param(True, id="stacked")]
+WINDOW, H0, AT = 30, 0.5, np.array([0, 100, T - 1])
+X0 = 15.0
+J, BEFORE, AFTER, LAGS = 3, 2, 3, (-3, 5)
+
+
+def slab_columns(keep):
+    """the range of compact columns of every slab that is not all land"""
+    k = np.concatenate(([0], np.cumsum(keep)))
+    return [(int(k[lo]), int(k[min(lo + SLAB, N)])) for lo in range(0, N, SLAB) if keep[lo:lo + SLAB].any()]
+
+
+def counted_in_every_slab(n, c):
+    """a case that counts nothing in the columns of some slab cannot tell whether that slab's pointers were right"""
+    cols = slab_columns(c["keep"])
+    assert len(cols) == 4 and cols[0][0] == 0 and cols[-1][1] == c["C"] and cols[1][0] == cols[0][1] == 46
+    for a, b in cols:
+        assert (np.asarray(n)[..., a:b] != 0).any(), (a, b)
+
+
+def same_as_both(got, dense, want, names):
+    assert len(got) == len(dense) == len(want) == len(names)
+    for a, one, w, name in zip(got, dense, want, names):
+        assert a.dtype == one.dtype and a.shape == np.shape(w), name
+        npt.assert_array_equal(a, one, err_msg=name)
+        npt.assert_array_equal(a, w, err_msg=name)
+
+
+def with_n_range_zero(oracle, *args):
+    counters = {}
+    out = oracle(*args, counters=counters)
+    assert counters and not any(counters.values())
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def stress_want():
+    c = case(False)
+    classes, K = hc.per_year(T)
+    args = (c["doy"], c["doys"], classes, K, WINDOW, H0, hc.levels(2), AT)
+    want = with_n_range_zero(ho.heat_stress_cells, c["ts_c"], c["seas_c"], *args)
+    hc.check_case(dict(zip(("counts", "hsum_q", "peak_q", "peak_t", "snap_q"), want)))
+    counted_in_every_slab(want[0][:, 1], c)                   # hot steps
+    counted_in_every_slab(want[4], c)
+    return args, want
+
+
+@pytest.mark.parametrize("stacked", CLIMS)
+def test_heat_stress_grid_over_five_slabs(gpu, stacked):
+    from xmhw_amd.heat_stress import heat_stress_cells, heat_stress_grid
+    c = case(False)
+    args, want = stress_want()
+    se, _, _ = clims(c, stacked)
+    *got, keep = heat_stress_grid(c["ts"], False, se, *args, max_batch_bytes=BUDGET["heat_stress"], clim_stacked=stacked)
+    npt.assert_array_equal(keep, c["keep"])
+    same_as_both(got, heat_stress_cells(c["ts_c"], c["seas_c"], *args), want, ("counts", "hsum_q", "peak_q", "peak_t", "snap_q"))
+
+
+@functools.lru_cache(maxsize=None)
+def sums_want():
+    c = case(False)
+    want = with_n_range_zero(ho.class_sums_cells, c["ts_c"], c["classes"], c["K"], X0)
+    counted_in_every_slab(want[0], c)
+    counted_in_every_slab(want[1], c)
+    return want
+
+
+@pytest.mark.parametrize("stacked", CLIMS)
+def test_class_sums_grid_over_five_slabs(gpu, stacked):
+    from xmhw_amd.heat_stress import class_sums_cells, class_sums_grid
+    c = case(False)
+    land = np.where(c["keep"], 0.0, np.nan)[None]
+    land = np.ascontiguousarray(land[:, c["lines"]]) if stacked else np.zeros((1, c["C"]))
+    *got, keep = class_sums_grid(c["ts"], False, land, c["classes"], c["K"], X0, max_batch_bytes=BUDGET["class_sums"],
+                                 clim_stacked=stacked)
+    npt.assert_array_equal(keep, c["keep"])
+    same_as_both(got, class_sums_cells(c["ts_c"], c["classes"], c["K"], X0), sums_want(), ("n_valid", "sum_q"))
+
+
+@functools.lru_cache(maxsize=None)
+def regress_want():
+    c = case(False)
+    classes, K = irc.runs(T)
+    args = (c["doy"], c["doys"], classes, K, irc.predictors(T, J, 5))
+    want = with_n_range_zero(iro.regress_cells, c["ts_c"], c["seas_c"], *args)
+    irc.check_case(dict(zip(iro.FIELDS, want)))
+    for name in ("n", "saz", "mz"):
+        counted_in_every_slab(want[iro.FIELDS.index(name)], c)
+    return args, want
+
+
+@pytest.mark.parametrize("stacked", CLIMS)
+def test_regress_grid_over_five_slabs(gpu, stacked):
+    from xmhw_amd.index_regression import FIELDS, regress_cells, regress_grid
+    c = case(False)
+    args, want = regress_want()
+    se, _, _ = clims(c, stacked)
+    *got, keep = regress_grid(c["ts"], False, se, *args, max_batch_bytes=BUDGET["regress"], clim_stacked=stacked)
+    npt.assert_array_equal(keep, c["keep"])
+    assert got[5].shape == (args[3], J, c["C"])
+    same_as_both(got, regress_cells(c["ts_c"], c["seas_c"], *args), want, FIELDS)
+
+
+@functools.lru_cache(maxsize=None)
+def composite_want():
+    """(the anchor table of the ocean cells, the arguments after the cells, the oracle's arrays)"""
+    c = case(False)
+    A = cpc.anchor_columns(T, c["C"], BEFORE + AFTER + 1)
+    for a, b in slab_columns(c["keep"]):
+        assert A[:, a:b].any(), "an anchor in every slab"
+    view = cpc.table_of(A)
+    classes, K = cpc.every_step(T)
+    args = (classes, K, BEFORE, AFTER, 0)
+    want = with_n_range_zero(cpo.composite_cells, c["ts_c"], c["seas_c"], c["doy"], c["doys"], view, np.arange(c["C"]), *args)
+    for a in want:
+        counted_in_every_slab(a, c)
+    return view, args, want
+
+
+@pytest.mark.parametrize("stacked", CLIMS)
+def test_composite_grid_over_five_slabs(gpu, stacked):
+    from xmhw_amd.composite import FIELDS, composite_cells, composite_grid
+    c = case(False)
+    view, args, want = composite_want()
+    se, _, _ = clims(c, stacked)
+    of_point = np.zeros(N, dtype=np.int64)                    # the table cell of every grid point; land points are not read
+    of_point[c["keep"]] = np.arange(c["C"])
+    *got, keep = composite_grid(c["ts"], False, se, c["doy"], c["doys"], view, of_point, *args,
+                                max_batch_bytes=BUDGET["composite"], clim_stacked=stacked)
+    npt.assert_array_equal(keep, c["keep"])
+    dense = composite_cells(c["ts_c"], c["seas_c"], c["doy"], c["doys"], view, np.arange(c["C"]), *args)
+    same_as_both(got, dense, want, FIELDS)
+
+
+@functools.lru_cache(maxsize=None)
+def lag_want():
+    """(y on the whole grid: no land of its own but NaN gaps and one all-NaN ocean cell of x, the arguments, the oracle)"""
+    c = case(False)
+    y = cc.synthetic(T, N, np.float32, seed=23, D=D, nan_frac=0.03)["ts"] + np.float32(0.4) * np.nan_to_num(c["ts"])
+    y[:, 120] = np.nan
+    assert c["keep"][120] and y.dtype == np.float32 and not np.isnan(y[:, ~c["keep"]]).all()
+    classes = ((np.arange(T) // 17) % 2).astype(np.int32)
+    args = (c["doy"], c["doys"], classes, 2, *LAGS)
+    want = with_n_range_zero(lco.lag_corr_cells, c["ts_c"], y[:, c["keep"]], c["seas_c"], c["thresh_c"], *args)
+    assert want[0].shape == (2, LAGS[1] - LAGS[0] + 1, c["C"])
+    for a in want:
+        counted_in_every_slab(a[:, :-LAGS[0]], c)             # the second pass: the negative lags
+        counted_in_every_slab(a[:, -LAGS[0]:], c)
+    assert not np.array_equal(want[1][:, 0], want[2][:, 0])   # sx and sy differ: the roles are told apart
+    return y, args, want
+
+
+@pytest.mark.parametrize("stacked", CLIMS)
+def test_lag_corr_grid_over_five_slabs(gpu, stacked):
+    from xmhw_amd.lag_correlation import FIELDS, lag_corr_cells, lag_corr_grid
+    c = case(False)
+    y, args, want = lag_want()
+    se, th, _ = clims(c, stacked)
+    *got, keep = lag_corr_grid(c["ts"], False, y, se, th, *args, max_batch_bytes=BUDGET["lag_corr"], clim_stacked=stacked)
+    npt.assert_array_equal(keep, c["keep"])
+    dense = lag_corr_cells(c["ts_c"], np.ascontiguousarray(y[:, c["keep"]]), c["seas_c"], c["thresh_c"], *args)
+    same_as_both(got, dense, want, FIELDS)
 
 
 # ---- the refusals ----

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Wall time of the three public series stages -- mhw_coverage(), mhw_days_by(), mhw_track_intensity() -- on a grid that
-goes through the device in several slabs: one JSON line.  What it is for: the host time per slab of the grid walker
+"""Wall time of the public series stages -- mhw_coverage(), mhw_days_by(), mhw_track_intensity(), heat_stress(),
+index_regression(), mhw_composite(), lag_correlation() -- on a grid that goes through the device in several slabs: one
+JSON line.  What it is for: the host time per slab of the grid walker
 (xmhw_amd/series_stage.py), which no kernel timing shows.
 
     python tools/bench_series_stage.py [--grid 160x320] [--tile 1] [--years 10] [--slabs 10] [--reps 3] [--package DIR]
@@ -9,7 +10,10 @@ goes through the device in several slabs: one JSON line.  What it is for: the ho
 A synthetic float32 (time, lat, lon) series with 20 % land, AR(1) anomalies around a 366-row climatology; detect(),
 mhw_objects() and mhw_tracks() run once, untimed, for the track-intensity call.  ``--tile K`` repeats the grid K times
 along the longitude (a larger series at the cost of a copy, not of K times the random numbers).  ``max_batch_bytes`` is set so that
-device._grid_batch() cuts the grid into --slabs slabs (the number it gives is reported).  Each stage: one warm-up call,
+device._grid_batch() cuts the grid into --slabs slabs for the first three stages (the number it gives is reported; a stage
+with fewer bytes a cell takes a slab or two fewer, lag_correlation() with its second field a few more).  heat_stress()
+and index_regression() (one index, lags 0, 30, 60) take ``se`` as their base, mhw_composite() the detection's events
+(30 steps either side), lag_correlation() the series against its own negation with lags -5 .. 10.  Each stage: one warm-up call,
 then the median of --reps calls, time.perf_counter() around the public function.  ``--package DIR`` imports xmhw_amd
 from DIR instead of this checkout (an A/B of two checkouts with the same compiled library); ``--once`` makes one call
 of each stage (``--only``: of that stage) and times nothing, for a kernel trace."""
@@ -23,6 +27,8 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+STAGES = ("mhw_coverage", "mhw_days_by", "mhw_track_intensity", "heat_stress", "index_regression", "mhw_composite",
+          "lag_correlation")
 
 
 def grid_case(ny, nx, years, tile=1, seed=0):
@@ -62,7 +68,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--package", default=ROOT)
     ap.add_argument("--once", action="store_true")
-    ap.add_argument("--only", default=None, choices=["mhw_coverage", "mhw_days_by", "mhw_track_intensity"])
+    ap.add_argument("--only", default=None, choices=STAGES)
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.package))
     import xmhw_amd
@@ -80,14 +86,23 @@ def main():
     slabs = -(-N // _grid_batch(stacked, budget, per_cell_extra=extra))
     res = {"bench": "series_stage", "package": os.path.dirname(os.path.abspath(xmhw_amd.__file__)), "grid": [ny, nx], "T": T,
            "dtype": "float32", "max_batch_bytes": budget, "slabs": slabs, "reps": a.reps, "seconds": {}}
-    if a.only in (None, "mhw_track_intensity"):
+    if a.only in (None, "mhw_track_intensity", "mhw_composite"):
         mhw = xmhw_amd.detect(temp, th, se)
+        res.update(ocean_cells=int(mhw.n_cells), events=int(mhw.n_events))
+    if a.only in (None, "mhw_track_intensity"):
         obj = xmhw_amd.mhw_objects(mhw)
         tr = xmhw_amd.mhw_tracks(mhw, obj)
-        res.update(ocean_cells=int(mhw.n_cells), events=int(mhw.n_events), objects=int(obj.n_objects))
+        res.update(objects=int(obj.n_objects))
+    index = {"index": np.cumsum(np.random.default_rng(1).normal(0, 0.1, T))}
+    other = xmhw_amd.GridSeries(-temp.values, temp.dims, temp.coords) if a.only in (None, "lag_correlation") else None
     calls = {"mhw_coverage": lambda: xmhw_amd.mhw_coverage(temp, th, se, weights="coslat", max_batch_bytes=budget),
              "mhw_days_by": lambda: xmhw_amd.mhw_days_by(temp, th, se, classes="month", max_batch_bytes=budget),
-             "mhw_track_intensity": lambda: xmhw_amd.mhw_track_intensity(temp, th, se, mhw, obj, tr, max_batch_bytes=budget)}
+             "mhw_track_intensity": lambda: xmhw_amd.mhw_track_intensity(temp, th, se, mhw, obj, tr, max_batch_bytes=budget),
+             "heat_stress": lambda: xmhw_amd.heat_stress(temp, se, max_batch_bytes=budget),
+             "index_regression": lambda: xmhw_amd.index_regression(temp, se, index, lags=(0, 30, 60), max_batch_bytes=budget),
+             "mhw_composite": lambda: xmhw_amd.mhw_composite(temp, se, mhw, max_batch_bytes=budget),
+             "lag_correlation": lambda: xmhw_amd.lag_correlation(temp, other, se, None, lags=(-5, 10),
+                                                                 max_batch_bytes=budget)}
     for name, call in calls.items():
         if a.only not in (None, name):
             continue

@@ -4,84 +4,53 @@ import importlib
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_mod = None
-_stress = None
-_regress = None
-_composite = None
-_lagcorr = None
-_err = None
+_loaded = {}
 
 
 class HipExtensionMissing(ImportError):
     pass
 
 
+def _extension(name):
+    """The pybind11 module ``xmhw_amd.<name>`` behind the out-of-memory retry, loaded once, or raise.  A module of stage
+    bindings ("Entry layer") raises the exception classes of ``_xmhw_hip``, which is loaded first."""
+    if name not in _loaded:
+        if name != "_xmhw_hip":
+            hip()
+        try:
+            _loaded[name] = _RetryOnNoMem(importlib.import_module(f"xmhw_amd.{name}"))
+        except ImportError as e:  # pragma: no cover - build problem
+            raise HipExtensionMissing(f"cannot import xmhw_amd.{name}: {e}") from e
+    return _loaded[name]
+
+
 def hip():
     """Return the pybind11 module ``xmhw_amd._xmhw_hip`` or raise."""
-    global _mod, _err
-    if _mod is not None:
-        return _mod
-    if not os.path.exists(os.path.join(_HERE, "libxmhw_amd.so")):
+    if "_xmhw_hip" not in _loaded and not os.path.exists(os.path.join(_HERE, "libxmhw_amd.so")):
         raise HipExtensionMissing(
             "xmhw_amd/libxmhw_amd.so not found: build it with "
             "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C xmhw_amd/csrc`")
-    try:
-        _mod = _RetryOnNoMem(importlib.import_module("xmhw_amd._xmhw_hip"))
-    except ImportError as e:  # pragma: no cover - build problem
-        raise HipExtensionMissing(f"cannot import xmhw_amd._xmhw_hip: {e}") from e
-    return _mod
+    return _extension("_xmhw_hip")
 
 
 def hip_stress():
-    """Return the pybind11 module ``xmhw_amd._xmhw_hip_stress`` (the bindings of heat_stress(); DESIGN.md, "Entry
-    layer") behind the same out-of-memory retry, or raise.  It raises the exception classes of ``_xmhw_hip``."""
-    global _stress
-    if _stress is None:
-        hip()
-        try:
-            _stress = _RetryOnNoMem(importlib.import_module("xmhw_amd._xmhw_hip_stress"))
-        except ImportError as e:  # pragma: no cover - build problem
-            raise HipExtensionMissing(f"cannot import xmhw_amd._xmhw_hip_stress: {e}") from e
-    return _stress
+    """the bindings of heat_stress()"""
+    return _extension("_xmhw_hip_stress")
 
 
 def hip_regress():
-    """Return the pybind11 module ``xmhw_amd._xmhw_hip_regress`` (the bindings of index_regression()), loaded as
-    hip_stress() loads its module, or raise.  It raises the exception classes of ``_xmhw_hip``."""
-    global _regress
-    if _regress is None:
-        hip()
-        try:
-            _regress = _RetryOnNoMem(importlib.import_module("xmhw_amd._xmhw_hip_regress"))
-        except ImportError as e:  # pragma: no cover - build problem
-            raise HipExtensionMissing(f"cannot import xmhw_amd._xmhw_hip_regress: {e}") from e
-    return _regress
+    """the bindings of index_regression()"""
+    return _extension("_xmhw_hip_regress")
 
 
 def hip_composite():
-    """Return the pybind11 module ``xmhw_amd._xmhw_hip_composite`` (the bindings of mhw_composite()), loaded as
-    hip_stress() loads its module, or raise.  It raises the exception classes of ``_xmhw_hip``."""
-    global _composite
-    if _composite is None:
-        hip()
-        try:
-            _composite = _RetryOnNoMem(importlib.import_module("xmhw_amd._xmhw_hip_composite"))
-        except ImportError as e:  # pragma: no cover - build problem
-            raise HipExtensionMissing(f"cannot import xmhw_amd._xmhw_hip_composite: {e}") from e
-    return _composite
+    """the bindings of mhw_composite()"""
+    return _extension("_xmhw_hip_composite")
 
 
 def hip_lagcorr():
-    """Return the pybind11 module ``xmhw_amd._xmhw_hip_lagcorr`` (the bindings of lag_correlation()), loaded as
-    hip_stress() loads its module, or raise.  It raises the exception classes of ``_xmhw_hip``."""
-    global _lagcorr
-    if _lagcorr is None:
-        hip()
-        try:
-            _lagcorr = _RetryOnNoMem(importlib.import_module("xmhw_amd._xmhw_hip_lagcorr"))
-        except ImportError as e:  # pragma: no cover - build problem
-            raise HipExtensionMissing(f"cannot import xmhw_amd._xmhw_hip_lagcorr: {e}") from e
-    return _lagcorr
+    """the bindings of lag_correlation()"""
+    return _extension("_xmhw_hip_lagcorr")
 
 
 class _RetryOnNoMem:

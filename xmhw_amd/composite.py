@@ -24,14 +24,13 @@ composite_cells() (a compact host series) and composite_grid() (a stacked grid, 
 """
 import numpy as np
 
-from ._lib import hip, hip_composite
-from .cooccurrence import _same_axis, check_view
-from .days_by import class_labels
+from ._lib import hip_composite
 from .device import DeviceScope, as_xmhw_errors
 from .exception import XmhwException
-from .heat_stress import _base_series, _constant_rows
-from .index_regression import _t_two_sided
-from .series_stage import CellFrame, check_class_ids, dense_ids, grid_layout, run, walk_cells, walk_grid, walk_stage
+from .series_stage import (Accumulators, base_series, cell_stage, check_class_ids, check_same_frame, check_steps, check_view,
+                           class_labels, class_result_labels, dense_ids, grid_layout, ocean_mask, run_cells, run_grid,
+                           stage_attrs, zero_base)
+from .trend import p_two_sided
 
 MAX_OFFSETS = 128               # XMHW_COMPOSITE_MAX_OFFSETS (include/xmhw_amd.h)
 MAX_CLASSES = 64                # XMHW_COMPOSITE_MAX_CLASSES
@@ -63,11 +62,6 @@ def check_window(before, after, shift):
     if not 0 <= shift <= MAX_SHIFT:
         raise XmhwException(f"shift should be in [0, {MAX_SHIFT}], got {shift}")
     return before, after, shift
-
-
-def check_steps(T):
-    if T >= MAX_STEPS:
-        raise XmhwException(f"mhw_composite handles fewer than 2**17 time steps, got {T}")
 
 
 def check_result_bytes(K, D, C, max_result_bytes):
@@ -120,46 +114,39 @@ def table_cell_of_point(view, N):
 
 # ---- the device stage --------------------------------------------------------------------------------
 
-class _Accumulators:
+class _Accumulators(Accumulators):
     """One call's arguments, its anchor table on the device and its accumulators n, s, ss (K, D, C) with the range
-    counter.  Initialised by begin(); they live across the slabs, each slab rasterises its own anchor bitmap and adds
-    into its own column range, and they are read back once."""
+    counter; each slab rasterises its own anchor bitmap."""
+    range_texts = {"n_range": _RANGE_TEXT}
 
     def __init__(self, view, cells, classes, K, before, after, shift, max_result_bytes):
-        self.h, self.hc = hip(), hip_composite()
+        super().__init__()
+        self.hc = hip_composite()
         self.view, self.cells = view, np.ascontiguousarray(cells, dtype=np.int64)
         self.args = (classes, K)
         self.before, self.after, self.shift = check_window(before, after, shift)
         self.D = self.before + self.after + 1
         self.max_result_bytes = max_result_bytes
-        self.C = None
-        self._scope = DeviceScope()
-
-    def _shapes(self):
-        return {"n": ((self.K, self.D, self.C), np.int32), "s": ((self.K, self.D, self.C), np.int64),
-                "ss": ((self.K, self.D, self.C), np.int64)}
 
     def begin(self, T, C):
         """T steps, C ocean cells"""
-        check_steps(T)
+        check_steps(T, "mhw_composite")
         self.classes, self.K = check_class_ids(T, *self.args, MAX_CLASSES, "mhw_composite")
         check_view(self.view, self.cells, T, "events")
         check_result_bytes(self.K, self.D, C, self.max_result_bytes)
-        self.C, s, v = C, self._scope, self.view
-        some = v["n"] > 0
-        self.d_start = s.upload(v["start"] if some else np.zeros(1, np.int32))
+        s, v = self._scope, self.view
+        self.d_start = s.upload(v["start"] if v["n"] > 0 else np.zeros(1, np.int32))
         self.d_off = s.upload(v["offsets"])
-        self.buf = {k: s.alloc(max(int(np.prod(shape)), 1) * np.dtype(dt).itemsize) for k, (shape, dt) in self._shapes().items()}
-        self.count = s.alloc(8)
+        self.make(C, {k: ((self.K, self.D, C), np.int32 if k == "n" else np.int64) for k in FIELDS})
         with as_xmhw_errors(also="Unsupported"):
-            self.hc.composite_init(self.K, self.D, C, *(self.buf[k].ptr for k in FIELDS), C, self.count.ptr)
+            self.hc.composite_init(self.K, self.D, C, *self.ptrs(), C, self.count.ptr)
 
     def add_slab(self, slab):
         """One slab (series_stage.Slab), columns k0..k0+n-1 of the accumulators: the anchors of its cells are rasterised
         from the table, then the composite ADDS; the base is where the slab carries its climatologies."""
-        T, n, k0 = slab.T, slab.n, slab.k0
+        T, n = slab.T, slab.n
         W = (T + 63) // 64
-        ptrs = [self.buf[k].ptr + np.dtype(dt).itemsize * k0 for k, (_, dt) in self._shapes().items()]
+        ptrs = self.ptrs(slab.k0)
         with DeviceScope() as s:
             d_cell = s.upload(np.ascontiguousarray(slab.take(self.cells), dtype=np.int64))
             d_bits = s.alloc(8 * W * n)
@@ -169,17 +156,6 @@ class _Accumulators:
                                              self.shift, d_bits.ptr, n, self.classes, self.K, self.before, self.after, *ptrs,
                                              self.C, self.count.ptr)
             self.h.stream_sync(0)                       # the slab's series and bitmap are freed on the way out
-
-    def result(self):
-        self.h.stream_sync(0)
-        shapes = self._shapes()
-        if self.C == 0:
-            return tuple(np.zeros(shape, dt) for shape, dt in shapes.values()), 0
-        return (tuple(self.buf[k].to_array(shape, dt) for k, (shape, dt) in shapes.items()),
-                int(self.count.to_array((1,), np.int64)[0]))
-
-    def free(self):
-        self._scope.free()
 
 
 def _bytes_per_cell(T, isz, D):
@@ -194,10 +170,8 @@ def composite_cells(ts, base, doy, doys, view, cells, classes, K, before, after,
     all (K, D, C).  Cells go through the device in batches below max_batch_bytes; the sums are integers, so the batch
     size does not change a single bit.  Raises if a sample is out of range (module docstring); with ``counters`` (a dict)
     it stores ``n_range`` there instead."""
-    acc = _Accumulators(view, cells, classes, K, before, after, shift, max_result_bytes)
-    out, _ = walk_stage(acc, lambda a: walk_cells(ts, base, base, doy, doys, _bytes_per_cell, max_batch_bytes, pad,
-                                                  a.add_slab, a.begin), _RANGE_TEXT, counters)
-    return out
+    return run_cells(_Accumulators(view, cells, classes, K, before, after, shift, max_result_bytes), ts, base, base, doy, doys,
+                     _bytes_per_cell, max_batch_bytes, pad, counters)
 
 
 def composite_grid(stacked, anynans, base, doy, doys, view, cells, classes, K, before, after, shift=0, max_batch_bytes=None,
@@ -205,10 +179,9 @@ def composite_grid(stacked, anynans, base, doy, doys, view, cells, classes, K, b
     """composite_cells() for an UNCOMPACTED stacked host series (T, N), float or a packed int16 view: the land mask and
     the compaction run on the device slab by slab (series_stage.walk_grid); ``cells`` (N,) holds the table cell of every
     grid point and is compacted by each slab's land mask.  Returns the three arrays over the ocean cells and keep[N]."""
-    acc = _Accumulators(view, cells, classes, K, before, after, shift, max_result_bytes)
-    out, keep = walk_stage(acc, lambda a: walk_grid(stacked, anynans, base, base, doy, doys,
-                                                    lambda T, D: 4 * D * 8 + T // 8 + 64, max_batch_bytes, clim_stacked, pad,
-                                                    a.add_slab, begin=a.begin), _RANGE_TEXT, counters)
+    out, keep = run_grid(_Accumulators(view, cells, classes, K, before, after, shift, max_result_bytes), stacked, anynans,
+                         base, base, doy, doys, lambda T, D: 4 * D * 8 + T // 8 + 64, max_batch_bytes, clim_stacked, pad,
+                         counters)
     return out + (keep,)
 
 
@@ -255,7 +228,7 @@ class CompositeDataset:
         if self._p is None:
             dof = np.where(self.n < 2, np.nan, self.n.astype(np.float64) - 1.0)
             with np.errstate(invalid="ignore"):
-                self._p = np.frompyfunc(_t_two_sided, 2, 1)(self.t, dof).astype(np.float64)
+                self._p = p_two_sided(self.t, dof)
         return self._p
 
     def to_xarray(self):
@@ -289,61 +262,38 @@ def mhw_composite(field, base, events, anchor="start", before=30, after=30, clas
     Returns a CompositeDataset.  Raises if a sample is out of range.  ``_compute``: a stand-in for composite_cells()
     (host tests)."""
     from .detect import EventDataset
-    from .landmask import keep_mask, stack_cells
     layout = grid_layout(field, tdim)
     coords, _, dims, point, sdims, sshape, N = layout
     time = np.asarray(coords[tdim])
     T = time.shape[0]
-    check_steps(T)
+    check_steps(T, "mhw_composite")
     before, after, shift = check_window(before, after, shift)
     D = before + after + 1
     if not isinstance(events, EventDataset):
         raise XmhwException("mhw_composite expects the EventDataset returned by xmhw_amd.detect()")
-    if bool(events.point) != bool(point):
-        raise XmhwException("mhw_composite cannot pair a single-point series with a grid")
-    if not point and (tuple(events.sdims) != tuple(sdims) or tuple(events.sshape) != tuple(sshape)):
-        raise XmhwException(f"field and events are not on the same grid: {tuple(sdims)} {tuple(sshape)} and "
-                            f"{tuple(events.sdims)} {tuple(events.sshape)}")
-    if np.asarray(events.time).shape[0] != T:
-        raise XmhwException(f"field and events have {T} and {np.asarray(events.time).shape[0]} time steps")
-    if not _same_axis(time, events.time):
-        raise XmhwException("field and events do not have the same time axis")
+    check_same_frame("mhw_composite", "field", "events", (point, sdims, sshape), time,
+                     (events.point, events.sdims, events.sshape), events.time)
     found, kid, K = dense_ids(class_labels(classes, time), MAX_CLASSES, "mhw_composite", "classes")
     view = anchor_table(events, anchor, select)
     of_point = np.zeros(1, dtype=np.int64) if point else table_cell_of_point(view, N)
     check_view(view, of_point, T, "events")
     if base is None:
-        # a base of zero that pairs with the ocean cells of the field as a climatology does: NaN on land
-        if point:
-            base = 0.0
-        else:
-            values = field.values if hasattr(field, "values") else field
-            ocean = keep_mask(stack_cells(np.asarray(values), dims, tdim)[0], anynans)
-            base = np.where(ocean, 0.0, np.nan).reshape(sshape)
-    base = _base_series(base, point, sdims, coords)
-    got, counters = [], {}
+        base = zero_base(ocean_mask(field, dims, tdim, point, anynans), point, sdims, sshape, coords)
+    base = base_series(base, point, sdims, coords)
+    more = (kid, K, before, after, shift)
 
-    def on_cells(host_keep, ts, sec, thc, doy, doys, minDuration, joinGaps, maxGap, cold, **extra):
-        doy, doys = _constant_rows(sec, doy, doys)
+    def on_cells(host_keep, ts, sec, thc, doy, doys, options, **extra):
         check_result_bytes(K, D, ts.shape[1], max_result_bytes)
-        got.extend((_compute or composite_cells)(ts, sec, doy, doys, view, of_point[host_keep()], kid, K, before, after,
-                                                 shift, counters=counters, max_result_bytes=max_result_bytes, **extra))
+        return (_compute or composite_cells)(ts, sec, doy, doys, view, of_point[host_keep()], *more,
+                                             max_result_bytes=max_result_bytes, **extra)
 
-    def on_grid(stacked, anynans_, sec, thc, doy, doys, minDuration, joinGaps, maxGap, cold, **extra):
-        doy, doys = _constant_rows(sec, doy, doys)
-        *out, keep = composite_grid(stacked, anynans_, sec, doy, doys, view, of_point, kid, K, before, after, shift,
-                                    counters=counters, max_result_bytes=max_result_bytes, **extra)
-        got.extend(out)
-        return keep
-
-    mhw = run(field, base, base, layout, tdim, on_cells, on_grid, maxPadLength, False, tstep, anynans, _compute,
-              max_batch_bytes)
-    if counters.get("n_range", 0):
-        raise XmhwException(f"{counters['n_range']} {_RANGE_TEXT}")
-    f = CellFrame(mhw.keep, mhw.cell_index, point, sdims, sshape, coords)
-    arrays = [np.asarray(a) for a in got]
-    if [a.shape for a in arrays] != [(K, D, f.C)] * 3:
-        raise XmhwException(f"composite stage returned {[a.shape for a in arrays]}, expected {[(K, D, f.C)] * 3}")
+    f, arrays, mhw = cell_stage(
+        "composite", field, base, base, layout, tdim, on_cells,
+        lambda stacked, anynans_, sec, thc, doy, doys, options, **extra:
+            composite_grid(stacked, anynans_, sec, doy, doys, view, of_point, *more, max_result_bytes=max_result_bytes,
+                           **extra),
+        lambda C: [(K, D, C)] * 3, _Accumulators.range_texts, maxPadLength=maxPadLength, tstep=tstep, anynans=anynans,
+        _compute=_compute, max_batch_bytes=max_batch_bytes)
     n, s, ss = (f.place(a, 0, np.int32 if k == "n" else np.int64) for k, a in zip(FIELDS, arrays))
     # the anchors of every class and cell of the field, from the table
     cells = of_point[np.asarray(mhw.cell_index, dtype=np.int64)]
@@ -353,7 +303,5 @@ def mhw_composite(field, base, events, anchor="start", before=30, after=30, clas
     n_anchors = f.place(per_table_cell[:, cells], 0, np.int32)
     field_keep = np.asarray(mhw.keep, dtype=bool).reshape(-1)
     dropped = 0 if point else int((~field_keep[view["cell_index"]]).sum())
-    klass = found if found.shape[0] else np.zeros(1, dtype=np.int64)
-    attrs = {"classes": classes if isinstance(classes, str) else "array", "xmhw_parameters": mhw.attrs["xmhw_parameters"]}
-    return CompositeDataset(klass, np.arange(-before, after + 1), n, s, ss, n_anchors, f.keep, f.sdims, f.coords, anchor,
-                            shift, dropped, tdim, attrs)
+    return CompositeDataset(class_result_labels(found), np.arange(-before, after + 1), n, s, ss, n_anchors, f.keep, f.sdims,
+                            f.coords, anchor, shift, dropped, tdim, stage_attrs(classes, mhw))

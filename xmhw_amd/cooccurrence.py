@@ -29,10 +29,10 @@ behind cooccur_tables().
 import numpy as np
 
 from ._lib import hip
-from .days_by import class_labels
 from .device import DeviceScope, as_xmhw_errors, device_budget_bytes
 from .exception import XmhwException
-from .series_stage import CellFrame, check_class_ids, dense_ids
+from .series_stage import (CellFrame, check_class_ids, check_view, class_labels, dense_ids,     # noqa: F401
+                           same_axis)                         # (check_view: imported from here too)
 
 MAX_CLASSES = 1024              # XMHW_COOCCUR_MAX_CLASSES (include/xmhw_amd.h)
 MAX_LAGS = 64                   # XMHW_COOCCUR_MAX_LAGS
@@ -55,25 +55,6 @@ def _check_lags(lags):
     if np.unique(arr).shape[0] != arr.shape[0]:
         raise XmhwException("lags should be distinct")
     return np.ascontiguousarray(arr, dtype=np.int32)
-
-
-def check_view(view, cells, T, what):
-    """What the rasteriser relies on, for the cells it will read: positions inside the table, 0 <= start <= end < T
-    (compact_view() gives the first two) and the rows of a cell in time order."""
-    cells = np.ascontiguousarray(cells, dtype=np.int64)
-    if cells.ndim != 1 or (cells.size and (cells.min() < 0 or cells.max() >= view["C"])):
-        raise XmhwException(f"{what}: cell positions outside the table")
-    start, end, offsets = view["start"], view["end"], view["offsets"]
-    if view["n"]:
-        if int(end.max()) >= T:
-            raise XmhwException(f"{what}: index_end outside the time axis")
-        later = np.diff(start.astype(np.int64)) < 0
-        if later.any():
-            first = np.zeros(view["n"], dtype=bool)              # rows that open a cell: no order across cells
-            first[offsets[:-1][offsets[:-1] < view["n"]]] = True
-            if (later & ~first[1:]).any():
-                raise XmhwException(f"{what}: the rows of a cell are not in time order")
-    return cells
 
 
 def n_valid_pairs(kid, K, lags):
@@ -207,16 +188,6 @@ class CooccurrenceDataset:
                           attrs=self.attrs)
 
 
-def _same_axis(ta, tb):
-    ta, tb = np.asarray(ta), np.asarray(tb)
-    if ta.shape != tb.shape:
-        return False
-    try:
-        return bool(np.array_equal(ta, tb))
-    except (TypeError, ValueError):
-        return False
-
-
 def mhw_cooccurrence(a, b, classes="all", lags=(0,), max_batch_bytes=None, _compute=None):
     """Per cell, class of time steps and lag: the steps on which the events of ``a`` and of ``b`` coincide.
 
@@ -240,7 +211,7 @@ def mhw_cooccurrence(a, b, classes="all", lags=(0,), max_batch_bytes=None, _comp
     T = time.shape[0]
     if np.asarray(b.time).shape[0] != T:
         raise XmhwException(f"a and b have {T} and {np.asarray(b.time).shape[0]} time steps")
-    if not _same_axis(time, b.time):
+    if not same_axis(time, b.time):
         raise XmhwException("a and b do not have the same time axis")
     found, kid, K = dense_ids(class_labels(classes, time), MAX_CLASSES, "mhw_cooccurrence", "classes")
     lags = _check_lags(lags)

@@ -28,12 +28,11 @@ Host side here (validation, weights, region labels, slabs); device side in csrc/
 import numpy as np
 
 from . import gridweights
-from ._lib import hip
 from .device import DeviceScope, as_xmhw_errors
 from .exception import XmhwException
 from .gridweights import quantise_weights, resolve_weights, weights_label     # (quantise_weights: imported from here too)
-from .series_stage import (check_weighted_cells, dense_ids, grid_layout, regions_of_result, run, walk_cells,     # noqa: F401
-                           walk_grid)                              # (grid_layout: imported from here too)
+from .series_stage import (Accumulators, check_weighted_cells, dense_ids, grid_layout, regions_of_result,     # noqa: F401
+                           run, run_cells, run_grid)               # (grid_layout: imported from here too)
 
 CATEGORIES = ("moderate", "strong", "severe", "extreme", "event")
 WEIGHT_ONE = 1 << 31            # the quantised value of the largest weight
@@ -44,24 +43,23 @@ def _check_cells(C, wq, region, R):
     return check_weighted_cells(C, wq, region, R, MAX_REGIONS, "mhw_coverage", "wq")
 
 
-class _Accumulators:
-    """One call's arguments and its (T, R, 5) int64 device accumulators: zeroed by begin(), every slab ADDS, read back
-    once at the end."""
+class _Accumulators(Accumulators):
+    """One call's arguments and its (T, R, 5) int64 device accumulators, which every slab ADDS to whole: they are not
+    sliced by column, and nothing is out of range."""
 
     def __init__(self, wq, region, R, minDuration, joinGaps, maxGap, coldSpells):
-        self.h, self.wq, self.region, self.R = hip(), wq, region, R
+        super().__init__()
+        self.wq, self.region, self.R = wq, region, R
         self.filter = (int(minDuration), int(bool(joinGaps)), int(maxGap))
         self.neg = int(bool(coldSpells))
-        self._scope = DeviceScope()
 
     def begin(self, T, C):
         """T steps; wq and region hold C entries"""
         self.wq, self.region, self.R = _check_cells(C, self.wq, self.region, self.R)
-        self.shape = (T, self.R, len(CATEGORIES))
-        nbytes = 8 * T * self.R * len(CATEGORIES)
-        self.cells, self.area = self._scope.alloc(nbytes), self._scope.alloc(nbytes)
-        self.h.memset(self.cells.ptr, 0, nbytes)
-        self.h.memset(self.area.ptr, 0, nbytes)
+        shape = (T, self.R, len(CATEGORIES))
+        self.make(None, {"cells": (shape, np.int64), "area_q": (shape, np.int64)})
+        for ptr in self.ptrs():
+            self.h.memset(ptr, 0, 8 * int(np.prod(shape)))
 
     def add_slab(self, slab):
         """One slab (series_stage.Slab): its cells' weights and region ids, exceedance bits, then the reduction."""
@@ -74,16 +72,8 @@ class _Accumulators:
                 self.h.exceed_bits(d_ts.ptr, slab.isz, T, n, slab.ld, slab.th_ptr, slab.ldc, slab.D, slab.rows, self.neg,
                                    d_bits.ptr, n)
                 self.h.coverage_accumulate(d_ts.ptr, slab.isz, T, n, slab.ld, slab.se_ptr, slab.th_ptr, slab.ldc, slab.rows,
-                                           self.neg, d_bits.ptr, n, *self.filter, d_wq.ptr, d_reg.ptr, self.R, self.cells.ptr,
-                                           self.area.ptr)
+                                           self.neg, d_bits.ptr, n, *self.filter, d_wq.ptr, d_reg.ptr, self.R, *self.ptrs())
             self.h.stream_sync(0)                       # the slab's buffers are freed on the way out
-
-    def result(self):
-        self.h.stream_sync(0)
-        return self.cells.to_array(self.shape, np.int64), self.area.to_array(self.shape, np.int64)
-
-    def free(self):
-        self._scope.free()
 
 
 def coverage_cells(ts, seas, thresh, doy, doys, wq, region, R, minDuration=5, joinGaps=True, maxGap=2, coldSpells=False,
@@ -92,28 +82,20 @@ def coverage_cells(ts, seas, thresh, doy, doys, wq, region, R, minDuration=5, jo
     quantised weights in [0, 2**31], region (C,) ids in [-1, R) (-1: the cell counts nowhere).
     Returns (cells, area_q), both int64 (T, R, 5), columns CATEGORIES.  Cells go through the device in batches
     below max_batch_bytes; the sums are integers, so the batch size does not change a single bit."""
-    acc = _Accumulators(wq, region, R, minDuration, joinGaps, maxGap, coldSpells)
-    try:
-        walk_cells(ts, seas, thresh, doy, doys, lambda T, isz, D: T * (isz + 1) + T // 4 + 2 * D * 8 + 64, max_batch_bytes,
-                   pad, acc.add_slab, acc.begin)
-        return acc.result()
-    finally:
-        acc.free()
+    return run_cells(_Accumulators(wq, region, R, minDuration, joinGaps, maxGap, coldSpells), ts, seas, thresh, doy, doys,
+                     lambda T, isz, D: T * (isz + 1) + T // 4 + 2 * D * 8 + 64, max_batch_bytes, pad)
 
 
 def coverage_grid(stacked, anynans, seas, thresh, doy, doys, wq, region, R, minDuration=5, joinGaps=True, maxGap=2,
                   coldSpells=False, max_batch_bytes=None, clim_stacked=False, pad=None):
     """coverage_cells() for an UNCOMPACTED stacked host series (T, N), as detect_front.detect_grid: the land mask
     and the compaction run on the device slab by slab (series_stage.walk_grid).  wq / region have N entries (the whole
-    grid) and are compacted by each slab's `keep`.  Returns (cells, area_q, keep[N])."""
-    acc = _Accumulators(wq, region, R, minDuration, joinGaps, maxGap, coldSpells)
-    try:
-        acc.begin(*stacked.shape)
-        keep = walk_grid(stacked, anynans, seas, thresh, doy, doys, lambda T, D: 6 * D * 8 + T // 4 + 64, max_batch_bytes,
-                         clim_stacked, pad, acc.add_slab)
-        return acc.result() + (keep,)
-    finally:
-        acc.free()
+    grid) and are compacted by each slab's `keep`: the accumulators begin with the shape of the grid, not with the ocean
+    cells.  Returns (cells, area_q, keep[N])."""
+    out, keep = run_grid(_Accumulators(wq, region, R, minDuration, joinGaps, maxGap, coldSpells), stacked, anynans, seas,
+                         thresh, doy, doys, lambda T, D: 6 * D * 8 + T // 4 + 64, max_batch_bytes, clim_stacked, pad,
+                         begin_with=stacked.shape)
+    return out + (keep,)
 
 
 class CoverageDataset:

@@ -31,18 +31,16 @@ coverage_grid()).
 """
 import numpy as np
 
-from . import calendar as cal
-from ._lib import hip
 from .coverage import CATEGORIES
 from .device import DeviceScope, as_xmhw_errors
 from .exception import XmhwException
-from .series_stage import CellFrame, check_class_ids, dense_ids, grid_layout, run, walk_cells, walk_grid, walk_stage
+from .series_stage import (Accumulators, cell_stage, check_class_ids, class_labels, class_result_labels, dense_ids,
+                           grid_layout, run_cells, run_grid, stage_attrs)     # (class_labels: imported from here too)
 
 MAX_CLASSES = 1024              # XMHW_CLASS_DAYS_MAX_CLASSES (include/xmhw_amd.h)
 CHANNELS = 6                    # XMHW_CLASS_DAYS_CHANNELS: CATEGORIES, then n_valid
 INTENSITY_BITS = 16             # XMHW_TRACK_INTENSITY_BITS
 RANGE_BITS = 7                  # |a| < 2**7
-NAMED_CLASSES = ("all", "month", "season", "year")
 _RANGE_TEXT = ("in-event samples lie 2**7 and more from their climatology (or are infinite): is the series in kelvin "
                "and the climatology in degrees Celsius?")
 
@@ -51,31 +49,30 @@ def _check_classes(T, classes, K):
     return check_class_ids(T, classes, K, MAX_CLASSES, "mhw_days_by")
 
 
-class _Accumulators:
-    """One call's arguments and its device accumulators: days int32 (K, 6, C), isum_q int64 (K, C), intensity_max (K, C)
-    used as the key array, and the range counter.  Initialised by begin(); they live across the slabs, each slab adds
-    into its own column range, and they are read back once."""
+class _Accumulators(Accumulators):
+    """One call's arguments and its device accumulators: days int32 (K, 6, C), isum_q int64 (K, C), intensity_max (K, C),
+    which holds the order-preserving keys until finish() turns them into float64 in place, and the range counter."""
+    range_texts = {"n_range": _RANGE_TEXT}
 
     def __init__(self, classes, K, minDuration, joinGaps, maxGap, coldSpells):
-        self.h, self.classes, self.K, self.C = hip(), classes, K, None
+        super().__init__()
+        self.classes, self.K = classes, K
         self.filter = (int(minDuration), int(bool(joinGaps)), int(maxGap))
         self.neg = int(bool(coldSpells))
-        self._scope = DeviceScope()
 
     def begin(self, T, C):
         """T steps, C ocean cells"""
         self.classes, self.K = _check_classes(T, self.classes, self.K)
-        n = max(self.K * C, 1)
-        s = self._scope
-        self.days, self.isum, self.imax, self.count = s.alloc(4 * CHANNELS * n), s.alloc(8 * n), s.alloc(8 * n), s.alloc(8)
+        K = self.K
+        self.make(C, {"days": ((K, CHANNELS, C), np.int32), "isum_q": ((K, C), np.int64),
+                      "intensity_max": ((K, C), np.float64)})
         with as_xmhw_errors(also="Unsupported"):
-            self.h.class_days_init(self.K, C, self.days.ptr, self.isum.ptr, self.imax.ptr, C, self.count.ptr)
-        self.C = C
+            self.h.class_days_init(K, C, *self.ptrs(), C, self.count.ptr)
 
     def add_slab(self, slab):
         """One slab (series_stage.Slab), columns k0..k0+n-1 of the accumulators: exceedance bits, then the reduction
         ADDS."""
-        d_ts, T, n, k0 = slab.d_ts, slab.T, slab.n, slab.k0
+        d_ts, T, n = slab.d_ts, slab.T, slab.n
         W = (T + 63) // 64
         with DeviceScope() as s:
             d_bits = s.alloc(8 * W * n)
@@ -84,23 +81,12 @@ class _Accumulators:
                                    d_bits.ptr, n)
                 self.h.class_days_accumulate(d_ts.ptr, slab.isz, T, n, slab.ld, slab.se_ptr, slab.th_ptr, slab.ldc, slab.rows,
                                              self.neg, d_bits.ptr, n, *self.filter, self.classes, self.K,
-                                             self.days.ptr + 4 * k0, self.isum.ptr + 8 * k0, self.imax.ptr + 8 * k0, self.C,
-                                             self.count.ptr)
+                                             *self.ptrs(slab.k0), self.C, self.count.ptr)
             self.h.stream_sync(0)                       # d_bits is freed on the way out
 
-    def result(self):
-        K, C = self.K, self.C
+    def finish(self):
         with as_xmhw_errors(also="Unsupported"):
-            self.h.class_days_finish(K, C, self.imax.ptr, C)
-        self.h.stream_sync(0)
-        if C == 0:
-            return (np.zeros((K, CHANNELS, 0), np.int32), np.zeros((K, 0), np.int64), np.zeros((K, 0), np.float64)), 0
-        out = (self.days.to_array((K, CHANNELS, C), np.int32), self.isum.to_array((K, C), np.int64),
-               self.imax.to_array((K, C), np.float64))
-        return out, int(self.count.to_array((1,), np.int64)[0])
-
-    def free(self):
-        self._scope.free()
+            self.h.class_days_finish(self.K, self.C, *self.ptrs(0, ("intensity_max",)), self.C)
 
 
 def class_days_cells(ts, seas, thresh, doy, doys, classes, K, minDuration=5, joinGaps=True, maxGap=2, coldSpells=False,
@@ -110,10 +96,8 @@ def class_days_cells(ts, seas, thresh, doy, doys, classes, K, minDuration=5, joi
     device in batches below max_batch_bytes, as in coverage_cells(); the sums are integers, so the batch size does not
     change a single bit.  Raises if a sample is out of range (module docstring); with ``counters`` (a dict) it stores
     ``n_range`` there instead."""
-    acc = _Accumulators(classes, K, minDuration, joinGaps, maxGap, coldSpells)
-    per_cell = lambda T, isz, D: T * (isz + 1) + T // 4 + 2 * D * 8 + 64                               # noqa: E731
-    return walk_stage(acc, lambda a: walk_cells(ts, seas, thresh, doy, doys, per_cell, max_batch_bytes, pad, a.add_slab,
-                                                a.begin), _RANGE_TEXT, counters)[0]
+    return run_cells(_Accumulators(classes, K, minDuration, joinGaps, maxGap, coldSpells), ts, seas, thresh, doy, doys,
+                     lambda T, isz, D: T * (isz + 1) + T // 4 + 2 * D * 8 + 64, max_batch_bytes, pad, counters)
 
 
 def class_days_grid(stacked, anynans, seas, thresh, doy, doys, classes, K, minDuration=5, joinGaps=True, maxGap=2,
@@ -122,39 +106,9 @@ def class_days_grid(stacked, anynans, seas, thresh, doy, doys, classes, K, minDu
     the land mask and the compaction run on the device slab by slab (series_stage.walk_grid).  The accumulators live
     across the slabs and each slab writes its own column range.  Returns (days, isum_q, intensity_max, keep[N]) over the
     ocean cells."""
-    acc = _Accumulators(classes, K, minDuration, joinGaps, maxGap, coldSpells)
-    out, keep = walk_stage(acc, lambda a: walk_grid(stacked, anynans, seas, thresh, doy, doys,
-                                                    lambda T, D: 6 * D * 8 + T // 4 + 64, max_batch_bytes, clim_stacked, pad,
-                                                    a.add_slab, begin=a.begin), _RANGE_TEXT, counters)
+    out, keep = run_grid(_Accumulators(classes, K, minDuration, joinGaps, maxGap, coldSpells), stacked, anynans, seas,
+                         thresh, doy, doys, lambda T, D: 6 * D * 8 + T // 4 + 64, max_batch_bytes, clim_stacked, pad, counters)
     return out + (keep,)
-
-
-def class_labels(classes, time):
-    """The ``classes`` argument as labels per time step: an integer array of length T as it is, or a named form taken from
-    a datetime64 time axis -- "all" (one class 0), "month" (1..12), "season" (DJF, MAM, JJA, SON = 0..3), "year" (the
-    calendar year)."""
-    time = np.asarray(time)
-    T = time.shape[0]
-    if isinstance(classes, str):
-        if classes not in NAMED_CLASSES:
-            raise XmhwException(f"classes should be an integer array or one of {NAMED_CLASSES}, got {classes!r}")
-        if classes == "all":
-            return np.zeros(T, dtype=np.int64)
-        if time.dtype.kind != "M":
-            raise XmhwException(f"classes={classes!r} needs a datetime64 time coordinate, got {time.dtype}: pass the class "
-                                "of every time step as an integer array instead")
-        year, month, _, _ = cal._fields(time)
-        if classes == "month":
-            return month.astype(np.int64)
-        if classes == "season":
-            return (month % 12) // 3
-        return year.astype(np.int64)
-    labels = np.asarray(classes)
-    if labels.dtype.kind not in "iu":
-        raise XmhwException(f"classes should be an integer array, got {labels.dtype}")
-    if labels.shape != (T,):
-        raise XmhwException(f"classes should have one entry per time step ({T}), got shape {labels.shape}")
-    return labels.astype(np.int64)
 
 
 def classes_from_events(T, *event_datasets):
@@ -248,28 +202,16 @@ def mhw_days_by(temp, th, se, classes="month", tdim="time", minDuration=5, joinG
     time = np.asarray(coords[tdim])
     found, kid, K = dense_ids(class_labels(classes, time), MAX_CLASSES, "mhw_days_by", "classes")
     n_steps = np.bincount(kid[kid >= 0], minlength=K).astype(np.int64)
-    got, counters = [], {}
-
-    def on_cells(host_keep, ts, sec, thc, doy, doys, *options, **extra):
-        got.extend((_compute or class_days_cells)(ts, sec, thc, doy, doys, kid, K, *options, counters=counters, **extra))
-
-    def on_grid(stacked, anynans_, sec, thc, doy, doys, *options, **extra):
-        *out, keep = class_days_grid(stacked, anynans_, sec, thc, doy, doys, kid, K, *options, counters=counters, **extra)
-        got.extend(out)
-        return keep
-
-    mhw = run(temp, th, se, layout, tdim, on_cells, on_grid, maxPadLength, coldSpells, tstep, anynans, _compute,
-              max_batch_bytes, minDuration, joinGaps, maxGap)
-    if counters.get("n_range", 0):
-        raise XmhwException(f"{counters['n_range']} {_RANGE_TEXT}")
-    f = CellFrame(mhw.keep, mhw.cell_index, point, sdims, sshape, coords)
-    C = f.C
-    days6, isum, imax = (np.asarray(a) for a in got)
-    if days6.shape != (K, CHANNELS, C) or isum.shape != (K, C) or imax.shape != (K, C):
-        raise XmhwException(f"class stage returned {days6.shape}, {isum.shape}, {imax.shape}, expected "
-                            f"{(K, CHANNELS, C)}, {(K, C)}, {(K, C)}")
-    klass = found if found.shape[0] else np.zeros(1, dtype=np.int64)
-    attrs = {"classes": classes if isinstance(classes, str) else "array", "xmhw_parameters": mhw.attrs["xmhw_parameters"]}
-    return ClassDaysDataset(klass, n_steps, f.place(days6[:, :5], 0, np.int32), f.place(days6[:, 5], 0, np.int32),
-                            f.place(isum, 0, np.int64), f.place(imax, np.nan, np.float64), f.keep, f.sdims, f.coords, tdim,
-                            attrs)
+    f, (days6, isum, imax), mhw = cell_stage(
+        "class", temp, th, se, layout, tdim,
+        lambda host_keep, ts, sec, thc, doy, doys, options, **extra:
+            (_compute or class_days_cells)(ts, sec, thc, doy, doys, kid, K, *options, **extra),
+        lambda stacked, anynans_, sec, thc, doy, doys, options, **extra:
+            class_days_grid(stacked, anynans_, sec, thc, doy, doys, kid, K, *options, **extra),
+        lambda C: [(K, CHANNELS, C), (K, C), (K, C)], _Accumulators.range_texts, based=False, maxPadLength=maxPadLength,
+        coldSpells=coldSpells, tstep=tstep, anynans=anynans, _compute=_compute, max_batch_bytes=max_batch_bytes,
+        detect_options=(minDuration, joinGaps, maxGap))
+    attrs = stage_attrs(classes, mhw)
+    return ClassDaysDataset(class_result_labels(found), n_steps, f.place(days6[:, :5], 0, np.int32),
+                            f.place(days6[:, 5], 0, np.int32), f.place(isum, 0, np.int64), f.place(imax, np.nan, np.float64),
+                            f.keep, f.sdims, f.coords, tdim, attrs)

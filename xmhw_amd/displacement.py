@@ -47,10 +47,10 @@ from collections import namedtuple
 import numpy as np
 
 from ._lib import hip
-from .days_by import class_labels
 from .device import DeviceScope, as_xmhw_errors, device_budget_bytes, is_packed, native_float
 from .exception import XmhwException
-from .series_stage import LAND_TEXT, CellFrame, check_class_ids, climatologies_on_device, dense_ids, grid_layout, run
+from .series_stage import (LAND_TEXT, CellFrame, check_class_ids, check_view, class_labels, climatologies_on_device, dense_ids,
+                           grid_layout, run)
 
 MAX_CLASSES = 1024              # XMHW_DISPLACEMENT_MAX_CLASSES (include/xmhw_amd.h)
 MAX_AXIS = 32767                # XMHW_DISPLACEMENT_MAX_AXIS: dj and di travel as int16
@@ -212,7 +212,6 @@ class DeviceSeas(namedtuple("DeviceSeas", "ptr ld D C")):
 def check_stage_inputs(field, seas, rows, view, cell_index, table, classes, K, basin):
     """What both stages (the device's and a stand-in) may rely on: returns (field, rows, cell_of_point, classes, K,
     basin) checked and in the layouts the device takes."""
-    from .cooccurrence import check_view
     if is_packed(field):
         raise XmhwException("mhw_displacement does not read packed int16 views: pass decoded floats")
     field = native_float(np.asarray(field))

@@ -38,12 +38,12 @@ grid, masked and compacted on the device slab by slab).  The baseline rides wher
 import numpy as np
 
 from . import calendar as cal
-from ._lib import hip, hip_stress
-from .api import GridSeries, _from_xarray, _is_xarray
-from .days_by import class_labels
-from .device import DeviceScope, as_xmhw_errors
+from ._lib import hip_stress
+from .api import GridSeries
+from .device import as_xmhw_errors
 from .exception import XmhwException
-from .series_stage import CellFrame, check_class_ids, dense_ids, grid_layout, run, walk_cells, walk_grid, walk_stage
+from .series_stage import (Accumulators, base_series, cell_stage, check_class_ids, class_labels, class_result_labels,
+                           dense_ids, grid_layout, ocean_mask, run_cells, run_grid, stage_attrs, zero_base)
 
 MAX_CLASSES = 1024              # XMHW_HEAT_STRESS_MAX_CLASSES (include/xmhw_amd.h)
 CHANNELS = 8                    # XMHW_HEAT_STRESS_CHANNELS: n_valid, n_hot, then the levels
@@ -136,98 +136,75 @@ def snapshot_steps(at, time):
 
 # ---- the device stages -------------------------------------------------------------------------------
 
-class _StressAccumulators:
+class _StressAccumulators(Accumulators):
     """One call's arguments and its device accumulators: counts int32 (K, 8, C), hsum_q int64 (K, C), the peak keys
-    (K, C), snap_q int32 (J, C) and the range counter.  Initialised by begin(); they live across the slabs, each slab
-    adds into its own column range, and they are read back once."""
+    (K, C), snap_q int32 (J, C) and the range counter; peak_q and peak_t are what finish() makes of the keys."""
+    range_texts = {"n_range": _RANGE_TEXT}
+    _ADDED = ("counts", "hsum_q", "key", "snap_q")
 
     def __init__(self, classes, K, window, h0, level_q, at, coldSpells):
-        self.h, self.hs = hip(), hip_stress()
+        super().__init__()
+        self.hs = hip_stress()
         self.args = (classes, K, window, h0, level_q, at)
-        self.neg, self.C = int(bool(coldSpells)), None
-        self._scope = DeviceScope()
+        self.neg = int(bool(coldSpells))
 
     def begin(self, T, C):
         """T steps, C ocean cells"""
         self.classes, self.K, self.W, self.h0, self.level_q, self.at = check_stress_arguments(T, *self.args)
-        n, s = max(self.K * C, 1), self._scope
-        self.J = int(self.at.shape[0])
-        self.counts, self.hsum, self.key = s.alloc(4 * CHANNELS * n), s.alloc(8 * n), s.alloc(8 * n)
-        self.snap, self.count = s.alloc(4 * max(self.J * C, 1)), s.alloc(8)
+        K, J = self.K, int(self.at.shape[0])
+        self.make(C, {"counts": ((K, CHANNELS, C), np.int32), "hsum_q": ((K, C), np.int64), "key": ((K, C), np.int64),
+                      "peak_q": ((K, C), np.int32), "peak_t": ((K, C), np.int32), "snap_q": ((J, C), np.int32)})
         with as_xmhw_errors(also="Unsupported"):
-            self.hs.heat_stress_init(self.K, C, self.counts.ptr, self.hsum.ptr, self.key.ptr, C, self.count.ptr)
-        self.C = C
+            self.hs.heat_stress_init(K, C, *self.ptrs(0, self._ADDED[:3]), C, self.count.ptr)
 
     def add_slab(self, slab):
         """One slab (series_stage.Slab), columns k0..k0+n-1 of the accumulators; the baseline is where the slab carries
         its climatologies."""
-        k0 = slab.k0
         with as_xmhw_errors(also="Unsupported"):
             self.hs.heat_stress_accumulate(slab.d_ts.ptr, slab.isz, slab.T, slab.n, slab.ld, slab.se_ptr, slab.ldc, slab.D,
                                            slab.rows, self.neg, self.W, self.h0, self.classes, self.K, self.level_q, self.at,
-                                           self.counts.ptr + 4 * k0, self.hsum.ptr + 8 * k0, self.key.ptr + 8 * k0,
-                                           self.snap.ptr + 4 * k0, self.C, self.count.ptr)
+                                           *self.ptrs(slab.k0, self._ADDED), self.C, self.count.ptr)
         self.h.stream_sync(0)                           # the slab's series is freed on the way out
 
-    def result(self):
-        K, C, J = self.K, self.C, self.J
-        if C == 0:
-            return (np.zeros((K, CHANNELS, 0), np.int32), np.zeros((K, 0), np.int64), np.zeros((K, 0), np.int32),
-                    np.zeros((K, 0), np.int32), np.zeros((J, 0), np.int32)), 0
-        with DeviceScope() as s:
-            pq, pt = s.alloc(4 * K * C), s.alloc(4 * K * C)
-            with as_xmhw_errors(also="Unsupported"):
-                self.hs.heat_stress_finish(K, C, self.key.ptr, pq.ptr, pt.ptr, C)
-            self.h.stream_sync(0)
-            out = (self.counts.to_array((K, CHANNELS, C), np.int32), self.hsum.to_array((K, C), np.int64),
-                   pq.to_array((K, C), np.int32), pt.to_array((K, C), np.int32),
-                   self.snap.to_array((J, C), np.int32) if J else np.zeros((0, C), np.int32))
-        return out, int(self.count.to_array((1,), np.int64)[0])
+    def finish(self):
+        with as_xmhw_errors(also="Unsupported"):
+            self.hs.heat_stress_finish(self.K, self.C, *self.ptrs(0, ("key", "peak_q", "peak_t")), self.C)
 
-    def free(self):
-        self._scope.free()
+    def read(self):
+        return super().read(("counts", "hsum_q", "peak_q", "peak_t", "snap_q"))
 
 
-class _SumsAccumulators:
+class _SumsAccumulators(Accumulators):
     """The class sums' counterpart: n_valid int32 (K, C), sum_q int64 (K, C) and the range counter."""
+    range_texts = {"n_range": _SUMS_RANGE_TEXT}
 
     def __init__(self, classes, K, x0):
-        self.h, self.hs = hip(), hip_stress()
-        self.classes, self.K, self.C = classes, K, None
+        super().__init__()
+        self.hs = hip_stress()
+        self.classes, self.K = classes, K
         self.x0 = float(x0)
         if not np.isfinite(self.x0):
             raise XmhwException(f"offset should be finite, got {x0!r}")
-        self._scope = DeviceScope()
 
     def begin(self, T, C):
         self.classes, self.K = check_class_ids(T, self.classes, self.K, MAX_CLASSES, "class_sums")
-        n, s = max(self.K * C, 1), self._scope
-        self.nv, self.sum, self.count = s.alloc(4 * n), s.alloc(8 * n), s.alloc(8)
+        self.make(C, {"n_valid": ((self.K, C), np.int32), "sum_q": ((self.K, C), np.int64)})
         with as_xmhw_errors(also="Unsupported"):
-            self.hs.class_sums_init(self.K, C, self.nv.ptr, self.sum.ptr, C, self.count.ptr)
-        self.C = C
+            self.hs.class_sums_init(self.K, C, *self.ptrs(), C, self.count.ptr)
 
     def add_slab(self, slab):
-        k0 = slab.k0
         with as_xmhw_errors(also="Unsupported"):
             self.hs.class_sums_accumulate(slab.d_ts.ptr, slab.isz, slab.T, slab.n, slab.ld, self.x0, self.classes, self.K,
-                                          self.nv.ptr + 4 * k0, self.sum.ptr + 8 * k0, self.C, self.count.ptr)
+                                          *self.ptrs(slab.k0), self.C, self.count.ptr)
         self.h.stream_sync(0)
-
-    def result(self):
-        K, C = self.K, self.C
-        self.h.stream_sync(0)
-        if C == 0:
-            return (np.zeros((K, 0), np.int32), np.zeros((K, 0), np.int64)), 0
-        return ((self.nv.to_array((K, C), np.int32), self.sum.to_array((K, C), np.int64)),
-                int(self.count.to_array((1,), np.int64)[0]))
-
-    def free(self):
-        self._scope.free()
 
 
 def _bytes_per_cell(T, isz, D):
     return T * isz + 2 * D * 8 + 64
+
+
+def _extra_per_cell(T, D):
+    return 4 * D * 8 + 64
 
 
 def heat_stress_cells(ts, base, doy, doys, classes, K, window, h0, level_q, at, coldSpells=False, max_batch_bytes=64 << 30,
@@ -238,10 +215,8 @@ def heat_stress_cells(ts, base, doy, doys, classes, K, window, h0, level_q, at, 
     Cells go through the device in batches below max_batch_bytes; the sums are integers, so the batch size does not
     change a single bit.  Raises if a sample is out of range (module docstring); with ``counters`` (a dict) it stores
     ``n_range`` there instead."""
-    acc = _StressAccumulators(classes, K, window, h0, level_q, at, coldSpells)
-    out, _ = walk_stage(acc, lambda a: walk_cells(ts, base, base, doy, doys, _bytes_per_cell, max_batch_bytes, pad,
-                                                  a.add_slab, a.begin), _RANGE_TEXT, counters)
-    return out
+    return run_cells(_StressAccumulators(classes, K, window, h0, level_q, at, coldSpells), ts, base, base, doy, doys,
+                     _bytes_per_cell, max_batch_bytes, pad, counters)
 
 
 def heat_stress_grid(stacked, anynans, base, doy, doys, classes, K, window, h0, level_q, at, coldSpells=False,
@@ -249,10 +224,8 @@ def heat_stress_grid(stacked, anynans, base, doy, doys, classes, K, window, h0, 
     """heat_stress_cells() for an UNCOMPACTED stacked host series (T, N), float or a packed int16 view: the land mask
     and the compaction run on the device slab by slab (series_stage.walk_grid).  Returns the five arrays over the ocean
     cells and keep[N]."""
-    acc = _StressAccumulators(classes, K, window, h0, level_q, at, coldSpells)
-    out, keep = walk_stage(acc, lambda a: walk_grid(stacked, anynans, base, base, doy, doys, lambda T, D: 4 * D * 8 + 64,
-                                                    max_batch_bytes, clim_stacked, pad, a.add_slab, begin=a.begin),
-                           _RANGE_TEXT, counters)
+    out, keep = run_grid(_StressAccumulators(classes, K, window, h0, level_q, at, coldSpells), stacked, anynans, base, base,
+                         doy, doys, _extra_per_cell, max_batch_bytes, clim_stacked, pad, counters)
     return out + (keep,)
 
 
@@ -260,10 +233,8 @@ def class_sums_cells(ts, classes, K, x0=0.0, max_batch_bytes=64 << 30, pad=None,
     """The class sums of a dense (T, C) series: (n_valid int32 (K, C), sum_q int64 (K, C))"""
     ts = np.asarray(ts)
     zero, steps = np.zeros((1, ts.shape[1])), np.zeros(ts.shape[0], dtype=np.int64)
-    acc = _SumsAccumulators(classes, K, x0)
-    out, _ = walk_stage(acc, lambda a: walk_cells(ts, zero, zero, steps, steps[:1], _bytes_per_cell, max_batch_bytes, pad,
-                                                  a.add_slab, a.begin), _SUMS_RANGE_TEXT, counters)
-    return out
+    return run_cells(_SumsAccumulators(classes, K, x0), ts, zero, zero, steps, steps[:1], _bytes_per_cell, max_batch_bytes,
+                     pad, counters)
 
 
 def class_sums_grid(stacked, anynans, land, classes, K, x0=0.0, max_batch_bytes=None, clim_stacked=False, pad=None,
@@ -272,10 +243,8 @@ def class_sums_grid(stacked, anynans, land, classes, K, x0=0.0, max_batch_bytes=
     the slabs' survivors with the accumulators' columns, as the climatologies do elsewhere.  Returns (n_valid, sum_q,
     keep[N])."""
     steps = np.zeros(stacked.shape[0], dtype=np.int64)
-    acc = _SumsAccumulators(classes, K, x0)
-    out, keep = walk_stage(acc, lambda a: walk_grid(stacked, anynans, land, land, steps, steps[:1],
-                                                    lambda T, D: 4 * D * 8 + 64, max_batch_bytes, clim_stacked, pad,
-                                                    a.add_slab, begin=a.begin), _SUMS_RANGE_TEXT, counters)
+    out, keep = run_grid(_SumsAccumulators(classes, K, x0), stacked, anynans, land, land, steps, steps[:1], _extra_per_cell,
+                         max_batch_bytes, clim_stacked, pad, counters)
     return out + (keep,)
 
 
@@ -356,36 +325,6 @@ class HeatStressDataset:
 
 # ---- the public functions ----------------------------------------------------------------------------
 
-def _constant_rows(sec, doy, doys):
-    """a one-row baseline pairs with every step: its labels are not day-of-year labels"""
-    if sec.shape[0] == 1:
-        return np.zeros(np.asarray(doy).shape[0], dtype=np.int64), np.zeros(1, dtype=np.int64)
-    return doy, doys
-
-
-def _base_series(base, point, sdims, coords):
-    """``base`` as the GridSeries with a 'doy' dimension that pairs with the series like th / se"""
-    if isinstance(base, MonthlyMeanDataset):
-        base = base.as_series()
-    elif _is_xarray(base):
-        base = GridSeries(base.values, base.dims, _from_xarray(base)[0])
-    elif not isinstance(base, GridSeries):
-        a = np.asarray(base, dtype=np.float64)
-        nd = 0 if point else len(sdims)
-        if a.ndim not in (nd, nd + 1):
-            raise XmhwException(f"base should be a {tuple(sdims)} array or a ('doy',) + {tuple(sdims)} climatology, got "
-                                f"shape {a.shape}")
-        dims = tuple(sdims) if a.ndim == nd else ("doy",) + tuple(sdims)
-        c = {d: coords[d] for d in sdims if d in coords}
-        if "doy" in dims:
-            c["doy"] = np.arange(1, a.shape[0] + 1)
-        base = GridSeries(a, dims, c)
-    if "doy" not in base.dims:
-        base = GridSeries(np.asarray(base.values, dtype=np.float64)[None], ("doy",) + tuple(base.dims),
-                          dict(base.coords, doy=np.zeros(1, dtype=np.int64)))
-    return base
-
-
 def heat_stress(temp, base, window=84, min_hotspot=1.0, unit=7.0, levels=(4.0, 8.0), classes="year", at=None, tdim="time",
                 coldSpells=False, maxPadLength=None, tstep=False, anynans=False, max_batch_bytes=None, _compute=None):
     """Accumulated thermal stress per cell: the sum over the last ``window`` steps of the excess of ``temp`` over
@@ -411,36 +350,21 @@ def heat_stress(temp, base, window=84, min_hotspot=1.0, unit=7.0, levels=(4.0, 8
     kid, K, window, h0, level_q, steps = check_stress_arguments(T, kid, K, window, min_hotspot, level_q,
                                                                 snapshot_steps(at, time))
     n_steps = np.bincount(kid[kid >= 0], minlength=K).astype(np.int64)
-    base = _base_series(base, point, sdims, coords)
-    got, counters = [], {}
-
-    def on_cells(host_keep, ts, sec, thc, doy, doys, minDuration, joinGaps, maxGap, cold, **extra):
-        doy, doys = _constant_rows(sec, doy, doys)
-        got.extend((_compute or heat_stress_cells)(ts, sec, doy, doys, kid, K, window, h0, level_q, steps, coldSpells=cold,
-                                                   counters=counters, **extra))
-
-    def on_grid(stacked, anynans_, sec, thc, doy, doys, minDuration, joinGaps, maxGap, cold, **extra):
-        doy, doys = _constant_rows(sec, doy, doys)
-        *out, keep = heat_stress_grid(stacked, anynans_, sec, doy, doys, kid, K, window, h0, level_q, steps, coldSpells=cold,
-                                      counters=counters, **extra)
-        got.extend(out)
-        return keep
-
-    mhw = run(temp, base, base, layout, tdim, on_cells, on_grid, maxPadLength, coldSpells, tstep, anynans, _compute,
-              max_batch_bytes)
-    if counters.get("n_range", 0):
-        raise XmhwException(f"{counters['n_range']} {_RANGE_TEXT}")
-    f = CellFrame(mhw.keep, mhw.cell_index, point, sdims, sshape, coords)
+    base = base_series(base, point, sdims, coords)
     J, L = steps.shape[0], level_q.shape[0]
-    counts, hsum, pq, pt, snap = (np.asarray(a) for a in got)
-    want = ((K, CHANNELS, f.C), (K, f.C), (K, f.C), (K, f.C), (J, f.C))
-    if tuple(a.shape for a in (counts, hsum, pq, pt, snap)) != want:
-        raise XmhwException(f"stress stage returned {[a.shape for a in (counts, hsum, pq, pt, snap)]}, expected {want}")
-    klass = found if found.shape[0] else np.zeros(1, dtype=np.int64)
-    attrs = {"classes": classes if isinstance(classes, str) else "array", "window": window, "min_hotspot": h0,
-             "unit": float(unit), "xmhw_parameters": mhw.attrs["xmhw_parameters"]}
-    return HeatStressDataset(klass, n_steps, f.place(counts[:, 0], 0, np.int32), f.place(counts[:, 1], 0, np.int32),
-                             f.place(counts[:, 2:2 + L], 0, np.int32), f.place(hsum, 0, np.int64), f.place(pq, 0, np.int32),
+    more = (kid, K, window, h0, level_q, steps)
+    f, (counts, hsum, pq, pt, snap), mhw = cell_stage(
+        "stress", temp, base, base, layout, tdim,
+        lambda host_keep, ts, sec, thc, doy, doys, options, **extra:
+            (_compute or heat_stress_cells)(ts, sec, doy, doys, *more, coldSpells=options[3], **extra),
+        lambda stacked, anynans_, sec, thc, doy, doys, options, **extra:
+            heat_stress_grid(stacked, anynans_, sec, doy, doys, *more, coldSpells=options[3], **extra),
+        lambda C: ((K, CHANNELS, C), (K, C), (K, C), (K, C), (J, C)), _StressAccumulators.range_texts,
+        maxPadLength=maxPadLength, coldSpells=coldSpells, tstep=tstep, anynans=anynans, _compute=_compute,
+        max_batch_bytes=max_batch_bytes)
+    attrs = stage_attrs(classes, mhw, window=window, min_hotspot=h0, unit=float(unit))
+    return HeatStressDataset(class_result_labels(found), n_steps, f.place(counts[:, 0], 0, np.int32),
+                             f.place(counts[:, 1], 0, np.int32), f.place(counts[:, 2:2 + L], 0, np.int32), f.place(hsum, 0, np.int64), f.place(pq, 0, np.int32),
                              f.place(pt, -1, np.int32), f.place(snap, 0, np.int32), steps, time[steps], f.keep, f.sdims,
                              f.coords, window, unit, np.atleast_1d(np.asarray(levels if levels is not None else (),
                                                                               dtype=np.float64)), tdim, attrs)
@@ -475,7 +399,6 @@ def maximum_monthly_mean(temp, period=None, tdim="time", offset=0.0, anynans=Fal
     of a month, mean = offset + sum_q / n_valid / 2**16.  Samples must lie within 2**7 of ``offset`` (kelvin: 273.15).
     Returns a MonthlyMeanDataset (mmm, monthly_mean, n_valid, sum_q); heat_stress() takes it as ``base``.  ``_compute``:
     a stand-in for class_sums_cells() (host tests)."""
-    from .landmask import keep_mask, stack_cells
     layout = grid_layout(temp, tdim)
     coords, _, dims, point, sdims, sshape, N = layout
     time = np.asarray(coords[tdim])
@@ -485,29 +408,15 @@ def maximum_monthly_mean(temp, period=None, tdim="time", offset=0.0, anynans=Fal
         raise XmhwException(f"offset should be finite, got {offset!r}")
     # what rides in the place of the climatologies: one row that is NaN on land, so that the series' survivors pair
     # with the accumulators' columns
-    if point:
-        land = GridSeries(np.zeros(1), ("doy",), {"doy": np.zeros(1, dtype=np.int64)})
-    else:
-        keep_host = keep_mask(stack_cells(np.asarray(temp.values), dims, tdim)[0], anynans)
-        land = GridSeries(np.where(keep_host, 0.0, np.nan).reshape((1,) + tuple(sshape)), ("doy",) + tuple(sdims),
-                          dict({d: coords[d] for d in sdims if d in coords}, doy=np.zeros(1, dtype=np.int64)))
-    got, counters = [], {}
-
-    def on_cells(host_keep, ts, sec, thc, doy, doys, minDuration, joinGaps, maxGap, cold, **extra):
-        got.extend((_compute or class_sums_cells)(ts, kid, 12, offset, counters=counters, **extra))
-
-    def on_grid(stacked, anynans_, sec, thc, doy, doys, minDuration, joinGaps, maxGap, cold, **extra):
-        *out, keep = class_sums_grid(stacked, anynans_, sec, kid, 12, offset, counters=counters, **extra)
-        got.extend(out)
-        return keep
-
-    mhw = run(temp, land, land, layout, tdim, on_cells, on_grid, None, False, False, anynans, _compute, max_batch_bytes)
-    if counters.get("n_range", 0):
-        raise XmhwException(f"{counters['n_range']} {_SUMS_RANGE_TEXT}")
-    f = CellFrame(mhw.keep, mhw.cell_index, point, sdims, sshape, coords)
-    nv, sq = (np.asarray(a) for a in got)
-    if nv.shape != (12, f.C) or sq.shape != (12, f.C):
-        raise XmhwException(f"class-sums stage returned {nv.shape}, {sq.shape}, expected {(12, f.C)}")
+    land = zero_base(ocean_mask(temp, dims, tdim, point, anynans), point, sdims, sshape, coords)
+    f, (nv, sq), _ = cell_stage(
+        "class-sums", temp, land, land, layout, tdim,
+        lambda host_keep, ts, sec, thc, doy, doys, options, **extra:
+            (_compute or class_sums_cells)(ts, kid, 12, offset, **extra),
+        lambda stacked, anynans_, sec, thc, doy, doys, options, **extra:
+            class_sums_grid(stacked, anynans_, sec, kid, 12, offset, **extra),
+        lambda C: [(12, C)] * 2, _SumsAccumulators.range_texts, anynans=anynans, _compute=_compute,
+        max_batch_bytes=max_batch_bytes)
     return MonthlyMeanDataset(f.place(nv, 0, np.int32), f.place(sq, 0, np.int64), f.keep, f.sdims, f.coords, offset, period,
                               {"period": "all" if period is None else str(tuple(period))})
 

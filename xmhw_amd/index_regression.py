@@ -25,16 +25,14 @@ geometry or the schedule.
 Host side here (validation, predictor table, class labels, slabs, land, derived fields); device side behind
 regress_cells() (a compact host series) and regress_grid() (a stacked grid, masked and compacted on the device).
 """
-import math
-
 import numpy as np
 
-from ._lib import hip, hip_regress
-from .days_by import class_labels
-from .device import DeviceScope, as_xmhw_errors
+from ._lib import hip_regress
+from .device import as_xmhw_errors
 from .exception import XmhwException
-from .heat_stress import _base_series, _constant_rows
-from .series_stage import CellFrame, check_class_ids, dense_ids, grid_layout, run, walk_cells, walk_grid, walk_stage
+from .series_stage import (Accumulators, base_series, cell_stage, check_class_ids, check_steps, class_labels,
+                           class_result_labels, dense_ids, grid_layout, run_cells, run_grid, stage_attrs)
+from .trend import p_two_sided
 
 MAX_PREDICTORS = 32             # XMHW_INDEX_REGRESS_MAX_PREDICTORS (include/xmhw_amd.h)
 MAX_CLASSES = 64                # XMHW_INDEX_REGRESS_MAX_CLASSES
@@ -46,14 +44,14 @@ _ZLIM = 1 << (BITS + RANGE_BITS)                # |zq| < 2**23
 _RANGE_TEXT = ("samples lie 2**7 and more from their base (or are infinite): is the series in kelvin and the base in "
                "degrees Celsius?")
 FIELDS = ("n", "sa", "saa", "n1", "saa1", "saz", "mz", "mzz")
+_PER_CELL = FIELDS[:5]                          # (K, C); the rest are per predictor as well, (K, J, C)
 
 
 # ---- validation (mirrors the refusals of the C entries) ----------------------------------------------
 
 def check_regress_arguments(T, classes, K, zq):
     """The stage-side check: (classes int32 (T,), K, zq int32 (T, J))"""
-    if T >= MAX_STEPS:
-        raise XmhwException(f"index_regression handles fewer than 2**17 time steps, got {T}")
+    check_steps(T, "index_regression")
     classes, K = check_class_ids(T, classes, K, MAX_CLASSES, "index_regression")
     zq = np.asarray(zq)
     if zq.ndim != 2 or zq.shape[0] != T or zq.dtype.kind not in "iu":
@@ -133,51 +131,32 @@ def quantise_predictors(X, kid, standardize):
 
 # ---- the device stage --------------------------------------------------------------------------------
 
-class _Accumulators:
-    """One call's arguments and its device accumulators (FIELDS) with the range counter.  Initialised by begin(); they
-    live across the slabs, each slab adds into its own column range, and they are read back once."""
+class _Accumulators(Accumulators):
+    """One call's arguments and its device accumulators (FIELDS) with the range counter."""
+    range_texts = {"n_range": _RANGE_TEXT}
 
     def __init__(self, classes, K, zq):
-        self.h, self.hr = hip(), hip_regress()
+        super().__init__()
+        self.hr = hip_regress()
         self.args = (classes, K, zq)
-        self.C = None
-        self._scope = DeviceScope()
-
-    def _shapes(self):
-        K, J, C = self.K, self.J, self.C
-        return {"n": ((K, C), np.int32), "sa": ((K, C), np.int64), "saa": ((K, C), np.int64), "n1": ((K, C), np.int32),
-                "saa1": ((K, C), np.int64), "saz": ((K, J, C), np.int64), "mz": ((K, J, C), np.int64),
-                "mzz": ((K, J, C), np.int64)}
 
     def begin(self, T, C):
         """T steps, C ocean cells"""
         self.classes, self.K, self.zq = check_regress_arguments(T, *self.args)
-        self.J, self.C, s = int(self.zq.shape[1]), C, self._scope
-        self.buf = {k: s.alloc(max(int(np.prod(shape)), 1) * np.dtype(dt).itemsize) for k, (shape, dt) in self._shapes().items()}
-        self.count = s.alloc(8)
+        K, J = self.K, int(self.zq.shape[1])
+        self.make(C, {k: ((K, C) if k in _PER_CELL else (K, J, C), np.int32 if k in ("n", "n1") else np.int64)
+                      for k in FIELDS})
         with as_xmhw_errors(also="Unsupported"):
-            self.hr.index_regress_init(self.K, self.J, C, *(self.buf[k].ptr for k in FIELDS), C, self.count.ptr)
+            self.hr.index_regress_init(K, J, C, *self.ptrs(), C, self.count.ptr)
 
     def add_slab(self, slab):
         """One slab (series_stage.Slab), columns k0..k0+n-1 of the accumulators; the base is where the slab carries its
         climatologies."""
-        k0 = slab.k0
-        ptrs = [self.buf[k].ptr + np.dtype(dt).itemsize * k0 for k, (_, dt) in self._shapes().items()]
         with as_xmhw_errors(also="Unsupported"):
             self.hr.index_regress_accumulate(slab.d_ts.ptr, slab.isz, slab.T, slab.n, slab.ld, slab.se_ptr, slab.ldc, slab.D,
-                                             slab.rows, self.classes, self.K, self.zq, *ptrs, self.C, self.count.ptr)
+                                             slab.rows, self.classes, self.K, self.zq, *self.ptrs(slab.k0), self.C,
+                                             self.count.ptr)
         self.h.stream_sync(0)                           # the slab's series is freed on the way out
-
-    def result(self):
-        self.h.stream_sync(0)
-        shapes = self._shapes()
-        if self.C == 0:
-            return tuple(np.zeros(shape, dt) for shape, dt in shapes.values()), 0
-        return (tuple(self.buf[k].to_array(shape, dt) for k, (shape, dt) in shapes.items()),
-                int(self.count.to_array((1,), np.int64)[0]))
-
-    def free(self):
-        self._scope.free()
 
 
 def _bytes_per_cell(T, isz, D):
@@ -190,10 +169,7 @@ def regress_cells(ts, base, doy, doys, classes, K, zq, max_batch_bytes=64 << 30,
     arrays of FIELDS.  Cells go through the device in batches below max_batch_bytes; the sums are integers, so the batch
     size does not change a single bit.  Raises if a sample is out of range (module docstring); with ``counters`` (a dict)
     it stores ``n_range`` there instead."""
-    acc = _Accumulators(classes, K, zq)
-    out, _ = walk_stage(acc, lambda a: walk_cells(ts, base, base, doy, doys, _bytes_per_cell, max_batch_bytes, pad,
-                                                  a.add_slab, a.begin), _RANGE_TEXT, counters)
-    return out
+    return run_cells(_Accumulators(classes, K, zq), ts, base, base, doy, doys, _bytes_per_cell, max_batch_bytes, pad, counters)
 
 
 def regress_grid(stacked, anynans, base, doy, doys, classes, K, zq, max_batch_bytes=None, clim_stacked=False, pad=None,
@@ -201,10 +177,8 @@ def regress_grid(stacked, anynans, base, doy, doys, classes, K, zq, max_batch_by
     """regress_cells() for an UNCOMPACTED stacked host series (T, N), float or a packed int16 view: the land mask and the
     compaction run on the device slab by slab (series_stage.walk_grid).  Returns the eight arrays over the ocean cells
     and keep[N]."""
-    acc = _Accumulators(classes, K, zq)
-    out, keep = walk_stage(acc, lambda a: walk_grid(stacked, anynans, base, base, doy, doys, lambda T, D: 4 * D * 8 + 64,
-                                                    max_batch_bytes, clim_stacked, pad, a.add_slab, begin=a.begin),
-                           _RANGE_TEXT, counters)
+    out, keep = run_grid(_Accumulators(classes, K, zq), stacked, anynans, base, base, doy, doys,
+                         lambda T, D: 4 * D * 8 + 64, max_batch_bytes, clim_stacked, pad, counters)
     return out + (keep,)
 
 
@@ -228,13 +202,6 @@ def class_totals(kid, K, zq):
         out["Z0"][k], out["Z1"][k] = before.sum(axis=0), now.sum(axis=0)
         out["ZZ0"][k], out["ZZ1"][k], out["Z01"][k] = (before ** 2).sum(axis=0), (now ** 2).sum(axis=0), (before * now).sum(axis=0)
     return out
-
-
-def _t_two_sided(t, dof):
-    from .trend import _t_sf
-    if not (dof > 0.0) or t != t:
-        return math.nan
-    return 0.0 if math.isinf(t) else min(1.0, 2.0 * _t_sf(abs(t), dof))
 
 
 class IndexRegressionDataset:
@@ -310,7 +277,7 @@ class IndexRegressionDataset:
             with np.errstate(divide="ignore", invalid="ignore"):
                 dof = self.n_eff - 2.0
                 t = self.r * np.sqrt(dof / (1.0 - self.r * self.r))
-                self._p = np.frompyfunc(_t_two_sided, 2, 1)(t, dof).astype(np.float64)
+                self._p = p_two_sided(t, dof)
         return self._p
 
     def quantisation_bound(self):
@@ -394,42 +361,26 @@ def index_regression(temp, base, indices, lags=(0,), classes="all", standardize=
     coords, _, _, point, sdims, sshape, N = layout
     time = np.asarray(coords[tdim])
     T = time.shape[0]
-    if T >= MAX_STEPS:
-        raise XmhwException(f"index_regression handles fewer than 2**17 time steps, got {T}")
+    check_steps(T, "index_regression")
     found, kid, K = dense_ids(class_labels(classes, time), MAX_CLASSES, "index_regression", "classes")
     names, lags, X = lagged_predictors(indices, lags, T)
     kid, n_dropped, zq, means, scales = quantise_predictors(X, kid, bool(standardize))
     kid, K, zq = check_regress_arguments(T, kid, K, zq)
-    base = _base_series(base, point, sdims, coords)
-    got, counters = [], {}
-
-    def on_cells(host_keep, ts, sec, thc, doy, doys, minDuration, joinGaps, maxGap, cold, **extra):
-        doy, doys = _constant_rows(sec, doy, doys)
-        got.extend((_compute or regress_cells)(ts, sec, doy, doys, kid, K, zq, counters=counters, **extra))
-
-    def on_grid(stacked, anynans_, sec, thc, doy, doys, minDuration, joinGaps, maxGap, cold, **extra):
-        doy, doys = _constant_rows(sec, doy, doys)
-        *out, keep = regress_grid(stacked, anynans_, sec, doy, doys, kid, K, zq, counters=counters, **extra)
-        got.extend(out)
-        return keep
-
-    mhw = run(temp, base, base, layout, tdim, on_cells, on_grid, maxPadLength, False, tstep, anynans, _compute,
-              max_batch_bytes)
-    if counters.get("n_range", 0):
-        raise XmhwException(f"{counters['n_range']} {_RANGE_TEXT}")
-    f = CellFrame(mhw.keep, mhw.cell_index, point, sdims, sshape, coords)
+    base = base_series(base, point, sdims, coords)
     I, L, J = len(names), lags.shape[0], zq.shape[1]
-    arrays = [np.asarray(a) for a in got]
-    want = [(K, f.C)] * 5 + [(K, J, f.C)] * 3
-    if [a.shape for a in arrays] != want:
-        raise XmhwException(f"regression stage returned {[a.shape for a in arrays]}, expected {want}")
+    f, arrays, mhw = cell_stage(
+        "regression", temp, base, base, layout, tdim,
+        lambda host_keep, ts, sec, thc, doy, doys, options, **extra:
+            (_compute or regress_cells)(ts, sec, doy, doys, kid, K, zq, **extra),
+        lambda stacked, anynans_, sec, thc, doy, doys, options, **extra:
+            regress_grid(stacked, anynans_, sec, doy, doys, kid, K, zq, **extra),
+        lambda C: [(K, C)] * 5 + [(K, J, C)] * 3, _Accumulators.range_texts, maxPadLength=maxPadLength, tstep=tstep,
+        anynans=anynans, _compute=_compute, max_batch_bytes=max_batch_bytes)
     raw = {}
     for k, a in zip(FIELDS, arrays):
         a = a.reshape((K, I, L, f.C)) if a.ndim == 3 else a
         raw[k] = f.place(a, 0, np.int32 if k in ("n", "n1") else np.int64)
     totals = class_totals(kid, K, zq)
-    klass = found if found.shape[0] else np.zeros(1, dtype=np.int64)
-    attrs = {"classes": classes if isinstance(classes, str) else "array", "standardize": bool(standardize),
-             "xmhw_parameters": mhw.attrs["xmhw_parameters"]}
-    return IndexRegressionDataset(klass, totals["N"], names, lags, n_dropped, means, scales, totals, raw, f.keep, f.sdims,
-                                  f.coords, tdim, attrs)
+    attrs = stage_attrs(classes, mhw, standardize=bool(standardize))
+    return IndexRegressionDataset(class_result_labels(found), totals["N"], names, lags, n_dropped, means, scales, totals, raw,
+                                  f.keep, f.sdims, f.coords, tdim, attrs)

@@ -28,14 +28,14 @@ import math
 
 import numpy as np
 
-from ._lib import hip, hip_lagcorr
-from .cooccurrence import _same_axis
-from .days_by import class_labels
+from ._lib import hip_lagcorr
+from .api import GridSeries, _from_xarray, _is_xarray
 from .device import DeviceScope, as_xmhw_errors
 from .exception import XmhwException
-from .heat_stress import _base_series, _constant_rows
-from .index_regression import _t_two_sided
-from .series_stage import CellFrame, check_class_ids, dense_ids, grid_layout, run, walk_cells, walk_grid
+from .series_stage import (Accumulators, base_series, cell_stage, check_class_ids, check_same_frame, check_steps, class_labels,
+                           class_result_labels, dense_ids, grid_layout, ocean_mask, run_cells, run_grid, stage_attrs,
+                           zero_base)
+from .trend import _t_two_sided, p_two_sided                 # noqa: F401  (_t_two_sided: the host tests reach it here)
 
 MAX_LAG = 63                    # XMHW_LAG_CORR_MAX_LAG (include/xmhw_amd.h)
 MAX_CLASSES = 64                # XMHW_LAG_CORR_MAX_CLASSES
@@ -48,9 +48,11 @@ _SWAPPED = ("n", "sy", "sx", "syy", "sxx", "sxy")       # the same sums with the
 BYTES_PER_ENTRY = 44            # int32 n and five int64 sums
 
 
-def _range_text(count, name, shift):
-    return (f"{count} samples of {name} lie 2**(7 + shift_{name}) and more from their base (or are infinite) with "
-            f"shift_{name} = {shift}: pass a larger shift_{name} (heat flux in W m-2 needs a shift of 4 or so)")
+def _range_texts(shift_x, shift_y):
+    """the refusal of out-of-range samples of each field, by the key of its counter"""
+    return {f"n_range_{name}": (f"samples of {name} lie 2**(7 + shift_{name}) and more from their base (or are infinite) with "
+                                f"shift_{name} = {shift}: pass a larger shift_{name} (heat flux in W m-2 needs a shift of 4 or so)")
+            for name, shift in (("x", shift_x), ("y", shift_y))}
 
 
 # ---- validation (mirrors the refusals of the C entries) ----------------------------------------------
@@ -82,11 +84,6 @@ def check_shifts(shift_x, shift_y):
     return int(shift_x), int(shift_y)
 
 
-def check_steps(T):
-    if T >= MAX_STEPS:
-        raise XmhwException(f"lag_correlation handles fewer than 2**17 time steps, got {T}")
-
-
 def check_result_bytes(K, lo, hi, C, max_result_bytes):
     """the (K, lags, C) accumulators, 44 bytes an entry, live on the device across the slabs and come back whole"""
     need = BYTES_PER_ENTRY * K * (hi - lo + 1) * C
@@ -109,43 +106,38 @@ def assemble(first, second, lo, hi, auto):
 
 # ---- the device stage --------------------------------------------------------------------------------
 
-class _Accumulators:
-    """One call's arguments and its device accumulators (FIELDS, (K, L + 1, C)) with the two range counters, for the pass
-    over (x, y) and, for negative lags of two fields, a second set for the pass over (y, x).  Initialised by begin();
-    they live across the slabs, each slab adds into its own column range, and they are read back once.  ``second(slab)``
-    gives the slab's columns of y on the device, or None for an autocorrelation."""
+class _Accumulators(Accumulators):
+    """One call's arguments and its device accumulators (FIELDS, (K, L + 1, C)) with the two range counters of the pass
+    over (x, y); for negative lags of two fields ``back`` is a second set of the same table, in the same scope, for the
+    pass over (y, x).  ``second(slab)`` gives the slab's columns of y on the device, or None for an autocorrelation."""
 
     def __init__(self, second, classes, K, lo, hi, shift_x, shift_y, max_result_bytes):
-        self.h, self.hl = hip(), hip_lagcorr()
+        super().__init__()
+        self.hl = hip_lagcorr()
         self.second, self.args = second, (classes, K)
         self.lo, self.hi = check_lags((lo, hi))
         self.shift_x, self.shift_y = check_shifts(shift_x, shift_y)
+        self.range_texts = _range_texts(self.shift_x, self.shift_y)
         self.max_result_bytes = max_result_bytes
-        self.C = None
-        self._scope = DeviceScope()
-
-    def _shapes(self, L):
-        return {k: ((self.K, L + 1, self.C), np.int32 if k == "n" else np.int64) for k in FIELDS}
 
     def begin(self, T, C):
         """T steps, C ocean cells"""
-        check_steps(T)
+        check_steps(T, "lag_correlation")
         self.classes, self.K = check_class_ids(T, *self.args, MAX_CLASSES, "lag_correlation")
         check_result_bytes(self.K, self.lo, self.hi, C, self.max_result_bytes)
-        self.C, s = C, self._scope
         # the largest lag of each pass: (x, y), and (y, x) where two fields have negative lags; the one pass of an
         # autocorrelation serves both signs
-        if self.second is None:
-            self.passes = [max(self.hi, -self.lo)]
-        else:
-            self.passes = [self.hi] + ([-self.lo] if self.lo < 0 else [])
-        self.buf, self.count = [], []
-        for L in self.passes:
-            self.buf.append({k: s.alloc(max(int(np.prod(shape)), 1) * np.dtype(dt).itemsize)
-                             for k, (shape, dt) in self._shapes(L).items()})
-            self.count.append(s.alloc(16))
+        two = self.second is not None and self.lo < 0
+        self.L = self.hi if self.second is not None else max(self.hi, -self.lo)
+        self.passes = [self]
+        if two:
+            self.back = Accumulators(self._scope)
+            self.back.L = -self.lo
+            self.passes.append(self.back)
+        for p in self.passes:
+            p.make(C, {k: ((self.K, p.L + 1, C), np.int32 if k == "n" else np.int64) for k in FIELDS}, counters=2)
             with as_xmhw_errors(also="Unsupported"):
-                self.hl.lag_corr_init(self.K, L, C, *(self.buf[-1][k].ptr for k in FIELDS), C, self.count[-1].ptr)
+                self.hl.lag_corr_init(self.K, p.L, C, *p.ptrs(), C, p.count.ptr)
 
     def add_slab(self, slab):
         """One slab (series_stage.Slab), columns k0..k0+n-1 of the accumulators; base_x is where the slab carries se,
@@ -154,57 +146,25 @@ class _Accumulators:
             d_y = None if self.second is None else s.adopt(self.second(slab))
             x = (slab.d_ts.ptr, slab.ld, slab.se_ptr, slab.ldc, self.shift_x)
             y = x if d_y is None else (d_y.ptr, slab.n, slab.th_ptr, slab.ldc, self.shift_y)
-            for i, L in enumerate(self.passes):
-                a, b = (x, y) if i == 0 else (y, x)
-                ptrs = [self.buf[i][k].ptr + np.dtype(dt).itemsize * slab.k0 for k, (_, dt) in self._shapes(L).items()]
+            for p in self.passes:
+                a, b = (x, y) if p is self else (y, x)
                 with as_xmhw_errors(also="Unsupported"):
                     self.hl.lag_corr_accumulate(a[0], a[1], b[0], b[1], slab.isz, slab.T, slab.n, a[2], a[3], b[2], b[3],
-                                                slab.D, slab.rows, a[4], b[4], self.classes, self.K, L, *ptrs, self.C,
-                                                self.count[i].ptr)
+                                                slab.D, slab.rows, a[4], b[4], self.classes, self.K, p.L, *p.ptrs(slab.k0),
+                                                self.C, p.count.ptr)
             self.h.stream_sync(0)                       # the slab's series are freed on the way out
 
     def result(self):
-        """(the six arrays over the lags lo .. hi, (n_range of x, n_range of y))"""
+        """(the six arrays over the lags lo .. hi, {n_range_x, n_range_y})"""
         self.h.stream_sync(0)
-        got, counts = [], []
-        for i, L in enumerate(self.passes):
-            shapes = self._shapes(L)
-            if self.C == 0:
-                got.append(tuple(np.zeros(shape, dt) for shape, dt in shapes.values()))
-                counts.append((0, 0))
-            else:
-                got.append(tuple(self.buf[i][k].to_array(shape, dt) for k, (shape, dt) in shapes.items()))
-                counts.append(tuple(int(v) for v in self.count[i].to_array((2,), np.int64)))
+        got, counts = [p.read() for p in self.passes], [p.counts() for p in self.passes]
         # x is a partner on every step in the second pass, and in an autocorrelation: that count holds the other
         if self.second is None:
             n_range = (counts[0][1], 0)
         else:
             n_range = (counts[1][1] if len(counts) > 1 else counts[0][0], counts[0][1])
-        return assemble(got[0], got[1] if len(got) > 1 else None, self.lo, self.hi, self.second is None), n_range
-
-    def free(self):
-        self._scope.free()
-
-
-def _walk(acc, walker, counters, shifts):
-    """one stage call around its accumulators, freed whatever happens; the range counts go into ``counters`` (a dict) or
-    raise"""
-    try:
-        keep = walker(acc)
-        out, n_range = acc.result()
-    finally:
-        acc.free()
-    report_range(n_range, counters, shifts)
-    return out, keep
-
-
-def report_range(n_range, counters, shifts):
-    if counters is not None:
-        counters["n_range_x"], counters["n_range_y"] = int(n_range[0]), int(n_range[1])
-        return
-    for count, name, shift in zip(n_range, "xy", shifts):
-        if count:
-            raise XmhwException(_range_text(int(count), name, shift))
+        return (assemble(got[0], got[1] if len(got) > 1 else None, self.lo, self.hi, self.second is None),
+                dict(zip(self.range_texts, n_range)))
 
 
 def _bytes_per_cell(T, isz, D, two):
@@ -234,11 +194,9 @@ def lag_corr_cells(x, y, base_x, base_y, doy, doys, classes, K, lo, hi, shift_x=
             if pad is not None:
                 pad.apply(d.ptr, slab.isz, slab.T, slab.n)
             return d
-    acc = _Accumulators(second, classes, K, lo, hi, shift_x, shift_y, max_result_bytes)
-    per_cell = lambda T, isz, D: _bytes_per_cell(T, isz, D, y is not None)                         # noqa: E731
-    out, _ = _walk(acc, lambda a: walk_cells(x, base_x, base_x if y is None else base_y, doy, doys, per_cell,
-                                             max_batch_bytes, pad, a.add_slab, a.begin), counters, (shift_x, shift_y))
-    return out
+    return run_cells(_Accumulators(second, classes, K, lo, hi, shift_x, shift_y, max_result_bytes), x, base_x,
+                     base_x if y is None else base_y, doy, doys, lambda T, isz, D: _bytes_per_cell(T, isz, D, y is not None),
+                     max_batch_bytes, pad, counters)
 
 
 def lag_corr_grid(stacked, anynans, ystacked, base_x, base_y, doy, doys, classes, K, lo, hi, shift_x=0, shift_y=0,
@@ -272,12 +230,10 @@ def lag_corr_grid(stacked, anynans, ystacked, base_x, base_y, doy, doys, classes
             return d_raw
     two = ystacked is not None
     isz_y = device_itemsize(ystacked) if two else 0
-    acc = _Accumulators(second, classes, K, lo, hi, shift_x, shift_y, max_result_bytes)
     # y's bytes per cell: the uploaded columns and the gathered ones
-    extra = lambda T, D: 4 * D * 8 + 64 + 2 * T * isz_y                                             # noqa: E731
-    out, keep = _walk(acc, lambda a: walk_grid(stacked, anynans, base_x, base_x if not two else base_y, doy, doys, extra,
-                                               max_batch_bytes, clim_stacked, pad, a.add_slab, begin=a.begin),
-                      counters, (shift_x, shift_y))
+    out, keep = run_grid(_Accumulators(second, classes, K, lo, hi, shift_x, shift_y, max_result_bytes), stacked, anynans,
+                         base_x, base_x if not two else base_y, doy, doys, lambda T, D: 4 * D * 8 + 64 + 2 * T * isz_y,
+                         max_batch_bytes, clim_stacked, pad, counters)
     return out + (keep,)
 
 
@@ -413,7 +369,7 @@ class LagCorrelationDataset:
         with np.errstate(divide="ignore", invalid="ignore"):
             dof = np.broadcast_to(ne - 2.0, self.r.shape)
             t = self.r * np.sqrt(dof / (1.0 - self.r * self.r))
-            return np.frompyfunc(_t_two_sided, 2, 1)(t, dof).astype(np.float64)
+            return p_two_sided(t, dof)
 
     def to_xarray(self):
         import xarray as xr
@@ -427,22 +383,13 @@ class LagCorrelationDataset:
 
 # ---- the public function -----------------------------------------------------------------------------
 
-def _ocean_of(field, dims, tdim, point, anynans):
-    from .landmask import keep_mask, stack_cells
-    if point:
-        return np.array([True])
-    values = field.values if hasattr(field, "values") else field
-    return keep_mask(stack_cells(np.asarray(values), dims, tdim)[0], anynans)
-
-
 def _base_on_ocean(base, ocean, point, sdims, sshape, coords, name):
     """``base`` as the ('doy', ...) GridSeries that pairs with the ocean cells of x as a climatology does: None is zero;
     NaN on the land of x and, where the base itself is missing on an ocean cell of x (a cell that is land in y), zero --
     the samples there are NaN anyway"""
-    from .api import GridSeries
     if base is None:
-        base = 0.0 if point else np.zeros(sshape)
-    base = _base_series(base, point, sdims, coords)
+        return zero_base(ocean, point, sdims, sshape, coords)
+    base = base_series(base, point, sdims, coords)
     if point:
         return base
     v = np.asarray(base.values, dtype=np.float64)
@@ -475,7 +422,6 @@ def lag_correlation(x, y=None, base_x=None, base_y=None, lags=(0, 30), classes="
 
     Returns a LagCorrelationDataset.  Raises if a sample is out of range.  ``_compute``: a stand-in for lag_corr_cells()
     (host tests)."""
-    from .api import GridSeries, _from_xarray, _is_xarray
     from .landmask import stack_cells
     lo, hi = check_lags(lags)
     shift_x, shift_y = check_shifts(shift_x, shift_y)
@@ -488,19 +434,11 @@ def lag_correlation(x, y=None, base_x=None, base_y=None, lags=(0, 30), classes="
     coords, _, dims, point, sdims, sshape, N = layout
     time = np.asarray(coords[tdim])
     T = time.shape[0]
-    check_steps(T)
+    check_steps(T, "lag_correlation")
     ydims = None
     if not auto:
         ycoords, _, ydims, ypoint, ysdims, ysshape, _ = grid_layout(y, tdim)
-        if bool(ypoint) != bool(point):
-            raise XmhwException("lag_correlation cannot pair a single-point series with a grid")
-        if not point and (tuple(ysdims) != tuple(sdims) or tuple(ysshape) != tuple(sshape)):
-            raise XmhwException(f"x and y are not on the same grid: {tuple(sdims)} {tuple(sshape)} and "
-                                f"{tuple(ysdims)} {tuple(ysshape)}")
-        if np.asarray(ycoords[tdim]).shape[0] != T:
-            raise XmhwException(f"x and y have {T} and {np.asarray(ycoords[tdim]).shape[0]} time steps")
-        if not _same_axis(time, ycoords[tdim]):
-            raise XmhwException("x and y do not have the same time axis")
+        check_same_frame("lag_correlation", "x", "y", (point, sdims, sshape), time, (ypoint, ysdims, ysshape), ycoords[tdim])
         xv, yv = np.asarray(x.values), np.asarray(y.values)
         if xv.dtype != yv.dtype or xv.dtype.kind != "f":
             # one float type on the device: float64 holds both
@@ -509,7 +447,7 @@ def lag_correlation(x, y=None, base_x=None, base_y=None, lags=(0, 30), classes="
             x, y = as64(x, xv, dims), as64(y, yv, ydims)
             layout = grid_layout(x, tdim)
     found, kid, K = dense_ids(class_labels(classes, time), MAX_CLASSES, "lag_correlation", "classes")
-    ocean = _ocean_of(x, dims, tdim, point, anynans)
+    ocean = ocean_mask(x, dims, tdim, point, anynans)
     bx = _base_on_ocean(base_x, ocean, point, sdims, sshape, coords, "base_x")
     by = bx if auto else _base_on_ocean(base_y, ocean, point, sdims, sshape, coords, "base_y")
     if not auto:
@@ -526,36 +464,24 @@ def lag_correlation(x, y=None, base_x=None, base_y=None, lags=(0, 30), classes="
     ystack = None
     if not auto:
         ystack = (np.asarray(y.values).reshape(-1, 1) if point else stack_cells(np.asarray(y.values), ydims, tdim)[0])
-    got, counters = [], {}
+    more = (kid, K, lo, hi, shift_x, shift_y)
 
-    def on_cells(host_keep, ts, sec, thc, doy, doys, minDuration, joinGaps, maxGap, cold, **extra):
-        doy, doys = _constant_rows(sec, doy, doys)
+    def on_cells(host_keep, ts, sec, thc, doy, doys, options, **extra):
         check_result_bytes(K, lo, hi, ts.shape[1], max_result_bytes)
         ycells = None if auto else (ystack if point else ystack[:, host_keep()])
-        got.extend((_compute or lag_corr_cells)(ts, ycells, sec, None if auto else thc, doy, doys, kid, K, lo, hi, shift_x,
-                                                shift_y, counters=counters, max_result_bytes=max_result_bytes, **extra))
+        return (_compute or lag_corr_cells)(ts, ycells, sec, None if auto else thc, doy, doys, *more,
+                                            max_result_bytes=max_result_bytes, **extra)
 
-    def on_grid(stacked, anynans_, sec, thc, doy, doys, minDuration, joinGaps, maxGap, cold, **extra):
-        doy, doys = _constant_rows(sec, doy, doys)
-        *out, keep = lag_corr_grid(stacked, anynans_, ystack, sec, None if auto else thc, doy, doys, kid, K, lo, hi, shift_x,
-                                   shift_y, counters=counters, max_result_bytes=max_result_bytes, **extra)
-        got.extend(out)
-        return keep
-
-    mhw = run(x, by, bx, layout, tdim, on_cells, on_grid, maxPadLength, False, False, anynans, _compute, max_batch_bytes)
-    for name, shift in (("x", shift_x), ("y", shift_y)):
-        if counters.get(f"n_range_{name}", 0):
-            raise XmhwException(_range_text(counters[f"n_range_{name}"], name, shift))
-    f = CellFrame(mhw.keep, mhw.cell_index, point, sdims, sshape, coords)
-    arrays = [np.asarray(a) for a in got]
-    want = [(K, hi - lo + 1, f.C)] * 6
-    if [a.shape for a in arrays] != want:
-        raise XmhwException(f"lag correlation stage returned {[a.shape for a in arrays]}, expected {want}")
+    f, arrays, mhw = cell_stage(
+        "lag correlation", x, by, bx, layout, tdim, on_cells,
+        lambda stacked, anynans_, sec, thc, doy, doys, options, **extra:
+            lag_corr_grid(stacked, anynans_, ystack, sec, None if auto else thc, doy, doys, *more,
+                          max_result_bytes=max_result_bytes, **extra),
+        lambda C: [(K, hi - lo + 1, C)] * 6, _range_texts(shift_x, shift_y), maxPadLength=maxPadLength, anynans=anynans,
+        _compute=_compute, max_batch_bytes=max_batch_bytes)
     raw = [f.place(a, 0, np.int32 if k == "n" else np.int64) for k, a in zip(FIELDS, arrays)]
-    klass = found if found.shape[0] else np.zeros(1, dtype=np.int64)
-    attrs = {"classes": classes if isinstance(classes, str) else "array", "xmhw_parameters": mhw.attrs["xmhw_parameters"]}
-    out = LagCorrelationDataset(klass, np.arange(lo, hi + 1), *raw, f.keep, f.sdims, f.coords, auto, shift_x, shift_y, tdim,
-                                attrs)
+    out = LagCorrelationDataset(class_result_labels(found), np.arange(lo, hi + 1), *raw, f.keep, f.sdims, f.coords, auto,
+                                shift_x, shift_y, tdim, stage_attrs(classes, mhw))
     land = ~np.asarray(out.keep, dtype=bool)
     if not point:
         for a in (out.mean_x, out.mean_y, out.cov, out.r, out.slope):

@@ -1,28 +1,39 @@
-"""What the stages that read the series and the climatologies together share ("What 3.7, 3.11 and 3.16
-share"): mhw_coverage(), mhw_track_intensity() and mhw_days_by() reduce them over the event steps, and each is a slab
-method on top of the things that exist once, here:
+"""The stage layer: what the stages that walk the series slab by slab share ("What 3.7, 3.11 and 3.16
+share").  mhw_coverage(), mhw_track_intensity(), mhw_days_by(), heat_stress() / maximum_monthly_mean(),
+index_regression(), mhw_composite() and lag_correlation() are each a ``begin(T, C)`` / ``add_slab(slab)`` pair on top of
+the things that exist once, here:
 
 * Slab                      one slab of cells on the device, as the slab methods take it;
 * climatologies_on_device() seas / thresh whole on the device, compacted there if needed (detect_grid() uses it too);
 * walk_cells(), walk_grid() the dense and the grid slab walker;
+* Accumulators              the base of every stage's accumulator class: scope, named device arrays with the cell axis
+                            last, their pointers at a column, the range counters, the read-back, free();
+* run_cells(), run_grid(), report_range()   one stage call: an Accumulators object over a walker, freed whatever happens,
+                            and what becomes of its out-of-range counts;
 * run()                     the one shim around detect._detect();
-* dense_ids(), check_class_ids(), check_weighted_cells()    labels and the stage-side checks of per-cell arguments;
+* cell_stage(), class_result_labels(), stage_attrs()    the tail of the public per-cell functions: run(), the range
+                            raise, the CellFrame and the shape check of what the stage returned;
+* class_labels(), dense_ids(), check_class_ids(), check_weighted_cells(), check_steps(), check_view()    labels and the
+                            stage-side checks of per-call and per-cell arguments;
+* base_series(), constant_rows(), ocean_mask(), zero_base()    a base in the place of the climatologies;
+* same_axis(), check_same_frame()   a second input on the grid and time axis of the first;
 * regions_of_result()       the regions found on ocean cells (mhw_coverage(), region_series());
-* walk_stage(), report_range()      one stage call around its accumulators, and its out-of-range count (mhw_days_by(),
-                            heat_stress());
-* CellFrame, grid_frame(), cells_to_grid()      per-cell results back on the grid (mhw_days_by(), mhw_cooccurrence(),
-                            mhw_displacement(), heat_stress());
+* CellFrame, grid_frame(), cells_to_grid()      per-cell results back on the grid;
 * grid_layout()             the spatial layout of a GridSeries / DataArray.
 """
 from collections import namedtuple
 
 import numpy as np
 
+from . import calendar as cal
+from ._lib import hip
 from .api import GridSeries, _from_xarray, _is_xarray
 from .device import DeviceScope
 from .exception import XmhwException
 
 LAND_TEXT = "All points of grid are either land or NaN"
+NAMED_CLASSES = ("all", "month", "season", "year")
+MAX_STEPS = 1 << 17             # XMHW_*_MAX_STEPS (include/xmhw_amd.h) of the entries that pack a step into 17 bits
 
 
 class Slab(namedtuple("Slab", "d_ts isz T n ld se_ptr th_ptr ldc D rows k0 cols")):
@@ -174,10 +185,7 @@ def run(temp, th, se, layout, tdim, cells_stage, grid_stage, maxPadLength, coldS
     coords, coord_attrs, dims, point = layout[:4]
 
     def host_keep():
-        from .landmask import keep_mask, stack_cells
-        if point:
-            return np.array([True])
-        return keep_mask(stack_cells(np.asarray(temp.values), dims, tdim)[0], anynans)
+        return ocean_mask(temp, dims, tdim, point, anynans)
 
     def no_events(C, **more):
         return dict(table=np.zeros((0, 31)), offsets=np.zeros(C + 1, dtype=np.int64), inter=None, **more)
@@ -199,6 +207,34 @@ def run(temp, th, se, layout, tdim, cells_stage, grid_stage, maxPadLength, coldS
     as_series = lambda a: GridSeries(a.values, a.dims, _from_xarray(a)[0]) if _is_xarray(a) else a   # noqa: E731
     return _detect(series, as_series(th), as_series(se), on_cells, tdim, minDuration, joinGaps, maxGap, maxPadLength,
                    coldSpells, False, anynans, tstep, grid_compute=None if _compute is not None else on_grid)
+
+
+def class_labels(classes, time):
+    """The ``classes`` argument as labels per time step: an integer array of length T as it is, or a named form taken from
+    a datetime64 time axis -- "all" (one class 0), "month" (1..12), "season" (DJF, MAM, JJA, SON = 0..3), "year" (the
+    calendar year)."""
+    time = np.asarray(time)
+    T = time.shape[0]
+    if isinstance(classes, str):
+        if classes not in NAMED_CLASSES:
+            raise XmhwException(f"classes should be an integer array or one of {NAMED_CLASSES}, got {classes!r}")
+        if classes == "all":
+            return np.zeros(T, dtype=np.int64)
+        if time.dtype.kind != "M":
+            raise XmhwException(f"classes={classes!r} needs a datetime64 time coordinate, got {time.dtype}: pass the class "
+                                "of every time step as an integer array instead")
+        year, month, _, _ = cal._fields(time)
+        if classes == "month":
+            return month.astype(np.int64)
+        if classes == "season":
+            return (month % 12) // 3
+        return year.astype(np.int64)
+    labels = np.asarray(classes)
+    if labels.dtype.kind not in "iu":
+        raise XmhwException(f"classes should be an integer array, got {labels.dtype}")
+    if labels.shape != (T,):
+        raise XmhwException(f"classes should have one entry per time step ({T}), got shape {labels.shape}")
+    return labels.astype(np.int64)
 
 
 def dense_ids(labels, cap, who, what):
@@ -264,26 +300,247 @@ def regions_of_result(keep, rid, w, found):
     return sel, ncells[sel], total[sel], found[sel]
 
 
-def report_range(n_range, counters, text):
-    """What a stage does with its count of samples outside the fixed-point range: into ``counters`` (a dict) when the
-    caller collects it, otherwise an exception worded by ``text``."""
+class Accumulators:
+    """The base of a stage's accumulator class: the device arrays of one call, which live across the slabs -- each slab
+    adds into its own column range -- and are read back once.  A stage adds ``begin(T, C)`` (its argument checks,
+    make(), its init entry), ``add_slab(slab)`` (its launches) and, where it has one, ``finish()``; ``range_texts`` maps
+    the key of each of its out-of-range counters to the text of the refusal, in the order of the counters."""
+    range_texts = {}
+
+    def __init__(self, scope=None):
+        self.h, self.C = hip(), None
+        self._scope = DeviceScope() if scope is None else scope
+        self._table, self._buf, self.count = {}, {}, None
+
+    def make(self, C, table, counters=None):
+        """allocate the arrays of ``table``, name -> (shape, dtype) in the order they are read back, and ``counters``
+        int64 range counters (default: one per range text).  C: the cells, the last axis of every shape (None: the
+        arrays are not per cell)."""
+        self.C, self._table = C, dict(table)
+        self._buf = {k: self._scope.alloc(max(int(np.prod(shape)), 1) * np.dtype(dt).itemsize)
+                     for k, (shape, dt) in self._table.items()}
+        self.n_counters = len(self.range_texts) if counters is None else counters
+        if self.n_counters:
+            self.count = self._scope.alloc(8 * self.n_counters)
+
+    def ptrs(self, k0=0, names=None):
+        """the device pointers of the arrays (``names``: of those, in that order) at column k0"""
+        return [self._buf[k].ptr + np.dtype(self._table[k][1]).itemsize * k0 for k in (names or self._table)]
+
+    def read(self, names=None):
+        """the arrays on the host, in table order; an empty one (no cells) is not read"""
+        return tuple(self._buf[k].to_array(shape, dt) if int(np.prod(shape)) else np.zeros(shape, dt)
+                     for k, (shape, dt) in ((k, self._table[k]) for k in (names or self._table)))
+
+    def counts(self):
+        """the range counters as ints"""
+        if self.C == 0 or not self.n_counters:
+            return (0,) * self.n_counters
+        return tuple(int(v) for v in self.count.to_array((self.n_counters,), np.int64))
+
+    def finish(self):
+        """what a stage queues once after the last slab"""
+
+    def result(self):
+        """(the arrays, {key of range_texts: count})"""
+        if self.C != 0:
+            self.finish()
+        self.h.stream_sync(0)
+        return self.read(), dict(zip(self.range_texts, self.counts()))
+
+    def free(self):
+        self._scope.free()
+
+
+def report_range(n_range, counters, texts):
+    """What a stage does with its counts of samples outside the fixed-point range, ``n_range`` {key: count}: into
+    ``counters`` (a dict) when the caller collects them, otherwise an exception worded by ``texts`` {key: text} for the
+    first that is not zero."""
     if counters is not None:
-        counters["n_range"] = int(n_range)
-    elif n_range:
-        raise XmhwException(f"{int(n_range)} {text}")
+        counters.update((k, int(v)) for k, v in n_range.items())
+        return
+    for k, v in n_range.items():
+        if v:
+            raise XmhwException(f"{int(v)} {texts[k]}")
 
 
-def walk_stage(acc, walker, text, counters):
-    """One stage call around its accumulators (begin(), add_slab(), result() -> (arrays, n_range), free()):
-    ``walker(acc)`` sends the slabs through them and returns keep[N] or None; the accumulators are freed whatever
-    happens, then the range count is reported.  Returns (arrays, keep)."""
+def _run_stage(acc, walk, counters):
     try:
-        keep = walker(acc)
+        keep = walk()
         out, n_range = acc.result()
     finally:
         acc.free()
-    report_range(n_range, counters, text)
+    report_range(n_range, counters, acc.range_texts)
     return out, keep
+
+
+def run_cells(acc, ts, seas, thresh, doy, doys, per_cell, max_batch_bytes, pad, counters=None):
+    """One stage call over a dense series: the slabs of walk_cells() go through ``acc`` (an Accumulators), which is
+    freed whatever happens; then the range counts are reported (report_range()).  Returns what acc.result() read."""
+    return _run_stage(acc, lambda: walk_cells(ts, seas, thresh, doy, doys, per_cell, max_batch_bytes, pad, acc.add_slab,
+                                              acc.begin), counters)[0]
+
+
+def run_grid(acc, stacked, anynans, seas, thresh, doy, doys, per_cell_extra, max_batch_bytes, clim_stacked, pad,
+             counters=None, begin_with=None, check_keep=None):
+    """run_cells() over an uncompacted grid (walk_grid()).  ``begin_with``: None lets the walker call acc.begin(T, C)
+    with the ocean cells of the climatologies; a tuple is what acc.begin() is called with before the walk, for a stage
+    whose per-cell arguments are not those of the ocean cells.  ``check_keep``: as in walk_grid().  Returns (what
+    acc.result() read, keep[N])."""
+    def walk():
+        if begin_with is not None:
+            acc.begin(*begin_with)
+        return walk_grid(stacked, anynans, seas, thresh, doy, doys, per_cell_extra, max_batch_bytes, clim_stacked, pad,
+                         acc.add_slab, check_keep=check_keep, begin=acc.begin if begin_with is None else None)
+    return _run_stage(acc, walk, counters)
+
+
+def cell_stage(who, temp, th, se, layout, tdim, cells_stage, grid_stage, want, range_texts, based=True, maxPadLength=None,
+               coldSpells=False, tstep=False, anynans=False, _compute=None, max_batch_bytes=None, detect_options=()):
+    """The tail that the public per-cell functions share: run() around the two stages of one function, the refusal of
+    out-of-range samples, the CellFrame of the result and the shape check of what the stage returned.
+
+    ``cells_stage(host_keep, ts, sec, thc, doy, doys, options, **extra)`` returns the stage's arrays for the series that
+    _detect() compacted on the host; ``grid_stage(stacked, anynans, sec, thc, doy, doys, options, **extra)`` returns them
+    and keep[N].  ``options`` is (minDuration, joinGaps, maxGap, coldSpells); ``extra`` holds ``counters`` and what run()
+    adds.  ``based``: th / se are a base, whose single row pairs with every step (constant_rows()).  ``want(C)``: the
+    shapes expected for C cells; ``who`` names the stage in the message.  ``range_texts``: as Accumulators.range_texts.
+    Returns (the CellFrame, the arrays, the EventDataset of run())."""
+    got, counters = [], {}
+
+    def on_cells(host_keep, ts, sec, thc, doy, doys, *options, **extra):
+        if based:
+            doy, doys = constant_rows(sec, doy, doys)
+        got.extend(cells_stage(host_keep, ts, sec, thc, doy, doys, options, counters=counters, **extra))
+
+    def on_grid(stacked, anynans_, sec, thc, doy, doys, *options, **extra):
+        if based:
+            doy, doys = constant_rows(sec, doy, doys)
+        *out, keep = grid_stage(stacked, anynans_, sec, thc, doy, doys, options, counters=counters, **extra)
+        got.extend(out)
+        return keep
+
+    mhw = run(temp, th, se, layout, tdim, on_cells, on_grid, maxPadLength, coldSpells, tstep, anynans, _compute,
+              max_batch_bytes, *detect_options)
+    for key, text in range_texts.items():
+        if counters.get(key, 0):
+            raise XmhwException(f"{counters[key]} {text}")
+    coords, point, sdims, sshape = layout[0], layout[3], layout[4], layout[5]
+    f = CellFrame(mhw.keep, mhw.cell_index, point, sdims, sshape, coords)
+    arrays = [np.asarray(a) for a in got]
+    if [a.shape for a in arrays] != list(want(f.C)):
+        raise XmhwException(f"{who} stage returned {[a.shape for a in arrays]}, expected {want(f.C)}")
+    return f, arrays, mhw
+
+
+def class_result_labels(found):
+    """the klass axis of a result: the labels found, or the one class 0 of a call that labels no step"""
+    return found if found.shape[0] else np.zeros(1, dtype=np.int64)
+
+
+def stage_attrs(classes, mhw, **more):
+    """the attrs that the per-class results share, ``more`` between them"""
+    return {"classes": classes if isinstance(classes, str) else "array", **more,
+            "xmhw_parameters": mhw.attrs["xmhw_parameters"]}
+
+
+# ---- a base in the place of the climatologies, a second input beside the first ------------------------------------
+
+def constant_rows(sec, doy, doys):
+    """a one-row baseline pairs with every step: its labels are not day-of-year labels"""
+    if sec.shape[0] == 1:
+        return np.zeros(np.asarray(doy).shape[0], dtype=np.int64), np.zeros(1, dtype=np.int64)
+    return doy, doys
+
+
+def base_series(base, point, sdims, coords):
+    """``base`` as the GridSeries with a 'doy' dimension that pairs with the series like th / se; a result that stands
+    for a base (MonthlyMeanDataset) says so with as_series()"""
+    if hasattr(base, "as_series"):
+        base = base.as_series()
+    elif _is_xarray(base):
+        base = GridSeries(base.values, base.dims, _from_xarray(base)[0])
+    elif not isinstance(base, GridSeries):
+        a = np.asarray(base, dtype=np.float64)
+        nd = 0 if point else len(sdims)
+        if a.ndim not in (nd, nd + 1):
+            raise XmhwException(f"base should be a {tuple(sdims)} array or a ('doy',) + {tuple(sdims)} climatology, got "
+                                f"shape {a.shape}")
+        dims = tuple(sdims) if a.ndim == nd else ("doy",) + tuple(sdims)
+        c = {d: coords[d] for d in sdims if d in coords}
+        if "doy" in dims:
+            c["doy"] = np.arange(1, a.shape[0] + 1)
+        base = GridSeries(a, dims, c)
+    if "doy" not in base.dims:
+        base = GridSeries(np.asarray(base.values, dtype=np.float64)[None], ("doy",) + tuple(base.dims),
+                          dict(base.coords, doy=np.zeros(1, dtype=np.int64)))
+    return base
+
+
+def ocean_mask(field, dims, tdim, point, anynans):
+    """(N,) bool: the ocean cells of a field, computed on the host as _detect() masks them"""
+    from .landmask import keep_mask, stack_cells
+    if point:
+        return np.array([True])
+    values = field.values if hasattr(field, "values") else field
+    return keep_mask(stack_cells(np.asarray(values), dims, tdim)[0], anynans)
+
+
+def zero_base(ocean, point, sdims, sshape, coords):
+    """A base of zero that pairs with the ocean cells of a field as a climatology does: one row, NaN on land."""
+    values = 0.0 if point else np.where(ocean, 0.0, np.nan).reshape(sshape)
+    return base_series(values, point, sdims, coords)
+
+
+def same_axis(ta, tb):
+    ta, tb = np.asarray(ta), np.asarray(tb)
+    if ta.shape != tb.shape:
+        return False
+    try:
+        return bool(np.array_equal(ta, tb))
+    except (TypeError, ValueError):
+        return False
+
+
+def check_same_frame(who, first, second, layout, time, other_layout, other_time):
+    """A second input (named ``second``) has to be on the grid and the time axis of the first: the layouts are (point,
+    sdims, sshape)."""
+    (point, sdims, sshape), (opoint, osdims, osshape) = layout, other_layout
+    T, To = np.asarray(time).shape[0], np.asarray(other_time).shape[0]
+    if bool(opoint) != bool(point):
+        raise XmhwException(f"{who} cannot pair a single-point series with a grid")
+    if not point and (tuple(osdims) != tuple(sdims) or tuple(osshape) != tuple(sshape)):
+        raise XmhwException(f"{first} and {second} are not on the same grid: {tuple(sdims)} {tuple(sshape)} and "
+                            f"{tuple(osdims)} {tuple(osshape)}")
+    if To != T:
+        raise XmhwException(f"{first} and {second} have {T} and {To} time steps")
+    if not same_axis(time, other_time):
+        raise XmhwException(f"{first} and {second} do not have the same time axis")
+
+
+def check_steps(T, who):
+    """the entries that pack a time step into 17 bits refuse a longer series"""
+    if T >= MAX_STEPS:
+        raise XmhwException(f"{who} handles fewer than 2**17 time steps, got {T}")
+
+
+def check_view(view, cells, T, what):
+    """What the rasteriser relies on, for the cells it will read: positions inside the table, 0 <= start <= end < T
+    (compact_view() gives the first two) and the rows of a cell in time order."""
+    cells = np.ascontiguousarray(cells, dtype=np.int64)
+    if cells.ndim != 1 or (cells.size and (cells.min() < 0 or cells.max() >= view["C"])):
+        raise XmhwException(f"{what}: cell positions outside the table")
+    start, end, offsets = view["start"], view["end"], view["offsets"]
+    if view["n"]:
+        if int(end.max()) >= T:
+            raise XmhwException(f"{what}: index_end outside the time axis")
+        later = np.diff(start.astype(np.int64)) < 0
+        if later.any():
+            first = np.zeros(view["n"], dtype=bool)              # rows that open a cell: no order across cells
+            first[offsets[:-1][offsets[:-1] < view["n"]]] = True
+            if (later & ~first[1:]).any():
+                raise XmhwException(f"{what}: the rows of a cell are not in time order")
+    return cells
 
 
 class CellFrame:

@@ -36,13 +36,12 @@ device slab by slab, as coverage_grid()).
 """
 import numpy as np
 
-from ._lib import hip
 from .detect import EventDataset
 from .device import DeviceScope, as_xmhw_errors
 from .exception import XmhwException
 from .gridweights import quantise_weights, resolve_weights, weights_label
 from .objects import ObjectDataset
-from .series_stage import grid_layout, run, walk_cells, walk_grid
+from .series_stage import Accumulators, grid_layout, run, run_cells, run_grid
 from .track_common import ChainDataset, Selection
 from .tracks import TrackDataset
 
@@ -66,30 +65,30 @@ def selection_rows(mhw, obj, tr):
     return Selection.of_tracks(mhw, obj, tr, "mhw_track_intensity")
 
 
-class _Accumulators:
-    """One call's arguments and its device accumulators: initialised by begin(); they persist across the slabs and are
-    read back once."""
+class _Accumulators(Accumulators):
+    """One call's arguments and its device accumulators, one entry per day of every selected object (L in all): they are
+    not sliced by column, every slab adds to them whole.  Two counters, out-of-range voxels and voxels outside their
+    object's days, come back in the stage dict: the public function words their refusals."""
 
     def __init__(self, rows, wi, coldSpells):
-        self.h, self.rows, self.wi, self.neg = hip(), rows, wi, int(bool(coldSpells))
+        super().__init__()
+        self.rows, self.wi, self.neg = rows, wi, int(bool(coldSpells))
         self.L, self.m = rows.L, rows.m
-        self._scope = DeviceScope()
 
     def begin(self, T=None, C=None):
         """C: the cells of a dense series, which the table and the weights have to match"""
         rows, s = self.rows, self._scope
         if C is not None and (rows.row_offsets.shape != (C + 1,) or np.shape(self.wi) != (C,)):
             raise XmhwException("the table does not have one block of rows per ocean cell of temp: mhw does not belong to temp")
-        L = max(self.L, 1)
-        self.n_valid, self.wsum, self.isum, self.imax = s.alloc(4 * L), s.alloc(8 * L), s.alloc(8 * L), s.alloc(8 * L)
-        self.cat, self.count = s.alloc(4 * 4 * L), s.alloc(16)
+        L = self.L
+        self.make(None, {"n_valid": ((L,), np.int32), "wsum_i": ((L,), np.int64), "isum_q": ((L,), np.int64),
+                         "intensity_max": ((L,), np.float64), "cat_cells": ((4, L), np.int32)}, counters=2)
         self.time_start, self.offsets = s.upload(rows.time_start), s.upload(rows.offsets)
         with as_xmhw_errors(also="Unsupported", hint="select fewer objects with ids= in mhw_tracks()"):
             self.h.track_intensity_init(self.L, *self._out())
 
     def _out(self):
-        return (self.n_valid.ptr, self.wsum.ptr, self.isum.ptr, self.imax.ptr, self.cat.ptr, max(self.L, 1),
-                self.count.ptr, self.count.ptr + 8)
+        return (*self.ptrs(), max(self.L, 1), self.count.ptr, self.count.ptr + 8)
 
     def add_slab(self, slab):
         """One slab (series_stage.Slab), the compact cells k0..k0 + n - 1: upload its rows, queue the pass"""
@@ -108,32 +107,23 @@ class _Accumulators:
                                                   self.m, self.L, *self._out())
             self.h.stream_sync(0)                       # the slab's rows are freed on the way out
 
-    def result(self):
-        h, L = self.h, self.L
+    def finish(self):
         with as_xmhw_errors(also="Unsupported"):
-            h.track_intensity_finish(L, self.imax.ptr)
-        h.stream_sync(0)
-        count = self.count.to_array((2,), np.int64)
-        return dict(n_valid=self.n_valid.to_array((L,), np.int32), wsum_i=self.wsum.to_array((L,), np.int64),
-                    isum_q=self.isum.to_array((L,), np.int64), intensity_max=self.imax.to_array((L,), np.float64),
-                    cat_cells=self.cat.to_array((4, max(L, 1)), np.int32)[:, :L].copy(), n_range=int(count[0]),
-                    n_bad=int(count[1]))
+            self.h.track_intensity_finish(self.L, *self.ptrs(0, ("intensity_max",)))
 
-    def free(self):
-        self._scope.free()
+    def result(self):
+        """(the stage dict: STAGE_FIELDS and the counters n_range and n_bad, no range to report)"""
+        arrays, _ = super().result()
+        n_range, n_bad = self.counts()
+        return dict(zip(STAGE_FIELDS, arrays), n_range=n_range, n_bad=n_bad), {}
 
 
 def track_intensity_cells(ts, seas, thresh, doy, doys, rows, wi, coldSpells=False, max_batch_bytes=64 << 30, pad=None):
     """The device stage for a dense (T, C) host series (arguments as coverage.coverage_cells): ``rows`` the selection_rows()
     of the selection, ``wi`` (C,) int64 weights.  Returns a dict of STAGE_FIELDS plus the counters n_range and n_bad.  Cells go
     through the device in batches below max_batch_bytes; the sums are integers, so the batch size does not change a bit."""
-    acc = _Accumulators(rows, wi, coldSpells)
-    try:
-        walk_cells(ts, seas, thresh, doy, doys, lambda T, isz, D: T * isz + 2 * D * 8 + 64, max_batch_bytes, pad, acc.add_slab,
-                   acc.begin)
-        return acc.result()
-    finally:
-        acc.free()
+    return run_cells(_Accumulators(rows, wi, coldSpells), ts, seas, thresh, doy, doys, lambda T, isz, D: T * isz + 2 * D * 8 + 64,
+                     max_batch_bytes, pad)
 
 
 def track_intensity_grid(stacked, anynans, seas, thresh, doy, doys, rows, wi, keep_want, coldSpells=False,
@@ -149,14 +139,8 @@ def track_intensity_grid(stacked, anynans, seas, thresh, doy, doys, rows, wi, ke
         if not np.array_equal(keep, keep_want[lo:hi]):
             raise XmhwException("the land mask of temp differs from mhw.keep: mhw does not belong to temp")
 
-    acc = _Accumulators(rows, wi, coldSpells)
-    try:
-        acc.begin()
-        keep = walk_grid(stacked, anynans, seas, thresh, doy, doys, lambda T, D: 6 * D * 8 + 64, max_batch_bytes,
-                         clim_stacked, pad, acc.add_slab, check_keep=check_keep)
-        return acc.result(), keep
-    finally:
-        acc.free()
+    return run_grid(_Accumulators(rows, wi, coldSpells), stacked, anynans, seas, thresh, doy, doys, lambda T, D: 6 * D * 8 + 64,
+                    max_batch_bytes, clim_stacked, pad, begin_with=(), check_keep=check_keep)
 
 
 class TrackIntensityDataset(ChainDataset):

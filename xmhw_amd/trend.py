@@ -104,6 +104,18 @@ def _t_sf(t, dof):
     return 0.5 * _betainc(0.5 * dof, 0.5, dof / (dof + t2))
 
 
+def _t_two_sided(t, dof):
+    """the two-sided p-value of one t statistic: NaN without degrees of freedom or for a NaN, 0 for an infinite t"""
+    if not (dof > 0.0) or t != t:
+        return math.nan
+    return 0.0 if math.isinf(t) else min(1.0, 2.0 * _t_sf(abs(t), dof))
+
+
+def p_two_sided(t, dof):
+    """_t_two_sided() over arrays that broadcast: float64"""
+    return np.frompyfunc(_t_two_sided, 2, 1)(t, dof).astype(np.float64)
+
+
 def student_t_isf(q, dof):
     """t with P(T > t) = q for Student's t with ``dof`` degrees of freedom, 0 < q < 0.5: Newton's iteration
     on the survival function kept inside a bracket, until the step is below one part in 1e15."""
