@@ -1322,6 +1322,83 @@ int xmhw_lag_corr_accumulate_f64(const double *x_dev, int64_t ldx, const double 
                                  int64_t *sy_dev, int64_t *sxx_dev, int64_t *syy_dev, int64_t *sxy_dev, int64_t ldo,
                                  int64_t *n_range_dev, void *stream);
 
+/* ---- anomaly_distribution(): per-cell histograms, quantiles and moments of the anomaly ---- *
+ * What the distribution of the anomaly of a cell looks like, per class of time steps: skewness and kurtosis (why heatwaves
+ * and cold spells of one cell are not mirror images: Sura & Sardeshmukh 2008; the check on every Gaussian p-value),
+ * quantile maps that are not the day-of-year threshold, exceedance probabilities at levels of the user's choosing.  The
+ * first stage whose accumulator's address is the sample: a per-lane histogram in LDS, and sums 128 bits wide.
+ *
+ * ts_dev[T][ld] is a series of float32 / float64; base_dev[Dr][ldb] is float64 with row_of_t_host[T] in [0, Dr): Dr = 1 is a
+ * constant per cell, read once.  shift in [0, XMHW_DISTRIBUTION_MAX_SHIFT]; class_of_t_host[T]: one int32 label per step in
+ * [-1, K), K <= XMHW_DISTRIBUTION_MAX_CLASSES, -1 counts nowhere (the step is not read); T < 2^17, C < 2^31.
+ *   d(t) = (float64(ts[t][c]) - base[row_of_t[t]][c]) * 2^-shift                        (the scaling is exact)
+ *   NaN is no sample; |d| >= 2^XMHW_DISTRIBUTION_RANGE_BITS (infinities included) is left out and counted in *n_range_dev;
+ *   otherwise the step is VALID and q = int64(rint(d * 2^XMHW_DISTRIBUTION_BITS)), |q| <= 2^23.
+ * The bins are lo_q (|lo_q| <= 2^23), width_q >= 1 and B in [1, XMHW_DISTRIBUTION_MAX_BINS]: the bin of q is
+ * b = floor((q - lo_q) / width_q), exactly; b < 0 counts in the UNDER row (row 0), b >= B in the OVER row (row B + 1),
+ * anything else in row 1 + b.  For every class k and cell c, over the valid steps of class k, exact integers:
+ *   hist[k][0 .. B + 1][c]  int32   the counts per row
+ *   n   [k][c]              int32   the valid steps (the sum of the rows)
+ *   s1, s2 [k][c]           int64   the sums of q and q^2 (fewer than 2^17 steps of at most 2^46)
+ *   s3, s4 [k][0 .. 1][c]           the sums of q^3 and q^4 as 128-bit two's-complement integers: [k][0] the low words
+ *                                   (to be read as uint64), [k][1] the high words (int64)
+ *   kmax, kmin [k][c]       uint64  the order-preserving keys of the largest d and of the largest -d (0: none); after
+ *                                   xmhw_distribution_finish float64: the largest and the smallest d, NaN for none
+ * All outputs have the cells as their fastest axis with leading dimension ldo >= C; columns past C are never touched, and
+ * a slab addresses its columns by pointer offset.  Everything is an integer sum, an integer maximum or a function of
+ * those: the result does not depend on the time blocks, the slabs, the launch geometry or the schedule.
+ *
+ *  1. xmhw_distribution_init zeroes columns 0..C-1 of the ten accumulators and the counter.
+ *  2. xmhw_distribution_accumulate_* handles one slab of C cells and ADDS into the accumulators: two calls on disjoint
+ *     column ranges equal one.  Lane = cell, workgroup = 256 cells x a block of steps; the histogram of a lane is a column
+ *     of 16-bit halves in LDS (32 / 64 / 128 KB for B <= 64 / 128 / 256), flushed by integer atomics when the class changes,
+ *     at the end of the block and after 65,535 steps of a run (csrc/kernels_distribution.hip, csrc/hist_bin.h,
+ *     csrc/wide_sum.h).
+ *  3. xmhw_distribution_finish, once per column after the last slab, works from the device-resident histogram: the keys
+ *     become float64, and for P <= XMHW_DISTRIBUTION_MAX_QUANTILES probabilities p_q_host[j] = rint(p * 2^32) in
+ *     [0, 2^32], with the rank r = max(1, ceil(p_q * n / 2^32)) in 64-bit integers,
+ *       qbin  [k][j][c] int32: the bin that holds the r-th smallest valid sample; -1 = UNDER, B = OVER, INT32_MIN: n == 0
+ *       qbelow[k][j][c] int32: the valid samples in rows strictly below that row (0 for n == 0)
+ *       qcount[k][j][c] int32: the valid samples in that row (0 for n == 0): what a quantile inside the bin needs
+ *     and for L <= XMHW_DISTRIBUTION_MAX_LEVELS edges edge_host[l] in [0, B]
+ *       n_at_least[k][l][c] int32: the valid samples with b >= edge[l] (edge 0: everything but UNDER; edge B: OVER).
+ * All three are asynchronous on `stream`.  Refusals, in this order and before the first HIP call: K < 1 or
+ * K > XMHW_DISTRIBUTION_MAX_CLASSES, B < 1 or B > XMHW_DISTRIBUTION_MAX_BINS, T of 2^17 and more, C of 2^31 and more, then
+ * (accumulate) width_q < 1, lo_q outside [-2^23, 2^23], a shift outside [0, XMHW_DISTRIBUTION_MAX_SHIFT], (finish) P or L
+ * outside their range: XMHW_ERR_UNSUPPORTED.  A bad T, C, Dr or leading dimension, a NULL host table, a label outside
+ * [-1, K), a row outside [0, Dr), a p_q above 2^32, an edge outside [0, B]: XMHW_ERR_INVALID.  Then nothing is launched for
+ * C == 0 (or T == 0); then a NULL device buffer is XMHW_ERR_INVALID (qbin, qbelow and qcount may be NULL for P == 0, n_at_least for
+ * L == 0).
+ * xmhw_set_distribution_block (process-wide; tests and measurements): the steps a workgroup takes per block, 0 = automatic,
+ * a negative value is XMHW_ERR_INVALID.  Same results for every value.                                               */
+#define XMHW_DISTRIBUTION_MAX_BINS       256
+#define XMHW_DISTRIBUTION_MAX_CLASSES    64
+#define XMHW_DISTRIBUTION_MAX_QUANTILES  16
+#define XMHW_DISTRIBUTION_MAX_LEVELS     8
+#define XMHW_DISTRIBUTION_MAX_STEPS      (1 << 17)   /* T below it */
+#define XMHW_DISTRIBUTION_BITS           16
+#define XMHW_DISTRIBUTION_RANGE_BITS     7
+#define XMHW_DISTRIBUTION_MAX_SHIFT      24
+int xmhw_set_distribution_block(int32_t steps);       /* tests and measurements; 0 = automatic */
+int xmhw_distribution_init(int32_t K, int32_t B, int64_t C, int32_t *hist_dev, int32_t *n_dev, int64_t *s1_dev, int64_t *s2_dev,
+                           int64_t *s3_dev, int64_t *s4_dev, uint64_t *kmin_dev, uint64_t *kmax_dev, int64_t ldo,
+                           int64_t *n_range_dev, void *stream);
+int xmhw_distribution_accumulate_f32(const float *ts_dev, int64_t T, int64_t C, int64_t ld, const double *base_dev, int64_t ldb,
+                                     int64_t Dr, const int32_t *row_of_t_host, int32_t shift, const int32_t *class_of_t_host,
+                                     int32_t K, int64_t lo_q, int32_t width_q, int32_t B, int32_t *hist_dev, int32_t *n_dev,
+                                     int64_t *s1_dev, int64_t *s2_dev, int64_t *s3_dev, int64_t *s4_dev, uint64_t *kmin_dev,
+                                     uint64_t *kmax_dev, int64_t ldo, int64_t *n_range_dev, void *stream);
+int xmhw_distribution_accumulate_f64(const double *ts_dev, int64_t T, int64_t C, int64_t ld, const double *base_dev,
+                                     int64_t ldb, int64_t Dr, const int32_t *row_of_t_host, int32_t shift,
+                                     const int32_t *class_of_t_host, int32_t K, int64_t lo_q, int32_t width_q, int32_t B,
+                                     int32_t *hist_dev, int32_t *n_dev, int64_t *s1_dev, int64_t *s2_dev, int64_t *s3_dev,
+                                     int64_t *s4_dev, uint64_t *kmin_dev, uint64_t *kmax_dev, int64_t ldo,
+                                     int64_t *n_range_dev, void *stream);
+int xmhw_distribution_finish(int32_t K, int32_t B, int64_t C, const int32_t *hist_dev, const int32_t *n_dev, double *kmin_dev,
+                             double *kmax_dev, const uint64_t *p_q_host, int32_t P, const int32_t *edge_host, int32_t L,
+                             int32_t *qbin_dev, int32_t *qbelow_dev, int32_t *qcount_dev, int32_t *n_at_least_dev, int64_t ldo,
+                             void *stream);
+
 /* ---- the sharded path: cells split across the GPUs of a node, ONE gather at the end ------- *
  * Replaces the reference's collect, dask.compute(climls) + xr.concat(dim='cell')
  * (xmhw/xmhw.py:197, :210-211).  Cells are independent (xmhw/xmhw.py:184-196), so rank r runs the

@@ -30,6 +30,7 @@ from .heat_stress import heat_stress, maximum_monthly_mean, degree_heating_weeks
 from .index_regression import index_regression, IndexRegressionDataset
 from .composite import mhw_composite, CompositeDataset
 from .lag_correlation import lag_correlation, LagCorrelationDataset
+from .distribution import anomaly_distribution, DistributionDataset
 from .ingest import open_series, threshold_file
 from .detrend import detrend, DetrendSpec, FitDataset
 
@@ -42,6 +43,7 @@ __all__ = ["threshold", "threshold_array", "GridSeries", "ClimDataset", "XmhwExc
            "classes_from_events", "mhw_cooccurrence", "CooccurrenceDataset", "mhw_displacement", "displacement_offsets",
            "DisplacementDataset", "DisplacementTable", "heat_stress", "maximum_monthly_mean", "degree_heating_weeks",
            "HeatStressDataset", "MonthlyMeanDataset", "index_regression", "IndexRegressionDataset", "mhw_composite",
-           "CompositeDataset", "lag_correlation", "LagCorrelationDataset", "open_series",
+           "CompositeDataset", "lag_correlation", "LagCorrelationDataset", "anomaly_distribution",
+           "DistributionDataset", "open_series",
            "threshold_file", "detrend", "DetrendSpec", "FitDataset"]
 __version__ = "0.1.0"

@@ -53,6 +53,11 @@ def hip_lagcorr():
     return _extension("_xmhw_hip_lagcorr")
 
 
+def hip_distribution():
+    """the bindings of anomaly_distribution()"""
+    return _extension("_xmhw_hip_distribution")
+
+
 class _RetryOnNoMem:
     """The pybind11 module with one behaviour added: a call that runs out of device memory
     (XMHW_ERR_NOMEM -> MemoryError) is repeated once after the cached large device buffers of

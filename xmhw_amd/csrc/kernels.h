@@ -385,7 +385,8 @@ hipError_t launch_track_intensity_accumulate(const T* ts, int64_t Tn, int64_t n,
 hipError_t launch_track_intensity_finish(int64_t L, double* intensity_max, hipStream_t stream);
 
 // The frame of a class reduction: the kernels below that reduce over TIME and keep the cell (class_days_accumulate,
-// class_sums_accumulate, heat_stress_accumulate, index_regress_accumulate, lag_corr_accumulate, composite_accumulate -- which keeps no addends
+// class_sums_accumulate, heat_stress_accumulate, index_regress_accumulate, lag_corr_accumulate, distribution_accumulate,
+// composite_accumulate -- which keeps no addends
 // and adds every (anchor, offset) pair directly; displacement_accumulate with a grid point and
 // cooccur_accumulate with 64-step words in the place of the cell and the step).  Lane = cell, consecutive lanes on consecutive cells; a workgroup
 // is 256 cells x a block of steps (stage_blocks.h has the block lengths); class_of_t[t] and row_of_t[t] are uniform over
@@ -569,6 +570,38 @@ hipError_t launch_lag_corr_accumulate(const T* x, int64_t ldx, const T* y, int64
                                       const int32_t* row_of_t, int32_t shift_x, int32_t shift_y, const int32_t* class_of_t,
                                       int32_t K, int32_t L, int64_t block_steps, int32_t* n, int64_t* sx, int64_t* sy,
                                       int64_t* sxx, int64_t* syy, int64_t* sxy, int64_t ldo, int64_t* n_range,
+                                      hipStream_t stream);
+
+// anomaly_distribution() (kernels_distribution.hip, hist_bin.h, wide_sum.h): per cell and class of the step, over the steps
+// whose anomaly d = (sample - base[row_of_t[t]][c]) * 2^-shift is valid, with q = rint(d * 2^kDistributionBits): the counts
+// hist[k][0 .. B + 1][c] of the rows of the bins (lo_q, width_q, B) -- row 0 UNDER, row B + 1 OVER --, n[k][c], s1 and s2
+// [k][c] the sums of q and q^2, s3 and s4 [k][0..1][c] the sums of q^3 and q^4 as 128-bit integers (low words, high words),
+// all ADDED, and kmax, kmin [k][c] RAISED to the key of the largest d and of the largest -d; the definition is in
+// include/xmhw_amd.h, "anomaly_distribution()".  *n_range counts the steps of a class whose d is not NaN and out of range.
+// launch_distribution_finish turns the keys into float64 (kmin: the smallest d; NaN for none) and writes, from the
+// histogram, qbin, qbelow and qcount [k][P][c] of the ranks of p_q[P] and n_at_least[k][L][c] of the edges edge[L].  row_of_t and
+// class_of_t are DEVICE arrays, p_q and edge HOST arrays here.  block_steps: the steps a workgroup takes per block,
+// 0 = automatic; same results for every value.
+constexpr int kDistributionMaxBins = 256;            // two 16-bit counters to a dword: 128 KB of LDS per workgroup
+constexpr int kDistributionMaxClasses = 64;
+constexpr int kDistributionMaxQuantiles = 16;
+constexpr int kDistributionMaxLevels = 8;
+constexpr int kDistributionMaxSteps = 1 << 17;       // T below it, as kLagCorrMaxSteps: 2^17 * 2^46 = 2^63
+constexpr int kDistributionBits = 16;
+constexpr int kDistributionRangeBits = 7;
+constexpr int kDistributionMaxShift = 24;
+hipError_t launch_distribution_init(int32_t K, int32_t B, int64_t C, int32_t* hist, int32_t* n, int64_t* s1, int64_t* s2,
+                                    int64_t* s3, int64_t* s4, uint64_t* kmin, uint64_t* kmax, int64_t ldo, int64_t* n_range,
+                                    hipStream_t stream);
+template <typename T>
+hipError_t launch_distribution_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* base, int64_t ldb,
+                                          int64_t Dr, const int32_t* row_of_t, int32_t shift, const int32_t* class_of_t,
+                                          int32_t K, int64_t lo_q, int32_t width_q, int32_t B, int64_t block_steps,
+                                          int32_t* hist, int32_t* n, int64_t* s1, int64_t* s2, int64_t* s3, int64_t* s4,
+                                          uint64_t* kmin, uint64_t* kmax, int64_t ldo, int64_t* n_range, hipStream_t stream);
+hipError_t launch_distribution_finish(int32_t K, int32_t B, int64_t C, const int32_t* hist, const int32_t* n, double* kmin,
+                                      double* kmax, const uint64_t* p_q, int32_t P, const int32_t* edge, int32_t L,
+                                      int32_t* qbin, int32_t* qbelow, int32_t* qcount, int32_t* n_at_least, int64_t ldo,
                                       hipStream_t stream);
 
 // file bytes -> samples (kernels_ingest.hip): raw_type = item size of the stored type (2 int16, 4 float32,

@@ -88,6 +88,18 @@ static inline int64_t lag_corr_auto_block(int64_t Tn, int64_t C, int64_t L) {
     return stage_auto_block(Tn, ceil_div(C, kStageThreads) * lag_corr_groups(L), Tn / least, least > 4096 ? least : 4096, 1);
 }
 
+// anomaly_distribution().  A block pays the clearing of nothing (a flush leaves the LDS column empty) and one flush at its
+// end, whose scan covers the dwords the block touched: the rule of class_days_auto_block -- a slab too small to fill the
+// chip with one block per 256 cells splits the time axis until about 2048 workgroups exist, in blocks of 256 steps at
+// least -- with about 4,096 steps as the most a block takes, as in heat_stress() and lag_correlation(): with 128 KB of LDS
+// a CU holds one workgroup at a time, and several blocks per 256 cells let the workgroups finish evenly.  Measured on a
+// grid that fills the chip by its cells alone (profiles/r31_distribution_bench.json, one class): forced blocks of 256 /
+// 512 / 4,096 steps and one block over 14,610 steps take 73.5 / 71.6 / 70.4 / 72.5 ms at 128 bins and 139.5 / 134.9 /
+// 131.9 / 132.8 ms at 256 -- long blocks win by 3 to 6 %, and 4,096 is not slower than one block.
+static inline int64_t distribution_auto_block(int64_t Tn, int64_t C) {
+    return stage_auto_block(Tn, ceil_div(C, kStageThreads), ceil_div(Tn, 256), 4096, 1);
+}
+
 // mhw_displacement(): a workgroup is four waves of 64 longitudes of one grid row.  One block over the steps keeps the
 // flushes rare; a grid whose waves do not fill the chip splits the steps until about 2048 workgroups exist.
 static inline int64_t displacement_auto_block(int64_t nt, int64_t ny, int64_t nx) {
