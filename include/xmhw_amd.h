@@ -1399,6 +1399,74 @@ int xmhw_distribution_finish(int32_t K, int32_t B, int64_t C, const int32_t *his
                              int32_t *qbin_dev, int32_t *qbelow_dev, int32_t *qcount_dev, int32_t *n_at_least_dev, int64_t ldo,
                              void *stream);
 
+/* ---- spatial_correlation(): per-cell correlation with grid neighbours ---- *
+ * The spatial correlation function of the anomaly and its decorrelation length: how large heatwaves are, the spatial
+ * counterpart of the e-folding time, and the input to every field-significance statement (the effective number of
+ * independent cells of a map).  The first stage whose per-sample work is a product with the samples of OTHER grid points at
+ * the same step: a stencil over a tile with a halo in LDS.
+ *
+ * ts_dev[nt][ld] is a block of steps t0 .. t0 + nt - 1 of the UNCOMPACTED series on the ny x nx grid, float32 or float64,
+ * ld >= ny * nx, land NaN; point p = j * nx + i, longitude the fast axis.  base_dev[Dr][ldb] is float64 on the same grid
+ * (ldb >= ny * nx) with row_of_t_host[T] in [0, Dr): Dr = 1 is a constant per point, read once.  shift in
+ * [0, XMHW_SPATIAL_CORR_MAX_SHIFT]; class_of_t_host[T]: one int32 label per step in [-1, K), K <=
+ * XMHW_SPATIAL_CORR_MAX_CLASSES; periodic != 0: longitude wraps; T < 2^17; ny, nx <= XMHW_SPATIAL_CORR_MAX_AXIS.
+ * offsets_host[D][2] holds D offsets (dj, di) as int32 pairs, 1 <= D <= XMHW_SPATIAL_CORR_MAX_OFFSETS, |dj|, |di| <=
+ * XMHW_SPATIAL_CORR_REACH; duplicates and (0, 0) are allowed; with periodic, an offset with |di| >= nx is XMHW_ERR_INVALID.
+ *   a(t, p) = (float64(ts[t][p]) - base[row_of_t[t]][p]) * 2^-shift                     (the scaling is exact)
+ *   a sample is VALID iff a is not NaN and |a| < 2^XMHW_SPATIAL_CORR_RANGE_BITS; q = int64(rint(a * 2^XMHW_SPATIAL_CORR_BITS)).
+ * For every grid point p = (j, i), every step t of the block with k = class_of_t[t] >= 0 and every offset e = (dj, di),
+ * the partner is p' = (j + dj, i + di), i + di taken mod nx when periodic.  The pair is valid iff p' lies in the grid and
+ * a(t, p) and a(t, p') are both valid; for a valid pair, into the outputs [K][D][ldo], ldo >= ny * nx:
+ *   n  [k][e][p] += 1 (int32)        sx [k][e][p] += q(p)           sy [k][e][p] += q(p')
+ *   sxx[k][e][p] += q(p)^2           syy[k][e][p] += q(p')^2        sxy[k][e][p] += q(p) q(p')           (all int64)
+ * All six sums run over the valid pairs alone (pairwise deletion, as in lag_correlation()).  Land points keep n = 0;
+ * columns past ny * nx are never touched; steps of class -1 are not read.  *n_range_dev (int64) counts the (t, p) of class
+ * >= 0 whose a is not NaN and out of range: each once, by its own point, whatever the blocks, tiles and halos; such a
+ * sample is no partner either.  |q| <= 2^23, products <= 2^46, fewer than 2^17 pairs per entry: everything stays inside 64
+ * bits.  Everything is an integer sum: the result is exact and does not depend on the time blocks, the tile geometry, the
+ * offset grouping or the schedule.
+ *
+ *  1. xmhw_spatial_corr_init zeroes columns 0 .. ny * nx - 1 of the accumulators and the counter.
+ *  2. xmhw_spatial_corr_accumulate_* ADDS the block: consecutive blocks follow each other on one stream without a
+ *     read-back.  A workgroup owns a tile of 8 grid rows x 64 longitudes, walks a block of steps and takes a group of 8 or
+ *     16 offsets; per step it converts the tile and the halo the group's offsets reach once into LDS, and every lane reads
+ *     one dword per offset (csrc/kernels_spatialcorr.hip, csrc/halo_tile.h).
+ * Both are asynchronous on `stream`.  Refusals, in this order and before the first HIP call: K < 1 or
+ * K > XMHW_SPATIAL_CORR_MAX_CLASSES, D < 1 or D > XMHW_SPATIAL_CORR_MAX_OFFSETS, a shift outside
+ * [0, XMHW_SPATIAL_CORR_MAX_SHIFT], T of 2^17 and more, a grid axis above XMHW_SPATIAL_CORR_MAX_AXIS, an offset (of a table
+ * that is not NULL) beyond XMHW_SPATIAL_CORR_REACH: XMHW_ERR_UNSUPPORTED.  A negative ny or nx, a bad T, t0 or nt (0 <= t0,
+ * 0 <= nt <= T - t0), a bad leading dimension or Dr, a NULL host table (offsets always; the labels and rows for T > 0), an
+ * offset with |di| >= nx on a periodic grid, a label outside [-1, K), a row outside [0, Dr): XMHW_ERR_INVALID.  Then
+ * nothing is launched for nt == 0 or ny * nx == 0; then a NULL device buffer is XMHW_ERR_INVALID.
+ * xmhw_set_spatial_corr_block (process-wide; tests and measurements): the steps a workgroup takes per block, 0 = automatic,
+ * a negative value is XMHW_ERR_INVALID.  xmhw_set_spatial_corr_tile (likewise): the grid rows of a tile, 4 or 8, 0 = the
+ * default (8).  Same results for every value of either.                                                            */
+#define XMHW_SPATIAL_CORR_MAX_OFFSETS 64
+#define XMHW_SPATIAL_CORR_REACH       32
+#define XMHW_SPATIAL_CORR_MAX_CLASSES 64
+#define XMHW_SPATIAL_CORR_MAX_STEPS   131072         /* T below it */
+#define XMHW_SPATIAL_CORR_MAX_AXIS    32767
+#define XMHW_SPATIAL_CORR_BITS        16
+#define XMHW_SPATIAL_CORR_RANGE_BITS  7
+#define XMHW_SPATIAL_CORR_MAX_SHIFT   24
+int xmhw_set_spatial_corr_block(int32_t steps);       /* tests and measurements; 0 = automatic */
+int xmhw_set_spatial_corr_tile(int32_t rows);         /* tests and measurements; 0 = the default */
+int xmhw_spatial_corr_init(int32_t K, int32_t D, int32_t ny, int32_t nx, int32_t *n_dev, int64_t *sx_dev, int64_t *sy_dev,
+                           int64_t *sxx_dev, int64_t *syy_dev, int64_t *sxy_dev, int64_t ldo, int64_t *n_range_dev,
+                           void *stream);
+int xmhw_spatial_corr_accumulate_f32(const float *ts_dev, int64_t ld, int64_t t0, int64_t nt, int64_t T, int32_t ny,
+                                     int32_t nx, int32_t periodic, const double *base_dev, int64_t ldb, int64_t Dr,
+                                     const int32_t *row_of_t_host, int32_t shift, const int32_t *class_of_t_host, int32_t K,
+                                     const int32_t *offsets_host, int32_t D, int32_t *n_dev, int64_t *sx_dev, int64_t *sy_dev,
+                                     int64_t *sxx_dev, int64_t *syy_dev, int64_t *sxy_dev, int64_t ldo, int64_t *n_range_dev,
+                                     void *stream);
+int xmhw_spatial_corr_accumulate_f64(const double *ts_dev, int64_t ld, int64_t t0, int64_t nt, int64_t T, int32_t ny,
+                                     int32_t nx, int32_t periodic, const double *base_dev, int64_t ldb, int64_t Dr,
+                                     const int32_t *row_of_t_host, int32_t shift, const int32_t *class_of_t_host, int32_t K,
+                                     const int32_t *offsets_host, int32_t D, int32_t *n_dev, int64_t *sx_dev, int64_t *sy_dev,
+                                     int64_t *sxx_dev, int64_t *syy_dev, int64_t *sxy_dev, int64_t ldo, int64_t *n_range_dev,
+                                     void *stream);
+
 /* ---- the sharded path: cells split across the GPUs of a node, ONE gather at the end ------- *
  * Replaces the reference's collect, dask.compute(climls) + xr.concat(dim='cell')
  * (xmhw/xmhw.py:197, :210-211).  Cells are independent (xmhw/xmhw.py:184-196), so rank r runs the

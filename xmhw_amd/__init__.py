@@ -31,6 +31,7 @@ from .index_regression import index_regression, IndexRegressionDataset
 from .composite import mhw_composite, CompositeDataset
 from .lag_correlation import lag_correlation, LagCorrelationDataset
 from .distribution import anomaly_distribution, DistributionDataset
+from .spatial_correlation import spatial_correlation, SpatialCorrelationDataset
 from .ingest import open_series, threshold_file
 from .detrend import detrend, DetrendSpec, FitDataset
 
@@ -44,6 +45,6 @@ __all__ = ["threshold", "threshold_array", "GridSeries", "ClimDataset", "XmhwExc
            "DisplacementDataset", "DisplacementTable", "heat_stress", "maximum_monthly_mean", "degree_heating_weeks",
            "HeatStressDataset", "MonthlyMeanDataset", "index_regression", "IndexRegressionDataset", "mhw_composite",
            "CompositeDataset", "lag_correlation", "LagCorrelationDataset", "anomaly_distribution",
-           "DistributionDataset", "open_series",
+           "DistributionDataset", "spatial_correlation", "SpatialCorrelationDataset", "open_series",
            "threshold_file", "detrend", "DetrendSpec", "FitDataset"]
 __version__ = "0.1.0"

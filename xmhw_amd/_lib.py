@@ -58,6 +58,11 @@ def hip_distribution():
     return _extension("_xmhw_hip_distribution")
 
 
+def hip_spatialcorr():
+    """the bindings of spatial_correlation()"""
+    return _extension("_xmhw_hip_spatialcorr")
+
+
 class _RetryOnNoMem:
     """The pybind11 module with one behaviour added: a call that runs out of device memory
     (XMHW_ERR_NOMEM -> MemoryError) is repeated once after the cached large device buffers of

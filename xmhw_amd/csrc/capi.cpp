@@ -22,6 +22,7 @@
 #include "kernels.h"
 #include "plan.h"
 #include "route.h"
+#include "stage_blocks.h"
 
 namespace {
 
@@ -1074,6 +1075,77 @@ int lag_corr_accumulate(const T* x, int64_t ldx, const T* y, int64_t ldy, int64_
                                                          g_lag_corr_block.load(), n, sx, sy, sxx, syy, sxy, ldo, n_range,
                                                          static_cast<hipStream_t>(stream)),
                      "lag_corr_accumulate launch");
+}
+
+static std::atomic<int> g_spatial_corr_block{0};   // steps a workgroup takes per block, 0 = automatic (xmhw_set_spatial_corr_block)
+static std::atomic<int> g_spatial_corr_tile{0};    // grid rows of a tile, 0 = the default (xmhw_set_spatial_corr_tile)
+
+static_assert(XMHW_SPATIAL_CORR_MAX_OFFSETS == xmhw::kSpatialCorrMaxOffsets && XMHW_SPATIAL_CORR_REACH == xmhw::kSpatialCorrReach &&
+                  XMHW_SPATIAL_CORR_MAX_CLASSES == xmhw::kSpatialCorrMaxClasses &&
+                  XMHW_SPATIAL_CORR_MAX_STEPS == xmhw::kSpatialCorrMaxSteps &&
+                  XMHW_SPATIAL_CORR_MAX_AXIS == xmhw::kSpatialCorrMaxAxis && XMHW_SPATIAL_CORR_BITS == xmhw::kSpatialCorrBits &&
+                  XMHW_SPATIAL_CORR_RANGE_BITS == xmhw::kSpatialCorrRangeBits &&
+                  XMHW_SPATIAL_CORR_MAX_SHIFT == xmhw::kSpatialCorrMaxShift,
+              "the public limits of spatial_correlation() are the kernel's");
+
+static int spatial_corr_check_shape(int32_t K, int32_t D, int32_t shift, int64_t Tn, int32_t ny, int32_t nx) {
+    if (K < 1 || K > xmhw::kSpatialCorrMaxClasses)
+        return fail(XMHW_ERR_UNSUPPORTED,
+                    "spatial_corr: K must be in [1, " + std::to_string(xmhw::kSpatialCorrMaxClasses) + "]");
+    if (D < 1 || D > xmhw::kSpatialCorrMaxOffsets)
+        return fail(XMHW_ERR_UNSUPPORTED,
+                    "spatial_corr: D must be in [1, " + std::to_string(xmhw::kSpatialCorrMaxOffsets) + "]");
+    if (shift < 0 || shift > xmhw::kSpatialCorrMaxShift)
+        return fail(XMHW_ERR_UNSUPPORTED,
+                    "spatial_corr: shift must be in [0, " + std::to_string(xmhw::kSpatialCorrMaxShift) + "]");
+    if (Tn >= xmhw::kSpatialCorrMaxSteps) return fail(XMHW_ERR_UNSUPPORTED, "spatial_corr: 2^17 steps and more");
+    if (ny > xmhw::kSpatialCorrMaxAxis || nx > xmhw::kSpatialCorrMaxAxis)
+        return fail(XMHW_ERR_UNSUPPORTED, "spatial_corr: a grid axis of 2^15 points and more");
+    return XMHW_OK;
+}
+
+template <typename T>
+int spatial_corr_accumulate(const T* ts, int64_t ld, int64_t t0, int64_t nt, int64_t Tn, int32_t ny, int32_t nx,
+                            int32_t periodic, const double* base, int64_t ldb, int64_t Dr, const int32_t* row_of_t,
+                            int32_t shift, const int32_t* class_of_t, int32_t K, const int32_t* offsets, int32_t D, int32_t* n,
+                            int64_t* sx, int64_t* sy, int64_t* sxx, int64_t* syy, int64_t* sxy, int64_t ldo, int64_t* n_range,
+                            void* stream) {
+    if (spatial_corr_check_shape(K, D, shift, Tn, ny, nx) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (offsets)
+        for (int32_t e = 0; e < 2 * D; ++e)
+            if (offsets[e] < -xmhw::kSpatialCorrReach || offsets[e] > xmhw::kSpatialCorrReach)
+                return fail(XMHW_ERR_UNSUPPORTED,
+                            "spatial_corr: offsets reach at most " + std::to_string(xmhw::kSpatialCorrReach) + " points");
+    if (ny < 0 || nx < 0) return fail(XMHW_ERR_INVALID, "bad ny/nx");
+    const int64_t N = static_cast<int64_t>(ny) * nx;
+    if (Tn < 0 || t0 < 0 || nt < 0 || nt > Tn - t0) return fail(XMHW_ERR_INVALID, "bad T/t0/nt");
+    if (ld < N || ldb < N || ldo < N || Dr < 1) return fail(XMHW_ERR_INVALID, "bad ld/ldb/ldo/Dr");
+    if (!offsets || (Tn > 0 && (!class_of_t || !row_of_t))) return fail(XMHW_ERR_INVALID, "NULL host table");
+    if (periodic)
+        for (int32_t e = 0; e < D; ++e)
+            if (nx > 0 && std::abs(offsets[2 * e + 1]) >= nx)
+                return fail(XMHW_ERR_INVALID, "spatial_corr: |di| must be below nx on a periodic grid");
+    if (int rc = check_labels(class_of_t, Tn, -1, K, kClassesOutside)) return rc;
+    if (int rc = check_labels(row_of_t, Tn, 0, Dr, kRowsOutside)) return rc;
+    if (nt == 0 || N == 0) return XMHW_OK;
+    if (!ts || !base || !n || !sx || !sy || !sxx || !syy || !sxy || !n_range) return fail(XMHW_ERR_INVALID, "NULL buffer");
+    RowsRef rows;
+    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
+    RowsRef classes;                                   // the same content-keyed cache: one more int32[T] table
+    if (int rc = upload_table(class_of_t, Tn, "class table upload", &classes)) return rc;
+    // ... and the offsets, padded with (0, 0) to whole groups: int32[groups * G][2]
+    const int64_t padded_n = xmhw::spatial_corr_groups(D) * xmhw::spatial_corr_group(D);
+    std::vector<int32_t> padded(static_cast<size_t>(2 * padded_n), 0);
+    std::copy(offsets, offsets + 2 * D, padded.begin());
+    RowsRef table;
+    if (int rc = upload_table(padded.data(), 2 * padded_n, "offset table upload", &table)) return rc;
+    const int32_t tile = g_spatial_corr_tile.load();
+    return status_of(xmhw::launch_spatial_corr_accumulate<T>(ts, ld, t0, nt, ny, nx, periodic != 0, base, ldb, Dr, rows->d_rows,
+                                                             shift, classes->d_rows, K, table->d_rows, padded.data(), D,
+                                                             tile ? tile : xmhw::kSpatialCorrRows, g_spatial_corr_block.load(),
+                                                             n, sx, sy, sxx, syy, sxy, ldo, n_range,
+                                                             static_cast<hipStream_t>(stream)),
+                     "spatial_corr_accumulate launch");
 }
 
 static std::atomic<int> g_distribution_block{0};    // steps a workgroup takes per block, 0 = automatic (xmhw_set_distribution_block)
@@ -2513,6 +2585,44 @@ int xmhw_lag_corr_accumulate_f64(const double* x, int64_t ldx, const double* y, 
                                  int64_t ldo, int64_t* n_range, void* stream) {
     return lag_corr_accumulate<double>(x, ldx, y, ldy, T, C, base_x, ldbx, base_y, ldby, Dr, row_of_t, shift_x, shift_y,
                                        class_of_t, K, max_lag, n, sx, sy, sxx, syy, sxy, ldo, n_range, stream);
+}
+
+int xmhw_set_spatial_corr_block(int32_t steps) {
+    if (steps < 0) return fail(XMHW_ERR_INVALID, "steps must be >= 0");
+    g_spatial_corr_block = steps;
+    return XMHW_OK;
+}
+int xmhw_set_spatial_corr_tile(int32_t rows) {
+    if (rows != 0 && rows != xmhw::kSpatialCorrRows && rows != xmhw::kSpatialCorrShortRows)
+        return fail(XMHW_ERR_INVALID, "rows must be 0, 4 or 8");
+    g_spatial_corr_tile = rows;
+    return XMHW_OK;
+}
+int xmhw_spatial_corr_init(int32_t K, int32_t D, int32_t ny, int32_t nx, int32_t* n, int64_t* sx, int64_t* sy, int64_t* sxx,
+                           int64_t* syy, int64_t* sxy, int64_t ldo, int64_t* n_range, void* stream) {
+    if (spatial_corr_check_shape(K, D, 0, 1, ny, nx) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (ny < 0 || nx < 0 || ldo < static_cast<int64_t>(ny) * nx) return fail(XMHW_ERR_INVALID, "bad ny/nx/ldo");
+    if (!n_range || (ny > 0 && nx > 0 && (!n || !sx || !sy || !sxx || !syy || !sxy)))
+        return fail(XMHW_ERR_INVALID, "NULL output buffer");
+    return status_of(xmhw::launch_spatial_corr_init(K, D, static_cast<int64_t>(ny) * nx, n, sx, sy, sxx, syy, sxy, ldo, n_range,
+                                                    static_cast<hipStream_t>(stream)),
+                     "spatial_corr_init");
+}
+int xmhw_spatial_corr_accumulate_f32(const float* ts, int64_t ld, int64_t t0, int64_t nt, int64_t T, int32_t ny, int32_t nx,
+                                     int32_t periodic, const double* base, int64_t ldb, int64_t Dr, const int32_t* row_of_t,
+                                     int32_t shift, const int32_t* class_of_t, int32_t K, const int32_t* offsets, int32_t D,
+                                     int32_t* n, int64_t* sx, int64_t* sy, int64_t* sxx, int64_t* syy, int64_t* sxy,
+                                     int64_t ldo, int64_t* n_range, void* stream) {
+    return spatial_corr_accumulate<float>(ts, ld, t0, nt, T, ny, nx, periodic, base, ldb, Dr, row_of_t, shift, class_of_t, K,
+                                          offsets, D, n, sx, sy, sxx, syy, sxy, ldo, n_range, stream);
+}
+int xmhw_spatial_corr_accumulate_f64(const double* ts, int64_t ld, int64_t t0, int64_t nt, int64_t T, int32_t ny, int32_t nx,
+                                     int32_t periodic, const double* base, int64_t ldb, int64_t Dr, const int32_t* row_of_t,
+                                     int32_t shift, const int32_t* class_of_t, int32_t K, const int32_t* offsets, int32_t D,
+                                     int32_t* n, int64_t* sx, int64_t* sy, int64_t* sxx, int64_t* syy, int64_t* sxy,
+                                     int64_t ldo, int64_t* n_range, void* stream) {
+    return spatial_corr_accumulate<double>(ts, ld, t0, nt, T, ny, nx, periodic, base, ldb, Dr, row_of_t, shift, class_of_t, K,
+                                           offsets, D, n, sx, sy, sxx, syy, sxy, ldo, n_range, stream);
 }
 
 int xmhw_set_distribution_block(int32_t steps) {

@@ -387,7 +387,7 @@ hipError_t launch_track_intensity_finish(int64_t L, double* intensity_max, hipSt
 // The frame of a class reduction: the kernels below that reduce over TIME and keep the cell (class_days_accumulate,
 // class_sums_accumulate, heat_stress_accumulate, index_regress_accumulate, lag_corr_accumulate, distribution_accumulate,
 // composite_accumulate -- which keeps no addends
-// and adds every (anchor, offset) pair directly; displacement_accumulate with a grid point and
+// and adds every (anchor, offset) pair directly; displacement_accumulate and spatial_corr_accumulate with a grid point and
 // cooccur_accumulate with 64-step words in the place of the cell and the step).  Lane = cell, consecutive lanes on consecutive cells; a workgroup
 // is 256 cells x a block of steps (stage_blocks.h has the block lengths); class_of_t[t] and row_of_t[t] are uniform over
 // the wave.  A lane keeps the addends of the CURRENT class in registers while the class stays the same and flushes them
@@ -603,6 +603,34 @@ hipError_t launch_distribution_finish(int32_t K, int32_t B, int64_t C, const int
                                       double* kmax, const uint64_t* p_q, int32_t P, const int32_t* edge, int32_t L,
                                       int32_t* qbin, int32_t* qbelow, int32_t* qcount, int32_t* n_at_least, int64_t ldo,
                                       hipStream_t stream);
+
+// spatial_correlation() (kernels_spatialcorr.hip, halo_tile.h): per grid point of the UNCOMPACTED ny x nx grid, class of the
+// step and offset e = (dj, di) of the table djdi[D][2], the sums over the pairs (q(t, p), q(t, p + e)) of one step whose two
+// anomalies are valid -- n int32, sx, sy, sxx, syy, sxy int64, [K][D][ldo], ADDED; the definition is in
+// include/xmhw_amd.h, "spatial_correlation()".  ts is row t0 of the series, the block t0 .. t0 + nt - 1; row_of_t and
+// class_of_t are DEVICE arrays over all T steps here; the offsets come twice, padded with (0, 0) to whole groups
+// (spatial_corr_group): djdi_dev for the kernel, djdi_host for the size of its LDS tile.  *n_range counts the samples of a
+// class >= 0 that are not NaN and out of range, each once.  tile_rows: kSpatialCorrRows or kSpatialCorrShortRows grid rows per
+// workgroup; block_steps: the steps a workgroup takes per block, 0 = automatic; same results for every value of either.
+constexpr int kSpatialCorrMaxOffsets = 64;
+constexpr int kSpatialCorrReach = 32;                // |dj|, |di| at most
+constexpr int kSpatialCorrMaxClasses = 64;
+constexpr int kSpatialCorrMaxSteps = 1 << 17;        // T below it: 2^17 * 2^46 = 2^63
+constexpr int kSpatialCorrMaxAxis = 32767;
+constexpr int kSpatialCorrBits = 16;
+constexpr int kSpatialCorrRangeBits = 7;
+constexpr int kSpatialCorrMaxShift = 24;
+constexpr int kSpatialCorrRows = 8;                  // the tile: 8 rows x 64 longitudes, 512 lanes
+constexpr int kSpatialCorrShortRows = 4;             // ... or 4 x 64, 256 lanes (measurements: the slower of the two)
+hipError_t launch_spatial_corr_init(int32_t K, int32_t D, int64_t N, int32_t* n, int64_t* sx, int64_t* sy, int64_t* sxx,
+                                    int64_t* syy, int64_t* sxy, int64_t ldo, int64_t* n_range, hipStream_t stream);
+template <typename T>
+hipError_t launch_spatial_corr_accumulate(const T* ts, int64_t ld, int64_t t0, int64_t nt, int32_t ny, int32_t nx,
+                                          bool periodic, const double* base, int64_t ldb, int64_t Dr, const int32_t* row_of_t,
+                                          int32_t shift, const int32_t* class_of_t, int32_t K, const int32_t* djdi_dev,
+                                          const int32_t* djdi_host, int32_t D, int32_t tile_rows, int64_t block_steps,
+                                          int32_t* n, int64_t* sx, int64_t* sy, int64_t* sxx, int64_t* syy, int64_t* sxy,
+                                          int64_t ldo, int64_t* n_range, hipStream_t stream);
 
 // file bytes -> samples (kernels_ingest.hip): raw_type = item size of the stored type (2 int16, 4 float32,
 // 8 float64), swap = the file is big-endian, optional scale/offset (CF packing) and fill value -> NaN

@@ -106,6 +106,23 @@ static inline int64_t displacement_auto_block(int64_t nt, int64_t ny, int64_t nx
     return nt > 0 ? stage_auto_block(nt, ceil_div(ny * ceil_div(nx, 64), kStageThreads / 64), nt, 0, 1) : 1;
 }
 
+// spatial_correlation(): a workgroup is a tile of `rows` grid rows x 64 longitudes, times the offset groups (grid.z).  A
+// block pays no warm-up -- the partners of a step are samples of the same step -- and one flush at its end, so the rule
+// is that of displacement_auto_block with the offset groups multiplying the workgroups: one block over the steps keeps
+// the flushes rare; a grid whose tiles x groups do not fill the chip splits the steps until about 2048 workgroups exist.
+// Short blocks measured faster at the default offsets on a grid that fills the chip by its tiles alone
+// (profiles/r32_spatial_corr_bench.json, one class: forced blocks of 256 / 4,096 steps and one block take 242.1 / 238.1 /
+// 260.6 ms at 13 offsets and 1,298 / 1,254 / 1,247 ms at 64; on half the grid 120.8 / 121.1 / 144.3 and 619.1 / 615.3 /
+// 627.6 ms -- with one or two workgroups per CU and two barriers per step the workgroups finish more evenly), so about
+// 256 steps is the most a block takes; 4,096 would do as well or 2 to 3 % better on the full grid.
+constexpr int kSpatialCorrGroup = kLagCorrGroup;     // offsets per workgroup up to 8 offsets, the registers of lag_corr
+constexpr int kSpatialCorrWideGroup = kLagCorrWideGroup;
+static inline int64_t spatial_corr_group(int64_t D) { return D > kSpatialCorrGroup ? kSpatialCorrWideGroup : kSpatialCorrGroup; }
+static inline int64_t spatial_corr_groups(int64_t D) { return D > 0 ? ceil_div(D, spatial_corr_group(D)) : 1; }
+static inline int64_t spatial_corr_auto_block(int64_t nt, int64_t ny, int64_t nx, int64_t rows, int64_t D) {
+    return nt > 0 ? stage_auto_block(nt, ceil_div(ny, rows) * ceil_div(nx, 64) * spatial_corr_groups(D), nt, 256, 1) : 1;
+}
+
 // mhw_cooccurrence(): the axis is the W words of the bitmaps, a workgroup takes one lag group (grid.z).  One block over W
 // keeps the flushes rare and needs no first-word loads; a slab whose workgroups x lag groups do not fill the chip splits
 // the word axis until about 2048 workgroups exist.
