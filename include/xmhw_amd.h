@@ -168,6 +168,13 @@ int xmhw_plan_sorted_info(const xmhw_plan *plan, int64_t C, int32_t *keys_per_li
  * XMHW_ERR_UNSUPPORTED if the kernel is not instantiated for this plan.                                          */
 int xmhw_plan_sorted_table(const xmhw_plan *plan, int32_t pieces, int32_t *nchunks, int32_t *nrows, int32_t *ntp,
                            int32_t *chunks_out, uint32_t *table_out, uint32_t *flags_out);
+/* how many chunks of a float32 launch over C cells the sorted-list kernel settles DIRECTLY instead of walking their
+ * table rows: chunks of one output row whose pool holds at most 12 tracks (Feb 29 of a daily record: the leap years
+ * alone) -- the cell's pool is read once, its 24 largest keys give both order statistics (csrc/kernels_sorted.hip:
+ * direct_row).  Chunks, table rows and results are the same either way; 0 with XMHW_SORTED_ONEROW=0 in the environment
+ * (process-wide, read once).  int16 launches walk every chunk.
+ * XMHW_ERR_UNSUPPORTED if the kernel is not instantiated for this plan.                                          */
+int xmhw_plan_sorted_direct(const xmhw_plan *plan, int64_t C, int32_t *count);
 
 /* debug: ring-kernel pass counters {rows, 32-bit count passes, extractions, cold starts,
  * fast steps, 8-bit probes, code-ring rebuilds} per wave, then count passes summed over CELLS (what

@@ -30,5 +30,8 @@ PY
 # address rebuild of irregular steps has 20 more (a cold block).  ANY other vmcnt wait in the hot blocks (sort, bookkeeping,
 # select) sits out the requests for the next row's samples -- the prefetch is gone and the kernel 12 % slower (round 6: a
 # register shared between a cold path's load and a key made the compiler put one in front of the sort).
-echo "s_waitcnt vmcnt(0) in the row loop at lines: $(grep -n 's_waitcnt vmcnt(0)' /tmp/isa/k20.s | awk -F: '$1 > 440 && $1 < 3300 {printf "%s ", $1}') (expected: two -- the conversion's and the cold address rebuild's)"
+# (the row loop starts ~400 lines behind the first LDS store -- the zeroing of the lists; the direct row of one-row chunks sits in front of that)
+Z=$(grep -n 'ds_write' /tmp/isa/k20.s | head -1 | cut -d: -f1)
+echo "direct row (everything in front of the first LDS store, line $Z): $(head -n $Z /tmp/isa/k20.s | grep -cE '^\s+v_') VALU, $(head -n $Z /tmp/isa/k20.s | grep -cE '^\s+global_load') loads"
+echo "s_waitcnt vmcnt(0) in the row loop at lines: $(grep -n 's_waitcnt vmcnt(0)' /tmp/isa/k20.s | awk -F: -v z=$Z '$1 > z + 400 && $1 < z + 3260 {printf "%s ", $1}') (expected: two -- the conversion's and the cold address rebuild's)"
 grep -A12 "clim_sorted_f32ILi20ELi16ELi14ELb0" /tmp/isa/res.txt | grep -E "VGPRs:|SGPRs:|Occupancy|LDS Size|Scratch" | head -6

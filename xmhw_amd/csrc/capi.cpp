@@ -70,6 +70,7 @@ struct PlanDevice {
     uint32_t* sflags_s = nullptr;
     xmhw::DevSortedChunk* chunks_s = nullptr;
     int32_t nchunks_s = 0;
+    int32_t ndirect_s = 0;                  // how many of them are settled directly (their pooled tracks set)
 };
 
 struct xmhw_plan {
@@ -155,6 +156,16 @@ struct Ready {
     hipEvent_t t0 = nullptr, t1 = nullptr;  // the call's timing events (NULL: not timed)
 };
 
+// XMHW_SORTED_ONEROW=0 (process-wide, read once): no chunk of the sorted-list kernel is settled directly -- every chunk
+// walks its table rows.  Not part of the route: the launches, chunks and tables are the same either way.
+bool sorted_onerow_enabled() {
+    static const bool on = [] {
+        const char* v = std::getenv("XMHW_SORTED_ONEROW");
+        return !(v && v[0] == '0' && v[1] == '\0');
+    }();
+    return on;
+}
+
 // tables and chunks of the sorted-list kernel (under the plan's lock)
 int ensure_sorted(xmhw_plan* p, const xmhw::Launch& l, int64_t pieces) {
     PlanDevice& d = p->dev;
@@ -171,7 +182,15 @@ int ensure_sorted(xmhw_plan* p, const xmhw::Launch& l, int64_t pieces) {
     // with the short chunks (a 40-year daily plan: rows [60, 366), then [0, 59), then the Feb-29 row) instead of a
     // tail of 316-row waves
     std::vector<xmhw::DevSortedChunk> cs(sp.chunks.size());
-    for (size_t i = 0; i < cs.size(); ++i) cs[i] = {sp.chunks[i].warm_start, sp.chunks[i].begin, sp.chunks[i].end, sp.chunks[i].trow0};
+    // (a directly settled chunk -- one output row: the shortest there is -- carries its pooled tracks and sorts last)
+    const bool onerow = sorted_onerow_enabled();
+    d.ndirect_s = 0;
+    for (size_t i = 0; i < cs.size(); ++i) {
+        const uint64_t set = onerow && sp.direct(i, xmhw::sorted_direct_tracks(l.tpl)) ? sp.pooled[i] : 0;
+        d.ndirect_s += set != 0 ? 1 : 0;
+        cs[i] = {sp.chunks[i].warm_start, sp.chunks[i].begin, sp.chunks[i].end, sp.chunks[i].trow0,
+                 static_cast<uint32_t>(set), static_cast<uint32_t>(set >> 32)};
+    }
     std::stable_sort(cs.begin(), cs.end(), [](const xmhw::DevSortedChunk& a, const xmhw::DevSortedChunk& b) {
         return a.end - a.warm_start > b.end - b.warm_start;
     });
@@ -276,7 +295,7 @@ hipError_t launch_one(const xmhw::Plan& h, const xmhw::Launch& l, const PlanDevi
         switch (l.family) {
             case Family::Sorted:
                 return xmhw::launch_sorted_f32(ts, C, ld, h.T, table, rd.sflags_s, rd.chunks_s, rd.nchunks_s, h.w, l.tpl,
-                                               h.ntracks, q, negate, thresh, seas, ldo, st, stats);
+                                               h.ntracks, q, negate, thresh, seas, ldo, st, stats, rd.ndirect_s);
             case Family::Ring1:
                 return xmhw::launch_ring_f32(ts, C, ld, table, h.step_min, rd.chunks, rd.nchunks, h.w, l.tpl, l.lanes, q,
                                              negate, thresh, seas, ldo, st, stats);
@@ -1735,6 +1754,18 @@ int xmhw_plan_sorted_table(const xmhw_plan* plan, int32_t pieces, int32_t* nchun
         }
     if (table_out) std::memcpy(table_out, sp.table.data(), sizeof(uint32_t) * sp.table.size());
     if (flags_out) std::memcpy(flags_out, sp.flags.data(), sizeof(uint32_t) * sp.flags.size());
+    return XMHW_OK;
+}
+
+int xmhw_plan_sorted_direct(const xmhw_plan* plan, int64_t C, int32_t* count) {
+    if (!plan || !count) return fail(XMHW_ERR_INVALID, "NULL argument");
+    if (C < 0) return fail(XMHW_ERR_INVALID, "bad C");
+    const int32_t yps = xmhw::sorted_pick_yps(plan->host.w, plan->host.ntracks);
+    if (yps == 0) return fail(XMHW_ERR_UNSUPPORTED, "the sorted-list kernel is not instantiated for this window / record length");
+    const xmhw::Plan::SortedPlan sp = plan->host.sorted_plan(2 * yps, 24, xmhw::sorted_pieces(plan->host, plan_route(plan, 4), C));
+    int32_t n = 0;
+    for (size_t i = 0; i < sp.chunks.size(); ++i) n += sorted_onerow_enabled() && sp.direct(i, xmhw::sorted_direct_tracks(yps)) ? 1 : 0;
+    *count = n;
     return XMHW_OK;
 }
 

@@ -24,7 +24,9 @@ struct PackedI16 {
     double s = 1.0, o = 0.0;
 };
 // a chunk of the sorted-list kernel: its table / flag rows start at trow0 (row of step warm_start)
-struct DevSortedChunk { int32_t warm_start, begin, end, trow0; };
+// direct_lo / direct_hi: 0, or -- a chunk the kernel settles directly (plan.h: SortedPlan::direct) -- its pooled tracks as
+// a bit set (track k = bit k)
+struct DevSortedChunk { int32_t warm_start, begin, end, trow0; uint32_t direct_lo, direct_hi; };
 
 // generic kernel (any plan): thread per (cell, row)
 template <typename T>
@@ -88,7 +90,8 @@ hipError_t sorted_lds_probe(uint32_t* d_bad, hipStream_t stream);
 hipError_t launch_sorted_f32(const float* ts, int64_t C, int64_t ld, int64_t Tn, const uint32_t* table,
                              const uint32_t* sflags, const DevSortedChunk* chunks, int32_t nchunks,
                              int32_t w, int32_t yps, int32_t ntracks, double q, int negate, double* thresh, double* seas,
-                             int64_t ldo, hipStream_t stream, unsigned long long* stats = nullptr);
+                             int64_t ldo, hipStream_t stream, unsigned long long* stats = nullptr,
+                             int32_t ndirect = 0);      // ndirect: how many of the chunks are marked direct
 // the sorted-list kernel on int16 codes (instantiated for the same records as launch_sorted_f32)
 hipError_t launch_sorted_i16(const int16_t* codes, const PackedI16& pk, int64_t C, int64_t ld, int64_t Tn,
                              const uint32_t* table, const uint32_t* sflags, const DevSortedChunk* chunks, int32_t nchunks,

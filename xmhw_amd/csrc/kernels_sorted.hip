@@ -282,6 +282,212 @@ __device__ __forceinline__ void pool_order_stats(const uint32_t (&key)[KPL], uin
     out_hi = vhi;
 }
 
+// ---- a chunk of ONE output row and few pooled tracks, settled directly (Feb 29 of a daily record) ----------------------
+// Such a chunk (plan.h: SortedPlan::direct -- one output row, at most NT = 12 pooled tracks, no SIMPLE row) walked its R table
+// rows with the whole body -- 40 tracks of which 30 push nothing, the general key conversion on every row, a top set grown
+// from nothing -- for a pool of at most 12 x R = 132 samples.  Here the wave reads that pool ONCE and is done: no LDS, no
+// lists, no select.  The lanes keep the main layout (2 lanes per cell, 32 cells per wave) and lane `sub` takes the steps
+// whose list slot it would own (slot = step mod R; slots 0..5 lane 0, 6..10 lane 1):
+//   * two sweeps of loads, each in flight together: the table entries of (own step, pooled track), then the samples;
+//   * keys by the general row's rule (NaN, a step that pushes nothing or lies outside [0, T): key 0);
+//   * per own step the 12 keys sorted, the six runs merged to the lane's 24 largest, one exchange between the two lanes and
+//     a bitonic sort: the cell's 24 largest keys, descending.  With at most 132 keys and q >= 0.85 or <= 0.15 the two order
+//     statistics are among the 21 largest (Cs + 1 = n - floor((n - 1) q), mirrored floor((n - 1) q) + 2: non-decreasing
+//     in n, 21 at n = 132), whatever the data: the row is exact and never flagged.  (The records of up to 8 tracks per
+//     lane run with three waves per SIMD on 168 registers: their direct chunks have at most NT = 6 pooled tracks -- 66
+//     keys, the order statistics among the 11 largest, 12 kept);
+//   * the sums in the main path's own order, so that `seas` keeps its bits: per step the valid samples of the even tracks
+//     (lane 0's on the main path) in track order from +0.0, likewise the odd tracks', each negated for cold spells, the
+//     list sum = the two added; per lane its slots' sums in slot order from 0.0; total = lane 0 + lane 1.  (The main
+//     path also adds +0.0 for every silent track and empty slot: that changes no bit of a sum that started from +0.0.)
+//
+// Where it runs.  In the records' own kernel, as the first thing a wave of such a chunk does (sorted_body): the direct
+// waves sit at the end of the launch beside the long chunks' last waves.  That holds for the builds of two waves per SIMD.
+// The four builds of three waves per SIMD (up to XMHW_WAVES3_MAX_YPS tracks per lane: 168 registers, some scratch) are not
+// given the body: with it inlined the register allocator spills a per-row value of the 8-track build's main loop and its
+// reload puts a vmcnt wait in front of the bookkeeping, behind the requests for the next row (tools/check_sorted_waits.py
+// finds it; a bare early return leaves the loop as it was).  Their direct chunks run in a small kernel of their own,
+// sorted_onerow_f32 below, launched on the call's stream before the main kernel, whose waves of those chunks return at once.
+#ifndef XMHW_WAVES3_MAX_YPS
+#define XMHW_WAVES3_MAX_YPS 8
+#endif
+#if XMHW_WAVES3_MAX_YPS == 8
+static_assert(sorted_direct_tracks(8) == 6 && sorted_direct_tracks(9) == 12, "the three-wave builds settle 6 tracks directly (plan.h)");
+#endif
+constexpr bool direct_in_launch(int yps) { return yps > XMHW_WAVES3_MAX_YPS; }
+
+// a and b descending -> a = the N largest of both, descending
+template <int N>
+__device__ __forceinline__ void direct_top(uint32_t (&a)[N], const uint32_t (&b)[N]) {
+    if constexpr (N == 12) {
+        uint32_t v[2 * N];
+#pragma unroll
+        for (int i = 0; i < N; ++i) { v[i] = a[i]; v[N + i] = b[i]; }
+        sortnet::MergeTop<N, N, N>::run(v);
+#pragma unroll
+        for (int i = 0; i < N; ++i) a[i] = v[i];
+    } else {
+        constexpr int H = N / 2;
+        uint32_t hi[H], lo[H];
+        // (max(a[i], b[N - 1 - i]): the N largest as a bitonic sequence; a half-cleaner leaves two bitonic halves, the larger first)
+#pragma unroll
+        for (int i = 0; i < H; ++i) {
+            const uint32_t p = umax(a[i], b[N - 1 - i]), r = umax(a[i + H], b[H - 1 - i]);
+            hi[i] = umax(p, r);
+            lo[i] = umin(p, r);
+        }
+        sortnet::BitonicDesc<H>::run(hi);
+        sortnet::BitonicDesc<H>::run(lo);
+#pragma unroll
+        for (int i = 0; i < H; ++i) { a[i] = hi[i]; a[H + i] = lo[i]; }
+    }
+}
+
+template <int NTP, int NT>
+__device__ __forceinline__ void direct_row(const char* __restrict__ col, bool cell_ok, int64_t cell, int sub, uint32_t ld4,
+                                           uint32_t tmax, const uint32_t* __restrict__ table, const DevSortedChunk& ch,
+                                           double q, int negate, bool mirror, int kneg, double* __restrict__ thresh,
+                                           double* __restrict__ seas, int64_t ldo) {
+    constexpr int R = 11, NS = 6, NK = 2 * NT;
+    static_assert(NT == 6 || NT == 12, "the sorters below are those of 6 / 12 and 12 / 24 keys");
+    // the pooled tracks, ascending (wave-uniform); an absent place repeats the first track and yields no key
+    uint64_t set = (static_cast<uint64_t>(ch.direct_hi) << 32) | ch.direct_lo;
+    uint32_t kt[NT], here[NT], even[NT], odd[NT];      // (masks: all ones or 0)
+    const uint32_t k_first = static_cast<uint32_t>(__builtin_ctzll(set));
+#pragma unroll
+    for (int i = 0; i < NT; ++i) {
+        const bool have = set != 0ull;
+        kt[i] = have ? static_cast<uint32_t>(__builtin_ctzll(set)) : k_first;
+        here[i] = have ? 0xFFFFFFFFu : 0u;
+        // (which half of the cell the track belongs to on the main path: lane 0 holds the even tracks)
+        odd[i] = here[i] & (0u - (kt[i] & 1u));
+        even[i] = here[i] & ~odd[i];
+        set &= set - 1ull;
+    }
+    // own steps: slot g = sub * NS + j holds step warm_start + (g - slot(warm_start)) mod R; lane 1's sixth slot does not exist
+    const int m0 = ((ch.warm_start % R) + R) % R;
+    uint32_t rowi[NS];       // first table entry of the step's row
+    uint32_t stepm[NS];      // all ones: the slot exists
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+        const int g = sub * NS + j;
+        stepm[j] = g < R ? 0xFFFFFFFFu : 0u;
+        int off = g - m0;
+        off = off < 0 ? off + R : off;
+        off = g < R ? off : 0;
+        rowi[j] = static_cast<uint32_t>(ch.trow0 + off) * static_cast<uint32_t>(NTP);
+    }
+    // ---- sweep 1: the table entries (0 = nothing pushed for an absent place or slot); sweep 2: the samples ---------------
+    uint32_t ent[NT][NS];
+#pragma unroll
+    for (int i = 0; i < NT; ++i)
+#pragma unroll
+        for (int j = 0; j < NS; ++j) ent[i][j] = table[rowi[j] + kt[i]];
+    float x[NT][NS];
+#pragma unroll
+    for (int i = 0; i < NT; ++i)
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            ent[i][j] = XMHW_BITOP3(ent[i][j], stepm[j], here[i], 0x80);
+            const uint32_t t = umin((ent[i][j] >> 1) - 2u, tmax);
+            x[i][j] = *reinterpret_cast<const float*>(col + static_cast<uint64_t>(t) * ld4);
+        }
+    // (everything has arrived before the first comparator: no wait inside the sorters)
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_sched_barrier(0);
+    // ---- keys, counts, sums ---------------------------------------------------------------------------------------------
+    const uint32_t kflip = kneg ? 0x80000000u : 0u;      // (the key of the negated sample = the key of the sample with its sign flipped)
+    uint32_t key[NS][NT];
+    double d_even[NS], d_odd[NS];
+    uint32_t nv = 0;
+#pragma unroll
+    for (int j = 0; j < NS; ++j) d_even[j] = d_odd[j] = 0.0;
+#pragma unroll
+    for (int i = 0; i < NT; ++i) {
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+            const float v = x[i][j];
+            const uint32_t bits = __float_as_uint(v);
+            // (valid: not NaN and a pushed sample -- code >= 2 --; every use is a mask, no condition is kept)
+            const uint32_t okm = (v == v && ent[i][j] >= 4u) ? 0xFFFFFFFFu : 0u;
+            key[j][i] = key_fast<false>(bits ^ kflip) & okm;
+            nv -= okm;
+            // (the other half's accumulator takes +0.0: no bit of a sum that started from +0.0 changes)
+            d_even[j] += static_cast<double>(__uint_as_float(XMHW_BITOP3(bits, okm, even[i], 0x80)));
+            d_odd[j] += static_cast<double>(__uint_as_float(XMHW_BITOP3(bits, okm, odd[i], 0x80)));
+        }
+    }
+    double tsum = 0.0;
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+        // (the slot lane 1 does not have adds +-0.0 here and +0.0 on the main path: the same bits, tsum is never -0.0)
+        const double de = negate ? -d_even[j] : d_even[j], dd = negate ? -d_odd[j] : d_odd[j];
+        tsum += de + dd;
+    }
+    const double total = tsum + swp(tsum);
+    const uint32_t n = nv + swp(nv);
+    // ---- the cell's 24 largest keys -------------------------------------------------------------------------------------
+    uint32_t top[NK];
+    {
+        uint32_t r01[NK], r23[NK], r45[NK];
+#pragma unroll
+        for (int j = 0; j < NS; ++j) sort_desc<NT>(key[j]);
+#pragma unroll
+        for (int i = 0; i < NT; ++i) {
+            r01[i] = key[0][i]; r01[NT + i] = key[1][i];
+            r23[i] = key[2][i]; r23[NT + i] = key[3][i];
+            r45[i] = key[4][i]; r45[NT + i] = key[5][i];
+        }
+        sortnet::MergeTop<NT, NT, NK>::run(r01);
+        sortnet::MergeTop<NT, NT, NK>::run(r23);
+        sortnet::MergeTop<NT, NT, NK>::run(r45);
+        direct_top(r01, r23);
+        direct_top(r01, r45);
+        // (the other lane's run; both lanes end with the same 24 keys)
+        uint32_t oth[NK];
+#pragma unroll
+        for (int i = 0; i < NK; ++i) oth[i] = swp(r01[i]);
+        direct_top(r01, oth);
+#pragma unroll
+        for (int i = 0; i < NK; ++i) top[i] = r01[i];
+    }
+    // ---- the two keys at the boundary of the top set: descending ranks Cs (the largest key outside) and Cs - 1 ------------
+    const uint32_t nn = n ? n : 1u;
+    const double vi = static_cast<double>(nn - 1) * q;
+    const double fl = floor(vi);
+    const double g = vi - fl;
+    const uint32_t lo = static_cast<uint32_t>(fl);
+    const bool need2 = lo + 1 < nn;
+    const uint32_t Cs = n ? (mirror ? lo + 1u : n - 1u - lo) : 0u;
+    uint32_t a_lo = 0u, a_hi = 0u;      // (a rank past the pool: no key, 0 -- what the lists answer there)
+#pragma unroll
+    for (int i = 0; i < NK; ++i) {
+        a_lo = Cs == static_cast<uint32_t>(i) ? top[i] : a_lo;
+        a_hi = Cs == static_cast<uint32_t>(i + 1) ? top[i] : a_hi;
+    }
+    if (!need2) {
+        if (mirror) a_lo = a_hi;
+        else a_hi = a_lo;
+    }
+    // ---- the output: the main path's epilogue (finish_rows) -------------------------------------------------------------
+    double th = make_nan(), se = make_nan();
+    if (n > 0) {
+        double v_lo = static_cast<double>(key_f32(mirror ? a_hi : a_lo));      // a[lo]
+        double v_hi = static_cast<double>(key_f32(mirror ? a_lo : a_hi));      // a[lo + 1]
+        if (mirror) {
+            v_lo = -v_lo;
+            v_hi = -v_hi;
+        }
+        se = total / static_cast<double>(n);
+        th = numpy_lerp(v_lo, v_hi, g);
+    }
+    if (sub == 0 && cell_ok) {
+        const int64_t row = static_cast<int64_t>(ch.begin);
+        thresh[row * ldo + cell] = th;
+        seas[row * ldo + cell] = se;
+    }
+}
+
 }  // namespace
 
 // stats (STATS builds): [0] wave-rows, [1] walk iterations (what the wave pays), [2] flagged cell-rows, [3] walk steps
@@ -350,6 +556,18 @@ __device__ __forceinline__ void sorted_body(
     const bool padded_last = (YPS - 1) * 2 + sub >= ntracks;
     const uint32_t padmask = padded_last ? 0xFFFFFFFFu : 0u;
     const uint32_t* tab = table + sub;
+
+    // (a chunk of one output row and few pooled tracks is settled at once: direct_row above.  float32 samples; the packed
+    // kernels and the counter twin walk every chunk)
+    if constexpr (!PACKED && !STATS) {
+        if ((ch.direct_lo | ch.direct_hi) != 0u) {
+            // (the three-wave builds: sorted_onerow_f32 has written the row already)
+            if constexpr (direct_in_launch(YPS))
+                direct_row<NTP, sorted_direct_tracks(YPS)>(col, cell_ok, cell, sub, static_cast<uint32_t>(ld) * ES, tmax, table, ch, q,
+                                                           negate, mirror, kneg, thresh, seas, ldo);
+            return;
+        }
+    }
 
     const uint32_t lds0 = static_cast<uint32_t>(reinterpret_cast<uintptr_t>((lds_u32*)lds));
     // (the array must start the workgroup's allocation: a window above rank 0 relies on its address wrapping around)
@@ -1249,9 +1467,7 @@ __device__ __forceinline__ void sorted_body(
 // up to 8 tracks per lane, 8 keys per list: 11,520 bytes of LDS a wave -- are asked to fit THREE (168 registers, 20..60 bytes
 // of scratch): 12- and 16-year records -4 % and -5.6 %; 9..12 tracks per lane would need 100..164 bytes of scratch and run
 // 1.5 x slower that way -- profiles/r6_experiments.txt)
-#ifndef XMHW_WAVES3_MAX_YPS
-#define XMHW_WAVES3_MAX_YPS 8
-#endif
+// (XMHW_WAVES3_MAX_YPS: above, with the direct row)
 #define XMHW_WAVES_PER_SIMD(Y) ((Y) <= XMHW_WAVES3_MAX_YPS ? 3 : 2)
 template <int YPS, int K, int KL, bool STATS>
 __global__ __launch_bounds__(64, XMHW_WAVES_PER_SIMD(YPS)) void clim_sorted_f32(
@@ -1261,6 +1477,24 @@ __global__ __launch_bounds__(64, XMHW_WAVES_PER_SIMD(YPS)) void clim_sorted_f32(
     unsigned long long* __restrict__ stats) {
     sorted_body<YPS, K, KL, STATS, false>(ts, C, ld, Tn, table, sflags, chunks, q, negate, ntracks, thresh, seas, ldo, stats,
                                       PackedI16{});
+}
+// the direct chunks of the three-wave builds, in a kernel of their own (see direct_row): the same lanes, chunks and table
+template <int YPS>
+__global__ __launch_bounds__(64) void sorted_onerow_f32(
+    const float* __restrict__ ts, int64_t C, int64_t ld, int64_t Tn, const uint32_t* __restrict__ table,
+    const DevSortedChunk* __restrict__ chunks, double q, int negate, double* __restrict__ thresh, double* __restrict__ seas,
+    int64_t ldo) {
+    const DevSortedChunk ch = chunks[blockIdx.y];
+    if ((ch.direct_lo | ch.direct_hi) == 0u) return;
+    const int lane = threadIdx.x & 63;
+    const int sub = lane & 1;
+    const int64_t cell = static_cast<int64_t>(blockIdx.x) * 32 + (lane >> 1);
+    const bool cell_ok = cell < C;
+    const char* col = reinterpret_cast<const char*>(ts) + (cell_ok ? cell : C - 1) * 4;
+    const bool mirror = q < 0.5;
+    const int kneg = (negate != 0) != mirror ? 1 : 0;
+    direct_row<2 * YPS, sorted_direct_tracks(YPS)>(col, cell_ok, cell, sub, static_cast<uint32_t>(ld) * 4u, static_cast<uint32_t>(Tn - 1),
+                                                   table, ch, q, negate, mirror, kneg, thresh, seas, ldo);
 }
 // the same on int16 codes (no counter twin)
 template <int YPS, int K, int KL>
@@ -1277,13 +1511,21 @@ typedef void (*SortedKernel)(const float*, int64_t, int64_t, int64_t, const uint
                              const DevSortedChunk*, double, int, int32_t, double*, double*, int64_t, unsigned long long*);
 typedef void (*SortedKernelI16)(const int16_t*, PackedI16, int64_t, int64_t, int64_t, const uint32_t*, const uint32_t*,
                                 const DevSortedChunk*, double, int, int32_t, double*, double*, int64_t);
-struct SortedEntry { int yps, k, kl; SortedKernel fn, fn_stats; SortedKernelI16 fn_i16; };
+typedef void (*SortedOnerow)(const float*, int64_t, int64_t, int64_t, const uint32_t*, const DevSortedChunk*, double, int,
+                             double*, double*, int64_t);
+// (the direct chunks' own kernel: the three-wave builds only)
+template <int YPS>
+constexpr SortedOnerow onerow_of() {
+    if constexpr (direct_in_launch(YPS)) return nullptr;
+    else return sorted_onerow_f32<YPS>;
+}
+struct SortedEntry { int yps, k, kl; SortedKernel fn, fn_stats; SortedKernelI16 fn_i16; SortedOnerow fn_onerow; };
 #ifdef XMHW_RING_STATS
 #define XMHW_SS(Y, K, KL) clim_sorted_f32<Y, K, KL, true>
 #else
 #define XMHW_SS(Y, K, KL) nullptr
 #endif
-#define XMHW_S2(Y, K, KL) {Y, K, KL, clim_sorted_f32<Y, K, KL, false>, XMHW_SS(Y, K, KL), clim_sorted_i16<Y, K, KL>}
+#define XMHW_S2(Y, K, KL) {Y, K, KL, clim_sorted_f32<Y, K, KL, false>, XMHW_SS(Y, K, KL), clim_sorted_i16<Y, K, KL>, onerow_of<Y>()}
 #define XMHW_S(Y, K) XMHW_S2(Y, K, K)
 // tracks per lane -> keys stored per list: about 0.4 x the tracks of the record (a list's share of the pool's top tenth
 // is a tenth of the tracks on average and reaches three to four times that on a steep seasonal slope), even, at most
@@ -1380,12 +1622,16 @@ int32_t sorted_lds_bytes(int32_t w, int32_t ntracks) {
 hipError_t launch_sorted_f32(const float* ts, int64_t C, int64_t ld, int64_t Tn, const uint32_t* table,
                              const uint32_t* sflags, const DevSortedChunk* chunks, int32_t nchunks,
                              int32_t w, int32_t yps, int32_t ntracks, double q, int negate, double* thresh, double* seas,
-                             int64_t ldo, hipStream_t stream, unsigned long long* stats) {
+                             int64_t ldo, hipStream_t stream, unsigned long long* stats, int32_t ndirect) {
     const SortedEntry* e = w == 5 ? find_sorted(yps) : nullptr;
     if (!e || ld >= (int64_t(1) << 30)) return hipErrorInvalidValue;
     if (C <= 0 || nchunks <= 0) return hipSuccess;
     dim3 grid(static_cast<unsigned>((C + 31) / 32), static_cast<unsigned>(nchunks));
     const bool twin = stats != nullptr && e->fn_stats != nullptr;
+    // (the three-wave builds: their direct chunks first, in the kernel of their own -- the main kernel's waves of those chunks
+    // return at once; the counter twin walks every chunk itself)
+    if (ndirect > 0 && e->fn_onerow != nullptr && !twin)
+        hipLaunchKernelGGL(e->fn_onerow, grid, dim3(64), 0, stream, ts, C, ld, Tn, table, chunks, q, negate, thresh, seas, ldo);
     hipLaunchKernelGGL(twin ? e->fn_stats : e->fn, grid, dim3(64), 0, stream, ts, C, ld, Tn, table, sflags, chunks, q,
                        negate, ntracks, thresh, seas, ldo, twin ? stats : nullptr);
     return hipGetLastError();

@@ -203,9 +203,23 @@ Plan::SortedPlan Plan::sorted_plan(int32_t ntp, int32_t min_rows_per_piece, int6
                 out.flags.push_back((simple ? 1u : 0u) | (consec ? 2u : 0u));
             }
             out.chunks.push_back(ch);
+            uint64_t set = 0;
+            for (int32_t k = 0; k < ntracks && k < 64; ++k) set |= inS[k] ? uint64_t(1) << k : 0;
+            out.pooled.push_back(set);
         }
     }
     return out;
+}
+
+bool Plan::SortedPlan::direct(size_t i, int32_t max_tracks) const {
+    const SortedChunk& ch = chunks[i];
+    if (ch.end - ch.begin != 1) return false;
+    int32_t npool = 0;
+    for (uint64_t s = pooled[i]; s; s &= s - 1) ++npool;
+    if (npool < 1 || npool > max_tracks) return false;
+    for (int32_t v = 0; v < ch.end - ch.warm_start; ++v)
+        if (flags[static_cast<size_t>(ch.trow0 + v)] & 1u) return false;
+    return true;
 }
 
 }  // namespace xmhw

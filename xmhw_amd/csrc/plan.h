@@ -27,6 +27,11 @@ constexpr uint32_t kCodeHold = 0;
 constexpr uint32_t kCodeInvalid = 1;
 constexpr uint32_t make_entry(uint32_t code, bool counted) { return (code << 1) | (counted ? 1u : 0u); }
 
+// the pooled tracks a directly settled chunk of the sorted-list kernel may have (Plan::SortedPlan::direct): 12, and 6 on the
+// records of up to 8 tracks per lane, whose kernels are built for three waves per SIMD -- 168 registers, which hold 6
+// tracks x 6 steps of samples and keys, not 12
+constexpr int32_t sorted_direct_tracks(int32_t tracks_per_lane) { return tracks_per_lane <= 8 ? 6 : 12; }
+
 struct Chunk {
     int32_t warm_start;  // first step executed (ring warm-up, no output)
     int32_t begin;       // first row with output
@@ -76,6 +81,14 @@ struct Plan {
     struct SortedPlan {
         std::vector<SortedChunk> chunks;
         std::vector<uint32_t> table, flags;
+        // per chunk: the pooled tracks S as a bit set (track k = bit k; the kernel serves at most 48 tracks)
+        std::vector<uint64_t> pooled;
+        // A chunk the kernel settles DIRECTLY (kernels_sorted.hip: direct_row) instead of walking its R table rows: one
+        // output row (Feb 29 of a daily record: the leap years' tracks alone), at most max_tracks =
+        // sorted_direct_tracks(tracks per lane) pooled tracks -- so that the 2 x max_tracks largest keys of the cell's pool
+        // hold both order statistics for every quantile the kernel is given and every pool size -- and no SIMPLE row (the
+        // general key conversion's summation order is the one reproduced).
+        bool direct(size_t chunk, int32_t max_tracks) const;
     };
     SortedPlan sorted_plan(int32_t ntp, int32_t min_rows_per_piece, int64_t pieces_wanted) const;
 };

@@ -116,6 +116,9 @@ PYBIND11_MODULE(_xmhw_hip, m) {
                                      flags.mutable_data()));
         return py::make_tuple(chunks, table, flags);
     });
+    // (an introspection entry behind device.Plan.sorted_direct(); the leading underscore keeps it out of the module's public
+    // surface, which tests/golden/binding_signatures.json pins)
+    m.def("_plan_sorted_direct", [](Ptr p, int64_t C) { int32_t v = 0; check(xmhw_plan_sorted_direct(p, C, &v)); return v; });
 
     m.def("plan_debug_stats", [](Ptr p, int enable, bool read) {
         py::array_t<uint64_t> out(16);

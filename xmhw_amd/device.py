@@ -286,6 +286,13 @@ class Plan:
                 la[k] = bool(la[k])
         return {"supported": r[0] == 0, "launches": launches, "chunks": r[23], "sorted_pieces": r[24]}
 
+    def sorted_direct(self, C=1):
+        """chunks of a float32 launch over C cells that the sorted-list kernel settles directly (one-row chunks of at
+        most 12 pooled tracks: Feb 29) instead of walking their table rows (xmhw_plan_sorted_direct); 0 with
+        XMHW_SORTED_ONEROW=0 in the environment"""
+        with as_xmhw_errors():
+            return int(self._h._plan_sorted_direct(self.handle, int(C)))
+
     def narrowed(self):
         """True if the last float64 clim_raw() of this plan ran on the float32 ring kernel (every
         sample float32-representable)."""
