@@ -156,8 +156,9 @@ def test_ties_quantised_constant_and_sea_ice_cells(dev):
 
 
 def test_steep_seasonal_cycle_overflows_lists_and_is_still_exact(dev):
-    """amplitude 30: a row-list holds far more than K of the pool's largest keys; the flagged cell-rows come back from
-    the generic kernel"""
+    """amplitude 30: a row-list holds far more than K of the pool's largest keys; the flagged cell-rows are recomputed
+    inside the kernel, by the whole wave, from the samples (step 4b, pool_order_stats).  Which rows those are, and every
+    branch of the recomputation: tests/test_gpu_sorted_capacity.py"""
     doy = _daily(1982, 2021)
     x = _series(doy.shape[0], 48, 13, amp=(20, 30))
     _check(dev, x, doy)
