@@ -1474,6 +1474,59 @@ int xmhw_spatial_corr_accumulate_f64(const double *ts_dev, int64_t ld, int64_t t
                                      int64_t *sxx_dev, int64_t *syy_dev, int64_t *sxy_dev, int64_t ldo, int64_t *n_range_dev,
                                      void *stream);
 
+/* ---- coarsen(): weighted block means in space and time ---- *
+ * The front-end stage: daily series to pentad or monthly means, a fine tile to the grid of a climatology, the grid under a
+ * reach or a lag range that the analysis stages cap.  Every sample is read once; the output is fy * fx * len times smaller.
+ *
+ * Inputs.  ts_dev[nt][ld] is the fine series x[t][j][i], UNCOMPACTED on the ny x nx grid, longitude the fast axis, float32
+ * or float64, ld >= ny * nx, NaN = no sample.  wi_dev[ny * nx] int32 weights, 0 <= wi <= 2^24 (not checked: they live on
+ * the device).  Spatial factors fy, fx >= 1.  The coarse grid is ncy x ncx with ncy <= ceil(ny / fy), ncx <= ceil(nx / fx):
+ * the caller chooses floor or ceil (or fewer); a block that hangs over the grid holds only its in-grid points.
+ * win_host[ns + 1] int32, relative to the first row passed, strictly increasing, win[0] >= 0, win[ns] <= nt: window s covers
+ * rows win[s] .. win[s + 1] - 1; rows in no window are not read.
+ *
+ * Sums.  For the coarse entry (s, J, I), over the in-grid fine samples of block x window that have wi > 0 and are not NaN:
+ *   xq = rint(((double)x - x0) * 2^XMHW_REGION_SERIES_BITS)     (the fixed point of region_series(), in float64 as written)
+ *   a sample with |x - x0| >= 2^7, or infinite, is left out of all sums and counted in *n_range_dev (int64, ADDED to)
+ *   n += 1, wsum += wi, xsum += wi * xq                          (exact integers)
+ * W = the sum of wi over the in-grid points of the block, land included; len = the window's length.
+ *
+ * Validity.  The entry is valid iff n >= 1 and wsum * 65536 >= a * len * W; a is an integer in [0, 65536], the least
+ * covered share in 65536ths; equality counts as valid.
+ *
+ * Output.  out_dev[s][J * ncx + I] = x0 + ((double)xsum / (double)wsum) / 65536.0, in float64 exactly as written, rounded
+ * once to the sample type; NaN for an invalid entry.  out_dev[ns][ldo] (ldo >= ncy * ncx) is WRITTEN, not added to; columns
+ * past ncy * ncx are never touched.  wsum_dev (int64 [ns][ldo]) and n_dev (int32 [ns][ldo]) are optional: NULL = not written.
+ *
+ * Cap and overflow.  fy * fx * (the longest window) <= XMHW_COARSEN_MAX_VOLUME = 4096, else XMHW_ERR_UNSUPPORTED.  With the
+ * cap |xsum| <= 2^12 * 2^24 * 2^23 = 2^59, wsum * 65536 < 2^52 and a * len * W <= 2^52.  The finish is two integer-to-double
+ * conversions, one correctly rounded division, an exact scaling and one add (the build uses -ffp-contract=off): numpy
+ * reproduces every bit.  The result does not depend on launch geometry, window chunks, time blocks or load widths.
+ *
+ * Refusals, in this order and before the first HIP call: a volume above the cap, ny * nx of 2^31 and more:
+ * XMHW_ERR_UNSUPPORTED.  A negative nt, ny or nx, ld < ny * nx, a factor below 1, ncy or ncx negative or above ceil, ldo <
+ * ncy * ncx, a negative ns, a NULL win_host with ns > 0, a win that is not strictly increasing or leaves [0, nt], a outside
+ * [0, 65536], x0 not finite: XMHW_ERR_INVALID.  Then nothing is launched for ns == 0 or an empty coarse grid; then a NULL
+ * ts_dev, wi_dev, out_dev or n_range_dev is XMHW_ERR_INVALID.  Asynchronous on `stream`.
+ * A lane owns one coarse cell and walks its fy rows x fx columns x len steps with three sums in registers; fx = 1, 2, 4 read
+ * a row's samples in one load of the lane's width where the pointers, ld and nx keep every lane aligned
+ * (csrc/kernels_coarsen.hip, csrc/coarsen_index.h).  xmhw_set_coarsen_variant (process-wide; tests and measurements): 0 = the
+ * widest loads the call allows (the default), 1 = loads of one sample, 2 = the run-time column loop of any other fx.
+ * xmhw_set_coarsen_chunk (likewise): the windows a workgroup takes per chunk, 0 = automatic.  Same results for every value. */
+#define XMHW_COARSEN_MAX_VOLUME      4096
+#define XMHW_COARSEN_MAX_WEIGHT_BITS 24
+int xmhw_set_coarsen_variant(int32_t variant);        /* tests and measurements; 0 = automatic */
+int xmhw_set_coarsen_chunk(int32_t windows);          /* tests and measurements; 0 = automatic */
+/* which instantiation a call with these arguments takes under the variant in force (no HIP call): 0 = the column loop,
+ * 1 = fx 1, 2 / 3 = fx 2 with loads of one / two samples, 4 / 5 = fx 4 with loads of one / four samples                  */
+int xmhw_coarsen_class(const void *ts_dev, const int32_t *wi_dev, int64_t ld, int32_t nx, int32_t itemsize, int32_t fx);
+int xmhw_coarsen_f32(const float *ts_dev, int64_t nt, int64_t ld, int32_t ny, int32_t nx, int32_t fy, int32_t fx, int32_t ncy,
+                     int32_t ncx, const int32_t *wi_dev, double x0, int32_t a, const int32_t *win_host, int32_t ns,
+                     float *out_dev, int64_t ldo, int64_t *wsum_dev, int32_t *n_dev, int64_t *n_range_dev, void *stream);
+int xmhw_coarsen_f64(const double *ts_dev, int64_t nt, int64_t ld, int32_t ny, int32_t nx, int32_t fy, int32_t fx, int32_t ncy,
+                     int32_t ncx, const int32_t *wi_dev, double x0, int32_t a, const int32_t *win_host, int32_t ns,
+                     double *out_dev, int64_t ldo, int64_t *wsum_dev, int32_t *n_dev, int64_t *n_range_dev, void *stream);
+
 /* ---- the sharded path: cells split across the GPUs of a node, ONE gather at the end ------- *
  * Replaces the reference's collect, dask.compute(climls) + xr.concat(dim='cell')
  * (xmhw/xmhw.py:197, :210-211).  Cells are independent (xmhw/xmhw.py:184-196), so rank r runs the

@@ -32,6 +32,7 @@ from .composite import mhw_composite, CompositeDataset
 from .lag_correlation import lag_correlation, LagCorrelationDataset
 from .distribution import anomaly_distribution, DistributionDataset
 from .spatial_correlation import spatial_correlation, SpatialCorrelationDataset
+from .coarsen import coarsen, CoarsenInfo, calendar_windows
 from .ingest import open_series, threshold_file
 from .detrend import detrend, DetrendSpec, FitDataset
 
@@ -45,6 +46,7 @@ __all__ = ["threshold", "threshold_array", "GridSeries", "ClimDataset", "XmhwExc
            "DisplacementDataset", "DisplacementTable", "heat_stress", "maximum_monthly_mean", "degree_heating_weeks",
            "HeatStressDataset", "MonthlyMeanDataset", "index_regression", "IndexRegressionDataset", "mhw_composite",
            "CompositeDataset", "lag_correlation", "LagCorrelationDataset", "anomaly_distribution",
-           "DistributionDataset", "spatial_correlation", "SpatialCorrelationDataset", "open_series",
+           "DistributionDataset", "spatial_correlation", "SpatialCorrelationDataset", "coarsen", "CoarsenInfo",
+           "calendar_windows", "open_series",
            "threshold_file", "detrend", "DetrendSpec", "FitDataset"]
 __version__ = "0.1.0"

@@ -63,6 +63,11 @@ def hip_spatialcorr():
     return _extension("_xmhw_hip_spatialcorr")
 
 
+def hip_coarsen():
+    """the bindings of coarsen()"""
+    return _extension("_xmhw_hip_coarsen")
+
+
 class _RetryOnNoMem:
     """The pybind11 module with one behaviour added: a call that runs out of device memory
     (XMHW_ERR_NOMEM -> MemoryError) is repeated once after the cached large device buffers of

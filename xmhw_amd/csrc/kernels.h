@@ -635,6 +635,24 @@ hipError_t launch_spatial_corr_accumulate(const T* ts, int64_t ld, int64_t t0, i
                                           int32_t* n, int64_t* sx, int64_t* sy, int64_t* sxx, int64_t* syy, int64_t* sxy,
                                           int64_t ldo, int64_t* n_range, hipStream_t stream);
 
+// coarsen() (kernels_coarsen.hip, coarsen_index.h): the weighted means of the blocks fy x fx of the UNCOMPACTED ny x nx grid
+// over the windows win[s] .. win[s + 1] - 1 of the nt rows at ts -- out [ns][ldo] in the sample type, WRITTEN; wsum int64 and
+// n int32 likewise where not NULL; *n_range ADDED to; the definition is in include/xmhw_amd.h, "coarsen()".  win_dev is a
+// DEVICE array of ns + 1 boundaries here, max_len the longest window of it.  variant: kCoarsenVariantAuto, or a narrower
+// instantiation than the call's alignment allows (tests and measurements); chunk_windows: the windows a workgroup takes per
+// chunk, 0 = automatic (coarsen_auto_chunk); same results for every value of either.
+constexpr int kCoarsenBits = 16;
+constexpr int kCoarsenRangeBits = 7;
+constexpr int kCoarsenMaxWeightBits = 24;
+constexpr int kCoarsenVariantAuto = 0;               // the widest loads the call's alignment allows
+constexpr int kCoarsenVariantNarrow = 1;             // fx = 2, 4 with loads of one sample
+constexpr int kCoarsenVariantGeneric = 2;            // the run-time column loop whatever fx
+template <typename T>
+hipError_t launch_coarsen(const T* ts, int64_t ld, int32_t ny, int32_t nx, int32_t fy, int32_t fx, int32_t ncy, int32_t ncx,
+                          const int32_t* wi, double x0, int32_t a, const int32_t* win_dev, int32_t ns, int32_t max_len,
+                          int32_t variant, int32_t chunk_windows, T* out, int64_t ldo, int64_t* wsum, int32_t* n,
+                          int64_t* n_range, hipStream_t stream);
+
 // file bytes -> samples (kernels_ingest.hip): raw_type = item size of the stored type (2 int16, 4 float32,
 // 8 float64), swap = the file is big-endian, optional scale/offset (CF packing) and fill value -> NaN
 hipError_t launch_encode_i16(const float* in, int64_t rows, int64_t cols, int64_t ld_in, int16_t* out, int64_t ld_out,

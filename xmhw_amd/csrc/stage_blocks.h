@@ -123,6 +123,17 @@ static inline int64_t spatial_corr_auto_block(int64_t nt, int64_t ny, int64_t nx
     return nt > 0 ? stage_auto_block(nt, ceil_div(ny, rows) * ceil_div(nx, 64) * spatial_corr_groups(D), nt, 256, 1) : 1;
 }
 
+// coarsen(): the axis is the ns windows, a workgroup is 256 coarse cells.  A chunk carries nothing over and flushes
+// nothing, so short chunks cost a workgroup's start and no more; long ones leave the last workgroups of a launch alone on
+// the chip.  A chunk takes the windows that hold about 64 lines x steps of requests per lane (`rows` = fy fine rows by
+// `max_len` steps of the longest window each): a workgroup then lives for microseconds, thousands of them per launch; a
+// grid too small to fill the chip with such chunks splits the windows until about 2048 workgroups exist.
+static inline int64_t coarsen_auto_chunk(int64_t ns, int64_t cells, int64_t rows, int64_t max_len) {
+    const int64_t work = rows * max_len > 0 ? rows * max_len : 1;
+    const int64_t wg = cells > 0 ? ceil_div(cells, kStageThreads) : 1;
+    return ns > 0 ? stage_auto_block(ns, wg, ns, 64 / work > 0 ? 64 / work : 1, 1) : 1;
+}
+
 // mhw_cooccurrence(): the axis is the W words of the bitmaps, a workgroup takes one lag group (grid.z).  One block over W
 // keeps the flushes rare and needs no first-word loads; a slab whose workgroups x lag groups do not fill the chip splits
 // the word axis until about 2048 workgroups exist.
