@@ -1527,6 +1527,82 @@ int xmhw_coarsen_f64(const double *ts_dev, int64_t nt, int64_t ld, int32_t ny, i
                      int32_t ncx, const int32_t *wi_dev, double x0, int32_t a, const int32_t *win_host, int32_t ns,
                      double *out_dev, int64_t ldo, int64_t *wsum_dev, int32_t *n_dev, int64_t *n_range_dev, void *stream);
 
+/* ---- regrid(): first-order conservative remapping between two rectilinear grids ---- *
+ * The front-end stage that brings two products onto one grid: OISST (ascending latitude, centres at x.125) onto ERA5
+ * (descending, centres at x.00), either onto a model's 1 degree grid.  coarsen() nests integer blocks of one grid; this
+ * stage takes any two lat-lon grids.  Rectilinear grids make the overlap of the destination cell (J, I) with the source cell
+ * (j, i) a product, the overlap of row J with row j times the overlap of column I with column i: the device sees two small
+ * CSR tables and no 2-D weight matrix.
+ *
+ * Source series.  ts_dev[nt][ld] is x[t][j][i], UNCOMPACTED on the ny x nx grid, longitude the fast axis, float32 or
+ * float64, ld >= ny * nx, NaN = no sample.
+ *
+ * Row table (host arrays).  row_first[my], row_ptr[my + 1] (row_ptr[0] = 0, non-decreasing): destination row J reads the
+ * source rows row_first[J] + r, r < row_ptr[J + 1] - row_ptr[J] -- consecutive indices in memory order, so ascending or
+ * descending latitude makes no difference to the device -- under the int32 weights ay[row_ptr[J] + r]; wy[J] is the row's
+ * full extent in the same unit.  Column table.  col_first[mx], col_ptr[mx + 1], ax[], wx[mx] likewise; with periodic != 0
+ * the source column is (col_first[I] + k) mod nx, and a run may cross the seam.
+ *
+ * Caps.  0 <= ay, ax <= XMHW_REGRID_MAX_WEIGHT = 2^12; a run holds at most XMHW_REGRID_MAX_RUN = 64 entries per axis, so at
+ * most 4,096 samples feed a cell and w = ay * ax <= 2^24, the bound of coarsen(); the weights of a run sum to its extent at
+ * most and wy, wx <= XMHW_REGRID_MAX_EXTENT = 2^18; row_first + count <= ny; col_first + count <= nx, or, periodic,
+ * 0 <= col_first < nx and count <= nx.  A run of 0 entries is allowed: that cell is NaN with n = 0.
+ *
+ * Sums.  For (t, J, I), over the pairs (r, k) with w = ay * ax > 0 whose sample is not NaN:
+ *   xq = rint(((double)x - x0) * 2^XMHW_REGION_SERIES_BITS)     (the fixed point of region_series(), in float64 as written)
+ *   a pair with |x - x0| >= 2^7, or an infinite x, is left out of all sums and counted in *n_range_dev (int64, ADDED to):
+ *   the count is of (destination, source) PAIRS, because a source sample may feed several cells or none
+ *   n += 1, wsum += w, xsum += w * xq                            (exact integers)
+ * |xsum| <= 2^12 * 2^24 * 2^23 = 2^59, wsum * 65536 <= 2^52 and a * wy * wx <= 2^52.  The sums are exactly separable,
+ * sum_r ay * (sum_k ax * ...), and the kernel uses that.
+ *
+ * Validity.  n >= 1 and wsum * 65536 >= a * wy[J] * wx[I]; a is an integer in [0, 65536], the least covered share in
+ * 65536ths; equality counts as valid.
+ *
+ * Output.  out_dev[t][J * mx + I] = x0 + ((double)xsum / (double)wsum) / 65536.0, in float64 exactly as written, rounded
+ * once to the sample type; NaN for an invalid cell.  out_dev[nt][ldo] (ldo >= my * mx) is WRITTEN, not added to; columns
+ * past my * mx are never touched.  wsum_dev (int64 [nt][ldo]) and n_dev (int32 [nt][ldo]) are optional: NULL = not written.
+ * The finish is two integer-to-double conversions, one correctly rounded division, an exact scaling and one add (the build
+ * uses -ffp-contract=off): numpy reproduces every bit.  The result does not depend on launch geometry, step chunks, time
+ * blocks or the path taken.
+ *
+ * Refusals, in this order and before the first HIP call.  (1) Over the tables that can be read (all pointers of the axis
+ * there, the pointer table from 0 and non-decreasing): a run longer than 64, an extent above 2^18, a weight above 2^12; then
+ * ny * nx or my * mx of 2^31 and more: XMHW_ERR_UNSUPPORTED.  (2) A negative nt, ny, nx, my or mx, ld < ny * nx,
+ * ldo < my * mx; tables that cannot be read, a negative weight, weights of a run that exceed its extent, a run that leaves
+ * the source grid (rows first, then columns); a outside [0, 65536]; x0 not finite: XMHW_ERR_INVALID.  (3) Nothing is
+ * launched for nt == 0 or an empty destination grid.  (4) A NULL ts_dev, out_dev or n_range_dev is XMHW_ERR_INVALID.  The
+ * tables are then uploaded as one cached device table (the time blocks of a call reuse it).  Asynchronous on `stream`.
+ *
+ * A lane owns one destination cell; a workgroup is one destination row x 256 columns.  Two paths give identical bits
+ * (csrc/kernels_regrid.hip, csrc/regrid_index.h): direct -- every lane loads and converts its own samples, the samples of
+ * four steps requested together, any table within the caps -- and staged -- the workgroup loads the source footprint of its
+ * tile once per step, converts every sample once into an LDS dword and the lanes read their words from LDS; possible where
+ * (the longest row run) x (the widest column span of a tile) fits 16,384 dwords.  The automatic choice takes the staged path
+ * where it measured faster: that product is 4,096 dwords at most and the span holds two source columns per lane and more.
+ * xmhw_set_regrid_variant (process-wide; tests and measurements): 0 = automatic, 1 = direct, 2 = staged where it fits.
+ * xmhw_set_regrid_chunk (likewise): the steps a workgroup takes per chunk, 0 = automatic.  Same results for every value.  */
+#define XMHW_REGRID_MAX_RUN    64
+#define XMHW_REGRID_MAX_WEIGHT 4096
+#define XMHW_REGRID_MAX_EXTENT 262144
+int xmhw_set_regrid_variant(int32_t variant);         /* tests and measurements; 0 = automatic */
+int xmhw_set_regrid_chunk(int32_t steps);             /* tests and measurements; 0 = automatic */
+/* which path a call with these host tables takes under the variant in force (no HIP call): 1 = direct, 2 = staged;
+ * 0 = the tables describe no call (a negative size, nx < 1, a NULL table, a run that is negative, longer than 64 or
+ * leaves the grid)                                                                                                       */
+int xmhw_regrid_class(int32_t nx, int32_t my, int32_t mx, const int32_t *row_ptr_host, const int32_t *col_first_host,
+                      const int32_t *col_ptr_host, int32_t periodic);
+int xmhw_regrid_f32(const float *ts_dev, int64_t nt, int64_t ld, int32_t ny, int32_t nx, int32_t my, int32_t mx,
+                    const int32_t *row_first_host, const int32_t *row_ptr_host, const int32_t *ay_host, const int32_t *wy_host,
+                    const int32_t *col_first_host, const int32_t *col_ptr_host, const int32_t *ax_host, const int32_t *wx_host,
+                    int32_t periodic, double x0, int32_t a, float *out_dev, int64_t ldo, int64_t *wsum_dev, int32_t *n_dev,
+                    int64_t *n_range_dev, void *stream);
+int xmhw_regrid_f64(const double *ts_dev, int64_t nt, int64_t ld, int32_t ny, int32_t nx, int32_t my, int32_t mx,
+                    const int32_t *row_first_host, const int32_t *row_ptr_host, const int32_t *ay_host, const int32_t *wy_host,
+                    const int32_t *col_first_host, const int32_t *col_ptr_host, const int32_t *ax_host, const int32_t *wx_host,
+                    int32_t periodic, double x0, int32_t a, double *out_dev, int64_t ldo, int64_t *wsum_dev, int32_t *n_dev,
+                    int64_t *n_range_dev, void *stream);
+
 /* ---- the sharded path: cells split across the GPUs of a node, ONE gather at the end ------- *
  * Replaces the reference's collect, dask.compute(climls) + xr.concat(dim='cell')
  * (xmhw/xmhw.py:197, :210-211).  Cells are independent (xmhw/xmhw.py:184-196), so rank r runs the

@@ -33,6 +33,7 @@ from .lag_correlation import lag_correlation, LagCorrelationDataset
 from .distribution import anomaly_distribution, DistributionDataset
 from .spatial_correlation import spatial_correlation, SpatialCorrelationDataset
 from .coarsen import coarsen, CoarsenInfo, calendar_windows
+from .regrid import regrid, RegridInfo, axis_bounds, overlap_table
 from .ingest import open_series, threshold_file
 from .detrend import detrend, DetrendSpec, FitDataset
 
@@ -47,6 +48,6 @@ __all__ = ["threshold", "threshold_array", "GridSeries", "ClimDataset", "XmhwExc
            "HeatStressDataset", "MonthlyMeanDataset", "index_regression", "IndexRegressionDataset", "mhw_composite",
            "CompositeDataset", "lag_correlation", "LagCorrelationDataset", "anomaly_distribution",
            "DistributionDataset", "spatial_correlation", "SpatialCorrelationDataset", "coarsen", "CoarsenInfo",
-           "calendar_windows", "open_series",
+           "calendar_windows", "regrid", "RegridInfo", "axis_bounds", "overlap_table", "open_series",
            "threshold_file", "detrend", "DetrendSpec", "FitDataset"]
 __version__ = "0.1.0"

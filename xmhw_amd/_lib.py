@@ -68,6 +68,11 @@ def hip_coarsen():
     return _extension("_xmhw_hip_coarsen")
 
 
+def hip_regrid():
+    """the bindings of regrid()"""
+    return _extension("_xmhw_hip_regrid")
+
+
 class _RetryOnNoMem:
     """The pybind11 module with one behaviour added: a call that runs out of device memory
     (XMHW_ERR_NOMEM -> MemoryError) is repeated once after the cached large device buffers of

@@ -653,6 +653,25 @@ hipError_t launch_coarsen(const T* ts, int64_t ld, int32_t ny, int32_t nx, int32
                           int32_t variant, int32_t chunk_windows, T* out, int64_t ldo, int64_t* wsum, int32_t* n,
                           int64_t* n_range, hipStream_t stream);
 
+// regrid() (kernels_regrid.hip, regrid_index.h): first-order conservative remapping of the UNCOMPACTED ny x nx series at ts
+// onto the my x mx destination grid under two CSR overlap tables -- out [nt][ldo] in the sample type, WRITTEN; wsum int64 and
+// n int32 likewise where not NULL; *n_range ADDED to; the definition is in include/xmhw_amd.h, "regrid()".  table_dev is the
+// ONE device table that holds the ten int32 tables of the call at the places `lay` names (regrid_layout); max_rows, max_cols
+// the longest run per axis and max_width the widest tile span (regrid_max_width), taken from the host tables.  variant:
+// kRegridVariantAuto, Direct or Staged (staged where the footprint fits, tests and measurements); chunk_steps: the steps a
+// workgroup takes per chunk, 0 = automatic (regrid_auto_chunk); same results for every value of either.
+constexpr int kRegridBits = 16;
+constexpr int kRegridRangeBits = 7;
+constexpr int kRegridVariantAuto = 0;
+constexpr int kRegridVariantDirect = 1;
+constexpr int kRegridVariantStaged = 2;
+struct RegridLayout;
+template <typename T>
+hipError_t launch_regrid(const T* ts, int64_t nt, int64_t ld, int32_t ny, int32_t nx, int32_t my, int32_t mx,
+                         const int32_t* table_dev, const RegridLayout& lay, int32_t max_rows, int32_t max_cols,
+                         int32_t max_width, int32_t periodic, double x0, int32_t a, int32_t variant, int64_t chunk_steps,
+                         T* out, int64_t ldo, int64_t* wsum, int32_t* n, int64_t* n_range, hipStream_t stream);
+
 // file bytes -> samples (kernels_ingest.hip): raw_type = item size of the stored type (2 int16, 4 float32,
 // 8 float64), swap = the file is big-endian, optional scale/offset (CF packing) and fill value -> NaN
 hipError_t launch_encode_i16(const float* in, int64_t rows, int64_t cols, int64_t ld_in, int16_t* out, int64_t ld_out,

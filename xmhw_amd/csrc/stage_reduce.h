@@ -3,7 +3,7 @@
 // mhw_days_by() (kernels_class.hip), mhw_cooccurrence() (kernels_cooccur.hip), mhw_displacement()
 // (kernels_displacement.hip), heat_stress() (kernels_stress.hip), index_regression() (kernels_regress.hip),
 // mhw_composite() (kernels_composite.hip), lag_correlation() (kernels_lagcorr.hip), anomaly_distribution()
-// (kernels_distribution.hip), spatial_correlation() (kernels_spatialcorr.hip) and coarsen() (kernels_coarsen.hip).  Each rule below exists once: the Python oracles and the public documentation state it once as well.  kernels.h, "The
+// (kernels_distribution.hip), spatial_correlation() (kernels_spatialcorr.hip), coarsen() (kernels_coarsen.hip) and regrid() (kernels_regrid.hip).  Each rule below exists once: the Python oracles and the public documentation state it once as well.  kernels.h, "The
 // frame of a class reduction", describes the kernels that use most of it; stage_blocks.h holds the block lengths.
 #pragma once
 #include "device_common.h"
