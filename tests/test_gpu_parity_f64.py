@@ -1,7 +1,11 @@
 """Parity of the float64 paths (the second-generation ring kernel's 64-bit mode where it is instantiated: w = 5;
 the generic kernel elsewhere) against the oracle and against each other, on the same families of inputs as the
 float32 tests.  The round-1 float64 ring kernel is gone (round 3): an explicit ring request on a plan the 64-bit
-mode does not cover is refused, see test_explicit_ring_request_on_an_uncovered_float64_plan_is_refused."""
+mode does not cover is refused, see test_explicit_ring_request_on_an_uncovered_float64_plan_is_refused.
+
+The per-instantiation sweep is tests/test_gpu_f64_modes.py: every dispatchable instantiation of the 64-bit mode, the ones
+behind XMHW_RING3_F64=0 and XMHW_RING3_F64_LANES=8 included, at its fewest and most tracks on clustered doubles of both
+signs (test_clustered_doubles_through_every_dispatchable_float64_kernel here reaches four of them)."""
 import numpy as np
 import numpy.testing as npt
 import pytest
