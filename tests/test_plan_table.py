@@ -174,13 +174,16 @@ def test_bad_arguments():
 
 
 def test_c_abi_exports_every_declared_symbol():
+    """The stage entries stand at the end of their kernel files and the extension modules link with unresolved symbols
+    allowed: an entry lost in a move would otherwise show up only as the import error of one module.  This names it."""
     hdr = open(os.path.join(ROOT, "include", "xmhw_amd.h")).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     names = sorted(set(re.findall(r"\b(xmhw_[a-z0-9_]+)\s*\(", hdr)))
-    assert len(names) >= 35
+    # the functions the header declared when the stage entries left capi.cpp: the scan may find more, never fewer
+    assert len(names) >= 179, len(names)
     lib = ctypes.CDLL(os.path.join(ROOT, "xmhw_amd", "libxmhw_amd.so"))
     missing = [n for n in names if not hasattr(lib, n)]
-    assert not missing, missing
+    assert not missing, "declared in include/xmhw_amd.h but not exported by libxmhw_amd.so: " + ", ".join(missing)
     lib.xmhw_arch.restype = ctypes.c_char_p
     assert lib.xmhw_arch() == b"gfx950"
     assert lib.xmhw_version() >= 1

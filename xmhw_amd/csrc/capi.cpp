@@ -19,22 +19,22 @@
 #include <string>
 #include <vector>
 
+#include "entry_common.h"
 #include "kernels.h"
 #include "plan.h"
 #include "route.h"
-#include "stage_blocks.h"
-#include "coarsen_index.h"
-#include "regrid_index.h"
+
+using namespace xmhw::entry;
 
 namespace {
-
 thread_local std::string g_err;
+}  // namespace
 
-int fail(int code, const std::string& msg) {
+int xmhw::entry::fail(int code, const std::string& msg) {
     g_err = msg;
     return code;
 }
-int hip_fail(hipError_t e, const char* what) {
+int xmhw::entry::hip_fail(hipError_t e, const char* what) {
     // out of device memory is reported as such wherever it happens (callers that cache device
     // buffers release them and retry on XMHW_ERR_NOMEM)
     if (e == hipErrorOutOfMemory) {
@@ -43,7 +43,6 @@ int hip_fail(hipError_t e, const char* what) {
     }
     return fail(XMHW_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
-}  // namespace
 // shared with comm.cpp
 int xmhw_set_error_(int code, const std::string& msg) { return fail(code, msg); }
 namespace {
@@ -404,28 +403,16 @@ int clim_oneshot(const T* ts, const int32_t* doy, int64_t Tn, int64_t C, int32_t
 // "asynchronous" stream argument a fiction.  Now a small cache keyed by the table's content keeps them
 // (uploaded once, with a blocking copy, at the first call that sees them), and scratch buffers are
 // kept per stream and grow on demand: steady-state calls neither allocate nor synchronise.
-struct ChunkTables {
-    int32_t *tile_begin = nullptr, *t0 = nullptr, *i0 = nullptr, *n = nullptr;
-    int32_t ntiles = 0;
-    int64_t nchunks = 0;
-};
-struct RowsEntry {
-    std::vector<int32_t> host;
-    int device = 0;
-    int32_t* d_rows = nullptr;
-    std::map<std::pair<int64_t, int>, ChunkTables> chunks;      // (D, tile) -> tables
-    void* d_segs = nullptr;                                     // class labels: the per-word segment list (cooccur_segments)
-    int32_t *seg_off = nullptr, *seg_class = nullptr;
-    uint64_t* seg_mask = nullptr;
-    uint64_t stamp = 0;
-    ~RowsEntry() {
-        if (d_rows) (void)hipFree(d_rows);
-        if (d_segs) (void)hipFree(d_segs);
-        for (auto& kv : chunks)
-            for (int32_t* p : {kv.second.tile_begin, kv.second.t0, kv.second.i0, kv.second.n})
-                if (p) (void)hipFree(p);
-    }
-};
+// (RowsEntry, RowsRef and ScratchRef are declared in entry_common.h: the stage entries in the kernel files hold them too)
+}  // namespace
+xmhw::entry::RowsEntry::~RowsEntry() {
+    if (d_rows) (void)hipFree(d_rows);
+    if (d_segs) (void)hipFree(d_segs);
+    for (auto& kv : chunks)
+        for (int32_t* p : {kv.second.tile_begin, kv.second.t0, kv.second.i0, kv.second.n})
+            if (p) (void)hipFree(p);
+}
+namespace {
 std::mutex g_cache_mu;
 std::vector<std::shared_ptr<RowsEntry>> g_rows_cache;
 uint64_t g_stamp = 0;
@@ -434,7 +421,6 @@ constexpr size_t kRowsCacheSlots = 8;
 // returns nullptr and sets *err on failure.  The caller HOLDS the returned pointer until its launches are queued: an
 // entry another thread evicts meanwhile is destroyed (hipFree, which waits for the device) only when the last holder
 // lets go of it.
-using RowsRef = std::shared_ptr<RowsEntry>;
 RowsRef cached_rows(const int32_t* row_of_t, int64_t Tn, hipError_t* err) {
     std::lock_guard<std::mutex> lock(g_cache_mu);
     int dev = 0;
@@ -468,7 +454,6 @@ RowsRef cached_rows(const int32_t* row_of_t, int64_t Tn, hipError_t* err) {
 // scratch memory per (device, stream): grows on demand (the only synchronising moment), never shrinks.  A caller
 // keeps the ScratchRef for the length of its call -- scratch->get() is its buffer: a buffer that another thread on the
 // same stream outgrows meanwhile is freed only when its last holder is done.
-using ScratchRef = std::shared_ptr<void>;
 struct Scratch { ScratchRef ptr; size_t cap = 0; };
 std::map<std::pair<int, void*>, Scratch> g_scratch;
 hipError_t scratch_get(hipStream_t st, size_t bytes, ScratchRef* keep) {
@@ -500,26 +485,31 @@ void release_cached_tables() {
     g_scratch.clear();
 }
 
-// ---- the steps the stage entries share ----------------------------------------------------------
-// Each is one call in the entry, in the entry's own order: which refusal wins when two apply, and which zero-size return
-// comes before which NULL check, is part of the ABI (tests/test_host_entry_refusals.py).
+}  // namespace
 
-// the status of an entry's last HIP call as the entry's own
+// ---- the steps the stage entries share (declared in entry_common.h) ------------------------------
+namespace xmhw {
+namespace entry {
+
 int status_of(hipError_t e, const char* what) { return e == hipSuccess ? XMHW_OK : hip_fail(e, what); }
 
-// an int32 host table on the device (cached_rows); the caller holds *table until its launches are queued
+int set_knob(std::atomic<int>& knob, int32_t value, const char* message) {
+    if (value < 0) return fail(XMHW_ERR_INVALID, message);
+    knob = value;
+    return XMHW_OK;
+}
+
+// (cached_rows)
 int upload_table(const int32_t* host, int64_t n, const char* what, RowsRef* table) {
     hipError_t e = hipSuccess;
     *table = cached_rows(host, n, &e);
     return *table ? XMHW_OK : hip_fail(e, what);
 }
 
-// `bytes` of this stream's scratch buffer; the caller holds *scratch until its launches are queued
 int claim_scratch(hipStream_t st, size_t bytes, ScratchRef* scratch) {
     return status_of(scratch_get(st, bytes, scratch), "scratch allocation");
 }
 
-// the first step whose label lies outside [lo, hi), or n
 int64_t first_outside(const int32_t* labels, int64_t n, int64_t lo, int64_t hi) {
     int64_t t = 0;
     while (t < n && labels[t] >= lo && labels[t] < hi) ++t;
@@ -528,10 +518,7 @@ int64_t first_outside(const int32_t* labels, int64_t n, int64_t lo, int64_t hi) 
 int check_labels(const int32_t* labels, int64_t n, int64_t lo, int64_t hi, const char* message) {
     return first_outside(labels, n, lo, hi) < n ? fail(XMHW_ERR_INVALID, message) : XMHW_OK;
 }
-constexpr const char* kRowsOutside = "row_of_t outside [0, D)";
-constexpr const char* kClassesOutside = "class_of_t outside [-1, K)";
 
-// the event-day bitmap of this call in this stream's scratch buffer: (T + 63) / 64 words per cell, leading dimension C
 int event_day_bitmap(const uint64_t* bits, int64_t Tn, int64_t C, int64_t ldb, int32_t min_duration, int32_t join_gaps,
                      int32_t max_gap, hipStream_t st, ScratchRef* scratch, const uint64_t** inev) {
     const int64_t W = (Tn + 63) / 64;
@@ -541,6 +528,48 @@ int event_day_bitmap(const uint64_t* bits, int64_t Tn, int64_t C, int64_t ldb, i
     return status_of(xmhw::launch_event_day_bits(bits, Tn, C, ldb, min_duration, join_gaps, max_gap, words, C, st),
                      "event_day_bits launch");
 }
+
+// One allocation: masks, offsets, classes.
+hipError_t cooccur_segments(const RowsRef& classes, int64_t Tn) {
+    std::lock_guard<std::mutex> lock(g_cache_mu);
+    if (classes->d_segs) return hipSuccess;
+    const std::vector<int32_t>& k = classes->host;
+    const int64_t W = (Tn + 63) / 64;
+    std::vector<int32_t> off(static_cast<size_t>(W) + 1, 0), cls;
+    std::vector<uint64_t> mask;
+    for (int64_t w = 0; w < W; ++w) {
+        const int64_t t1 = std::min<int64_t>(Tn, w * 64 + 64);
+        for (int64_t t = w * 64; t < t1;) {
+            if (k[t] < 0) { ++t; continue; }
+            uint64_t m = 0;
+            const int32_t c = k[t];
+            for (; t < t1 && k[t] == c; ++t) m |= uint64_t{1} << (t & 63);
+            cls.push_back(c);
+            mask.push_back(m);
+        }
+        off[static_cast<size_t>(w) + 1] = static_cast<int32_t>(cls.size());
+    }
+    const size_t n = cls.size();
+    const size_t b_mask = sizeof(uint64_t) * n, b_off = sizeof(int32_t) * off.size(), b_cls = sizeof(int32_t) * n;
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, b_mask + b_off + b_cls + 8);
+    if (e != hipSuccess) return e;
+    char* base = static_cast<char*>(p);
+    if (n) e = hipMemcpy(base, mask.data(), b_mask, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(base + b_mask, off.data(), b_off, hipMemcpyHostToDevice);
+    if (e == hipSuccess && n) e = hipMemcpy(base + b_mask + b_off, cls.data(), b_cls, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(p); return e; }
+    classes->d_segs = p;
+    classes->seg_mask = reinterpret_cast<uint64_t*>(base);
+    classes->seg_off = reinterpret_cast<int32_t*>(base + b_mask);
+    classes->seg_class = reinterpret_cast<int32_t*>(base + b_mask + b_off);
+    return hipSuccess;
+}
+
+}  // namespace entry
+}  // namespace xmhw
+
+namespace {
 
 template <typename T>
 int detect_events(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* thresh, int64_t ldt,
@@ -690,684 +719,6 @@ int exceed_bits(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* th
         return status_of(xmhw::launch_exceed_bits<double, double>(ts, Tn, C, ld, thresh, ldt, rows->d_rows, negate, bits,
                                                                   ldb, st),
                          "exceed_bits launch");
-}
-
-template <typename T>
-int coverage_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* seas, const double* thresh,
-                        int64_t ldc, const int32_t* row_of_t, int32_t negate, const uint64_t* bits, int64_t ldb,
-                        int32_t min_duration, int32_t join_gaps, int32_t max_gap, const int64_t* wq,
-                        const int32_t* region, int32_t R, int64_t* cells, int64_t* area_q, void* stream) {
-    if (Tn <= 0 || C < 0 || ld < C || ldc < C || ldb < C) return fail(XMHW_ERR_INVALID, "bad T/C/ld/ldc/ldb");
-    if (Tn >= (int64_t{1} << 31)) return fail(XMHW_ERR_INVALID, "T too large");
-    if (min_duration < 1 || max_gap < 0) return fail(XMHW_ERR_INVALID, "bad minDuration/maxGap");
-    if (R < 1) return fail(XMHW_ERR_INVALID, "R must be >= 1");
-    if (R > xmhw::kCoverageMaxRegions)
-        return fail(XMHW_ERR_UNSUPPORTED, "coverage: R above the cap of " + std::to_string(xmhw::kCoverageMaxRegions) + " regions");
-    if (C == 0) return XMHW_OK;
-    if (!ts || !seas || !thresh || !row_of_t || !bits || !wq || !region || !cells || !area_q)
-        return fail(XMHW_ERR_INVALID, "NULL buffer");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    RowsRef rows;
-    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
-    ScratchRef scratch;
-    const uint64_t* inev = nullptr;
-    if (int rc = event_day_bitmap(bits, Tn, C, ldb, min_duration, join_gaps, max_gap, st, &scratch, &inev)) return rc;
-    return status_of(xmhw::launch_coverage_accumulate<T>(ts, Tn, C, ld, seas, thresh, ldc, rows->d_rows, negate, inev, C, wq,
-                                                         region, R, cells, area_q, st),
-                     "coverage_accumulate launch");
-}
-
-static std::atomic<int> g_region_wave_sum{1};   // region_accumulate sums 8 steps of a wave together (xmhw_set_region_wave_sum)
-
-template <typename T>
-int region_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, double x0, const int64_t* wi, const int32_t* region,
-                      int32_t R, int64_t* acc, int64_t* n_range, void* stream) {
-    if (Tn < 0 || C < 0 || ld < C) return fail(XMHW_ERR_INVALID, "bad T/C/ld");
-    if (Tn >= (int64_t{1} << 31)) return fail(XMHW_ERR_INVALID, "T too large");
-    if (R < 1) return fail(XMHW_ERR_INVALID, "R must be >= 1");
-    if (R > xmhw::kRegionMaxRegions)
-        return fail(XMHW_ERR_UNSUPPORTED, "region_accumulate: R above the cap of " + std::to_string(xmhw::kRegionMaxRegions) + " regions");
-    if (!(x0 == x0) || std::isinf(x0)) return fail(XMHW_ERR_INVALID, "x0 must be finite");
-    if (C == 0 || Tn == 0) return XMHW_OK;
-    if (!ts || !wi || !region || !acc || !n_range) return fail(XMHW_ERR_INVALID, "NULL buffer");
-    return status_of(xmhw::launch_region_accumulate<T>(ts, Tn, C, ld, x0, wi, region, R, acc, n_range,
-                                                       g_region_wave_sum.load(), static_cast<hipStream_t>(stream)),
-                     "region_accumulate launch");
-}
-
-static std::atomic<int> g_track_intensity_combine{1};   // runs of equal entries summed in the wave (xmhw_set_track_intensity_combine)
-
-template <typename T>
-int track_intensity_accumulate(const T* ts, int64_t Tn, int64_t n, int64_t ld, const double* seas, const double* thresh,
-                               int64_t ldc, int64_t D, const int32_t* row_of_t, int32_t negate, const int32_t* start,
-                               const int32_t* end, const int32_t* slot, int64_t n_rows, const int64_t* row_offsets,
-                               const int64_t* wi, const int32_t* time_start, const int64_t* offsets, int64_t n_slots,
-                               int64_t L, int32_t* n_valid, int64_t* wsum_i, int64_t* isum_q, double* intensity_max,
-                               int32_t* cat_cells, int64_t ldcat, int64_t* n_range, int64_t* n_bad, void* stream) {
-    if (Tn <= 0 || n < 0 || ld < n || ldc < n || D < 1) return fail(XMHW_ERR_INVALID, "bad T/n/ld/ldc/D");
-    if (n_rows < 0 || n_slots < 0 || L < 0 || ldcat < L) return fail(XMHW_ERR_INVALID, "bad n_rows/n_slots/L/ldcat");
-    if (Tn > 0x7FFFFFFFll || n > 0x7FFFFFFFll || n_rows > 0x7FFFFFFFll || n_slots > 0x7FFFFFFFll || L > 0x7FFFFFFFll)
-        return fail(XMHW_ERR_UNSUPPORTED, "track_intensity: 2^31 steps, cells, rows, slots or series entries and more");
-    if (n == 0 || n_rows == 0 || n_slots == 0 || L == 0) return XMHW_OK;
-    if (!ts || !seas || !thresh || !row_of_t || !start || !end || !slot || !row_offsets || !wi || !time_start || !offsets)
-        return fail(XMHW_ERR_INVALID, "NULL buffer");
-    if (!n_valid || !wsum_i || !isum_q || !intensity_max || !cat_cells || !n_range || !n_bad)
-        return fail(XMHW_ERR_INVALID, "NULL output buffer");
-    if (int rc = check_labels(row_of_t, Tn, 0, D, kRowsOutside)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    RowsRef rows;
-    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
-    return status_of(xmhw::launch_track_intensity_accumulate<T>(ts, Tn, n, ld, seas, thresh, ldc, rows->d_rows, negate,
-                                                                start, end, slot, n_rows, row_offsets, wi, time_start,
-                                                                offsets, n_slots, L, n_valid, wsum_i, isum_q, intensity_max,
-                                                                cat_cells, ldcat, n_range, n_bad,
-                                                                g_track_intensity_combine.load(), st),
-                     "track_intensity_accumulate launch");
-}
-
-static std::atomic<int> g_class_days_block{0};   // steps a workgroup takes per block, 0 = automatic (xmhw_set_class_days_block)
-
-static int class_days_check_k(int32_t K) {
-    if (K < 1 || K > xmhw::kClassDaysMaxClasses)
-        return fail(XMHW_ERR_UNSUPPORTED, "class_days: K must be in [1, " + std::to_string(xmhw::kClassDaysMaxClasses) + "]");
-    return XMHW_OK;
-}
-
-template <typename T>
-int class_days_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* seas, const double* thresh,
-                          int64_t ldc, const int32_t* row_of_t, int32_t negate, const uint64_t* bits, int64_t ldb,
-                          int32_t min_duration, int32_t join_gaps, int32_t max_gap, const int32_t* class_of_t, int32_t K,
-                          int32_t* days, int64_t* isum_q, double* intensity_max, int64_t ldo, int64_t* n_range,
-                          void* stream) {
-    if (class_days_check_k(K) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
-    if (Tn > 0x7FFFFFFFll || C > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "class_days: 2^31 steps or cells and more");
-    if (Tn <= 0 || C < 0 || ld < C || ldc < C || ldb < C || ldo < C) return fail(XMHW_ERR_INVALID, "bad T/C/ld/ldc/ldb/ldo");
-    if (min_duration < 1 || max_gap < 0) return fail(XMHW_ERR_INVALID, "bad minDuration/maxGap");
-    if (!class_of_t) return fail(XMHW_ERR_INVALID, "NULL class_of_t");
-    if (int rc = check_labels(class_of_t, Tn, -1, K, kClassesOutside)) return rc;
-    if (C == 0) return XMHW_OK;
-    if (!ts || !seas || !thresh || !row_of_t || !bits || !days || !isum_q || !intensity_max || !n_range)
-        return fail(XMHW_ERR_INVALID, "NULL buffer");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    RowsRef rows;
-    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
-    RowsRef classes;                                   // the same content-keyed cache: one more int32[T] table
-    if (int rc = upload_table(class_of_t, Tn, "class table upload", &classes)) return rc;
-    ScratchRef scratch;
-    const uint64_t* inev = nullptr;
-    if (int rc = event_day_bitmap(bits, Tn, C, ldb, min_duration, join_gaps, max_gap, st, &scratch, &inev)) return rc;
-    return status_of(xmhw::launch_class_days_accumulate<T>(ts, Tn, C, ld, seas, thresh, ldc, rows->d_rows, classes->d_rows,
-                                                           K, negate, inev, C, g_class_days_block.load(), days, isum_q,
-                                                           intensity_max, ldo, n_range, st),
-                     "class_days_accumulate launch");
-}
-
-static std::atomic<int> g_cooccur_block{0};      // words a workgroup takes per block, 0 = automatic (xmhw_set_cooccur_block)
-
-static int cooccur_check_shape(int32_t K, int32_t L, int64_t Tn, int64_t C) {
-    if (K < 1 || K > xmhw::kCooccurMaxClasses)
-        return fail(XMHW_ERR_UNSUPPORTED, "cooccur: K must be in [1, " + std::to_string(xmhw::kCooccurMaxClasses) + "]");
-    if (L < 1 || L > xmhw::kCooccurMaxLags)
-        return fail(XMHW_ERR_UNSUPPORTED, "cooccur: L must be in [1, " + std::to_string(xmhw::kCooccurMaxLags) + "]");
-    if (Tn > 0x7FFFFFFFll || C > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "cooccur: 2^31 steps or cells and more");
-    return XMHW_OK;
-}
-
-// The class labels as the segment list of the accumulate kernel, built and uploaded once per label table (it hangs on
-// the table's entry of the content-keyed cache): seg_off[W + 1], then per segment -- a run of one non-negative class
-// inside one 64-step word -- its class and the mask of its bits.  One allocation: masks, offsets, classes.
-static hipError_t cooccur_segments(const RowsRef& classes, int64_t Tn) {
-    std::lock_guard<std::mutex> lock(g_cache_mu);
-    if (classes->d_segs) return hipSuccess;
-    const std::vector<int32_t>& k = classes->host;
-    const int64_t W = (Tn + 63) / 64;
-    std::vector<int32_t> off(static_cast<size_t>(W) + 1, 0), cls;
-    std::vector<uint64_t> mask;
-    for (int64_t w = 0; w < W; ++w) {
-        const int64_t t1 = std::min<int64_t>(Tn, w * 64 + 64);
-        for (int64_t t = w * 64; t < t1;) {
-            if (k[t] < 0) { ++t; continue; }
-            uint64_t m = 0;
-            const int32_t c = k[t];
-            for (; t < t1 && k[t] == c; ++t) m |= uint64_t{1} << (t & 63);
-            cls.push_back(c);
-            mask.push_back(m);
-        }
-        off[static_cast<size_t>(w) + 1] = static_cast<int32_t>(cls.size());
-    }
-    const size_t n = cls.size();
-    const size_t b_mask = sizeof(uint64_t) * n, b_off = sizeof(int32_t) * off.size(), b_cls = sizeof(int32_t) * n;
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, b_mask + b_off + b_cls + 8);
-    if (e != hipSuccess) return e;
-    char* base = static_cast<char*>(p);
-    if (n) e = hipMemcpy(base, mask.data(), b_mask, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(base + b_mask, off.data(), b_off, hipMemcpyHostToDevice);
-    if (e == hipSuccess && n) e = hipMemcpy(base + b_mask + b_off, cls.data(), b_cls, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(p); return e; }
-    classes->d_segs = p;
-    classes->seg_mask = reinterpret_cast<uint64_t*>(base);
-    classes->seg_off = reinterpret_cast<int32_t*>(base + b_mask);
-    classes->seg_class = reinterpret_cast<int32_t*>(base + b_mask + b_off);
-    return hipSuccess;
-}
-
-static std::atomic<int> g_displacement_block{0};  // steps a workgroup takes per block, 0 = automatic (xmhw_set_displacement_block)
-
-static int displacement_check_shape(int32_t K, int64_t C) {
-    if (K < 1 || K > xmhw::kDisplacementMaxClasses)
-        return fail(XMHW_ERR_UNSUPPORTED,
-                    "displacement: K must be in [1, " + std::to_string(xmhw::kDisplacementMaxClasses) + "]");
-    if (C > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "displacement: 2^31 cells and more");
-    return XMHW_OK;
-}
-
-template <typename T>
-int displacement_accumulate(const T* ts, int64_t ld, int64_t t0, int64_t nt, int64_t Tn, int32_t ny, int32_t nx,
-                            int32_t periodic, const double* seas, int64_t ldc, int64_t D, const int32_t* row_of_t,
-                            int32_t negate, const uint64_t* bits, int64_t ldb, const int32_t* cell_of_point, int64_t C,
-                            const int32_t* basin, const int64_t* list_off, const int32_t* djdi, const int32_t* dist_m,
-                            const int32_t* north_m, const int32_t* east_m, int64_t n_entries, const int32_t* class_of_t,
-                            int32_t K, int32_t* n_days, int32_t* n_found, int64_t* sum_m, int64_t* sum_north_m,
-                            int64_t* sum_east_m, int32_t* max_m, int64_t ldo, int64_t* n_visited, void* stream) {
-    if (displacement_check_shape(K, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
-    if (Tn > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "displacement: 2^31 steps and more");
-    if (ny > xmhw::kDisplacementMaxAxis || nx > xmhw::kDisplacementMaxAxis)
-        return fail(XMHW_ERR_UNSUPPORTED, "displacement: a grid axis of 2^15 points and more");
-    if (ny < 1 || nx < 1) return fail(XMHW_ERR_INVALID, "bad ny/nx");
-    const int64_t N = static_cast<int64_t>(ny) * nx;
-    if (Tn <= 0 || t0 < 0 || nt < 1 || nt > Tn - t0) return fail(XMHW_ERR_INVALID, "bad T/t0/nt");
-    if (C < 0 || C > N || ld < N || ldc < C || ldb < C || ldo < C || D < 1 || n_entries < 0)
-        return fail(XMHW_ERR_INVALID, "bad C/ld/ldc/ldb/ldo/D/n_entries");
-    if (!class_of_t || !row_of_t) return fail(XMHW_ERR_INVALID, "NULL class_of_t or row_of_t");
-    // the two tables are judged step by step: the one with the earlier bad label is named, class_of_t where both are bad
-    // at one step
-    const int64_t bad_class = first_outside(class_of_t, Tn, -1, K);
-    if (int rc = check_labels(row_of_t, bad_class, 0, D, kRowsOutside)) return rc;
-    if (bad_class < Tn) return fail(XMHW_ERR_INVALID, kClassesOutside);
-    if (C == 0) return XMHW_OK;
-    if (!ts || !seas || !bits || !cell_of_point || !list_off) return fail(XMHW_ERR_INVALID, "NULL buffer");
-    if (n_entries > 0 && (!djdi || !dist_m || !north_m || !east_m)) return fail(XMHW_ERR_INVALID, "NULL list buffer");
-    if (!n_days || !n_found || !sum_m || !sum_north_m || !sum_east_m || !max_m || !n_visited)
-        return fail(XMHW_ERR_INVALID, "NULL output buffer");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    RowsRef rows;
-    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
-    RowsRef classes;                                   // the same content-keyed cache: one more int32[T] table
-    if (int rc = upload_table(class_of_t, Tn, "class table upload", &classes)) return rc;
-    return status_of(xmhw::launch_displacement_accumulate<T>(ts, ld, t0, nt, ny, nx, periodic != 0, seas, ldc, rows->d_rows,
-                                                             negate != 0, bits, ldb, cell_of_point, C, basin, list_off, djdi,
-                                                             dist_m, north_m, east_m, n_entries, classes->d_rows, K,
-                                                             g_displacement_block.load(), n_days, n_found, sum_m,
-                                                             sum_north_m, sum_east_m, max_m, ldo, n_visited, st),
-                     "displacement_accumulate launch");
-}
-
-static std::atomic<int> g_heat_stress_block{0};   // steps a workgroup takes per block, 0 = automatic (xmhw_set_heat_stress_block)
-
-static int heat_stress_check_shape(const char* who, int32_t K, int64_t Tn, int64_t C) {
-    if (K < 1 || K > xmhw::kHeatStressMaxClasses)
-        return fail(XMHW_ERR_UNSUPPORTED,
-                    std::string(who) + ": K must be in [1, " + std::to_string(xmhw::kHeatStressMaxClasses) + "]");
-    if (Tn > 0x7FFFFFFFll || C > 0x7FFFFFFFll)
-        return fail(XMHW_ERR_UNSUPPORTED, std::string(who) + ": 2^31 steps or cells and more");
-    return XMHW_OK;
-}
-
-template <typename T>
-int class_sums_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, double x0, const int32_t* class_of_t, int32_t K,
-                          int32_t* n_valid, int64_t* sum_q, int64_t ldo, int64_t* n_range, void* stream) {
-    if (heat_stress_check_shape("class_sums", K, Tn, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
-    if (Tn <= 0 || C < 0 || ld < C || ldo < C) return fail(XMHW_ERR_INVALID, "bad T/C/ld/ldo");
-    if (!std::isfinite(x0)) return fail(XMHW_ERR_INVALID, "x0 must be finite");
-    if (!class_of_t) return fail(XMHW_ERR_INVALID, "NULL class_of_t");
-    if (int rc = check_labels(class_of_t, Tn, -1, K, kClassesOutside)) return rc;
-    if (C == 0) return XMHW_OK;
-    if (!ts || !n_valid || !sum_q || !n_range) return fail(XMHW_ERR_INVALID, "NULL buffer");
-    RowsRef classes;
-    if (int rc = upload_table(class_of_t, Tn, "class table upload", &classes)) return rc;
-    return status_of(xmhw::launch_class_sums_accumulate<T>(ts, Tn, C, ld, x0, classes->d_rows, K, g_heat_stress_block.load(),
-                                                           n_valid, sum_q, ldo, n_range, static_cast<hipStream_t>(stream)),
-                     "class_sums_accumulate launch");
-}
-
-template <typename T>
-int heat_stress_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* base, int64_t ldb, int64_t D,
-                           const int32_t* row_of_t, int32_t negate, int32_t W, double h0, const int32_t* class_of_t,
-                           int32_t K, const int64_t* level_q, int32_t L, const int32_t* at, int32_t J, int32_t* counts,
-                           int64_t* hsum_q, int64_t* peak_key, int32_t* snap_q, int64_t ldo, int64_t* n_range,
-                           void* stream) {
-    if (heat_stress_check_shape("heat_stress", K, Tn, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
-    if (W < 1 || W > xmhw::kHeatStressMaxWindow)
-        return fail(XMHW_ERR_UNSUPPORTED, "heat_stress: W must be in [1, " + std::to_string(xmhw::kHeatStressMaxWindow) + "]");
-    if (L > xmhw::kHeatStressMaxLevels)
-        return fail(XMHW_ERR_UNSUPPORTED, "heat_stress: at most " + std::to_string(xmhw::kHeatStressMaxLevels) + " levels");
-    if (J > xmhw::kHeatStressMaxSnapshots)
-        return fail(XMHW_ERR_UNSUPPORTED,
-                    "heat_stress: at most " + std::to_string(xmhw::kHeatStressMaxSnapshots) + " snapshot steps");
-    if (Tn <= 0 || C < 0 || ld < C || ldb < C || ldo < C || D < 1 || L < 0 || J < 0)
-        return fail(XMHW_ERR_INVALID, "bad T/C/ld/ldb/ldo/D/L/J");
-    if (!(h0 >= 1.0 / 65536.0 && h0 < 128.0)) return fail(XMHW_ERR_INVALID, "h0 outside [2^-16, 2^7)");
-    if (!class_of_t || !row_of_t || (L > 0 && !level_q) || (J > 0 && !at)) return fail(XMHW_ERR_INVALID, "NULL host table");
-    if (int rc = check_labels(class_of_t, Tn, -1, K, kClassesOutside)) return rc;
-    if (int rc = check_labels(row_of_t, Tn, 0, D, kRowsOutside)) return rc;
-    for (int32_t l = 1; l < L; ++l)
-        if (level_q[l] <= level_q[l - 1]) return fail(XMHW_ERR_INVALID, "level_q not strictly ascending");
-    for (int32_t j = 0; j < J; ++j)
-        if (at[j] < 0 || at[j] >= Tn || (j > 0 && at[j] <= at[j - 1]))
-            return fail(XMHW_ERR_INVALID, "snapshot steps not strictly ascending in [0, T)");
-    if (C == 0) return XMHW_OK;
-    if (!ts || !base || !counts || !hsum_q || !peak_key || !n_range || (J > 0 && !snap_q))
-        return fail(XMHW_ERR_INVALID, "NULL buffer");
-    RowsRef rows;
-    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
-    RowsRef classes;                                   // the same content-keyed cache: one more int32[T] table
-    if (int rc = upload_table(class_of_t, Tn, "class table upload", &classes)) return rc;
-    RowsRef steps;                                     // ... and the snapshot steps, int32[J]
-    if (J > 0)
-        if (int rc = upload_table(at, J, "snapshot table upload", &steps)) return rc;
-    return status_of(xmhw::launch_heat_stress_accumulate<T>(ts, Tn, C, ld, base, ldb, D, rows->d_rows, negate, W, h0,
-                                                            classes->d_rows, K, level_q, L, J > 0 ? steps->d_rows : nullptr, J,
-                                                            g_heat_stress_block.load(), counts, hsum_q, peak_key, snap_q, ldo,
-                                                            n_range, static_cast<hipStream_t>(stream)),
-                     "heat_stress_accumulate launch");
-}
-
-static std::atomic<int> g_index_regress_block{0};   // steps a workgroup takes per block, 0 = automatic (xmhw_set_index_regress_block)
-
-static int index_regress_check_shape(int32_t K, int32_t J, int64_t Tn, int64_t C) {
-    if (K < 1 || K > xmhw::kIndexRegressMaxClasses)
-        return fail(XMHW_ERR_UNSUPPORTED,
-                    "index_regress: K must be in [1, " + std::to_string(xmhw::kIndexRegressMaxClasses) + "]");
-    if (J < 1 || J > xmhw::kIndexRegressMaxPredictors)
-        return fail(XMHW_ERR_UNSUPPORTED,
-                    "index_regress: J must be in [1, " + std::to_string(xmhw::kIndexRegressMaxPredictors) + "]");
-    if (Tn >= xmhw::kIndexRegressMaxSteps) return fail(XMHW_ERR_UNSUPPORTED, "index_regress: 2^17 steps and more");
-    if (C > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "index_regress: 2^31 cells and more");
-    return XMHW_OK;
-}
-
-template <typename T>
-int index_regress_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* base, int64_t ldb, int64_t D,
-                             const int32_t* row_of_t, const int32_t* class_of_t, int32_t K, const int32_t* zq, int32_t J,
-                             int32_t* n, int64_t* sa, int64_t* saa, int32_t* n1, int64_t* saa1, int64_t* saz, int64_t* mz,
-                             int64_t* mzz, int64_t ldo, int64_t* n_range, void* stream) {
-    if (index_regress_check_shape(K, J, Tn, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
-    if (Tn <= 0 || C < 0 || ld < C || ldb < C || ldo < C || D < 1) return fail(XMHW_ERR_INVALID, "bad T/C/ld/ldb/ldo/D");
-    if (!class_of_t || !row_of_t || !zq) return fail(XMHW_ERR_INVALID, "NULL host table");
-    if (int rc = check_labels(class_of_t, Tn, -1, K, kClassesOutside)) return rc;
-    if (int rc = check_labels(row_of_t, Tn, 0, D, kRowsOutside)) return rc;
-    constexpr int32_t zlim = 1 << xmhw::kIndexRegressPredictorBits;
-    if (int rc = check_labels(zq, Tn * J, -zlim + 1, zlim, "zq outside (-2^23, 2^23)")) return rc;
-    if (C == 0) return XMHW_OK;
-    if (!ts || !base || !n || !sa || !saa || !n1 || !saa1 || !saz || !mz || !mzz || !n_range)
-        return fail(XMHW_ERR_INVALID, "NULL buffer");
-    RowsRef rows;
-    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
-    RowsRef classes;                                   // the same content-keyed cache: one more int32[T] table
-    if (int rc = upload_table(class_of_t, Tn, "class table upload", &classes)) return rc;
-    // ... and the predictors, step-major, J padded with zero columns to the kernel's group: int32[T][G]
-    const int G = xmhw::index_regress_group(J);
-    std::vector<int32_t> padded(static_cast<size_t>(Tn) * G, 0);
-    for (int64_t t = 0; t < Tn; ++t) std::copy(zq + t * J, zq + (t + 1) * J, padded.begin() + t * G);
-    RowsRef predictors;
-    if (int rc = upload_table(padded.data(), Tn * G, "predictor table upload", &predictors)) return rc;
-    return status_of(xmhw::launch_index_regress_accumulate<T>(ts, Tn, C, ld, base, ldb, D, rows->d_rows, classes->d_rows, K,
-                                                              predictors->d_rows, J, g_index_regress_block.load(), n, sa, saa,
-                                                              n1, saa1, saz, mz, mzz, ldo, n_range,
-                                                              static_cast<hipStream_t>(stream)),
-                     "index_regress_accumulate launch");
-}
-
-static std::atomic<int> g_composite_block{0};   // steps a workgroup takes per block, 0 = automatic (xmhw_set_composite_block)
-
-static int composite_check_shape(int32_t K, int64_t D, int32_t shift, int64_t Tn, int64_t C) {
-    if (K < 1 || K > xmhw::kCompositeMaxClasses)
-        return fail(XMHW_ERR_UNSUPPORTED, "composite: K must be in [1, " + std::to_string(xmhw::kCompositeMaxClasses) + "]");
-    if (D < 1 || D > xmhw::kCompositeMaxOffsets)
-        return fail(XMHW_ERR_UNSUPPORTED,
-                    "composite: before + after + 1 must be in [1, " + std::to_string(xmhw::kCompositeMaxOffsets) + "]");
-    if (shift < 0 || shift > xmhw::kCompositeMaxShift)
-        return fail(XMHW_ERR_UNSUPPORTED, "composite: shift must be in [0, " + std::to_string(xmhw::kCompositeMaxShift) + "]");
-    if (Tn >= xmhw::kCompositeMaxSteps) return fail(XMHW_ERR_UNSUPPORTED, "composite: 2^17 steps and more");
-    if (C > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "composite: 2^31 cells and more");
-    return XMHW_OK;
-}
-
-template <typename T>
-int composite_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* base, int64_t ldb, int64_t Dr,
-                         const int32_t* row_of_t, int32_t shift, const uint64_t* anchor_bits, int64_t lda,
-                         const int32_t* class_of_t, int32_t K, int32_t before, int32_t after, int32_t* n, int64_t* s,
-                         int64_t* ss, int64_t ldo, int64_t* n_range, void* stream) {
-    if (before < 0 || after < 0) return fail(XMHW_ERR_UNSUPPORTED, "composite: before and after must be >= 0");
-    if (composite_check_shape(K, static_cast<int64_t>(before) + after + 1, shift, Tn, C) != XMHW_OK)
-        return XMHW_ERR_UNSUPPORTED;
-    if (Tn < 0 || C < 0 || ld < C || ldb < C || lda < C || ldo < C || Dr < 1)
-        return fail(XMHW_ERR_INVALID, "bad T/C/ld/ldb/lda/ldo/D");
-    if (Tn > 0 && (!class_of_t || !row_of_t)) return fail(XMHW_ERR_INVALID, "NULL host table");
-    if (int rc = check_labels(class_of_t, Tn, -1, K, kClassesOutside)) return rc;
-    if (int rc = check_labels(row_of_t, Tn, 0, Dr, kRowsOutside)) return rc;
-    if (C == 0 || Tn == 0) return XMHW_OK;
-    if (!ts || !base || !anchor_bits || !n || !s || !ss || !n_range) return fail(XMHW_ERR_INVALID, "NULL buffer");
-    RowsRef rows;
-    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
-    RowsRef classes;                                   // the same content-keyed cache: one more int32[T] table
-    if (int rc = upload_table(class_of_t, Tn, "class table upload", &classes)) return rc;
-    return status_of(xmhw::launch_composite_accumulate<T>(ts, Tn, C, ld, base, ldb, Dr, rows->d_rows, shift, anchor_bits, lda,
-                                                          classes->d_rows, K, before, after, g_composite_block.load(), n, s,
-                                                          ss, ldo, n_range, static_cast<hipStream_t>(stream)),
-                     "composite_accumulate launch");
-}
-
-static std::atomic<int> g_lag_corr_block{0};    // steps a workgroup takes per block, 0 = automatic (xmhw_set_lag_corr_block)
-
-static int lag_corr_check_shape(int32_t K, int32_t L, int32_t shift_x, int32_t shift_y, int64_t Tn, int64_t C) {
-    if (K < 1 || K > xmhw::kLagCorrMaxClasses)
-        return fail(XMHW_ERR_UNSUPPORTED, "lag_corr: K must be in [1, " + std::to_string(xmhw::kLagCorrMaxClasses) + "]");
-    if (L < 0 || L > xmhw::kLagCorrMaxLag)
-        return fail(XMHW_ERR_UNSUPPORTED, "lag_corr: max_lag must be in [0, " + std::to_string(xmhw::kLagCorrMaxLag) + "]");
-    if (shift_x < 0 || shift_x > xmhw::kLagCorrMaxShift || shift_y < 0 || shift_y > xmhw::kLagCorrMaxShift)
-        return fail(XMHW_ERR_UNSUPPORTED, "lag_corr: shifts must be in [0, " + std::to_string(xmhw::kLagCorrMaxShift) + "]");
-    if (Tn >= xmhw::kLagCorrMaxSteps) return fail(XMHW_ERR_UNSUPPORTED, "lag_corr: 2^17 steps and more");
-    if (C > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "lag_corr: 2^31 cells and more");
-    return XMHW_OK;
-}
-
-template <typename T>
-int lag_corr_accumulate(const T* x, int64_t ldx, const T* y, int64_t ldy, int64_t Tn, int64_t C, const double* base_x,
-                        int64_t ldbx, const double* base_y, int64_t ldby, int64_t Dr, const int32_t* row_of_t, int32_t shift_x,
-                        int32_t shift_y, const int32_t* class_of_t, int32_t K, int32_t max_lag, int32_t* n, int64_t* sx,
-                        int64_t* sy, int64_t* sxx, int64_t* syy, int64_t* sxy, int64_t ldo, int64_t* n_range, void* stream) {
-    if (lag_corr_check_shape(K, max_lag, shift_x, shift_y, Tn, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
-    if (Tn < 0 || C < 0 || ldx < C || ldy < C || ldbx < C || ldby < C || ldo < C || Dr < 1)
-        return fail(XMHW_ERR_INVALID, "bad T/C/ldx/ldy/ldbx/ldby/ldo/D");
-    if (Tn > 0 && (!class_of_t || !row_of_t)) return fail(XMHW_ERR_INVALID, "NULL host table");
-    if (int rc = check_labels(class_of_t, Tn, -1, K, kClassesOutside)) return rc;
-    if (int rc = check_labels(row_of_t, Tn, 0, Dr, kRowsOutside)) return rc;
-    if (C == 0 || Tn == 0) return XMHW_OK;
-    if (!x || !y || !base_x || !base_y || !n || !sx || !sy || !sxx || !syy || !sxy || !n_range)
-        return fail(XMHW_ERR_INVALID, "NULL buffer");
-    RowsRef rows;
-    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
-    RowsRef classes;                                   // the same content-keyed cache: one more int32[T] table
-    if (int rc = upload_table(class_of_t, Tn, "class table upload", &classes)) return rc;
-    return status_of(xmhw::launch_lag_corr_accumulate<T>(x, ldx, y, ldy, Tn, C, base_x, ldbx, base_y, ldby, Dr, rows->d_rows,
-                                                         shift_x, shift_y, classes->d_rows, K, max_lag,
-                                                         g_lag_corr_block.load(), n, sx, sy, sxx, syy, sxy, ldo, n_range,
-                                                         static_cast<hipStream_t>(stream)),
-                     "lag_corr_accumulate launch");
-}
-
-static std::atomic<int> g_spatial_corr_block{0};   // steps a workgroup takes per block, 0 = automatic (xmhw_set_spatial_corr_block)
-static std::atomic<int> g_spatial_corr_tile{0};    // grid rows of a tile, 0 = the default (xmhw_set_spatial_corr_tile)
-
-static_assert(XMHW_SPATIAL_CORR_MAX_OFFSETS == xmhw::kSpatialCorrMaxOffsets && XMHW_SPATIAL_CORR_REACH == xmhw::kSpatialCorrReach &&
-                  XMHW_SPATIAL_CORR_MAX_CLASSES == xmhw::kSpatialCorrMaxClasses &&
-                  XMHW_SPATIAL_CORR_MAX_STEPS == xmhw::kSpatialCorrMaxSteps &&
-                  XMHW_SPATIAL_CORR_MAX_AXIS == xmhw::kSpatialCorrMaxAxis && XMHW_SPATIAL_CORR_BITS == xmhw::kSpatialCorrBits &&
-                  XMHW_SPATIAL_CORR_RANGE_BITS == xmhw::kSpatialCorrRangeBits &&
-                  XMHW_SPATIAL_CORR_MAX_SHIFT == xmhw::kSpatialCorrMaxShift,
-              "the public limits of spatial_correlation() are the kernel's");
-
-static int spatial_corr_check_shape(int32_t K, int32_t D, int32_t shift, int64_t Tn, int32_t ny, int32_t nx) {
-    if (K < 1 || K > xmhw::kSpatialCorrMaxClasses)
-        return fail(XMHW_ERR_UNSUPPORTED,
-                    "spatial_corr: K must be in [1, " + std::to_string(xmhw::kSpatialCorrMaxClasses) + "]");
-    if (D < 1 || D > xmhw::kSpatialCorrMaxOffsets)
-        return fail(XMHW_ERR_UNSUPPORTED,
-                    "spatial_corr: D must be in [1, " + std::to_string(xmhw::kSpatialCorrMaxOffsets) + "]");
-    if (shift < 0 || shift > xmhw::kSpatialCorrMaxShift)
-        return fail(XMHW_ERR_UNSUPPORTED,
-                    "spatial_corr: shift must be in [0, " + std::to_string(xmhw::kSpatialCorrMaxShift) + "]");
-    if (Tn >= xmhw::kSpatialCorrMaxSteps) return fail(XMHW_ERR_UNSUPPORTED, "spatial_corr: 2^17 steps and more");
-    if (ny > xmhw::kSpatialCorrMaxAxis || nx > xmhw::kSpatialCorrMaxAxis)
-        return fail(XMHW_ERR_UNSUPPORTED, "spatial_corr: a grid axis of 2^15 points and more");
-    return XMHW_OK;
-}
-
-template <typename T>
-int spatial_corr_accumulate(const T* ts, int64_t ld, int64_t t0, int64_t nt, int64_t Tn, int32_t ny, int32_t nx,
-                            int32_t periodic, const double* base, int64_t ldb, int64_t Dr, const int32_t* row_of_t,
-                            int32_t shift, const int32_t* class_of_t, int32_t K, const int32_t* offsets, int32_t D, int32_t* n,
-                            int64_t* sx, int64_t* sy, int64_t* sxx, int64_t* syy, int64_t* sxy, int64_t ldo, int64_t* n_range,
-                            void* stream) {
-    if (spatial_corr_check_shape(K, D, shift, Tn, ny, nx) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
-    if (offsets)
-        for (int32_t e = 0; e < 2 * D; ++e)
-            if (offsets[e] < -xmhw::kSpatialCorrReach || offsets[e] > xmhw::kSpatialCorrReach)
-                return fail(XMHW_ERR_UNSUPPORTED,
-                            "spatial_corr: offsets reach at most " + std::to_string(xmhw::kSpatialCorrReach) + " points");
-    if (ny < 0 || nx < 0) return fail(XMHW_ERR_INVALID, "bad ny/nx");
-    const int64_t N = static_cast<int64_t>(ny) * nx;
-    if (Tn < 0 || t0 < 0 || nt < 0 || nt > Tn - t0) return fail(XMHW_ERR_INVALID, "bad T/t0/nt");
-    if (ld < N || ldb < N || ldo < N || Dr < 1) return fail(XMHW_ERR_INVALID, "bad ld/ldb/ldo/Dr");
-    if (!offsets || (Tn > 0 && (!class_of_t || !row_of_t))) return fail(XMHW_ERR_INVALID, "NULL host table");
-    if (periodic)
-        for (int32_t e = 0; e < D; ++e)
-            if (nx > 0 && std::abs(offsets[2 * e + 1]) >= nx)
-                return fail(XMHW_ERR_INVALID, "spatial_corr: |di| must be below nx on a periodic grid");
-    if (int rc = check_labels(class_of_t, Tn, -1, K, kClassesOutside)) return rc;
-    if (int rc = check_labels(row_of_t, Tn, 0, Dr, kRowsOutside)) return rc;
-    if (nt == 0 || N == 0) return XMHW_OK;
-    if (!ts || !base || !n || !sx || !sy || !sxx || !syy || !sxy || !n_range) return fail(XMHW_ERR_INVALID, "NULL buffer");
-    RowsRef rows;
-    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
-    RowsRef classes;                                   // the same content-keyed cache: one more int32[T] table
-    if (int rc = upload_table(class_of_t, Tn, "class table upload", &classes)) return rc;
-    // ... and the offsets, padded with (0, 0) to whole groups: int32[groups * G][2]
-    const int64_t padded_n = xmhw::spatial_corr_groups(D) * xmhw::spatial_corr_group(D);
-    std::vector<int32_t> padded(static_cast<size_t>(2 * padded_n), 0);
-    std::copy(offsets, offsets + 2 * D, padded.begin());
-    RowsRef table;
-    if (int rc = upload_table(padded.data(), 2 * padded_n, "offset table upload", &table)) return rc;
-    const int32_t tile = g_spatial_corr_tile.load();
-    return status_of(xmhw::launch_spatial_corr_accumulate<T>(ts, ld, t0, nt, ny, nx, periodic != 0, base, ldb, Dr, rows->d_rows,
-                                                             shift, classes->d_rows, K, table->d_rows, padded.data(), D,
-                                                             tile ? tile : xmhw::kSpatialCorrRows, g_spatial_corr_block.load(),
-                                                             n, sx, sy, sxx, syy, sxy, ldo, n_range,
-                                                             static_cast<hipStream_t>(stream)),
-                     "spatial_corr_accumulate launch");
-}
-
-static std::atomic<int> g_coarsen_variant{0};      // which loads coarsen() may use, 0 = the widest (xmhw_set_coarsen_variant)
-static std::atomic<int> g_coarsen_chunk{0};        // windows a workgroup takes per chunk, 0 = automatic (xmhw_set_coarsen_chunk)
-
-static_assert(XMHW_COARSEN_MAX_VOLUME == xmhw::kCoarsenMaxVolume && XMHW_COARSEN_MAX_WEIGHT_BITS == xmhw::kCoarsenMaxWeightBits &&
-                  XMHW_REGION_SERIES_BITS == xmhw::kCoarsenBits,
-              "the public limits of coarsen() are the kernel's");
-
-template <typename T>
-int coarsen(const T* ts, int64_t nt, int64_t ld, int32_t ny, int32_t nx, int32_t fy, int32_t fx, int32_t ncy, int32_t ncx,
-            const int32_t* wi, double x0, int32_t a, const int32_t* win, int32_t ns, T* out, int64_t ldo, int64_t* wsum,
-            int32_t* n, int64_t* n_range, void* stream) {
-    // the caps: the volume of the largest block x window, over the windows of positive length of a table that is there
-    int64_t max_len = 1;
-    if (win)
-        for (int32_t s = 0; s < ns; ++s) max_len = std::max<int64_t>(max_len, static_cast<int64_t>(win[s + 1]) - win[s]);
-    if (fy >= 1 && fx >= 1 && static_cast<int64_t>(fy) * fx * max_len > xmhw::kCoarsenMaxVolume)
-        return fail(XMHW_ERR_UNSUPPORTED, "coarsen: fy * fx * the longest window is above the cap of " +
-                                              std::to_string(xmhw::kCoarsenMaxVolume) + " samples");
-    if (ny > 0 && nx > 0 && static_cast<int64_t>(ny) * nx > INT32_MAX)
-        return fail(XMHW_ERR_UNSUPPORTED, "coarsen: a grid of 2^31 points and more");
-    if (nt < 0 || ny < 0 || nx < 0 || ld < static_cast<int64_t>(ny) * nx) return fail(XMHW_ERR_INVALID, "bad nt/ny/nx/ld");
-    if (fy < 1 || fx < 1) return fail(XMHW_ERR_INVALID, "coarsen: the factors must be >= 1");
-    if (!xmhw::coarsen_grid_ok(ny, nx, fy, fx, ncy, ncx))
-        return fail(XMHW_ERR_INVALID, "coarsen: ncy, ncx must lie in [0, ceil(ny / fy)], [0, ceil(nx / fx)]");
-    if (ldo < static_cast<int64_t>(ncy) * ncx) return fail(XMHW_ERR_INVALID, "bad ldo");
-    if (ns < 0 || (ns > 0 && !win)) return fail(XMHW_ERR_INVALID, "bad ns / NULL window table");
-    if (ns > 0 && (win[0] < 0 || win[ns] > nt)) return fail(XMHW_ERR_INVALID, "coarsen: the windows leave [0, nt]");
-    for (int32_t s = 0; s < ns; ++s)
-        if (win[s + 1] <= win[s]) return fail(XMHW_ERR_INVALID, "coarsen: the window table must be strictly increasing");
-    if (a < 0 || a > 65536) return fail(XMHW_ERR_INVALID, "coarsen: a must be in [0, 65536]");
-    if (!std::isfinite(x0)) return fail(XMHW_ERR_INVALID, "coarsen: x0 must be finite");
-    if (ns == 0 || ncy == 0 || ncx == 0) return XMHW_OK;
-    if (!ts || !wi || !out || !n_range) return fail(XMHW_ERR_INVALID, "NULL buffer");
-    RowsRef table;
-    if (int rc = upload_table(win, static_cast<int64_t>(ns) + 1, "window table upload", &table)) return rc;
-    return status_of(xmhw::launch_coarsen<T>(ts, ld, ny, nx, fy, fx, ncy, ncx, wi, x0, a, table->d_rows, ns,
-                                             static_cast<int32_t>(max_len), g_coarsen_variant.load(), g_coarsen_chunk.load(),
-                                             out, ldo, wsum, n, n_range, static_cast<hipStream_t>(stream)),
-                     "coarsen launch");
-}
-
-static std::atomic<int> g_regrid_variant{0};       // the path regrid() takes, 0 = automatic (xmhw_set_regrid_variant)
-static std::atomic<int> g_regrid_chunk{0};         // steps a workgroup takes per chunk, 0 = automatic (xmhw_set_regrid_chunk)
-
-static_assert(XMHW_REGRID_MAX_RUN == xmhw::kRegridMaxRun && XMHW_REGRID_MAX_WEIGHT == xmhw::kRegridMaxWeight &&
-                  XMHW_REGRID_MAX_EXTENT == xmhw::kRegridMaxExtent && XMHW_REGION_SERIES_BITS == xmhw::kRegridBits,
-              "the public limits of regrid() are the kernel's");
-
-// one axis of a regrid() call: m destination runs over n source points
-struct RegridAxis {
-    const int32_t *first, *ptr, *w, *full;
-    int32_t m, n;
-    bool periodic;
-    const char* name;
-};
-// can the tables be read as CSR tables: all there, the pointers from 0 and non-decreasing?
-bool regrid_axis_readable(const RegridAxis& x) {
-    if (x.m < 0) return false;
-    if (x.m == 0) return true;
-    if (!x.first || !x.ptr || !x.full || x.ptr[0] != 0) return false;
-    for (int32_t k = 0; k < x.m; ++k)
-        if (x.ptr[k + 1] < x.ptr[k]) return false;
-    return x.ptr[x.m] == 0 || x.w;
-}
-// the caps of an axis (of tables that can be read): "" or what is above them
-std::string regrid_axis_cap(const RegridAxis& x) {
-    if (!regrid_axis_readable(x)) return "";
-    for (int32_t k = 0; k < x.m; ++k) {
-        if (x.ptr[k + 1] - x.ptr[k] > xmhw::kRegridMaxRun)
-            return std::string("regrid: a ") + x.name + " run of more than " + std::to_string(xmhw::kRegridMaxRun) + " entries";
-        if (x.full[k] > xmhw::kRegridMaxExtent) return std::string("regrid: a ") + x.name + " extent above 2^18";
-    }
-    for (int32_t e = 0; e < x.ptr[x.m]; ++e)
-        if (x.w[e] > xmhw::kRegridMaxWeight) return std::string("regrid: a ") + x.name + " weight above 2^12";
-    return "";
-}
-// the shape of an axis: "" or what is malformed
-std::string regrid_axis_bad(const RegridAxis& x) {
-    if (!regrid_axis_readable(x)) return std::string("regrid: bad ") + x.name + " tables (NULL, or pointers not from 0 and non-decreasing)";
-    for (int32_t k = 0; k < x.m; ++k) {
-        const int64_t cnt = x.ptr[k + 1] - x.ptr[k];
-        int64_t sum = 0;
-        for (int32_t e = x.ptr[k]; e < x.ptr[k + 1]; ++e) {
-            if (x.w[e] < 0) return std::string("regrid: a negative ") + x.name + " weight";
-            sum += x.w[e];
-        }
-        if (sum > x.full[k]) return std::string("regrid: the ") + x.name + " weights of a run exceed its extent";
-        const int64_t first = x.first[k];
-        const bool inside = x.periodic ? first >= 0 && first < x.n && cnt <= x.n : first >= 0 && first + cnt <= x.n;
-        if (cnt > 0 && !inside) return std::string("regrid: a ") + x.name + " run leaves the source grid";
-    }
-    return "";
-}
-
-template <typename T>
-int regrid(const T* ts, int64_t nt, int64_t ld, int32_t ny, int32_t nx, int32_t my, int32_t mx, const int32_t* row_first,
-           const int32_t* row_ptr, const int32_t* ay, const int32_t* wy, const int32_t* col_first, const int32_t* col_ptr,
-           const int32_t* ax, const int32_t* wx, int32_t periodic, double x0, int32_t a, T* out, int64_t ldo, int64_t* wsum,
-           int32_t* n, int64_t* n_range, void* stream) {
-    const RegridAxis rows{row_first, row_ptr, ay, wy, my, ny, false, "row"};
-    const RegridAxis cols{col_first, col_ptr, ax, wx, mx, nx, periodic != 0, "column"};
-    // the caps, over the tables that can be read
-    for (const RegridAxis* x : {&rows, &cols}) {
-        const std::string cap = regrid_axis_cap(*x);
-        if (!cap.empty()) return fail(XMHW_ERR_UNSUPPORTED, cap);
-    }
-    if ((ny > 0 && nx > 0 && static_cast<int64_t>(ny) * nx > INT32_MAX) || (my > 0 && mx > 0 && static_cast<int64_t>(my) * mx > INT32_MAX))
-        return fail(XMHW_ERR_UNSUPPORTED, "regrid: a grid of 2^31 points and more");
-    if (nt < 0 || ny < 0 || nx < 0 || ld < static_cast<int64_t>(ny) * nx) return fail(XMHW_ERR_INVALID, "bad nt/ny/nx/ld");
-    if (my < 0 || mx < 0 || ldo < static_cast<int64_t>(my) * mx) return fail(XMHW_ERR_INVALID, "bad my/mx/ldo");
-    for (const RegridAxis* x : {&rows, &cols}) {
-        const std::string bad = regrid_axis_bad(*x);
-        if (!bad.empty()) return fail(XMHW_ERR_INVALID, bad);
-    }
-    if (a < 0 || a > 65536) return fail(XMHW_ERR_INVALID, "regrid: a must be in [0, 65536]");
-    if (!std::isfinite(x0)) return fail(XMHW_ERR_INVALID, "regrid: x0 must be finite");
-    if (nt == 0 || my == 0 || mx == 0) return XMHW_OK;
-    if (!ts || !out || !n_range) return fail(XMHW_ERR_INVALID, "NULL buffer");
-    // the ten tables as one: one upload, one cache slot, reused by the time blocks of a call
-    const xmhw::RegridLayout lay = xmhw::regrid_layout(my, mx, row_ptr[my], col_ptr[mx]);
-    std::vector<int32_t> packed(static_cast<size_t>(lay.total), 0);
-    const auto put = [&](int64_t at, const int32_t* src, int64_t count) {
-        if (count > 0) std::memcpy(packed.data() + at, src, sizeof(int32_t) * static_cast<size_t>(count));
-    };
-    put(lay.row_first, row_first, my);
-    put(lay.row_ptr, row_ptr, static_cast<int64_t>(my) + 1);
-    put(lay.ay, ay, row_ptr[my]);
-    put(lay.wy, wy, my);
-    put(lay.col_first, col_first, mx);
-    put(lay.col_ptr, col_ptr, static_cast<int64_t>(mx) + 1);
-    put(lay.ax, ax, col_ptr[mx]);
-    put(lay.wx, wx, mx);
-    int32_t max_width = 0;
-    for (int32_t I0 = 0; I0 < mx; I0 += xmhw::kRegridTile) {
-        const xmhw::RegridSpan sp = xmhw::regrid_tile_span(col_first, col_ptr, mx, nx, periodic != 0, I0);
-        packed[static_cast<size_t>(lay.tile_c0 + I0 / xmhw::kRegridTile)] = sp.c0;
-        packed[static_cast<size_t>(lay.tile_w + I0 / xmhw::kRegridTile)] = sp.width;
-        max_width = std::max(max_width, sp.width);
-    }
-    RowsRef table;
-    if (int rc = upload_table(packed.data(), lay.total, "overlap table upload", &table)) return rc;
-    return status_of(xmhw::launch_regrid<T>(ts, nt, ld, ny, nx, my, mx, table->d_rows, lay, xmhw::regrid_max_run(row_ptr, my),
-                                            xmhw::regrid_max_run(col_ptr, mx), max_width, periodic != 0, x0, a,
-                                            g_regrid_variant.load(), g_regrid_chunk.load(), out, ldo, wsum, n, n_range,
-                                            static_cast<hipStream_t>(stream)),
-                     "regrid launch");
-}
-
-static std::atomic<int> g_distribution_block{0};    // steps a workgroup takes per block, 0 = automatic (xmhw_set_distribution_block)
-
-static_assert(XMHW_DISTRIBUTION_MAX_BINS == xmhw::kDistributionMaxBins &&
-                  XMHW_DISTRIBUTION_MAX_CLASSES == xmhw::kDistributionMaxClasses &&
-                  XMHW_DISTRIBUTION_MAX_QUANTILES == xmhw::kDistributionMaxQuantiles &&
-                  XMHW_DISTRIBUTION_MAX_LEVELS == xmhw::kDistributionMaxLevels &&
-                  XMHW_DISTRIBUTION_MAX_STEPS == xmhw::kDistributionMaxSteps &&
-                  XMHW_DISTRIBUTION_BITS == xmhw::kDistributionBits &&
-                  XMHW_DISTRIBUTION_RANGE_BITS == xmhw::kDistributionRangeBits &&
-                  XMHW_DISTRIBUTION_MAX_SHIFT == xmhw::kDistributionMaxShift,
-              "the public limits of anomaly_distribution() are the kernel's");
-
-static int distribution_check_shape(int32_t K, int32_t B, int64_t Tn, int64_t C) {
-    if (K < 1 || K > xmhw::kDistributionMaxClasses)
-        return fail(XMHW_ERR_UNSUPPORTED,
-                    "distribution: K must be in [1, " + std::to_string(xmhw::kDistributionMaxClasses) + "]");
-    if (B < 1 || B > xmhw::kDistributionMaxBins)
-        return fail(XMHW_ERR_UNSUPPORTED, "distribution: B must be in [1, " + std::to_string(xmhw::kDistributionMaxBins) + "]");
-    if (Tn >= xmhw::kDistributionMaxSteps) return fail(XMHW_ERR_UNSUPPORTED, "distribution: 2^17 steps and more");
-    if (C > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "distribution: 2^31 cells and more");
-    return XMHW_OK;
-}
-
-template <typename T>
-int distribution_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* base, int64_t ldb, int64_t Dr,
-                            const int32_t* row_of_t, int32_t shift, const int32_t* class_of_t, int32_t K, int64_t lo_q,
-                            int32_t width_q, int32_t B, int32_t* hist, int32_t* n, int64_t* s1, int64_t* s2, int64_t* s3,
-                            int64_t* s4, uint64_t* kmin, uint64_t* kmax, int64_t ldo, int64_t* n_range, void* stream) {
-    if (distribution_check_shape(K, B, Tn, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
-    if (width_q < 1) return fail(XMHW_ERR_UNSUPPORTED, "distribution: width_q must be >= 1");
-    if (lo_q < -(int64_t{1} << 23) || lo_q > (int64_t{1} << 23))
-        return fail(XMHW_ERR_UNSUPPORTED, "distribution: lo_q must be in [-2^23, 2^23]");
-    if (shift < 0 || shift > xmhw::kDistributionMaxShift)
-        return fail(XMHW_ERR_UNSUPPORTED,
-                    "distribution: shift must be in [0, " + std::to_string(xmhw::kDistributionMaxShift) + "]");
-    if (Tn < 0 || C < 0 || ld < C || ldb < C || ldo < C || Dr < 1) return fail(XMHW_ERR_INVALID, "bad T/C/ld/ldb/ldo/D");
-    if (Tn > 0 && (!class_of_t || !row_of_t)) return fail(XMHW_ERR_INVALID, "NULL host table");
-    if (int rc = check_labels(class_of_t, Tn, -1, K, kClassesOutside)) return rc;
-    if (int rc = check_labels(row_of_t, Tn, 0, Dr, kRowsOutside)) return rc;
-    if (C == 0 || Tn == 0) return XMHW_OK;
-    if (!ts || !base || !hist || !n || !s1 || !s2 || !s3 || !s4 || !kmin || !kmax || !n_range)
-        return fail(XMHW_ERR_INVALID, "NULL buffer");
-    RowsRef rows;
-    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
-    RowsRef classes;                                   // the same content-keyed cache: one more int32[T] table
-    if (int rc = upload_table(class_of_t, Tn, "class table upload", &classes)) return rc;
-    return status_of(xmhw::launch_distribution_accumulate<T>(ts, Tn, C, ld, base, ldb, Dr, rows->d_rows, shift, classes->d_rows,
-                                                             K, lo_q, width_q, B, g_distribution_block.load(), hist, n, s1,
-                                                             s2, s3, s4, kmin, kmax, ldo, n_range,
-                                                             static_cast<hipStream_t>(stream)),
-                     "distribution_accumulate launch");
 }
 
 template <typename T>
@@ -2292,37 +1643,6 @@ int xmhw_series_remove_f64(double* ts, int64_t T, int64_t C, int64_t ld, const d
     return series_remove<double>(ts, T, C, ld, basis, P, R, coef, ldc, stream);
 }
 
-int xmhw_coverage_accumulate_f32(const float* ts, int64_t T, int64_t C, int64_t ld, const double* seas,
-                                 const double* thresh, int64_t ldc, const int32_t* row_of_t, int32_t negate,
-                                 const uint64_t* bits, int64_t ldb, int32_t min_duration, int32_t join_gaps,
-                                 int32_t max_gap, const int64_t* wq, const int32_t* region, int32_t R, int64_t* cells,
-                                 int64_t* area_q, void* stream) {
-    return coverage_accumulate<float>(ts, T, C, ld, seas, thresh, ldc, row_of_t, negate, bits, ldb, min_duration,
-                                      join_gaps, max_gap, wq, region, R, cells, area_q, stream);
-}
-int xmhw_coverage_accumulate_f64(const double* ts, int64_t T, int64_t C, int64_t ld, const double* seas,
-                                 const double* thresh, int64_t ldc, const int32_t* row_of_t, int32_t negate,
-                                 const uint64_t* bits, int64_t ldb, int32_t min_duration, int32_t join_gaps,
-                                 int32_t max_gap, const int64_t* wq, const int32_t* region, int32_t R, int64_t* cells,
-                                 int64_t* area_q, void* stream) {
-    return coverage_accumulate<double>(ts, T, C, ld, seas, thresh, ldc, row_of_t, negate, bits, ldb, min_duration,
-                                       join_gaps, max_gap, wq, region, R, cells, area_q, stream);
-}
-
-int xmhw_set_region_wave_sum(int32_t variant) {
-    if (variant != 0 && variant != 1) return fail(XMHW_ERR_INVALID, "variant must be 0 or 1");
-    g_region_wave_sum = variant;
-    return XMHW_OK;
-}
-int xmhw_region_accumulate_f32(const float* ts, int64_t T, int64_t C, int64_t ld, double x0, const int64_t* wi,
-                               const int32_t* region, int32_t R, int64_t* acc, int64_t* n_range, void* stream) {
-    return region_accumulate<float>(ts, T, C, ld, x0, wi, region, R, acc, n_range, stream);
-}
-int xmhw_region_accumulate_f64(const double* ts, int64_t T, int64_t C, int64_t ld, double x0, const int64_t* wi,
-                               const int32_t* region, int32_t R, int64_t* acc, int64_t* n_range, void* stream) {
-    return region_accumulate<double>(ts, T, C, ld, x0, wi, region, R, acc, n_range, stream);
-}
-
 int xmhw_event_objects(const int32_t* start, const int32_t* end, int64_t n, const int64_t* offsets, int64_t C,
                        const int32_t* nbr, int32_t K, int32_t gap, int32_t* cell_of_row, int32_t* root, void* stream) {
     if (n < 0 || C < 0) return fail(XMHW_ERR_INVALID, "bad n/C");
@@ -2449,484 +1769,6 @@ int xmhw_object_shape(const int32_t* start, const int32_t* end, const int32_t* s
                                                offsets, n_slots, L, edges, perimeter_q, cells_edge, n_bad,
                                                static_cast<hipStream_t>(stream)),
                      "object_shape launch");
-}
-
-int xmhw_set_track_intensity_combine(int32_t on) {
-    if (on != 0 && on != 1) return fail(XMHW_ERR_INVALID, "on must be 0 or 1");
-    g_track_intensity_combine = on;
-    return XMHW_OK;
-}
-int xmhw_track_intensity_init(int64_t L, int32_t* n_valid, int64_t* wsum_i, int64_t* isum_q, double* intensity_max,
-                              int32_t* cat_cells, int64_t ldcat, int64_t* n_range, int64_t* n_bad, void* stream) {
-    if (L < 0 || ldcat < L) return fail(XMHW_ERR_INVALID, "bad L/ldcat");
-    if (L > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "track_intensity: 2^31 series entries and more");
-    if (!n_range || !n_bad || (L > 0 && (!n_valid || !wsum_i || !isum_q || !intensity_max || !cat_cells)))
-        return fail(XMHW_ERR_INVALID, "NULL output buffer");
-    return status_of(xmhw::launch_track_intensity_init(L, n_valid, wsum_i, isum_q, intensity_max, cat_cells, ldcat, n_range,
-                                                       n_bad, static_cast<hipStream_t>(stream)),
-                     "track_intensity_init");
-}
-int xmhw_track_intensity_accumulate_f32(const float* ts, int64_t T, int64_t n, int64_t ld, const double* seas,
-                                        const double* thresh, int64_t ldc, int64_t D, const int32_t* row_of_t, int32_t negate,
-                                        const int32_t* start, const int32_t* end, const int32_t* slot, int64_t n_rows,
-                                        const int64_t* row_offsets, const int64_t* wi, const int32_t* time_start,
-                                        const int64_t* offsets, int64_t n_slots, int64_t L, int32_t* n_valid, int64_t* wsum_i,
-                                        int64_t* isum_q, double* intensity_max, int32_t* cat_cells, int64_t ldcat,
-                                        int64_t* n_range, int64_t* n_bad, void* stream) {
-    return track_intensity_accumulate<float>(ts, T, n, ld, seas, thresh, ldc, D, row_of_t, negate, start, end, slot, n_rows,
-                                             row_offsets, wi, time_start, offsets, n_slots, L, n_valid, wsum_i, isum_q,
-                                             intensity_max, cat_cells, ldcat, n_range, n_bad, stream);
-}
-int xmhw_track_intensity_accumulate_f64(const double* ts, int64_t T, int64_t n, int64_t ld, const double* seas,
-                                        const double* thresh, int64_t ldc, int64_t D, const int32_t* row_of_t, int32_t negate,
-                                        const int32_t* start, const int32_t* end, const int32_t* slot, int64_t n_rows,
-                                        const int64_t* row_offsets, const int64_t* wi, const int32_t* time_start,
-                                        const int64_t* offsets, int64_t n_slots, int64_t L, int32_t* n_valid, int64_t* wsum_i,
-                                        int64_t* isum_q, double* intensity_max, int32_t* cat_cells, int64_t ldcat,
-                                        int64_t* n_range, int64_t* n_bad, void* stream) {
-    return track_intensity_accumulate<double>(ts, T, n, ld, seas, thresh, ldc, D, row_of_t, negate, start, end, slot, n_rows,
-                                              row_offsets, wi, time_start, offsets, n_slots, L, n_valid, wsum_i, isum_q,
-                                              intensity_max, cat_cells, ldcat, n_range, n_bad, stream);
-}
-int xmhw_track_intensity_finish(int64_t L, double* intensity_max, void* stream) {
-    if (L < 0) return fail(XMHW_ERR_INVALID, "bad L");
-    if (L > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "track_intensity: 2^31 series entries and more");
-    if (L == 0) return XMHW_OK;
-    if (!intensity_max) return fail(XMHW_ERR_INVALID, "NULL output buffer");
-    return status_of(xmhw::launch_track_intensity_finish(L, intensity_max, static_cast<hipStream_t>(stream)),
-                     "track_intensity_finish launch");
-}
-
-int xmhw_set_class_days_block(int32_t steps) {
-    if (steps < 0) return fail(XMHW_ERR_INVALID, "steps must be >= 0");
-    g_class_days_block = steps;
-    return XMHW_OK;
-}
-int xmhw_class_days_init(int32_t K, int64_t C, int32_t* days, int64_t* isum_q, double* intensity_max, int64_t ldo,
-                         int64_t* n_range, void* stream) {
-    if (class_days_check_k(K) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
-    if (C > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "class_days: 2^31 cells and more");
-    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
-    if (!n_range || (C > 0 && (!days || !isum_q || !intensity_max))) return fail(XMHW_ERR_INVALID, "NULL output buffer");
-    return status_of(xmhw::launch_class_days_init(K, C, days, isum_q, intensity_max, ldo, n_range,
-                                                  static_cast<hipStream_t>(stream)),
-                     "class_days_init");
-}
-int xmhw_class_days_accumulate_f32(const float* ts, int64_t T, int64_t C, int64_t ld, const double* seas, const double* thresh,
-                                   int64_t ldc, const int32_t* row_of_t, int32_t negate, const uint64_t* bits, int64_t ldb,
-                                   int32_t min_duration, int32_t join_gaps, int32_t max_gap, const int32_t* class_of_t,
-                                   int32_t K, int32_t* days, int64_t* isum_q, double* intensity_max, int64_t ldo,
-                                   int64_t* n_range, void* stream) {
-    return class_days_accumulate<float>(ts, T, C, ld, seas, thresh, ldc, row_of_t, negate, bits, ldb, min_duration, join_gaps,
-                                        max_gap, class_of_t, K, days, isum_q, intensity_max, ldo, n_range, stream);
-}
-int xmhw_class_days_accumulate_f64(const double* ts, int64_t T, int64_t C, int64_t ld, const double* seas, const double* thresh,
-                                   int64_t ldc, const int32_t* row_of_t, int32_t negate, const uint64_t* bits, int64_t ldb,
-                                   int32_t min_duration, int32_t join_gaps, int32_t max_gap, const int32_t* class_of_t,
-                                   int32_t K, int32_t* days, int64_t* isum_q, double* intensity_max, int64_t ldo,
-                                   int64_t* n_range, void* stream) {
-    return class_days_accumulate<double>(ts, T, C, ld, seas, thresh, ldc, row_of_t, negate, bits, ldb, min_duration, join_gaps,
-                                         max_gap, class_of_t, K, days, isum_q, intensity_max, ldo, n_range, stream);
-}
-int xmhw_class_days_finish(int32_t K, int64_t C, double* intensity_max, int64_t ldo, void* stream) {
-    if (class_days_check_k(K) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
-    if (C > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "class_days: 2^31 cells and more");
-    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
-    if (C == 0) return XMHW_OK;
-    if (!intensity_max) return fail(XMHW_ERR_INVALID, "NULL output buffer");
-    return status_of(xmhw::launch_class_days_finish(K, C, intensity_max, ldo, static_cast<hipStream_t>(stream)),
-                     "class_days_finish launch");
-}
-
-int xmhw_event_table_bits(const int32_t* start, const int32_t* end, const int64_t* offsets, const int64_t* cell, int64_t C,
-                          int64_t T, uint64_t* bits, int64_t ldb, void* stream) {
-    if (T > 0x7FFFFFFFll || C > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "event_table_bits: 2^31 steps or cells and more");
-    if (T < 0 || C < 0 || ldb < C) return fail(XMHW_ERR_INVALID, "bad T/C/ldb");
-    if (C == 0 || T == 0) return XMHW_OK;
-    if (!offsets || !cell || !bits) return fail(XMHW_ERR_INVALID, "NULL buffer");
-    return status_of(xmhw::launch_event_table_bits(start, end, offsets, cell, C, T, bits, ldb,
-                                                   static_cast<hipStream_t>(stream)),
-                     "event_table_bits launch");
-}
-int xmhw_set_cooccur_block(int32_t words) {
-    if (words < 0) return fail(XMHW_ERR_INVALID, "words must be >= 0");
-    g_cooccur_block = words;
-    return XMHW_OK;
-}
-int xmhw_cooccur_init(int32_t K, int32_t L, int64_t C, int32_t* counts, int64_t ldo, void* stream) {
-    if (cooccur_check_shape(K, L, 0, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
-    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
-    if (C == 0) return XMHW_OK;
-    if (!counts) return fail(XMHW_ERR_INVALID, "NULL output buffer");
-    return status_of(xmhw::launch_cooccur_init(K, L, C, counts, ldo, static_cast<hipStream_t>(stream)), "cooccur_init");
-}
-int xmhw_cooccur_accumulate(const uint64_t* a_bits, int64_t lda, const uint64_t* b_bits, int64_t ldb, int64_t T, int64_t C,
-                            const int32_t* class_of_t, int32_t K, const int32_t* lags, int32_t L, int32_t* counts,
-                            int64_t ldo, void* stream) {
-    if (cooccur_check_shape(K, L, T, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
-    if (T < 0 || C < 0 || lda < C || ldb < C || ldo < C) return fail(XMHW_ERR_INVALID, "bad T/C/lda/ldb/ldo");
-    if (!lags || (T > 0 && !class_of_t)) return fail(XMHW_ERR_INVALID, "NULL class_of_t or lags");
-    if (int rc = check_labels(class_of_t, T, -1, K, kClassesOutside)) return rc;
-    if (C == 0 || T == 0) return XMHW_OK;
-    if (!a_bits || !b_bits || !counts) return fail(XMHW_ERR_INVALID, "NULL buffer");
-    RowsRef classes;                                   // the content-keyed cache of int32 tables
-    if (int rc = upload_table(class_of_t, T, "class table upload", &classes)) return rc;
-    if (int rc = status_of(cooccur_segments(classes, T), "segment table upload")) return rc;
-    RowsRef lag_table;
-    if (int rc = upload_table(lags, L, "lag table upload", &lag_table)) return rc;
-    return status_of(xmhw::launch_cooccur_accumulate(a_bits, lda, b_bits, ldb, T, C, classes->seg_off, classes->seg_class,
-                                                     classes->seg_mask, lag_table->d_rows, L, g_cooccur_block.load(), counts,
-                                                     ldo, static_cast<hipStream_t>(stream)),
-                     "cooccur_accumulate launch");
-}
-
-int xmhw_set_displacement_block(int32_t steps) {
-    if (steps < 0) return fail(XMHW_ERR_INVALID, "steps must be >= 0");
-    g_displacement_block = steps;
-    return XMHW_OK;
-}
-int xmhw_displacement_init(int32_t K, int64_t C, int32_t* n_days, int32_t* n_found, int64_t* sum_m, int64_t* sum_north_m,
-                           int64_t* sum_east_m, int32_t* max_m, int64_t ldo, int64_t* n_visited, void* stream) {
-    if (displacement_check_shape(K, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
-    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
-    if (!n_visited || (C > 0 && (!n_days || !n_found || !sum_m || !sum_north_m || !sum_east_m || !max_m)))
-        return fail(XMHW_ERR_INVALID, "NULL output buffer");
-    return status_of(xmhw::launch_displacement_init(K, C, n_days, n_found, sum_m, sum_north_m, sum_east_m, max_m, ldo,
-                                                    n_visited, static_cast<hipStream_t>(stream)),
-                     "displacement_init");
-}
-int xmhw_displacement_accumulate_f32(const float* ts, int64_t ld, int64_t t0, int64_t nt, int64_t T, int32_t ny, int32_t nx,
-                                     int32_t periodic, const double* seas, int64_t ldc, int64_t D, const int32_t* row_of_t,
-                                     int32_t negate, const uint64_t* bits, int64_t ldb, const int32_t* cell_of_point,
-                                     int64_t C, const int32_t* basin, const int64_t* list_off, const int32_t* djdi,
-                                     const int32_t* dist_m, const int32_t* north_m, const int32_t* east_m, int64_t n_entries,
-                                     const int32_t* class_of_t, int32_t K, int32_t* n_days, int32_t* n_found, int64_t* sum_m,
-                                     int64_t* sum_north_m, int64_t* sum_east_m, int32_t* max_m, int64_t ldo,
-                                     int64_t* n_visited, void* stream) {
-    return displacement_accumulate<float>(ts, ld, t0, nt, T, ny, nx, periodic, seas, ldc, D, row_of_t, negate, bits, ldb,
-                                          cell_of_point, C, basin, list_off, djdi, dist_m, north_m, east_m, n_entries,
-                                          class_of_t, K, n_days, n_found, sum_m, sum_north_m, sum_east_m, max_m, ldo,
-                                          n_visited, stream);
-}
-int xmhw_displacement_accumulate_f64(const double* ts, int64_t ld, int64_t t0, int64_t nt, int64_t T, int32_t ny, int32_t nx,
-                                     int32_t periodic, const double* seas, int64_t ldc, int64_t D, const int32_t* row_of_t,
-                                     int32_t negate, const uint64_t* bits, int64_t ldb, const int32_t* cell_of_point,
-                                     int64_t C, const int32_t* basin, const int64_t* list_off, const int32_t* djdi,
-                                     const int32_t* dist_m, const int32_t* north_m, const int32_t* east_m, int64_t n_entries,
-                                     const int32_t* class_of_t, int32_t K, int32_t* n_days, int32_t* n_found, int64_t* sum_m,
-                                     int64_t* sum_north_m, int64_t* sum_east_m, int32_t* max_m, int64_t ldo,
-                                     int64_t* n_visited, void* stream) {
-    return displacement_accumulate<double>(ts, ld, t0, nt, T, ny, nx, periodic, seas, ldc, D, row_of_t, negate, bits, ldb,
-                                           cell_of_point, C, basin, list_off, djdi, dist_m, north_m, east_m, n_entries,
-                                           class_of_t, K, n_days, n_found, sum_m, sum_north_m, sum_east_m, max_m, ldo,
-                                           n_visited, stream);
-}
-
-int xmhw_set_heat_stress_block(int32_t steps) {
-    if (steps < 0) return fail(XMHW_ERR_INVALID, "steps must be >= 0");
-    g_heat_stress_block = steps;
-    return XMHW_OK;
-}
-int xmhw_class_sums_init(int32_t K, int64_t C, int32_t* n_valid, int64_t* sum_q, int64_t ldo, int64_t* n_range, void* stream) {
-    if (heat_stress_check_shape("class_sums", K, 1, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
-    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
-    if (!n_range || (C > 0 && (!n_valid || !sum_q))) return fail(XMHW_ERR_INVALID, "NULL output buffer");
-    return status_of(xmhw::launch_class_sums_init(K, C, n_valid, sum_q, ldo, n_range, static_cast<hipStream_t>(stream)),
-                     "class_sums_init");
-}
-int xmhw_class_sums_accumulate_f32(const float* ts, int64_t T, int64_t C, int64_t ld, double x0, const int32_t* class_of_t,
-                                   int32_t K, int32_t* n_valid, int64_t* sum_q, int64_t ldo, int64_t* n_range, void* stream) {
-    return class_sums_accumulate<float>(ts, T, C, ld, x0, class_of_t, K, n_valid, sum_q, ldo, n_range, stream);
-}
-int xmhw_class_sums_accumulate_f64(const double* ts, int64_t T, int64_t C, int64_t ld, double x0, const int32_t* class_of_t,
-                                   int32_t K, int32_t* n_valid, int64_t* sum_q, int64_t ldo, int64_t* n_range, void* stream) {
-    return class_sums_accumulate<double>(ts, T, C, ld, x0, class_of_t, K, n_valid, sum_q, ldo, n_range, stream);
-}
-int xmhw_heat_stress_init(int32_t K, int64_t C, int32_t* counts, int64_t* hsum_q, int64_t* peak_key, int64_t ldo,
-                          int64_t* n_range, void* stream) {
-    if (heat_stress_check_shape("heat_stress", K, 1, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
-    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
-    if (!n_range || (C > 0 && (!counts || !hsum_q || !peak_key))) return fail(XMHW_ERR_INVALID, "NULL output buffer");
-    return status_of(xmhw::launch_heat_stress_init(K, C, counts, hsum_q, peak_key, ldo, n_range,
-                                                   static_cast<hipStream_t>(stream)),
-                     "heat_stress_init");
-}
-int xmhw_heat_stress_accumulate_f32(const float* ts, int64_t T, int64_t C, int64_t ld, const double* base, int64_t ldb,
-                                    int64_t D, const int32_t* row_of_t, int32_t negate, int32_t W, double h0,
-                                    const int32_t* class_of_t, int32_t K, const int64_t* level_q, int32_t L, const int32_t* at,
-                                    int32_t J, int32_t* counts, int64_t* hsum_q, int64_t* peak_key, int32_t* snap_q,
-                                    int64_t ldo, int64_t* n_range, void* stream) {
-    return heat_stress_accumulate<float>(ts, T, C, ld, base, ldb, D, row_of_t, negate, W, h0, class_of_t, K, level_q, L, at, J,
-                                         counts, hsum_q, peak_key, snap_q, ldo, n_range, stream);
-}
-int xmhw_heat_stress_accumulate_f64(const double* ts, int64_t T, int64_t C, int64_t ld, const double* base, int64_t ldb,
-                                    int64_t D, const int32_t* row_of_t, int32_t negate, int32_t W, double h0,
-                                    const int32_t* class_of_t, int32_t K, const int64_t* level_q, int32_t L, const int32_t* at,
-                                    int32_t J, int32_t* counts, int64_t* hsum_q, int64_t* peak_key, int32_t* snap_q,
-                                    int64_t ldo, int64_t* n_range, void* stream) {
-    return heat_stress_accumulate<double>(ts, T, C, ld, base, ldb, D, row_of_t, negate, W, h0, class_of_t, K, level_q, L, at, J,
-                                          counts, hsum_q, peak_key, snap_q, ldo, n_range, stream);
-}
-int xmhw_heat_stress_finish(int32_t K, int64_t C, const int64_t* peak_key, int32_t* peak_q, int32_t* peak_t, int64_t ldo,
-                            void* stream) {
-    if (heat_stress_check_shape("heat_stress", K, 1, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
-    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
-    if (C == 0) return XMHW_OK;
-    if (!peak_key || !peak_q || !peak_t) return fail(XMHW_ERR_INVALID, "NULL buffer");
-    return status_of(xmhw::launch_heat_stress_finish(K, C, peak_key, peak_q, peak_t, ldo, static_cast<hipStream_t>(stream)),
-                     "heat_stress_finish launch");
-}
-
-int xmhw_set_index_regress_block(int32_t steps) {
-    if (steps < 0) return fail(XMHW_ERR_INVALID, "steps must be >= 0");
-    g_index_regress_block = steps;
-    return XMHW_OK;
-}
-int xmhw_index_regress_init(int32_t K, int32_t J, int64_t C, int32_t* n, int64_t* sa, int64_t* saa, int32_t* n1, int64_t* saa1,
-                            int64_t* saz, int64_t* mz, int64_t* mzz, int64_t ldo, int64_t* n_range, void* stream) {
-    if (index_regress_check_shape(K, J, 1, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
-    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
-    if (!n_range || (C > 0 && (!n || !sa || !saa || !n1 || !saa1 || !saz || !mz || !mzz)))
-        return fail(XMHW_ERR_INVALID, "NULL output buffer");
-    return status_of(xmhw::launch_index_regress_init(K, J, C, n, sa, saa, n1, saa1, saz, mz, mzz, ldo, n_range,
-                                                     static_cast<hipStream_t>(stream)),
-                     "index_regress_init");
-}
-int xmhw_index_regress_accumulate_f32(const float* ts, int64_t T, int64_t C, int64_t ld, const double* base, int64_t ldb,
-                                      int64_t D, const int32_t* row_of_t, const int32_t* class_of_t, int32_t K,
-                                      const int32_t* zq, int32_t J, int32_t* n, int64_t* sa, int64_t* saa, int32_t* n1,
-                                      int64_t* saa1, int64_t* saz, int64_t* mz, int64_t* mzz, int64_t ldo, int64_t* n_range,
-                                      void* stream) {
-    return index_regress_accumulate<float>(ts, T, C, ld, base, ldb, D, row_of_t, class_of_t, K, zq, J, n, sa, saa, n1, saa1,
-                                           saz, mz, mzz, ldo, n_range, stream);
-}
-int xmhw_index_regress_accumulate_f64(const double* ts, int64_t T, int64_t C, int64_t ld, const double* base, int64_t ldb,
-                                      int64_t D, const int32_t* row_of_t, const int32_t* class_of_t, int32_t K,
-                                      const int32_t* zq, int32_t J, int32_t* n, int64_t* sa, int64_t* saa, int32_t* n1,
-                                      int64_t* saa1, int64_t* saz, int64_t* mz, int64_t* mzz, int64_t ldo, int64_t* n_range,
-                                      void* stream) {
-    return index_regress_accumulate<double>(ts, T, C, ld, base, ldb, D, row_of_t, class_of_t, K, zq, J, n, sa, saa, n1, saa1,
-                                            saz, mz, mzz, ldo, n_range, stream);
-}
-
-int xmhw_set_composite_block(int32_t steps) {
-    if (steps < 0) return fail(XMHW_ERR_INVALID, "steps must be >= 0");
-    g_composite_block = steps;
-    return XMHW_OK;
-}
-int xmhw_composite_init(int32_t K, int32_t D, int64_t C, int32_t* n, int64_t* s, int64_t* ss, int64_t ldo, int64_t* n_range,
-                        void* stream) {
-    if (composite_check_shape(K, D, 0, 1, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
-    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
-    if (!n_range || (C > 0 && (!n || !s || !ss))) return fail(XMHW_ERR_INVALID, "NULL output buffer");
-    return status_of(xmhw::launch_composite_init(K, D, C, n, s, ss, ldo, n_range, static_cast<hipStream_t>(stream)),
-                     "composite_init");
-}
-int xmhw_composite_accumulate_f32(const float* ts, int64_t T, int64_t C, int64_t ld, const double* base, int64_t ldb,
-                                  int64_t Dr, const int32_t* row_of_t, int32_t shift, const uint64_t* anchor_bits, int64_t lda,
-                                  const int32_t* class_of_t, int32_t K, int32_t before, int32_t after, int32_t* n, int64_t* s,
-                                  int64_t* ss, int64_t ldo, int64_t* n_range, void* stream) {
-    return composite_accumulate<float>(ts, T, C, ld, base, ldb, Dr, row_of_t, shift, anchor_bits, lda, class_of_t, K, before,
-                                       after, n, s, ss, ldo, n_range, stream);
-}
-int xmhw_composite_accumulate_f64(const double* ts, int64_t T, int64_t C, int64_t ld, const double* base, int64_t ldb,
-                                  int64_t Dr, const int32_t* row_of_t, int32_t shift, const uint64_t* anchor_bits, int64_t lda,
-                                  const int32_t* class_of_t, int32_t K, int32_t before, int32_t after, int32_t* n, int64_t* s,
-                                  int64_t* ss, int64_t ldo, int64_t* n_range, void* stream) {
-    return composite_accumulate<double>(ts, T, C, ld, base, ldb, Dr, row_of_t, shift, anchor_bits, lda, class_of_t, K, before,
-                                        after, n, s, ss, ldo, n_range, stream);
-}
-
-int xmhw_set_lag_corr_block(int32_t steps) {
-    if (steps < 0) return fail(XMHW_ERR_INVALID, "steps must be >= 0");
-    g_lag_corr_block = steps;
-    return XMHW_OK;
-}
-int xmhw_lag_corr_init(int32_t K, int32_t max_lag, int64_t C, int32_t* n, int64_t* sx, int64_t* sy, int64_t* sxx, int64_t* syy,
-                       int64_t* sxy, int64_t ldo, int64_t* n_range, void* stream) {
-    if (lag_corr_check_shape(K, max_lag, 0, 0, 1, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
-    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
-    if (!n_range || (C > 0 && (!n || !sx || !sy || !sxx || !syy || !sxy))) return fail(XMHW_ERR_INVALID, "NULL output buffer");
-    return status_of(xmhw::launch_lag_corr_init(K, max_lag, C, n, sx, sy, sxx, syy, sxy, ldo, n_range,
-                                                static_cast<hipStream_t>(stream)),
-                     "lag_corr_init");
-}
-int xmhw_lag_corr_accumulate_f32(const float* x, int64_t ldx, const float* y, int64_t ldy, int64_t T, int64_t C,
-                                 const double* base_x, int64_t ldbx, const double* base_y, int64_t ldby, int64_t Dr,
-                                 const int32_t* row_of_t, int32_t shift_x, int32_t shift_y, const int32_t* class_of_t, int32_t K,
-                                 int32_t max_lag, int32_t* n, int64_t* sx, int64_t* sy, int64_t* sxx, int64_t* syy, int64_t* sxy,
-                                 int64_t ldo, int64_t* n_range, void* stream) {
-    return lag_corr_accumulate<float>(x, ldx, y, ldy, T, C, base_x, ldbx, base_y, ldby, Dr, row_of_t, shift_x, shift_y,
-                                      class_of_t, K, max_lag, n, sx, sy, sxx, syy, sxy, ldo, n_range, stream);
-}
-int xmhw_lag_corr_accumulate_f64(const double* x, int64_t ldx, const double* y, int64_t ldy, int64_t T, int64_t C,
-                                 const double* base_x, int64_t ldbx, const double* base_y, int64_t ldby, int64_t Dr,
-                                 const int32_t* row_of_t, int32_t shift_x, int32_t shift_y, const int32_t* class_of_t, int32_t K,
-                                 int32_t max_lag, int32_t* n, int64_t* sx, int64_t* sy, int64_t* sxx, int64_t* syy, int64_t* sxy,
-                                 int64_t ldo, int64_t* n_range, void* stream) {
-    return lag_corr_accumulate<double>(x, ldx, y, ldy, T, C, base_x, ldbx, base_y, ldby, Dr, row_of_t, shift_x, shift_y,
-                                       class_of_t, K, max_lag, n, sx, sy, sxx, syy, sxy, ldo, n_range, stream);
-}
-
-int xmhw_set_spatial_corr_block(int32_t steps) {
-    if (steps < 0) return fail(XMHW_ERR_INVALID, "steps must be >= 0");
-    g_spatial_corr_block = steps;
-    return XMHW_OK;
-}
-int xmhw_set_spatial_corr_tile(int32_t rows) {
-    if (rows != 0 && rows != xmhw::kSpatialCorrRows && rows != xmhw::kSpatialCorrShortRows)
-        return fail(XMHW_ERR_INVALID, "rows must be 0, 4 or 8");
-    g_spatial_corr_tile = rows;
-    return XMHW_OK;
-}
-int xmhw_spatial_corr_init(int32_t K, int32_t D, int32_t ny, int32_t nx, int32_t* n, int64_t* sx, int64_t* sy, int64_t* sxx,
-                           int64_t* syy, int64_t* sxy, int64_t ldo, int64_t* n_range, void* stream) {
-    if (spatial_corr_check_shape(K, D, 0, 1, ny, nx) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
-    if (ny < 0 || nx < 0 || ldo < static_cast<int64_t>(ny) * nx) return fail(XMHW_ERR_INVALID, "bad ny/nx/ldo");
-    if (!n_range || (ny > 0 && nx > 0 && (!n || !sx || !sy || !sxx || !syy || !sxy)))
-        return fail(XMHW_ERR_INVALID, "NULL output buffer");
-    return status_of(xmhw::launch_spatial_corr_init(K, D, static_cast<int64_t>(ny) * nx, n, sx, sy, sxx, syy, sxy, ldo, n_range,
-                                                    static_cast<hipStream_t>(stream)),
-                     "spatial_corr_init");
-}
-int xmhw_spatial_corr_accumulate_f32(const float* ts, int64_t ld, int64_t t0, int64_t nt, int64_t T, int32_t ny, int32_t nx,
-                                     int32_t periodic, const double* base, int64_t ldb, int64_t Dr, const int32_t* row_of_t,
-                                     int32_t shift, const int32_t* class_of_t, int32_t K, const int32_t* offsets, int32_t D,
-                                     int32_t* n, int64_t* sx, int64_t* sy, int64_t* sxx, int64_t* syy, int64_t* sxy,
-                                     int64_t ldo, int64_t* n_range, void* stream) {
-    return spatial_corr_accumulate<float>(ts, ld, t0, nt, T, ny, nx, periodic, base, ldb, Dr, row_of_t, shift, class_of_t, K,
-                                          offsets, D, n, sx, sy, sxx, syy, sxy, ldo, n_range, stream);
-}
-int xmhw_spatial_corr_accumulate_f64(const double* ts, int64_t ld, int64_t t0, int64_t nt, int64_t T, int32_t ny, int32_t nx,
-                                     int32_t periodic, const double* base, int64_t ldb, int64_t Dr, const int32_t* row_of_t,
-                                     int32_t shift, const int32_t* class_of_t, int32_t K, const int32_t* offsets, int32_t D,
-                                     int32_t* n, int64_t* sx, int64_t* sy, int64_t* sxx, int64_t* syy, int64_t* sxy,
-                                     int64_t ldo, int64_t* n_range, void* stream) {
-    return spatial_corr_accumulate<double>(ts, ld, t0, nt, T, ny, nx, periodic, base, ldb, Dr, row_of_t, shift, class_of_t, K,
-                                           offsets, D, n, sx, sy, sxx, syy, sxy, ldo, n_range, stream);
-}
-
-int xmhw_set_coarsen_variant(int32_t variant) {
-    if (variant < xmhw::kCoarsenVariantAuto || variant > xmhw::kCoarsenVariantGeneric)
-        return fail(XMHW_ERR_INVALID, "variant must be 0, 1 or 2");
-    g_coarsen_variant = variant;
-    return XMHW_OK;
-}
-int xmhw_set_coarsen_chunk(int32_t windows) {
-    if (windows < 0) return fail(XMHW_ERR_INVALID, "windows must be >= 0");
-    g_coarsen_chunk = windows;
-    return XMHW_OK;
-}
-int xmhw_coarsen_class(const void* ts, const int32_t* wi, int64_t ld, int32_t nx, int32_t itemsize, int32_t fx) {
-    const int32_t variant = g_coarsen_variant.load();
-    return xmhw::coarsen_class(reinterpret_cast<uint64_t>(ts), reinterpret_cast<uint64_t>(wi), ld, nx, itemsize, fx,
-                               variant == xmhw::kCoarsenVariantNarrow, variant == xmhw::kCoarsenVariantGeneric);
-}
-int xmhw_coarsen_f32(const float* ts, int64_t nt, int64_t ld, int32_t ny, int32_t nx, int32_t fy, int32_t fx, int32_t ncy,
-                     int32_t ncx, const int32_t* wi, double x0, int32_t a, const int32_t* win, int32_t ns, float* out,
-                     int64_t ldo, int64_t* wsum, int32_t* n, int64_t* n_range, void* stream) {
-    return coarsen<float>(ts, nt, ld, ny, nx, fy, fx, ncy, ncx, wi, x0, a, win, ns, out, ldo, wsum, n, n_range, stream);
-}
-int xmhw_coarsen_f64(const double* ts, int64_t nt, int64_t ld, int32_t ny, int32_t nx, int32_t fy, int32_t fx, int32_t ncy,
-                     int32_t ncx, const int32_t* wi, double x0, int32_t a, const int32_t* win, int32_t ns, double* out,
-                     int64_t ldo, int64_t* wsum, int32_t* n, int64_t* n_range, void* stream) {
-    return coarsen<double>(ts, nt, ld, ny, nx, fy, fx, ncy, ncx, wi, x0, a, win, ns, out, ldo, wsum, n, n_range, stream);
-}
-
-int xmhw_set_regrid_variant(int32_t variant) {
-    if (variant < xmhw::kRegridVariantAuto || variant > xmhw::kRegridVariantStaged)
-        return fail(XMHW_ERR_INVALID, "variant must be 0, 1 or 2");
-    g_regrid_variant = variant;
-    return XMHW_OK;
-}
-int xmhw_set_regrid_chunk(int32_t steps) {
-    if (steps < 0) return fail(XMHW_ERR_INVALID, "steps must be >= 0");
-    g_regrid_chunk = steps;
-    return XMHW_OK;
-}
-int xmhw_regrid_class(int32_t nx, int32_t my, int32_t mx, const int32_t* row_ptr, const int32_t* col_first, const int32_t* col_ptr,
-                      int32_t periodic) {
-    const RegridAxis rows{nullptr, row_ptr, nullptr, nullptr, my, 0, false, "row"};
-    const RegridAxis cols{col_first, col_ptr, nullptr, nullptr, mx, nx, periodic != 0, "column"};
-    // (the pointer tables alone: first, weights and extents are not read for the row axis)
-    if (my < 0 || mx < 0 || nx < 1 || (my > 0 && !row_ptr) || (mx > 0 && (!col_ptr || !col_first))) return xmhw::kRegridNone;
-    for (const RegridAxis* x : {&rows, &cols})
-        for (int32_t k = 0; k < x->m; ++k)
-            if (x->ptr[k + 1] < x->ptr[k] || x->ptr[k + 1] - x->ptr[k] > xmhw::kRegridMaxRun) return xmhw::kRegridNone;
-    for (int32_t I = 0; I < mx; ++I) {
-        const int64_t cnt = col_ptr[I + 1] - col_ptr[I], first = col_first[I];
-        if (cnt > 0 && !(periodic ? first >= 0 && first < nx && cnt <= nx : first >= 0 && first + cnt <= nx)) return xmhw::kRegridNone;
-    }
-    return xmhw::regrid_class(xmhw::regrid_max_run(row_ptr, my), xmhw::regrid_max_width(col_first, col_ptr, mx, nx, periodic != 0),
-                              mx < xmhw::kRegridTile ? mx : xmhw::kRegridTile, nx, periodic != 0, g_regrid_variant.load());
-}
-int xmhw_regrid_f32(const float* ts, int64_t nt, int64_t ld, int32_t ny, int32_t nx, int32_t my, int32_t mx,
-                    const int32_t* row_first, const int32_t* row_ptr, const int32_t* ay, const int32_t* wy,
-                    const int32_t* col_first, const int32_t* col_ptr, const int32_t* ax, const int32_t* wx, int32_t periodic,
-                    double x0, int32_t a, float* out, int64_t ldo, int64_t* wsum, int32_t* n, int64_t* n_range, void* stream) {
-    return regrid<float>(ts, nt, ld, ny, nx, my, mx, row_first, row_ptr, ay, wy, col_first, col_ptr, ax, wx, periodic, x0, a, out,
-                         ldo, wsum, n, n_range, stream);
-}
-int xmhw_regrid_f64(const double* ts, int64_t nt, int64_t ld, int32_t ny, int32_t nx, int32_t my, int32_t mx,
-                    const int32_t* row_first, const int32_t* row_ptr, const int32_t* ay, const int32_t* wy,
-                    const int32_t* col_first, const int32_t* col_ptr, const int32_t* ax, const int32_t* wx, int32_t periodic,
-                    double x0, int32_t a, double* out, int64_t ldo, int64_t* wsum, int32_t* n, int64_t* n_range, void* stream) {
-    return regrid<double>(ts, nt, ld, ny, nx, my, mx, row_first, row_ptr, ay, wy, col_first, col_ptr, ax, wx, periodic, x0, a, out,
-                          ldo, wsum, n, n_range, stream);
-}
-
-int xmhw_set_distribution_block(int32_t steps) {
-    if (steps < 0) return fail(XMHW_ERR_INVALID, "steps must be >= 0");
-    g_distribution_block = steps;
-    return XMHW_OK;
-}
-int xmhw_distribution_init(int32_t K, int32_t B, int64_t C, int32_t* hist, int32_t* n, int64_t* s1, int64_t* s2, int64_t* s3,
-                           int64_t* s4, uint64_t* kmin, uint64_t* kmax, int64_t ldo, int64_t* n_range, void* stream) {
-    if (distribution_check_shape(K, B, 1, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
-    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
-    if (!n_range || (C > 0 && (!hist || !n || !s1 || !s2 || !s3 || !s4 || !kmin || !kmax)))
-        return fail(XMHW_ERR_INVALID, "NULL output buffer");
-    return status_of(xmhw::launch_distribution_init(K, B, C, hist, n, s1, s2, s3, s4, kmin, kmax, ldo, n_range,
-                                                    static_cast<hipStream_t>(stream)),
-                     "distribution_init");
-}
-int xmhw_distribution_accumulate_f32(const float* ts, int64_t T, int64_t C, int64_t ld, const double* base, int64_t ldb,
-                                     int64_t Dr, const int32_t* row_of_t, int32_t shift, const int32_t* class_of_t, int32_t K,
-                                     int64_t lo_q, int32_t width_q, int32_t B, int32_t* hist, int32_t* n, int64_t* s1,
-                                     int64_t* s2, int64_t* s3, int64_t* s4, uint64_t* kmin, uint64_t* kmax, int64_t ldo,
-                                     int64_t* n_range, void* stream) {
-    return distribution_accumulate<float>(ts, T, C, ld, base, ldb, Dr, row_of_t, shift, class_of_t, K, lo_q, width_q, B, hist,
-                                          n, s1, s2, s3, s4, kmin, kmax, ldo, n_range, stream);
-}
-int xmhw_distribution_accumulate_f64(const double* ts, int64_t T, int64_t C, int64_t ld, const double* base, int64_t ldb,
-                                     int64_t Dr, const int32_t* row_of_t, int32_t shift, const int32_t* class_of_t, int32_t K,
-                                     int64_t lo_q, int32_t width_q, int32_t B, int32_t* hist, int32_t* n, int64_t* s1,
-                                     int64_t* s2, int64_t* s3, int64_t* s4, uint64_t* kmin, uint64_t* kmax, int64_t ldo,
-                                     int64_t* n_range, void* stream) {
-    return distribution_accumulate<double>(ts, T, C, ld, base, ldb, Dr, row_of_t, shift, class_of_t, K, lo_q, width_q, B, hist,
-                                           n, s1, s2, s3, s4, kmin, kmax, ldo, n_range, stream);
-}
-int xmhw_distribution_finish(int32_t K, int32_t B, int64_t C, const int32_t* hist, const int32_t* n, double* kmin, double* kmax,
-                             const uint64_t* p_q, int32_t P, const int32_t* edge, int32_t L, int32_t* qbin, int32_t* qbelow,
-                             int32_t* qcount, int32_t* n_at_least, int64_t ldo, void* stream) {
-    if (distribution_check_shape(K, B, 1, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
-    if (P < 0 || P > xmhw::kDistributionMaxQuantiles)
-        return fail(XMHW_ERR_UNSUPPORTED,
-                    "distribution: P must be in [0, " + std::to_string(xmhw::kDistributionMaxQuantiles) + "]");
-    if (L < 0 || L > xmhw::kDistributionMaxLevels)
-        return fail(XMHW_ERR_UNSUPPORTED, "distribution: L must be in [0, " + std::to_string(xmhw::kDistributionMaxLevels) + "]");
-    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
-    if ((P > 0 && !p_q) || (L > 0 && !edge)) return fail(XMHW_ERR_INVALID, "NULL host table");
-    for (int32_t j = 0; j < P; ++j)
-        if (p_q[j] > (uint64_t{1} << 32)) return fail(XMHW_ERR_INVALID, "p_q outside [0, 2^32]");
-    for (int32_t l = 0; l < L; ++l)
-        if (edge[l] < 0 || edge[l] > B) return fail(XMHW_ERR_INVALID, "edge outside [0, B]");
-    if (C == 0) return XMHW_OK;
-    if (!hist || !n || !kmin || !kmax || (P > 0 && (!qbin || !qbelow || !qcount)) || (L > 0 && !n_at_least))
-        return fail(XMHW_ERR_INVALID, "NULL buffer");
-    return status_of(xmhw::launch_distribution_finish(K, B, C, hist, n, kmin, kmax, p_q, P, edge, L, qbin, qbelow, qcount, n_at_least,
-                                                      ldo, static_cast<hipStream_t>(stream)),
-                     "distribution_finish launch");
 }
 
 int xmhw_synth_sst_f32(float* ts, int64_t T, int64_t C, int64_t ld, int64_t cell0, uint64_t seed,

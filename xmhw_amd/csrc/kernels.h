@@ -253,29 +253,11 @@ hipError_t launch_series_remove(T* ts, int64_t Tn, int64_t C, int64_t ld, const 
                                 const double* coef, int64_t ldc, hipStream_t stream);
 
 // mhw_coverage() (kernels_coverage.hip): event_day_bits turns the exceedance words of exceed_bits into the per-day
-// in-event bitmap inev[w][ldi] (steps first..last of every filtered, gap-joined event; zeroed here first);
-// coverage_accumulate ADDS, for every step t and region r < R, the number of in-event cells per state (moderate, strong,
-// severe, extreme, event) to cells[t][r][5] and the sum of their weights wq[c] to area_q[t][r][5].  region[c] in
-// [-1, R), -1 = the cell counts nowhere; R <= kCoverageMaxRegions.  row_of_t is a DEVICE array here.
-constexpr int kCoverageMaxRegions = 1024;
+// in-event bitmap inev[w][ldi] (steps first..last of every filtered, gap-joined event; zeroed here first).  The stage
+// entries that take such a bitmap get it through entry_common.h's event_day_bitmap; what a stage adds from it, its
+// limits and its launches stand in the stage's own kernel file, beside its C entries.
 hipError_t launch_event_day_bits(const uint64_t* bits, int64_t Tn, int64_t C, int64_t ldb, int32_t min_duration,
                                  int32_t join_gaps, int32_t max_gap, uint64_t* inev, int64_t ldi, hipStream_t stream);
-template <typename T>
-hipError_t launch_coverage_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* seas,
-                                      const double* thresh, int64_t ldc, const int32_t* row_of_t, int32_t negate,
-                                      const uint64_t* inev, int64_t ldi, const int64_t* wq, const int32_t* region,
-                                      int32_t R, int64_t* cells, int64_t* area_q, hipStream_t stream);
-
-// region_series() (kernels_region.hip): region_accumulate ADDS, for every step t and region r < R, over the cells c with
-// region[c] == r whose sample is not NaN: acc[t][r][0] += 1, acc[t][r][1] += wi[c], acc[t][r][2] += wi[c] *
-// rint(((double)ts[t][c] - x0) * 2^16); a valid sample with |ts - x0| >= 2^7 or infinite is left out and counted in
-// *n_range.  region[c] in [-1, R), -1 = the cell counts nowhere; R <= kRegionMaxRegions.  blocked selects how a wave sums:
-// 0 = one wave sum per step, 1 = the sums of 8 steps together (kernels_region.hip).  Same results.
-constexpr int kRegionMaxRegions = 1024;
-template <typename T>
-hipError_t launch_region_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, double x0, const int64_t* wi,
-                                    const int32_t* region, int32_t R, int64_t* acc, int64_t* n_range, int32_t blocked,
-                                    hipStream_t stream);
 
 // mhw_objects() (kernels_objects.hip): launch_event_objects groups the table rows (runs of days start..end in one cell,
 // rows of cell c = offsets[c]..offsets[c + 1], in time order) into connected components: rows of DIFFERENT cells are
@@ -373,19 +355,6 @@ hipError_t launch_object_shape(const int32_t* start, const int32_t* end, const i
 // entries among the lanes of a wave are summed by a segmented scan before the atomics.
 constexpr int kTrackIntensityChunk = 64;
 constexpr int kTrackIntensityBits = 16;
-hipError_t launch_track_intensity_init(int64_t L, int32_t* n_valid, int64_t* wsum_i, int64_t* isum_q, double* intensity_max,
-                                       int32_t* cat_cells, int64_t ldcat, int64_t* n_range, int64_t* n_bad,
-                                       hipStream_t stream);
-template <typename T>
-hipError_t launch_track_intensity_accumulate(const T* ts, int64_t Tn, int64_t n, int64_t ld, const double* seas,
-                                             const double* thresh, int64_t ldc, const int32_t* row_of_t, int32_t negate,
-                                             const int32_t* start, const int32_t* end, const int32_t* slot,
-                                             int64_t n_rows, const int64_t* row_offsets, const int64_t* wi,
-                                             const int32_t* time_start, const int64_t* offsets, int64_t n_slots, int64_t L,
-                                             int32_t* n_valid, int64_t* wsum_i, int64_t* isum_q, double* intensity_max,
-                                             int32_t* cat_cells, int64_t ldcat, int64_t* n_range, int64_t* n_bad,
-                                             int32_t combine_runs, hipStream_t stream);
-hipError_t launch_track_intensity_finish(int64_t L, double* intensity_max, hipStream_t stream);
 
 // The frame of a class reduction: the kernels below that reduce over TIME and keep the cell (class_days_accumulate,
 // class_sums_accumulate, heat_stress_accumulate, index_regress_accumulate, lag_corr_accumulate, distribution_accumulate,
@@ -412,15 +381,6 @@ hipError_t launch_track_intensity_finish(int64_t L, double* intensity_max, hipSt
 constexpr int kClassDaysMaxClasses = 1024;
 constexpr int kClassDaysChannels = 6;
 constexpr int kClassDaysBits = 16;
-hipError_t launch_class_days_init(int32_t K, int64_t C, int32_t* days, int64_t* isum_q, double* intensity_max, int64_t ldo,
-                                  int64_t* n_range, hipStream_t stream);
-template <typename T>
-hipError_t launch_class_days_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* seas,
-                                        const double* thresh, int64_t ldc, const int32_t* row_of_t,
-                                        const int32_t* class_of_t, int32_t K, int32_t negate, const uint64_t* inev,
-                                        int64_t ldi, int64_t block_steps, int32_t* days, int64_t* isum_q,
-                                        double* intensity_max, int64_t ldo, int64_t* n_range, hipStream_t stream);
-hipError_t launch_class_days_finish(int32_t K, int64_t C, double* intensity_max, int64_t ldo, hipStream_t stream);
 // the finish of every float maximum kept as an order-preserving key (kernels_class.hip): keys -> float64, 0 -> NaN, in
 // place, over rows x cols with leading dimension ld (rows <= 65535)
 hipError_t launch_keys_to_f64(double* key, int64_t rows, int64_t cols, int64_t ld, hipStream_t stream);
@@ -437,39 +397,6 @@ constexpr int kCooccurMaxClasses = 1024;
 constexpr int kCooccurMaxLags = 64;
 constexpr int kCooccurChannels = 4;
 constexpr int kCooccurLagGroup = 8;
-hipError_t launch_event_table_bits(const int32_t* start, const int32_t* end, const int64_t* offsets, const int64_t* cell,
-                                   int64_t C, int64_t Tn, uint64_t* bits, int64_t ldb, hipStream_t stream);
-hipError_t launch_cooccur_init(int32_t K, int32_t L, int64_t C, int32_t* counts, int64_t ldo, hipStream_t stream);
-hipError_t launch_cooccur_accumulate(const uint64_t* a_bits, int64_t lda, const uint64_t* b_bits, int64_t ldb, int64_t Tn,
-                                     int64_t C, const int32_t* seg_off, const int32_t* seg_class, const uint64_t* seg_mask,
-                                     const int32_t* lags, int32_t L, int64_t block_words, int32_t* counts, int64_t ldo,
-                                     hipStream_t stream);
-
-// mhw_displacement() (kernels_displacement.hip): the thermal displacement of every MHW cell-day.  The series is the
-// UNCOMPACTED block ts[nt][ld] of the steps t0 .. t0 + nt - 1 on the (ny, nx) grid, longitude fastest; inev is the
-// in-event bitmap of launch_event_table_bits over the C compact cells and ALL steps; cell_of_point[ny * nx] maps a grid
-// point to its compact cell (-1: land), basin[ny * nx] (or NULL) holds its basin label (negative: no source).  Row j's
-// candidates are the entries list_off[j] .. list_off[j + 1] - 1 of djdi[] (dj << 16 | di & 0xFFFF), dist_m[], north_m[],
-// east_m[], sorted by (dist_m, dj, di).  launch_displacement_accumulate ADDS, per class k of the step and compact cell c,
-// the sources to n_days[k][c], those that found a qualifying entry to n_found[k][c], the entry's dist_m, north_m, east_m
-// to sum_m, sum_north_m, sum_east_m[k][c], raises max_m[k][c] to its dist_m and adds the entries every source looked at
-// to *n_visited (launch_displacement_init zeroes all of them).  row_of_t and class_of_t are DEVICE arrays over all steps
-// here.  block_steps: the steps a workgroup takes per block, 0 = automatic; same results for every value.
-constexpr int kDisplacementMaxClasses = 1024;
-constexpr int kDisplacementMaxAxis = 32767;          // dj and di are packed as int16
-hipError_t launch_displacement_init(int32_t K, int64_t C, int32_t* n_days, int32_t* n_found, int64_t* sum_m,
-                                    int64_t* sum_north_m, int64_t* sum_east_m, int32_t* max_m, int64_t ldo,
-                                    int64_t* n_visited, hipStream_t stream);
-template <typename T>
-hipError_t launch_displacement_accumulate(const T* ts, int64_t ld, int64_t t0, int64_t nt, int32_t ny, int32_t nx,
-                                          int32_t periodic, const double* seas, int64_t ldc, const int32_t* row_of_t,
-                                          int32_t negate, const uint64_t* inev, int64_t ldi, const int32_t* cell_of_point,
-                                          int64_t C, const int32_t* basin, const int64_t* list_off, const int32_t* djdi,
-                                          const int32_t* dist_m, const int32_t* north_m, const int32_t* east_m,
-                                          int64_t n_entries, const int32_t* class_of_t, int32_t K, int64_t block_steps,
-                                          int32_t* n_days, int32_t* n_found, int64_t* sum_m, int64_t* sum_north_m,
-                                          int64_t* sum_east_m, int32_t* max_m, int64_t ldo, int64_t* n_visited,
-                                          hipStream_t stream);
 
 // heat_stress() (kernels_stress.hip): accumulated thermal stress and the class sums of the plain series.
 // launch_class_sums_accumulate ADDS, per class k of the step and cell c, the steps with d = sample - x0 not NaN and
@@ -487,190 +414,6 @@ constexpr int kHeatStressMaxLevels = 6;
 constexpr int kHeatStressMaxSnapshots = 64;
 constexpr int kHeatStressMaxWindow = 255;
 constexpr int kHeatStressBits = 16;
-hipError_t launch_class_sums_init(int32_t K, int64_t C, int32_t* n_valid, int64_t* sum_q, int64_t ldo, int64_t* n_range,
-                                  hipStream_t stream);
-template <typename T>
-hipError_t launch_class_sums_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, double x0, const int32_t* class_of_t,
-                                        int32_t K, int64_t block_steps, int32_t* n_valid, int64_t* sum_q, int64_t ldo,
-                                        int64_t* n_range, hipStream_t stream);
-hipError_t launch_heat_stress_init(int32_t K, int64_t C, int32_t* counts, int64_t* hsum_q, int64_t* peak_key, int64_t ldo,
-                                   int64_t* n_range, hipStream_t stream);
-template <typename T>
-hipError_t launch_heat_stress_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* base, int64_t ldb,
-                                         int64_t D, const int32_t* row_of_t, int32_t negate, int32_t W, double h0,
-                                         const int32_t* class_of_t, int32_t K, const int64_t* level_q, int32_t L,
-                                         const int32_t* at, int32_t J, int64_t block_steps, int32_t* counts, int64_t* hsum_q,
-                                         int64_t* peak_key, int32_t* snap_q, int64_t ldo, int64_t* n_range,
-                                         hipStream_t stream);
-hipError_t launch_heat_stress_finish(int32_t K, int64_t C, const int64_t* peak_key, int32_t* peak_q, int32_t* peak_t,
-                                     int64_t ldo, hipStream_t stream);
-
-// index_regression() (kernels_regress.hip): the sums behind lagged regression maps of anomalies on indices.  With
-// a = sample - base[row_of_t[t]][c], the step VALID iff a is not NaN and |a| < 2^7, q = rint(a * 2^kIndexRegressBits) on
-// valid steps, and the predictor row zq[t][0..J) of the step, launch_index_regress_accumulate ADDS per class k of the step
-// and cell c: over the valid steps n[k][c] += 1, sa += q, saa += q^2, saz[k][j][c] += q * zq[t][j]; over the valid steps
-// whose step t - 1 is valid and of class k as well n1 += 1, saa1 += q(t) q(t - 1); over the steps of class k that are NOT
-// valid mz[k][j][c] += zq[t][j], mzz[k][j][c] += zq[t][j]^2; and counts the non-NaN a with |a| >= 2^7 of the steps with a
-// class in *n_range.  Cells are the fastest axis, leading dimension ldo >= C.  row_of_t and class_of_t are DEVICE arrays
-// here, and so is zq: int32 [T][G], step-major, G = index_regress_group(J) columns of which those past J are zero.
-// block_steps: the steps a workgroup takes per block, 0 = automatic; same results for every value.
-constexpr int kIndexRegressMaxPredictors = 32;
-constexpr int kIndexRegressMaxClasses = 64;
-constexpr int kIndexRegressMaxSteps = 1 << 17;       // T below it: 2^17 * 2^23 * 2^23 = 2^63
-constexpr int kIndexRegressBits = 16;
-constexpr int kIndexRegressPredictorBits = 23;       // |zq| < 2^23
-// the predictor columns of the kernel instantiation that takes J predictors: 4, 8, 16 or 32
-inline int index_regress_group(int32_t J) { return J <= 4 ? 4 : J <= 8 ? 8 : J <= 16 ? 16 : 32; }
-hipError_t launch_index_regress_init(int32_t K, int32_t J, int64_t C, int32_t* n, int64_t* sa, int64_t* saa, int32_t* n1,
-                                     int64_t* saa1, int64_t* saz, int64_t* mz, int64_t* mzz, int64_t ldo, int64_t* n_range,
-                                     hipStream_t stream);
-template <typename T>
-hipError_t launch_index_regress_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* base, int64_t ldb,
-                                           int64_t D, const int32_t* row_of_t, const int32_t* class_of_t, int32_t K,
-                                           const int32_t* zq, int32_t J, int64_t block_steps, int32_t* n, int64_t* sa,
-                                           int64_t* saa, int32_t* n1, int64_t* saa1, int64_t* saz, int64_t* mz, int64_t* mzz,
-                                           int64_t ldo, int64_t* n_range, hipStream_t stream);
-
-// mhw_composite() (kernels_composite.hip): event-centred composites of a field, per cell.  anchor_bits is a bitmap of
-// launch_event_table_bits whose set bits are the anchor steps of every cell (leading dimension lda).  With
-// D = before + after + 1, for every cell c, anchor step s of c with k = class_of_t[s] >= 0 and offset d in [-before, after]
-// with 0 <= s + d < Tn, and a = (sample(s + d) - base[row_of_t[s + d]][c]) * 2^-shift: launch_composite_accumulate ADDS,
-// with i = d + before and for an a that is not NaN and |a| < 2^7, 1 to n[k][i][c], q = rint(a * 2^kCompositeBits) to
-// s[k][i][c] and q^2 to ss[k][i][c]; any other non-NaN a adds 1 to *n_range.  The class is that of the anchor step.  Cells
-// are the fastest axis, leading dimension ldo >= C; the outputs are [K][D][ldo].  row_of_t and class_of_t are DEVICE arrays
-// here.  block_steps: the steps a workgroup takes per block, 0 = automatic; same results for every value.
-constexpr int kCompositeMaxOffsets = 128;            // D at most: a window of two words
-constexpr int kCompositeMaxClasses = 64;
-constexpr int kCompositeMaxSteps = 1 << 17;          // T below it, the cap of index_regression(): 2^17 * 2^46 = 2^63
-constexpr int kCompositeBits = 16;
-constexpr int kCompositeRangeBits = 7;
-constexpr int kCompositeMaxShift = 24;
-hipError_t launch_composite_init(int32_t K, int32_t D, int64_t C, int32_t* n, int64_t* s, int64_t* ss, int64_t ldo,
-                                 int64_t* n_range, hipStream_t stream);
-template <typename T>
-hipError_t launch_composite_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* base, int64_t ldb,
-                                       int64_t Dr, const int32_t* row_of_t, int32_t shift, const uint64_t* anchor_bits,
-                                       int64_t lda, const int32_t* class_of_t, int32_t K, int32_t before, int32_t after,
-                                       int64_t block_steps, int32_t* n, int64_t* s, int64_t* ss, int64_t ldo,
-                                       int64_t* n_range, hipStream_t stream);
-
-// lag_correlation() (kernels_lagcorr.hip, lag_ring.h): per cell, class of the LATER step and lag l in [0, L], the sums over
-// the pairs (qx(t), qy(t - l)) whose two anomalies are valid -- n int32, sx, sy, sxx, syy, sxy int64, [K][L + 1][ldo],
-// ADDED; the definition is in include/xmhw_amd.h, "lag_correlation()".  y may be x.  n_range[0] counts the steps of class
-// >= 0 whose ax is not NaN and out of range, n_range[1] the steps of any class whose ay is.  row_of_t and class_of_t are
-// DEVICE arrays here.  block_steps: the steps a workgroup takes per block, 0 = automatic; same results for every value.
-constexpr int kLagCorrMaxLag = 63;                   // one validity bit per lag in a 64-bit mask
-constexpr int kLagCorrMaxClasses = 64;
-constexpr int kLagCorrMaxSteps = 1 << 17;            // T below it: 2^17 * 2^46 = 2^63
-constexpr int kLagCorrBits = 16;
-constexpr int kLagCorrRangeBits = 7;
-constexpr int kLagCorrMaxShift = 24;
-hipError_t launch_lag_corr_init(int32_t K, int32_t L, int64_t C, int32_t* n, int64_t* sx, int64_t* sy, int64_t* sxx,
-                                int64_t* syy, int64_t* sxy, int64_t ldo, int64_t* n_range, hipStream_t stream);
-template <typename T>
-hipError_t launch_lag_corr_accumulate(const T* x, int64_t ldx, const T* y, int64_t ldy, int64_t Tn, int64_t C,
-                                      const double* base_x, int64_t ldbx, const double* base_y, int64_t ldby, int64_t Dr,
-                                      const int32_t* row_of_t, int32_t shift_x, int32_t shift_y, const int32_t* class_of_t,
-                                      int32_t K, int32_t L, int64_t block_steps, int32_t* n, int64_t* sx, int64_t* sy,
-                                      int64_t* sxx, int64_t* syy, int64_t* sxy, int64_t ldo, int64_t* n_range,
-                                      hipStream_t stream);
-
-// anomaly_distribution() (kernels_distribution.hip, hist_bin.h, wide_sum.h): per cell and class of the step, over the steps
-// whose anomaly d = (sample - base[row_of_t[t]][c]) * 2^-shift is valid, with q = rint(d * 2^kDistributionBits): the counts
-// hist[k][0 .. B + 1][c] of the rows of the bins (lo_q, width_q, B) -- row 0 UNDER, row B + 1 OVER --, n[k][c], s1 and s2
-// [k][c] the sums of q and q^2, s3 and s4 [k][0..1][c] the sums of q^3 and q^4 as 128-bit integers (low words, high words),
-// all ADDED, and kmax, kmin [k][c] RAISED to the key of the largest d and of the largest -d; the definition is in
-// include/xmhw_amd.h, "anomaly_distribution()".  *n_range counts the steps of a class whose d is not NaN and out of range.
-// launch_distribution_finish turns the keys into float64 (kmin: the smallest d; NaN for none) and writes, from the
-// histogram, qbin, qbelow and qcount [k][P][c] of the ranks of p_q[P] and n_at_least[k][L][c] of the edges edge[L].  row_of_t and
-// class_of_t are DEVICE arrays, p_q and edge HOST arrays here.  block_steps: the steps a workgroup takes per block,
-// 0 = automatic; same results for every value.
-constexpr int kDistributionMaxBins = 256;            // two 16-bit counters to a dword: 128 KB of LDS per workgroup
-constexpr int kDistributionMaxClasses = 64;
-constexpr int kDistributionMaxQuantiles = 16;
-constexpr int kDistributionMaxLevels = 8;
-constexpr int kDistributionMaxSteps = 1 << 17;       // T below it, as kLagCorrMaxSteps: 2^17 * 2^46 = 2^63
-constexpr int kDistributionBits = 16;
-constexpr int kDistributionRangeBits = 7;
-constexpr int kDistributionMaxShift = 24;
-hipError_t launch_distribution_init(int32_t K, int32_t B, int64_t C, int32_t* hist, int32_t* n, int64_t* s1, int64_t* s2,
-                                    int64_t* s3, int64_t* s4, uint64_t* kmin, uint64_t* kmax, int64_t ldo, int64_t* n_range,
-                                    hipStream_t stream);
-template <typename T>
-hipError_t launch_distribution_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* base, int64_t ldb,
-                                          int64_t Dr, const int32_t* row_of_t, int32_t shift, const int32_t* class_of_t,
-                                          int32_t K, int64_t lo_q, int32_t width_q, int32_t B, int64_t block_steps,
-                                          int32_t* hist, int32_t* n, int64_t* s1, int64_t* s2, int64_t* s3, int64_t* s4,
-                                          uint64_t* kmin, uint64_t* kmax, int64_t ldo, int64_t* n_range, hipStream_t stream);
-hipError_t launch_distribution_finish(int32_t K, int32_t B, int64_t C, const int32_t* hist, const int32_t* n, double* kmin,
-                                      double* kmax, const uint64_t* p_q, int32_t P, const int32_t* edge, int32_t L,
-                                      int32_t* qbin, int32_t* qbelow, int32_t* qcount, int32_t* n_at_least, int64_t ldo,
-                                      hipStream_t stream);
-
-// spatial_correlation() (kernels_spatialcorr.hip, halo_tile.h): per grid point of the UNCOMPACTED ny x nx grid, class of the
-// step and offset e = (dj, di) of the table djdi[D][2], the sums over the pairs (q(t, p), q(t, p + e)) of one step whose two
-// anomalies are valid -- n int32, sx, sy, sxx, syy, sxy int64, [K][D][ldo], ADDED; the definition is in
-// include/xmhw_amd.h, "spatial_correlation()".  ts is row t0 of the series, the block t0 .. t0 + nt - 1; row_of_t and
-// class_of_t are DEVICE arrays over all T steps here; the offsets come twice, padded with (0, 0) to whole groups
-// (spatial_corr_group): djdi_dev for the kernel, djdi_host for the size of its LDS tile.  *n_range counts the samples of a
-// class >= 0 that are not NaN and out of range, each once.  tile_rows: kSpatialCorrRows or kSpatialCorrShortRows grid rows per
-// workgroup; block_steps: the steps a workgroup takes per block, 0 = automatic; same results for every value of either.
-constexpr int kSpatialCorrMaxOffsets = 64;
-constexpr int kSpatialCorrReach = 32;                // |dj|, |di| at most
-constexpr int kSpatialCorrMaxClasses = 64;
-constexpr int kSpatialCorrMaxSteps = 1 << 17;        // T below it: 2^17 * 2^46 = 2^63
-constexpr int kSpatialCorrMaxAxis = 32767;
-constexpr int kSpatialCorrBits = 16;
-constexpr int kSpatialCorrRangeBits = 7;
-constexpr int kSpatialCorrMaxShift = 24;
-constexpr int kSpatialCorrRows = 8;                  // the tile: 8 rows x 64 longitudes, 512 lanes
-constexpr int kSpatialCorrShortRows = 4;             // ... or 4 x 64, 256 lanes (measurements: the slower of the two)
-hipError_t launch_spatial_corr_init(int32_t K, int32_t D, int64_t N, int32_t* n, int64_t* sx, int64_t* sy, int64_t* sxx,
-                                    int64_t* syy, int64_t* sxy, int64_t ldo, int64_t* n_range, hipStream_t stream);
-template <typename T>
-hipError_t launch_spatial_corr_accumulate(const T* ts, int64_t ld, int64_t t0, int64_t nt, int32_t ny, int32_t nx,
-                                          bool periodic, const double* base, int64_t ldb, int64_t Dr, const int32_t* row_of_t,
-                                          int32_t shift, const int32_t* class_of_t, int32_t K, const int32_t* djdi_dev,
-                                          const int32_t* djdi_host, int32_t D, int32_t tile_rows, int64_t block_steps,
-                                          int32_t* n, int64_t* sx, int64_t* sy, int64_t* sxx, int64_t* syy, int64_t* sxy,
-                                          int64_t ldo, int64_t* n_range, hipStream_t stream);
-
-// coarsen() (kernels_coarsen.hip, coarsen_index.h): the weighted means of the blocks fy x fx of the UNCOMPACTED ny x nx grid
-// over the windows win[s] .. win[s + 1] - 1 of the nt rows at ts -- out [ns][ldo] in the sample type, WRITTEN; wsum int64 and
-// n int32 likewise where not NULL; *n_range ADDED to; the definition is in include/xmhw_amd.h, "coarsen()".  win_dev is a
-// DEVICE array of ns + 1 boundaries here, max_len the longest window of it.  variant: kCoarsenVariantAuto, or a narrower
-// instantiation than the call's alignment allows (tests and measurements); chunk_windows: the windows a workgroup takes per
-// chunk, 0 = automatic (coarsen_auto_chunk); same results for every value of either.
-constexpr int kCoarsenBits = 16;
-constexpr int kCoarsenRangeBits = 7;
-constexpr int kCoarsenMaxWeightBits = 24;
-constexpr int kCoarsenVariantAuto = 0;               // the widest loads the call's alignment allows
-constexpr int kCoarsenVariantNarrow = 1;             // fx = 2, 4 with loads of one sample
-constexpr int kCoarsenVariantGeneric = 2;            // the run-time column loop whatever fx
-template <typename T>
-hipError_t launch_coarsen(const T* ts, int64_t ld, int32_t ny, int32_t nx, int32_t fy, int32_t fx, int32_t ncy, int32_t ncx,
-                          const int32_t* wi, double x0, int32_t a, const int32_t* win_dev, int32_t ns, int32_t max_len,
-                          int32_t variant, int32_t chunk_windows, T* out, int64_t ldo, int64_t* wsum, int32_t* n,
-                          int64_t* n_range, hipStream_t stream);
-
-// regrid() (kernels_regrid.hip, regrid_index.h): first-order conservative remapping of the UNCOMPACTED ny x nx series at ts
-// onto the my x mx destination grid under two CSR overlap tables -- out [nt][ldo] in the sample type, WRITTEN; wsum int64 and
-// n int32 likewise where not NULL; *n_range ADDED to; the definition is in include/xmhw_amd.h, "regrid()".  table_dev is the
-// ONE device table that holds the ten int32 tables of the call at the places `lay` names (regrid_layout); max_rows, max_cols
-// the longest run per axis and max_width the widest tile span (regrid_max_width), taken from the host tables.  variant:
-// kRegridVariantAuto, Direct or Staged (staged where the footprint fits, tests and measurements); chunk_steps: the steps a
-// workgroup takes per chunk, 0 = automatic (regrid_auto_chunk); same results for every value of either.
-constexpr int kRegridBits = 16;
-constexpr int kRegridRangeBits = 7;
-constexpr int kRegridVariantAuto = 0;
-constexpr int kRegridVariantDirect = 1;
-constexpr int kRegridVariantStaged = 2;
-struct RegridLayout;
-template <typename T>
-hipError_t launch_regrid(const T* ts, int64_t nt, int64_t ld, int32_t ny, int32_t nx, int32_t my, int32_t mx,
-                         const int32_t* table_dev, const RegridLayout& lay, int32_t max_rows, int32_t max_cols,
-                         int32_t max_width, int32_t periodic, double x0, int32_t a, int32_t variant, int64_t chunk_steps,
-                         T* out, int64_t ldo, int64_t* wsum, int32_t* n, int64_t* n_range, hipStream_t stream);
 
 // file bytes -> samples (kernels_ingest.hip): raw_type = item size of the stored type (2 int16, 4 float32,
 // 8 float64), swap = the file is big-endian, optional scale/offset (CF packing) and fill value -> NaN

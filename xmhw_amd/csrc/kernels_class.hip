@@ -19,6 +19,8 @@
 //                     nothing.
 //   keys_to_f64       key -> float64 (NaN where no step, voxel or row had a value), in place: the finish of this stage,
 //                     of mhw_track_intensity() and of mhw_objects() (launch_keys_to_f64, kernels.h).
+#include "../../include/xmhw_amd.h"
+#include "entry_common.h"
 #include "stage_reduce.h"
 
 namespace xmhw {
@@ -138,6 +140,8 @@ hipError_t launch_keys_to_f64(double* key, int64_t rows, int64_t cols, int64_t l
     return hipGetLastError();
 }
 
+namespace {
+
 hipError_t launch_class_days_init(int32_t K, int64_t C, int32_t* days, int64_t* isum_q, double* intensity_max, int64_t ldo,
                                   int64_t* n_range, hipStream_t stream) {
     hipError_t e = hipMemsetAsync(n_range, 0, sizeof(int64_t), stream);
@@ -167,13 +171,91 @@ hipError_t launch_class_days_finish(int32_t K, int64_t C, double* intensity_max,
     return launch_keys_to_f64(intensity_max, K, C, ldo, stream);       // K <= kClassDaysMaxClasses rows
 }
 
-template hipError_t launch_class_days_accumulate<float>(const float*, int64_t, int64_t, int64_t, const double*,
-                                                        const double*, int64_t, const int32_t*, const int32_t*, int32_t,
-                                                        int32_t, const uint64_t*, int64_t, int64_t, int32_t*, int64_t*,
-                                                        double*, int64_t, int64_t*, hipStream_t);
-template hipError_t launch_class_days_accumulate<double>(const double*, int64_t, int64_t, int64_t, const double*,
-                                                         const double*, int64_t, const int32_t*, const int32_t*, int32_t,
-                                                         int32_t, const uint64_t*, int64_t, int64_t, int32_t*, int64_t*,
-                                                         double*, int64_t, int64_t*, hipStream_t);
+}  // namespace
 
 }  // namespace xmhw
+
+// ---- the C entries of mhw_days_by() (include/xmhw_amd.h) --------------------------------------------------------------
+namespace {
+
+using namespace xmhw::entry;
+
+static std::atomic<int> g_class_days_block{0};   // steps a workgroup takes per block, 0 = automatic (xmhw_set_class_days_block)
+
+static int class_days_check_k(int32_t K) {
+    if (K < 1 || K > xmhw::kClassDaysMaxClasses)
+        return fail(XMHW_ERR_UNSUPPORTED, "class_days: K must be in [1, " + std::to_string(xmhw::kClassDaysMaxClasses) + "]");
+    return XMHW_OK;
+}
+
+template <typename T>
+int class_days_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* seas, const double* thresh,
+                          int64_t ldc, const int32_t* row_of_t, int32_t negate, const uint64_t* bits, int64_t ldb,
+                          int32_t min_duration, int32_t join_gaps, int32_t max_gap, const int32_t* class_of_t, int32_t K,
+                          int32_t* days, int64_t* isum_q, double* intensity_max, int64_t ldo, int64_t* n_range,
+                          void* stream) {
+    if (class_days_check_k(K) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (Tn > 0x7FFFFFFFll || C > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "class_days: 2^31 steps or cells and more");
+    if (Tn <= 0 || C < 0 || ld < C || ldc < C || ldb < C || ldo < C) return fail(XMHW_ERR_INVALID, "bad T/C/ld/ldc/ldb/ldo");
+    if (min_duration < 1 || max_gap < 0) return fail(XMHW_ERR_INVALID, "bad minDuration/maxGap");
+    if (!class_of_t) return fail(XMHW_ERR_INVALID, "NULL class_of_t");
+    if (int rc = check_labels(class_of_t, Tn, -1, K, kClassesOutside)) return rc;
+    if (C == 0) return XMHW_OK;
+    if (!ts || !seas || !thresh || !row_of_t || !bits || !days || !isum_q || !intensity_max || !n_range)
+        return fail(XMHW_ERR_INVALID, "NULL buffer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    RowsRef rows;
+    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
+    RowsRef classes;                                   // the same content-keyed cache: one more int32[T] table
+    if (int rc = upload_table(class_of_t, Tn, "class table upload", &classes)) return rc;
+    ScratchRef scratch;
+    const uint64_t* inev = nullptr;
+    if (int rc = event_day_bitmap(bits, Tn, C, ldb, min_duration, join_gaps, max_gap, st, &scratch, &inev)) return rc;
+    return status_of(xmhw::launch_class_days_accumulate<T>(ts, Tn, C, ld, seas, thresh, ldc, rows->d_rows, classes->d_rows,
+                                                           K, negate, inev, C, g_class_days_block.load(), days, isum_q,
+                                                           intensity_max, ldo, n_range, st),
+                     "class_days_accumulate launch");
+}
+
+}  // namespace
+
+extern "C" {
+
+int xmhw_set_class_days_block(int32_t steps) { return set_knob(g_class_days_block, steps, "steps must be >= 0"); }
+int xmhw_class_days_init(int32_t K, int64_t C, int32_t* days, int64_t* isum_q, double* intensity_max, int64_t ldo,
+                         int64_t* n_range, void* stream) {
+    if (class_days_check_k(K) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (C > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "class_days: 2^31 cells and more");
+    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
+    if (!n_range || (C > 0 && (!days || !isum_q || !intensity_max))) return fail(XMHW_ERR_INVALID, "NULL output buffer");
+    return status_of(xmhw::launch_class_days_init(K, C, days, isum_q, intensity_max, ldo, n_range,
+                                                  static_cast<hipStream_t>(stream)),
+                     "class_days_init");
+}
+int xmhw_class_days_accumulate_f32(const float* ts, int64_t T, int64_t C, int64_t ld, const double* seas, const double* thresh,
+                                   int64_t ldc, const int32_t* row_of_t, int32_t negate, const uint64_t* bits, int64_t ldb,
+                                   int32_t min_duration, int32_t join_gaps, int32_t max_gap, const int32_t* class_of_t,
+                                   int32_t K, int32_t* days, int64_t* isum_q, double* intensity_max, int64_t ldo,
+                                   int64_t* n_range, void* stream) {
+    return class_days_accumulate<float>(ts, T, C, ld, seas, thresh, ldc, row_of_t, negate, bits, ldb, min_duration, join_gaps,
+                                        max_gap, class_of_t, K, days, isum_q, intensity_max, ldo, n_range, stream);
+}
+int xmhw_class_days_accumulate_f64(const double* ts, int64_t T, int64_t C, int64_t ld, const double* seas, const double* thresh,
+                                   int64_t ldc, const int32_t* row_of_t, int32_t negate, const uint64_t* bits, int64_t ldb,
+                                   int32_t min_duration, int32_t join_gaps, int32_t max_gap, const int32_t* class_of_t,
+                                   int32_t K, int32_t* days, int64_t* isum_q, double* intensity_max, int64_t ldo,
+                                   int64_t* n_range, void* stream) {
+    return class_days_accumulate<double>(ts, T, C, ld, seas, thresh, ldc, row_of_t, negate, bits, ldb, min_duration, join_gaps,
+                                         max_gap, class_of_t, K, days, isum_q, intensity_max, ldo, n_range, stream);
+}
+int xmhw_class_days_finish(int32_t K, int64_t C, double* intensity_max, int64_t ldo, void* stream) {
+    if (class_days_check_k(K) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (C > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "class_days: 2^31 cells and more");
+    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
+    if (C == 0) return XMHW_OK;
+    if (!intensity_max) return fail(XMHW_ERR_INVALID, "NULL output buffer");
+    return status_of(xmhw::launch_class_days_finish(K, C, intensity_max, ldo, static_cast<hipStream_t>(stream)),
+                     "class_days_finish launch");
+}
+
+}  // extern "C"

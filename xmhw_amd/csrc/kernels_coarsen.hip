@@ -26,10 +26,26 @@
 //   per sample        f32 -> f64, subtract, d == d and |d| < 2^7, scale, rint, convert, the gates, one v_mad_i64_i32 (xsum),
 //                     one 64-bit add (wsum) and one 32-bit add (n): the chain region_series() has, without its wave sums.
 //   what binds        the bytes a wave has in flight between two windows, not this chain (measured).
+#include "../../include/xmhw_amd.h"
+#include "entry_common.h"
 #include "stage_reduce.h"
 #include "coarsen_index.h"
 
 namespace xmhw {
+
+// What the stage computes (coarsen_index.h holds the index rules): the weighted means of the blocks fy x fx of the
+// UNCOMPACTED ny x nx grid
+// over the windows win[s] .. win[s + 1] - 1 of the nt rows at ts -- out [ns][ldo] in the sample type, WRITTEN; wsum int64 and
+// n int32 likewise where not NULL; *n_range ADDED to; the definition is in include/xmhw_amd.h, "coarsen()".  win_dev is a
+// DEVICE array of ns + 1 boundaries here, max_len the longest window of it.  variant: kCoarsenVariantAuto, or a narrower
+// instantiation than the call's alignment allows (tests and measurements); chunk_windows: the windows a workgroup takes per
+// chunk, 0 = automatic (coarsen_auto_chunk); same results for every value of either.
+constexpr int kCoarsenBits = 16;
+constexpr int kCoarsenRangeBits = 7;
+constexpr int kCoarsenMaxWeightBits = 24;
+constexpr int kCoarsenVariantAuto = 0;               // the widest loads the call's alignment allows
+constexpr int kCoarsenVariantNarrow = 1;             // fx = 2, 4 with loads of one sample
+constexpr int kCoarsenVariantGeneric = 2;            // the run-time column loop whatever fx
 
 static_assert(kCoarsenBits == kFixedBits && kCoarsenRangeBits == kFixedRangeBits, "one scale for every stage");
 
@@ -212,8 +228,6 @@ hipError_t co_launch(const CoIn<T>& in, const CoOut<T>& out, hipStream_t stream)
     return hipGetLastError();
 }
 
-}  // namespace
-
 template <typename T>
 hipError_t launch_coarsen(const T* ts, int64_t ld, int32_t ny, int32_t nx, int32_t fy, int32_t fx, int32_t ncy, int32_t ncx,
                           const int32_t* wi, double x0, int32_t a, const int32_t* win_dev, int32_t ns, int32_t max_len,
@@ -238,12 +252,81 @@ hipError_t launch_coarsen(const T* ts, int64_t ld, int32_t ny, int32_t nx, int32
     }
 }
 
-#define XMHW_CO_INSTANCE(T)                                                                                                 \
-    template hipError_t launch_coarsen<T>(const T*, int64_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t,           \
-                                          const int32_t*, double, int32_t, const int32_t*, int32_t, int32_t, int32_t,       \
-                                          int32_t, T*, int64_t, int64_t*, int32_t*, int64_t*, hipStream_t)
-XMHW_CO_INSTANCE(float);
-XMHW_CO_INSTANCE(double);
-#undef XMHW_CO_INSTANCE
+}  // namespace
 
 }  // namespace xmhw
+
+// ---- the C entries of coarsen() (include/xmhw_amd.h) ------------------------------------------------------------------
+namespace {
+
+using namespace xmhw::entry;
+
+static std::atomic<int> g_coarsen_variant{0};      // which loads coarsen() may use, 0 = the widest (xmhw_set_coarsen_variant)
+static std::atomic<int> g_coarsen_chunk{0};        // windows a workgroup takes per chunk, 0 = automatic (xmhw_set_coarsen_chunk)
+
+static_assert(XMHW_COARSEN_MAX_VOLUME == xmhw::kCoarsenMaxVolume && XMHW_COARSEN_MAX_WEIGHT_BITS == xmhw::kCoarsenMaxWeightBits &&
+                  XMHW_REGION_SERIES_BITS == xmhw::kCoarsenBits,
+              "the public limits of coarsen() are the kernel's");
+
+template <typename T>
+int coarsen(const T* ts, int64_t nt, int64_t ld, int32_t ny, int32_t nx, int32_t fy, int32_t fx, int32_t ncy, int32_t ncx,
+            const int32_t* wi, double x0, int32_t a, const int32_t* win, int32_t ns, T* out, int64_t ldo, int64_t* wsum,
+            int32_t* n, int64_t* n_range, void* stream) {
+    // the caps: the volume of the largest block x window, over the windows of positive length of a table that is there
+    int64_t max_len = 1;
+    if (win)
+        for (int32_t s = 0; s < ns; ++s) max_len = std::max<int64_t>(max_len, static_cast<int64_t>(win[s + 1]) - win[s]);
+    if (fy >= 1 && fx >= 1 && static_cast<int64_t>(fy) * fx * max_len > xmhw::kCoarsenMaxVolume)
+        return fail(XMHW_ERR_UNSUPPORTED, "coarsen: fy * fx * the longest window is above the cap of " +
+                                              std::to_string(xmhw::kCoarsenMaxVolume) + " samples");
+    if (ny > 0 && nx > 0 && static_cast<int64_t>(ny) * nx > INT32_MAX)
+        return fail(XMHW_ERR_UNSUPPORTED, "coarsen: a grid of 2^31 points and more");
+    if (nt < 0 || ny < 0 || nx < 0 || ld < static_cast<int64_t>(ny) * nx) return fail(XMHW_ERR_INVALID, "bad nt/ny/nx/ld");
+    if (fy < 1 || fx < 1) return fail(XMHW_ERR_INVALID, "coarsen: the factors must be >= 1");
+    if (!xmhw::coarsen_grid_ok(ny, nx, fy, fx, ncy, ncx))
+        return fail(XMHW_ERR_INVALID, "coarsen: ncy, ncx must lie in [0, ceil(ny / fy)], [0, ceil(nx / fx)]");
+    if (ldo < static_cast<int64_t>(ncy) * ncx) return fail(XMHW_ERR_INVALID, "bad ldo");
+    if (ns < 0 || (ns > 0 && !win)) return fail(XMHW_ERR_INVALID, "bad ns / NULL window table");
+    if (ns > 0 && (win[0] < 0 || win[ns] > nt)) return fail(XMHW_ERR_INVALID, "coarsen: the windows leave [0, nt]");
+    for (int32_t s = 0; s < ns; ++s)
+        if (win[s + 1] <= win[s]) return fail(XMHW_ERR_INVALID, "coarsen: the window table must be strictly increasing");
+    if (a < 0 || a > 65536) return fail(XMHW_ERR_INVALID, "coarsen: a must be in [0, 65536]");
+    if (!std::isfinite(x0)) return fail(XMHW_ERR_INVALID, "coarsen: x0 must be finite");
+    if (ns == 0 || ncy == 0 || ncx == 0) return XMHW_OK;
+    if (!ts || !wi || !out || !n_range) return fail(XMHW_ERR_INVALID, "NULL buffer");
+    RowsRef table;
+    if (int rc = upload_table(win, static_cast<int64_t>(ns) + 1, "window table upload", &table)) return rc;
+    return status_of(xmhw::launch_coarsen<T>(ts, ld, ny, nx, fy, fx, ncy, ncx, wi, x0, a, table->d_rows, ns,
+                                             static_cast<int32_t>(max_len), g_coarsen_variant.load(), g_coarsen_chunk.load(),
+                                             out, ldo, wsum, n, n_range, static_cast<hipStream_t>(stream)),
+                     "coarsen launch");
+}
+
+}  // namespace
+
+extern "C" {
+
+int xmhw_set_coarsen_variant(int32_t variant) {
+    if (variant < xmhw::kCoarsenVariantAuto || variant > xmhw::kCoarsenVariantGeneric)
+        return fail(XMHW_ERR_INVALID, "variant must be 0, 1 or 2");
+    g_coarsen_variant = variant;
+    return XMHW_OK;
+}
+int xmhw_set_coarsen_chunk(int32_t windows) { return set_knob(g_coarsen_chunk, windows, "windows must be >= 0"); }
+int xmhw_coarsen_class(const void* ts, const int32_t* wi, int64_t ld, int32_t nx, int32_t itemsize, int32_t fx) {
+    const int32_t variant = g_coarsen_variant.load();
+    return xmhw::coarsen_class(reinterpret_cast<uint64_t>(ts), reinterpret_cast<uint64_t>(wi), ld, nx, itemsize, fx,
+                               variant == xmhw::kCoarsenVariantNarrow, variant == xmhw::kCoarsenVariantGeneric);
+}
+int xmhw_coarsen_f32(const float* ts, int64_t nt, int64_t ld, int32_t ny, int32_t nx, int32_t fy, int32_t fx, int32_t ncy,
+                     int32_t ncx, const int32_t* wi, double x0, int32_t a, const int32_t* win, int32_t ns, float* out,
+                     int64_t ldo, int64_t* wsum, int32_t* n, int64_t* n_range, void* stream) {
+    return coarsen<float>(ts, nt, ld, ny, nx, fy, fx, ncy, ncx, wi, x0, a, win, ns, out, ldo, wsum, n, n_range, stream);
+}
+int xmhw_coarsen_f64(const double* ts, int64_t nt, int64_t ld, int32_t ny, int32_t nx, int32_t fy, int32_t fx, int32_t ncy,
+                     int32_t ncx, const int32_t* wi, double x0, int32_t a, const int32_t* win, int32_t ns, double* out,
+                     int64_t ldo, int64_t* wsum, int32_t* n, int64_t* n_range, void* stream) {
+    return coarsen<double>(ts, nt, ld, ny, nx, fy, fx, ncy, ncx, wi, x0, a, win, ns, out, ldo, wsum, n, n_range, stream);
+}
+
+}  // extern "C"

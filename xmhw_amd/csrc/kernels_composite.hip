@@ -25,10 +25,27 @@
 //                     class >= 0 three integer atomics without a return value at (k * D + i) * ldo + c.  Lanes of a wave
 //                     at the same i hit consecutive addresses.  Nothing accumulates in registers: each (anchor, offset)
 //                     pair is visited exactly once.  No barrier, no LDS, no scratch.
+#include "../../include/xmhw_amd.h"
+#include "entry_common.h"
 #include "stage_reduce.h"
 #include "composite_window.h"
 
 namespace xmhw {
+
+// What the stage computes: event-centred composites of a field, per cell.  anchor_bits is a bitmap of
+// launch_event_table_bits whose set bits are the anchor steps of every cell (leading dimension lda).  With
+// D = before + after + 1, for every cell c, anchor step s of c with k = class_of_t[s] >= 0 and offset d in [-before, after]
+// with 0 <= s + d < Tn, and a = (sample(s + d) - base[row_of_t[s + d]][c]) * 2^-shift: launch_composite_accumulate ADDS,
+// with i = d + before and for an a that is not NaN and |a| < 2^7, 1 to n[k][i][c], q = rint(a * 2^kCompositeBits) to
+// s[k][i][c] and q^2 to ss[k][i][c]; any other non-NaN a adds 1 to *n_range.  The class is that of the anchor step.  Cells
+// are the fastest axis, leading dimension ldo >= C; the outputs are [K][D][ldo].  row_of_t and class_of_t are DEVICE arrays
+// here.  block_steps: the steps a workgroup takes per block, 0 = automatic; same results for every value.
+constexpr int kCompositeMaxOffsets = 128;            // D at most: a window of two words
+constexpr int kCompositeMaxClasses = 64;
+constexpr int kCompositeMaxSteps = 1 << 17;          // T below it, the cap of index_regression(): 2^17 * 2^46 = 2^63
+constexpr int kCompositeBits = 16;
+constexpr int kCompositeRangeBits = 7;
+constexpr int kCompositeMaxShift = 24;
 
 static_assert(kCompositeBits == kFixedBits && kCompositeRangeBits == kFixedRangeBits, "one scale for every stage");
 
@@ -122,8 +139,6 @@ void co_launch(const CoIn<T>& in, int64_t Tn, int64_t C, const int32_t* class_of
                        Tn, C, class_of_t, K, before, D, tb, out);
 }
 
-}  // namespace
-
 hipError_t launch_composite_init(int32_t K, int32_t D, int64_t C, int32_t* n, int64_t* s, int64_t* ss, int64_t ldo,
                                  int64_t* n_range, hipStream_t stream) {
     hipError_t e = hipMemsetAsync(n_range, 0, sizeof(int64_t), stream);
@@ -156,13 +171,81 @@ hipError_t launch_composite_accumulate(const T* ts, int64_t Tn, int64_t C, int64
     return hipGetLastError();
 }
 
-template hipError_t launch_composite_accumulate<float>(const float*, int64_t, int64_t, int64_t, const double*, int64_t,
-                                                       int64_t, const int32_t*, int32_t, const uint64_t*, int64_t,
-                                                       const int32_t*, int32_t, int32_t, int32_t, int64_t, int32_t*,
-                                                       int64_t*, int64_t*, int64_t, int64_t*, hipStream_t);
-template hipError_t launch_composite_accumulate<double>(const double*, int64_t, int64_t, int64_t, const double*, int64_t,
-                                                        int64_t, const int32_t*, int32_t, const uint64_t*, int64_t,
-                                                        const int32_t*, int32_t, int32_t, int32_t, int64_t, int32_t*,
-                                                        int64_t*, int64_t*, int64_t, int64_t*, hipStream_t);
+}  // namespace
 
 }  // namespace xmhw
+
+// ---- the C entries of mhw_composite() (include/xmhw_amd.h) ------------------------------------------------------------
+namespace {
+
+using namespace xmhw::entry;
+
+static std::atomic<int> g_composite_block{0};   // steps a workgroup takes per block, 0 = automatic (xmhw_set_composite_block)
+
+static int composite_check_shape(int32_t K, int64_t D, int32_t shift, int64_t Tn, int64_t C) {
+    if (K < 1 || K > xmhw::kCompositeMaxClasses)
+        return fail(XMHW_ERR_UNSUPPORTED, "composite: K must be in [1, " + std::to_string(xmhw::kCompositeMaxClasses) + "]");
+    if (D < 1 || D > xmhw::kCompositeMaxOffsets)
+        return fail(XMHW_ERR_UNSUPPORTED,
+                    "composite: before + after + 1 must be in [1, " + std::to_string(xmhw::kCompositeMaxOffsets) + "]");
+    if (shift < 0 || shift > xmhw::kCompositeMaxShift)
+        return fail(XMHW_ERR_UNSUPPORTED, "composite: shift must be in [0, " + std::to_string(xmhw::kCompositeMaxShift) + "]");
+    if (Tn >= xmhw::kCompositeMaxSteps) return fail(XMHW_ERR_UNSUPPORTED, "composite: 2^17 steps and more");
+    if (C > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "composite: 2^31 cells and more");
+    return XMHW_OK;
+}
+
+template <typename T>
+int composite_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* base, int64_t ldb, int64_t Dr,
+                         const int32_t* row_of_t, int32_t shift, const uint64_t* anchor_bits, int64_t lda,
+                         const int32_t* class_of_t, int32_t K, int32_t before, int32_t after, int32_t* n, int64_t* s,
+                         int64_t* ss, int64_t ldo, int64_t* n_range, void* stream) {
+    if (before < 0 || after < 0) return fail(XMHW_ERR_UNSUPPORTED, "composite: before and after must be >= 0");
+    if (composite_check_shape(K, static_cast<int64_t>(before) + after + 1, shift, Tn, C) != XMHW_OK)
+        return XMHW_ERR_UNSUPPORTED;
+    if (Tn < 0 || C < 0 || ld < C || ldb < C || lda < C || ldo < C || Dr < 1)
+        return fail(XMHW_ERR_INVALID, "bad T/C/ld/ldb/lda/ldo/D");
+    if (Tn > 0 && (!class_of_t || !row_of_t)) return fail(XMHW_ERR_INVALID, "NULL host table");
+    if (int rc = check_labels(class_of_t, Tn, -1, K, kClassesOutside)) return rc;
+    if (int rc = check_labels(row_of_t, Tn, 0, Dr, kRowsOutside)) return rc;
+    if (C == 0 || Tn == 0) return XMHW_OK;
+    if (!ts || !base || !anchor_bits || !n || !s || !ss || !n_range) return fail(XMHW_ERR_INVALID, "NULL buffer");
+    RowsRef rows;
+    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
+    RowsRef classes;                                   // the same content-keyed cache: one more int32[T] table
+    if (int rc = upload_table(class_of_t, Tn, "class table upload", &classes)) return rc;
+    return status_of(xmhw::launch_composite_accumulate<T>(ts, Tn, C, ld, base, ldb, Dr, rows->d_rows, shift, anchor_bits, lda,
+                                                          classes->d_rows, K, before, after, g_composite_block.load(), n, s,
+                                                          ss, ldo, n_range, static_cast<hipStream_t>(stream)),
+                     "composite_accumulate launch");
+}
+
+}  // namespace
+
+extern "C" {
+
+int xmhw_set_composite_block(int32_t steps) { return set_knob(g_composite_block, steps, "steps must be >= 0"); }
+int xmhw_composite_init(int32_t K, int32_t D, int64_t C, int32_t* n, int64_t* s, int64_t* ss, int64_t ldo, int64_t* n_range,
+                        void* stream) {
+    if (composite_check_shape(K, D, 0, 1, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
+    if (!n_range || (C > 0 && (!n || !s || !ss))) return fail(XMHW_ERR_INVALID, "NULL output buffer");
+    return status_of(xmhw::launch_composite_init(K, D, C, n, s, ss, ldo, n_range, static_cast<hipStream_t>(stream)),
+                     "composite_init");
+}
+int xmhw_composite_accumulate_f32(const float* ts, int64_t T, int64_t C, int64_t ld, const double* base, int64_t ldb,
+                                  int64_t Dr, const int32_t* row_of_t, int32_t shift, const uint64_t* anchor_bits, int64_t lda,
+                                  const int32_t* class_of_t, int32_t K, int32_t before, int32_t after, int32_t* n, int64_t* s,
+                                  int64_t* ss, int64_t ldo, int64_t* n_range, void* stream) {
+    return composite_accumulate<float>(ts, T, C, ld, base, ldb, Dr, row_of_t, shift, anchor_bits, lda, class_of_t, K, before,
+                                       after, n, s, ss, ldo, n_range, stream);
+}
+int xmhw_composite_accumulate_f64(const double* ts, int64_t T, int64_t C, int64_t ld, const double* base, int64_t ldb,
+                                  int64_t Dr, const int32_t* row_of_t, int32_t shift, const uint64_t* anchor_bits, int64_t lda,
+                                  const int32_t* class_of_t, int32_t K, int32_t before, int32_t after, int32_t* n, int64_t* s,
+                                  int64_t* ss, int64_t ldo, int64_t* n_range, void* stream) {
+    return composite_accumulate<double>(ts, T, C, ld, base, ldb, Dr, row_of_t, shift, anchor_bits, lda, class_of_t, K, before,
+                                        after, n, s, ss, ldo, n_range, stream);
+}
+
+}  // extern "C"

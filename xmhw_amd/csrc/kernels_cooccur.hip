@@ -43,6 +43,8 @@
 //                      path: atomics also where a workgroup owns all of T, as in kernels_class.hip (a second path would
 //                      need its own tests for nothing measurable).  No LDS, no cross-lane traffic, no scratch, and
 //                      nothing waits for another workgroup.
+#include "../../include/xmhw_amd.h"
+#include "entry_common.h"
 #include "stage_reduce.h"
 
 namespace xmhw {
@@ -210,8 +212,6 @@ __global__ __launch_bounds__(kCoThreads) void cooccur_accumulate(
     }
 }
 
-}  // namespace
-
 hipError_t launch_event_table_bits(const int32_t* start, const int32_t* end, const int64_t* offsets, const int64_t* cell,
                                    int64_t C, int64_t Tn, uint64_t* bits, int64_t ldb, hipStream_t stream) {
     if (C <= 0 || Tn <= 0) return hipSuccess;
@@ -240,4 +240,66 @@ hipError_t launch_cooccur_accumulate(const uint64_t* a_bits, int64_t lda, const 
     return hipGetLastError();
 }
 
+}  // namespace
+
 }  // namespace xmhw
+
+// ---- the C entries of mhw_cooccurrence() (include/xmhw_amd.h) ---------------------------------------------------------
+namespace {
+
+using namespace xmhw::entry;
+
+static std::atomic<int> g_cooccur_block{0};      // words a workgroup takes per block, 0 = automatic (xmhw_set_cooccur_block)
+
+static int cooccur_check_shape(int32_t K, int32_t L, int64_t Tn, int64_t C) {
+    if (K < 1 || K > xmhw::kCooccurMaxClasses)
+        return fail(XMHW_ERR_UNSUPPORTED, "cooccur: K must be in [1, " + std::to_string(xmhw::kCooccurMaxClasses) + "]");
+    if (L < 1 || L > xmhw::kCooccurMaxLags)
+        return fail(XMHW_ERR_UNSUPPORTED, "cooccur: L must be in [1, " + std::to_string(xmhw::kCooccurMaxLags) + "]");
+    if (Tn > 0x7FFFFFFFll || C > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "cooccur: 2^31 steps or cells and more");
+    return XMHW_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int xmhw_event_table_bits(const int32_t* start, const int32_t* end, const int64_t* offsets, const int64_t* cell, int64_t C,
+                          int64_t T, uint64_t* bits, int64_t ldb, void* stream) {
+    if (T > 0x7FFFFFFFll || C > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "event_table_bits: 2^31 steps or cells and more");
+    if (T < 0 || C < 0 || ldb < C) return fail(XMHW_ERR_INVALID, "bad T/C/ldb");
+    if (C == 0 || T == 0) return XMHW_OK;
+    if (!offsets || !cell || !bits) return fail(XMHW_ERR_INVALID, "NULL buffer");
+    return status_of(xmhw::launch_event_table_bits(start, end, offsets, cell, C, T, bits, ldb,
+                                                   static_cast<hipStream_t>(stream)),
+                     "event_table_bits launch");
+}
+int xmhw_set_cooccur_block(int32_t words) { return set_knob(g_cooccur_block, words, "words must be >= 0"); }
+int xmhw_cooccur_init(int32_t K, int32_t L, int64_t C, int32_t* counts, int64_t ldo, void* stream) {
+    if (cooccur_check_shape(K, L, 0, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
+    if (C == 0) return XMHW_OK;
+    if (!counts) return fail(XMHW_ERR_INVALID, "NULL output buffer");
+    return status_of(xmhw::launch_cooccur_init(K, L, C, counts, ldo, static_cast<hipStream_t>(stream)), "cooccur_init");
+}
+int xmhw_cooccur_accumulate(const uint64_t* a_bits, int64_t lda, const uint64_t* b_bits, int64_t ldb, int64_t T, int64_t C,
+                            const int32_t* class_of_t, int32_t K, const int32_t* lags, int32_t L, int32_t* counts,
+                            int64_t ldo, void* stream) {
+    if (cooccur_check_shape(K, L, T, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (T < 0 || C < 0 || lda < C || ldb < C || ldo < C) return fail(XMHW_ERR_INVALID, "bad T/C/lda/ldb/ldo");
+    if (!lags || (T > 0 && !class_of_t)) return fail(XMHW_ERR_INVALID, "NULL class_of_t or lags");
+    if (int rc = check_labels(class_of_t, T, -1, K, kClassesOutside)) return rc;
+    if (C == 0 || T == 0) return XMHW_OK;
+    if (!a_bits || !b_bits || !counts) return fail(XMHW_ERR_INVALID, "NULL buffer");
+    RowsRef classes;                                   // the content-keyed cache of int32 tables
+    if (int rc = upload_table(class_of_t, T, "class table upload", &classes)) return rc;
+    if (int rc = status_of(cooccur_segments(classes, T), "segment table upload")) return rc;
+    RowsRef lag_table;
+    if (int rc = upload_table(lags, L, "lag table upload", &lag_table)) return rc;
+    return status_of(xmhw::launch_cooccur_accumulate(a_bits, lda, b_bits, ldb, T, C, classes->seg_off, classes->seg_class,
+                                                     classes->seg_mask, lag_table->d_rows, L, g_cooccur_block.load(), counts,
+                                                     ldo, static_cast<hipStream_t>(stream)),
+                     "cooccur_accumulate launch");
+}
+
+}  // extern "C"

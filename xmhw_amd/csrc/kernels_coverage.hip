@@ -18,10 +18,18 @@
 //                        would not hold one step) the wave leader adds to global memory directly - the
 //                        addresses are then spread over the regions.
 // All sums are integers: the result does not depend on the order of the adds, the tiling or the slabs.
+#include "../../include/xmhw_amd.h"
+#include "entry_common.h"
 #include "stage_reduce.h"
 #include "event_walk.h"
 
 namespace xmhw {
+
+// What the stage computes, on the bitmap of launch_event_day_bits (kernels.h): coverage_accumulate ADDS, for every step t
+// and region r < R, the number of in-event cells per state (moderate, strong, severe, extreme, event) to cells[t][r][5]
+// and the sum of their weights wq[c] to area_q[t][r][5].  region[c] in [-1, R), -1 = the cell counts nowhere;
+// R <= kCoverageMaxRegions.  row_of_t is a DEVICE array here.
+constexpr int kCoverageMaxRegions = 1024;
 
 namespace {
 
@@ -159,6 +167,8 @@ hipError_t launch_event_day_bits(const uint64_t* bits, int64_t Tn, int64_t C, in
     return hipGetLastError();
 }
 
+namespace {
+
 template <typename T>
 hipError_t launch_coverage_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* seas,
                                       const double* thresh, int64_t ldc, const int32_t* row_of_t, int32_t negate,
@@ -182,13 +192,59 @@ hipError_t launch_coverage_accumulate(const T* ts, int64_t Tn, int64_t C, int64_
     return hipGetLastError();
 }
 
-template hipError_t launch_coverage_accumulate<float>(const float*, int64_t, int64_t, int64_t, const double*,
-                                                      const double*, int64_t, const int32_t*, int32_t, const uint64_t*,
-                                                      int64_t, const int64_t*, const int32_t*, int32_t, int64_t*,
-                                                      int64_t*, hipStream_t);
-template hipError_t launch_coverage_accumulate<double>(const double*, int64_t, int64_t, int64_t, const double*,
-                                                       const double*, int64_t, const int32_t*, int32_t, const uint64_t*,
-                                                       int64_t, const int64_t*, const int32_t*, int32_t, int64_t*,
-                                                       int64_t*, hipStream_t);
+}  // namespace
 
 }  // namespace xmhw
+
+// ---- the C entries of mhw_coverage() (include/xmhw_amd.h) -------------------------------------------------------------
+namespace {
+
+using namespace xmhw::entry;
+
+template <typename T>
+int coverage_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* seas, const double* thresh,
+                        int64_t ldc, const int32_t* row_of_t, int32_t negate, const uint64_t* bits, int64_t ldb,
+                        int32_t min_duration, int32_t join_gaps, int32_t max_gap, const int64_t* wq,
+                        const int32_t* region, int32_t R, int64_t* cells, int64_t* area_q, void* stream) {
+    if (Tn <= 0 || C < 0 || ld < C || ldc < C || ldb < C) return fail(XMHW_ERR_INVALID, "bad T/C/ld/ldc/ldb");
+    if (Tn >= (int64_t{1} << 31)) return fail(XMHW_ERR_INVALID, "T too large");
+    if (min_duration < 1 || max_gap < 0) return fail(XMHW_ERR_INVALID, "bad minDuration/maxGap");
+    if (R < 1) return fail(XMHW_ERR_INVALID, "R must be >= 1");
+    if (R > xmhw::kCoverageMaxRegions)
+        return fail(XMHW_ERR_UNSUPPORTED, "coverage: R above the cap of " + std::to_string(xmhw::kCoverageMaxRegions) + " regions");
+    if (C == 0) return XMHW_OK;
+    if (!ts || !seas || !thresh || !row_of_t || !bits || !wq || !region || !cells || !area_q)
+        return fail(XMHW_ERR_INVALID, "NULL buffer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    RowsRef rows;
+    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
+    ScratchRef scratch;
+    const uint64_t* inev = nullptr;
+    if (int rc = event_day_bitmap(bits, Tn, C, ldb, min_duration, join_gaps, max_gap, st, &scratch, &inev)) return rc;
+    return status_of(xmhw::launch_coverage_accumulate<T>(ts, Tn, C, ld, seas, thresh, ldc, rows->d_rows, negate, inev, C, wq,
+                                                         region, R, cells, area_q, st),
+                     "coverage_accumulate launch");
+}
+
+}  // namespace
+
+extern "C" {
+
+int xmhw_coverage_accumulate_f32(const float* ts, int64_t T, int64_t C, int64_t ld, const double* seas,
+                                 const double* thresh, int64_t ldc, const int32_t* row_of_t, int32_t negate,
+                                 const uint64_t* bits, int64_t ldb, int32_t min_duration, int32_t join_gaps,
+                                 int32_t max_gap, const int64_t* wq, const int32_t* region, int32_t R, int64_t* cells,
+                                 int64_t* area_q, void* stream) {
+    return coverage_accumulate<float>(ts, T, C, ld, seas, thresh, ldc, row_of_t, negate, bits, ldb, min_duration,
+                                      join_gaps, max_gap, wq, region, R, cells, area_q, stream);
+}
+int xmhw_coverage_accumulate_f64(const double* ts, int64_t T, int64_t C, int64_t ld, const double* seas,
+                                 const double* thresh, int64_t ldc, const int32_t* row_of_t, int32_t negate,
+                                 const uint64_t* bits, int64_t ldb, int32_t min_duration, int32_t join_gaps,
+                                 int32_t max_gap, const int64_t* wq, const int32_t* region, int32_t R, int64_t* cells,
+                                 int64_t* area_q, void* stream) {
+    return coverage_accumulate<double>(ts, T, C, ld, seas, thresh, ldc, row_of_t, negate, bits, ldb, min_duration,
+                                       join_gaps, max_gap, wq, region, R, cells, area_q, stream);
+}
+
+}  // extern "C"

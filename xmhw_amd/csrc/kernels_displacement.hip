@@ -33,9 +33,24 @@
 //                     Every index is checked where it is formed: an entry whose row leaves the grid is skipped, list
 //                     bounds are clamped to the stream's length, a cell id outside [0, C) is no source -- whatever the
 //                     tables hold, no access leaves its buffer.
+#include "../../include/xmhw_amd.h"
+#include "entry_common.h"
 #include "stage_reduce.h"
 
 namespace xmhw {
+
+// What the stage computes: the thermal displacement of every MHW cell-day.  The series is the
+// UNCOMPACTED block ts[nt][ld] of the steps t0 .. t0 + nt - 1 on the (ny, nx) grid, longitude fastest; inev is the
+// in-event bitmap of launch_event_table_bits over the C compact cells and ALL steps; cell_of_point[ny * nx] maps a grid
+// point to its compact cell (-1: land), basin[ny * nx] (or NULL) holds its basin label (negative: no source).  Row j's
+// candidates are the entries list_off[j] .. list_off[j + 1] - 1 of djdi[] (dj << 16 | di & 0xFFFF), dist_m[], north_m[],
+// east_m[], sorted by (dist_m, dj, di).  launch_displacement_accumulate ADDS, per class k of the step and compact cell c,
+// the sources to n_days[k][c], those that found a qualifying entry to n_found[k][c], the entry's dist_m, north_m, east_m
+// to sum_m, sum_north_m, sum_east_m[k][c], raises max_m[k][c] to its dist_m and adds the entries every source looked at
+// to *n_visited (launch_displacement_init zeroes all of them).  row_of_t and class_of_t are DEVICE arrays over all steps
+// here.  block_steps: the steps a workgroup takes per block, 0 = automatic; same results for every value.
+constexpr int kDisplacementMaxClasses = 1024;
+constexpr int kDisplacementMaxAxis = 32767;          // dj and di are packed as int16
 
 namespace {
 
@@ -174,8 +189,6 @@ __global__ __launch_bounds__(kDpThreads) void displacement_accumulate(
     if (lane == 0 && visited) atomicAdd(out.n_visited, visited);
 }
 
-}  // namespace
-
 hipError_t launch_displacement_init(int32_t K, int64_t C, int32_t* n_days, int32_t* n_found, int64_t* sum_m,
                                     int64_t* sum_north_m, int64_t* sum_east_m, int32_t* max_m, int64_t ldo,
                                     int64_t* n_visited, hipStream_t stream) {
@@ -209,14 +222,106 @@ hipError_t launch_displacement_accumulate(const T* ts, int64_t ld, int64_t t0, i
     return hipGetLastError();
 }
 
-#define XMHW_DP_INST(T)                                                                                                  \
-    template hipError_t launch_displacement_accumulate<T>(                                                               \
-        const T*, int64_t, int64_t, int64_t, int32_t, int32_t, int32_t, const double*, int64_t, const int32_t*, int32_t, \
-        const uint64_t*, int64_t, const int32_t*, int64_t, const int32_t*, const int64_t*, const int32_t*, const int32_t*, \
-        const int32_t*, const int32_t*, int64_t, const int32_t*, int32_t, int64_t, int32_t*, int32_t*, int64_t*, int64_t*, \
-        int64_t*, int32_t*, int64_t, int64_t*, hipStream_t);
-XMHW_DP_INST(float)
-XMHW_DP_INST(double)
-#undef XMHW_DP_INST
+}  // namespace
 
 }  // namespace xmhw
+
+// ---- the C entries of mhw_displacement() (include/xmhw_amd.h) ---------------------------------------------------------
+namespace {
+
+using namespace xmhw::entry;
+
+static std::atomic<int> g_displacement_block{0};  // steps a workgroup takes per block, 0 = automatic (xmhw_set_displacement_block)
+
+static int displacement_check_shape(int32_t K, int64_t C) {
+    if (K < 1 || K > xmhw::kDisplacementMaxClasses)
+        return fail(XMHW_ERR_UNSUPPORTED,
+                    "displacement: K must be in [1, " + std::to_string(xmhw::kDisplacementMaxClasses) + "]");
+    if (C > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "displacement: 2^31 cells and more");
+    return XMHW_OK;
+}
+
+template <typename T>
+int displacement_accumulate(const T* ts, int64_t ld, int64_t t0, int64_t nt, int64_t Tn, int32_t ny, int32_t nx,
+                            int32_t periodic, const double* seas, int64_t ldc, int64_t D, const int32_t* row_of_t,
+                            int32_t negate, const uint64_t* bits, int64_t ldb, const int32_t* cell_of_point, int64_t C,
+                            const int32_t* basin, const int64_t* list_off, const int32_t* djdi, const int32_t* dist_m,
+                            const int32_t* north_m, const int32_t* east_m, int64_t n_entries, const int32_t* class_of_t,
+                            int32_t K, int32_t* n_days, int32_t* n_found, int64_t* sum_m, int64_t* sum_north_m,
+                            int64_t* sum_east_m, int32_t* max_m, int64_t ldo, int64_t* n_visited, void* stream) {
+    if (displacement_check_shape(K, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (Tn > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "displacement: 2^31 steps and more");
+    if (ny > xmhw::kDisplacementMaxAxis || nx > xmhw::kDisplacementMaxAxis)
+        return fail(XMHW_ERR_UNSUPPORTED, "displacement: a grid axis of 2^15 points and more");
+    if (ny < 1 || nx < 1) return fail(XMHW_ERR_INVALID, "bad ny/nx");
+    const int64_t N = static_cast<int64_t>(ny) * nx;
+    if (Tn <= 0 || t0 < 0 || nt < 1 || nt > Tn - t0) return fail(XMHW_ERR_INVALID, "bad T/t0/nt");
+    if (C < 0 || C > N || ld < N || ldc < C || ldb < C || ldo < C || D < 1 || n_entries < 0)
+        return fail(XMHW_ERR_INVALID, "bad C/ld/ldc/ldb/ldo/D/n_entries");
+    if (!class_of_t || !row_of_t) return fail(XMHW_ERR_INVALID, "NULL class_of_t or row_of_t");
+    // the two tables are judged step by step: the one with the earlier bad label is named, class_of_t where both are bad
+    // at one step
+    const int64_t bad_class = first_outside(class_of_t, Tn, -1, K);
+    if (int rc = check_labels(row_of_t, bad_class, 0, D, kRowsOutside)) return rc;
+    if (bad_class < Tn) return fail(XMHW_ERR_INVALID, kClassesOutside);
+    if (C == 0) return XMHW_OK;
+    if (!ts || !seas || !bits || !cell_of_point || !list_off) return fail(XMHW_ERR_INVALID, "NULL buffer");
+    if (n_entries > 0 && (!djdi || !dist_m || !north_m || !east_m)) return fail(XMHW_ERR_INVALID, "NULL list buffer");
+    if (!n_days || !n_found || !sum_m || !sum_north_m || !sum_east_m || !max_m || !n_visited)
+        return fail(XMHW_ERR_INVALID, "NULL output buffer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    RowsRef rows;
+    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
+    RowsRef classes;                                   // the same content-keyed cache: one more int32[T] table
+    if (int rc = upload_table(class_of_t, Tn, "class table upload", &classes)) return rc;
+    return status_of(xmhw::launch_displacement_accumulate<T>(ts, ld, t0, nt, ny, nx, periodic != 0, seas, ldc, rows->d_rows,
+                                                             negate != 0, bits, ldb, cell_of_point, C, basin, list_off, djdi,
+                                                             dist_m, north_m, east_m, n_entries, classes->d_rows, K,
+                                                             g_displacement_block.load(), n_days, n_found, sum_m,
+                                                             sum_north_m, sum_east_m, max_m, ldo, n_visited, st),
+                     "displacement_accumulate launch");
+}
+
+}  // namespace
+
+extern "C" {
+
+int xmhw_set_displacement_block(int32_t steps) { return set_knob(g_displacement_block, steps, "steps must be >= 0"); }
+int xmhw_displacement_init(int32_t K, int64_t C, int32_t* n_days, int32_t* n_found, int64_t* sum_m, int64_t* sum_north_m,
+                           int64_t* sum_east_m, int32_t* max_m, int64_t ldo, int64_t* n_visited, void* stream) {
+    if (displacement_check_shape(K, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
+    if (!n_visited || (C > 0 && (!n_days || !n_found || !sum_m || !sum_north_m || !sum_east_m || !max_m)))
+        return fail(XMHW_ERR_INVALID, "NULL output buffer");
+    return status_of(xmhw::launch_displacement_init(K, C, n_days, n_found, sum_m, sum_north_m, sum_east_m, max_m, ldo,
+                                                    n_visited, static_cast<hipStream_t>(stream)),
+                     "displacement_init");
+}
+int xmhw_displacement_accumulate_f32(const float* ts, int64_t ld, int64_t t0, int64_t nt, int64_t T, int32_t ny, int32_t nx,
+                                     int32_t periodic, const double* seas, int64_t ldc, int64_t D, const int32_t* row_of_t,
+                                     int32_t negate, const uint64_t* bits, int64_t ldb, const int32_t* cell_of_point,
+                                     int64_t C, const int32_t* basin, const int64_t* list_off, const int32_t* djdi,
+                                     const int32_t* dist_m, const int32_t* north_m, const int32_t* east_m, int64_t n_entries,
+                                     const int32_t* class_of_t, int32_t K, int32_t* n_days, int32_t* n_found, int64_t* sum_m,
+                                     int64_t* sum_north_m, int64_t* sum_east_m, int32_t* max_m, int64_t ldo,
+                                     int64_t* n_visited, void* stream) {
+    return displacement_accumulate<float>(ts, ld, t0, nt, T, ny, nx, periodic, seas, ldc, D, row_of_t, negate, bits, ldb,
+                                          cell_of_point, C, basin, list_off, djdi, dist_m, north_m, east_m, n_entries,
+                                          class_of_t, K, n_days, n_found, sum_m, sum_north_m, sum_east_m, max_m, ldo,
+                                          n_visited, stream);
+}
+int xmhw_displacement_accumulate_f64(const double* ts, int64_t ld, int64_t t0, int64_t nt, int64_t T, int32_t ny, int32_t nx,
+                                     int32_t periodic, const double* seas, int64_t ldc, int64_t D, const int32_t* row_of_t,
+                                     int32_t negate, const uint64_t* bits, int64_t ldb, const int32_t* cell_of_point,
+                                     int64_t C, const int32_t* basin, const int64_t* list_off, const int32_t* djdi,
+                                     const int32_t* dist_m, const int32_t* north_m, const int32_t* east_m, int64_t n_entries,
+                                     const int32_t* class_of_t, int32_t K, int32_t* n_days, int32_t* n_found, int64_t* sum_m,
+                                     int64_t* sum_north_m, int64_t* sum_east_m, int32_t* max_m, int64_t ldo,
+                                     int64_t* n_visited, void* stream) {
+    return displacement_accumulate<double>(ts, ld, t0, nt, T, ny, nx, periodic, seas, ldc, D, row_of_t, negate, bits, ldb,
+                                           cell_of_point, C, basin, list_off, djdi, dist_m, north_m, east_m, n_entries,
+                                           class_of_t, K, n_days, n_found, sum_m, sum_north_m, sum_east_m, max_m, ldo,
+                                           n_visited, stream);
+}
+
+}  // extern "C"

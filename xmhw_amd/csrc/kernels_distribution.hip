@@ -30,11 +30,32 @@
 //                     running count serves the P ranks (the row with running < r <= running + h holds rank r: below =
 //                     running, count = h; the ranks need no order for that) and the L levels (n - running at row 1 + e),
 //                     and the float64 of the smallest d is 0 - that of the largest -d.
+#include "../../include/xmhw_amd.h"
+#include "entry_common.h"
 #include "stage_reduce.h"
 #include "hist_bin.h"
 #include "wide_sum.h"
 
 namespace xmhw {
+
+// What the stage computes (hist_bin.h, wide_sum.h hold the pieces): per cell and class of the step, over the steps
+// whose anomaly d = (sample - base[row_of_t[t]][c]) * 2^-shift is valid, with q = rint(d * 2^kDistributionBits): the counts
+// hist[k][0 .. B + 1][c] of the rows of the bins (lo_q, width_q, B) -- row 0 UNDER, row B + 1 OVER --, n[k][c], s1 and s2
+// [k][c] the sums of q and q^2, s3 and s4 [k][0..1][c] the sums of q^3 and q^4 as 128-bit integers (low words, high words),
+// all ADDED, and kmax, kmin [k][c] RAISED to the key of the largest d and of the largest -d; the definition is in
+// include/xmhw_amd.h, "anomaly_distribution()".  *n_range counts the steps of a class whose d is not NaN and out of range.
+// launch_distribution_finish turns the keys into float64 (kmin: the smallest d; NaN for none) and writes, from the
+// histogram, qbin, qbelow and qcount [k][P][c] of the ranks of p_q[P] and n_at_least[k][L][c] of the edges edge[L].  row_of_t and
+// class_of_t are DEVICE arrays, p_q and edge HOST arrays here.  block_steps: the steps a workgroup takes per block,
+// 0 = automatic; same results for every value.
+constexpr int kDistributionMaxBins = 256;            // two 16-bit counters to a dword: 128 KB of LDS per workgroup
+constexpr int kDistributionMaxClasses = 64;
+constexpr int kDistributionMaxQuantiles = 16;
+constexpr int kDistributionMaxLevels = 8;
+constexpr int kDistributionMaxSteps = 1 << 17;       // T below it, as the cap of lag_correlation(): 2^17 * 2^46 = 2^63
+constexpr int kDistributionBits = 16;
+constexpr int kDistributionRangeBits = 7;
+constexpr int kDistributionMaxShift = 24;
 
 static_assert(kDistributionBits == kFixedBits && kDistributionRangeBits == kFixedRangeBits, "one scale for every stage");
 static_assert(kDistributionMaxBins == kHistMaxBins, "a column of 128 dwords at most");
@@ -262,8 +283,6 @@ __global__ __launch_bounds__(kDsThreads) void distribution_finish(int32_t K, int
 // the dynamic LDS of B bins: 32, 64 or 128 KB
 size_t ds_lds_bytes(int32_t B) { return (B <= 64 ? 32u : B <= 128 ? 64u : 128u) * 1024u; }
 
-}  // namespace
-
 hipError_t launch_distribution_init(int32_t K, int32_t B, int64_t C, int32_t* hist, int32_t* n, int64_t* s1, int64_t* s2,
                                     int64_t* s3, int64_t* s4, uint64_t* kmin, uint64_t* kmax, int64_t ldo, int64_t* n_range,
                                     hipStream_t stream) {
@@ -321,15 +340,120 @@ hipError_t launch_distribution_finish(int32_t K, int32_t B, int64_t C, const int
     return hipGetLastError();
 }
 
-template hipError_t launch_distribution_accumulate<float>(const float*, int64_t, int64_t, int64_t, const double*, int64_t,
-                                                          int64_t, const int32_t*, int32_t, const int32_t*, int32_t, int64_t,
-                                                          int32_t, int32_t, int64_t, int32_t*, int32_t*, int64_t*, int64_t*,
-                                                          int64_t*, int64_t*, uint64_t*, uint64_t*, int64_t, int64_t*,
-                                                          hipStream_t);
-template hipError_t launch_distribution_accumulate<double>(const double*, int64_t, int64_t, int64_t, const double*, int64_t,
-                                                           int64_t, const int32_t*, int32_t, const int32_t*, int32_t, int64_t,
-                                                           int32_t, int32_t, int64_t, int32_t*, int32_t*, int64_t*, int64_t*,
-                                                           int64_t*, int64_t*, uint64_t*, uint64_t*, int64_t, int64_t*,
-                                                           hipStream_t);
+}  // namespace
 
 }  // namespace xmhw
+
+// ---- the C entries of anomaly_distribution() (include/xmhw_amd.h) -----------------------------------------------------
+namespace {
+
+using namespace xmhw::entry;
+
+static std::atomic<int> g_distribution_block{0};    // steps a workgroup takes per block, 0 = automatic (xmhw_set_distribution_block)
+
+static_assert(XMHW_DISTRIBUTION_MAX_BINS == xmhw::kDistributionMaxBins &&
+                  XMHW_DISTRIBUTION_MAX_CLASSES == xmhw::kDistributionMaxClasses &&
+                  XMHW_DISTRIBUTION_MAX_QUANTILES == xmhw::kDistributionMaxQuantiles &&
+                  XMHW_DISTRIBUTION_MAX_LEVELS == xmhw::kDistributionMaxLevels &&
+                  XMHW_DISTRIBUTION_MAX_STEPS == xmhw::kDistributionMaxSteps &&
+                  XMHW_DISTRIBUTION_BITS == xmhw::kDistributionBits &&
+                  XMHW_DISTRIBUTION_RANGE_BITS == xmhw::kDistributionRangeBits &&
+                  XMHW_DISTRIBUTION_MAX_SHIFT == xmhw::kDistributionMaxShift,
+              "the public limits of anomaly_distribution() are the kernel's");
+
+static int distribution_check_shape(int32_t K, int32_t B, int64_t Tn, int64_t C) {
+    if (K < 1 || K > xmhw::kDistributionMaxClasses)
+        return fail(XMHW_ERR_UNSUPPORTED,
+                    "distribution: K must be in [1, " + std::to_string(xmhw::kDistributionMaxClasses) + "]");
+    if (B < 1 || B > xmhw::kDistributionMaxBins)
+        return fail(XMHW_ERR_UNSUPPORTED, "distribution: B must be in [1, " + std::to_string(xmhw::kDistributionMaxBins) + "]");
+    if (Tn >= xmhw::kDistributionMaxSteps) return fail(XMHW_ERR_UNSUPPORTED, "distribution: 2^17 steps and more");
+    if (C > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "distribution: 2^31 cells and more");
+    return XMHW_OK;
+}
+
+template <typename T>
+int distribution_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* base, int64_t ldb, int64_t Dr,
+                            const int32_t* row_of_t, int32_t shift, const int32_t* class_of_t, int32_t K, int64_t lo_q,
+                            int32_t width_q, int32_t B, int32_t* hist, int32_t* n, int64_t* s1, int64_t* s2, int64_t* s3,
+                            int64_t* s4, uint64_t* kmin, uint64_t* kmax, int64_t ldo, int64_t* n_range, void* stream) {
+    if (distribution_check_shape(K, B, Tn, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (width_q < 1) return fail(XMHW_ERR_UNSUPPORTED, "distribution: width_q must be >= 1");
+    if (lo_q < -(int64_t{1} << 23) || lo_q > (int64_t{1} << 23))
+        return fail(XMHW_ERR_UNSUPPORTED, "distribution: lo_q must be in [-2^23, 2^23]");
+    if (shift < 0 || shift > xmhw::kDistributionMaxShift)
+        return fail(XMHW_ERR_UNSUPPORTED,
+                    "distribution: shift must be in [0, " + std::to_string(xmhw::kDistributionMaxShift) + "]");
+    if (Tn < 0 || C < 0 || ld < C || ldb < C || ldo < C || Dr < 1) return fail(XMHW_ERR_INVALID, "bad T/C/ld/ldb/ldo/D");
+    if (Tn > 0 && (!class_of_t || !row_of_t)) return fail(XMHW_ERR_INVALID, "NULL host table");
+    if (int rc = check_labels(class_of_t, Tn, -1, K, kClassesOutside)) return rc;
+    if (int rc = check_labels(row_of_t, Tn, 0, Dr, kRowsOutside)) return rc;
+    if (C == 0 || Tn == 0) return XMHW_OK;
+    if (!ts || !base || !hist || !n || !s1 || !s2 || !s3 || !s4 || !kmin || !kmax || !n_range)
+        return fail(XMHW_ERR_INVALID, "NULL buffer");
+    RowsRef rows;
+    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
+    RowsRef classes;                                   // the same content-keyed cache: one more int32[T] table
+    if (int rc = upload_table(class_of_t, Tn, "class table upload", &classes)) return rc;
+    return status_of(xmhw::launch_distribution_accumulate<T>(ts, Tn, C, ld, base, ldb, Dr, rows->d_rows, shift, classes->d_rows,
+                                                             K, lo_q, width_q, B, g_distribution_block.load(), hist, n, s1,
+                                                             s2, s3, s4, kmin, kmax, ldo, n_range,
+                                                             static_cast<hipStream_t>(stream)),
+                     "distribution_accumulate launch");
+}
+
+}  // namespace
+
+extern "C" {
+
+int xmhw_set_distribution_block(int32_t steps) { return set_knob(g_distribution_block, steps, "steps must be >= 0"); }
+int xmhw_distribution_init(int32_t K, int32_t B, int64_t C, int32_t* hist, int32_t* n, int64_t* s1, int64_t* s2, int64_t* s3,
+                           int64_t* s4, uint64_t* kmin, uint64_t* kmax, int64_t ldo, int64_t* n_range, void* stream) {
+    if (distribution_check_shape(K, B, 1, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
+    if (!n_range || (C > 0 && (!hist || !n || !s1 || !s2 || !s3 || !s4 || !kmin || !kmax)))
+        return fail(XMHW_ERR_INVALID, "NULL output buffer");
+    return status_of(xmhw::launch_distribution_init(K, B, C, hist, n, s1, s2, s3, s4, kmin, kmax, ldo, n_range,
+                                                    static_cast<hipStream_t>(stream)),
+                     "distribution_init");
+}
+int xmhw_distribution_accumulate_f32(const float* ts, int64_t T, int64_t C, int64_t ld, const double* base, int64_t ldb,
+                                     int64_t Dr, const int32_t* row_of_t, int32_t shift, const int32_t* class_of_t, int32_t K,
+                                     int64_t lo_q, int32_t width_q, int32_t B, int32_t* hist, int32_t* n, int64_t* s1,
+                                     int64_t* s2, int64_t* s3, int64_t* s4, uint64_t* kmin, uint64_t* kmax, int64_t ldo,
+                                     int64_t* n_range, void* stream) {
+    return distribution_accumulate<float>(ts, T, C, ld, base, ldb, Dr, row_of_t, shift, class_of_t, K, lo_q, width_q, B, hist,
+                                          n, s1, s2, s3, s4, kmin, kmax, ldo, n_range, stream);
+}
+int xmhw_distribution_accumulate_f64(const double* ts, int64_t T, int64_t C, int64_t ld, const double* base, int64_t ldb,
+                                     int64_t Dr, const int32_t* row_of_t, int32_t shift, const int32_t* class_of_t, int32_t K,
+                                     int64_t lo_q, int32_t width_q, int32_t B, int32_t* hist, int32_t* n, int64_t* s1,
+                                     int64_t* s2, int64_t* s3, int64_t* s4, uint64_t* kmin, uint64_t* kmax, int64_t ldo,
+                                     int64_t* n_range, void* stream) {
+    return distribution_accumulate<double>(ts, T, C, ld, base, ldb, Dr, row_of_t, shift, class_of_t, K, lo_q, width_q, B, hist,
+                                           n, s1, s2, s3, s4, kmin, kmax, ldo, n_range, stream);
+}
+int xmhw_distribution_finish(int32_t K, int32_t B, int64_t C, const int32_t* hist, const int32_t* n, double* kmin, double* kmax,
+                             const uint64_t* p_q, int32_t P, const int32_t* edge, int32_t L, int32_t* qbin, int32_t* qbelow,
+                             int32_t* qcount, int32_t* n_at_least, int64_t ldo, void* stream) {
+    if (distribution_check_shape(K, B, 1, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (P < 0 || P > xmhw::kDistributionMaxQuantiles)
+        return fail(XMHW_ERR_UNSUPPORTED,
+                    "distribution: P must be in [0, " + std::to_string(xmhw::kDistributionMaxQuantiles) + "]");
+    if (L < 0 || L > xmhw::kDistributionMaxLevels)
+        return fail(XMHW_ERR_UNSUPPORTED, "distribution: L must be in [0, " + std::to_string(xmhw::kDistributionMaxLevels) + "]");
+    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
+    if ((P > 0 && !p_q) || (L > 0 && !edge)) return fail(XMHW_ERR_INVALID, "NULL host table");
+    for (int32_t j = 0; j < P; ++j)
+        if (p_q[j] > (uint64_t{1} << 32)) return fail(XMHW_ERR_INVALID, "p_q outside [0, 2^32]");
+    for (int32_t l = 0; l < L; ++l)
+        if (edge[l] < 0 || edge[l] > B) return fail(XMHW_ERR_INVALID, "edge outside [0, B]");
+    if (C == 0) return XMHW_OK;
+    if (!hist || !n || !kmin || !kmax || (P > 0 && (!qbin || !qbelow || !qcount)) || (L > 0 && !n_at_least))
+        return fail(XMHW_ERR_INVALID, "NULL buffer");
+    return status_of(xmhw::launch_distribution_finish(K, B, C, hist, n, kmin, kmax, p_q, P, edge, L, qbin, qbelow, qcount, n_at_least,
+                                                      ldo, static_cast<hipStream_t>(stream)),
+                     "distribution_finish launch");
+}
+
+}  // extern "C"

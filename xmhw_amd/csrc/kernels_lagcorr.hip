@@ -22,10 +22,24 @@
 //   a block           clears its ring, then stores steps max(0, t0 - L) .. t0 - 1 of y and pushes their validity; it
 //                     reduces and counts nothing from them: blocks are independent.
 //   the counters      the lag group 0 alone counts the out-of-range steps, each once.
+#include "../../include/xmhw_amd.h"
+#include "entry_common.h"
 #include "stage_reduce.h"
 #include "lag_ring.h"
 
 namespace xmhw {
+
+// What the stage computes (lag_ring.h holds the ring): per cell, class of the LATER step and lag l in [0, L], the sums over
+// the pairs (qx(t), qy(t - l)) whose two anomalies are valid -- n int32, sx, sy, sxx, syy, sxy int64, [K][L + 1][ldo],
+// ADDED; the definition is in include/xmhw_amd.h, "lag_correlation()".  y may be x.  n_range[0] counts the steps of class
+// >= 0 whose ax is not NaN and out of range, n_range[1] the steps of any class whose ay is.  row_of_t and class_of_t are
+// DEVICE arrays here.  block_steps: the steps a workgroup takes per block, 0 = automatic; same results for every value.
+constexpr int kLagCorrMaxLag = 63;                   // one validity bit per lag in a 64-bit mask
+constexpr int kLagCorrMaxClasses = 64;
+constexpr int kLagCorrMaxSteps = 1 << 17;            // T below it: 2^17 * 2^46 = 2^63
+constexpr int kLagCorrBits = 16;
+constexpr int kLagCorrRangeBits = 7;
+constexpr int kLagCorrMaxShift = 24;
 
 static_assert(kLagCorrBits == kFixedBits && kLagCorrRangeBits == kFixedRangeBits, "one scale for every stage");
 static_assert(kLagCorrMaxLag == kLagRingMaxLag, "the mask holds one bit per lag");
@@ -198,8 +212,6 @@ void lc_launch(const LcIn<T>& in, int64_t Tn, int64_t C, const int32_t* class_of
                        0, stream, in, Tn, C, class_of_t, K, L, tb, out);
 }
 
-}  // namespace
-
 hipError_t launch_lag_corr_init(int32_t K, int32_t L, int64_t C, int32_t* n, int64_t* sx, int64_t* sy, int64_t* sxx,
                                 int64_t* syy, int64_t* sxy, int64_t ldo, int64_t* n_range, hipStream_t stream) {
     hipError_t e = hipMemsetAsync(n_range, 0, 2 * sizeof(int64_t), stream);
@@ -240,15 +252,83 @@ hipError_t launch_lag_corr_accumulate(const T* x, int64_t ldx, const T* y, int64
     return hipGetLastError();
 }
 
-template hipError_t launch_lag_corr_accumulate<float>(const float*, int64_t, const float*, int64_t, int64_t, int64_t,
-                                                      const double*, int64_t, const double*, int64_t, int64_t, const int32_t*,
-                                                      int32_t, int32_t, const int32_t*, int32_t, int32_t, int64_t, int32_t*,
-                                                      int64_t*, int64_t*, int64_t*, int64_t*, int64_t*, int64_t, int64_t*,
-                                                      hipStream_t);
-template hipError_t launch_lag_corr_accumulate<double>(const double*, int64_t, const double*, int64_t, int64_t, int64_t,
-                                                       const double*, int64_t, const double*, int64_t, int64_t, const int32_t*,
-                                                       int32_t, int32_t, const int32_t*, int32_t, int32_t, int64_t, int32_t*,
-                                                       int64_t*, int64_t*, int64_t*, int64_t*, int64_t*, int64_t, int64_t*,
-                                                       hipStream_t);
+}  // namespace
 
 }  // namespace xmhw
+
+// ---- the C entries of lag_correlation() (include/xmhw_amd.h) ----------------------------------------------------------
+namespace {
+
+using namespace xmhw::entry;
+
+static std::atomic<int> g_lag_corr_block{0};    // steps a workgroup takes per block, 0 = automatic (xmhw_set_lag_corr_block)
+
+static int lag_corr_check_shape(int32_t K, int32_t L, int32_t shift_x, int32_t shift_y, int64_t Tn, int64_t C) {
+    if (K < 1 || K > xmhw::kLagCorrMaxClasses)
+        return fail(XMHW_ERR_UNSUPPORTED, "lag_corr: K must be in [1, " + std::to_string(xmhw::kLagCorrMaxClasses) + "]");
+    if (L < 0 || L > xmhw::kLagCorrMaxLag)
+        return fail(XMHW_ERR_UNSUPPORTED, "lag_corr: max_lag must be in [0, " + std::to_string(xmhw::kLagCorrMaxLag) + "]");
+    if (shift_x < 0 || shift_x > xmhw::kLagCorrMaxShift || shift_y < 0 || shift_y > xmhw::kLagCorrMaxShift)
+        return fail(XMHW_ERR_UNSUPPORTED, "lag_corr: shifts must be in [0, " + std::to_string(xmhw::kLagCorrMaxShift) + "]");
+    if (Tn >= xmhw::kLagCorrMaxSteps) return fail(XMHW_ERR_UNSUPPORTED, "lag_corr: 2^17 steps and more");
+    if (C > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "lag_corr: 2^31 cells and more");
+    return XMHW_OK;
+}
+
+template <typename T>
+int lag_corr_accumulate(const T* x, int64_t ldx, const T* y, int64_t ldy, int64_t Tn, int64_t C, const double* base_x,
+                        int64_t ldbx, const double* base_y, int64_t ldby, int64_t Dr, const int32_t* row_of_t, int32_t shift_x,
+                        int32_t shift_y, const int32_t* class_of_t, int32_t K, int32_t max_lag, int32_t* n, int64_t* sx,
+                        int64_t* sy, int64_t* sxx, int64_t* syy, int64_t* sxy, int64_t ldo, int64_t* n_range, void* stream) {
+    if (lag_corr_check_shape(K, max_lag, shift_x, shift_y, Tn, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (Tn < 0 || C < 0 || ldx < C || ldy < C || ldbx < C || ldby < C || ldo < C || Dr < 1)
+        return fail(XMHW_ERR_INVALID, "bad T/C/ldx/ldy/ldbx/ldby/ldo/D");
+    if (Tn > 0 && (!class_of_t || !row_of_t)) return fail(XMHW_ERR_INVALID, "NULL host table");
+    if (int rc = check_labels(class_of_t, Tn, -1, K, kClassesOutside)) return rc;
+    if (int rc = check_labels(row_of_t, Tn, 0, Dr, kRowsOutside)) return rc;
+    if (C == 0 || Tn == 0) return XMHW_OK;
+    if (!x || !y || !base_x || !base_y || !n || !sx || !sy || !sxx || !syy || !sxy || !n_range)
+        return fail(XMHW_ERR_INVALID, "NULL buffer");
+    RowsRef rows;
+    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
+    RowsRef classes;                                   // the same content-keyed cache: one more int32[T] table
+    if (int rc = upload_table(class_of_t, Tn, "class table upload", &classes)) return rc;
+    return status_of(xmhw::launch_lag_corr_accumulate<T>(x, ldx, y, ldy, Tn, C, base_x, ldbx, base_y, ldby, Dr, rows->d_rows,
+                                                         shift_x, shift_y, classes->d_rows, K, max_lag,
+                                                         g_lag_corr_block.load(), n, sx, sy, sxx, syy, sxy, ldo, n_range,
+                                                         static_cast<hipStream_t>(stream)),
+                     "lag_corr_accumulate launch");
+}
+
+}  // namespace
+
+extern "C" {
+
+int xmhw_set_lag_corr_block(int32_t steps) { return set_knob(g_lag_corr_block, steps, "steps must be >= 0"); }
+int xmhw_lag_corr_init(int32_t K, int32_t max_lag, int64_t C, int32_t* n, int64_t* sx, int64_t* sy, int64_t* sxx, int64_t* syy,
+                       int64_t* sxy, int64_t ldo, int64_t* n_range, void* stream) {
+    if (lag_corr_check_shape(K, max_lag, 0, 0, 1, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
+    if (!n_range || (C > 0 && (!n || !sx || !sy || !sxx || !syy || !sxy))) return fail(XMHW_ERR_INVALID, "NULL output buffer");
+    return status_of(xmhw::launch_lag_corr_init(K, max_lag, C, n, sx, sy, sxx, syy, sxy, ldo, n_range,
+                                                static_cast<hipStream_t>(stream)),
+                     "lag_corr_init");
+}
+int xmhw_lag_corr_accumulate_f32(const float* x, int64_t ldx, const float* y, int64_t ldy, int64_t T, int64_t C,
+                                 const double* base_x, int64_t ldbx, const double* base_y, int64_t ldby, int64_t Dr,
+                                 const int32_t* row_of_t, int32_t shift_x, int32_t shift_y, const int32_t* class_of_t, int32_t K,
+                                 int32_t max_lag, int32_t* n, int64_t* sx, int64_t* sy, int64_t* sxx, int64_t* syy, int64_t* sxy,
+                                 int64_t ldo, int64_t* n_range, void* stream) {
+    return lag_corr_accumulate<float>(x, ldx, y, ldy, T, C, base_x, ldbx, base_y, ldby, Dr, row_of_t, shift_x, shift_y,
+                                      class_of_t, K, max_lag, n, sx, sy, sxx, syy, sxy, ldo, n_range, stream);
+}
+int xmhw_lag_corr_accumulate_f64(const double* x, int64_t ldx, const double* y, int64_t ldy, int64_t T, int64_t C,
+                                 const double* base_x, int64_t ldbx, const double* base_y, int64_t ldby, int64_t Dr,
+                                 const int32_t* row_of_t, int32_t shift_x, int32_t shift_y, const int32_t* class_of_t, int32_t K,
+                                 int32_t max_lag, int32_t* n, int64_t* sx, int64_t* sy, int64_t* sxx, int64_t* syy, int64_t* sxy,
+                                 int64_t ldo, int64_t* n_range, void* stream) {
+    return lag_corr_accumulate<double>(x, ldx, y, ldy, T, C, base_x, ldbx, base_y, ldby, Dr, row_of_t, shift_x, shift_y,
+                                       class_of_t, K, max_lag, n, sx, sy, sxx, syy, sxy, ldo, n_range, stream);
+}
+
+}  // extern "C"

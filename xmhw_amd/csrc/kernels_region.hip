@@ -22,9 +22,18 @@
 //                      that hold a step's total (A, B) or all lanes (C) add to global memory directly.
 //                      *n_range is summed in the workgroup and added once per workgroup when non-zero.
 // All sums are integers: the result does not depend on the order of the adds, the tiling or the slabs.
+#include "../../include/xmhw_amd.h"
+#include "entry_common.h"
 #include "stage_reduce.h"
 
 namespace xmhw {
+
+// What the stage computes: region_accumulate ADDS, for every step t and region r < R, over the cells c with
+// region[c] == r whose sample is not NaN: acc[t][r][0] += 1, acc[t][r][1] += wi[c], acc[t][r][2] += wi[c] *
+// rint(((double)ts[t][c] - x0) * 2^16); a valid sample with |ts - x0| >= 2^7 or infinite is left out and counted in
+// *n_range.  region[c] in [-1, R), -1 = the cell counts nowhere; R <= kRegionMaxRegions.  blocked selects how a wave sums:
+// 0 = one wave sum per step, 1 = the sums of 8 steps together (below).  Same results.
+constexpr int kRegionMaxRegions = 1024;
 
 namespace {
 
@@ -259,8 +268,6 @@ __global__ __launch_bounds__(kRegThreads) void region_accumulate(const T* __rest
     if (threadIdx.x == 0 && lrange) atomicAdd(n_range, lrange);
 }
 
-}  // namespace
-
 template <typename T>
 hipError_t launch_region_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, double x0, const int64_t* wi,
                                     const int32_t* region, int32_t R, int64_t* acc, int64_t* n_range, int32_t blocked,
@@ -288,9 +295,49 @@ hipError_t launch_region_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t 
     return hipGetLastError();
 }
 
-template hipError_t launch_region_accumulate<float>(const float*, int64_t, int64_t, int64_t, double, const int64_t*,
-                                                    const int32_t*, int32_t, int64_t*, int64_t*, int32_t, hipStream_t);
-template hipError_t launch_region_accumulate<double>(const double*, int64_t, int64_t, int64_t, double, const int64_t*,
-                                                     const int32_t*, int32_t, int64_t*, int64_t*, int32_t, hipStream_t);
+}  // namespace
 
 }  // namespace xmhw
+
+// ---- the C entries of region_series() (include/xmhw_amd.h) ------------------------------------------------------------
+namespace {
+
+using namespace xmhw::entry;
+
+static std::atomic<int> g_region_wave_sum{1};   // region_accumulate sums 8 steps of a wave together (xmhw_set_region_wave_sum)
+
+template <typename T>
+int region_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, double x0, const int64_t* wi, const int32_t* region,
+                      int32_t R, int64_t* acc, int64_t* n_range, void* stream) {
+    if (Tn < 0 || C < 0 || ld < C) return fail(XMHW_ERR_INVALID, "bad T/C/ld");
+    if (Tn >= (int64_t{1} << 31)) return fail(XMHW_ERR_INVALID, "T too large");
+    if (R < 1) return fail(XMHW_ERR_INVALID, "R must be >= 1");
+    if (R > xmhw::kRegionMaxRegions)
+        return fail(XMHW_ERR_UNSUPPORTED, "region_accumulate: R above the cap of " + std::to_string(xmhw::kRegionMaxRegions) + " regions");
+    if (!(x0 == x0) || std::isinf(x0)) return fail(XMHW_ERR_INVALID, "x0 must be finite");
+    if (C == 0 || Tn == 0) return XMHW_OK;
+    if (!ts || !wi || !region || !acc || !n_range) return fail(XMHW_ERR_INVALID, "NULL buffer");
+    return status_of(xmhw::launch_region_accumulate<T>(ts, Tn, C, ld, x0, wi, region, R, acc, n_range,
+                                                       g_region_wave_sum.load(), static_cast<hipStream_t>(stream)),
+                     "region_accumulate launch");
+}
+
+}  // namespace
+
+extern "C" {
+
+int xmhw_set_region_wave_sum(int32_t variant) {
+    if (variant != 0 && variant != 1) return fail(XMHW_ERR_INVALID, "variant must be 0 or 1");
+    g_region_wave_sum = variant;
+    return XMHW_OK;
+}
+int xmhw_region_accumulate_f32(const float* ts, int64_t T, int64_t C, int64_t ld, double x0, const int64_t* wi,
+                               const int32_t* region, int32_t R, int64_t* acc, int64_t* n_range, void* stream) {
+    return region_accumulate<float>(ts, T, C, ld, x0, wi, region, R, acc, n_range, stream);
+}
+int xmhw_region_accumulate_f64(const double* ts, int64_t T, int64_t C, int64_t ld, double x0, const int64_t* wi,
+                               const int32_t* region, int32_t R, int64_t* acc, int64_t* n_range, void* stream) {
+    return region_accumulate<double>(ts, T, C, ld, x0, wi, region, R, acc, n_range, stream);
+}
+
+}  // extern "C"

@@ -32,9 +32,28 @@
 //   the lag-1 pair    kprev = the class of the previous step if that step was valid, -1 otherwise (per lane), qprev its
 //                     q.  A block that starts at t0 > 0 derives both from step t0 - 1, which it reads once and reduces
 //                     nowhere: blocks are independent.
+#include "../../include/xmhw_amd.h"
+#include "entry_common.h"
 #include "stage_reduce.h"
 
 namespace xmhw {
+
+// What the stage computes: the sums behind lagged regression maps of anomalies on indices.  With
+// a = sample - base[row_of_t[t]][c], the step VALID iff a is not NaN and |a| < 2^7, q = rint(a * 2^kIndexRegressBits) on
+// valid steps, and the predictor row zq[t][0..J) of the step, launch_index_regress_accumulate ADDS per class k of the step
+// and cell c: over the valid steps n[k][c] += 1, sa += q, saa += q^2, saz[k][j][c] += q * zq[t][j]; over the valid steps
+// whose step t - 1 is valid and of class k as well n1 += 1, saa1 += q(t) q(t - 1); over the steps of class k that are NOT
+// valid mz[k][j][c] += zq[t][j], mzz[k][j][c] += zq[t][j]^2; and counts the non-NaN a with |a| >= 2^7 of the steps with a
+// class in *n_range.  Cells are the fastest axis, leading dimension ldo >= C.  row_of_t and class_of_t are DEVICE arrays
+// here, and so is zq: int32 [T][G], step-major, G = index_regress_group(J) columns of which those past J are zero.
+// block_steps: the steps a workgroup takes per block, 0 = automatic; same results for every value.
+constexpr int kIndexRegressMaxPredictors = 32;
+constexpr int kIndexRegressMaxClasses = 64;
+constexpr int kIndexRegressMaxSteps = 1 << 17;       // T below it: 2^17 * 2^23 * 2^23 = 2^63
+constexpr int kIndexRegressBits = 16;
+constexpr int kIndexRegressPredictorBits = 23;       // |zq| < 2^23
+// the predictor columns of the kernel instantiation that takes J predictors: 4, 8, 16 or 32
+inline int index_regress_group(int32_t J) { return J <= 4 ? 4 : J <= 8 ? 8 : J <= 16 ? 16 : 32; }
 
 static_assert(kIndexRegressBits == kFixedBits, "one scale for every stage");
 
@@ -205,8 +224,6 @@ void ir_launch(const IrIn<T>& in, int64_t Tn, int64_t C, const int32_t* class_of
                        C, class_of_t, K, zq, tb, out);
 }
 
-}  // namespace
-
 hipError_t launch_index_regress_init(int32_t K, int32_t J, int64_t C, int32_t* n, int64_t* sa, int64_t* saa, int32_t* n1,
                                      int64_t* saa1, int64_t* saz, int64_t* mz, int64_t* mzz, int64_t ldo, int64_t* n_range,
                                      hipStream_t stream) {
@@ -241,13 +258,91 @@ hipError_t launch_index_regress_accumulate(const T* ts, int64_t Tn, int64_t C, i
     return hipGetLastError();
 }
 
-template hipError_t launch_index_regress_accumulate<float>(const float*, int64_t, int64_t, int64_t, const double*, int64_t,
-                                                           int64_t, const int32_t*, const int32_t*, int32_t, const int32_t*,
-                                                           int32_t, int64_t, int32_t*, int64_t*, int64_t*, int32_t*, int64_t*,
-                                                           int64_t*, int64_t*, int64_t*, int64_t, int64_t*, hipStream_t);
-template hipError_t launch_index_regress_accumulate<double>(const double*, int64_t, int64_t, int64_t, const double*, int64_t,
-                                                            int64_t, const int32_t*, const int32_t*, int32_t, const int32_t*,
-                                                            int32_t, int64_t, int32_t*, int64_t*, int64_t*, int32_t*, int64_t*,
-                                                            int64_t*, int64_t*, int64_t*, int64_t, int64_t*, hipStream_t);
+}  // namespace
 
 }  // namespace xmhw
+
+// ---- the C entries of index_regression() (include/xmhw_amd.h) ---------------------------------------------------------
+namespace {
+
+using namespace xmhw::entry;
+
+static std::atomic<int> g_index_regress_block{0};   // steps a workgroup takes per block, 0 = automatic (xmhw_set_index_regress_block)
+
+static int index_regress_check_shape(int32_t K, int32_t J, int64_t Tn, int64_t C) {
+    if (K < 1 || K > xmhw::kIndexRegressMaxClasses)
+        return fail(XMHW_ERR_UNSUPPORTED,
+                    "index_regress: K must be in [1, " + std::to_string(xmhw::kIndexRegressMaxClasses) + "]");
+    if (J < 1 || J > xmhw::kIndexRegressMaxPredictors)
+        return fail(XMHW_ERR_UNSUPPORTED,
+                    "index_regress: J must be in [1, " + std::to_string(xmhw::kIndexRegressMaxPredictors) + "]");
+    if (Tn >= xmhw::kIndexRegressMaxSteps) return fail(XMHW_ERR_UNSUPPORTED, "index_regress: 2^17 steps and more");
+    if (C > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "index_regress: 2^31 cells and more");
+    return XMHW_OK;
+}
+
+template <typename T>
+int index_regress_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* base, int64_t ldb, int64_t D,
+                             const int32_t* row_of_t, const int32_t* class_of_t, int32_t K, const int32_t* zq, int32_t J,
+                             int32_t* n, int64_t* sa, int64_t* saa, int32_t* n1, int64_t* saa1, int64_t* saz, int64_t* mz,
+                             int64_t* mzz, int64_t ldo, int64_t* n_range, void* stream) {
+    if (index_regress_check_shape(K, J, Tn, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (Tn <= 0 || C < 0 || ld < C || ldb < C || ldo < C || D < 1) return fail(XMHW_ERR_INVALID, "bad T/C/ld/ldb/ldo/D");
+    if (!class_of_t || !row_of_t || !zq) return fail(XMHW_ERR_INVALID, "NULL host table");
+    if (int rc = check_labels(class_of_t, Tn, -1, K, kClassesOutside)) return rc;
+    if (int rc = check_labels(row_of_t, Tn, 0, D, kRowsOutside)) return rc;
+    constexpr int32_t zlim = 1 << xmhw::kIndexRegressPredictorBits;
+    if (int rc = check_labels(zq, Tn * J, -zlim + 1, zlim, "zq outside (-2^23, 2^23)")) return rc;
+    if (C == 0) return XMHW_OK;
+    if (!ts || !base || !n || !sa || !saa || !n1 || !saa1 || !saz || !mz || !mzz || !n_range)
+        return fail(XMHW_ERR_INVALID, "NULL buffer");
+    RowsRef rows;
+    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
+    RowsRef classes;                                   // the same content-keyed cache: one more int32[T] table
+    if (int rc = upload_table(class_of_t, Tn, "class table upload", &classes)) return rc;
+    // ... and the predictors, step-major, J padded with zero columns to the kernel's group: int32[T][G]
+    const int G = xmhw::index_regress_group(J);
+    std::vector<int32_t> padded(static_cast<size_t>(Tn) * G, 0);
+    for (int64_t t = 0; t < Tn; ++t) std::copy(zq + t * J, zq + (t + 1) * J, padded.begin() + t * G);
+    RowsRef predictors;
+    if (int rc = upload_table(padded.data(), Tn * G, "predictor table upload", &predictors)) return rc;
+    return status_of(xmhw::launch_index_regress_accumulate<T>(ts, Tn, C, ld, base, ldb, D, rows->d_rows, classes->d_rows, K,
+                                                              predictors->d_rows, J, g_index_regress_block.load(), n, sa, saa,
+                                                              n1, saa1, saz, mz, mzz, ldo, n_range,
+                                                              static_cast<hipStream_t>(stream)),
+                     "index_regress_accumulate launch");
+}
+
+}  // namespace
+
+extern "C" {
+
+int xmhw_set_index_regress_block(int32_t steps) { return set_knob(g_index_regress_block, steps, "steps must be >= 0"); }
+int xmhw_index_regress_init(int32_t K, int32_t J, int64_t C, int32_t* n, int64_t* sa, int64_t* saa, int32_t* n1, int64_t* saa1,
+                            int64_t* saz, int64_t* mz, int64_t* mzz, int64_t ldo, int64_t* n_range, void* stream) {
+    if (index_regress_check_shape(K, J, 1, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
+    if (!n_range || (C > 0 && (!n || !sa || !saa || !n1 || !saa1 || !saz || !mz || !mzz)))
+        return fail(XMHW_ERR_INVALID, "NULL output buffer");
+    return status_of(xmhw::launch_index_regress_init(K, J, C, n, sa, saa, n1, saa1, saz, mz, mzz, ldo, n_range,
+                                                     static_cast<hipStream_t>(stream)),
+                     "index_regress_init");
+}
+int xmhw_index_regress_accumulate_f32(const float* ts, int64_t T, int64_t C, int64_t ld, const double* base, int64_t ldb,
+                                      int64_t D, const int32_t* row_of_t, const int32_t* class_of_t, int32_t K,
+                                      const int32_t* zq, int32_t J, int32_t* n, int64_t* sa, int64_t* saa, int32_t* n1,
+                                      int64_t* saa1, int64_t* saz, int64_t* mz, int64_t* mzz, int64_t ldo, int64_t* n_range,
+                                      void* stream) {
+    return index_regress_accumulate<float>(ts, T, C, ld, base, ldb, D, row_of_t, class_of_t, K, zq, J, n, sa, saa, n1, saa1,
+                                           saz, mz, mzz, ldo, n_range, stream);
+}
+int xmhw_index_regress_accumulate_f64(const double* ts, int64_t T, int64_t C, int64_t ld, const double* base, int64_t ldb,
+                                      int64_t D, const int32_t* row_of_t, const int32_t* class_of_t, int32_t K,
+                                      const int32_t* zq, int32_t J, int32_t* n, int64_t* sa, int64_t* saa, int32_t* n1,
+                                      int64_t* saa1, int64_t* saz, int64_t* mz, int64_t* mzz, int64_t ldo, int64_t* n_range,
+                                      void* stream) {
+    return index_regress_accumulate<double>(ts, T, C, ld, base, ldb, D, row_of_t, class_of_t, K, zq, J, n, sa, saa, n1, saa1,
+                                            saz, mz, mzz, ldo, n_range, stream);
+}
+
+}  // extern "C"

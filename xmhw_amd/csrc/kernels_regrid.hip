@@ -26,10 +26,28 @@
 //                     takes it where it measured faster (regrid_auto_staged).
 //   the sums          separable: per source row sw = sum ax, sx = sum ax * xq over the lane's columns (|sx| <= 2^41), then
 //                     wsum += ay * sw, xsum += ay * sx; a row with ay = 0 is skipped (uniform).
+#include <cstring>
+
+#include "../../include/xmhw_amd.h"
+#include "entry_common.h"
 #include "stage_reduce.h"
 #include "regrid_index.h"
 
 namespace xmhw {
+
+// What the stage computes (regrid_index.h holds the index rules): first-order conservative remapping of the UNCOMPACTED
+// ny x nx series at ts
+// onto the my x mx destination grid under two CSR overlap tables -- out [nt][ldo] in the sample type, WRITTEN; wsum int64 and
+// n int32 likewise where not NULL; *n_range ADDED to; the definition is in include/xmhw_amd.h, "regrid()".  table_dev is the
+// ONE device table that holds the ten int32 tables of the call at the places `lay` names (regrid_layout); max_rows, max_cols
+// the longest run per axis and max_width the widest tile span (regrid_max_width), taken from the host tables.  variant:
+// kRegridVariantAuto, Direct or Staged (staged where the footprint fits, tests and measurements); chunk_steps: the steps a
+// workgroup takes per chunk, 0 = automatic (regrid_auto_chunk); same results for every value of either.
+constexpr int kRegridBits = 16;
+constexpr int kRegridRangeBits = 7;
+constexpr int kRegridVariantAuto = 0;
+constexpr int kRegridVariantDirect = 1;
+constexpr int kRegridVariantStaged = 2;
 
 static_assert(kRegridBits == kFixedBits && kRegridRangeBits == kFixedRangeBits, "one scale for every stage");
 
@@ -221,8 +239,6 @@ hipError_t rg_launch_kx(int32_t max_cols, const RgIn<T>& in, const RgOut<T>& out
     return rg_launch<T, 0, STAGED>(in, out, lds_bytes, stream);
 }
 
-}  // namespace
-
 template <typename T>
 hipError_t launch_regrid(const T* ts, int64_t nt, int64_t ld, int32_t ny, int32_t nx, int32_t my, int32_t mx,
                          const int32_t* table_dev, const RegridLayout& lay, int32_t max_rows, int32_t max_cols,
@@ -249,12 +265,162 @@ hipError_t launch_regrid(const T* ts, int64_t nt, int64_t ld, int32_t ny, int32_
     return rg_launch_kx<T, false>(max_cols, in, o, 0, stream);
 }
 
-#define XMHW_RG_INSTANCE(T)                                                                                                  \
-    template hipError_t launch_regrid<T>(const T*, int64_t, int64_t, int32_t, int32_t, int32_t, int32_t, const int32_t*,        \
-                                         const RegridLayout&, int32_t, int32_t, int32_t, int32_t, double, int32_t, int32_t,    \
-                                         int64_t, T*, int64_t, int64_t*, int32_t*, int64_t*, hipStream_t)
-XMHW_RG_INSTANCE(float);
-XMHW_RG_INSTANCE(double);
-#undef XMHW_RG_INSTANCE
+}  // namespace
 
 }  // namespace xmhw
+
+// ---- the C entries of regrid() (include/xmhw_amd.h) -------------------------------------------------------------------
+namespace {
+
+using namespace xmhw::entry;
+
+static std::atomic<int> g_regrid_variant{0};       // the path regrid() takes, 0 = automatic (xmhw_set_regrid_variant)
+static std::atomic<int> g_regrid_chunk{0};         // steps a workgroup takes per chunk, 0 = automatic (xmhw_set_regrid_chunk)
+
+static_assert(XMHW_REGRID_MAX_RUN == xmhw::kRegridMaxRun && XMHW_REGRID_MAX_WEIGHT == xmhw::kRegridMaxWeight &&
+                  XMHW_REGRID_MAX_EXTENT == xmhw::kRegridMaxExtent && XMHW_REGION_SERIES_BITS == xmhw::kRegridBits,
+              "the public limits of regrid() are the kernel's");
+
+// one axis of a regrid() call: m destination runs over n source points
+struct RegridAxis {
+    const int32_t *first, *ptr, *w, *full;
+    int32_t m, n;
+    bool periodic;
+    const char* name;
+};
+// can the tables be read as CSR tables: all there, the pointers from 0 and non-decreasing?
+bool regrid_axis_readable(const RegridAxis& x) {
+    if (x.m < 0) return false;
+    if (x.m == 0) return true;
+    if (!x.first || !x.ptr || !x.full || x.ptr[0] != 0) return false;
+    for (int32_t k = 0; k < x.m; ++k)
+        if (x.ptr[k + 1] < x.ptr[k]) return false;
+    return x.ptr[x.m] == 0 || x.w;
+}
+// the caps of an axis (of tables that can be read): "" or what is above them
+std::string regrid_axis_cap(const RegridAxis& x) {
+    if (!regrid_axis_readable(x)) return "";
+    for (int32_t k = 0; k < x.m; ++k) {
+        if (x.ptr[k + 1] - x.ptr[k] > xmhw::kRegridMaxRun)
+            return std::string("regrid: a ") + x.name + " run of more than " + std::to_string(xmhw::kRegridMaxRun) + " entries";
+        if (x.full[k] > xmhw::kRegridMaxExtent) return std::string("regrid: a ") + x.name + " extent above 2^18";
+    }
+    for (int32_t e = 0; e < x.ptr[x.m]; ++e)
+        if (x.w[e] > xmhw::kRegridMaxWeight) return std::string("regrid: a ") + x.name + " weight above 2^12";
+    return "";
+}
+// the shape of an axis: "" or what is malformed
+std::string regrid_axis_bad(const RegridAxis& x) {
+    if (!regrid_axis_readable(x)) return std::string("regrid: bad ") + x.name + " tables (NULL, or pointers not from 0 and non-decreasing)";
+    for (int32_t k = 0; k < x.m; ++k) {
+        const int64_t cnt = x.ptr[k + 1] - x.ptr[k];
+        int64_t sum = 0;
+        for (int32_t e = x.ptr[k]; e < x.ptr[k + 1]; ++e) {
+            if (x.w[e] < 0) return std::string("regrid: a negative ") + x.name + " weight";
+            sum += x.w[e];
+        }
+        if (sum > x.full[k]) return std::string("regrid: the ") + x.name + " weights of a run exceed its extent";
+        const int64_t first = x.first[k];
+        const bool inside = x.periodic ? first >= 0 && first < x.n && cnt <= x.n : first >= 0 && first + cnt <= x.n;
+        if (cnt > 0 && !inside) return std::string("regrid: a ") + x.name + " run leaves the source grid";
+    }
+    return "";
+}
+
+template <typename T>
+int regrid(const T* ts, int64_t nt, int64_t ld, int32_t ny, int32_t nx, int32_t my, int32_t mx, const int32_t* row_first,
+           const int32_t* row_ptr, const int32_t* ay, const int32_t* wy, const int32_t* col_first, const int32_t* col_ptr,
+           const int32_t* ax, const int32_t* wx, int32_t periodic, double x0, int32_t a, T* out, int64_t ldo, int64_t* wsum,
+           int32_t* n, int64_t* n_range, void* stream) {
+    const RegridAxis rows{row_first, row_ptr, ay, wy, my, ny, false, "row"};
+    const RegridAxis cols{col_first, col_ptr, ax, wx, mx, nx, periodic != 0, "column"};
+    // the caps, over the tables that can be read
+    for (const RegridAxis* x : {&rows, &cols}) {
+        const std::string cap = regrid_axis_cap(*x);
+        if (!cap.empty()) return fail(XMHW_ERR_UNSUPPORTED, cap);
+    }
+    if ((ny > 0 && nx > 0 && static_cast<int64_t>(ny) * nx > INT32_MAX) || (my > 0 && mx > 0 && static_cast<int64_t>(my) * mx > INT32_MAX))
+        return fail(XMHW_ERR_UNSUPPORTED, "regrid: a grid of 2^31 points and more");
+    if (nt < 0 || ny < 0 || nx < 0 || ld < static_cast<int64_t>(ny) * nx) return fail(XMHW_ERR_INVALID, "bad nt/ny/nx/ld");
+    if (my < 0 || mx < 0 || ldo < static_cast<int64_t>(my) * mx) return fail(XMHW_ERR_INVALID, "bad my/mx/ldo");
+    for (const RegridAxis* x : {&rows, &cols}) {
+        const std::string bad = regrid_axis_bad(*x);
+        if (!bad.empty()) return fail(XMHW_ERR_INVALID, bad);
+    }
+    if (a < 0 || a > 65536) return fail(XMHW_ERR_INVALID, "regrid: a must be in [0, 65536]");
+    if (!std::isfinite(x0)) return fail(XMHW_ERR_INVALID, "regrid: x0 must be finite");
+    if (nt == 0 || my == 0 || mx == 0) return XMHW_OK;
+    if (!ts || !out || !n_range) return fail(XMHW_ERR_INVALID, "NULL buffer");
+    // the ten tables as one: one upload, one cache slot, reused by the time blocks of a call
+    const xmhw::RegridLayout lay = xmhw::regrid_layout(my, mx, row_ptr[my], col_ptr[mx]);
+    std::vector<int32_t> packed(static_cast<size_t>(lay.total), 0);
+    const auto put = [&](int64_t at, const int32_t* src, int64_t count) {
+        if (count > 0) std::memcpy(packed.data() + at, src, sizeof(int32_t) * static_cast<size_t>(count));
+    };
+    put(lay.row_first, row_first, my);
+    put(lay.row_ptr, row_ptr, static_cast<int64_t>(my) + 1);
+    put(lay.ay, ay, row_ptr[my]);
+    put(lay.wy, wy, my);
+    put(lay.col_first, col_first, mx);
+    put(lay.col_ptr, col_ptr, static_cast<int64_t>(mx) + 1);
+    put(lay.ax, ax, col_ptr[mx]);
+    put(lay.wx, wx, mx);
+    int32_t max_width = 0;
+    for (int32_t I0 = 0; I0 < mx; I0 += xmhw::kRegridTile) {
+        const xmhw::RegridSpan sp = xmhw::regrid_tile_span(col_first, col_ptr, mx, nx, periodic != 0, I0);
+        packed[static_cast<size_t>(lay.tile_c0 + I0 / xmhw::kRegridTile)] = sp.c0;
+        packed[static_cast<size_t>(lay.tile_w + I0 / xmhw::kRegridTile)] = sp.width;
+        max_width = std::max(max_width, sp.width);
+    }
+    RowsRef table;
+    if (int rc = upload_table(packed.data(), lay.total, "overlap table upload", &table)) return rc;
+    return status_of(xmhw::launch_regrid<T>(ts, nt, ld, ny, nx, my, mx, table->d_rows, lay, xmhw::regrid_max_run(row_ptr, my),
+                                            xmhw::regrid_max_run(col_ptr, mx), max_width, periodic != 0, x0, a,
+                                            g_regrid_variant.load(), g_regrid_chunk.load(), out, ldo, wsum, n, n_range,
+                                            static_cast<hipStream_t>(stream)),
+                     "regrid launch");
+}
+
+}  // namespace
+
+extern "C" {
+
+int xmhw_set_regrid_variant(int32_t variant) {
+    if (variant < xmhw::kRegridVariantAuto || variant > xmhw::kRegridVariantStaged)
+        return fail(XMHW_ERR_INVALID, "variant must be 0, 1 or 2");
+    g_regrid_variant = variant;
+    return XMHW_OK;
+}
+int xmhw_set_regrid_chunk(int32_t steps) { return set_knob(g_regrid_chunk, steps, "steps must be >= 0"); }
+int xmhw_regrid_class(int32_t nx, int32_t my, int32_t mx, const int32_t* row_ptr, const int32_t* col_first, const int32_t* col_ptr,
+                      int32_t periodic) {
+    const RegridAxis rows{nullptr, row_ptr, nullptr, nullptr, my, 0, false, "row"};
+    const RegridAxis cols{col_first, col_ptr, nullptr, nullptr, mx, nx, periodic != 0, "column"};
+    // (the pointer tables alone: first, weights and extents are not read for the row axis)
+    if (my < 0 || mx < 0 || nx < 1 || (my > 0 && !row_ptr) || (mx > 0 && (!col_ptr || !col_first))) return xmhw::kRegridNone;
+    for (const RegridAxis* x : {&rows, &cols})
+        for (int32_t k = 0; k < x->m; ++k)
+            if (x->ptr[k + 1] < x->ptr[k] || x->ptr[k + 1] - x->ptr[k] > xmhw::kRegridMaxRun) return xmhw::kRegridNone;
+    for (int32_t I = 0; I < mx; ++I) {
+        const int64_t cnt = col_ptr[I + 1] - col_ptr[I], first = col_first[I];
+        if (cnt > 0 && !(periodic ? first >= 0 && first < nx && cnt <= nx : first >= 0 && first + cnt <= nx)) return xmhw::kRegridNone;
+    }
+    return xmhw::regrid_class(xmhw::regrid_max_run(row_ptr, my), xmhw::regrid_max_width(col_first, col_ptr, mx, nx, periodic != 0),
+                              mx < xmhw::kRegridTile ? mx : xmhw::kRegridTile, nx, periodic != 0, g_regrid_variant.load());
+}
+int xmhw_regrid_f32(const float* ts, int64_t nt, int64_t ld, int32_t ny, int32_t nx, int32_t my, int32_t mx,
+                    const int32_t* row_first, const int32_t* row_ptr, const int32_t* ay, const int32_t* wy,
+                    const int32_t* col_first, const int32_t* col_ptr, const int32_t* ax, const int32_t* wx, int32_t periodic,
+                    double x0, int32_t a, float* out, int64_t ldo, int64_t* wsum, int32_t* n, int64_t* n_range, void* stream) {
+    return regrid<float>(ts, nt, ld, ny, nx, my, mx, row_first, row_ptr, ay, wy, col_first, col_ptr, ax, wx, periodic, x0, a, out,
+                         ldo, wsum, n, n_range, stream);
+}
+int xmhw_regrid_f64(const double* ts, int64_t nt, int64_t ld, int32_t ny, int32_t nx, int32_t my, int32_t mx,
+                    const int32_t* row_first, const int32_t* row_ptr, const int32_t* ay, const int32_t* wy,
+                    const int32_t* col_first, const int32_t* col_ptr, const int32_t* ax, const int32_t* wx, int32_t periodic,
+                    double x0, int32_t a, double* out, int64_t ldo, int64_t* wsum, int32_t* n, int64_t* n_range, void* stream) {
+    return regrid<double>(ts, nt, ld, ny, nx, my, mx, row_first, row_ptr, ay, wy, col_first, col_ptr, ax, wx, periodic, x0, a, out,
+                          ldo, wsum, n, n_range, stream);
+}
+
+}  // extern "C"

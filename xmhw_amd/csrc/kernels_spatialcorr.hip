@@ -30,10 +30,31 @@
 //                     share a CU either way; the barrier joins eight (or four) waves that have just done the same work.
 //   steps of class -1 are not read: the label is uniform over the workgroup, so every wave skips the same barriers.
 //   the counter       the lanes of offset group 0 count the out-of-range samples of their OWN point, each once.
+#include "../../include/xmhw_amd.h"
+#include "entry_common.h"
 #include "stage_reduce.h"
 #include "halo_tile.h"
 
 namespace xmhw {
+
+// What the stage computes (halo_tile.h holds the tile): per grid point of the UNCOMPACTED ny x nx grid, class of the
+// step and offset e = (dj, di) of the table djdi[D][2], the sums over the pairs (q(t, p), q(t, p + e)) of one step whose two
+// anomalies are valid -- n int32, sx, sy, sxx, syy, sxy int64, [K][D][ldo], ADDED; the definition is in
+// include/xmhw_amd.h, "spatial_correlation()".  ts is row t0 of the series, the block t0 .. t0 + nt - 1; row_of_t and
+// class_of_t are DEVICE arrays over all T steps here; the offsets come twice, padded with (0, 0) to whole groups
+// (spatial_corr_group): djdi_dev for the kernel, djdi_host for the size of its LDS tile.  *n_range counts the samples of a
+// class >= 0 that are not NaN and out of range, each once.  tile_rows: kSpatialCorrRows or kSpatialCorrShortRows grid rows per
+// workgroup; block_steps: the steps a workgroup takes per block, 0 = automatic; same results for every value of either.
+constexpr int kSpatialCorrMaxOffsets = 64;
+constexpr int kSpatialCorrReach = 32;                // |dj|, |di| at most
+constexpr int kSpatialCorrMaxClasses = 64;
+constexpr int kSpatialCorrMaxSteps = 1 << 17;        // T below it: 2^17 * 2^46 = 2^63
+constexpr int kSpatialCorrMaxAxis = 32767;
+constexpr int kSpatialCorrBits = 16;
+constexpr int kSpatialCorrRangeBits = 7;
+constexpr int kSpatialCorrMaxShift = 24;
+constexpr int kSpatialCorrRows = 8;                  // the tile: 8 rows x 64 longitudes, 512 lanes
+constexpr int kSpatialCorrShortRows = 4;             // ... or 4 x 64, 256 lanes (measurements: the slower of the two)
 
 static_assert(kSpatialCorrBits == kFixedBits && kSpatialCorrRangeBits == kFixedRangeBits, "one scale for every stage");
 static_assert(kSpatialCorrReach == kHaloReach, "the halo box clamps at the public reach");
@@ -254,8 +275,6 @@ hipError_t sc_launch(ScIn<T> in, const int32_t* djdi_host, int32_t groups, int64
     return hipGetLastError();
 }
 
-}  // namespace
-
 hipError_t launch_spatial_corr_init(int32_t K, int32_t D, int64_t N, int32_t* n, int64_t* sx, int64_t* sy, int64_t* sxx,
                                     int64_t* syy, int64_t* sxy, int64_t ldo, int64_t* n_range, hipStream_t stream) {
     hipError_t e = hipMemsetAsync(n_range, 0, sizeof(int64_t), stream);
@@ -290,14 +309,122 @@ hipError_t launch_spatial_corr_accumulate(const T* ts, int64_t ld, int64_t t0, i
                  : sc_launch<T, kSpatialCorrRows, kSpatialCorrWideGroup>(in, djdi_host, groups, block_steps, out, stream);
 }
 
-#define XMHW_SC_INSTANCE(T)                                                                                                    \
-    template hipError_t launch_spatial_corr_accumulate<T>(const T*, int64_t, int64_t, int64_t, int32_t, int32_t, bool,          \
-                                                          const double*, int64_t, int64_t, const int32_t*, int32_t,             \
-                                                          const int32_t*, int32_t, const int32_t*, const int32_t*, int32_t,     \
-                                                          int32_t, int64_t, int32_t*, int64_t*, int64_t*, int64_t*, int64_t*,   \
-                                                          int64_t*, int64_t, int64_t*, hipStream_t)
-XMHW_SC_INSTANCE(float);
-XMHW_SC_INSTANCE(double);
-#undef XMHW_SC_INSTANCE
+}  // namespace
 
 }  // namespace xmhw
+
+// ---- the C entries of spatial_correlation() (include/xmhw_amd.h) ------------------------------------------------------
+namespace {
+
+using namespace xmhw::entry;
+
+static std::atomic<int> g_spatial_corr_block{0};   // steps a workgroup takes per block, 0 = automatic (xmhw_set_spatial_corr_block)
+static std::atomic<int> g_spatial_corr_tile{0};    // grid rows of a tile, 0 = the default (xmhw_set_spatial_corr_tile)
+
+static_assert(XMHW_SPATIAL_CORR_MAX_OFFSETS == xmhw::kSpatialCorrMaxOffsets && XMHW_SPATIAL_CORR_REACH == xmhw::kSpatialCorrReach &&
+                  XMHW_SPATIAL_CORR_MAX_CLASSES == xmhw::kSpatialCorrMaxClasses &&
+                  XMHW_SPATIAL_CORR_MAX_STEPS == xmhw::kSpatialCorrMaxSteps &&
+                  XMHW_SPATIAL_CORR_MAX_AXIS == xmhw::kSpatialCorrMaxAxis && XMHW_SPATIAL_CORR_BITS == xmhw::kSpatialCorrBits &&
+                  XMHW_SPATIAL_CORR_RANGE_BITS == xmhw::kSpatialCorrRangeBits &&
+                  XMHW_SPATIAL_CORR_MAX_SHIFT == xmhw::kSpatialCorrMaxShift,
+              "the public limits of spatial_correlation() are the kernel's");
+
+static int spatial_corr_check_shape(int32_t K, int32_t D, int32_t shift, int64_t Tn, int32_t ny, int32_t nx) {
+    if (K < 1 || K > xmhw::kSpatialCorrMaxClasses)
+        return fail(XMHW_ERR_UNSUPPORTED,
+                    "spatial_corr: K must be in [1, " + std::to_string(xmhw::kSpatialCorrMaxClasses) + "]");
+    if (D < 1 || D > xmhw::kSpatialCorrMaxOffsets)
+        return fail(XMHW_ERR_UNSUPPORTED,
+                    "spatial_corr: D must be in [1, " + std::to_string(xmhw::kSpatialCorrMaxOffsets) + "]");
+    if (shift < 0 || shift > xmhw::kSpatialCorrMaxShift)
+        return fail(XMHW_ERR_UNSUPPORTED,
+                    "spatial_corr: shift must be in [0, " + std::to_string(xmhw::kSpatialCorrMaxShift) + "]");
+    if (Tn >= xmhw::kSpatialCorrMaxSteps) return fail(XMHW_ERR_UNSUPPORTED, "spatial_corr: 2^17 steps and more");
+    if (ny > xmhw::kSpatialCorrMaxAxis || nx > xmhw::kSpatialCorrMaxAxis)
+        return fail(XMHW_ERR_UNSUPPORTED, "spatial_corr: a grid axis of 2^15 points and more");
+    return XMHW_OK;
+}
+
+template <typename T>
+int spatial_corr_accumulate(const T* ts, int64_t ld, int64_t t0, int64_t nt, int64_t Tn, int32_t ny, int32_t nx,
+                            int32_t periodic, const double* base, int64_t ldb, int64_t Dr, const int32_t* row_of_t,
+                            int32_t shift, const int32_t* class_of_t, int32_t K, const int32_t* offsets, int32_t D, int32_t* n,
+                            int64_t* sx, int64_t* sy, int64_t* sxx, int64_t* syy, int64_t* sxy, int64_t ldo, int64_t* n_range,
+                            void* stream) {
+    if (spatial_corr_check_shape(K, D, shift, Tn, ny, nx) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (offsets)
+        for (int32_t e = 0; e < 2 * D; ++e)
+            if (offsets[e] < -xmhw::kSpatialCorrReach || offsets[e] > xmhw::kSpatialCorrReach)
+                return fail(XMHW_ERR_UNSUPPORTED,
+                            "spatial_corr: offsets reach at most " + std::to_string(xmhw::kSpatialCorrReach) + " points");
+    if (ny < 0 || nx < 0) return fail(XMHW_ERR_INVALID, "bad ny/nx");
+    const int64_t N = static_cast<int64_t>(ny) * nx;
+    if (Tn < 0 || t0 < 0 || nt < 0 || nt > Tn - t0) return fail(XMHW_ERR_INVALID, "bad T/t0/nt");
+    if (ld < N || ldb < N || ldo < N || Dr < 1) return fail(XMHW_ERR_INVALID, "bad ld/ldb/ldo/Dr");
+    if (!offsets || (Tn > 0 && (!class_of_t || !row_of_t))) return fail(XMHW_ERR_INVALID, "NULL host table");
+    if (periodic)
+        for (int32_t e = 0; e < D; ++e)
+            if (nx > 0 && std::abs(offsets[2 * e + 1]) >= nx)
+                return fail(XMHW_ERR_INVALID, "spatial_corr: |di| must be below nx on a periodic grid");
+    if (int rc = check_labels(class_of_t, Tn, -1, K, kClassesOutside)) return rc;
+    if (int rc = check_labels(row_of_t, Tn, 0, Dr, kRowsOutside)) return rc;
+    if (nt == 0 || N == 0) return XMHW_OK;
+    if (!ts || !base || !n || !sx || !sy || !sxx || !syy || !sxy || !n_range) return fail(XMHW_ERR_INVALID, "NULL buffer");
+    RowsRef rows;
+    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
+    RowsRef classes;                                   // the same content-keyed cache: one more int32[T] table
+    if (int rc = upload_table(class_of_t, Tn, "class table upload", &classes)) return rc;
+    // ... and the offsets, padded with (0, 0) to whole groups: int32[groups * G][2]
+    const int64_t padded_n = xmhw::spatial_corr_groups(D) * xmhw::spatial_corr_group(D);
+    std::vector<int32_t> padded(static_cast<size_t>(2 * padded_n), 0);
+    std::copy(offsets, offsets + 2 * D, padded.begin());
+    RowsRef table;
+    if (int rc = upload_table(padded.data(), 2 * padded_n, "offset table upload", &table)) return rc;
+    const int32_t tile = g_spatial_corr_tile.load();
+    return status_of(xmhw::launch_spatial_corr_accumulate<T>(ts, ld, t0, nt, ny, nx, periodic != 0, base, ldb, Dr, rows->d_rows,
+                                                             shift, classes->d_rows, K, table->d_rows, padded.data(), D,
+                                                             tile ? tile : xmhw::kSpatialCorrRows, g_spatial_corr_block.load(),
+                                                             n, sx, sy, sxx, syy, sxy, ldo, n_range,
+                                                             static_cast<hipStream_t>(stream)),
+                     "spatial_corr_accumulate launch");
+}
+
+}  // namespace
+
+extern "C" {
+
+int xmhw_set_spatial_corr_block(int32_t steps) { return set_knob(g_spatial_corr_block, steps, "steps must be >= 0"); }
+int xmhw_set_spatial_corr_tile(int32_t rows) {
+    if (rows != 0 && rows != xmhw::kSpatialCorrRows && rows != xmhw::kSpatialCorrShortRows)
+        return fail(XMHW_ERR_INVALID, "rows must be 0, 4 or 8");
+    g_spatial_corr_tile = rows;
+    return XMHW_OK;
+}
+int xmhw_spatial_corr_init(int32_t K, int32_t D, int32_t ny, int32_t nx, int32_t* n, int64_t* sx, int64_t* sy, int64_t* sxx,
+                           int64_t* syy, int64_t* sxy, int64_t ldo, int64_t* n_range, void* stream) {
+    if (spatial_corr_check_shape(K, D, 0, 1, ny, nx) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (ny < 0 || nx < 0 || ldo < static_cast<int64_t>(ny) * nx) return fail(XMHW_ERR_INVALID, "bad ny/nx/ldo");
+    if (!n_range || (ny > 0 && nx > 0 && (!n || !sx || !sy || !sxx || !syy || !sxy)))
+        return fail(XMHW_ERR_INVALID, "NULL output buffer");
+    return status_of(xmhw::launch_spatial_corr_init(K, D, static_cast<int64_t>(ny) * nx, n, sx, sy, sxx, syy, sxy, ldo, n_range,
+                                                    static_cast<hipStream_t>(stream)),
+                     "spatial_corr_init");
+}
+int xmhw_spatial_corr_accumulate_f32(const float* ts, int64_t ld, int64_t t0, int64_t nt, int64_t T, int32_t ny, int32_t nx,
+                                     int32_t periodic, const double* base, int64_t ldb, int64_t Dr, const int32_t* row_of_t,
+                                     int32_t shift, const int32_t* class_of_t, int32_t K, const int32_t* offsets, int32_t D,
+                                     int32_t* n, int64_t* sx, int64_t* sy, int64_t* sxx, int64_t* syy, int64_t* sxy,
+                                     int64_t ldo, int64_t* n_range, void* stream) {
+    return spatial_corr_accumulate<float>(ts, ld, t0, nt, T, ny, nx, periodic, base, ldb, Dr, row_of_t, shift, class_of_t, K,
+                                          offsets, D, n, sx, sy, sxx, syy, sxy, ldo, n_range, stream);
+}
+int xmhw_spatial_corr_accumulate_f64(const double* ts, int64_t ld, int64_t t0, int64_t nt, int64_t T, int32_t ny, int32_t nx,
+                                     int32_t periodic, const double* base, int64_t ldb, int64_t Dr, const int32_t* row_of_t,
+                                     int32_t shift, const int32_t* class_of_t, int32_t K, const int32_t* offsets, int32_t D,
+                                     int32_t* n, int64_t* sx, int64_t* sy, int64_t* sxx, int64_t* syy, int64_t* sxy,
+                                     int64_t ldo, int64_t* n_range, void* stream) {
+    return spatial_corr_accumulate<double>(ts, ld, t0, nt, T, ny, nx, periodic, base, ldb, Dr, row_of_t, shift, class_of_t, K,
+                                           offsets, D, n, sx, sy, sxx, syy, sxy, ldo, n_range, stream);
+}
+
+}  // extern "C"

@@ -46,6 +46,8 @@
 //                     most: measured faster than one block over the whole series (heat_stress_auto_block).
 //   snapshots         plain stores by the block that owns the step.
 //   heat_stress_finish     key -> peak_q = key >> 32, peak_t = ~key (low word); key 0 -> 0 and -1.
+#include "../../include/xmhw_amd.h"
+#include "entry_common.h"
 #include "stage_reduce.h"
 
 namespace xmhw {
@@ -269,8 +271,6 @@ __global__ __launch_bounds__(kHsThreads) void heat_stress_finish(int32_t K, int6
     }
 }
 
-}  // namespace
-
 hipError_t launch_class_sums_init(int32_t K, int64_t C, int32_t* n_valid, int64_t* sum_q, int64_t ldo, int64_t* n_range,
                                   hipStream_t stream) {
     hipError_t e = hipMemsetAsync(n_range, 0, sizeof(int64_t), stream);
@@ -330,19 +330,138 @@ hipError_t launch_heat_stress_finish(int32_t K, int64_t C, const int64_t* peak_k
     return hipGetLastError();
 }
 
-template hipError_t launch_class_sums_accumulate<float>(const float*, int64_t, int64_t, int64_t, double, const int32_t*,
-                                                        int32_t, int64_t, int32_t*, int64_t*, int64_t, int64_t*, hipStream_t);
-template hipError_t launch_class_sums_accumulate<double>(const double*, int64_t, int64_t, int64_t, double, const int32_t*,
-                                                         int32_t, int64_t, int32_t*, int64_t*, int64_t, int64_t*, hipStream_t);
-template hipError_t launch_heat_stress_accumulate<float>(const float*, int64_t, int64_t, int64_t, const double*, int64_t,
-                                                         int64_t, const int32_t*, int32_t, int32_t, double, const int32_t*,
-                                                         int32_t, const int64_t*, int32_t, const int32_t*, int32_t, int64_t,
-                                                         int32_t*, int64_t*, int64_t*, int32_t*, int64_t, int64_t*,
-                                                         hipStream_t);
-template hipError_t launch_heat_stress_accumulate<double>(const double*, int64_t, int64_t, int64_t, const double*, int64_t,
-                                                          int64_t, const int32_t*, int32_t, int32_t, double, const int32_t*,
-                                                          int32_t, const int64_t*, int32_t, const int32_t*, int32_t, int64_t,
-                                                          int32_t*, int64_t*, int64_t*, int32_t*, int64_t, int64_t*,
-                                                          hipStream_t);
+}  // namespace
 
 }  // namespace xmhw
+
+// ---- the C entries of heat_stress() and its class sums (include/xmhw_amd.h) -------------------------------------------
+namespace {
+
+using namespace xmhw::entry;
+
+static std::atomic<int> g_heat_stress_block{0};   // steps a workgroup takes per block, 0 = automatic (xmhw_set_heat_stress_block)
+
+static int heat_stress_check_shape(const char* who, int32_t K, int64_t Tn, int64_t C) {
+    if (K < 1 || K > xmhw::kHeatStressMaxClasses)
+        return fail(XMHW_ERR_UNSUPPORTED,
+                    std::string(who) + ": K must be in [1, " + std::to_string(xmhw::kHeatStressMaxClasses) + "]");
+    if (Tn > 0x7FFFFFFFll || C > 0x7FFFFFFFll)
+        return fail(XMHW_ERR_UNSUPPORTED, std::string(who) + ": 2^31 steps or cells and more");
+    return XMHW_OK;
+}
+
+template <typename T>
+int class_sums_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, double x0, const int32_t* class_of_t, int32_t K,
+                          int32_t* n_valid, int64_t* sum_q, int64_t ldo, int64_t* n_range, void* stream) {
+    if (heat_stress_check_shape("class_sums", K, Tn, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (Tn <= 0 || C < 0 || ld < C || ldo < C) return fail(XMHW_ERR_INVALID, "bad T/C/ld/ldo");
+    if (!std::isfinite(x0)) return fail(XMHW_ERR_INVALID, "x0 must be finite");
+    if (!class_of_t) return fail(XMHW_ERR_INVALID, "NULL class_of_t");
+    if (int rc = check_labels(class_of_t, Tn, -1, K, kClassesOutside)) return rc;
+    if (C == 0) return XMHW_OK;
+    if (!ts || !n_valid || !sum_q || !n_range) return fail(XMHW_ERR_INVALID, "NULL buffer");
+    RowsRef classes;
+    if (int rc = upload_table(class_of_t, Tn, "class table upload", &classes)) return rc;
+    return status_of(xmhw::launch_class_sums_accumulate<T>(ts, Tn, C, ld, x0, classes->d_rows, K, g_heat_stress_block.load(),
+                                                           n_valid, sum_q, ldo, n_range, static_cast<hipStream_t>(stream)),
+                     "class_sums_accumulate launch");
+}
+
+template <typename T>
+int heat_stress_accumulate(const T* ts, int64_t Tn, int64_t C, int64_t ld, const double* base, int64_t ldb, int64_t D,
+                           const int32_t* row_of_t, int32_t negate, int32_t W, double h0, const int32_t* class_of_t,
+                           int32_t K, const int64_t* level_q, int32_t L, const int32_t* at, int32_t J, int32_t* counts,
+                           int64_t* hsum_q, int64_t* peak_key, int32_t* snap_q, int64_t ldo, int64_t* n_range,
+                           void* stream) {
+    if (heat_stress_check_shape("heat_stress", K, Tn, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (W < 1 || W > xmhw::kHeatStressMaxWindow)
+        return fail(XMHW_ERR_UNSUPPORTED, "heat_stress: W must be in [1, " + std::to_string(xmhw::kHeatStressMaxWindow) + "]");
+    if (L > xmhw::kHeatStressMaxLevels)
+        return fail(XMHW_ERR_UNSUPPORTED, "heat_stress: at most " + std::to_string(xmhw::kHeatStressMaxLevels) + " levels");
+    if (J > xmhw::kHeatStressMaxSnapshots)
+        return fail(XMHW_ERR_UNSUPPORTED,
+                    "heat_stress: at most " + std::to_string(xmhw::kHeatStressMaxSnapshots) + " snapshot steps");
+    if (Tn <= 0 || C < 0 || ld < C || ldb < C || ldo < C || D < 1 || L < 0 || J < 0)
+        return fail(XMHW_ERR_INVALID, "bad T/C/ld/ldb/ldo/D/L/J");
+    if (!(h0 >= 1.0 / 65536.0 && h0 < 128.0)) return fail(XMHW_ERR_INVALID, "h0 outside [2^-16, 2^7)");
+    if (!class_of_t || !row_of_t || (L > 0 && !level_q) || (J > 0 && !at)) return fail(XMHW_ERR_INVALID, "NULL host table");
+    if (int rc = check_labels(class_of_t, Tn, -1, K, kClassesOutside)) return rc;
+    if (int rc = check_labels(row_of_t, Tn, 0, D, kRowsOutside)) return rc;
+    for (int32_t l = 1; l < L; ++l)
+        if (level_q[l] <= level_q[l - 1]) return fail(XMHW_ERR_INVALID, "level_q not strictly ascending");
+    for (int32_t j = 0; j < J; ++j)
+        if (at[j] < 0 || at[j] >= Tn || (j > 0 && at[j] <= at[j - 1]))
+            return fail(XMHW_ERR_INVALID, "snapshot steps not strictly ascending in [0, T)");
+    if (C == 0) return XMHW_OK;
+    if (!ts || !base || !counts || !hsum_q || !peak_key || !n_range || (J > 0 && !snap_q))
+        return fail(XMHW_ERR_INVALID, "NULL buffer");
+    RowsRef rows;
+    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
+    RowsRef classes;                                   // the same content-keyed cache: one more int32[T] table
+    if (int rc = upload_table(class_of_t, Tn, "class table upload", &classes)) return rc;
+    RowsRef steps;                                     // ... and the snapshot steps, int32[J]
+    if (J > 0)
+        if (int rc = upload_table(at, J, "snapshot table upload", &steps)) return rc;
+    return status_of(xmhw::launch_heat_stress_accumulate<T>(ts, Tn, C, ld, base, ldb, D, rows->d_rows, negate, W, h0,
+                                                            classes->d_rows, K, level_q, L, J > 0 ? steps->d_rows : nullptr, J,
+                                                            g_heat_stress_block.load(), counts, hsum_q, peak_key, snap_q, ldo,
+                                                            n_range, static_cast<hipStream_t>(stream)),
+                     "heat_stress_accumulate launch");
+}
+
+}  // namespace
+
+extern "C" {
+
+int xmhw_set_heat_stress_block(int32_t steps) { return set_knob(g_heat_stress_block, steps, "steps must be >= 0"); }
+int xmhw_class_sums_init(int32_t K, int64_t C, int32_t* n_valid, int64_t* sum_q, int64_t ldo, int64_t* n_range, void* stream) {
+    if (heat_stress_check_shape("class_sums", K, 1, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
+    if (!n_range || (C > 0 && (!n_valid || !sum_q))) return fail(XMHW_ERR_INVALID, "NULL output buffer");
+    return status_of(xmhw::launch_class_sums_init(K, C, n_valid, sum_q, ldo, n_range, static_cast<hipStream_t>(stream)),
+                     "class_sums_init");
+}
+int xmhw_class_sums_accumulate_f32(const float* ts, int64_t T, int64_t C, int64_t ld, double x0, const int32_t* class_of_t,
+                                   int32_t K, int32_t* n_valid, int64_t* sum_q, int64_t ldo, int64_t* n_range, void* stream) {
+    return class_sums_accumulate<float>(ts, T, C, ld, x0, class_of_t, K, n_valid, sum_q, ldo, n_range, stream);
+}
+int xmhw_class_sums_accumulate_f64(const double* ts, int64_t T, int64_t C, int64_t ld, double x0, const int32_t* class_of_t,
+                                   int32_t K, int32_t* n_valid, int64_t* sum_q, int64_t ldo, int64_t* n_range, void* stream) {
+    return class_sums_accumulate<double>(ts, T, C, ld, x0, class_of_t, K, n_valid, sum_q, ldo, n_range, stream);
+}
+int xmhw_heat_stress_init(int32_t K, int64_t C, int32_t* counts, int64_t* hsum_q, int64_t* peak_key, int64_t ldo,
+                          int64_t* n_range, void* stream) {
+    if (heat_stress_check_shape("heat_stress", K, 1, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
+    if (!n_range || (C > 0 && (!counts || !hsum_q || !peak_key))) return fail(XMHW_ERR_INVALID, "NULL output buffer");
+    return status_of(xmhw::launch_heat_stress_init(K, C, counts, hsum_q, peak_key, ldo, n_range,
+                                                   static_cast<hipStream_t>(stream)),
+                     "heat_stress_init");
+}
+int xmhw_heat_stress_accumulate_f32(const float* ts, int64_t T, int64_t C, int64_t ld, const double* base, int64_t ldb,
+                                    int64_t D, const int32_t* row_of_t, int32_t negate, int32_t W, double h0,
+                                    const int32_t* class_of_t, int32_t K, const int64_t* level_q, int32_t L, const int32_t* at,
+                                    int32_t J, int32_t* counts, int64_t* hsum_q, int64_t* peak_key, int32_t* snap_q,
+                                    int64_t ldo, int64_t* n_range, void* stream) {
+    return heat_stress_accumulate<float>(ts, T, C, ld, base, ldb, D, row_of_t, negate, W, h0, class_of_t, K, level_q, L, at, J,
+                                         counts, hsum_q, peak_key, snap_q, ldo, n_range, stream);
+}
+int xmhw_heat_stress_accumulate_f64(const double* ts, int64_t T, int64_t C, int64_t ld, const double* base, int64_t ldb,
+                                    int64_t D, const int32_t* row_of_t, int32_t negate, int32_t W, double h0,
+                                    const int32_t* class_of_t, int32_t K, const int64_t* level_q, int32_t L, const int32_t* at,
+                                    int32_t J, int32_t* counts, int64_t* hsum_q, int64_t* peak_key, int32_t* snap_q,
+                                    int64_t ldo, int64_t* n_range, void* stream) {
+    return heat_stress_accumulate<double>(ts, T, C, ld, base, ldb, D, row_of_t, negate, W, h0, class_of_t, K, level_q, L, at, J,
+                                          counts, hsum_q, peak_key, snap_q, ldo, n_range, stream);
+}
+int xmhw_heat_stress_finish(int32_t K, int64_t C, const int64_t* peak_key, int32_t* peak_q, int32_t* peak_t, int64_t ldo,
+                            void* stream) {
+    if (heat_stress_check_shape("heat_stress", K, 1, C) != XMHW_OK) return XMHW_ERR_UNSUPPORTED;
+    if (C < 0 || ldo < C) return fail(XMHW_ERR_INVALID, "bad C/ldo");
+    if (C == 0) return XMHW_OK;
+    if (!peak_key || !peak_q || !peak_t) return fail(XMHW_ERR_INVALID, "NULL buffer");
+    return status_of(xmhw::launch_heat_stress_finish(K, C, peak_key, peak_q, peak_t, ldo, static_cast<hipStream_t>(stream)),
+                     "heat_stress_finish launch");
+}
+
+}  // extern "C"

@@ -21,6 +21,8 @@
 //                     row whose days leave its object's entries is left out and counted (*n_bad): nothing outside
 //                     entries 0..L-1 is ever written.
 //   the finish                  key -> float64 (NaN where no voxel had a value): launch_keys_to_f64 (kernels.h).
+#include "../../include/xmhw_amd.h"
+#include "entry_common.h"
 #include "stage_reduce.h"
 
 namespace xmhw {
@@ -155,8 +157,6 @@ __global__ __launch_bounds__(kTiThreads) void track_intensity_accumulate(
     }
 }
 
-}  // namespace
-
 hipError_t launch_track_intensity_init(int64_t L, int32_t* n_valid, int64_t* wsum_i, int64_t* isum_q, double* intensity_max,
                                        int32_t* cat_cells, int64_t ldcat, int64_t* n_range, int64_t* n_bad,
                                        hipStream_t stream) {
@@ -200,15 +200,93 @@ hipError_t launch_track_intensity_finish(int64_t L, double* intensity_max, hipSt
     return launch_keys_to_f64(intensity_max, 1, L, L, stream);
 }
 
-#define XMHW_TI_INSTANCE(T)                                                                                             \
-    template hipError_t launch_track_intensity_accumulate<T>(                                                           \
-        const T*, int64_t, int64_t, int64_t, const double*, const double*, int64_t, const int32_t*, int32_t,            \
-        const int32_t*, const int32_t*, const int32_t*, int64_t, const int64_t*, const int64_t*, const int32_t*,        \
-        const int64_t*,                                                                                                 \
-        int64_t, int64_t, int32_t*, int64_t*, int64_t*, double*, int32_t*, int64_t, int64_t*, int64_t*, int32_t,        \
-        hipStream_t);
-XMHW_TI_INSTANCE(float)
-XMHW_TI_INSTANCE(double)
-#undef XMHW_TI_INSTANCE
+}  // namespace
 
 }  // namespace xmhw
+
+// ---- the C entries of mhw_track_intensity() (include/xmhw_amd.h) ------------------------------------------------------
+namespace {
+
+using namespace xmhw::entry;
+
+static std::atomic<int> g_track_intensity_combine{1};   // runs of equal entries summed in the wave (xmhw_set_track_intensity_combine)
+
+template <typename T>
+int track_intensity_accumulate(const T* ts, int64_t Tn, int64_t n, int64_t ld, const double* seas, const double* thresh,
+                               int64_t ldc, int64_t D, const int32_t* row_of_t, int32_t negate, const int32_t* start,
+                               const int32_t* end, const int32_t* slot, int64_t n_rows, const int64_t* row_offsets,
+                               const int64_t* wi, const int32_t* time_start, const int64_t* offsets, int64_t n_slots,
+                               int64_t L, int32_t* n_valid, int64_t* wsum_i, int64_t* isum_q, double* intensity_max,
+                               int32_t* cat_cells, int64_t ldcat, int64_t* n_range, int64_t* n_bad, void* stream) {
+    if (Tn <= 0 || n < 0 || ld < n || ldc < n || D < 1) return fail(XMHW_ERR_INVALID, "bad T/n/ld/ldc/D");
+    if (n_rows < 0 || n_slots < 0 || L < 0 || ldcat < L) return fail(XMHW_ERR_INVALID, "bad n_rows/n_slots/L/ldcat");
+    if (Tn > 0x7FFFFFFFll || n > 0x7FFFFFFFll || n_rows > 0x7FFFFFFFll || n_slots > 0x7FFFFFFFll || L > 0x7FFFFFFFll)
+        return fail(XMHW_ERR_UNSUPPORTED, "track_intensity: 2^31 steps, cells, rows, slots or series entries and more");
+    if (n == 0 || n_rows == 0 || n_slots == 0 || L == 0) return XMHW_OK;
+    if (!ts || !seas || !thresh || !row_of_t || !start || !end || !slot || !row_offsets || !wi || !time_start || !offsets)
+        return fail(XMHW_ERR_INVALID, "NULL buffer");
+    if (!n_valid || !wsum_i || !isum_q || !intensity_max || !cat_cells || !n_range || !n_bad)
+        return fail(XMHW_ERR_INVALID, "NULL output buffer");
+    if (int rc = check_labels(row_of_t, Tn, 0, D, kRowsOutside)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    RowsRef rows;
+    if (int rc = upload_table(row_of_t, Tn, "row table upload", &rows)) return rc;
+    return status_of(xmhw::launch_track_intensity_accumulate<T>(ts, Tn, n, ld, seas, thresh, ldc, rows->d_rows, negate,
+                                                                start, end, slot, n_rows, row_offsets, wi, time_start,
+                                                                offsets, n_slots, L, n_valid, wsum_i, isum_q, intensity_max,
+                                                                cat_cells, ldcat, n_range, n_bad,
+                                                                g_track_intensity_combine.load(), st),
+                     "track_intensity_accumulate launch");
+}
+
+}  // namespace
+
+extern "C" {
+
+int xmhw_set_track_intensity_combine(int32_t on) {
+    if (on != 0 && on != 1) return fail(XMHW_ERR_INVALID, "on must be 0 or 1");
+    g_track_intensity_combine = on;
+    return XMHW_OK;
+}
+int xmhw_track_intensity_init(int64_t L, int32_t* n_valid, int64_t* wsum_i, int64_t* isum_q, double* intensity_max,
+                              int32_t* cat_cells, int64_t ldcat, int64_t* n_range, int64_t* n_bad, void* stream) {
+    if (L < 0 || ldcat < L) return fail(XMHW_ERR_INVALID, "bad L/ldcat");
+    if (L > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "track_intensity: 2^31 series entries and more");
+    if (!n_range || !n_bad || (L > 0 && (!n_valid || !wsum_i || !isum_q || !intensity_max || !cat_cells)))
+        return fail(XMHW_ERR_INVALID, "NULL output buffer");
+    return status_of(xmhw::launch_track_intensity_init(L, n_valid, wsum_i, isum_q, intensity_max, cat_cells, ldcat, n_range,
+                                                       n_bad, static_cast<hipStream_t>(stream)),
+                     "track_intensity_init");
+}
+int xmhw_track_intensity_accumulate_f32(const float* ts, int64_t T, int64_t n, int64_t ld, const double* seas,
+                                        const double* thresh, int64_t ldc, int64_t D, const int32_t* row_of_t, int32_t negate,
+                                        const int32_t* start, const int32_t* end, const int32_t* slot, int64_t n_rows,
+                                        const int64_t* row_offsets, const int64_t* wi, const int32_t* time_start,
+                                        const int64_t* offsets, int64_t n_slots, int64_t L, int32_t* n_valid, int64_t* wsum_i,
+                                        int64_t* isum_q, double* intensity_max, int32_t* cat_cells, int64_t ldcat,
+                                        int64_t* n_range, int64_t* n_bad, void* stream) {
+    return track_intensity_accumulate<float>(ts, T, n, ld, seas, thresh, ldc, D, row_of_t, negate, start, end, slot, n_rows,
+                                             row_offsets, wi, time_start, offsets, n_slots, L, n_valid, wsum_i, isum_q,
+                                             intensity_max, cat_cells, ldcat, n_range, n_bad, stream);
+}
+int xmhw_track_intensity_accumulate_f64(const double* ts, int64_t T, int64_t n, int64_t ld, const double* seas,
+                                        const double* thresh, int64_t ldc, int64_t D, const int32_t* row_of_t, int32_t negate,
+                                        const int32_t* start, const int32_t* end, const int32_t* slot, int64_t n_rows,
+                                        const int64_t* row_offsets, const int64_t* wi, const int32_t* time_start,
+                                        const int64_t* offsets, int64_t n_slots, int64_t L, int32_t* n_valid, int64_t* wsum_i,
+                                        int64_t* isum_q, double* intensity_max, int32_t* cat_cells, int64_t ldcat,
+                                        int64_t* n_range, int64_t* n_bad, void* stream) {
+    return track_intensity_accumulate<double>(ts, T, n, ld, seas, thresh, ldc, D, row_of_t, negate, start, end, slot, n_rows,
+                                              row_offsets, wi, time_start, offsets, n_slots, L, n_valid, wsum_i, isum_q,
+                                              intensity_max, cat_cells, ldcat, n_range, n_bad, stream);
+}
+int xmhw_track_intensity_finish(int64_t L, double* intensity_max, void* stream) {
+    if (L < 0) return fail(XMHW_ERR_INVALID, "bad L");
+    if (L > 0x7FFFFFFFll) return fail(XMHW_ERR_UNSUPPORTED, "track_intensity: 2^31 series entries and more");
+    if (L == 0) return XMHW_OK;
+    if (!intensity_max) return fail(XMHW_ERR_INVALID, "NULL output buffer");
+    return status_of(xmhw::launch_track_intensity_finish(L, intensity_max, static_cast<hipStream_t>(stream)),
+                     "track_intensity_finish launch");
+}
+
+}  // extern "C"
